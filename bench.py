@@ -20,7 +20,10 @@ in HBM; R > 1 only lengthens the timed region (one pass at 10 000 packets is 1.5
          processes (`python -m torch.distributed.run ... bench.py ...` as a CHILD process, decided before torch or the
          GPU is touched) and relays rank 0's line; under `torch.distributed.run` it is a rank.
 `--packets P` overrides the per-rank batch (e.g. `--gpus 1 --packets 125000` runs the configs[3] shard shape on one GPU).
-Rank 0 prints ONE JSON line.
+`--dump-outputs DIR` writes what the last timed pass computed (the re-assembled stream at N > 1) as DIR/<name>.npy: every
+packet size and offset (float64) and the bytes of a fixed, seeded sample of 256 packets (float32).  The inputs are fixed
+by the arguments, so two builds run with the same arguments can be compared array for array.
+Rank 0 prints ONE JSON line; `ms_per_step` is the wall time of one timed step.
 """
 import argparse
 import json
@@ -58,7 +61,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-reassemble", action="store_true", help="skip the RCCL re-assembly at N > 1")
     ap.add_argument("--force-reassemble", action="store_true",
                     help="rehearsal: run the RCCL re-assembly path even with one rank (needs torch.distributed.run)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed pass computed as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+    return args
 
 
 # ---- self-launch (N > 1 from the plain command) ------------------------------------------------------------------------
@@ -249,6 +259,30 @@ def sampled_oracle_check(alac_amd, fmt, first_frame, B, stream_dev, offsets_dev,
         got = stream_dev[int(offs[p]):int(offs[p + 1])].cpu().numpy()
         ok = ok and int(sizes[p]) == len(want) and np.array_equal(got, want)
     return len(idx), bool(ok)
+
+
+DUMP_SAMPLE_PACKETS = 256  # bytes of at most 256 packets: 256 x 4 x the largest stereo packet (32-bit, ~32 KB) < 64 MB
+DUMP_SEED = 20261015
+
+
+def dump_outputs(np, dirname, stream_dev, sizes_dev, offsets_dev=None):
+    """--dump-outputs: the arrays a caller of the timed path receives, as float64 / float32 .npy files — every packet size and
+    offset, and the bytes of a fixed, seeded sample of packets (the whole stream of a 10 000-packet pass is ~68 MB, 4x that as
+    float32).  offsets_dev None: the offsets are the prefix sum of the sizes (the re-assembled stream).  -> {name: shape}"""
+    sizes = sizes_dev.cpu().numpy().astype(np.int64)
+    offs = (offsets_dev.cpu().numpy().astype(np.int64) if offsets_dev is not None
+            else np.concatenate([[0], np.cumsum(sizes)]))
+    n = len(sizes)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(n, DUMP_SAMPLE_PACKETS), replace=False))
+    sample = [stream_dev[int(offs[p]):int(offs[p + 1])].cpu().numpy() for p in pick]
+    arrays = {"packet_sizes": sizes.astype(np.float64), "packet_offsets": offs.astype(np.float64),
+              "sample_packet_index": pick.astype(np.float64),
+              "sample_packet_bytes": np.concatenate(sample).astype(np.float32)}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20, "dump exceeds 64 MB"
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def shard_checksum(torch, x):
@@ -641,6 +675,14 @@ def rank_main_body(args, json_fd):
     state["timing"] = False
     calls, stage_ms = ctx.profile_end()
     ctx.synchronize()  # raises if an in-launch hand-off of any timed pass was lost (the outputs would be invalid)
+    # before the N > 1 encode-only passes below, which encode into the same buffer sets again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        g = state["gather"]
+        if reassemble and g is not None and g["sizes"] is not None:
+            dumped = dump_outputs(np, args.dump_outputs, g["stream"], g["sizes"])
+        else:
+            dumped = dump_outputs(np, args.dump_outputs, last["out"], last["sizes"], last["offsets"])
 
     tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
     if use_dist:
@@ -762,6 +804,8 @@ def rank_main_body(args, json_fd):
             out["bit_exact_sampled"] = sampled
         if placement is not None:
             out["reassembly_check"] = placement
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if world == 1 and not args.no_decode:
             try:
                 out["decode"] = decode_leg(torch, ctx, fmt, B, last["out"], last["offsets"], d_pcm, reps=max(3, min(args.steps, 10)))
@@ -806,7 +850,8 @@ def main():
         return stub_rank_main(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # decided before torch / alac_amd are imported or any GPU call is made: the ranks are CHILD processes
-        return self_launch(args, sys.argv[1:])
+        # the ranks start in the repository root: hand them DIR as the absolute path parse_args made of it
+        return self_launch(args, sys.argv[1:] + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else []))
     return rank_main(args)
 
 

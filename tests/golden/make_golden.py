@@ -16,9 +16,12 @@ Outputs (data only — inputs and expected outputs, no reference source):
                       pc_block / dyn_comp / BitBufferWrite) and the PCM the decoder driver produces from them over the
                       reference's dyn_decomp / unpc_block: the pin of the decoder's general paths
   caf_headers.json    chunk bytes, BER codes and base packet tables from the reference's own CAFFileALAC.cpp
-  wav50_pcm.xz,       the sample data of the reference's audio/50.wav (stereo, 237 packets) and audio/05.wav (mono, 302
-  wav05_pcm.xz        packets), xz-compressed: the INPUTS of the whole-file known answers, so that the GPU box (which has
-                      no /root/reference) can encode the full-length chains (tests/test_gpu_wholefile.py)
+  wav50_pcm.xz,       the sample data of the reference's audio/50.wav (stereo, 237 packets), audio/05.wav (mono, 302
+  wav05_pcm.xz,       packets) and audio/70.wav (stereo, near silence, 227 packets), xz-compressed: the INPUTS of the
+  wav70_pcm.xz        whole-file known answers, so that a machine without the reference can encode the full-length chains
+                      (tests/test_gpu_wholefile.py) and the CPU suite can check them (tests/test_oracle.py)
+  wav_headers.json    the bytes in front of the sample data of each of those WAV files: with the xz fixture, the whole
+                      file (oracle_lib.reference_wav_bytes, tests/test_container.py)
 """
 import json
 import os
@@ -29,7 +32,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
-from oracle_lib import Oracle, Ref, read_wav  # noqa: E402
+from oracle_lib import REFERENCE_WAVS, Oracle, Ref, read_wav  # noqa: E402
 
 REF_AUDIO = "/root/reference/audio"
 
@@ -169,11 +172,21 @@ def make_forged(o, r):
 
 def make_wav_pcm_fixtures():
     import lzma
-    for name, out in (("50.wav", "wav50_pcm.xz"), ("05.wav", "wav05_pcm.xz")):
-        ch, rate, bits, data = read_wav(os.path.join(REF_AUDIO, name))
+    headers = {}
+    for name, out in REFERENCE_WAVS.items():
+        path = os.path.join(REF_AUDIO, name)
+        ch, rate, bits, data = read_wav(path)
+        with open(path, "rb") as f:
+            raw = f.read()
+        start = len(raw) - data.size
+        assert raw[start:] == data.tobytes(), f"{name}: the sample data must end the file"
+        headers[name] = raw[:start].hex()
         with open(os.path.join(HERE, out), "wb") as f:
             f.write(lzma.compress(data.tobytes(), preset=9 | lzma.PRESET_EXTREME))
         print(out, "written:", os.path.getsize(os.path.join(HERE, out)), "bytes for", data.size, "bytes of PCM")
+    with open(os.path.join(HERE, "wav_headers.json"), "w") as f:
+        json.dump(headers, f, indent=1, sort_keys=True)
+    print("wav_headers.json written")
 
 
 def make_caf_headers():

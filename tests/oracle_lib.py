@@ -11,6 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_SO = os.path.join(ORACLE_DIR, "liboracle.so")
 REF_SO = os.path.join(ORACLE_DIR, "_ref", "libalacref.so")
+GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
+# the reference's WAV files -> the fixture holding their sample data (tests/golden/make_golden.py writes both)
+REFERENCE_WAVS = {"50.wav": "wav50_pcm.xz", "05.wav": "wav05_pcm.xz", "70.wav": "wav70_pcm.xz"}
 
 i16p = C.POINTER(C.c_int16)
 i32p = C.POINTER(C.c_int32)
@@ -301,7 +304,22 @@ def have_ref():
 def read_wav(path):
     """minimal RIFF/WAVE PCM reader -> (channels, rate, bits, data bytes as uint8 array)."""
     with open(path, "rb") as f:
-        b = f.read()
+        return parse_wav(f.read())
+
+
+def reference_wav_bytes(name):
+    """The reference's audio/<name> (a key of REFERENCE_WAVS), whole, from the committed fixtures under tests/golden/:
+    the bytes in front of its sample data (wav_headers.json) followed by the sample data (xz)."""
+    import json
+    import lzma
+    with open(os.path.join(GOLDEN_DIR, "wav_headers.json")) as f:
+        head = bytes.fromhex(json.load(f)[name])
+    with open(os.path.join(GOLDEN_DIR, REFERENCE_WAVS[name]), "rb") as f:
+        return head + lzma.decompress(f.read())
+
+
+def parse_wav(b):
+    """read_wav on the bytes of a file"""
     assert b[:4] == b"RIFF" and b[8:12] == b"WAVE"
     pos = 12
     fmt = None

@@ -57,3 +57,42 @@ def test_launch_command_shape():
     assert cmd[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"] and "--nproc-per-node=8" in cmd
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-4:] == ["--gpus", "8", "--steps", "20"]
     assert os.path.basename(cmd[cmd.index("--master-port") + 2]) == "bench.py"
+
+
+def test_dump_dir_reaches_the_ranks_as_an_absolute_path(tmp_path):
+    """the ranks start in the repository root: a relative --dump-outputs DIR is resolved where the command was given"""
+    code = (f"import sys, json; sys.path.insert(0, {ROOT!r}); sys.argv = ['bench.py', '--gpus', '2', '--dump-outputs', 'out']; "
+            "import bench; seen = {}; "
+            "bench.self_launch = lambda a, argv, run=None: (seen.update(argv=argv), 0)[1]; "
+            "rc = bench.main(); print(json.dumps(dict(rc=rc, **seen)))")
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=tmp_path, env=env, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    argv = json.loads(p.stdout.strip().splitlines()[-1])["argv"]
+    assert argv[-2:] == ["--dump-outputs", str(tmp_path / "out")]
+    assert run({}, "--steps", "0").returncode != 0
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_64_mb(tmp_path):
+    """no GPU: CPU tensors stand in for the encode buffers of a 10 000-packet pass of ~16 KB packets"""
+    import numpy as np
+    import torch
+
+    import bench
+    rng = np.random.default_rng(5)
+    sizes = rng.integers(20, 16400, 10000).astype(np.int32)
+    offs = np.concatenate([[0], np.cumsum(sizes.astype(np.int64))])
+    stream = torch.from_numpy(rng.integers(0, 256, int(offs[-1]), dtype=np.uint8))
+    shapes = bench.dump_outputs(np, str(tmp_path / "a"), stream, torch.from_numpy(sizes), torch.from_numpy(offs))
+    bench.dump_outputs(np, str(tmp_path / "b"), stream, torch.from_numpy(sizes))  # offsets from the sizes (re-assembled stream)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in shapes}
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in shapes) <= 64 << 20
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert all(np.array_equal(x, np.load(tmp_path / "b" / f"{n}.npy")) for n, x in a.items())
+    assert np.array_equal(a["packet_sizes"], sizes) and np.array_equal(a["packet_offsets"], offs)
+    pick = a["sample_packet_index"].astype(np.int64)
+    assert len(pick) == bench.DUMP_SAMPLE_PACKETS and np.all(np.diff(pick) > 0)
+    want = np.concatenate([stream.numpy()[offs[p]:offs[p + 1]] for p in pick])
+    assert np.array_equal(a["sample_packet_bytes"], want)

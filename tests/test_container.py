@@ -12,8 +12,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 import caf_oracle as co  # noqa: E402
 from container_lib import Container, music_like  # noqa: E402
-
-REF_AUDIO = "/root/reference/audio"
+from oracle_lib import reference_wav_bytes  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -158,11 +157,9 @@ def test_big_endian_caf_input_encodes_like_the_wav(cont, oracle):
     assert outs[0] == outs[1]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_AUDIO), reason="reference audio only exists in the build container")
 def test_reference_wav_known_answers(cont, oracle):
     """audio/50.wav -> 237 packets, 1 164 578 payload bytes; the CAF decodes back to the WAV's data chunk."""
-    with open(os.path.join(REF_AUDIO, "50.wav"), "rb") as fh:
-        wav = fh.read()
+    wav = reference_wav_bytes("50.wav")
     fmt = co.get_input_format(wav)
     cookie, encode_packet, decode_packet = oracle_codec(oracle, fmt["bits"], fmt["channels"], int(fmt["rate"]))
     sizes = []
