@@ -298,7 +298,9 @@ class Context:
             assert pcm.is_cuda and pcm.dtype == t.uint8 and pcm.numel() >= num_packets * fmt.packet_bytes
             nseg = num_packets if seg_first is None else seg_first.numel() - 1
             bufs = bufs or self.encode_buffers(fmt, num_packets)
-            wsb = int(self.lib.alac_hip_encode_workspace_bytes(C.byref(fmt), num_packets, nseg))
+            # option "lpc": every packet is its own segment, and the workspace is sized for that
+            wsb = int(self.lib.alac_hip_encode_workspace_bytes(C.byref(fmt), num_packets,
+                                                               num_packets if self.get_option("lpc") else nseg))
             ws = self._workspace(wsb)
             rc = self.lib.alac_hip_encode_segmented(
                 self.h, C.byref(fmt), pcm.data_ptr(),

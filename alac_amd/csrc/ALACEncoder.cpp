@@ -109,6 +109,7 @@ int32_t ALACEncoder::EncodeBatch(const void *pcm, uint64_t totalSamples, uint32_
 {
     if (!mCtx) return kALAC_ParamError;
     (void)alac_hip_set_option(mCtx, "fast_mode", mFastMode ? 1 : 0);  // SetFastMode: EncodeStereoFast, codec/ALACEncoder.cu:998-1001
+    (void)alac_hip_set_option(mCtx, "lpc", mLPCMode ? 1 : 0);
     alac_hip_format fmt = {mFrameSize, (uint32_t)mBitDepth, mNumChannels, mOutputSampleRate};
     const uint64_t np = (totalSamples + mFrameSize - 1) / mFrameSize;
     const uint64_t nseg = segmentPackets ? (np + segmentPackets - 1) / segmentPackets : 1;
@@ -120,7 +121,7 @@ int32_t ALACEncoder::EncodeBatch(const void *pcm, uint64_t totalSamples, uint32_
     mLastStatus = alac_hip_encode_host(mCtx, &fmt, pcm, totalSamples, segmentPackets, state.data(), chain ? 1 : 0, out,
                                        outCapacity, packetBytes, &total);
     if (mLastStatus != ALAC_HIP_noErr) return mLastStatus;
-    if (segmentPackets == 0 && np) {
+    if (segmentPackets == 0 && np && !mLPCMode) {  // LPC packets leave no predictor state behind
         memcpy(mState, state.data(), stateInt16 * 2u);
         mStateValid = true;
     }
@@ -135,6 +136,7 @@ int32_t ALACEncoder::EncodeSegments(const void *pcm, const uint32_t *numSamples,
 {
     if (!mCtx) return kALAC_ParamError;
     (void)alac_hip_set_option(mCtx, "fast_mode", mFastMode ? 1 : 0);
+    (void)alac_hip_set_option(mCtx, "lpc", mLPCMode ? 1 : 0);
     alac_hip_format fmt = {mFrameSize, (uint32_t)mBitDepth, mNumChannels, mOutputSampleRate};
     uint64_t total = 0;
     mLastStatus = alac_hip_encode_host_segments(mCtx, &fmt, pcm, numSamples, numPackets, segFirst, numSegments, nullptr, 0,
@@ -165,10 +167,11 @@ void ALACEncoder::InitializeSampling(void *d_ip, AudioFormatDescription theInput
     const uint32_t np = (uint32_t)ns.size();
     if (np == 0) return;
     (void)alac_hip_set_option(mCtx, "fast_mode", mFastMode ? 1 : 0);
+    (void)alac_hip_set_option(mCtx, "lpc", mLPCMode ? 1 : 0);
     alac_hip_format fmt = {mFrameSize, (uint32_t)mBitDepth, mNumChannels, mOutputSampleRate};
     const uint32_t segFirst[2] = {0, np};
     const uint64_t stateBytes = alac_hip_state_int16(&fmt) * 2ull;
-    const uint64_t wsBytes = alac_hip_encode_workspace_bytes(&fmt, np, 1);
+    const uint64_t wsBytes = alac_hip_encode_workspace_bytes(&fmt, np, mLPCMode ? np : 1);
     const uint64_t outMax = alac_hip_encode_max_output_bytes(&fmt, np);
     void *dNs = nullptr, *dSeg = nullptr, *dState = nullptr, *dWs = nullptr, *dOut = nullptr, *dSizes = nullptr,
          *dOffs = nullptr;

@@ -77,7 +77,7 @@ const AlacOptionKey *alac_option_keys(uint32_t *count)
         {"fast_mode", &AlacOptions::fastMode, 0, 1},   {"encoder_lane", &AlacOptions::laneEncoder, 0, 1},
         {"decoder_lane", &AlacOptions::laneDecoder, 0, 1}, {"dec_fused", &AlacOptions::decFused, -1, 1},
         {"dec_pair", &AlacOptions::decPair, 0, 1},     {"dec_direct", &AlacOptions::decDirect, 0, 2},
-        {"stage_taps", &AlacOptions::stageTaps, 0, 1},
+        {"stage_taps", &AlacOptions::stageTaps, 0, 1},  {"lpc", &AlacOptions::lpc, 0, 1},
         {"debug_lose_handoff", &AlacOptions::loseHandoff, 0, 1}, {"debug_waves", &AlacOptions::debugWaves, 0, 1},
     };
     if (count) *count = (uint32_t)(sizeof(table) / sizeof(table[0]));
@@ -351,6 +351,9 @@ DecLayout dec_layout(const alac_hip_format *f, uint32_t numPackets, uint64_t str
     return L;
 }
 
+// LPC mode: the header overrides of every packet and channel, behind the regular layout
+uint64_t lpc_table_bytes(uint32_t numPackets) { return align_up((uint64_t)numPackets * 2 * sizeof(LpcChan), 256); }
+
 bool use_lane_decoder(const alac_hip_ctx *ctx) { return ctx->opt.laneDecoder != 0; }
 
 struct DevBuf {
@@ -491,7 +494,7 @@ uint64_t alac_hip_encode_workspace_bytes(const alac_hip_format *fmt, uint32_t nu
 {
     if (!format_ok(fmt)) return 0;
     if (fmt->num_channels > 2) return mc_layout(fmt, num_packets, num_segments ? num_segments : num_packets).total;
-    return enc_layout(fmt, num_packets, num_segments ? num_segments : num_packets).total;
+    return enc_layout(fmt, num_packets, num_segments ? num_segments : num_packets).total + lpc_table_bytes(num_packets);
 }
 
 uint32_t alac_hip_state_int16(const alac_hip_format *fmt)
@@ -553,6 +556,7 @@ static int32_t encode_elements(alac_hip_ctx *ctx, const alac_hip_format *fmt, co
                                uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
                                uint32_t *d_packet_bytes, uint64_t *d_packet_offsets, uint32_t maxSegHint)
 {
+    if (ctx->opt.lpc) return fail(ctx, ALAC_HIP_ParamError, "option lpc: mono and stereo streams only");
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!d_pcm || !d_workspace || !d_out || !d_packet_bytes || !d_packet_offsets)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
@@ -650,6 +654,18 @@ static int32_t encode_core(alac_hip_ctx *ctx, const alac_hip_format *fmt, const 
                            uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
                            uint32_t *d_packet_bytes, uint64_t *d_packet_offsets, bool timed, uint32_t maxSegHint)
 {
+    // LPC mode: every packet is its own segment, whatever table the caller passes; the coefficient state is neither read
+    // nor written
+    const bool lpc = ctx->opt.lpc != 0;
+    if (lpc) {
+        if (ctx->opt.fastMode) return fail(ctx, ALAC_HIP_ParamError, "options lpc and fast_mode exclude each other");
+        if ((uint64_t)fmt->frame_size * fmt->num_channels * 4 > 65536)
+            return fail(ctx, ALAC_HIP_ParamError, "option lpc: frame_size x channels above 16 384");
+        d_seg_first = nullptr;
+        d_state = nullptr;
+        state_in = 0;
+        maxSegHint = 0;
+    }
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!d_pcm || !d_workspace || !d_out || !d_packet_bytes || !d_packet_offsets)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
@@ -658,7 +674,9 @@ static int32_t encode_core(alac_hip_ctx *ctx, const alac_hip_format *fmt, const 
     if (((uintptr_t)d_out & 3) || ((uintptr_t)d_workspace & 255) || ((uintptr_t)d_pcm & 15))
         return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer (out 4 B, pcm 16 B, workspace 256 B)");
     const EncLayout L = enc_layout(fmt, num_packets, num_segments);
-    if (workspace_bytes < L.total) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    if (workspace_bytes < L.total + (lpc ? lpc_table_bytes(num_packets) : 0))
+        return fail(ctx, ALAC_HIP_ParamError, lpc ? "workspace too small (option lpc: size it for num_segments = num_packets)"
+                                                  : "workspace too small");
     if (out_capacity < alac_hip_encode_max_output_bytes(fmt, num_packets))
         return fail(ctx, ALAC_HIP_ParamError, "output capacity below alac_hip_encode_max_output_bytes");
 
@@ -757,6 +775,24 @@ static int32_t encode_core(alac_hip_ctx *ctx, const alac_hip_format *fmt, const 
         e = launch_encode_v1(fmt->bit_depth, fmt->num_channels, ea, pa, vb, ctx->vs, num_packets, maxSeg, ctx->stream, ev);
     }
     if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "encode launch", e);
+    if (lpc) {
+        // Apple's independent packets are in the records and bit strings: the LPC candidates replace channels they beat,
+        // then the sizes are scanned and the packets packed again, with the LPC headers
+        LpcArgs la;
+        la.pcm = ea.pcm;
+        la.frameSize = fmt->frame_size;
+        la.recs = ea.recs;
+        la.packetBytes = d_packet_bytes;
+        la.bitWords = ea.bitWords;
+        la.wcap = L.wcap;
+        la.lpc = (LpcChan *)(ws + L.total);
+        e = launch_lpc(fmt->bit_depth, fmt->num_channels, la, num_packets, ctx->stream);
+        if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "lpc launch", e);
+        pa.lpc = la.lpc;
+        launch_scan_pack(fmt->bit_depth, fmt->num_channels, d_packet_bytes, pa, num_packets, ctx->stream, nullptr);
+        e = hipGetLastError();
+        if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "lpc pack launch", e);
+    }
     return ALAC_HIP_noErr;
 }
 
@@ -1071,7 +1107,7 @@ int32_t alac_hip_encode_host_segments(alac_hip_ctx *ctx, const alac_hip_format *
     const uint32_t np = num_packets, nseg = num_segments;
     const uint64_t stateBytes = (uint64_t)nseg * alac_hip_state_int16(fmt) * 2;
     const uint64_t pcmBytes = (uint64_t)np * fmt->frame_size * bpf;
-    const uint64_t wsBytes = alac_hip_encode_workspace_bytes(fmt, np, nseg);
+    const uint64_t wsBytes = alac_hip_encode_workspace_bytes(fmt, np, ctx->opt.lpc ? np : nseg);
     const uint64_t outMax = alac_hip_encode_max_output_bytes(fmt, np);
 
     DevBuf dPcm, dNs, dSeg, dState, dWs, dOut, dSizes, dOffs;

@@ -468,7 +468,9 @@ __global__ __launch_bounds__(256) void k_pack(PackArgs A, uint32_t numPackets)
     // bound by workgroup DISPATCH (125 000 empty 256-thread workgroups alone take 0.6 ms, measured), not by the copy.
     // Nothing in the loop synchronises the workgroup: waves 0..2 only copy, the last wave builds the header (its lanes
     // are the header's fields), writes the few words around the spans, then joins the copy.
-    __shared__ uint32_t hdr[16];  // touched by the last wave only: LDS operations of one wave execute in order
+    // the longest header: 23 + 32 + 16 + 2 x (16 + 16 x kLpcMaxOrder) bits
+    constexpr uint32_t kHdrWords = (23 + 32 + 16 + 2 * (16 + 16 * kLpcMaxOrder) + 31) / 32;
+    __shared__ uint32_t hdr[kHdrWords];  // touched by the last wave only: LDS operations of one wave execute in order
     const uint32_t lane = threadIdx.x & 63;
     const bool seamWave = (threadIdx.x >> 6) == (blockDim.x >> 6) - 1;
     constexpr uint32_t SHB = bytes_shifted(DEPTH);
@@ -757,39 +759,51 @@ __global__ __launch_bounds__(256) void k_pack(PackArgs A, uint32_t numPackets)
         // into zeroed LDS words.  lane 0: tag 3 | 0 4 | 0 12 | flags 4 (:467 / :762 / :921); lane 1: numSamples of a
         // partial frame; lane 2: mixBits | mixRes; per channel c: lane 3 + 9c = (mode|denShift, pbFactor|num), lanes
         // 4 + 9c + k = coefficient k (picked out of the record's registers by a select chain: no load).
-        if (lane < 16) hdr[lane] = 0;
-        uint32_t fpos = 0, fn = 0, fv = 0;
+        // LPC mode (PackArgs::lpc): a channel may carry its own denShift and up to kLpcMaxOrder coefficients; lane f then
+        // also takes field f + 64 (31 fields per channel).
+        if (lane < kHdrWords) hdr[lane] = 0;
+        const uint32_t perChan = A.lpc ? 1u + kLpcMaxOrder : 9u;
+        const LpcChan *lpcRec = A.lpc ? A.lpc + (uint64_t)p * 2 : nullptr;
         const uint32_t base = 23 + (partial ? 32u : 0u);
-        if (lane == 0) {
-            fn = 23;
-            fv = ((CH == 2 ? 1u : 0u) << 20) | (rec.escape ? ((partial << 3) | 1u) : ((partial << 3) | (SHB << 1)));
-        } else if (lane == 1) {
-            fpos = 23, fn = partial ? 32u : 0u, fv = N;
-        } else if (!rec.escape) {
-            if (lane == 2) {
-                fpos = base, fn = 16, fv = CH == 2 ? (((uint32_t)kMixBits << 8) | (rec.mixRes & 0xffu)) : 0u;
-            } else if (lane < 3 + 9 * CH) {
-                const uint32_t c = (lane - 3) / 9, k = (lane - 3) - 9 * c;
-                const uint32_t num = c ? rec.c[CH - 1].num : rec.c[0].num;
-                const uint32_t cstart = base + 16 + (c ? 16 + 16 * (uint32_t)rec.c[0].num : 0u);
-                if (k == 0) {
-                    fpos = cstart, fn = 16, fv = (((0u << 4) | kDenShift) << 8) | ((4u << 5) | num);
-                } else if (k - 1 < num) {
-                    uint32_t coef = 0;
+        for (uint32_t f = lane; f < 3 + perChan * CH; f += 64) {
+            uint32_t fpos = 0, fn = 0, fv = 0;
+            if (f == 0) {
+                fn = 23;
+                fv = ((CH == 2 ? 1u : 0u) << 20) | (rec.escape ? ((partial << 3) | 1u) : ((partial << 3) | (SHB << 1)));
+            } else if (f == 1) {
+                fpos = 23, fn = partial ? 32u : 0u, fv = N;
+            } else if (!rec.escape) {
+                if (f == 2) {
+                    fpos = base, fn = 16, fv = CH == 2 ? (((uint32_t)kMixBits << 8) | (rec.mixRes & 0xffu)) : 0u;
+                } else {
+                    const uint32_t c = (f - 3) / perChan, k = (f - 3) - perChan * c;
+                    const uint32_t num = c ? rec.c[CH - 1].num : rec.c[0].num;
+                    const uint32_t cstart = base + 16 + (c ? 16 + 16 * (uint32_t)rec.c[0].num : 0u);
+                    const bool own = lpcRec && lpcRec[c].num != 0;
+                    if (k == 0) {
+                        const uint32_t den = own ? lpcRec[c].den : kDenShift;
+                        fpos = cstart, fn = 16, fv = (((0u << 4) | den) << 8) | ((4u << 5) | num);
+                    } else if (k - 1 < num) {
+                        uint32_t coef = 0;
+                        if (own) {
+                            coef = (uint16_t)lpcRec[c].coefs[k - 1];
+                        } else {
 #pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        const uint32_t cq = (uint16_t)(c ? rec.c[CH - 1].coefs[q] : rec.c[0].coefs[q]);
-                        coef = (k - 1 == (uint32_t)q) ? cq : coef;
+                            for (int q = 0; q < 8; q++) {
+                                const uint32_t cq = (uint16_t)(c ? rec.c[CH - 1].coefs[q] : rec.c[0].coefs[q]);
+                                coef = (k - 1 == (uint32_t)q) ? cq : coef;
+                            }
+                        }
+                        fpos = cstart + 16 * k, fn = 16, fv = coef;
                     }
-                    fpos = cstart + 16 * k, fn = 16, fv = coef;
                 }
             }
-        }
-        if (fn) {
-            const uint32_t i = fpos >> 5, o = fpos & 31;
-            const uint64_t x = ((uint64_t)fv << (64 - fn)) >> o;  // field left-aligned at bit o of a 64-bit window
-            atomicOr(&hdr[i], (uint32_t)(x >> 32));
-            if (o + fn > 32) atomicOr(&hdr[i + 1], (uint32_t)x);
+            if (fn) {
+                const uint32_t i = fpos >> 5, o = fpos & 31;
+                const uint64_t x = ((uint64_t)fv << (64 - fn)) >> o;  // field left-aligned at bit o of a 64-bit window
+                atomicOr(&hdr[i], (uint32_t)(x >> 32));
+                if (o + fn > 32) atomicOr(&hdr[i + 1], (uint32_t)x);
+            }
         }
         if (!rec.escape && lane < nSeam) {
             seamU = fetch_pair(wU, lenU, seamBp - offU);

@@ -22,6 +22,15 @@ struct PacketRec {
     ChanRec c[2];
 };
 static_assert(sizeof(PacketRec) == 64, "PacketRec layout");
+// LPC mode (option "lpc", alac_lpc.hip): the header of a channel whose coefficients were computed from the packet's PCM,
+// [packet][2]; num == 0: the channel keeps Apple's header (PacketRec, denShift kDenShift)
+constexpr int kLpcMaxOrder = 30;
+struct LpcChan {
+    uint16_t den;
+    uint16_t num;
+    int16_t coefs[kLpcMaxOrder];
+};
+static_assert(sizeof(LpcChan) == 64, "LpcChan layout");
 
 struct EncodeArgs {
     const uint8_t *pcm;
@@ -54,7 +63,21 @@ struct PackArgs {
     const uint64_t *offsets;
     uint8_t *out;
     const uint32_t *segBad;      // nullable; != 0: the segment table was refused on the device — pack nothing
+    const LpcChan *lpc = nullptr; // nullable (LPC mode only): per packet and channel header overrides
 };
+
+// LPC mode, after the regular pipeline has encoded every packet as its own segment (alac_lpc.hip)
+struct LpcArgs {
+    const uint8_t *pcm;
+    uint32_t frameSize;
+    PacketRec *recs;
+    uint32_t *packetBytes;
+    uint32_t *bitWords;
+    uint32_t wcap;
+    LpcChan *lpc;  // [numPackets][2]
+};
+// one workgroup per packet; dynamic LDS channels * frameSize * 4 bytes (the caller keeps it <= 64 KB)
+hipError_t launch_lpc(uint32_t depth, uint32_t channels, const LpcArgs &a, uint32_t numPackets, hipStream_t st);
 
 // Stage timing: when `ev` is non-null, ev[i] is recorded BEFORE stage i and ev[kNumStages] after the
 // last one (stages that do not run in a given configuration record back-to-back events).
@@ -107,6 +130,7 @@ struct AlacOptions {
                                // copy): 0 never, 1 from kDecDirectPackets on, 2 whenever legal
     int32_t stageTaps = 1;     // "stage_taps"   ALAC_HIP_STAGE_TAPS  stage-level pc_block: tap-parallel kernel for 5..30 taps
     int32_t loseHandoff = 0;   // "debug_lose_handoff" ALAC_HIP_DEBUG_LOSE_HANDOFF  TEST switch: producers never publish (results invalid by design)
+    int32_t lpc = 0;           // "lpc"          (no env)             independent packets with per-packet LPC coefficients (alac_lpc.hip)
     int32_t debugWaves = 0;    // "debug_waves"  wave placement / timing stamps of the fused final launch into the workspace (tools/wave_map.py)
 };
 AlacOptions alac_options_from_env();

@@ -16,6 +16,10 @@
  *   --segment-packets K                       encode only: restart the predictor state every K packets so that
  *                                             one long file spreads over the GPU (valid ALAC, NOT byte-identical
  *                                             to the reference's output, about 1 % larger at K = 1)
+ *   --lpc                                     encode only: every packet independent, each channel with predictor
+ *                                             coefficients computed from the packet's own PCM where they code smaller
+ *                                             (valid ALAC, NOT byte-identical to the reference's output, never larger
+ *                                             than --segment-packets 1); mono and stereo
  *   --devices N                               with --batch: the files are dealt round-robin to N GPUs, one context and
  *                                             one host thread per device (replicas: independent files need no exchange
  *                                             between the GPUs, so there is no RCCL here); outputs are unchanged
@@ -63,6 +67,7 @@ void usage()
     printf("        alacconvert --batch <in1> <out1> [<in2> <out2> ...]\n");
     printf("        alacconvert --segment-packets K <input wav or caf file> <output caf file>\n");
     printf("        alacconvert --batch --devices N <in1> <out1> [<in2> <out2> ...]\n");
+    printf("        alacconvert --lpc [--batch] <input wav or caf file> <output caf or m4a file> ...\n");
     printf("\n");
 }
 
@@ -82,7 +87,7 @@ AudioFormatDescription alac_format(const InputInfo &in)
 }
 
 // ---- encode: all jobs share bit depth and channel count; each file is one segment ----
-bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, int device)
+bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, int device)
 {
     const InputInfo &first = jobs[0]->info;
     const uint32_t bps = (first.bitsPerChannel + 7) >> 3, ch = first.channels;  // 20 bits: 3-byte containers (container.cpp)
@@ -91,6 +96,7 @@ bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, int device)
 
     ALACEncoder enc;
     enc.SetFrameSize(frame);
+    enc.SetLPCMode(lpc);
     if (device >= 0) enc.SetDevice(device);
     AudioFormatDescription outFmt = alac_format(first);
     if (enc.InitializeEncoder(outFmt, 0) != ALAC_noErr) {
@@ -238,7 +244,7 @@ bool decode_group(std::vector<Job *> &jobs, const std::vector<alacfile::AlacCafC
 int main(int argc, char *argv[])
 {
     std::vector<std::string> files;
-    bool batch = false, malformed = argc < 2;
+    bool batch = false, lpc = false, malformed = argc < 2;
     uint32_t segmentPackets = 0, devices = 0;
     for (int i = 1; i < argc && !malformed; i++) {
         const std::string a = argv[i];
@@ -246,6 +252,8 @@ int main(int argc, char *argv[])
             malformed = true;
         } else if (a == "--batch") {
             batch = true;
+        } else if (a == "--lpc") {
+            lpc = true;
         } else if (a == "--segment-packets" && i + 1 < argc) {
             segmentPackets = (uint32_t)strtoul(argv[++i], nullptr, 10);
             if (segmentPackets == 0) malformed = true;
@@ -362,7 +370,7 @@ int main(int argc, char *argv[])
         const int device = firstDevice < 0 ? -1 : (int)(k % (uint32_t)visible);
         for (size_t i = 0; i < perWorker[k].size() && ok[k]; i++) {
             Work &w = perWorker[k][i];
-            ok[k] = w.decode ? decode_group(w.jobs, w.contents, device) : encode_group(w.jobs, segmentPackets, device);
+            ok[k] = w.decode ? decode_group(w.jobs, w.contents, device) : encode_group(w.jobs, segmentPackets, lpc, device);
         }
     };
     if (workers == 1) {

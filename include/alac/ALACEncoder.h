@@ -28,6 +28,9 @@ public:
     virtual int32_t Finish();
 
     void SetFastMode(bool fast) { mFastMode = fast; }
+    // Extension: independent packets with per-packet LPC coefficients (option "lpc" of include/alac_hip.h); together
+    // with SetFastMode(true) every encode call fails with kALAC_ParamError.  Mono and stereo only.
+    void SetLPCMode(bool lpc) { mLPCMode = lpc; }
     void SetFrameSize(uint32_t frameSize) { mFrameSize = frameSize; } /* before InitializeEncoder */
     /* Extension: the HIP device this object's context is created on (before InitializeEncoder; default: environment
      * ALAC_HIP_DEVICE, else 0).  One object = one device = one stream; objects on different devices may be driven from
@@ -61,6 +64,7 @@ public:
 protected:
     int16_t mBitDepth;
     bool mFastMode;
+    bool mLPCMode = false;
     uint32_t mTotalBytesGenerated, mAvgBitRate, mMaxFrameBytes;
     uint32_t mFrameSize, mMaxOutputBytes, mNumChannels, mOutputSampleRate;
 

@@ -87,10 +87,19 @@ int32_t alac_hip_synchronize(alac_hip_ctx *ctx);
  *                          staged copy: 0 never, 1 (default) from 80 000 packets on (below that the swap per word on the
  *                          entropy lanes' chain costs more than the copy), 2 whenever the stream allows it
  *   "stage_taps" (0/1)     alac_hip_pc_block: tap-parallel kernel for 5..30 taps
+ *   "lpc" (0/1)            encode, every entry point: independent packets whose channels may carry predictor coefficients
+ *                          computed from the packet's own PCM (autocorrelation + Levinson-Durbin, orders 4 8 12 16 24 30, any
+ *                          denShift <= 15, counted exactly on the GPU) wherever they code smaller than Apple's init_coefs
+ *                          channel; a packet is never larger than with one segment per packet.  The segment table is
+ *                          ignored (every packet is its own segment: size the workspace with num_segments = num_packets, and
+ *                          pass the packet count to alac_hip_encode_regime), d_state is neither read nor written, escaped
+ *                          packets stay escaped.  Mono and stereo, frame_size x channels <= 16 384; 3..8 channels, or
+ *                          "fast_mode" = 1 at the same time -> kALAC_ParamError from the encode call.  NOT the reference's
+ *                          bytes (decoders that follow the format decode it; orders above 8 take their generic predictor)
  *   "debug_waves" (0/1)    diagnostics, see alac_hip_debug_waves_offset
  *   "debug_lose_handoff" (0/1)  TEST switch, the one key that invalidates results by design: producers of the in-launch
  *                          hand-offs never publish, so every call fails with kALAC_MemFullError at the next synchronize
- * Every other setting produces the same bytes; only the kernels that run differ.  Unknown key or a value outside the
+ * Every other setting except "lpc" produces the same bytes; only the kernels that run differ.  Unknown key or a value outside the
  * key's range -> kALAC_ParamError. */
 int32_t alac_hip_set_option(alac_hip_ctx *ctx, const char *key, int32_t value);
 int32_t alac_hip_get_option(alac_hip_ctx *ctx, const char *key, int32_t *value);
@@ -98,7 +107,8 @@ int32_t alac_hip_get_option(alac_hip_ctx *ctx, const char *key, int32_t *value);
  * byte offset of the caller's workspace (HW_ID, XCC_ID, s_memtime at entry, at exit, HW_ID at exit, 0): where and when every
  * wave ran (tools/wave_map.py).  Batches above 4096 chains only (below, the words are the row-ready flags of chained files). */
 uint64_t alac_hip_debug_waves_offset(const alac_hip_format *fmt, uint32_t num_packets, uint32_t num_segments);
-/* The encode regime this context would pick for a batch of num_segments independent segments of this format (a static
+/* The encode regime this context would pick for a batch of num_segments independent segments of this format (option "lpc":
+ * num_segments = the packet count, every packet is its own segment there) (a static
  * string, from the launcher's own predicates): "throughput" (separate launches, 64 chains per wave), "latency"
  * (producer/consumer launches, two lanes per chain), "tiny" (four lanes per chain: chained files), "stagewise" (option
  * "fused" = 0) or "lane" (first-generation kernel).  For reporting. */
@@ -112,7 +122,7 @@ void *alac_hip_stream(const alac_hip_ctx *ctx);
  * (codec/ALACEncoder.cu:1385-1451, :973-1057, :290-558, :749-806, :812-963; the stage calls
  *  pc_block codec/dp_enc.c:77, dyn_comp codec/ag_enc.c:249, mixNN codec/matrix_enc.cu:101-425). */
 
-/* Bytes of device scratch alac_hip_encode needs for this shape. */
+/* Bytes of device scratch alac_hip_encode needs for this shape (option "lpc": num_segments = num_packets). */
 uint64_t alac_hip_encode_workspace_bytes(const alac_hip_format *fmt, uint32_t num_packets,
                                          uint32_t num_segments);
 /* Upper bound of the packed output of num_packets packets (every packet escaped + header). */
