@@ -73,9 +73,11 @@ __device__ uint32_t lpc_pass(const int32_t *X, uint32_t N, const Cand &cd, int n
     return g.bits;
 }
 
-// Levinson-Durbin over r[0..30] into the candidate table (one lane)
+// Levinson-Durbin over r[0..30] into the candidate table (one lane).  The arithmetic is pinned for the host reference
+// (oracle/lpc_ref.py): the three fused steps are explicit fma() calls, and nothing else may be contracted.
 __device__ void lpc_levinson(const double *r, uint32_t N, Cand *cand)
 {
+#pragma clang fp contract(off)
     for (int c = 0; c < kCands; c++) cand[c].den = 0;
     if (!(r[0] > 0.0)) return;
     double a[kLags] = {0}, t[kLags];
@@ -83,13 +85,13 @@ __device__ void lpc_levinson(const double *r, uint32_t N, Cand *cand)
     int next = 0;
     for (int m = 1; m <= kLpcMaxOrder && next < kCands; m++) {
         double acc = r[m];
-        for (int i = 1; i < m; i++) acc -= a[i] * r[m - i];
+        for (int i = 1; i < m; i++) acc = fma(-a[i], r[m - i], acc);
         const double km = acc / err;
         if (!(fabs(km) < 1.0)) return;
-        for (int i = 1; i < m; i++) t[i] = a[i] - km * a[m - i];
+        for (int i = 1; i < m; i++) t[i] = fma(-km, a[m - i], a[i]);
         for (int i = 1; i < m; i++) a[i] = t[i];
         a[m] = km;
-        err *= 1.0 - km * km;
+        err *= fma(-km, km, 1.0);
         if (!(err > 0.0)) return;
         if (m != kOrders[next]) continue;
         Cand &cd = cand[next++];

@@ -108,12 +108,10 @@ class Forger:
             r, _ = self.o.pc_block(r, n, np.zeros(32, np.int16), 31, chan_bits, 0, fn=self.pc_fn)
         return r[:n]
 
-    def element(self, pcm, n, depth, channels, frame_size, params, mix_bits=0, mix_res=0, bytes_shifted=0,
-                instance=0, pb=40, mb=10, kb=14, lfe=False, force_partial=False, end=True, buf=None, pos=None):
-        """One compressed element for `channels` in (1, 2) from n sample-frames of packed PCM.  Returns the finished
-        packet (element + ID_END + byte alignment) as bytes, or with end=False appends to (buf, pos) for multi-element
-        packets.  params: [ChannelParams] per channel."""
-        assert channels in (1, 2) and 0 <= bytes_shifted <= 2 and n <= frame_size
+    @staticmethod
+    def planes(pcm, n, depth, channels, mix_bits=0, mix_res=0, bytes_shifted=0):
+        """the planes the predictor runs over: (planes [int64 array per channel], shifted-off low bits [channels][n] or None,
+        chanBits).  Stereo: u, v of the mix (v = R and u = L for mixRes 0)."""
         x = pcm_to_channels(pcm, depth, channels, n)
         shift = 8 * bytes_shifted
         sh = x & ((1 << shift) - 1) if shift else None
@@ -130,6 +128,16 @@ class Forger:
             planes = [x[0]]
         for p in planes:
             assert p.size == 0 or (p.min() >= -(1 << 31) and p.max() < (1 << 31))
+        return planes, sh, chan_bits
+
+    def element(self, pcm, n, depth, channels, frame_size, params, mix_bits=0, mix_res=0, bytes_shifted=0,
+                instance=0, pb=40, mb=10, kb=14, lfe=False, force_partial=False, end=True, buf=None, pos=None):
+        """One compressed element for `channels` in (1, 2) from n sample-frames of packed PCM.  Returns the finished
+        packet (element + ID_END + byte alignment) as bytes, or with end=False appends to (buf, pos) for multi-element
+        packets.  params: [ChannelParams] per channel."""
+        assert channels in (1, 2) and 0 <= bytes_shifted <= 2 and n <= frame_size
+        planes, sh, chan_bits = self.planes(pcm, n, depth, channels, mix_bits, mix_res, bytes_shifted)
+        shift = 8 * bytes_shifted
         own = buf is None
         if own:
             buf = np.zeros(n * channels * 8 + 4096, np.uint8)
@@ -175,6 +183,36 @@ class Forger:
         self._put(buf, pos, tag, 3)
         self._put(buf, pos, 0x5a5a5a5a, 32)
         return buf[:8].copy()
+
+
+class Bits:
+    """MSB-first bit reader over a packet"""
+
+    def __init__(self, b):
+        self.v, self.n, self.pos = int.from_bytes(bytes(b), "big"), len(b) * 8, 0
+
+    def get(self, k, signed=False):
+        x = (self.v >> (self.n - self.pos - k)) & ((1 << k) - 1)
+        self.pos += k
+        return x - (1 << k) if signed and x >> (k - 1) else x
+
+
+def parse_header(pkt, channels):
+    """(escape, n or None, bytes_shifted, mix_bits, mix_res, [ChannelParams]) of a one-element packet"""
+    r = Bits(pkt)
+    r.get(3), r.get(4), r.get(12)
+    partial, shifted, escape = r.get(1), r.get(2), r.get(1)
+    n = r.get(32) if partial else None
+    if escape:
+        return True, n, 0, 0, 0, []
+    mix_bits, mix_res = r.get(8), r.get(8, signed=True)
+    params = []
+    for _ in range(channels):
+        mode, den = r.get(4), r.get(4)
+        pbf, num = r.get(3), r.get(5)
+        coefs = [r.get(16, signed=True) for _ in range(num)]
+        params.append(ChannelParams(num=num, den_shift=den, pb_factor=pbf, mode=mode, coefs=coefs))
+    return False, n, shifted, mix_bits, mix_res, params
 
 
 def random_params(rng, num_choices=(0, 1, 2, 3, 4, 5, 6, 8, 12, 16, 30, 31), den_choices=(4, 5, 6, 7, 8, 9, 10, 11, 12),

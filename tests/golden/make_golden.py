@@ -10,8 +10,8 @@ Outputs (data only — inputs and expected outputs, no reference source):
   packets.npz         short excerpts of the reference's audio/50.wav (stereo) and audio/05.wav (mono)
                       with the packets produced by the encoder driver running over the reference's
                       pc_block/dyn_comp, chained and independent
-  known_answers.json  sizes / FNV-1a-64 of whole-file encodes of the three reference WAVs and of the
-                      synthetic workload (pins the generator too)
+  known_answers.json  sizes / FNV-1a-64 of whole-file encodes of the three reference WAVs (chained, independent and
+                      in the LPC mode, the last from oracle/lpc_ref.py) and of the synthetic workload (pins the generator too)
   forged.npz          packets with FOREIGN header / cookie parameters (oracle/forge.py run over the reference's compiled
                       pc_block / dyn_comp / BitBufferWrite) and the PCM the decoder driver produces from them over the
                       reference's dyn_decomp / unpc_block: the pin of the decoder's general paths
@@ -32,6 +32,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle"))
 from oracle_lib import REFERENCE_WAVS, Oracle, Ref, read_wav  # noqa: E402
 
 REF_AUDIO = "/root/reference/audio"
@@ -198,6 +199,13 @@ def make_caf_headers():
     print("caf_headers.json written")
 
 
+def lpc_known_answers(o, data, total, bits, ch):
+    """the LPC-mode stream (option lpc) of a file, forged by the host reference oracle/lpc_ref.py"""
+    import lpc_ref
+    s, _, _ = lpc_ref.stream(o, data, total, bits, ch, 4096)
+    return dict(lpc_bytes=int(len(s)), lpc_fnv=f"{o.fnv(s):016x}")
+
+
 def make_known_answers(o, r):
     import alac_amd
     H = r.hooks()
@@ -211,6 +219,7 @@ def make_known_answers(o, r):
                                chained_bytes=int(len(s)), chained_fnv=f"{o.fnv(s):016x}",
                                chained_first_sizes=[int(x) for x in sz[:8]], chained_last_size=int(sz[-1]),
                                indep_bytes=int(len(s1)), indep_fnv=f"{o.fnv(s1):016x}")
+        ka["wav"][name].update(lpc_known_answers(o, data, total, bits, ch))
     for depth, ch in ((16, 2), (24, 2), (20, 2), (32, 2), (16, 1), (24, 1)):
         fmt = alac_amd.make_format(4096, depth, ch)
         n = 64

@@ -48,59 +48,31 @@ def split(stream, sizes):
     return [stream[e - s:e] for s, e in zip(sizes.astype(np.int64), ends)]
 
 
-class Bits:
-    def __init__(self, b):
-        self.v, self.n, self.pos = int.from_bytes(bytes(b), "big"), len(b) * 8, 0
-
-    def get(self, k, signed=False):
-        x = (self.v >> (self.n - self.pos - k)) & ((1 << k) - 1)
-        self.pos += k
-        return x - (1 << k) if signed and x >> (k - 1) else x
-
-
-def parse_header(pkt, channels):
-    """(escape, n or None, bytes_shifted, mix_bits, mix_res, [ChannelParams]) of a one-element packet"""
-    r = Bits(pkt)
-    r.get(3), r.get(4), r.get(12)
-    partial, shifted, escape = r.get(1), r.get(2), r.get(1)
-    n = r.get(32) if partial else None
-    if escape:
-        return True, n, 0, 0, 0, []
-    mix_bits, mix_res = r.get(8), r.get(8, signed=True)
-    params = []
-    for _ in range(channels):
-        mode, den = r.get(4), r.get(4)
-        pbf, num = r.get(3), r.get(5)
-        coefs = [r.get(16, signed=True) for _ in range(num)]
-        params.append(forge.ChannelParams(num=num, den_shift=den, pb_factor=pbf, mode=mode, coefs=coefs))
-    return False, n, shifted, mix_bits, mix_res, params
-
-
-def check_packets(ctx, oracle, fmt, pcm, total, stream, sizes, ref=None):
+def check_packets(ctx, oracle, fmt, pcm, total, stream, sizes, ref=None, frame=FRAME):
     """round trip through the oracle / reference / GPU decoders and the byte-for-byte re-forge; returns the LPC channels"""
     ch, depth, bpf = fmt.num_channels, fmt.bit_depth, fmt.bytes_per_frame
-    pcm = np.concatenate([pcm, np.zeros(len(sizes) * FRAME * bpf - pcm.size, np.uint8)])
+    pcm = np.concatenate([pcm, np.zeros(len(sizes) * frame * bpf - pcm.size, np.uint8)])
     cookie = ctx.magic_cookie(fmt)
     dec = oracle.decoder(cookie)
     rdec = oracle.decoder(cookie, hooks=ref.hooks()) if ref is not None else None
     forger = forge.Forger(oracle)
     lpc_channels = 0
     for p, pkt in enumerate(split(stream, sizes)):
-        n = min(FRAME, total - p * FRAME)
-        src = pcm[p * FRAME * bpf:(p * FRAME + n) * bpf]
+        n = min(frame, total - p * frame)
+        src = pcm[p * frame * bpf:(p * frame + n) * bpf]
         for d in (dec, rdec):
             if d is None:
                 continue
             st, out, ns = d.decode_packet(pkt, bpf)
             assert st == 0 and ns == n and np.array_equal(out, src), f"packet {p}"
-        esc, hn, shifted, mix_bits, mix_res, params = parse_header(pkt, ch)
-        assert hn == (None if n == FRAME else n)
+        esc, hn, shifted, mix_bits, mix_res, params = forge.parse_header(pkt, ch)
+        assert hn == (None if n == frame else n)
         if esc:
             continue
         for cp in params:
             assert cp.mode == 0 and cp.pb_factor == 4 and cp.num <= 30 and cp.num != 31
             lpc_channels += cp.den_shift != 9 or cp.num not in (4, 8)
-        again = forger.element(src, n, depth, ch, FRAME, params, mix_bits=mix_bits, mix_res=mix_res,
+        again = forger.element(src, n, depth, ch, frame, params, mix_bits=mix_bits, mix_res=mix_res,
                                bytes_shifted=shifted)
         assert np.array_equal(again, pkt), f"re-forged packet {p} differs"
     offs = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes.astype(np.int64))])).cuda()
@@ -111,8 +83,8 @@ def check_packets(ctx, oracle, fmt, pcm, total, stream, sizes, ref=None):
     return lpc_channels
 
 
-def never_larger(oracle, fmt, pcm, total, sizes):
-    enc = oracle.encoder(FRAME, fmt.bit_depth, fmt.num_channels, 44100)
+def never_larger(oracle, fmt, pcm, total, sizes, frame=FRAME):
+    enc = oracle.encoder(frame, fmt.bit_depth, fmt.num_channels, 44100)
     _, ind = enc.encode_stream(pcm, total, segment_packets=1)
     assert len(ind) == len(sizes) and bool((sizes <= ind).all()), np.flatnonzero(sizes > ind)[:8]
     return int(ind.sum())
@@ -201,7 +173,7 @@ def test_silence_noise_wrap(gpu_ctx, oracle, kind):
     check_packets(gpu_ctx, oracle, fmt, pcm, frames, stream, sizes)
     never_larger(oracle, fmt, pcm, frames, sizes)
     if kind == "noise":
-        assert all(parse_header(p, 2)[0] for p in split(stream, sizes))
+        assert all(forge.parse_header(p, 2)[0] for p in split(stream, sizes))
 
 
 def test_lpc_with_fast_mode_is_refused(gpu_ctx):
