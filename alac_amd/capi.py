@@ -75,6 +75,9 @@ SIGNATURES = {
     "alac_hip_encode_host_segments": (_i32, [_vp, C.POINTER(Format), _vp, _vp, _u32, _vp, _u32, _vp, _i32, _vp, _u64, _vp,
                                              C.POINTER(_u64)]),
     "alac_hip_decode_host": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "alac_hip_verify_workspace_bytes_stream": (_u64, [C.POINTER(Format), _u32, _u64]),
+    "alac_hip_verify": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "alac_hip_verify_host": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "alac_synth_frame": (None, [_u64, _u32, _u32, _u32, _vp]),
     "alac_synth_pcm": (None, [_u64, _u32, _u32, _u32, _u32, _vp]),
     "alac_hip_synth_pcm": (_i32, [_vp, _u64, _u32, C.POINTER(Format), _vp]),
@@ -390,6 +393,35 @@ class Context:
             for x in (pcm, ns, st):
                 x.record_stream(cur)  # allocated on self.stream, consumed on the caller's
             return pcm, ns, st, fmt
+
+    def verify(self, cookie, stream, offsets, num_packets, pcm, num_samples=None):
+        """Decode on the device and compare with `pcm` (uint8 cuda, the layout decode() returns), writing no PCM.
+        num_samples: expected frames per packet (int32 cuda [num_packets]), None = every packet full.
+        Returns (first_mismatch, status, bad_packets): int32 cuda tensors [num_packets], [num_packets], [1];
+        first_mismatch[p] is the lowest differing sample-frame, -1 (0xFFFFFFFF) where the packet matches, 0 where it did not
+        decode; bad_packets counts the packets that are not -1.  Asynchronous like decode()."""
+        with self._call() as cur:
+            t = self.torch
+            ck = np.ascontiguousarray(cookie, np.uint8)
+            fmt = Format()
+            self._check(self.lib.alac_hip_format_from_cookie(ck.ctypes.data, ck.size, C.byref(fmt)))
+            if pcm.numel() < num_packets * fmt.packet_bytes:
+                raise ValueError("verify: expected PCM too small")
+            if num_samples is not None and num_samples.numel() < num_packets:
+                raise ValueError("verify: num_samples too small")
+            # every word is written by the call (no fill launches in front of it)
+            fm = t.empty(num_packets, dtype=t.int32, device=self.device)
+            st = t.empty(num_packets, dtype=t.int32, device=self.device)
+            bad = t.empty(1, dtype=t.int32, device=self.device)
+            wsb = int(self.lib.alac_hip_verify_workspace_bytes_stream(C.byref(fmt), num_packets, int(stream.numel())))
+            ws = self._workspace(wsb)
+            rc = self.lib.alac_hip_verify(self.h, ck.ctypes.data, ck.size, stream.data_ptr(), offsets.data_ptr(), num_packets,
+                                          pcm.data_ptr(), None if num_samples is None else num_samples.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), fm.data_ptr(), st.data_ptr(), bad.data_ptr())
+            self._check(rc)
+            for x in (fm, st, bad):
+                x.record_stream(cur)
+            return fm, st, bad
 
     # ---- stage level ------------------------------------------------------------------------
     def pc_block(self, x, num, coefs, numactive, chanbits, denshift=9, decode=False):

@@ -74,6 +74,18 @@ int32_t ALACDecoder::DecodeBatch(const uint8_t *stream, const uint32_t *packetBy
     return mLastStatus;
 }
 
+int32_t ALACDecoder::VerifyBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets,
+                                 const uint8_t *pcmExpected, const uint32_t *numSamplesExpected, uint32_t *firstMismatchOut,
+                                 int32_t *statusOut, uint32_t *badPacketsOut)
+{
+    if (!mCtx || mCookie.empty() || !firstMismatchOut || !statusOut) return kALAC_ParamError;
+    const int32_t bad = alac_hip_verify_host(mCtx, mCookie.data(), (uint32_t)mCookie.size(), stream, packetBytes, numPackets,
+                                             pcmExpected, numSamplesExpected, firstMismatchOut, statusOut);
+    mLastStatus = bad < 0 ? bad : ALAC_noErr;
+    if (bad >= 0 && badPacketsOut) *badPacketsOut = (uint32_t)bad;
+    return mLastStatus;
+}
+
 int32_t ALACDecoder::Decode(BitBuffer *bits, uint8_t *sampleBuffer, uint32_t /*numSamples*/, uint32_t numChannels,
                             uint32_t *outNumSamples)
 {

@@ -946,10 +946,13 @@ uint64_t alac_hip_decode_workspace_bytes_stream(const alac_hip_format *fmt, uint
     return dec_layout(fmt, num_packets, stream_bytes).total;
 }
 
-int32_t alac_hip_decode(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
-                        const uint64_t *d_packet_offsets, uint32_t num_packets, void *d_workspace,
-                        uint64_t workspace_bytes, uint8_t *d_pcm_out, uint32_t *d_num_samples_out,
-                        int32_t *d_status)
+}  // extern "C"
+
+namespace {
+// alac_hip_decode, and alac_hip_verify's decode pass (verifyMismatch non-null: d_pcm_out is the expected PCM, only read)
+int32_t decode_impl(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
+                    const uint64_t *d_packet_offsets, uint32_t num_packets, void *d_workspace, uint64_t workspace_bytes,
+                    uint8_t *d_pcm_out, uint32_t *d_num_samples_out, int32_t *d_status, uint32_t *verifyMismatch)
 {
     if (!ctx) return ALAC_HIP_ParamError;
     alac_hip_format fmt;
@@ -995,6 +998,8 @@ int32_t alac_hip_decode(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t coo
     da.optFused = ctx->opt.decFused;
     da.optPair = ctx->opt.decPair;
     da.optDirect = ctx->opt.decDirect;
+    da.firstMismatch = verifyMismatch;
+    da.frameBytes = fmt.num_channels * bytes_per_sample(fmt.bit_depth);
     hipError_t e;
     if (use_lane_decoder(ctx)) {
         e = launch_decode(da, ctx->stream);
@@ -1027,6 +1032,68 @@ int32_t alac_hip_decode(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t coo
         }
     }
     if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "decode launch", e);
+    return ALAC_HIP_noErr;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t alac_hip_decode(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
+                        const uint64_t *d_packet_offsets, uint32_t num_packets, void *d_workspace,
+                        uint64_t workspace_bytes, uint8_t *d_pcm_out, uint32_t *d_num_samples_out,
+                        int32_t *d_status)
+{
+    return decode_impl(ctx, h_cookie, cookie_size, d_stream, d_packet_offsets, num_packets, d_workspace, workspace_bytes,
+                       d_pcm_out, d_num_samples_out, d_status, nullptr);
+}
+
+// ---- verify: alac_hip_decode with the PCM store sites comparing against the caller's PCM ------------------------------
+// Workspace: the decoder's own (dec_layout) + the decoded frame counts; no PCM plane on any path — every kernel that writes
+// PCM in alac_hip_decode has an instantiation that compares there instead (alac_verify.hpp), the lane decoder's too.
+// The decoded frame counts sit in FRONT of the decoder's workspace: the decoder takes everything behind its own layout as
+// staging words, so a longer stream only needs a larger workspace here too.
+static uint64_t verify_ns_bytes(uint32_t numPackets) { return align_up((uint64_t)numPackets * 4, 256); }
+
+uint64_t alac_hip_verify_workspace_bytes_stream(const alac_hip_format *fmt, uint32_t num_packets, uint64_t stream_bytes)
+{
+    if (!format_ok(fmt)) return 0;
+    return verify_ns_bytes(num_packets) + dec_layout(fmt, num_packets, stream_bytes).total;
+}
+
+int32_t alac_hip_verify(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
+                        const uint64_t *d_packet_offsets, uint32_t num_packets, const uint8_t *d_pcm_expected,
+                        const uint32_t *d_num_samples_expected, void *d_workspace, uint64_t workspace_bytes,
+                        uint32_t *d_first_mismatch, int32_t *d_status, uint32_t *d_bad_packets)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    alac_hip_format fmt;
+    if (alac_hip_format_from_cookie(h_cookie, cookie_size, &fmt) != ALAC_HIP_noErr)
+        return fail(ctx, ALAC_HIP_ParamError, "bad magic cookie");
+    if (!format_ok(&fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format in cookie");
+    if (!d_bad_packets) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    if (num_packets == 0) {
+        const hipError_t e = hipMemsetAsync(d_bad_packets, 0, 4, ctx->stream);
+        return e == hipSuccess ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
+    }
+    if (!d_stream || !d_packet_offsets || !d_workspace || !d_pcm_expected || !d_first_mismatch || !d_status)
+        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if (((uintptr_t)d_workspace & 255) || ((uintptr_t)d_pcm_expected & 3))
+        return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
+    const DecLayout L = dec_layout(&fmt, num_packets);
+    const uint64_t nsBytes = verify_ns_bytes(num_packets);
+    if (workspace_bytes < nsBytes + L.total) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    uint8_t *ws = (uint8_t *)d_workspace;
+    uint32_t *ns = (uint32_t *)ws;
+    hipError_t e = launch_verify_init(d_first_mismatch, num_packets, d_bad_packets, ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
+    const int32_t rc = decode_impl(ctx, h_cookie, cookie_size, d_stream, d_packet_offsets, num_packets, ws + nsBytes,
+                                   workspace_bytes - nsBytes, const_cast<uint8_t *>(d_pcm_expected), ns, d_status,
+                                   d_first_mismatch);
+    if (rc != ALAC_HIP_noErr) return rc;
+    e = launch_verify_finish(d_status, ns, d_num_samples_expected, fmt.frame_size, num_packets, d_first_mismatch, d_bad_packets,
+                             ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
     return ALAC_HIP_noErr;
 }
 
@@ -1219,6 +1286,51 @@ int32_t alac_hip_decode_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_
         (e = hipStreamSynchronize(st)))
         return fail(ctx, ALAC_HIP_ParamError, "decode execution", e);
     return check_handoff(ctx);
+}
+
+int32_t alac_hip_verify_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *h_stream,
+                             const uint32_t *h_packet_bytes, uint32_t num_packets, const uint8_t *h_pcm_expected,
+                             const uint32_t *h_num_samples_expected, uint32_t *h_first_mismatch, int32_t *h_status)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    alac_hip_format fmt;
+    if (alac_hip_format_from_cookie(h_cookie, cookie_size, &fmt) != ALAC_HIP_noErr || !format_ok(&fmt))
+        return fail(ctx, ALAC_HIP_ParamError, "bad magic cookie");
+    if (num_packets == 0) return 0;
+    if (!h_stream || !h_packet_bytes || !h_pcm_expected) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if (num_packets > 0x7fffffffu) return fail(ctx, ALAC_HIP_ParamError, "more packets than the return value counts");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    std::vector<uint64_t> offs(num_packets + 1, 0);
+    for (uint32_t i = 0; i < num_packets; i++) offs[i + 1] = offs[i] + h_packet_bytes[i];
+    const uint64_t total = offs[num_packets];
+    const uint32_t bpf = fmt.num_channels * bytes_per_sample(fmt.bit_depth);
+    const uint64_t pcmBytes = (uint64_t)num_packets * fmt.frame_size * bpf;
+    const uint64_t wsBytes = alac_hip_verify_workspace_bytes_stream(&fmt, num_packets, total);
+    DevBuf dStream, dOffs, dWs, dPcm, dNs, dFm, dSt, dBad;
+    hipError_t e;
+    if ((e = dStream.alloc(total + 16)) || (e = dOffs.alloc((num_packets + 1) * 8ull)) || (e = dWs.alloc(wsBytes)) ||
+        (e = dPcm.alloc(pcmBytes)) || (h_num_samples_expected && (e = dNs.alloc(num_packets * 4ull))) ||
+        (e = dFm.alloc(num_packets * 4ull)) || (e = dSt.alloc(num_packets * 4ull)) || (e = dBad.alloc(4)))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    hipStream_t st = ctx->stream;
+    if ((e = hipMemcpyAsync(dStream.p, h_stream, total, hipMemcpyHostToDevice, st)) ||
+        (e = hipMemcpyAsync(dOffs.p, offs.data(), (num_packets + 1) * 8ull, hipMemcpyHostToDevice, st)) ||
+        (e = hipMemcpyAsync(dPcm.p, h_pcm_expected, pcmBytes, hipMemcpyHostToDevice, st)) ||
+        (h_num_samples_expected &&
+         (e = hipMemcpyAsync(dNs.p, h_num_samples_expected, num_packets * 4ull, hipMemcpyHostToDevice, st))))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    int32_t rc = alac_hip_verify(ctx, h_cookie, cookie_size, (const uint8_t *)dStream.p, (const uint64_t *)dOffs.p, num_packets,
+                                 (const uint8_t *)dPcm.p, (const uint32_t *)dNs.p, dWs.p, wsBytes, (uint32_t *)dFm.p,
+                                 (int32_t *)dSt.p, (uint32_t *)dBad.p);
+    if (rc != ALAC_HIP_noErr) return rc;
+    uint32_t bad = 0;
+    if ((e = hipMemcpyAsync(&bad, dBad.p, 4, hipMemcpyDeviceToHost, st)) ||
+        (h_first_mismatch && (e = hipMemcpyAsync(h_first_mismatch, dFm.p, num_packets * 4ull, hipMemcpyDeviceToHost, st))) ||
+        (h_status && (e = hipMemcpyAsync(h_status, dSt.p, num_packets * 4ull, hipMemcpyDeviceToHost, st))) ||
+        (e = hipStreamSynchronize(st)))
+        return fail(ctx, ALAC_HIP_ParamError, "verify execution", e);
+    rc = check_handoff(ctx);
+    return rc != ALAC_HIP_noErr ? rc : (int32_t)bad;
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include "alac_dev.hpp"
 #include "alac_kernels.hpp"
 #include "alac_unpc.hpp"
+#include "alac_verify.hpp"
 
 namespace alacdev {
 
@@ -279,22 +280,22 @@ __global__ __launch_bounds__(64) void k_decode_unpc(DecodeArgs A)
 
 // ---- un-mix + pack (gpu_unmixNN / gpu_copyPredictorToNN, codec/ALACDecoder.cu:193-495) --------
 
-template <int DEPTH>
-__device__ __forceinline__ void store_sample(uint8_t *p, int32_t x)
+template <int DEPTH, bool VERIFY>
+__device__ __forceinline__ void store_sample(const DecodeArgs &A, uint8_t *p, int32_t x)
 {
     if constexpr (DEPTH == 16) {
-        *(int16_t *)p = (int16_t)x;
+        PCM_PUT(VERIFY, A, (int16_t *)p, (int16_t)x);
     } else if constexpr (DEPTH == 32) {
-        *(int32_t *)p = x;
+        PCM_PUT(VERIFY, A, (int32_t *)p, x);
     } else {
         if constexpr (DEPTH == 20) x = (int32_t)((uint32_t)x << 4);
-        p[0] = (uint8_t)x;
-        p[1] = (uint8_t)(x >> 8);
-        p[2] = (uint8_t)(x >> 16);
+        PCM_PUT(VERIFY, A, p, (uint8_t)x);
+        PCM_PUT(VERIFY, A, p + 1, (uint8_t)(x >> 8));
+        PCM_PUT(VERIFY, A, p + 2, (uint8_t)(x >> 16));
     }
 }
 
-template <int DEPTH, int CH>
+template <int DEPTH, int CH, bool VERIFY>
 __global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A)
 {
     if (A.gate && *A.gate == 0) return;
@@ -352,8 +353,8 @@ __global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A)
             l = (int32_t)(((uint32_t)l << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
             if constexpr (CH == 2) r = (int32_t)(((uint32_t)r << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
         }
-        store_sample<DEPTH>(op, l);
-        if constexpr (CH == 2) store_sample<DEPTH>(op + BPS, r);
+        store_sample<DEPTH, VERIFY>(A, op, l);
+        if constexpr (CH == 2) store_sample<DEPTH, VERIFY>(A, op + BPS, r);
     }
     __syncthreads();
     }
@@ -362,7 +363,7 @@ __global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A)
 // > 2 channels: the same tile walk once per output channel c; a packet's element that STARTS at c is un-mixed and
 // written at channel c (and c + 1) of the numChannels-interleaved frame (unmixNN / copyPredictorToNN with stride
 // numChannels, codec/ALACDecoder.cu:733-753,:900-935); channels no element carries are zero (:971-998).
-template <int DEPTH>
+template <int DEPTH, bool VERIFY>
 __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A)
 {
     if (A.gate && *A.gate == 0) return;
@@ -396,7 +397,7 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A)
             uint8_t *op = A.pcmOut + (((uint64_t)p * A.frameSize + j) * nch + c) * BPS;
             if (!rec) {
                 const uint32_t ns = A.recs[p].elementChannels ? A.recs[p].numSamples : A.frameSize;
-                if (j < ns) store_sample<DEPTH>(op, 0);
+                if (j < ns) store_sample<DEPTH, VERIFY>(A, op, 0);
                 continue;
             }
             if (rec->chanIndex != c || j >= rec->numSamples) continue;
@@ -417,15 +418,15 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A)
                 l = (int32_t)(((uint32_t)l << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
                 if (ech == 2) r = (int32_t)(((uint32_t)r << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
             }
-            store_sample<DEPTH>(op, l);
-            if (ech == 2) store_sample<DEPTH>(op + BPS, r);
+            store_sample<DEPTH, VERIFY>(A, op, l);
+            if (ech == 2) store_sample<DEPTH, VERIFY>(A, op + BPS, r);
         }
         __syncthreads();
     }
     }
 }
 
-template <int DEPTH>
+template <int DEPTH, bool VERIFY>
 static void launch_unmix_depth(const DecodeArgs &da, hipStream_t st)
 {
     dim3 grid((da.numPackets + 63) / 64, (da.frameSize + 63) / 64);
@@ -433,9 +434,9 @@ static void launch_unmix_depth(const DecodeArgs &da, hipStream_t st)
     // two channels may arrive as one CPE or as two SCE / LFE elements (codec/ALACDecoder.cu:622-756): the per-element
     // kernel follows the records, k_decode_unmix<., 2> would take the packet for one pair
     if (da.numChannels >= 2)
-        hipLaunchKernelGGL((k_decode_unmix_mc<DEPTH>), grid, dim3(256), 0, st, da);
+        hipLaunchKernelGGL((k_decode_unmix_mc<DEPTH, VERIFY>), grid, dim3(256), 0, st, da);
     else
-        hipLaunchKernelGGL((k_decode_unmix<DEPTH, 1>), grid, dim3(256), 0, st, da);
+        hipLaunchKernelGGL((k_decode_unmix<DEPTH, 1, VERIFY>), grid, dim3(256), 0, st, da);
 }
 
 hipError_t launch_decode(const DecodeArgs &da, hipStream_t st)
@@ -444,11 +445,16 @@ hipError_t launch_decode(const DecodeArgs &da, hipStream_t st)
     hipLaunchKernelGGL(k_decode_entropy, dim3((da.numPackets + 63) / 64), dim3(64), 0, st, da);
     const uint64_t lanes = (uint64_t)da.numPackets * da.numChannels;
     hipLaunchKernelGGL(k_decode_unpc, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, st, da);
-    switch (da.bitDepth) {
-    case 16: launch_unmix_depth<16>(da, st); break;
-    case 20: launch_unmix_depth<20>(da, st); break;
-    case 24: launch_unmix_depth<24>(da, st); break;
-    case 32: launch_unmix_depth<32>(da, st); break;
+    // verify mode (alac_hip_verify): the un-mix instantiations whose store sites compare instead (alac_verify.hpp)
+    switch (da.bitDepth * 2 + (da.firstMismatch ? 1 : 0)) {
+    case 32: launch_unmix_depth<16, false>(da, st); break;
+    case 40: launch_unmix_depth<20, false>(da, st); break;
+    case 48: launch_unmix_depth<24, false>(da, st); break;
+    case 64: launch_unmix_depth<32, false>(da, st); break;
+    case 33: launch_unmix_depth<16, true>(da, st); break;
+    case 41: launch_unmix_depth<20, true>(da, st); break;
+    case 49: launch_unmix_depth<24, true>(da, st); break;
+    case 65: launch_unmix_depth<32, true>(da, st); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -28,6 +28,7 @@
 #include "alac_kernels.hpp"
 #include "alac_unpc.hpp"
 #include "alac_lms.hpp"
+#include "alac_verify.hpp"
 
 namespace alacdev {
 
@@ -499,7 +500,7 @@ __global__ __launch_bounds__(64 * kHdrWaves) void k_dec_header(DecV1Args V)
 
 // ---- k_dec_raw: uncompressed (escape) elements are fixed-width fields, i.e. not serial at all: one thread per
 // sample-frame reads its fields straight from the staged words (codec/ALACDecoder.cu:697-727 / :856-896)
-template <bool DIRECT>
+template <bool DIRECT, bool VERIFY>
 __device__ __forceinline__ void raw_body(const DecV1Args &V, uint32_t p, uint32_t first, uint32_t step)
 {
     const DecodeArgs &A = V.d;
@@ -547,7 +548,7 @@ __device__ __forceinline__ void raw_body(const DecV1Args &V, uint32_t p, uint32_
                 o[k] = (v >> 16) | (v << 16);
             }
             const U4 t4 = {o[0], o[1], o[2], o[3]};
-            *(U4 *)(pcm + 4 * (uint64_t)g) = t4;
+            PCM_PUT(VERIFY, A, (U4 *)(pcm + 4 * (uint64_t)g), t4);
         }
         done = safe * 4;
     }
@@ -578,7 +579,7 @@ __device__ __forceinline__ void raw_body(const DecV1Args &V, uint32_t p, uint32_
                     if (!direct) (rowU + c * A.frameSize)[j] = (int32_t)(v << (32 - w)) >> (32 - w);
                 }
             }
-            if (direct && j < n) pcm[j] = f[0] | (f[1] << 16);
+            if (direct && j < n) PCM_PUT(VERIFY, A, pcm + j, f[0] | (f[1] << 16));
         }
     }
 }
@@ -590,14 +591,15 @@ __device__ __host__ inline uint32_t blocks_per_packet(uint32_t frameSize) { retu
 // packet (times the blocks of a frame) spent the launch on workgroups that read one record and left — 1.23 ms for
 // 500 000 workgroups at 125 000 packets, 15 600 of them with work.
 // (round 3: the packets come from k_dec_header's list of uncompressed elements, so nobody reads records to find them)
+template <bool VERIFY>
 __global__ __launch_bounds__(256) void k_dec_raw(DecV1Args V)
 {
     const DecLists L = dec_lists(V);
     const uint32_t count = L.cnt[4];
     if (V.raw) {  // wave-uniform
-        for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) raw_body<true>(V, L.raw[i], threadIdx.x, blockDim.x);
+        for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) raw_body<true, VERIFY>(V, L.raw[i], threadIdx.x, blockDim.x);
     } else {
-        for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) raw_body<false>(V, L.raw[i], threadIdx.x, blockDim.x);
+        for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) raw_body<false, VERIFY>(V, L.raw[i], threadIdx.x, blockDim.x);
     }
 }
 
@@ -1522,7 +1524,7 @@ __device__ __forceinline__ int32_t lms_step_dec_pair(int32_t (&a)[T], int32_t (&
     return out;
 }
 
-template <int T, int DEPTH = 16>
+template <int T, int DEPTH = 16, bool VERIFY = false>
 __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t block, uint32_t count)
 {
     const DecodeArgs &A = V.d;
@@ -1610,7 +1612,7 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
 #pragma unroll
                 for (int q = 0; q < 3 * K / 16; q++) {
                     const U4s t4 = {d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]};
-                    *(U4s *)(dst + 16 * q) = t4;
+                    PCM_PUT(VERIFY, A, (U4s *)(dst + 16 * q), t4);
                 }
             } else if (active) {
                 // the last frames of a short packet
@@ -1620,9 +1622,9 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
 #pragma unroll
                         for (int c2 = 0; c2 < 2; c2++) {
                             const uint32_t v3 = fld[2 * k + c2];
-                            dst[6 * k + 3 * c2] = (uint8_t)v3;
-                            dst[6 * k + 3 * c2 + 1] = (uint8_t)(v3 >> 8);
-                            dst[6 * k + 3 * c2 + 2] = (uint8_t)(v3 >> 16);
+                            PCM_PUT(VERIFY, A, dst + 6 * k + 3 * c2, (uint8_t)v3);
+                            PCM_PUT(VERIFY, A, dst + 6 * k + 3 * c2 + 1, (uint8_t)(v3 >> 8));
+                            PCM_PUT(VERIFY, A, dst + 6 * k + 3 * c2 + 2, (uint8_t)(v3 >> 16));
                         }
                     }
                 }
@@ -1646,11 +1648,11 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
             const uint32_t f = f0 + 4 * q;
             if (active && f + 4 <= n) {
                 const U4 t4 = {word[4 * q], word[4 * q + 1], word[4 * q + 2], word[4 * q + 3]};
-                *(U4 *)(pcm + f) = t4;
+                PCM_PUT(VERIFY, A, (U4 *)(pcm + f), t4);
             } else if (active && f < n) {
 #pragma unroll
                 for (int e = 0; e < 4; e++)
-                    if (f + e < n) pcm[f + e] = word[4 * q + e];
+                    if (f + e < n) PCM_PUT(VERIFY, A, pcm + f + e, word[4 * q + e]);
             }
         }
     };
@@ -1726,18 +1728,18 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
 // Four waves to a workgroup (one per SIMD of its CU), consecutive roles: see k_dec_entropy_wide.
 // DEPTH: what the pairs write (16: one word per frame; 20 / 24: six bytes per frame) — one instantiation per output format,
 // so that a launch carries four loop bodies, not eight (they share the CU's instruction cache)
-template <int DEPTH>
+template <int DEPTH, bool VERIFY>
 __global__ __launch_bounds__(64 * kEntWavesPerWg) void k_dec_unpc_wide(DecV1Args V)
 {
     const uint32_t *cnt = dec_lists(V).cnt;
     const uint32_t c4 = cnt[0], c8 = cnt[1], pA = cnt[2], pB = cnt[3], cAny = cnt[6];
     const uint32_t nbB = (pB + 31u) / 32u, nb8 = (c8 + 63u) / 64u, nbA = (pA + 31u) / 32u, nb4 = (c4 + 63u) / 64u;
     uint32_t b = blockIdx.x * (uint32_t)kEntWavesPerWg + (threadIdx.x >> 6);
-    if (b < nbB) return unpc_pair_body<8, DEPTH>(V, b, pB);
+    if (b < nbB) return unpc_pair_body<8, DEPTH, VERIFY>(V, b, pB);
     b -= nbB;
     if (b < nb8) return unpc_wide_body<8>(V, b, c8);
     b -= nb8;
-    if (b < nbA) return unpc_pair_body<4, DEPTH>(V, b, pA);
+    if (b < nbA) return unpc_pair_body<4, DEPTH, VERIFY>(V, b, pA);
     b -= nbA;
     if (b < nb4) return unpc_wide_body<4>(V, b, c4);
     b -= nb4;
@@ -1752,6 +1754,7 @@ __global__ __launch_bounds__(64 * kEntWavesPerWg) void k_dec_unpc_wide(DecV1Args
 // ~10 us, sixteen times per packet; removed in round 4.)  Workgroups >= nEnt: one wave per packet for the uncompressed
 // elements (nobody waits for them; their dispatch hides under the entropy chain instead of costing a launch of its own).
 constexpr int kFusedPpw = 48;
+template <bool VERIFY>
 __global__ __launch_bounds__(256, 1) void k_dec_fused_wg(DecV1Args V, uint32_t nEnt)
 {
     __shared__ uint32_t ringOne[64 * kWinStride];
@@ -1766,7 +1769,7 @@ __global__ __launch_bounds__(256, 1) void k_dec_fused_wg(DecV1Args V, uint32_t n
             unpc_fast_body<true, kFusedPpw>(V, blockIdx.x * 3u + (slot - 1), progLds);
     } else {
         const uint32_t p = (blockIdx.x - nEnt) * 4u + slot;
-        if (p < V.d.numPackets) raw_body<false>(V, p, threadIdx.x & 63, 64);
+        if (p < V.d.numPackets) raw_body<false, VERIFY>(V, p, threadIdx.x & 63, 64);
     }
 }
 
@@ -1789,22 +1792,22 @@ __global__ __launch_bounds__(64) void k_dec_unpc(DecV1Args V)
 }
 
 // ---- un-mix + pack (gpu_unmixNN / gpu_copyPredictorToNN, codec/ALACDecoder.cu:193-495) ----
-template <int DEPTH>
-__device__ __forceinline__ void put_sample(uint8_t *q, int32_t x)
+template <int DEPTH, bool VERIFY>
+__device__ __forceinline__ void put_sample(const DecodeArgs &A, uint8_t *q, int32_t x)
 {
     if constexpr (DEPTH == 16) {
-        *(int16_t *)q = (int16_t)x;
+        PCM_PUT(VERIFY, A, (int16_t *)q, (int16_t)x);
     } else if constexpr (DEPTH == 32) {
-        *(int32_t *)q = x;
+        PCM_PUT(VERIFY, A, (int32_t *)q, x);
     } else {
         if constexpr (DEPTH == 20) x = (int32_t)((uint32_t)x << 4);
-        q[0] = (uint8_t)x;
-        q[1] = (uint8_t)(x >> 8);
-        q[2] = (uint8_t)(x >> 16);
+        PCM_PUT(VERIFY, A, q, (uint8_t)x);
+        PCM_PUT(VERIFY, A, q + 1, (uint8_t)(x >> 8));
+        PCM_PUT(VERIFY, A, q + 2, (uint8_t)(x >> 16));
     }
 }
 
-template <int DEPTH, int CH>
+template <int DEPTH, int CH, bool VERIFY>
 __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint32_t part, uint32_t bx)
 {
     const DecodeArgs &A = V.d;
@@ -1843,7 +1846,7 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
                     }
                     o[k] = ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16);
                 }
-                *(U4 *)(out + (uint64_t)j * 4) = o;
+                PCM_PUT(VERIFY, A, (U4 *)(out + (uint64_t)j * 4), o);
             }
             // the last n mod 4 frames of a short packet
             for (uint32_t j = n4 + part * blockDim.x + threadIdx.x; j < n; j += bx * blockDim.x) {
@@ -1856,7 +1859,7 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
                     l = uu;
                     r = vv;
                 }
-                *(uint32_t *)(out + (uint64_t)j * 4) = ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16);
+                PCM_PUT(VERIFY, A, (uint32_t *)(out + (uint64_t)j * 4), ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16));
             }
             return;
         }
@@ -1918,12 +1921,12 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
                     const uint32_t d0 = a0 | (a1 << 24), d1 = (a1 >> 8) | (a2 << 16), d2 = (a2 >> 16) | (a3 << 8);
                     if (h == 0) {
                         const U2 t0 = {d0, d1};
-                        q[0] = t0;
+                        PCM_PUT(VERIFY, A, q, t0);
                         s[0] = d2;  // first half of the middle store
                     } else {
                         const U2 t1 = {s[0], d0}, t2 = {d1, d2};
-                        q[1] = t1;
-                        q[2] = t2;
+                        PCM_PUT(VERIFY, A, q + 1, t1);
+                        PCM_PUT(VERIFY, A, q + 2, t2);
                     }
                 }
             }
@@ -1953,10 +1956,10 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
         }
         uint8_t *q = out + (uint64_t)j * och * BPS;
         if (DEPTH == 16 && CH == 2 && och == 2) {
-            *(uint32_t *)q = ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16);
+            PCM_PUT(VERIFY, A, (uint32_t *)q, ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16));
         } else {
-            put_sample<DEPTH>(q, l);
-            if constexpr (CH == 2) put_sample<DEPTH>(q + BPS, r);
+            put_sample<DEPTH, VERIFY>(A, q, l);
+            if constexpr (CH == 2) put_sample<DEPTH, VERIFY>(A, q + BPS, r);
         }
     }
 }
@@ -1964,28 +1967,28 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
 // Fused launch: workgroup = (packet, part of the frame).  Separate launches: the workgroups walk k_dec_header's list of the
 // packets nobody else writes (with pairs and direct uncompressed elements that is none of the benchmark's packets; launching
 // a workgroup per packet just to read a record and leave cost 0.5 ms at 125 000 packets).
-template <int DEPTH, int CH>
+template <int DEPTH, int CH, bool VERIFY>
 __global__ __launch_bounds__(256) void k_dec_unmix(DecV1Args V)
 {
     const uint32_t bx = blocks_per_packet(V.d.frameSize);
     if (!V.lists) {
-        unmix_part<DEPTH, CH>(V, blockIdx.x / bx, blockIdx.x % bx, bx);
+        unmix_part<DEPTH, CH, VERIFY>(V, blockIdx.x / bx, blockIdx.x % bx, bx);
         return;
     }
     const DecLists L = dec_lists(V);
     const uint64_t work = (uint64_t)L.cnt[5] * bx;
-    for (uint64_t i = blockIdx.x; i < work; i += gridDim.x) unmix_part<DEPTH, CH>(V, L.rest[i / bx], (uint32_t)(i % bx), bx);
+    for (uint64_t i = blockIdx.x; i < work; i += gridDim.x) unmix_part<DEPTH, CH, VERIFY>(V, L.rest[i / bx], (uint32_t)(i % bx), bx);
 }
 
-template <int DEPTH>
+template <int DEPTH, bool VERIFY>
 static void launch_unmix_v1(const DecV1Args &V, hipStream_t st)
 {
     const uint64_t all = (uint64_t)blocks_per_packet(V.d.frameSize) * V.d.numPackets;
     dim3 grid((uint32_t)(V.lists && all > 8192 ? 8192 : all));
     if (V.d.numChannels == 2)
-        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 2>), grid, dim3(256), 0, st, V);
+        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 2, VERIFY>), grid, dim3(256), 0, st, V);
     else
-        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 1>), grid, dim3(256), 0, st, V);
+        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 1, VERIFY>), grid, dim3(256), 0, st, V);
 }
 
 // everything after the staging of the stream: one pass of the pipeline over the elements V describes
@@ -2065,11 +2068,17 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, const DecS
     // 34 000 2.84 / 2.88, 125 000 17.6 (round 1) / 5.3.  Option dec_fused (ALAC_HIP_DEC_FUSED) = 0 / 1 forces.
     const int forced = V.d.optFused;
     const bool fused = forced >= 0 ? forced != 0 : dec_fused_auto(da.numPackets, da.numChannels);
+    // verify mode (alac_hip_verify): the same launches, with the instantiations whose PCM store sites compare instead
+    const bool verify = da.firstMismatch != nullptr;
     if (fused) {
         const uint32_t nEntWg = (da.numPackets + kFusedPpw - 1) / kFusedPpw;
-        hipLaunchKernelGGL(k_dec_fused_wg, dim3(nEntWg + (da.numPackets + 3) / 4), dim3(256), 0, st, V, nEntWg);
+        const dim3 grid(nEntWg + (da.numPackets + 3) / 4);
+        if (verify) hipLaunchKernelGGL(k_dec_fused_wg<true>, grid, dim3(256), 0, st, V, nEntWg);
+        else hipLaunchKernelGGL(k_dec_fused_wg<false>, grid, dim3(256), 0, st, V, nEntWg);
     } else {
-        hipLaunchKernelGGL(k_dec_raw, dim3(da.numPackets < 4096u ? da.numPackets : 4096u), dim3(256), 0, st, V);
+        const dim3 rgrid(da.numPackets < 4096u ? da.numPackets : 4096u);
+        if (verify) hipLaunchKernelGGL(k_dec_raw<true>, rgrid, dim3(256), 0, st, V);
+        else hipLaunchKernelGGL(k_dec_raw<false>, rgrid, dim3(256), 0, st, V);
         // deferred residual stores, four 16-byte stores per round of sixteen consecutive residuals (round 2, 4-byte stores:
         // paid only up to two entropy waves per SIMD; with the wide stores, measured whole decode pass at 125 000 / 250 000 /
         // 500 000 packets: 9.31 -> 8.19, 19.4 -> 14.2, 38.1 -> 26.5 ms — the kernel was bound by the number of store
@@ -2081,16 +2090,26 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, const DecS
         // chains sorted by tap count, one lane per chain
         // (five lists, each rounded up to whole waves)
         const dim3 ugrid(((uint32_t)((lanes + 63) / 64) + 6 + kEntWavesPerWg - 1) / kEntWavesPerWg), ublock(64 * kEntWavesPerWg);
-        if (da.bitDepth == 24) hipLaunchKernelGGL(k_dec_unpc_wide<24>, ugrid, ublock, 0, st, V);
-        else if (da.bitDepth == 20) hipLaunchKernelGGL(k_dec_unpc_wide<20>, ugrid, ublock, 0, st, V);
-        else hipLaunchKernelGGL(k_dec_unpc_wide<16>, ugrid, ublock, 0, st, V);
+        if (verify) {
+            if (da.bitDepth == 24) hipLaunchKernelGGL((k_dec_unpc_wide<24, true>), ugrid, ublock, 0, st, V);
+            else if (da.bitDepth == 20) hipLaunchKernelGGL((k_dec_unpc_wide<20, true>), ugrid, ublock, 0, st, V);
+            else hipLaunchKernelGGL((k_dec_unpc_wide<16, true>), ugrid, ublock, 0, st, V);
+        } else {
+            if (da.bitDepth == 24) hipLaunchKernelGGL((k_dec_unpc_wide<24, false>), ugrid, ublock, 0, st, V);
+            else if (da.bitDepth == 20) hipLaunchKernelGGL((k_dec_unpc_wide<20, false>), ugrid, ublock, 0, st, V);
+            else hipLaunchKernelGGL((k_dec_unpc_wide<16, false>), ugrid, ublock, 0, st, V);
+        }
     }
     hipLaunchKernelGGL(k_dec_unpc, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, st, V);
-    switch (da.bitDepth) {
-    case 16: launch_unmix_v1<16>(V, st); break;
-    case 20: launch_unmix_v1<20>(V, st); break;
-    case 24: launch_unmix_v1<24>(V, st); break;
-    case 32: launch_unmix_v1<32>(V, st); break;
+    switch (da.bitDepth * 2 + (verify ? 1 : 0)) {
+    case 32: launch_unmix_v1<16, false>(V, st); break;
+    case 40: launch_unmix_v1<20, false>(V, st); break;
+    case 48: launch_unmix_v1<24, false>(V, st); break;
+    case 64: launch_unmix_v1<32, false>(V, st); break;
+    case 33: launch_unmix_v1<16, true>(V, st); break;
+    case 41: launch_unmix_v1<20, true>(V, st); break;
+    case 49: launch_unmix_v1<24, true>(V, st); break;
+    case 65: launch_unmix_v1<32, true>(V, st); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

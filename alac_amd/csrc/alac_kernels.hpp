@@ -211,12 +211,22 @@ struct DecodeArgs {
     HandoffCtl ho;
     int32_t optFused = -1, optPair = 1, optDirect = 1;  // AlacOptions::decFused / decPair / decDirect (host-side launch choices)
     int32_t *resid;  // [ch][frameSize][numPackets] residuals, then samples, in place
-    uint8_t *pcmOut;
+    uint8_t *pcmOut;  // verify mode: the caller's EXPECTED PCM, only ever read (alac_verify.hpp)
     uint32_t *numSamplesOut;
     int32_t *statusOut;
+    // verify mode (alac_hip_verify) when non-null: [numPackets] lowest sample-frame whose bytes differ, lowered with atomicMin
+    // by every store site of the PCM (pcm_put, alac_verify.hpp), which loads and compares instead of storing
+    uint32_t *firstMismatch = nullptr;
+    uint32_t frameBytes = 0;  // verify mode: bytes of one whole output frame (all channels)
 };
 
 hipError_t launch_decode(const DecodeArgs &da, hipStream_t st);
+// verify mode (alac_verify.hip): firstMismatch[p] = ~0, *bad = 0 in front of the decode; after it, packets of non-zero status
+// get 0, packets whose decoded frame count differs from the expected one min(decoded, expected), and *bad counts the packets
+// left with a mismatch (numSamplesExpected null = every packet frameSize frames)
+hipError_t launch_verify_init(uint32_t *firstMismatch, uint32_t numPackets, uint32_t *bad, hipStream_t st);
+hipError_t launch_verify_finish(const int32_t *status, const uint32_t *numSamplesDecoded, const uint32_t *numSamplesExpected,
+                                uint32_t frameSize, uint32_t numPackets, uint32_t *firstMismatch, uint32_t *bad, hipStream_t st);
 // second generation (alac_decode_v1.hip): `words` = capWords uint32 of scratch for the re-staged stream, `plane` =
 // numPackets * numChannels * frameSize int32, `prog` = 2 * numPackets + 2 uint32 (progress words of the fused launch;
 // chain list and its two counters where the stages are separate launches)

@@ -23,6 +23,12 @@
  *   --devices N                               with --batch: the files are dealt round-robin to N GPUs, one context and
  *                                             one host thread per device (replicas: independent files need no exchange
  *                                             between the GPUs, so there is no RCCL here); outputs are unchanged
+ *   --verify                                  encode only: decode every encoded group on its own device and compare it with
+ *                                             the PCM it was encoded from (alac_hip_verify) before any file is written; on
+ *                                             a mismatch name the file, packet and frame, write nothing, exit 1.  The
+ *                                             output bytes are those of the same command without --verify
+ *   --compare <in.caf|in.m4a> <reference.wav> decode an ALAC file and compare it with a WAV / PCM CAF on the GPU, writing
+ *                                             nothing: exit 0 if every frame matches, 1 otherwise (or on an error)
  *
  * A single chained file is serial by construction: one file runs as one chain of dependent
  * packets; the GPU pays off with --batch or --segment-packets.
@@ -68,6 +74,8 @@ void usage()
     printf("        alacconvert --segment-packets K <input wav or caf file> <output caf file>\n");
     printf("        alacconvert --batch --devices N <in1> <out1> [<in2> <out2> ...]\n");
     printf("        alacconvert --lpc [--batch] <input wav or caf file> <output caf or m4a file> ...\n");
+    printf("        alacconvert --verify [--batch] [--lpc] ... <input wav or caf file> <output caf or m4a file> ...\n");
+    printf("        alacconvert --compare <input caf or m4a file> <reference wav or caf file>\n");
     printf("\n");
 }
 
@@ -87,7 +95,46 @@ AudioFormatDescription alac_format(const InputInfo &in)
 }
 
 // ---- encode: all jobs share bit depth and channel count; each file is one segment ----
-bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, int device)
+// --verify: decode the group's stream on `device` and compare it with the PCM it was encoded from; names the first bad
+// packet of every file that fails
+bool verify_group(std::vector<Job *> &jobs, ALACEncoder &enc, const std::vector<uint32_t> &firstPacket, const Bytes &pcm,
+                  const std::vector<uint32_t> &numSamples, const Bytes &stream, const std::vector<uint32_t> &sizes, int device)
+{
+    const uint32_t np = (uint32_t)sizes.size();
+    if (np == 0) return true;
+    uint32_t cookieSize = enc.GetMagicCookieSize(jobs[0]->info.channels);
+    Bytes cookie(cookieSize, 0);
+    enc.GetMagicCookie(cookie.data(), &cookieSize);
+    ALACDecoder dec;
+    if (device >= 0) dec.SetDevice(device);
+    if (dec.Init(cookie.data(), cookieSize, 0) != ALAC_noErr) {
+        fprintf(stderr, " Cannot initialise the decoder for --verify\n");
+        return false;
+    }
+    std::vector<uint32_t> firstMismatch(np, 0);
+    std::vector<int32_t> status(np, 0);
+    uint32_t bad = 0;
+    const int32_t rc = dec.VerifyBatch(stream.data(), sizes.data(), np, pcm.data(), numSamples.data(), firstMismatch.data(),
+                                       status.data(), &bad);
+    if (rc != ALAC_noErr) {
+        fprintf(stderr, " Verification failed to run (status %d)\n", rc);
+        return false;
+    }
+    if (bad == 0) return true;
+    for (size_t j = 0; j < jobs.size(); j++) {
+        const uint32_t p0 = firstPacket[j], p1 = j + 1 < jobs.size() ? firstPacket[j + 1] : np;
+        for (uint32_t p = p0; p < p1; p++) {
+            if (firstMismatch[p] != 0xffffffffu) {
+                fprintf(stderr, " Verify failed: \"%s\" -> \"%s\": packet %u, frame %u (status %d)\n", jobs[j]->in.c_str(),
+                        jobs[j]->out.c_str(), p - p0, firstMismatch[p], status[p]);
+                break;
+            }
+        }
+    }
+    return false;
+}
+
+bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, bool verify, int device)
 {
     const InputInfo &first = jobs[0]->info;
     const uint32_t bps = (first.bitsPerChannel + 7) >> 3, ch = first.channels;  // 20 bits: 3-byte containers (container.cpp)
@@ -143,6 +190,7 @@ bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, i
             fprintf(stderr, " Encoding failed (status %d)\n", rc);
             return false;
         }
+        if (verify && !verify_group(jobs, enc, firstPacket, pcm, numSamples, stream, sizes, device)) return false;
     }
     // per file: cookie + container
     std::vector<uint64_t> offs(np + 1, 0);
@@ -172,6 +220,104 @@ bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, i
     return true;
 }
 
+// the packets of an ALAC file back to back
+void append_packets(const Job &J, const alacfile::AlacCafContents &c, Bytes &stream, std::vector<uint32_t> &sizes)
+{
+    uint64_t pos = c.dataPos;
+    for (size_t p = 0; p < c.packetBytes.size(); p++) {
+        const uint32_t sz = c.packetBytes[p];
+        if (!c.packetPos.empty()) pos = c.packetPos[p];  // M4A: chunks need not be contiguous
+        stream.insert(stream.end(), J.file.begin() + pos, J.file.begin() + pos + sz);
+        sizes.push_back(sz);
+        pos += sz;
+    }
+}
+
+// ---- --compare <alac file> <reference pcm file>: decode and compare on the GPU, write nothing; 0 = identical ----
+int compare_files(const std::string &alacPath, const std::string &refPath)
+{
+    Job A, R;
+    A.in = alacPath;
+    R.in = refPath;
+    for (Job *J : {&A, &R}) {
+        if (!alacfile::read_file(J->in, J->file)) {
+            fprintf(stderr, " Cannot open file \"%s\"\n", J->in.c_str());
+            return 1;
+        }
+        const std::string err = alacfile::sniff_input(J->file, J->info);
+        if (!err.empty()) {
+            fprintf(stderr, " %s: \"%s\"\n", err.c_str(), J->in.c_str());
+            return 1;
+        }
+    }
+    if (!A.info.isAlac || R.info.isAlac) {
+        fprintf(stderr, " --compare takes an ALAC file (CAF or M4A) and a PCM reference (WAV or CAF)\n");
+        return 1;
+    }
+    alacfile::AlacCafContents c;
+    InputInfo again;
+    const std::string err = A.info.kind == alacfile::kM4aFile ? alacfile::parse_alac_m4a(A.file, again, c)
+                                                              : alacfile::parse_alac_caf(A.file, A.info, c);
+    if (!err.empty()) {
+        fprintf(stderr, " %s: \"%s\"\n", err.c_str(), A.in.c_str());
+        return 1;
+    }
+    ALACDecoder dec;
+    Bytes cookie(c.cookie);
+    if (dec.Init(cookie.data(), (uint32_t)cookie.size(), 0) != ALAC_noErr) {
+        fprintf(stderr, " Cannot initialise the decoder from the magic cookie\n");
+        return 1;
+    }
+    const uint32_t ch = dec.mConfig.numChannels, bits = dec.mConfig.bitDepth, frame = dec.mConfig.frameLength;
+    if (ch != R.info.channels || bits != R.info.bitsPerChannel) {
+        printf("Compare: \"%s\" is %u-bit %u-channel, \"%s\" %u-bit %u-channel: different\n", A.in.c_str(), bits, ch,
+               R.in.c_str(), R.info.bitsPerChannel, R.info.channels);
+        return 1;
+    }
+    const uint64_t bytesPerFrame = (uint64_t)ch * ((bits + 7) >> 3), packetBytes = bytesPerFrame * frame;
+    std::vector<uint32_t> sizes;
+    Bytes stream;
+    append_packets(A, c, stream, sizes);
+    const uint32_t np = (uint32_t)sizes.size();
+    // the reference cut into packets as the encoder cuts it: full packets, then one partial packet
+    const uint64_t refFrames = R.info.dataSize / bytesPerFrame;
+    const uint64_t refPackets = (refFrames + frame - 1) / frame;
+    Bytes pcm((size_t)np * packetBytes, 0);
+    std::vector<uint32_t> expected(np, 0);
+    for (uint32_t p = 0; p < np && p < refPackets; p++) {
+        const uint64_t f0 = (uint64_t)p * frame, n = refFrames - f0 < frame ? refFrames - f0 : frame;
+        expected[p] = (uint32_t)n;
+        memcpy(pcm.data() + (size_t)p * packetBytes, R.file.data() + R.info.dataPos + f0 * bytesPerFrame, (size_t)(n * bytesPerFrame));
+        if (R.info.bigEndianPcm)
+            alacfile::swap_samples_in_place(pcm.data() + (size_t)p * packetBytes, n * bytesPerFrame, R.info.bitsPerChannel);
+    }
+    std::vector<uint32_t> firstMismatch(np, 0);
+    std::vector<int32_t> status(np, 0);
+    uint32_t bad = 0;
+    if (np) {
+        const int32_t rc = dec.VerifyBatch(stream.data(), sizes.data(), np, pcm.data(), expected.data(), firstMismatch.data(),
+                                           status.data(), &bad);
+        if (rc != ALAC_noErr) {
+            fprintf(stderr, " Verification failed to run (status %d)\n", rc);
+            return 1;
+        }
+    }
+    for (uint32_t p = 0; p < np && bad; p++) {
+        if (firstMismatch[p] != 0xffffffffu) {
+            printf("Compare: \"%s\" differs from \"%s\" at packet %u, frame %u (sample-frame %llu, status %d)\n", A.in.c_str(),
+                   R.in.c_str(), p, firstMismatch[p], (unsigned long long)((uint64_t)p * frame + firstMismatch[p]), status[p]);
+            return 1;
+        }
+    }
+    if (refPackets != np) {
+        printf("Compare: \"%s\" has %u packets, \"%s\" makes %llu\n", A.in.c_str(), np, R.in.c_str(),
+               (unsigned long long)refPackets);
+        return 1;
+    }
+    printf("Compare: \"%s\" matches \"%s\" (%u packets)\n", A.in.c_str(), R.in.c_str(), np);
+    return 0;
+}
+
 // ---- decode: jobs with identical cookies decode in one batch ----
 bool decode_group(std::vector<Job *> &jobs, const std::vector<alacfile::AlacCafContents> &contents, int device)
 {
@@ -197,14 +343,7 @@ bool decode_group(std::vector<Job *> &jobs, const std::vector<alacfile::AlacCafC
     Bytes stream;
     for (size_t j = 0; j < jobs.size(); j++) {
         firstPacket.push_back((uint32_t)sizes.size());
-        uint64_t pos = contents[j].dataPos;
-        for (size_t p = 0; p < contents[j].packetBytes.size(); p++) {
-            const uint32_t sz = contents[j].packetBytes[p];
-            if (!contents[j].packetPos.empty()) pos = contents[j].packetPos[p];  // M4A: chunks need not be contiguous
-            stream.insert(stream.end(), jobs[j]->file.begin() + pos, jobs[j]->file.begin() + pos + sz);
-            sizes.push_back(sz);
-            pos += sz;
-        }
+        append_packets(*jobs[j], contents[j], stream, sizes);
     }
     const uint32_t np = (uint32_t)sizes.size();
     Bytes pcm((size_t)np * frame * bytesPerFrame);
@@ -244,7 +383,7 @@ bool decode_group(std::vector<Job *> &jobs, const std::vector<alacfile::AlacCafC
 int main(int argc, char *argv[])
 {
     std::vector<std::string> files;
-    bool batch = false, lpc = false, malformed = argc < 2;
+    bool batch = false, lpc = false, verify = false, compare = false, malformed = argc < 2;
     uint32_t segmentPackets = 0, devices = 0;
     for (int i = 1; i < argc && !malformed; i++) {
         const std::string a = argv[i];
@@ -254,6 +393,10 @@ int main(int argc, char *argv[])
             batch = true;
         } else if (a == "--lpc") {
             lpc = true;
+        } else if (a == "--verify") {
+            verify = true;
+        } else if (a == "--compare") {
+            compare = true;
         } else if (a == "--segment-packets" && i + 1 < argc) {
             segmentPackets = (uint32_t)strtoul(argv[++i], nullptr, 10);
             if (segmentPackets == 0) malformed = true;
@@ -269,10 +412,13 @@ int main(int argc, char *argv[])
     }
     if (!malformed && (files.size() < 2 || (files.size() & 1) || (!batch && files.size() != 2))) malformed = true;
     if (!malformed && devices && !batch) malformed = true;  // one file is one serial chain: nothing to deal out
+    // --compare stands alone: two files, no other option
+    if (!malformed && compare && (batch || lpc || verify || segmentPackets || devices)) malformed = true;
     if (malformed) {
         usage();
         return 1;
     }
+    if (compare) return compare_files(files[0], files[1]);
 
     std::vector<Job> jobs(files.size() / 2);
     for (size_t j = 0; j < jobs.size(); j++) {
@@ -370,7 +516,7 @@ int main(int argc, char *argv[])
         const int device = firstDevice < 0 ? -1 : (int)(k % (uint32_t)visible);
         for (size_t i = 0; i < perWorker[k].size() && ok[k]; i++) {
             Work &w = perWorker[k][i];
-            ok[k] = w.decode ? decode_group(w.jobs, w.contents, device) : encode_group(w.jobs, segmentPackets, lpc, device);
+            ok[k] = w.decode ? decode_group(w.jobs, w.contents, device) : encode_group(w.jobs, segmentPackets, lpc, verify, device);
         }
     };
     if (workers == 1) {

@@ -37,6 +37,13 @@ public:
     /* batch extension (host buffers) */
     int32_t DecodeBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets, uint8_t *pcmOut,
                         uint32_t *numSamplesOut, int32_t *statusOut);
+    /* batch extension (host buffers): decode on the device and compare with pcmExpected (the layout DecodeBatch writes)
+     * without writing PCM anywhere (alac_hip_verify_host).  firstMismatchOut[p] = lowest differing sample-frame of packet p,
+     * 0xFFFFFFFF if it matches; statusOut as DecodeBatch; numSamplesExpected NULL = every packet full; badPacketsOut may be
+     * NULL.  Returns ALAC_noErr or a parameter / HIP error — a mismatch is not an error. */
+    int32_t VerifyBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets, const uint8_t *pcmExpected,
+                        const uint32_t *numSamplesExpected, uint32_t *firstMismatchOut, int32_t *statusOut,
+                        uint32_t *badPacketsOut = nullptr);
 
     int32_t LastStatus() const { return mLastStatus; }
 

@@ -219,6 +219,46 @@ int32_t alac_hip_decode(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t coo
                         uint32_t num_packets, void *d_workspace, uint64_t workspace_bytes,
                         uint8_t *d_pcm_out, uint32_t *d_num_samples_out, int32_t *d_status);
 
+/* ---- batch verify: decode and compare with the PCM the stream was encoded from, on the device ----------------------
+ * What a caller of ALACDecoder::Decode (codec/ALACDecoder.cu:571-1002) does by hand before trusting an encode — decode, then
+ * compare the output of fillWriteBuffer (:497-563) with the source — without writing the decoded PCM anywhere: every kernel
+ * that stores PCM in alac_hip_decode loads the expected bytes at that place instead, with a load as wide as the store, and
+ * compares.  That holds on every decoder path (fused and separate launches, pair lanes, direct reads, uncompressed packets,
+ * the per-element rounds of 3..8 channels, the lane decoder and its fallback for other element sequences), so the answer is
+ * the one "alac_hip_decode, then compare on the host" gives, and the workspace has no PCM plane.  No reference counterpart.
+ *
+ * Bytes of device scratch alac_hip_verify needs (stream_bytes as in alac_hip_decode_workspace_bytes_stream, 0 = every
+ * packet at its largest regular size). */
+uint64_t alac_hip_verify_workspace_bytes_stream(const alac_hip_format *fmt, uint32_t num_packets, uint64_t stream_bytes);
+
+/*
+ * Verify num_packets packets against the PCM they should decode to.  Asynchronous like alac_hip_decode, same decoder options.
+ *   h_cookie/size          d_stream, d_packet_offsets: as alac_hip_decode
+ *   d_pcm_expected         the expected PCM in the layout alac_hip_decode writes: packet p at
+ *                          p * frame_size * num_channels * bytes_per_sample, 20-bit samples in 3-byte containers
+ *                          (left-justified, as gpu_unmix20 writes them, codec/ALACDecoder.cu:225-280); dword aligned
+ *   d_num_samples_expected [num_packets] expected sample-frames per packet, or NULL = every packet frame_size frames
+ *   d_workspace            alac_hip_verify_workspace_bytes_stream bytes, 256-byte aligned
+ *   d_first_mismatch       [num_packets] out: the lowest sample-frame index at which any channel differs; 0xFFFFFFFF when the
+ *                          packet decodes with status 0, has the expected frame count and matches every frame.  Frame counts
+ *                          that differ: min(decoded, expected) unless an earlier frame differs.  An undecodable packet: 0.
+ *                          Frames behind a packet's expected count are not compared.
+ *   d_status               [num_packets] out: per-packet status as alac_hip_decode reports it (0 or kALAC_ParamError)
+ *   d_bad_packets          [1] out: the number of packets whose d_first_mismatch is not 0xFFFFFFFF (one word to read back)
+ * The return value reports parameter and HIP errors only: a mismatch is data, not an error.
+ */
+int32_t alac_hip_verify(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
+                        const uint64_t *d_packet_offsets, uint32_t num_packets, const uint8_t *d_pcm_expected,
+                        const uint32_t *d_num_samples_expected, void *d_workspace, uint64_t workspace_bytes,
+                        uint32_t *d_first_mismatch, int32_t *d_status, uint32_t *d_bad_packets);
+
+/* Host-buffer form (synchronous, like alac_hip_decode_host): packets back to back with sizes h_packet_bytes; the expected
+ * PCM packed as above; h_num_samples_expected, h_first_mismatch and h_status may be NULL.  Returns the number of packets that
+ * failed (>= 0), or a negative status for a parameter / HIP error. */
+int32_t alac_hip_verify_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *h_stream,
+                             const uint32_t *h_packet_bytes, uint32_t num_packets, const uint8_t *h_pcm_expected,
+                             const uint32_t *h_num_samples_expected, uint32_t *h_first_mismatch, int32_t *h_status);
+
 /* Parse a magic cookie into a format (host only). */
 int32_t alac_hip_format_from_cookie(const uint8_t *h_cookie, uint32_t cookie_size,
                                     alac_hip_format *out_fmt);
