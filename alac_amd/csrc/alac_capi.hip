@@ -4,6 +4,7 @@
 #include "alac_hip.h"
 #include "alac_dev.hpp"
 #include "alac_kernels.hpp"
+#include "alac_encode_v1_types.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -19,13 +20,12 @@ struct alac_hip_ctx {
     hipStream_t stream = nullptr;
     bool ownStream = false;
     std::string err;
-    // optional per-kernel timing: 4 events per encode call (before encode, after encode, after
-    // scan, after pack), recorded on `stream`
+    // optional per-stage timing: kEventBlocks blocks of kNumStages + 1 events per encode call, recorded on `stream`
     bool profile = false;
     std::vector<hipEvent_t> events;
     uint32_t profCalls = 0;
-    std::vector<uint32_t> profSub;  // sub-batches used by each timed call (0 = fused lane encoder)
-    // side streams / events of the sub-batch overlap (created on first use)
+    std::vector<bool> profLane;  // per timed call: lane encoder, no predictor-stage events (block 0 unused)
+    // side stream / events of the tap-parallel pipeline (V1Streams, created on first use)
     V1Streams vs{};
     bool vsReady = false;
     // second stream of the > 2-channel encoder (mono elements beside the stereo ones)
@@ -121,6 +121,17 @@ bool format_ok(const alac_hip_format *f)
 
 inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
+// the ALACSpecificConfig inside a cookie: ALACDecoder::Init skips legacy 'frma' and 'alac' atoms (codec/ALACDecoder.cu:123-134)
+const uint8_t *cookie_config(const uint8_t *ck, uint32_t &size)
+{
+    for (const char *atom : {"frma", "alac"})
+        if (size >= 12 && memcmp(ck + 4, atom, 4) == 0) {
+            ck += 12;
+            size -= 12;
+        }
+    return ck;
+}
+
 HandoffCtl handoff_ctl(const alac_hip_ctx *ctx)
 {
     HandoffCtl h;
@@ -130,8 +141,8 @@ HandoffCtl handoff_ctl(const alac_hip_ctx *ctx)
     return h;
 }
 
-// the context's second stream + fork / join events (mono elements beside stereo ones in the > 2-channel encoder; buffer clears
-// beside the staging kernels in the decoder), created on first use
+// the context's second stream + fork / join events (mono elements beside stereo ones in the > 2-channel encoder), created on
+// first use
 bool ensure_second_stream(alac_hip_ctx *ctx)
 {
     if (ctx->mcReady) return true;
@@ -223,11 +234,11 @@ EncLayout enc_layout(const alac_hip_format *f, uint32_t numPackets, uint32_t num
     off = align_up(off + 256 + ((uint64_t)numSegments / 1024 + 2) * 8, 256);
     L.colChain = off;
     off = align_up(off + (uint64_t)L.colsPad * 4, 256);
-    // The smallest batches (<= 4096 chains: a chained file, a few hundred files side by side — the low end of the
+    // The smallest batches (<= kSplitCoderMaxChains: a chained file, a few hundred files side by side — the low end of the
     // four-lanes-per-chain regime, v1_narrow_regime): the final coder of a chain is split over two waves, the second one
     // writes here
     L.bitWordsB = L.bitsB = 0;
-    if (lanes <= 4096) {
+    if (lanes <= kSplitCoderMaxChains) {
         L.bitWordsB = off;
         off = align_up(off + ((uint64_t)numPackets + 1) * 2 * L.wcap * 4, 256);
         L.bitsB = off;
@@ -365,6 +376,29 @@ struct DevBuf {
     hipError_t alloc(uint64_t n) { return hipMalloc(&p, n ? n : 4); }
 };
 
+// alac_hip_decode_host / alac_hip_verify_host: the packets back to back and their offsets (prefix sum of the sizes) on the device
+struct DevStream {
+    DevBuf bytes, offs;
+    uint64_t total = 0;     // stream bytes
+    uint64_t pcmBytes = 0;  // of the decoded batch
+};
+int32_t upload_stream(alac_hip_ctx *ctx, const alac_hip_format &fmt, const uint8_t *h_stream, const uint32_t *h_packet_bytes,
+                      uint32_t num_packets, DevStream &d)
+{
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    d.pcmBytes = (uint64_t)num_packets * fmt.frame_size * fmt.num_channels * bytes_per_sample(fmt.bit_depth);
+    std::vector<uint64_t> offs(num_packets + 1, 0);
+    for (uint32_t i = 0; i < num_packets; i++) offs[i + 1] = offs[i] + h_packet_bytes[i];
+    d.total = offs[num_packets];
+    hipError_t e;
+    if ((e = d.bytes.alloc(d.total + 16)) || (e = d.offs.alloc((num_packets + 1) * 8ull)))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if ((e = hipMemcpyAsync(d.bytes.p, h_stream, d.total, hipMemcpyHostToDevice, ctx->stream)) ||
+        (e = hipMemcpyAsync(d.offs.p, offs.data(), (num_packets + 1) * 8ull, hipMemcpyHostToDevice, ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    return ALAC_HIP_noErr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -476,14 +510,8 @@ uint64_t alac_hip_debug_waves_offset(const alac_hip_format *fmt, uint32_t num_pa
 const char *alac_hip_encode_regime(alac_hip_ctx *ctx, const alac_hip_format *fmt, uint32_t num_segments)
 {
     if (!ctx || !format_ok(fmt)) return "";
-    if (use_lane_encoder(ctx)) return "lane";
-    const uint32_t ch = fmt->num_channels > 2 ? 2 : fmt->num_channels;
-    if (v1_throughput_regime(num_segments, ch, ctx->opt)) return "throughput";
-    const uint64_t chains = (uint64_t)num_segments * ch;
-    // the launcher's own predicates (launch_encode_v1 / launch_v1_typed): fuse = fused && !thru, narrow = narrow && fuse
-    if (!ctx->opt.fused) return "stagewise";
-    const bool narrow = v1_narrow_regime(chains, ch, ctx->opt);
-    return narrow ? "tiny" : "latency";
+    // the launcher's own plan (the longest segment only decides the overlap of chained positions, which the name leaves out)
+    return v1_regime_name(v1_plan(fmt->num_channels, num_segments, 1, fmt->frame_size, ctx->opt).shape);
 }
 
 const char *alac_hip_last_error(const alac_hip_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -648,6 +676,49 @@ static int32_t encode_elements(alac_hip_ctx *ctx, const alac_hip_format *fmt, co
     return ALAC_HIP_noErr;
 }
 
+// the argument block of the tap-parallel pipeline: the batch of `ea`, its scratch in the workspace `ws` laid out by L, the
+// switches of plan P; stateInternal: the coefficient rows live in the workspace (no caller state)
+static V1Args v1_args(const alac_hip_ctx *ctx, const EncodeArgs &ea, const EncLayout &L, uint8_t *ws, const V1Plan &P,
+                      bool stateInternal)
+{
+    V1Args A{};  // (flags2, thru and narrow, which no kernel reads, stay 0)
+    A.S = {ea.pcm, ea.numSamples, ea.segFirst, ea.numSegments, ea.frameSize, 0, 0, ea.numSegments, ea.numPackets, ea.segMax};
+    A.state = stateInternal ? (int16_t *)(ws + L.state) : ea.state;
+    A.recs = ea.recs;
+    A.resA = (int32_t *)(ws + L.resA);
+    A.resB = (int32_t *)(ws + L.resB);
+    A.resC = (int32_t *)(ws + L.resC);
+    A.bits1 = (uint32_t *)(ws + L.bits1);
+    A.cost2 = (uint32_t *)(ws + L.cost2);
+    A.chainsPad = L.chainsPad;
+    A.bitWords = ea.bitWords;
+    A.wcap = ea.wcap;
+    A.dumpSlot = ea.numPackets * 2;
+    A.packetBytes = ea.packetBytes;
+    // progress words: the search launch's, then the final launch's (overlapped positions of a chained batch run side by side)
+    A.flags = (uint32_t *)(ws + L.flags);
+    A.flagsF = A.ovFlagsF = A.flags + (L.chainsPad / 8 + 16);
+    A.ovRowReady = (uint32_t *)(ws + L.rowReady);
+    A.dbg = ctx->opt.debugWaves ? A.ovRowReady : nullptr;  // (the row-ready words are only used by chained tiny batches)
+    // rows that live in the workspace and hold no caller state are never read before they are written: the kernels of the first
+    // packet position take init_coefs as constants (load_row) instead of a k_init_state launch writing them first — except
+    // in fast mode, where no search launch takes them as constants
+    A.virgin = stateInternal && !P.fast ? 1u : 0u;
+    A.foldDecide = P.shape == V1Shape::Latency ? 1u : 0u;
+    // pubMask 0: producers publish after every tile, rows written through (a release fence per publish cost ~11 us)
+    A.idleFast = P.shape == V1Shape::Throughput ? 0u : 1u;
+    A.ho = handoff_ctl(ctx);
+    A.cls = (ClassInfo *)(ws + L.cls);
+    A.colChain = (uint32_t *)(ws + L.colChain);
+    A.colsPad = L.colsPad;
+    // the second wave first walks [0, splitAt) keeping only the coder's state (~half the instructions of coding), then codes
+    // the rest: both waves finish together at ~2/3 of the frame
+    A.bitWordsB = P.split ? (uint32_t *)(ws + L.bitWordsB) : nullptr;
+    A.bitsB = L.bitsB ? (uint32_t *)(ws + L.bitsB) : nullptr;
+    A.splitAt = v1_split_at(ea.frameSize);
+    return A;
+}
+
 static int32_t encode_core(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm,
                            const uint32_t *d_num_samples, uint32_t num_packets, const uint32_t *d_seg_first,
                            uint32_t num_segments, int16_t *d_state, int32_t state_in, void *d_workspace,
@@ -719,8 +790,8 @@ static int32_t encode_core(alac_hip_ctx *ctx, const alac_hip_format *fmt, const 
     if (unread)
         launch_check_segments(d_seg_first, num_segments, num_packets, ea.segMax, ctx->errDev ? ctx->errDev + 1 : nullptr,
                               ea.segBad, ctx->stream);
+    if (ev) ctx->profLane.push_back(use_lane_encoder(ctx));
     if (use_lane_encoder(ctx)) {
-        if (ev) ctx->profSub.push_back(0);
         e = launch_encode(fmt->bit_depth, fmt->num_channels, ea, pa, num_packets, ctx->stream,
                           ev ? ev + (kNumStages + 1) : nullptr);
     } else {
@@ -733,7 +804,6 @@ static int32_t encode_core(alac_hip_ctx *ctx, const alac_hip_format *fmt, const 
             if (!ok) return fail(ctx, ALAC_HIP_MemFullError, "creating side streams");
             ctx->vsReady = true;
         }
-        if (ev) ctx->profSub.push_back(1);
         // packets per segment: the pipeline runs once per packet position (a chained segment is serial)
         uint32_t maxSeg = 1;
         if (d_seg_first && maxSegHint) {
@@ -752,27 +822,11 @@ static int32_t encode_core(alac_hip_ctx *ctx, const alac_hip_format *fmt, const 
                 maxSeg = sf[s + 1] - sf[s] > maxSeg ? sf[s + 1] - sf[s] : maxSeg;
             }
         }
-        V1Buffers vb;
-        vb.opt = ctx->opt;
-        vb.state = d_state ? d_state : (int16_t *)(ws + L.state);
-        vb.stateInitialised = d_state && state_in;
-        vb.stateInternal = d_state == nullptr;
-        vb.resA = (int32_t *)(ws + L.resA);
-        vb.resB = (int32_t *)(ws + L.resB);
-        vb.resC = (int32_t *)(ws + L.resC);
-        vb.bits1 = (uint32_t *)(ws + L.bits1);
-        vb.cost2 = (uint32_t *)(ws + L.cost2);
-        vb.flags = (uint32_t *)(ws + L.flags);
-        vb.flagsF = vb.flags + (L.chainsPad / 8 + 16);
-        vb.rowReady = (uint32_t *)(ws + L.rowReady);
-        vb.chainsPad = L.chainsPad;
-        vb.cls = ws + L.cls;
-        vb.colChain = (uint32_t *)(ws + L.colChain);
-        vb.colsPad = L.colsPad;
-        vb.bitWordsB = L.bitWordsB ? (uint32_t *)(ws + L.bitWordsB) : nullptr;
-        vb.bitsB = L.bitsB ? (uint32_t *)(ws + L.bitsB) : nullptr;
-        vb.ho = handoff_ctl(ctx);
-        e = launch_encode_v1(fmt->bit_depth, fmt->num_channels, ea, pa, vb, ctx->vs, num_packets, maxSeg, ctx->stream, ev);
+        const V1Plan P = v1_plan(fmt->num_channels, num_segments, maxSeg, fmt->frame_size, ctx->opt);
+        const V1Args A = v1_args(ctx, ea, L, ws, P, d_state == nullptr);
+        // rows that hold no caller state and are not taken as constants (V1Args::virgin) get init_coefs first
+        const bool initState = !(d_state && state_in) && !A.virgin;
+        e = launch_encode_v1(fmt->bit_depth, fmt->num_channels, A, P, initState, pa, ctx->vs, num_packets, maxSeg, ctx->stream, ev);
     }
     if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "encode launch", e);
     if (lpc) {
@@ -815,7 +869,7 @@ int32_t alac_hip_profile_begin(alac_hip_ctx *ctx, uint32_t max_calls)
         ctx->events.push_back(e);
     }
     ctx->profCalls = 0;
-    ctx->profSub.clear();
+    ctx->profLane.clear();
     ctx->profile = max_calls != 0;
     return ALAC_HIP_noErr;
 }
@@ -837,17 +891,12 @@ int32_t alac_hip_profile_end(alac_hip_ctx *ctx, uint32_t *out_calls, float *out_
         return true;
     };
     for (uint32_t c = 0; c < ctx->profCalls; c++) {
+        // block 0: the predictor / Golomb stages of the tap-parallel pipeline; block 1: finalize, scan, pack — and every
+        // stage of the lane encoder
         hipEvent_t *base = &ctx->events[(size_t)c * EV];
-        const uint32_t H = ctx->profSub[c];
-        for (uint32_t h = 0; h < H; h++)  // predictor / Golomb stages, one launch per sub-batch
-            for (uint32_t k = kStageLms1; k <= kStageGol3; k++) {
-                if (!elapsed(base[h * BLK + k], base[h * BLK + k + 1], t[k]))
-                    return fail(ctx, ALAC_HIP_ParamError, "hipEventElapsedTime");
-                launches[k] += 1;
-            }
-        hipEvent_t *tail = base + BLK;
-        for (uint32_t k = (H ? kStageScan : 0); k < kNumStages; k++) {
-            if (!elapsed(tail[k], tail[k + 1], t[k])) return fail(ctx, ALAC_HIP_ParamError, "hipEventElapsedTime");
+        for (uint32_t k = 0; k < kNumStages; k++) {
+            hipEvent_t *blk = (ctx->profLane[c] || k >= kStageScan) ? base + BLK : base;
+            if (!elapsed(blk[k], blk[k + 1], t[k])) return fail(ctx, ALAC_HIP_ParamError, "hipEventElapsedTime");
             launches[k] += 1;
         }
     }
@@ -916,15 +965,7 @@ uint32_t alac_hip_magic_cookie_full(const alac_hip_format *fmt, uint32_t max_fra
 int32_t alac_hip_format_from_cookie(const uint8_t *ck, uint32_t size, alac_hip_format *out)
 {
     if (!ck || !out) return ALAC_HIP_ParamError;
-    // ALACDecoder::Init skips legacy 'frma' and 'alac' atoms (codec/ALACDecoder.cu:123-134)
-    if (size >= 12 && ck[4] == 'f' && ck[5] == 'r' && ck[6] == 'm' && ck[7] == 'a') {
-        ck += 12;
-        size -= 12;
-    }
-    if (size >= 12 && ck[4] == 'a' && ck[5] == 'l' && ck[6] == 'a' && ck[7] == 'c') {
-        ck += 12;
-        size -= 12;
-    }
+    ck = cookie_config(ck, size);
     if (size < 24) return ALAC_HIP_ParamError;
     if (ck[4] > 0) return ALAC_HIP_ParamError;  // compatibleVersion <= kALACVersion (:153)
     out->frame_size = ((uint32_t)ck[0] << 24) | ((uint32_t)ck[1] << 16) | ((uint32_t)ck[2] << 8) | ck[3];
@@ -949,6 +990,13 @@ uint64_t alac_hip_decode_workspace_bytes_stream(const alac_hip_format *fmt, uint
 }  // extern "C"
 
 namespace {
+int32_t cookie_format(alac_hip_ctx *ctx, const uint8_t *cookie, uint32_t size, alac_hip_format &fmt)
+{
+    if (alac_hip_format_from_cookie(cookie, size, &fmt) != ALAC_HIP_noErr) return fail(ctx, ALAC_HIP_ParamError, "bad magic cookie");
+    if (!format_ok(&fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format in cookie");
+    return ALAC_HIP_noErr;
+}
+
 // alac_hip_decode, and alac_hip_verify's decode pass (verifyMismatch non-null: d_pcm_out is the expected PCM, only read)
 int32_t decode_impl(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
                     const uint64_t *d_packet_offsets, uint32_t num_packets, void *d_workspace, uint64_t workspace_bytes,
@@ -956,9 +1004,7 @@ int32_t decode_impl(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_
 {
     if (!ctx) return ALAC_HIP_ParamError;
     alac_hip_format fmt;
-    if (alac_hip_format_from_cookie(h_cookie, cookie_size, &fmt) != ALAC_HIP_noErr)
-        return fail(ctx, ALAC_HIP_ParamError, "bad magic cookie");
-    if (!format_ok(&fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format in cookie");
+    if (int32_t rc = cookie_format(ctx, h_cookie, cookie_size, fmt)) return rc;
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!d_stream || !d_packet_offsets || !d_workspace || !d_pcm_out || !d_num_samples_out || !d_status)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
@@ -967,11 +1013,8 @@ int32_t decode_impl(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_
     DecLayout L = dec_layout(&fmt, num_packets);
     if (workspace_bytes < L.total) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
     L.capWords = (workspace_bytes - L.words) / 4;  // all of it: packets that do not fit the staged words get status -50
-    // skip wrappers again to reach pb/mb/kb
-    const uint8_t *ck = h_cookie;
     uint32_t size = cookie_size;
-    if (size >= 12 && ck[4] == 'f' && ck[5] == 'r' && ck[6] == 'm' && ck[7] == 'a') { ck += 12; size -= 12; }
-    if (size >= 12 && ck[4] == 'a' && ck[5] == 'l' && ck[6] == 'a' && ck[7] == 'c') { ck += 12; size -= 12; }
+    const uint8_t *ck = cookie_config(h_cookie, size);  // pb / mb / kb
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
     uint8_t *ws = (uint8_t *)d_workspace;
     DecodeArgs da;
@@ -1016,15 +1059,11 @@ int32_t decode_impl(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e == hipSuccess && mismatch) e = launch_decode(da, ctx->stream);
     } else {
-        // (the plane / progress clears on the context's second stream beside the staging and header kernels were measured in
-        // round 3: 1.978 against 1.952 ms per 10 000 packets — the two cross-stream waits cost more than the 45 us of clears
-        // they hide; launch_decode_v1 keeps the parameters)
-        const bool side = false;
         // A mono / stereo stream whose packets carry another element sequence (two SCEs for two channels, fill in
         // front of ...: status -4 from the fast pipeline, counted by its header kernel) is decoded again by the lane decoder,
         // which follows whatever the packets carry.  No host round trip: its kernels are gated on that device-side count.
         e = launch_decode_v1(da, (uint32_t *)(ws + L.words), L.capWords, da.resid, (uint32_t *)(ws + L.prog), ctx->stream,
-                             (uint32_t *)(ws + L.mismatch), side ? ctx->mcStream : nullptr, ctx->mcFork, ctx->mcJoin);
+                             (uint32_t *)(ws + L.mismatch));
         if (e == hipSuccess) {
             DecodeArgs dg = da;
             dg.gate = (const uint32_t *)(ws + L.mismatch);
@@ -1067,9 +1106,7 @@ int32_t alac_hip_verify(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t coo
 {
     if (!ctx) return ALAC_HIP_ParamError;
     alac_hip_format fmt;
-    if (alac_hip_format_from_cookie(h_cookie, cookie_size, &fmt) != ALAC_HIP_noErr)
-        return fail(ctx, ALAC_HIP_ParamError, "bad magic cookie");
-    if (!format_ok(&fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format in cookie");
+    if (int32_t rc = cookie_format(ctx, h_cookie, cookie_size, fmt)) return rc;
     if (!d_bad_packets) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
     if (num_packets == 0) {
@@ -1259,24 +1296,18 @@ int32_t alac_hip_decode_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!h_stream || !h_packet_bytes || !h_pcm_out || !h_num_samples_out || !h_status)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
-    std::vector<uint64_t> offs(num_packets + 1, 0);
-    for (uint32_t i = 0; i < num_packets; i++) offs[i + 1] = offs[i] + h_packet_bytes[i];
-    const uint64_t total = offs[num_packets];
-    const uint32_t bpf = fmt.num_channels * bytes_per_sample(fmt.bit_depth);
-    const uint64_t pcmBytes = (uint64_t)num_packets * fmt.frame_size * bpf;
-    const uint64_t wsBytes = alac_hip_decode_workspace_bytes_stream(&fmt, num_packets, total);
-    DevBuf dStream, dOffs, dWs, dPcm, dNs, dSt;
+    DevStream d;
+    if (int32_t rc = upload_stream(ctx, fmt, h_stream, h_packet_bytes, num_packets, d)) return rc;
+    const uint64_t pcmBytes = d.pcmBytes;
+    const uint64_t wsBytes = alac_hip_decode_workspace_bytes_stream(&fmt, num_packets, d.total);
+    DevBuf dWs, dPcm, dNs, dSt;
     hipError_t e;
-    if ((e = dStream.alloc(total + 16)) || (e = dOffs.alloc((num_packets + 1) * 8ull)) || (e = dWs.alloc(wsBytes)) ||
-        (e = dPcm.alloc(pcmBytes)) || (e = dNs.alloc(num_packets * 4ull)) || (e = dSt.alloc(num_packets * 4ull)))
+    if ((e = dWs.alloc(wsBytes)) || (e = dPcm.alloc(pcmBytes)) || (e = dNs.alloc(num_packets * 4ull)) ||
+        (e = dSt.alloc(num_packets * 4ull)))
         return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
     hipStream_t st = ctx->stream;
-    if ((e = hipMemcpyAsync(dStream.p, h_stream, total, hipMemcpyHostToDevice, st)) ||
-        (e = hipMemcpyAsync(dOffs.p, offs.data(), (num_packets + 1) * 8ull, hipMemcpyHostToDevice, st)) ||
-        (e = hipMemsetAsync(dPcm.p, 0, pcmBytes, st)))
-        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    int32_t rc = alac_hip_decode(ctx, h_cookie, cookie_size, (const uint8_t *)dStream.p, (const uint64_t *)dOffs.p,
+    if ((e = hipMemsetAsync(dPcm.p, 0, pcmBytes, st))) return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    int32_t rc = alac_hip_decode(ctx, h_cookie, cookie_size, (const uint8_t *)d.bytes.p, (const uint64_t *)d.offs.p,
                                  num_packets, dWs.p, wsBytes, (uint8_t *)dPcm.p, (uint32_t *)dNs.p,
                                  (int32_t *)dSt.p);
     if (rc != ALAC_HIP_noErr) return rc;
@@ -1299,27 +1330,21 @@ int32_t alac_hip_verify_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_
     if (num_packets == 0) return 0;
     if (!h_stream || !h_packet_bytes || !h_pcm_expected) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
     if (num_packets > 0x7fffffffu) return fail(ctx, ALAC_HIP_ParamError, "more packets than the return value counts");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
-    std::vector<uint64_t> offs(num_packets + 1, 0);
-    for (uint32_t i = 0; i < num_packets; i++) offs[i + 1] = offs[i] + h_packet_bytes[i];
-    const uint64_t total = offs[num_packets];
-    const uint32_t bpf = fmt.num_channels * bytes_per_sample(fmt.bit_depth);
-    const uint64_t pcmBytes = (uint64_t)num_packets * fmt.frame_size * bpf;
-    const uint64_t wsBytes = alac_hip_verify_workspace_bytes_stream(&fmt, num_packets, total);
-    DevBuf dStream, dOffs, dWs, dPcm, dNs, dFm, dSt, dBad;
+    DevStream d;
+    if (int32_t rc = upload_stream(ctx, fmt, h_stream, h_packet_bytes, num_packets, d)) return rc;
+    const uint64_t pcmBytes = d.pcmBytes;
+    const uint64_t wsBytes = alac_hip_verify_workspace_bytes_stream(&fmt, num_packets, d.total);
+    DevBuf dWs, dPcm, dNs, dFm, dSt, dBad;
     hipError_t e;
-    if ((e = dStream.alloc(total + 16)) || (e = dOffs.alloc((num_packets + 1) * 8ull)) || (e = dWs.alloc(wsBytes)) ||
-        (e = dPcm.alloc(pcmBytes)) || (h_num_samples_expected && (e = dNs.alloc(num_packets * 4ull))) ||
+    if ((e = dWs.alloc(wsBytes)) || (e = dPcm.alloc(pcmBytes)) || (h_num_samples_expected && (e = dNs.alloc(num_packets * 4ull))) ||
         (e = dFm.alloc(num_packets * 4ull)) || (e = dSt.alloc(num_packets * 4ull)) || (e = dBad.alloc(4)))
         return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
     hipStream_t st = ctx->stream;
-    if ((e = hipMemcpyAsync(dStream.p, h_stream, total, hipMemcpyHostToDevice, st)) ||
-        (e = hipMemcpyAsync(dOffs.p, offs.data(), (num_packets + 1) * 8ull, hipMemcpyHostToDevice, st)) ||
-        (e = hipMemcpyAsync(dPcm.p, h_pcm_expected, pcmBytes, hipMemcpyHostToDevice, st)) ||
+    if ((e = hipMemcpyAsync(dPcm.p, h_pcm_expected, pcmBytes, hipMemcpyHostToDevice, st)) ||
         (h_num_samples_expected &&
          (e = hipMemcpyAsync(dNs.p, h_num_samples_expected, num_packets * 4ull, hipMemcpyHostToDevice, st))))
         return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    int32_t rc = alac_hip_verify(ctx, h_cookie, cookie_size, (const uint8_t *)dStream.p, (const uint64_t *)dOffs.p, num_packets,
+    int32_t rc = alac_hip_verify(ctx, h_cookie, cookie_size, (const uint8_t *)d.bytes.p, (const uint64_t *)d.offs.p, num_packets,
                                  (const uint8_t *)dPcm.p, (const uint32_t *)dNs.p, dWs.p, wsBytes, (uint32_t *)dFm.p,
                                  (int32_t *)dSt.p, (uint32_t *)dBad.p);
     if (rc != ALAC_HIP_noErr) return rc;

@@ -439,25 +439,28 @@ static void launch_unmix_depth(const DecodeArgs &da, hipStream_t st)
         hipLaunchKernelGGL((k_decode_unmix<DEPTH, 1, VERIFY>), grid, dim3(256), 0, st, da);
 }
 
-hipError_t launch_decode(const DecodeArgs &da, hipStream_t st)
+// VERIFY: the un-mix instantiations whose store sites compare instead (alac_verify.hpp)
+template <bool VERIFY>
+static hipError_t launch_decode_lanes(const DecodeArgs &da, hipStream_t st)
 {
-    if (da.numPackets == 0) return hipSuccess;
     hipLaunchKernelGGL(k_decode_entropy, dim3((da.numPackets + 63) / 64), dim3(64), 0, st, da);
     const uint64_t lanes = (uint64_t)da.numPackets * da.numChannels;
     hipLaunchKernelGGL(k_decode_unpc, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, st, da);
-    // verify mode (alac_hip_verify): the un-mix instantiations whose store sites compare instead (alac_verify.hpp)
-    switch (da.bitDepth * 2 + (da.firstMismatch ? 1 : 0)) {
-    case 32: launch_unmix_depth<16, false>(da, st); break;
-    case 40: launch_unmix_depth<20, false>(da, st); break;
-    case 48: launch_unmix_depth<24, false>(da, st); break;
-    case 64: launch_unmix_depth<32, false>(da, st); break;
-    case 33: launch_unmix_depth<16, true>(da, st); break;
-    case 41: launch_unmix_depth<20, true>(da, st); break;
-    case 49: launch_unmix_depth<24, true>(da, st); break;
-    case 65: launch_unmix_depth<32, true>(da, st); break;
+    switch (da.bitDepth) {
+    case 16: launch_unmix_depth<16, VERIFY>(da, st); break;
+    case 20: launch_unmix_depth<20, VERIFY>(da, st); break;
+    case 24: launch_unmix_depth<24, VERIFY>(da, st); break;
+    case 32: launch_unmix_depth<32, VERIFY>(da, st); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+hipError_t launch_decode(const DecodeArgs &da, hipStream_t st)
+{
+    if (da.numPackets == 0) return hipSuccess;
+    // verify mode (alac_hip_verify) when the caller passes its first-mismatch words
+    return da.firstMismatch ? launch_decode_lanes<true>(da, st) : launch_decode_lanes<false>(da, st);
 }
 
 // ------------------------------------------------------------------------------------------------

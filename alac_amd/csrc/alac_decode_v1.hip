@@ -1991,39 +1991,31 @@ static void launch_unmix_v1(const DecV1Args &V, hipStream_t st)
         hipLaunchKernelGGL((k_dec_unmix<DEPTH, 1, VERIFY>), grid, dim3(256), 0, st, V);
 }
 
-// everything after the staging of the stream: one pass of the pipeline over the elements V describes
-// side: optional second stream + fork / join events — the clears of the residual plane (328 MB at 10 000 stereo packets: 50 us)
-// and of the progress words run there beside k_dec_stage / k_dec_header and are joined in front of the entropy launch
-struct DecSide {
-    hipStream_t stream = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-};
-static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, const DecSide *side = nullptr, bool stageFirst = false)
+// one pass of the pipeline over the elements V describes, after the staging of the stream (stageFirst: the pass stages it
+// itself); VERIFY: the instantiations whose PCM store sites compare instead (alac_hip_verify)
+template <bool VERIFY>
+static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stageFirst)
 {
     DecV1Args V = V0;
     const DecodeArgs &da = V.d;
     const uint64_t planeBytes = (uint64_t)da.numPackets * da.numChannels * da.frameSize * 4;
-    const int forced0 = V.d.optFused;
-    const bool fused0 = forced0 >= 0 ? forced0 != 0 : dec_fused_auto(da.numPackets, da.numChannels);
-    const bool useSide = side && side->stream && fused0;
-    hipStream_t sc = useSide ? side->stream : st;  // the clears
-    if (useSide) {
-        (void)hipEventRecord(side->fork, st);
-        (void)hipStreamWaitEvent(sc, side->fork, 0);
-    }
+    // One launch (entropy lanes followed by the predictor waves, producer/consumer through HBM) where the chains are few
+    // enough that a stage is as slow as its longest serial chain; separate launches where every kernel fills the machine by
+    // itself (no polling, no release fence per publish).  Measured, fused / separate, 16-bit stereo packets (round 3, HEAD;
+    // profiles/r03/regime_sweep.log): 10 000 1.72 / 2.9 ms, 22 000 2.19 / 2.78, 26 000 2.58 / 2.86, 30 000 2.78 / 2.85,
+    // 34 000 2.84 / 2.88, 125 000 17.6 (round 1) / 5.3.  Option dec_fused (ALAC_HIP_DEC_FUSED) = 0 / 1 forces.
+    const bool fused = da.optFused >= 0 ? da.optFused != 0 : dec_fused_auto(da.numPackets, da.numChannels);
     // zero runs only move the index (k_dec_entropy, fused launch) — except in k_dec_entropy_wide, which writes the zeros of its
     // runs itself (in the fused launch the same code made the entropy wave, the launch's serial chain, slower than the 50 us
     // fill it saves: 10 000 packets 1.95 -> 2.14 ms):
-    // every sample a later kernel reads is then written by somebody (coded rows: residuals + run zeros; uncompressed rows:
-    // k_dec_raw; absent elements of a > 2-channel round: k_dec_unmix reads nothing), and the fill is left out
-    const bool zerosWritten = !fused0;
+    // with separate launches every sample a later kernel reads is then written by somebody (coded rows: residuals + run zeros;
+    // uncompressed rows: k_dec_raw; absent elements of a > 2-channel round: k_dec_unmix reads nothing), and the fill is left out
     // (the runtime's fill: a kernel of this library in its place — 44 us for the 328 MB of 10 000 stereo packets, HBM write speed —
     // measured 1.745 against 1.733 ms per pass: no bubble in front of a fill that IS the pass's first real work, unlike the 4-byte
-    // ones DecZero replaced)
-    if (!zerosWritten) (void)hipMemsetAsync(V.plane, 0, planeBytes, sc);
-    if (useSide) (void)hipMemsetAsync(V.prog, 0, (size_t)da.numPackets * 8, sc);
-    V.lists = fused0 ? 0u : 1u;
-    V.pairs = (!fused0 && V.d.optPair != 0) ? 1u : 0u;
+    // ones DecZero replaced.  The fill on a second stream beside the staging and header kernels: 1.978 against 1.952 ms)
+    if (fused) (void)hipMemsetAsync(V.plane, 0, planeBytes, st);
+    V.lists = fused ? 0u : 1u;
+    V.pairs = (!fused && V.d.optPair != 0) ? 1u : 0u;
     // the pass's counters: cleared by its first kernel (k_dec_tail / k_dec_stage, see DecZero) where there is one
     DecZero zero;
     zero.a = V.lists ? dec_lists(V).cnt : nullptr;
@@ -2043,7 +2035,7 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, const DecS
     // copy it saves — 34 000 / 48 000 / 64 000 / 90 000 packets, direct against staged, one box: 2.99 / 2.85, 3.27 / 3.18,
     // 3.36 / 3.29, 4.25 / 4.30 ms (profiles/r04/decode_direct_sweep.log)
     const bool directWanted = V.d.optDirect == 2 || (V.d.optDirect == 1 && da.numPackets >= kDecDirectPackets);
-    const bool direct = stageFirst && !fused0 && V.elemBit == nullptr && ((uintptr_t)da.stream & 3) == 0 && directWanted &&
+    const bool direct = stageFirst && !fused && V.elemBit == nullptr && ((uintptr_t)da.stream & 3) == 0 && directWanted &&
                         da.bitDepth == 16;
     if (direct) {
         V.raw = (const uint32_t *)da.stream;
@@ -2055,30 +2047,13 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, const DecS
         hipLaunchKernelGGL(k_dec_stage, dim3(2048), dim3(256), 0, st, da.stream, da.offsets, da.numPackets, const_cast<uint32_t *>(V.words),
                            V.capWords, zero);
     hipLaunchKernelGGL(k_dec_header, dim3((da.numPackets + 64 * kHdrWaves - 1) / (64 * kHdrWaves)), dim3(64 * kHdrWaves), 0, st, V);
-    if (useSide) {
-        (void)hipEventRecord(side->join, sc);
-        (void)hipStreamWaitEvent(st, side->join, 0);
-    }
     const uint64_t lanes = (uint64_t)da.numPackets * da.numChannels;
     const uint32_t nEnt = (da.numPackets + 63) / 64;
-    // One launch (entropy lanes followed by the predictor waves, producer/consumer through HBM) where the chains are few
-    // enough that a stage is as slow as its longest serial chain; separate launches where every kernel fills the machine by
-    // itself (no polling, no release fence per publish).  Measured, fused / separate, 16-bit stereo packets (round 3, HEAD;
-    // profiles/r03/regime_sweep.log): 10 000 1.72 / 2.9 ms, 22 000 2.19 / 2.78, 26 000 2.58 / 2.86, 30 000 2.78 / 2.85,
-    // 34 000 2.84 / 2.88, 125 000 17.6 (round 1) / 5.3.  Option dec_fused (ALAC_HIP_DEC_FUSED) = 0 / 1 forces.
-    const int forced = V.d.optFused;
-    const bool fused = forced >= 0 ? forced != 0 : dec_fused_auto(da.numPackets, da.numChannels);
-    // verify mode (alac_hip_verify): the same launches, with the instantiations whose PCM store sites compare instead
-    const bool verify = da.firstMismatch != nullptr;
     if (fused) {
         const uint32_t nEntWg = (da.numPackets + kFusedPpw - 1) / kFusedPpw;
-        const dim3 grid(nEntWg + (da.numPackets + 3) / 4);
-        if (verify) hipLaunchKernelGGL(k_dec_fused_wg<true>, grid, dim3(256), 0, st, V, nEntWg);
-        else hipLaunchKernelGGL(k_dec_fused_wg<false>, grid, dim3(256), 0, st, V, nEntWg);
+        hipLaunchKernelGGL(k_dec_fused_wg<VERIFY>, dim3(nEntWg + (da.numPackets + 3) / 4), dim3(256), 0, st, V, nEntWg);
     } else {
-        const dim3 rgrid(da.numPackets < 4096u ? da.numPackets : 4096u);
-        if (verify) hipLaunchKernelGGL(k_dec_raw<true>, rgrid, dim3(256), 0, st, V);
-        else hipLaunchKernelGGL(k_dec_raw<false>, rgrid, dim3(256), 0, st, V);
+        hipLaunchKernelGGL(k_dec_raw<VERIFY>, dim3(da.numPackets < 4096u ? da.numPackets : 4096u), dim3(256), 0, st, V);
         // deferred residual stores, four 16-byte stores per round of sixteen consecutive residuals (round 2, 4-byte stores:
         // paid only up to two entropy waves per SIMD; with the wide stores, measured whole decode pass at 125 000 / 250 000 /
         // 500 000 packets: 9.31 -> 8.19, 19.4 -> 14.2, 38.1 -> 26.5 ms — the kernel was bound by the number of store
@@ -2090,29 +2065,25 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, const DecS
         // chains sorted by tap count, one lane per chain
         // (five lists, each rounded up to whole waves)
         const dim3 ugrid(((uint32_t)((lanes + 63) / 64) + 6 + kEntWavesPerWg - 1) / kEntWavesPerWg), ublock(64 * kEntWavesPerWg);
-        if (verify) {
-            if (da.bitDepth == 24) hipLaunchKernelGGL((k_dec_unpc_wide<24, true>), ugrid, ublock, 0, st, V);
-            else if (da.bitDepth == 20) hipLaunchKernelGGL((k_dec_unpc_wide<20, true>), ugrid, ublock, 0, st, V);
-            else hipLaunchKernelGGL((k_dec_unpc_wide<16, true>), ugrid, ublock, 0, st, V);
-        } else {
-            if (da.bitDepth == 24) hipLaunchKernelGGL((k_dec_unpc_wide<24, false>), ugrid, ublock, 0, st, V);
-            else if (da.bitDepth == 20) hipLaunchKernelGGL((k_dec_unpc_wide<20, false>), ugrid, ublock, 0, st, V);
-            else hipLaunchKernelGGL((k_dec_unpc_wide<16, false>), ugrid, ublock, 0, st, V);
-        }
+        if (da.bitDepth == 24) hipLaunchKernelGGL((k_dec_unpc_wide<24, VERIFY>), ugrid, ublock, 0, st, V);
+        else if (da.bitDepth == 20) hipLaunchKernelGGL((k_dec_unpc_wide<20, VERIFY>), ugrid, ublock, 0, st, V);
+        else hipLaunchKernelGGL((k_dec_unpc_wide<16, VERIFY>), ugrid, ublock, 0, st, V);
     }
     hipLaunchKernelGGL(k_dec_unpc, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, st, V);
-    switch (da.bitDepth * 2 + (verify ? 1 : 0)) {
-    case 32: launch_unmix_v1<16, false>(V, st); break;
-    case 40: launch_unmix_v1<20, false>(V, st); break;
-    case 48: launch_unmix_v1<24, false>(V, st); break;
-    case 64: launch_unmix_v1<32, false>(V, st); break;
-    case 33: launch_unmix_v1<16, true>(V, st); break;
-    case 41: launch_unmix_v1<20, true>(V, st); break;
-    case 49: launch_unmix_v1<24, true>(V, st); break;
-    case 65: launch_unmix_v1<32, true>(V, st); break;
+    switch (da.bitDepth) {
+    case 16: launch_unmix_v1<16, VERIFY>(V, st); break;
+    case 20: launch_unmix_v1<20, VERIFY>(V, st); break;
+    case 24: launch_unmix_v1<24, VERIFY>(V, st); break;
+    case 32: launch_unmix_v1<32, VERIFY>(V, st); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+// verify mode (alac_hip_verify) when the caller passes its first-mismatch words
+static hipError_t run_decode_v1_pass(const DecV1Args &V, hipStream_t st, bool stageFirst)
+{
+    return V.d.firstMismatch ? decode_v1_pass<true>(V, st, stageFirst) : decode_v1_pass<false>(V, st, stageFirst);
 }
 
 static DecV1Args decode_v1_args(const DecodeArgs &da, uint32_t *words, uint64_t capWords, int32_t *plane, uint32_t *prog)
@@ -2139,16 +2110,12 @@ static DecV1Args decode_v1_args(const DecodeArgs &da, uint32_t *words, uint64_t 
 }
 
 hipError_t launch_decode_v1(const DecodeArgs &da, uint32_t *words, uint64_t capWords, int32_t *plane, uint32_t *prog,
-                            hipStream_t st, uint32_t *mismatch, hipStream_t sideStream, hipEvent_t fork, hipEvent_t join)
+                            hipStream_t st, uint32_t *mismatch)
 {
     if (da.numPackets == 0) return hipSuccess;
     DecV1Args V = decode_v1_args(da, words, capWords, plane, prog);
     V.mismatch = mismatch;
-    DecSide side;
-    side.stream = sideStream;
-    side.fork = fork;
-    side.join = join;
-    return decode_v1_pass(V, st, sideStream ? &side : nullptr, true);
+    return run_decode_v1_pass(V, st, true);
 }
 
 // counts the packets whose status is `code` (the element-sequence mismatch of launch_decode_v1_elements)
@@ -2156,13 +2123,6 @@ __global__ void k_dec_count_status(const int32_t *status, uint32_t n, int32_t co
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && status[i] == code) atomicAdd(count, 1u);
-}
-
-hipError_t launch_count_status(const int32_t *status, uint32_t n, int32_t code, uint32_t *count, hipStream_t st)
-{
-    (void)hipMemsetAsync(count, 0, 4, st);
-    hipLaunchKernelGGL(k_dec_count_status, dim3((n + 255) / 256), dim3(256), 0, st, status, n, code, count);
-    return hipGetLastError();
 }
 
 hipError_t launch_decode_v1_elements(const DecodeArgs &da, const McElement *el, uint32_t numElements, uint32_t *words,
@@ -2181,7 +2141,7 @@ hipError_t launch_decode_v1_elements(const DecodeArgs &da, const McElement *el, 
         V.round = r;
         V.outChannels = da.numChannels;
         V.outFirst = el[r].first;
-        const hipError_t e = decode_v1_pass(V, st);
+        const hipError_t e = run_decode_v1_pass(V, st, false);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_dec_count_status, dim3((da.numPackets + 255) / 256), dim3(256), 0, st, da.statusOut, da.numPackets,

@@ -1,4 +1,4 @@
-// alac_encode_v1.hip — dispatcher of the tap-parallel encode pipeline: regime selection, argument block, and the call
+// alac_encode_v1.hip — dispatcher of the tap-parallel encode pipeline: the plan of a call (regime and shape), and the call
 // into the per-depth launcher (alac_encode_v1_impl.hpp, instantiated in alac_encode_v1_d16/20/24/32.hip).
 #include <cstdlib>
 #include "alac_encode_v1_types.hpp"
@@ -34,7 +34,7 @@ void launch_check_segments(const uint32_t *segFirst, uint32_t numSegments, uint3
 }
 
 // chains beyond what one 2-lane predictor wave per SIMD holds (1024 SIMDs x 32 chains x 2): throughput regime
-bool v1_throughput_regime(uint32_t numSegments, uint32_t channels, const AlacOptions &opt)
+static bool v1_throughput_regime(uint32_t numSegments, uint32_t channels, const AlacOptions &opt)
 {
     if (opt.thru >= 0) return opt.thru != 0;
     return (uint64_t)numSegments * (channels > 2 ? 2 : channels) > 65536;
@@ -50,7 +50,7 @@ bool v1_throughput_regime(uint32_t numSegments, uint32_t channels, const AlacOpt
 // Until round 4 the rule was "four lanes up to 4096 chains".  Mono streams (no mixRes search, whose five passes are where the
 // four-lane form gains most) cross over earlier at both ends: 10 000 / 11 000 chains 0.93 / 0.99 against 1.07 / 1.00 ms, and
 // 26 000 / 28 000 chains 1.55 / 1.77 against 1.97 / 1.78 — there the four-lane workers reach two per SIMD (26 214 chains).
-bool v1_narrow_regime(uint64_t chains, uint32_t channels, const AlacOptions &opt)
+static bool v1_narrow_regime(uint64_t chains, uint32_t channels, const AlacOptions &opt)
 {
     if (opt.narrow >= 0) return opt.narrow != 0;
     const bool mono = channels == 1;
@@ -59,77 +59,58 @@ bool v1_narrow_regime(uint64_t chains, uint32_t channels, const AlacOptions &opt
     return chains <= (mono ? 26112u : 34816u);
 }
 
-hipError_t launch_encode_v1(uint32_t depth, uint32_t channels, const EncodeArgs &ea, const PackArgs &pa,
-                            const V1Buffers &vb, const V1Streams &vs, uint32_t numPackets, uint32_t maxSegPackets,
-                            hipStream_t st, hipEvent_t *ev)
+// Latency regime (about one wave per SIMD: up to ~2 x 1024 x 32 chains): idle lanes should not slow their wave down
+// (V1Args::idleFast).  With many waves per SIMD the machine is throughput bound and the extra work of idle lanes costs more
+// than the checked paths (measured: 125 000 packets 18.6 ms vs 20.3 ms).
+V1Plan v1_plan(uint32_t channels, uint32_t numSegments, uint32_t maxSegPackets, uint32_t frameSize, const AlacOptions &opt)
 {
-    V1Args A;
-    A.S.pcm = ea.pcm;
-    A.S.numSamples = ea.numSamples;
-    A.S.segFirst = ea.segFirst;
-    A.S.numSegments = ea.numSegments;
-    A.S.frameSize = ea.frameSize;
-    A.S.pos = 0;
-    A.S.segBegin = 0;
-    A.S.segEnd = ea.numSegments;
-    A.S.numPackets = ea.numPackets;
-    A.S.segMax = ea.segMax;
-    A.state = vb.state;
-    A.recs = ea.recs;
-    A.resA = vb.resA;
-    A.resB = vb.resB;
-    A.resC = vb.resC;
-    A.bits1 = vb.bits1;
-    A.cost2 = vb.cost2;
-    A.chainsPad = vb.chainsPad;
-    A.bitWords = ea.bitWords;
-    A.wcap = ea.wcap;
-    A.dumpSlot = numPackets * 2;
-    {
-        // Latency regime (about one wave per SIMD: up to ~2 x 1024 x 32 chains): idle lanes should not slow their
-        // wave down (idleFast).  With many waves per SIMD the machine is throughput bound and the extra work of idle lanes
-        // costs more than the checked paths (measured: 125 000 packets 18.6 ms vs 20.3 ms).
-        const uint64_t chains = (uint64_t)ea.numSegments * channels;
-        A.thru = v1_throughput_regime(ea.numSegments, channels, vb.opt) ? 1u : 0u;
-        A.idleFast = A.thru ? 0u : 1u;
-        A.narrow = v1_narrow_regime(chains, channels, vb.opt) ? 1u : 0u;
+    V1Plan P{};
+    const uint32_t ch = channels > 2 ? 2 : channels;
+    const uint64_t chains = (uint64_t)numSegments * ch;
+    P.fast = ch == 2 && opt.fastMode != 0;  // SetFastMode: no search passes at all (mono has no fast form)
+    if (opt.laneEncoder)
+        P.shape = V1Shape::Lane;
+    else if (v1_throughput_regime(numSegments, ch, opt))
+        P.shape = V1Shape::Throughput;
+    else if (!opt.fused)
+        P.shape = V1Shape::Stagewise;
+    else if (v1_narrow_regime(chains, ch, opt))
+        P.shape = V1Shape::Tiny;
+    else
+        P.shape = opt.fold && !P.fast ? V1Shape::Latency : V1Shape::LatencyUnfolded;
+    // the search progress word is (pass << 16) + rows: rows of a pass must stay below 2^16, else the stagewise search runs
+    // (and, in the tiny regime, the four-lane converge launch behind it all the same)
+    P.fusedSearch = P.fused() && frameSize / 8 < 65536u;
+    const bool tiny = P.shape == V1Shape::Tiny;
+    P.split = tiny && opt.splitCoder && (chains + 63) / 64 * 64 <= kSplitCoderMaxChains && v1_split_at(frameSize) >= 48;
+    P.overlap = tiny && ch == 2 && !P.fast && opt.overlapPos && maxSegPackets > 1 && P.fusedSearch;
+    return P;
+}
+
+const char *v1_regime_name(V1Shape shape)
+{
+    switch (shape) {
+    case V1Shape::Lane: return "lane";
+    case V1Shape::Tiny: return "tiny";
+    case V1Shape::Latency:
+    case V1Shape::LatencyUnfolded: return "latency";
+    case V1Shape::Stagewise: return "stagewise";
+    case V1Shape::Throughput: return "throughput";
     }
-    A.packetBytes = ea.packetBytes;
-    A.flags = vb.flags;
-    A.flagsF = vb.flags;   // one set unless the launcher overlaps positions
-    A.rowReady = nullptr;
-    A.ovRowReady = vb.rowReady;
-    A.ovFlagsF = vb.flagsF;
-    A.ho = vb.ho;
-    A.cls = (ClassInfo *)vb.cls;
-    A.colChain = vb.colChain;
-    A.colsPad = vb.colsPad;
-    {
-        // ALAC_HIP_SPLIT_CODER=0: one coder wave per 64 chains also in the tiny-batch regime
-        const bool split = vb.opt.splitCoder != 0;
-        A.bitWordsB = split ? vb.bitWordsB : nullptr;
-        A.bitsB = vb.bitsB;
-        // the second wave first walks [0, splitAt) keeping only the coder's state (~half the instructions of coding), then
-        // codes the rest: both waves finish together at ~2/3 of the frame; whole 48-residual iterations of the coder loop
-        A.splitAt = (ea.frameSize * 2 / 3) / 48 * 48;
-    }
-    A.pubMask = 0;  // producers publish after every tile, rows written through (a release fence per publish cost ~11 us)
-    A.flags2 = vb.flags;
-    A.dbg = vb.opt.debugWaves ? vb.rowReady : nullptr;  // (the row-ready words are only used by chained tiny batches)
-    A.foldDecide = 0;
-    // rows that live in the workspace and hold no caller state are never read before they are written: the kernels of the first
-    // packet position take init_coefs as constants (load_row) instead of a k_init_state launch writing them first
-    A.virgin = (!vb.stateInitialised && vb.stateInternal) ? 1u : 0u;
-    if (vb.opt.fastMode && channels == 2) A.virgin = 0;  // no search launch takes init_coefs as constants there: write the rows
-    if (!vb.stateInitialised && !A.virgin)
-        hipLaunchKernelGGL(k_init_state, dim3((ea.numSegments * 64 + 255) / 256), dim3(256), 0, st, vb.state,
-                           ea.numSegments);
+    return "";
+}
+
+hipError_t launch_encode_v1(uint32_t depth, uint32_t channels, const V1Args &A, const V1Plan &P, bool initState, const PackArgs &pa,
+                            const V1Streams &vs, uint32_t numPackets, uint32_t maxSegPackets, hipStream_t st, hipEvent_t *ev)
+{
+    if (initState)
+        hipLaunchKernelGGL(k_init_state, dim3((A.S.numSegments * 64 + 255) / 256), dim3(256), 0, st, A.state, A.S.numSegments);
 #define V1_CASE(D)                                                                                   \
     case D:                                                                                          \
         if (channels == 2)                                                                           \
-            launch_v1_typed<D, 2>(A, numPackets, maxSegPackets, st, ev, pa, vs, vb.opt);                 \
+            launch_v1_typed<D, 2>(A, P, numPackets, maxSegPackets, st, ev, pa, vs);                  \
         else                                                                                         \
-            launch_v1_typed<D, 1>(A, numPackets, maxSegPackets, st, ev, pa, vs, vb.opt);                 \
+            launch_v1_typed<D, 1>(A, P, numPackets, maxSegPackets, st, ev, pa, vs);                  \
         break;
     switch (depth) {
         V1_CASE(16)

@@ -1766,190 +1766,167 @@ void v1c_class_layout(int ch, uint32_t nseg, hipStream_t st, const V1Args &A, ui
 void v1c_splice_split(int ch, uint32_t nseg, hipStream_t st, const V1Args &A);
 void v1c_gol_final(int ch, uint32_t cblocks, hipStream_t st, const V1Args &A, uint32_t chanBits);
 template <int DEPTH, int CH>
-void launch_v1_typed(const V1Args &A0, uint32_t numPackets, uint32_t maxSegPackets, hipStream_t st, hipEvent_t *ev,
-                     const PackArgs &pa, const V1Streams &vs, const AlacOptions &opt)
+void launch_v1_typed(const V1Args &A0, const V1Plan &P, uint32_t numPackets, uint32_t maxSegPackets, hipStream_t st, hipEvent_t *ev,
+                     const PackArgs &pa, const V1Streams &vs)
 {
-    constexpr uint32_t chanBits = DEPTH - 8 * bytes_shifted(DEPTH) + (CH == 2 ? 1 : 0);
-    const uint32_t nsegAll = A0.S.numSegments;
+    // Shapes (V1Plan, v1_plan in alac_encode_v1.hip):
+    //  Tiny / Latency  at most ~one predictor wave per SIMD: a stage is as slow as its longest serial chain, so the predictor
+    //                  and the coder that trails it share ONE launch (producer/consumer through HBM).  Tiny batches (a single
+    //                  chained file, a few hundred files side by side) do not even fill one wave per SIMD at 16 chains per
+    //                  wave, so a chain gets FOUR lanes x 2 taps (two lanes for the 4-tap rows of the search) — ~44 instead
+    //                  of ~62 instructions per wave step on every serial chain of the packet position; otherwise two lanes.
+    //                  Latency folds the small launches between the big ones away: the final launch decides numU / numV /
+    //                  escape and the packet sizes itself (k_final_fused<.., FOLD>), and ONE memset clears the progress
+    //                  words of both producer/consumer launches of the position.
+    //  Throughput      many waves per SIMD: every kernel fills the machine by itself, so the stages run as separate launches
+    //                  with plain coalesced stores (the 4-byte write-through hand-off stores of the fused launches are one
+    //                  fabric write each and cap them at ~1 TB/s), a chain's taps sit in one lane (fewest instructions per
+    //                  chain step), the final pass runs per packet class and the coder stores only completed words.
+    //                  125 000 packets: 15.8 -> 10.1 ms.
+    //  Stagewise       one kernel per stage (option fused = 0).
     // (Overlapped sub-batches — halves of the batch on two streams — were measured in rounds 1-3 and lost in both regimes,
-    // 12.3 / 13.6 ms for 2 / 4 against 11.6 at 125 000 packets; removed in round 4.  The whole batch is one "sub-batch".)
-    bool latFoldAny = false;
-    {
-        V1Args A = A0;
-        A.S.segBegin = 0;
-        A.S.segEnd = nsegAll;
-        uint32_t *blockCnt = (uint32_t *)(A0.cls + 1);
-        const uint32_t nseg = nsegAll;
-        const uint32_t cblocks = (nseg * CH + 63) / 64;
-        hipStream_t sh = st;
-        hipEvent_t *evh = ev;  // stage events of the predictor / Golomb stages: block 0 of ev
-        // Chained tiny batches (a file = one chain of packets): packet position p + 1's mixRes search only needs the 8-tap
-        // rows, which position p leaves alone once its own search is over unless it runs its FINAL pass on them — so the
-        // positions alternate between two streams, the search launch of p + 1 starts when decide2 of p has run and its
-        // predictor waves wait, per chain, for rows that p's final pass still owns (rowReady).  The rest of p + 1 waits for
-        // p's final pass.  58-75 % of packets choose 4 taps on both channels: their successor's search (a third of a
-        // position's serial chain) disappears behind the final pass.
-        const bool overlap = opt.overlapPos != 0 && !(CH == 2 && opt.fastMode) && CH == 2 && maxSegPackets > 1 && A.narrow != 0 && A.thru == 0 &&
-                             A.S.frameSize / 8 < 65536u && opt.fused != 0;
-        if (overlap) {
-            A.rowReady = A0.ovRowReady;
-            A.flagsF = A0.ovFlagsF;
-            (void)hipMemsetAsync(A.rowReady, 0, (size_t)A0.chainsPad * 4, sh);
-        }
-        for (uint32_t pos = 0; pos < maxSegPackets; pos++) {
-            A.S.pos = pos;
-            hipStream_t sp = (overlap && (pos & 1)) ? vs.side[0] : sh;
-            if (overlap && pos > 0) (void)hipStreamWaitEvent(sp, vs.stagger[(pos - 1) & 1], 0);  // decide2 of pos - 1
-            hipEvent_t *e = (evh && pos + 1 == maxSegPackets) ? evh : nullptr;
-            const bool firstPos = pos == 0;
-            if (e) (void)hipEventRecord(e[kStageLms1], sp);
-            const bool fused = opt.fused != 0;
-            // Two regimes (A.thru, set by launch_encode_v1 from the batch size):
-            //  latency     at most ~one predictor wave per SIMD: a stage is as slow as its longest serial chain, so the
-            //              predictor and the coder that trails it share ONE launch (producer/consumer through HBM) and a
-            //              chain gets two lanes;
-            //  throughput  many waves per SIMD: every kernel fills the machine by itself, so the stages run as separate
-            //              launches with plain coalesced stores (the 4-byte write-through hand-off stores of the fused
-            //              launches are one fabric write each and cap them at ~1 TB/s), a chain's taps sit in one lane
-            //              (fewest instructions per chain step), the final pass runs per packet class and the coder
-            //              stores only completed words.  125 000 packets: 15.8 -> 10.1 ms.
-            const bool thru = A.thru != 0;
-            const bool fuse = fused && !thru;
-            const uint32_t nLms = (nseg * CH + 31) / 32;
-            // Tiny batches (a single chained file, a few hundred files side by side): the chains do not even fill one
-            // wave per SIMD at 16 chains per wave, so a chain gets FOUR lanes x 2 taps (two lanes for the 4-tap rows of the
-            // search) — ~44 instead of ~62 instructions per wave step on every serial chain of the packet position.
-            const bool narrow = A.narrow != 0 && fuse;
-            const uint32_t nLms16 = (nseg * CH + 15) / 16;
-            A.virgin = firstPos ? A0.virgin : 0u;
-            // Latency regime, two lanes per chain: the small launches between the big ones are folded away ("fold" = 0 keeps
-            // them): the final launch decides numU / numV / escape and the packet sizes itself (k_final_fused<.., FOLD>), and ONE
-            // memset clears the progress words of both producer/consumer launches of the position.
-            const bool fast = CH == 2 && opt.fastMode != 0;  // SetFastMode: no search passes at all (mono has no fast form)
-            const bool foldOk = fuse && !narrow && !fast;
-            const bool latFold = foldOk && opt.fold != 0, oneMemset = latFold;
-            latFoldAny = latFoldAny || latFold;
-            if (foldOk) {
-                A.flags2 = A0.flags + ((A0.chainsPad / 32 + 4) & ~3u);   // behind the (at most chains / 32) words of the search launch
-                A.flagsF = A0.ovFlagsF;                                  // the second set
-                A.foldDecide = latFold ? 1 : 0;
-                if (oneMemset) (void)hipMemsetAsync(A.flags, 0, (size_t)2 * (A0.chainsPad / 8 + 16) * 4, sp);
-            }
-            if (fast) {
-                if (e) {
-                    (void)hipEventRecord(e[kStageGol1], sp);
-                    (void)hipEventRecord(e[kStageLms2], sp);
-                    (void)hipEventRecord(e[kStageGol2], sp);
-                }
-                v1c_decide_fast(nseg, sp, A);
-            } else if constexpr (CH == 2) {
-                const uint32_t nLms1 = nLms;
-                // the search progress word is (pass << 16) + rows: rows of a pass must stay below 2^16
-                if (fuse && narrow && A.S.frameSize / 8 < 65536u) {
-                    (void)hipMemsetAsync(A.flags, 0, ((size_t)nLms16 * 4 + 15) & ~(size_t)15, sp);
-                    hipLaunchKernelGGL((k_search1_fused<DEPTH, 2, 4>), dim3((nLms16 + 5 * cblocks + kWavesPerWg - 1) / kWavesPerWg), dim3(64 * kWavesPerWg), 0, sp, A, nLms16, cblocks,
-                                       chanBits);
-                    if (e) (void)hipEventRecord(e[kStageGol1], sp);
-                } else if (fuse && A.S.frameSize / 8 < 65536u) {
-                    if (!oneMemset) (void)hipMemsetAsync(A.flags, 0, ((size_t)nLms * 4 + 15) & ~(size_t)15, sp);
+    // 12.3 / 13.6 ms for 2 / 4 against 11.6 at 125 000 packets; removed in round 4: every launch covers the whole batch.)
+    constexpr uint32_t chanBits = DEPTH - 8 * bytes_shifted(DEPTH) + (CH == 2 ? 1 : 0);
+    const uint32_t nseg = A0.S.numSegments;
+    const uint32_t cblocks = (nseg * CH + 63) / 64;  // waves of 64 chains
+    const uint32_t nLms = (nseg * CH + 31) / 32;     // ... of 32 chains (two lanes per chain)
+    const uint32_t nLms16 = (nseg * CH + 15) / 16;   // ... of 16 chains (four lanes per chain)
+    const dim3 wg(64 * kWavesPerWg);
+    auto wgs = [](uint32_t waves) { return dim3((waves + kWavesPerWg - 1) / kWavesPerWg); };
+    auto clear = [](uint32_t *words, uint32_t n, hipStream_t s) { (void)hipMemsetAsync(words, 0, ((size_t)n * 4 + 15) & ~(size_t)15, s); };
+    const bool thru = P.shape == V1Shape::Throughput, tiny = P.shape == V1Shape::Tiny, fold = P.shape == V1Shape::Latency;
+    V1Args A = A0;
+    // Chained tiny batches (a file = one chain of packets): packet position p + 1's mixRes search only needs the 8-tap rows,
+    // which position p leaves alone once its own search is over unless it runs its FINAL pass on them — so the positions
+    // alternate between two streams, the search launch of p + 1 starts when decide2 of p has run and its predictor waves
+    // wait, per chain, for rows that p's final pass still owns (rowReady).  The rest of p + 1 waits for p's final pass.
+    // 58-75 % of packets choose 4 taps on both channels: their successor's search (a third of a position's serial chain)
+    // disappears behind the final pass.
+    if (P.overlap) {
+        A.rowReady = A0.ovRowReady;
+        (void)hipMemsetAsync(A.rowReady, 0, (size_t)A0.chainsPad * 4, st);
+    }
+    for (uint32_t pos = 0; pos < maxSegPackets; pos++) {
+        A.S.pos = pos;
+        A.virgin = pos == 0 ? A0.virgin : 0u;
+        const hipStream_t sp = (P.overlap && (pos & 1)) ? vs.side[0] : st;
+        if (P.overlap && pos > 0) (void)hipStreamWaitEvent(sp, vs.stagger[(pos - 1) & 1], 0);  // decide2 of pos - 1
+        hipEvent_t *e = pos + 1 == maxSegPackets ? ev : nullptr;  // stage events of the last position: block 0 of ev
+        auto mark = [&](EncodeStage k) {
+            if (e) (void)hipEventRecord(e[k], sp);
+        };
+        mark(kStageLms1);
+        if (fold) (void)hipMemsetAsync(A.flags, 0, (size_t)2 * (A0.chainsPad / 8 + 16) * 4, sp);  // both sets of progress words
+        // ---- mixRes search (stereo) and numU / numV converge passes, or SetFastMode's decision
+        if (P.fast) {
+            mark(kStageGol1);
+            mark(kStageLms2);
+            mark(kStageGol2);
+            v1c_decide_fast(nseg, sp, A);
+        } else {
+            if constexpr (CH == 2) {
+                if (P.fusedSearch && tiny) {
+                    clear(A.flags, nLms16, sp);
+                    hipLaunchKernelGGL((k_search1_fused<DEPTH, 2, 4>), wgs(nLms16 + 5 * cblocks), wg, 0, sp, A, nLms16, cblocks, chanBits);
+                    mark(kStageGol1);
+                } else if (P.fusedSearch) {
+                    if (!fold) clear(A.flags, nLms, sp);
                     // ONE count wave per 64 chains walks the five planes behind its two producers (WALK)
-                    hipLaunchKernelGGL((k_search1_fused<DEPTH, 4, 2, true>), dim3((3 * cblocks + kWavesPerWg - 1) / kWavesPerWg),
-                                       dim3(64 * kWavesPerWg), 0, sp, A, nLms1, cblocks, chanBits);
-                    if (e) (void)hipEventRecord(e[kStageGol1], sp);
+                    hipLaunchKernelGGL((k_search1_fused<DEPTH, 4, 2, true>), wgs(3 * cblocks), wg, 0, sp, A, nLms, cblocks, chanBits);
+                    mark(kStageGol1);
                 } else if (thru) {
                     // predictor passes and their bit counts in one lane: no residual planes except the mixRes = 4 pass's
                     hipLaunchKernelGGL((k_search1_lane<DEPTH>), dim3(cblocks), dim3(64), 0, sp, A, chanBits);
-                    if (e) (void)hipEventRecord(e[kStageGol1], sp);
+                    mark(kStageGol1);
                 } else {
-                    hipLaunchKernelGGL((k_lms_search1<DEPTH, 4, 2>), dim3(nLms1), dim3(64), 0, sp, A);
-                    if (e) (void)hipEventRecord(e[kStageGol1], sp);
+                    hipLaunchKernelGGL((k_lms_search1<DEPTH, 4, 2>), dim3(nLms), dim3(64), 0, sp, A);
+                    mark(kStageGol1);
                     v1c_gol_count1(CH, cblocks, sp, A, chanBits);
                 }
-            } else if (e) {
-                (void)hipEventRecord(e[kStageGol1], sp);
-            }
-            if (overlap && pos > 0) (void)hipStreamWaitEvent(sp, vs.join[(pos - 1) & 1], 0);  // final pass of pos - 1
-            if (!fast) {
-                if (e) (void)hipEventRecord(e[kStageLms2], sp);
-                const uint32_t nb3 = (nseg * CH + 63) / 64, nb7 = (nseg * CH + 31) / 32;
-                if (narrow)
-                    hipLaunchKernelGGL((k_lms_search2<DEPTH, CH, 2, 2, 2, 4>), dim3(nb7 + nLms16), dim3(64), 0, sp, A, nb7);
-                else if (thru)  // 64 chains per wave for both rows, two waves per SIMD; every lane counts its own residuals
-                    hipLaunchKernelGGL((k_search2_lane<DEPTH, CH>), dim3(nb3 + nb3), dim3(64), 0, sp, A, nb3, chanBits);
-                else if (fuse)  // latency regime: workers (one wave per SIMD by construction)
-                    hipLaunchKernelGGL((k_lms_search2_w<DEPTH, CH>), dim3((3 * nb3 + kWavesPerWg - 1) / kWavesPerWg), dim3(64 * kWavesPerWg), 0, sp, A,
-                                       nb3, nb7);
-                else
-                    hipLaunchKernelGGL((k_lms_search2<DEPTH, CH>), dim3(nb3 + nb7), dim3(64), 0, sp, A, nb3);
-                if (e) (void)hipEventRecord(e[kStageGol2], sp);
-                if (!thru) {
-                    if (fuse)
-                        v1c_gol_count2_w(CH, cblocks, sp, A, chanBits);
-                    else
-                        v1c_gol_count2(CH, cblocks, sp, A, chanBits);
-                }
-                if (!latFold) hipLaunchKernelGGL((k_decide2<DEPTH, CH>), dim3((nseg + 255) / 256), dim3(256), 0, sp, A);
-            }
-            if (overlap) (void)hipEventRecord(vs.stagger[pos & 1], sp);
-            if (e) (void)hipEventRecord(e[kStageLms3], sp);
-            if (thru) {
-                // final pass by packet class: compact the packets that still need it (k_class_count, k_class_assign), then per class the
-                // lane mapping that fits it — escaped packets cost nothing, all-4-tap packets run 64 chains per wave
-                const uint32_t cwaves = (((nseg * CH + 63) & ~63u) + 64) / 64;  // worst case per region, + the padding
-                v1c_class_layout(CH, nseg, sp, A, blockCnt);
-                // the two classes are independent from here on: predictor -> coder of the 4-tap class on a side stream beside
-                // those of the 8-tap class.  Each kernel alone leaves the machine unevenly filled (a few thousand waves of
-                // ~1 ms each on 1024 SIMDs, LDS-limited to 6 predictor waves per CU); side by side the light coder waves
-                // of one class fill what the predictor waves of the other cannot use.
-                hipStream_t s2 = vs.side[0];
-                (void)hipEventRecord(vs.fork, sp);
-                (void)hipStreamWaitEvent(s2, vs.fork, 0);
-                // predictor and coder of a chain in one lane: no residual plane (k_class_final)
-                hipLaunchKernelGGL((k_class_final<DEPTH, CH, 8>), dim3(cwaves), dim3(64), 0, sp, A, chanBits, 0u);
-                hipLaunchKernelGGL((k_class_final<DEPTH, CH, 4>), dim3(cwaves), dim3(64), 0, s2, A, chanBits, 1u);
-                (void)hipEventRecord(vs.join[0], s2);
-                (void)hipStreamWaitEvent(sh, vs.join[0], 0);
-                if (e) (void)hipEventRecord(e[kStageGol3], sp);
-            } else if (narrow) {
-                (void)hipMemsetAsync(A.flagsF, 0, ((size_t)nLms16 * 4 + 15) & ~(size_t)15, sp);
-                if (A.bitWordsB && A.splitAt >= 48) {
-                    hipLaunchKernelGGL((k_final_fused<DEPTH, CH, 2, 4, true>), dim3((nLms16 + 2 * cblocks + kWavesPerWg - 1) / kWavesPerWg), dim3(64 * kWavesPerWg), 0, sp, A, nLms16,
-                                       chanBits, cblocks, nLms16 + 2 * cblocks);
-                    v1c_splice_split(CH, nseg, sp, A);
-                } else {
-                    hipLaunchKernelGGL((k_final_fused<DEPTH, CH, 2, 4>), dim3((5 * cblocks + kWavesPerWg - 1) / kWavesPerWg),
-                                       dim3(64 * kWavesPerWg), 0, sp, A, nLms16, chanBits, 0u, 5 * cblocks);
-                }
-                if (e) (void)hipEventRecord(e[kStageGol3], sp);
-            } else if (latFold) {
-                if (!oneMemset) (void)hipMemsetAsync(A.flagsF, 0, ((size_t)nLms * 4 + 15) & ~(size_t)15, sp);
-                // (LAZY = true, the throughput regime's "store completed words only, four at a time", was measured here in round 3
-                // with the interleaved roles: coder waves 2.20 M instead of 1.70 M cycles, launch 0.95 instead of 0.75 ms — the
-                // queue's selects and branch cost a lone wave more than the scattered stores it saves)
-                hipLaunchKernelGGL((k_final_fused<DEPTH, CH, 4, 2, false, true>), dim3((3 * cblocks + kWavesPerWg - 1) / kWavesPerWg),
-                                   dim3(64 * kWavesPerWg), 0, sp, A, nLms, chanBits, 0u, 3 * cblocks);
-                if (e) (void)hipEventRecord(e[kStageGol3], sp);
-            } else if (fuse) {
-                (void)hipMemsetAsync(A.flagsF, 0, ((size_t)nLms * 4 + 15) & ~(size_t)15, sp);
-                hipLaunchKernelGGL((k_final_fused<DEPTH, CH>), dim3((3 * cblocks + kWavesPerWg - 1) / kWavesPerWg), dim3(64 * kWavesPerWg),
-                                   0, sp, A, nLms, chanBits, 0u, 3 * cblocks);
-                if (e) (void)hipEventRecord(e[kStageGol3], sp);
             } else {
-                hipLaunchKernelGGL((k_lms_final<DEPTH, CH>), dim3((nseg * CH + 31) / 32), dim3(64), 0, sp, A);
-                if (e) (void)hipEventRecord(e[kStageGol3], sp);
-                v1c_gol_final(CH, cblocks, sp, A, chanBits);
+                mark(kStageGol1);
             }
-            if (overlap) {
-                (void)hipEventRecord(vs.join[pos & 1], sp);
-                if (pos + 1 == maxSegPackets && sp != sh) (void)hipStreamWaitEvent(sh, vs.join[pos & 1], 0);
-            }
-            if (e) (void)hipEventRecord(e[kStageScan], sh);  // end marker of this sub-batch's last stage
+            if (P.overlap && pos > 0) (void)hipStreamWaitEvent(sp, vs.join[(pos - 1) & 1], 0);  // final pass of pos - 1
+            mark(kStageLms2);
+            if (tiny)
+                hipLaunchKernelGGL((k_lms_search2<DEPTH, CH, 2, 2, 2, 4>), dim3(nLms + nLms16), dim3(64), 0, sp, A, nLms);
+            else if (thru)  // 64 chains per wave for both rows, two waves per SIMD; every lane counts its own residuals
+                hipLaunchKernelGGL((k_search2_lane<DEPTH, CH>), dim3(2 * cblocks), dim3(64), 0, sp, A, cblocks, chanBits);
+            else if (P.fused())  // latency regime: workers (one wave per SIMD by construction)
+                hipLaunchKernelGGL((k_lms_search2_w<DEPTH, CH>), wgs(3 * cblocks), wg, 0, sp, A, cblocks, nLms);
+            else
+                hipLaunchKernelGGL((k_lms_search2<DEPTH, CH>), dim3(cblocks + nLms), dim3(64), 0, sp, A, cblocks);
+            mark(kStageGol2);
+            if (P.fused())
+                v1c_gol_count2_w(CH, cblocks, sp, A, chanBits);
+            else if (!thru)
+                v1c_gol_count2(CH, cblocks, sp, A, chanBits);
+            if (!fold) hipLaunchKernelGGL((k_decide2<DEPTH, CH>), dim3((nseg + 255) / 256), dim3(256), 0, sp, A);
         }
+        if (P.overlap) (void)hipEventRecord(vs.stagger[pos & 1], sp);
+        // ---- final pass: predictor and entropy coder
+        mark(kStageLms3);
+        switch (P.shape) {
+        case V1Shape::Throughput: {
+            // final pass by packet class: compact the packets that still need it (k_class_count, k_class_assign), then per class
+            // the lane mapping that fits it — escaped packets cost nothing, all-4-tap packets run 64 chains per wave
+            const uint32_t cwaves = (((nseg * CH + 63) & ~63u) + 64) / 64;  // worst case per region, + the padding
+            v1c_class_layout(CH, nseg, sp, A, (uint32_t *)(A0.cls + 1));
+            // the two classes are independent from here on: predictor -> coder of the 4-tap class on a side stream beside
+            // those of the 8-tap class.  Each kernel alone leaves the machine unevenly filled (a few thousand waves of
+            // ~1 ms each on 1024 SIMDs, LDS-limited to 6 predictor waves per CU); side by side the light coder waves
+            // of one class fill what the predictor waves of the other cannot use.
+            hipStream_t s2 = vs.side[0];
+            (void)hipEventRecord(vs.fork, sp);
+            (void)hipStreamWaitEvent(s2, vs.fork, 0);
+            // predictor and coder of a chain in one lane: no residual plane (k_class_final)
+            hipLaunchKernelGGL((k_class_final<DEPTH, CH, 8>), dim3(cwaves), dim3(64), 0, sp, A, chanBits, 0u);
+            hipLaunchKernelGGL((k_class_final<DEPTH, CH, 4>), dim3(cwaves), dim3(64), 0, s2, A, chanBits, 1u);
+            (void)hipEventRecord(vs.join[0], s2);
+            (void)hipStreamWaitEvent(st, vs.join[0], 0);
+            mark(kStageGol3);
+            break;
+        }
+        case V1Shape::Tiny:
+            clear(A.flagsF, nLms16, sp);
+            if (P.split) {
+                hipLaunchKernelGGL((k_final_fused<DEPTH, CH, 2, 4, true>), wgs(nLms16 + 2 * cblocks), wg, 0, sp, A, nLms16, chanBits,
+                                   cblocks, nLms16 + 2 * cblocks);
+                v1c_splice_split(CH, nseg, sp, A);
+            } else {
+                hipLaunchKernelGGL((k_final_fused<DEPTH, CH, 2, 4>), wgs(5 * cblocks), wg, 0, sp, A, nLms16, chanBits, 0u, 5 * cblocks);
+            }
+            mark(kStageGol3);
+            break;
+        case V1Shape::Latency:
+            // (LAZY = true, the throughput regime's "store completed words only, four at a time", was measured here in round 3
+            // with the interleaved roles: coder waves 2.20 M instead of 1.70 M cycles, launch 0.95 instead of 0.75 ms — the
+            // queue's selects and branch cost a lone wave more than the scattered stores it saves)
+            hipLaunchKernelGGL((k_final_fused<DEPTH, CH, 4, 2, false, true>), wgs(3 * cblocks), wg, 0, sp, A, nLms, chanBits, 0u,
+                               3 * cblocks);
+            mark(kStageGol3);
+            break;
+        case V1Shape::LatencyUnfolded:
+            clear(A.flagsF, nLms, sp);
+            hipLaunchKernelGGL((k_final_fused<DEPTH, CH>), wgs(3 * cblocks), wg, 0, sp, A, nLms, chanBits, 0u, 3 * cblocks);
+            mark(kStageGol3);
+            break;
+        default:  // Stagewise (Lane never gets here)
+            hipLaunchKernelGGL((k_lms_final<DEPTH, CH>), dim3(nLms), dim3(64), 0, sp, A);
+            mark(kStageGol3);
+            v1c_gol_final(CH, cblocks, sp, A, chanBits);
+            break;
+        }
+        if (P.overlap) {
+            (void)hipEventRecord(vs.join[pos & 1], sp);
+            if (pos + 1 == maxSegPackets && sp != st) (void)hipStreamWaitEvent(st, vs.join[pos & 1], 0);
+        }
+        if (e) (void)hipEventRecord(e[kStageScan], st);  // end marker of the last stage
     }
     // sizes, scan, pack: once, on the caller's stream; their events live in block 1 of ev
     hipEvent_t *evt = ev ? ev + (size_t)(kNumStages + 1) : nullptr;
     if (evt) (void)hipEventRecord(evt[kStageScan], st);
-    if (!latFoldAny)  // (the folded final launches have written the packet sizes)
+    if (!fold)  // (the folded final launches have written the packet sizes)
         hipLaunchKernelGGL((k_finalize<DEPTH, CH>), dim3((numPackets + 255) / 256), dim3(256), 0, st, A0.recs, A0.packetBytes,
                            numPackets, A0.S.frameSize, pa.segBad);
     launch_scan_pack(DEPTH, CH, A0.packetBytes, pa, numPackets, st, evt, false);

@@ -12,7 +12,7 @@ struct SegView {
     const uint32_t *numSamples;
     const uint32_t *segFirst;
     uint32_t numSegments, frameSize, pos;
-    uint32_t segBegin, segEnd;  // the sub-batch [segBegin, segEnd) this launch works on
+    uint32_t segBegin, segEnd;  // the segments [segBegin, segEnd) this launch works on: always the whole batch
     uint32_t numPackets, segMax;  // bounds every entry of an unvalidated segFirst is tested against (EncodeArgs::segMax)
 };
 
@@ -43,7 +43,7 @@ struct V1Args {
     uint32_t dumpSlot;     // channel slot index (2 * numPackets) no packet owns: bit words of lanes without a packet
     uint32_t *packetBytes;
     uint32_t *flags;       // producer progress words of the fused search launch (zeroed per call)
-    uint32_t *flags2;      // ... of the fused converge launch (k_search2_fused): behind those of the search launch
+    uint32_t *flags2;      // (no kernel reads it)
     uint32_t *dbg;         // option "debug_waves": 8 dwords per workgroup of the fused final launch (null: off)
     uint32_t virgin;       // 1: the coefficient rows have never been written (first packet position, state in the workspace):
                            // load_row takes init_coefs instead of reading them
@@ -52,12 +52,12 @@ struct V1Args {
     uint32_t pubMask;      // producers publish after every (low byte + 1) tiles; bit 31: with a release fence
     uint32_t idleFast;     // 1: lanes without work do not force the checked paths (latency regime, see launcher)
     HandoffCtl ho;         // error word / spin bound / test switch of the in-launch hand-offs
-    uint32_t thru;         // 1: throughput regime (see launch_v1_typed)
-    uint32_t narrow;       // 1: tiny batch: four lanes per chain
+    uint32_t thru;         // 1: V1Shape::Throughput (no kernel reads it)
+    uint32_t narrow;       // 1: V1Shape::Tiny (no kernel reads it)
     // chained tiny batches: the mixRes search of packet position p + 1 runs beside the final pass of position p
     uint32_t *rowReady;    // [chains] position + 1 whose final pass has stored the chain's 8-tap row (0: not used)
     uint32_t *flagsF;      // progress words of the final launch (the search launch next to it uses `flags`)
-    uint32_t *ovRowReady, *ovFlagsF;  // the buffers the launcher switches the two above to when it overlaps positions
+    uint32_t *ovRowReady, *ovFlagsF;  // the row-ready words the launcher switches to when it overlaps positions; = flagsF
     // final pass by packet class (k_class_count, k_class_assign): columns of the residual plane are handed out per class
     ClassInfo *cls;
     uint32_t *colChain;    // [colsPad] chain (segment * CH + channel) of every column, kNoChain for pad columns
@@ -68,10 +68,15 @@ struct V1Args {
     uint32_t splitAt;      // residuals [0, splitAt) belong to the first wave
 };
 
-// search + final passes of every packet position, then finalize / scan / pack (alac_encode_v1_impl.hpp); explicitly
-// instantiated for DEPTH in {16, 20, 24, 32} x CH in {1, 2}
+// search + final passes of every packet position as the plan says, then finalize / scan / pack (alac_encode_v1_impl.hpp);
+// explicitly instantiated for DEPTH in {16, 20, 24, 32} x CH in {1, 2}
 template <int DEPTH, int CH>
-void launch_v1_typed(const V1Args &A0, uint32_t numPackets, uint32_t maxSegPackets, hipStream_t st, hipEvent_t *ev,
-                     const PackArgs &pa, const V1Streams &vs, const AlacOptions &opt);
+void launch_v1_typed(const V1Args &A0, const V1Plan &P, uint32_t numPackets, uint32_t maxSegPackets, hipStream_t st, hipEvent_t *ev,
+                     const PackArgs &pa, const V1Streams &vs);
+// the whole tap-parallel encode of a mono / stereo batch (alac_encode_v1.hip); initState: write init_coefs into the rows first
+// (rows that neither hold the caller's state nor are taken as constants, V1Args::virgin); ev (nullable): kEventBlocks blocks of
+// kNumStages + 1 events
+hipError_t launch_encode_v1(uint32_t depth, uint32_t channels, const V1Args &A, const V1Plan &P, bool initState, const PackArgs &pa,
+                            const V1Streams &vs, uint32_t numPackets, uint32_t maxSegPackets, hipStream_t st, hipEvent_t *ev);
 
 }  // namespace alacdev

@@ -142,26 +142,9 @@ struct AlacOptionKey {
 const AlacOptionKey *alac_option_keys(uint32_t *count);
 const AlacOptionKey *alac_option_find(const char *key);  // nullptr for an unknown key
 
-struct V1Buffers {
-    AlacOptions opt;
-    HandoffCtl ho;
-    int16_t *state;        // [segments][64] working coefficient rows (caller's d_state or workspace)
-    bool stateInitialised; // rows already hold the caller's initial state
-    bool stateInternal;    // the rows live in the workspace: nobody reads entries the pipeline does not write
-    int32_t *resA, *resB, *resC;
-    uint32_t *bits1, *cost2;
-    uint32_t *flags;       // progress words of the fused kernels, one per predictor wave (up to chainsPad / 8 + 16)
-    uint32_t *flagsF;      // second set (final launch) for the overlapped packet positions of a chained batch
-    uint32_t *rowReady;    // [chainsPad] chained batches: packet position + 1 whose final pass has left the chain's 8-tap row
-    uint32_t chainsPad;
-    void *cls;             // ClassInfo of the class-based final pass (alac_encode_v1.hip)
-    uint32_t *colChain;    // [colsPad]
-    uint32_t colsPad;      // chainsPad + 256: the two class regions of the final pass are padded to whole waves
-    uint32_t *bitWordsB;   // tiny batches: bit words of the second coder wave (same layout as EncodeArgs::bitWords), else null
-    uint32_t *bitsB;       // [2 * numPackets + 2]
-};
 // side stream and fork/join events (owned by the context): the second packet class of the throughput regime's final pass runs
 // beside the first, and consecutive packet positions of a chained tiny batch alternate between the two streams
+// (the launcher, launch_encode_v1, is declared with its argument block in alac_encode_v1_types.hpp)
 constexpr uint32_t kSideEvents = 2;
 struct V1Streams {
     hipStream_t side[1];
@@ -173,12 +156,29 @@ constexpr uint32_t kEventBlocks = 2;
 void launch_check_segments(const uint32_t *segFirst, uint32_t numSegments, uint32_t numPackets, uint32_t maxSeg, uint32_t *err,
                            uint32_t *segBad,
                            hipStream_t st);
-bool v1_throughput_regime(uint32_t numSegments, uint32_t channels, const AlacOptions &opt);
-bool v1_narrow_regime(uint64_t chains, uint32_t channels, const AlacOptions &opt);  // four lanes per chain ("tiny") rather than two ("latency")
-// ev (nullable): kEventBlocks blocks of kNumStages + 1 events
-hipError_t launch_encode_v1(uint32_t depth, uint32_t channels, const EncodeArgs &ea, const PackArgs &pa,
-                            const V1Buffers &vb, const V1Streams &vs, uint32_t numPackets, uint32_t maxSegPackets,
-                            hipStream_t st, hipEvent_t *ev);
+// What one mono / stereo encode call launches, decided once on the host (v1_plan, alac_encode_v1.hip):
+//  Lane             the first-generation lane-per-chain encoder (option encoder_lane)
+//  Tiny             four lanes per chain, producer/consumer launches, the final coder split over two waves where it fits
+//  Latency          two lanes per chain, producer/consumer launches, the final launch decides and sizes the packets (fold)
+//  LatencyUnfolded  the same without the fold (option fold = 0, or fast mode): k_decide2 and k_finalize stay
+//  Stagewise        one kernel per stage (option fused = 0)
+//  Throughput       one lane per chain, plain stores, the final pass per packet class
+enum class V1Shape { Lane, Tiny, Latency, LatencyUnfolded, Stagewise, Throughput };
+struct V1Plan {
+    V1Shape shape;
+    bool fast;         // stereo SetFastMode: k_decide_fast in place of every search pass
+    bool fusedSearch;  // Tiny / Latency: the stereo mixRes search in one launch (its progress word counts rows below 2^16)
+    bool split;        // Tiny: the final coder of a chain on two waves
+    bool overlap;      // chained Tiny batch: the search of packet position p + 1 beside the final pass of p
+    bool fused() const { return shape == V1Shape::Tiny || shape == V1Shape::Latency || shape == V1Shape::LatencyUnfolded; }
+};
+// channels: of the stream, > 2 counts as 2 (its elements are encoded as mono / stereo batches)
+V1Plan v1_plan(uint32_t channels, uint32_t numSegments, uint32_t maxSegPackets, uint32_t frameSize, const AlacOptions &opt);
+const char *v1_regime_name(V1Shape shape);  // what alac_hip_encode_regime reports
+// the split coder's buffers exist in the workspace up to this many chains (rounded up to 64)
+constexpr uint32_t kSplitCoderMaxChains = 4096;
+// the second wave of the split coder starts coding at residual splitAt (whole 48-residual iterations, ~2/3 of the frame)
+inline uint32_t v1_split_at(uint32_t frameSize) { return (frameSize * 2 / 3) / 48 * 48; }
 
 // ---- decode ----
 struct DecChan {
@@ -231,11 +231,9 @@ hipError_t launch_verify_finish(const int32_t *status, const uint32_t *numSample
 // numPackets * numChannels * frameSize int32, `prog` = 2 * numPackets + 2 uint32 (progress words of the fused launch;
 // chain list and its two counters where the stages are separate launches)
 // mismatch (nullable): device counter of the packets whose elements are not the expected sequence (status -4), cleared and
-// counted by the pipeline itself; sideStream / fork / join (nullable): the plane and progress-word clears run there beside the
-// staging and header kernels
+// counted by the pipeline itself
 hipError_t launch_decode_v1(const DecodeArgs &da, uint32_t *words, uint64_t capWords, int32_t *plane, uint32_t *prog,
-                            hipStream_t st, uint32_t *mismatch = nullptr, hipStream_t sideStream = nullptr, hipEvent_t fork = nullptr,
-                            hipEvent_t join = nullptr);
+                            hipStream_t st, uint32_t *mismatch);
 
 // ---- > 2 channels (alac_multichannel.hip): a packet is a sequence of mono / stereo elements ----
 struct McElement {
@@ -267,9 +265,6 @@ void launch_mc_tables(const uint32_t *numSamples, uint32_t numPackets, const uin
 // sizes + exclusive scan + bit-granular concatenation of the element packets
 void launch_mc_splice(const McSpliceArgs &a, hipStream_t st);
 void launch_scan_sizes(const uint32_t *sizes, uint64_t *offsets, uint32_t n, hipStream_t st, const uint32_t *segBad = nullptr);
-
-// *count (device) = number of packets whose status is `code`
-hipError_t launch_count_status(const int32_t *status, uint32_t n, int32_t code, uint32_t *count, hipStream_t st);
 
 // a stream of 3..8 channels on the second-generation decoder: one pass per element of the channel count's element
 // sequence, element r of every packet decoded as the mono / stereo packet that starts where element r - 1 ended

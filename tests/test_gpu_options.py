@@ -56,3 +56,30 @@ def test_options_belong_to_one_context_and_steer_the_regime():
     assert b.regime(fmt, 10000) == "latency"
     with b.options(fused=0):  # the launcher's predicate: narrow only counts while the launches are fused
         assert b.regime(fmt, 100) == "stagewise" and b.regime(fmt, 10000) == "stagewise" and b.regime(fmt, 125000) == "throughput"
+
+
+# alac_hip_encode_regime over channels x segment counts x options, pinned to what the launcher has always run: the segment
+# counts sit on both sides of the four-lane / two-lane windows (v1_narrow_regime: mono 10 240 / 21 760 / 26 112 chains, stereo
+# 11 264 / 21 760 / 34 816) and of the throughput regime (65 536 chains); 6 channels count as stereo.
+# T tiny, L latency, H throughput, S stagewise, N lane
+REGIME_SEGMENTS = [100, 5632, 10880, 10881, 17408, 17409, 26113, 32769, 65537]
+REGIME_TABLE = [
+    ({}, {1: "TTLLLLLLH", 2: "TTLTTLLHH", 6: "TTLTTLLHH"}),
+    ({"thru": 0}, {1: "TTLLLLLLL", 2: "TTLTTLLLL", 6: "TTLTTLLLL"}),
+    ({"narrow": 0}, {1: "LLLLLLLLH", 2: "LLLLLLLHH", 6: "LLLLLLLHH"}),
+    ({"fused": 0}, {1: "SSSSSSSSH", 2: "SSSSSSSHH", 6: "SSSSSSSHH"}),
+    ({"fold": 0}, {1: "TTLLLLLLH", 2: "TTLTTLLHH", 6: "TTLTTLLHH"}),
+    ({"fast_mode": 1}, {1: "TTLLLLLLH", 2: "TTLTTLLHH", 6: "TTLTTLLHH"}),
+    ({"encoder_lane": 1}, {1: "NNNNNNNNN", 2: "NNNNNNNNN", 6: "NNNNNNNNN"}),
+]
+
+
+@pytest.mark.parametrize("opts,want", REGIME_TABLE)
+def test_regime_table(opts, want):
+    names = {"T": "tiny", "L": "latency", "H": "throughput", "S": "stagewise", "N": "lane"}
+    ctx = alac_amd.Context(0)
+    with ctx.options(**opts):
+        for ch, row in want.items():
+            fmt = alac_amd.make_format(4096, 16, ch, 44100)
+            got = [ctx.regime(fmt, s) for s in REGIME_SEGMENTS]
+            assert got == [names[c] for c in row], (opts, ch)
