@@ -75,6 +75,8 @@ SIGNATURES = {
     "alac_hip_encode_host_segments": (_i32, [_vp, C.POINTER(Format), _vp, _vp, _u32, _vp, _u32, _vp, _i32, _vp, _u64, _vp,
                                              C.POINTER(_u64)]),
     "alac_hip_decode_host": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "alac_hip_decode_float": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "alac_hip_decode_float_host": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _vp]),
     "alac_hip_verify_workspace_bytes_stream": (_u64, [C.POINTER(Format), _u32, _u64]),
     "alac_hip_verify": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "alac_hip_verify_host": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
@@ -392,6 +394,43 @@ class Context:
             self._check(rc)
             for x in (pcm, ns, st):
                 x.record_stream(cur)  # allocated on self.stream, consumed on the caller's
+            return pcm, ns, st, fmt
+
+    def decode_float(self, cookie, stream, offsets, num_packets, zero_fill=True, out=None, channel_stride=None):
+        """decode() straight to planar float32 (alac_hip_decode_float): sample / 2^(bit_depth - 1), what torchaudio.load
+        returns.  Returns (pcm float32 tensor [channels, num_packets * frame_size], num_samples int32, status int32, fmt).
+        channel_stride: floats between two channels' rows (default num_packets * frame_size); with a larger one pcm is a
+        view of the [channels, channel_stride] buffer.  zero_fill=False leaves the samples behind a short packet's frames
+        uninitialised.  out=(buffer, num_samples, status): write into these tensors instead of allocating; buffer is a
+        float32 cuda tensor of at least (channels - 1) * channel_stride + num_packets * frame_size elements."""
+        with self._call() as cur:
+            t = self.torch
+            ck = np.ascontiguousarray(cookie, np.uint8)
+            fmt = Format()
+            self._check(self.lib.alac_hip_format_from_cookie(ck.ctypes.data, ck.size, C.byref(fmt)))
+            frames = num_packets * fmt.frame_size
+            stride = frames if channel_stride is None else int(channel_stride)
+            need = (fmt.num_channels - 1) * stride + frames
+            if out is not None:
+                buf, ns, st = out
+                if buf.dtype != t.float32 or not buf.is_contiguous():
+                    raise ValueError("decode_float: out buffer must be a contiguous float32 tensor")
+                if buf.numel() < need or ns.numel() < num_packets or st.numel() < num_packets:
+                    raise ValueError("decode_float: output tensors too small")
+            else:
+                alloc = t.zeros if zero_fill else t.empty
+                buf = alloc(max(fmt.num_channels * stride, need), dtype=t.float32, device=self.device)
+                ns = t.zeros(num_packets, dtype=t.int32, device=self.device)
+                st = t.zeros(num_packets, dtype=t.int32, device=self.device)
+            wsb = int(self.lib.alac_hip_decode_workspace_bytes_stream(C.byref(fmt), num_packets, int(stream.numel())))
+            ws = self._workspace(wsb)
+            rc = self.lib.alac_hip_decode_float(self.h, ck.ctypes.data, ck.size, stream.data_ptr(), offsets.data_ptr(),
+                                                num_packets, ws.data_ptr(), ws.numel(), buf.data_ptr(), stride,
+                                                ns.data_ptr(), st.data_ptr())
+            self._check(rc)
+            for x in (buf, ns, st):
+                x.record_stream(cur)
+            pcm = buf.as_strided((fmt.num_channels, frames), (stride, 1))
             return pcm, ns, st, fmt
 
     def verify(self, cookie, stream, offsets, num_packets, pcm, num_samples=None):

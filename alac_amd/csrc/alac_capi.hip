@@ -4,6 +4,7 @@
 #include "alac_hip.h"
 #include "alac_dev.hpp"
 #include "alac_kernels.hpp"
+#include "alac_verify.hpp"
 #include "alac_encode_v1_types.hpp"
 
 #include <cstdio>
@@ -997,10 +998,13 @@ int32_t cookie_format(alac_hip_ctx *ctx, const uint8_t *cookie, uint32_t size, a
     return ALAC_HIP_noErr;
 }
 
-// alac_hip_decode, and alac_hip_verify's decode pass (verifyMismatch non-null: d_pcm_out is the expected PCM, only read)
+// alac_hip_decode (kPcmStore), alac_hip_verify's decode pass (kPcmVerify: d_pcm_out is the expected PCM, only read, and
+// verifyMismatch the first-mismatch words) and alac_hip_decode_float (kPcmFloat: d_pcm_out is planar float32, channel rows
+// channelStride floats apart)
 int32_t decode_impl(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
                     const uint64_t *d_packet_offsets, uint32_t num_packets, void *d_workspace, uint64_t workspace_bytes,
-                    uint8_t *d_pcm_out, uint32_t *d_num_samples_out, int32_t *d_status, uint32_t *verifyMismatch)
+                    uint8_t *d_pcm_out, uint32_t *d_num_samples_out, int32_t *d_status, PcmMode mode,
+                    uint32_t *verifyMismatch = nullptr, uint64_t channelStride = 0)
 {
     if (!ctx) return ALAC_HIP_ParamError;
     alac_hip_format fmt;
@@ -1041,7 +1045,9 @@ int32_t decode_impl(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_
     da.optFused = ctx->opt.decFused;
     da.optPair = ctx->opt.decPair;
     da.optDirect = ctx->opt.decDirect;
-    da.firstMismatch = verifyMismatch;
+    da.pcmMode = mode;
+    if (mode == kPcmVerify) da.firstMismatch = verifyMismatch;
+    if (mode == kPcmFloat) da.channelStride = channelStride;
     da.frameBytes = fmt.num_channels * bytes_per_sample(fmt.bit_depth);
     hipError_t e;
     if (use_lane_decoder(ctx)) {
@@ -1083,7 +1089,27 @@ int32_t alac_hip_decode(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t coo
                         int32_t *d_status)
 {
     return decode_impl(ctx, h_cookie, cookie_size, d_stream, d_packet_offsets, num_packets, d_workspace, workspace_bytes,
-                       d_pcm_out, d_num_samples_out, d_status, nullptr);
+                       d_pcm_out, d_num_samples_out, d_status, kPcmStore);
+}
+
+// ---- decode to planar float32: alac_hip_decode with the PCM store sites writing scaled floats ----------------------------
+int32_t alac_hip_decode_float(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
+                              const uint64_t *d_packet_offsets, uint32_t num_packets, void *d_workspace,
+                              uint64_t workspace_bytes, float *d_out, uint64_t channel_stride, uint32_t *d_num_samples_out,
+                              int32_t *d_status)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    alac_hip_format fmt;
+    if (int32_t rc = cookie_format(ctx, h_cookie, cookie_size, fmt)) return rc;
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (!d_out) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if ((uintptr_t)d_out & 3) return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
+    if (channel_stride < (uint64_t)num_packets * fmt.frame_size)
+        return fail(ctx, ALAC_HIP_ParamError, "channel_stride below num_packets * frame_size");
+    if (channel_stride > UINT64_MAX / sizeof(float) / fmt.num_channels)
+        return fail(ctx, ALAC_HIP_ParamError, "channel_stride * channels overflows");
+    return decode_impl(ctx, h_cookie, cookie_size, d_stream, d_packet_offsets, num_packets, d_workspace, workspace_bytes,
+                       (uint8_t *)d_out, d_num_samples_out, d_status, kPcmFloat, nullptr, channel_stride);
 }
 
 // ---- verify: alac_hip_decode with the PCM store sites comparing against the caller's PCM ------------------------------
@@ -1126,7 +1152,7 @@ int32_t alac_hip_verify(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t coo
     if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
     const int32_t rc = decode_impl(ctx, h_cookie, cookie_size, d_stream, d_packet_offsets, num_packets, ws + nsBytes,
                                    workspace_bytes - nsBytes, const_cast<uint8_t *>(d_pcm_expected), ns, d_status,
-                                   d_first_mismatch);
+                                   kPcmVerify, d_first_mismatch);
     if (rc != ALAC_HIP_noErr) return rc;
     e = launch_verify_finish(d_status, ns, d_num_samples_expected, fmt.frame_size, num_packets, d_first_mismatch, d_bad_packets,
                              ctx->stream);
@@ -1319,6 +1345,44 @@ int32_t alac_hip_decode_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_
     return check_handoff(ctx);
 }
 
+int32_t alac_hip_decode_float_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size,
+                                   const uint8_t *h_stream, const uint32_t *h_packet_bytes, uint32_t num_packets, float *h_out,
+                                   uint64_t channel_stride, uint32_t *h_num_samples_out, int32_t *h_status)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    alac_hip_format fmt;
+    if (alac_hip_format_from_cookie(h_cookie, cookie_size, &fmt) != ALAC_HIP_noErr || !format_ok(&fmt))
+        return fail(ctx, ALAC_HIP_ParamError, "bad magic cookie");
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (!h_stream || !h_packet_bytes || !h_out || !h_num_samples_out || !h_status)
+        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    const uint64_t row = (uint64_t)num_packets * fmt.frame_size;  // floats of one channel
+    if (channel_stride < row) return fail(ctx, ALAC_HIP_ParamError, "channel_stride below num_packets * frame_size");
+    if (channel_stride > UINT64_MAX / sizeof(float) / fmt.num_channels)
+        return fail(ctx, ALAC_HIP_ParamError, "channel_stride * channels overflows");
+    DevStream d;
+    if (int32_t rc = upload_stream(ctx, fmt, h_stream, h_packet_bytes, num_packets, d)) return rc;
+    // on the device the rows lie back to back; the copy back puts them channel_stride floats apart and leaves the gap alone
+    const uint64_t outBytes = row * fmt.num_channels * sizeof(float);
+    const uint64_t wsBytes = alac_hip_decode_workspace_bytes_stream(&fmt, num_packets, d.total);
+    DevBuf dWs, dOut, dNs, dSt;
+    hipError_t e;
+    if ((e = dWs.alloc(wsBytes)) || (e = dOut.alloc(outBytes)) || (e = dNs.alloc(num_packets * 4ull)) ||
+        (e = dSt.alloc(num_packets * 4ull)))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    hipStream_t st = ctx->stream;
+    if ((e = hipMemsetAsync(dOut.p, 0, outBytes, st))) return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    int32_t rc = alac_hip_decode_float(ctx, h_cookie, cookie_size, (const uint8_t *)d.bytes.p, (const uint64_t *)d.offs.p,
+                                       num_packets, dWs.p, wsBytes, (float *)dOut.p, row, (uint32_t *)dNs.p, (int32_t *)dSt.p);
+    if (rc != ALAC_HIP_noErr) return rc;
+    if ((e = hipMemcpy2DAsync(h_out, channel_stride * sizeof(float), dOut.p, row * sizeof(float), row * sizeof(float),
+                              fmt.num_channels, hipMemcpyDeviceToHost, st)) ||
+        (e = hipMemcpyAsync(h_num_samples_out, dNs.p, num_packets * 4ull, hipMemcpyDeviceToHost, st)) ||
+        (e = hipMemcpyAsync(h_status, dSt.p, num_packets * 4ull, hipMemcpyDeviceToHost, st)) ||
+        (e = hipStreamSynchronize(st)))
+        return fail(ctx, ALAC_HIP_ParamError, "decode execution", e);
+    return check_handoff(ctx);
+}
 int32_t alac_hip_verify_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *h_stream,
                              const uint32_t *h_packet_bytes, uint32_t num_packets, const uint8_t *h_pcm_expected,
                              const uint32_t *h_num_samples_expected, uint32_t *h_first_mismatch, int32_t *h_status)

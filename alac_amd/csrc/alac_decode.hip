@@ -280,22 +280,22 @@ __global__ __launch_bounds__(64) void k_decode_unpc(DecodeArgs A)
 
 // ---- un-mix + pack (gpu_unmixNN / gpu_copyPredictorToNN, codec/ALACDecoder.cu:193-495) --------
 
-template <int DEPTH, bool VERIFY>
+template <int DEPTH, PcmMode MODE>
 __device__ __forceinline__ void store_sample(const DecodeArgs &A, uint8_t *p, int32_t x)
 {
     if constexpr (DEPTH == 16) {
-        PCM_PUT(VERIFY, A, (int16_t *)p, (int16_t)x);
+        PCM_PUT(MODE, A, (int16_t *)p, (int16_t)x);
     } else if constexpr (DEPTH == 32) {
-        PCM_PUT(VERIFY, A, (int32_t *)p, x);
+        PCM_PUT(MODE, A, (int32_t *)p, x);
     } else {
         if constexpr (DEPTH == 20) x = (int32_t)((uint32_t)x << 4);
-        PCM_PUT(VERIFY, A, p, (uint8_t)x);
-        PCM_PUT(VERIFY, A, p + 1, (uint8_t)(x >> 8));
-        PCM_PUT(VERIFY, A, p + 2, (uint8_t)(x >> 16));
+        PCM_PUT(MODE, A, p, (uint8_t)x);
+        PCM_PUT(MODE, A, p + 1, (uint8_t)(x >> 8));
+        PCM_PUT(MODE, A, p + 2, (uint8_t)(x >> 16));
     }
 }
 
-template <int DEPTH, int CH, bool VERIFY>
+template <int DEPTH, int CH, PcmMode MODE>
 __global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A)
 {
     if (A.gate && *A.gate == 0) return;
@@ -353,8 +353,13 @@ __global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A)
             l = (int32_t)(((uint32_t)l << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
             if constexpr (CH == 2) r = (int32_t)(((uint32_t)r << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
         }
-        store_sample<DEPTH, VERIFY>(A, op, l);
-        if constexpr (CH == 2) store_sample<DEPTH, VERIFY>(A, op + BPS, r);
+        if constexpr (MODE == kPcmFloat) {
+            pcm_float_row(A, 0, p)[j] = pcm_float<DEPTH>(l);
+            if constexpr (CH == 2) pcm_float_row(A, 1, p)[j] = pcm_float<DEPTH>(r);
+        } else {
+            store_sample<DEPTH, MODE>(A, op, l);
+            if constexpr (CH == 2) store_sample<DEPTH, MODE>(A, op + BPS, r);
+        }
     }
     __syncthreads();
     }
@@ -363,7 +368,7 @@ __global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A)
 // > 2 channels: the same tile walk once per output channel c; a packet's element that STARTS at c is un-mixed and
 // written at channel c (and c + 1) of the numChannels-interleaved frame (unmixNN / copyPredictorToNN with stride
 // numChannels, codec/ALACDecoder.cu:733-753,:900-935); channels no element carries are zero (:971-998).
-template <int DEPTH, bool VERIFY>
+template <int DEPTH, PcmMode MODE>
 __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A)
 {
     if (A.gate && *A.gate == 0) return;
@@ -397,7 +402,10 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A)
             uint8_t *op = A.pcmOut + (((uint64_t)p * A.frameSize + j) * nch + c) * BPS;
             if (!rec) {
                 const uint32_t ns = A.recs[p].elementChannels ? A.recs[p].numSamples : A.frameSize;
-                if (j < ns) store_sample<DEPTH, VERIFY>(A, op, 0);
+                if (j < ns) {
+                    if constexpr (MODE == kPcmFloat) pcm_float_row(A, c, p)[j] = 0.0f;
+                    else store_sample<DEPTH, MODE>(A, op, 0);
+                }
                 continue;
             }
             if (rec->chanIndex != c || j >= rec->numSamples) continue;
@@ -418,15 +426,20 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A)
                 l = (int32_t)(((uint32_t)l << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
                 if (ech == 2) r = (int32_t)(((uint32_t)r << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
             }
-            store_sample<DEPTH, VERIFY>(A, op, l);
-            if (ech == 2) store_sample<DEPTH, VERIFY>(A, op + BPS, r);
+            if constexpr (MODE == kPcmFloat) {
+                pcm_float_row(A, c, p)[j] = pcm_float<DEPTH>(l);
+                if (ech == 2) pcm_float_row(A, c + 1, p)[j] = pcm_float<DEPTH>(r);
+            } else {
+                store_sample<DEPTH, MODE>(A, op, l);
+                if (ech == 2) store_sample<DEPTH, MODE>(A, op + BPS, r);
+            }
         }
         __syncthreads();
     }
     }
 }
 
-template <int DEPTH, bool VERIFY>
+template <int DEPTH, PcmMode MODE>
 static void launch_unmix_depth(const DecodeArgs &da, hipStream_t st)
 {
     dim3 grid((da.numPackets + 63) / 64, (da.frameSize + 63) / 64);
@@ -434,23 +447,23 @@ static void launch_unmix_depth(const DecodeArgs &da, hipStream_t st)
     // two channels may arrive as one CPE or as two SCE / LFE elements (codec/ALACDecoder.cu:622-756): the per-element
     // kernel follows the records, k_decode_unmix<., 2> would take the packet for one pair
     if (da.numChannels >= 2)
-        hipLaunchKernelGGL((k_decode_unmix_mc<DEPTH, VERIFY>), grid, dim3(256), 0, st, da);
+        hipLaunchKernelGGL((k_decode_unmix_mc<DEPTH, MODE>), grid, dim3(256), 0, st, da);
     else
-        hipLaunchKernelGGL((k_decode_unmix<DEPTH, 1, VERIFY>), grid, dim3(256), 0, st, da);
+        hipLaunchKernelGGL((k_decode_unmix<DEPTH, 1, MODE>), grid, dim3(256), 0, st, da);
 }
 
-// VERIFY: the un-mix instantiations whose store sites compare instead (alac_verify.hpp)
-template <bool VERIFY>
+// MODE: the un-mix instantiations whose store sites store, compare or write planar floats (alac_verify.hpp)
+template <PcmMode MODE>
 static hipError_t launch_decode_lanes(const DecodeArgs &da, hipStream_t st)
 {
     hipLaunchKernelGGL(k_decode_entropy, dim3((da.numPackets + 63) / 64), dim3(64), 0, st, da);
     const uint64_t lanes = (uint64_t)da.numPackets * da.numChannels;
     hipLaunchKernelGGL(k_decode_unpc, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, st, da);
     switch (da.bitDepth) {
-    case 16: launch_unmix_depth<16, VERIFY>(da, st); break;
-    case 20: launch_unmix_depth<20, VERIFY>(da, st); break;
-    case 24: launch_unmix_depth<24, VERIFY>(da, st); break;
-    case 32: launch_unmix_depth<32, VERIFY>(da, st); break;
+    case 16: launch_unmix_depth<16, MODE>(da, st); break;
+    case 20: launch_unmix_depth<20, MODE>(da, st); break;
+    case 24: launch_unmix_depth<24, MODE>(da, st); break;
+    case 32: launch_unmix_depth<32, MODE>(da, st); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -459,8 +472,12 @@ static hipError_t launch_decode_lanes(const DecodeArgs &da, hipStream_t st)
 hipError_t launch_decode(const DecodeArgs &da, hipStream_t st)
 {
     if (da.numPackets == 0) return hipSuccess;
-    // verify mode (alac_hip_verify) when the caller passes its first-mismatch words
-    return da.firstMismatch ? launch_decode_lanes<true>(da, st) : launch_decode_lanes<false>(da, st);
+    switch (da.pcmMode) {
+    case kPcmStore: return launch_decode_lanes<kPcmStore>(da, st);
+    case kPcmVerify: return launch_decode_lanes<kPcmVerify>(da, st);   // alac_hip_verify
+    case kPcmFloat: return launch_decode_lanes<kPcmFloat>(da, st);     // alac_hip_decode_float
+    default: return hipErrorInvalidValue;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -500,7 +500,7 @@ __global__ __launch_bounds__(64 * kHdrWaves) void k_dec_header(DecV1Args V)
 
 // ---- k_dec_raw: uncompressed (escape) elements are fixed-width fields, i.e. not serial at all: one thread per
 // sample-frame reads its fields straight from the staged words (codec/ALACDecoder.cu:697-727 / :856-896)
-template <bool DIRECT, bool VERIFY>
+template <bool DIRECT, PcmMode MODE>
 __device__ __forceinline__ void raw_body(const DecV1Args &V, uint32_t p, uint32_t first, uint32_t step)
 {
     const DecodeArgs &A = V.d;
@@ -547,8 +547,20 @@ __device__ __forceinline__ void raw_body(const DecV1Args &V, uint32_t p, uint32_
                 const uint32_t v = (uint32_t)(((((uint64_t)x[k] << 32) | x[k + 1]) << s) >> 32);
                 o[k] = (v >> 16) | (v << 16);
             }
-            const U4 t4 = {o[0], o[1], o[2], o[3]};
-            PCM_PUT(VERIFY, A, (U4 *)(pcm + 4 * (uint64_t)g), t4);
+            if constexpr (MODE == kPcmFloat) {
+                // the four frames' L (high halves of v) and R (low halves), one 16-byte store per channel
+                int32_t fl[4], fr[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    fl[k] = (int32_t)(o[k] & 0xffffu);
+                    fr[k] = (int32_t)(o[k] >> 16);
+                }
+                pcm_float_run<16>(pcm_float_row(A, 0, p), 4 * g, n, fl);
+                pcm_float_run<16>(pcm_float_row(A, 1, p), 4 * g, n, fr);
+            } else {
+                const U4 t4 = {o[0], o[1], o[2], o[3]};
+                PCM_PUT(MODE, A, (U4 *)(pcm + 4 * (uint64_t)g), t4);
+            }
         }
         done = safe * 4;
     }
@@ -579,7 +591,14 @@ __device__ __forceinline__ void raw_body(const DecV1Args &V, uint32_t p, uint32_
                     if (!direct) (rowU + c * A.frameSize)[j] = (int32_t)(v << (32 - w)) >> (32 - w);
                 }
             }
-            if (direct && j < n) PCM_PUT(VERIFY, A, pcm + j, f[0] | (f[1] << 16));
+            if constexpr (MODE == kPcmFloat) {
+                if (direct && j < n) {  // direct: 16-bit fields (pad2)
+                    pcm_float_row(A, 0, p)[j] = pcm_float<16>((int32_t)f[0]);
+                    pcm_float_row(A, 1, p)[j] = pcm_float<16>((int32_t)f[1]);
+                }
+            } else {
+                if (direct && j < n) PCM_PUT(MODE, A, pcm + j, f[0] | (f[1] << 16));
+            }
         }
     }
 }
@@ -591,15 +610,15 @@ __device__ __host__ inline uint32_t blocks_per_packet(uint32_t frameSize) { retu
 // packet (times the blocks of a frame) spent the launch on workgroups that read one record and left — 1.23 ms for
 // 500 000 workgroups at 125 000 packets, 15 600 of them with work.
 // (round 3: the packets come from k_dec_header's list of uncompressed elements, so nobody reads records to find them)
-template <bool VERIFY>
+template <PcmMode MODE>
 __global__ __launch_bounds__(256) void k_dec_raw(DecV1Args V)
 {
     const DecLists L = dec_lists(V);
     const uint32_t count = L.cnt[4];
     if (V.raw) {  // wave-uniform
-        for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) raw_body<true, VERIFY>(V, L.raw[i], threadIdx.x, blockDim.x);
+        for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) raw_body<true, MODE>(V, L.raw[i], threadIdx.x, blockDim.x);
     } else {
-        for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) raw_body<false, VERIFY>(V, L.raw[i], threadIdx.x, blockDim.x);
+        for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) raw_body<false, MODE>(V, L.raw[i], threadIdx.x, blockDim.x);
     }
 }
 
@@ -1524,7 +1543,7 @@ __device__ __forceinline__ int32_t lms_step_dec_pair(int32_t (&a)[T], int32_t (&
     return out;
 }
 
-template <int T, int DEPTH = 16, bool VERIFY = false>
+template <int T, int DEPTH = 16, PcmMode MODE = kPcmStore>
 __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t block, uint32_t count)
 {
     const DecodeArgs &A = V.d;
@@ -1573,6 +1592,7 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
                 for (int q = 0; q <= K / 4; q++) sw[q] = dec_word(V, sTail, i0 + q);
             }
             uint32_t fld[K];  // L0 R0 L1 R1 ... as 24-bit little-endian fields
+            int32_t fl[K / 2], fr[K / 2];  // float mode: the samples themselves, before the 20-bit left-justification
 #pragma unroll
             for (int k = 0; k < K / 2; k++) {
                 const int32_t give = isU ? o[k + K / 2] : o[k];
@@ -1590,15 +1610,26 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
                         l = (int32_t)(((uint32_t)l << 8) | (xx >> 8));
                         r = (int32_t)(((uint32_t)r << 8) | (xx & 0xffu));
                     }
-                } else {
+                } else if constexpr (MODE != kPcmFloat) {
                     l = (int32_t)((uint32_t)l << 4);  // 20 bits, left-justified in three bytes (gpu_unmix20 :225-280)
                     r = (int32_t)((uint32_t)r << 4);
                 }
-                fld[2 * k] = (uint32_t)l & 0xffffffu;
-                fld[2 * k + 1] = (uint32_t)r & 0xffffffu;
+                if constexpr (MODE == kPcmFloat) {
+                    fl[k] = l;
+                    fr[k] = r;
+                } else {
+                    fld[2 * k] = (uint32_t)l & 0xffffffu;
+                    fld[2 * k + 1] = (uint32_t)r & 0xffffffu;
+                }
             }
             uint8_t *dst = pcm3 + (uint64_t)f0 * 6;
-            if (active && f0 + (uint32_t)(K / 2) <= n) {
+            if constexpr (MODE == kPcmFloat) {
+                // K / 2 frames of each channel: 16-byte stores, the last frames of a short packet one by one
+                if (active) {
+                    pcm_float_run<DEPTH>(pcm_float_row(A, 0, p), f0, n, fl);
+                    pcm_float_run<DEPTH>(pcm_float_row(A, 1, p), f0, n, fr);
+                }
+            } else if (active && f0 + (uint32_t)(K / 2) <= n) {
                 // four 3-byte fields make three words; K fields = 3 K / 4 words = 3 K / 16 sixteen-byte stores
                 typedef uint32_t U4s __attribute__((ext_vector_type(4), aligned(4)));
                 uint32_t d[3 * K / 4];
@@ -1612,7 +1643,7 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
 #pragma unroll
                 for (int q = 0; q < 3 * K / 16; q++) {
                     const U4s t4 = {d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]};
-                    PCM_PUT(VERIFY, A, (U4s *)(dst + 16 * q), t4);
+                    PCM_PUT(MODE, A, (U4s *)(dst + 16 * q), t4);
                 }
             } else if (active) {
                 // the last frames of a short packet
@@ -1622,9 +1653,9 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
 #pragma unroll
                         for (int c2 = 0; c2 < 2; c2++) {
                             const uint32_t v3 = fld[2 * k + c2];
-                            PCM_PUT(VERIFY, A, dst + 6 * k + 3 * c2, (uint8_t)v3);
-                            PCM_PUT(VERIFY, A, dst + 6 * k + 3 * c2 + 1, (uint8_t)(v3 >> 8));
-                            PCM_PUT(VERIFY, A, dst + 6 * k + 3 * c2 + 2, (uint8_t)(v3 >> 16));
+                            PCM_PUT(MODE, A, dst + 6 * k + 3 * c2, (uint8_t)v3);
+                            PCM_PUT(MODE, A, dst + 6 * k + 3 * c2 + 1, (uint8_t)(v3 >> 8));
+                            PCM_PUT(MODE, A, dst + 6 * k + 3 * c2 + 2, (uint8_t)(v3 >> 16));
                         }
                     }
                 }
@@ -1632,6 +1663,7 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
             return;
         }
         uint32_t word[K / 2];
+        int32_t fl[K / 2], fr[K / 2];  // float mode: the samples themselves
 #pragma unroll
         for (int k = 0; k < K / 2; k++) {
             const int32_t give = isU ? o[k + K / 2] : o[k];
@@ -1640,19 +1672,31 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
             const int32_t uu = isU ? mine : recv, vv = isU ? recv : mine;
             const int32_t l = uu + ((vv - ((mixRes * vv) >> mixBits)) & mixMask);
             const int32_t r = mixRes != 0 ? l - vv : vv;
-            word[k] = __builtin_amdgcn_perm((uint32_t)r, (uint32_t)l, 0x05040100u);
+            if constexpr (MODE == kPcmFloat) {
+                fl[k] = l;
+                fr[k] = r;
+            } else {
+                word[k] = __builtin_amdgcn_perm((uint32_t)r, (uint32_t)l, 0x05040100u);
+            }
         }
         const uint32_t f0 = jb + (isU ? 0u : (uint32_t)(K / 2));
+        if constexpr (MODE == kPcmFloat) {
+            if (active) {
+                pcm_float_run<16>(pcm_float_row(A, 0, p), f0, n, fl);
+                pcm_float_run<16>(pcm_float_row(A, 1, p), f0, n, fr);
+            }
+        } else {
 #pragma unroll
-        for (int q = 0; q < K / 8; q++) {
-            const uint32_t f = f0 + 4 * q;
-            if (active && f + 4 <= n) {
-                const U4 t4 = {word[4 * q], word[4 * q + 1], word[4 * q + 2], word[4 * q + 3]};
-                PCM_PUT(VERIFY, A, (U4 *)(pcm + f), t4);
-            } else if (active && f < n) {
+            for (int q = 0; q < K / 8; q++) {
+                const uint32_t f = f0 + 4 * q;
+                if (active && f + 4 <= n) {
+                    const U4 t4 = {word[4 * q], word[4 * q + 1], word[4 * q + 2], word[4 * q + 3]};
+                    PCM_PUT(MODE, A, (U4 *)(pcm + f), t4);
+                } else if (active && f < n) {
 #pragma unroll
-                for (int e = 0; e < 4; e++)
-                    if (f + e < n) PCM_PUT(VERIFY, A, pcm + f + e, word[4 * q + e]);
+                    for (int e = 0; e < 4; e++)
+                        if (f + e < n) PCM_PUT(MODE, A, pcm + f + e, word[4 * q + e]);
+                }
             }
         }
     };
@@ -1728,18 +1772,18 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
 // Four waves to a workgroup (one per SIMD of its CU), consecutive roles: see k_dec_entropy_wide.
 // DEPTH: what the pairs write (16: one word per frame; 20 / 24: six bytes per frame) — one instantiation per output format,
 // so that a launch carries four loop bodies, not eight (they share the CU's instruction cache)
-template <int DEPTH, bool VERIFY>
+template <int DEPTH, PcmMode MODE>
 __global__ __launch_bounds__(64 * kEntWavesPerWg) void k_dec_unpc_wide(DecV1Args V)
 {
     const uint32_t *cnt = dec_lists(V).cnt;
     const uint32_t c4 = cnt[0], c8 = cnt[1], pA = cnt[2], pB = cnt[3], cAny = cnt[6];
     const uint32_t nbB = (pB + 31u) / 32u, nb8 = (c8 + 63u) / 64u, nbA = (pA + 31u) / 32u, nb4 = (c4 + 63u) / 64u;
     uint32_t b = blockIdx.x * (uint32_t)kEntWavesPerWg + (threadIdx.x >> 6);
-    if (b < nbB) return unpc_pair_body<8, DEPTH, VERIFY>(V, b, pB);
+    if (b < nbB) return unpc_pair_body<8, DEPTH, MODE>(V, b, pB);
     b -= nbB;
     if (b < nb8) return unpc_wide_body<8>(V, b, c8);
     b -= nb8;
-    if (b < nbA) return unpc_pair_body<4, DEPTH, VERIFY>(V, b, pA);
+    if (b < nbA) return unpc_pair_body<4, DEPTH, MODE>(V, b, pA);
     b -= nbA;
     if (b < nb4) return unpc_wide_body<4>(V, b, c4);
     b -= nb4;
@@ -1754,7 +1798,7 @@ __global__ __launch_bounds__(64 * kEntWavesPerWg) void k_dec_unpc_wide(DecV1Args
 // ~10 us, sixteen times per packet; removed in round 4.)  Workgroups >= nEnt: one wave per packet for the uncompressed
 // elements (nobody waits for them; their dispatch hides under the entropy chain instead of costing a launch of its own).
 constexpr int kFusedPpw = 48;
-template <bool VERIFY>
+template <PcmMode MODE>
 __global__ __launch_bounds__(256, 1) void k_dec_fused_wg(DecV1Args V, uint32_t nEnt)
 {
     __shared__ uint32_t ringOne[64 * kWinStride];
@@ -1769,7 +1813,7 @@ __global__ __launch_bounds__(256, 1) void k_dec_fused_wg(DecV1Args V, uint32_t n
             unpc_fast_body<true, kFusedPpw>(V, blockIdx.x * 3u + (slot - 1), progLds);
     } else {
         const uint32_t p = (blockIdx.x - nEnt) * 4u + slot;
-        if (p < V.d.numPackets) raw_body<false, VERIFY>(V, p, threadIdx.x & 63, 64);
+        if (p < V.d.numPackets) raw_body<false, MODE>(V, p, threadIdx.x & 63, 64);
     }
 }
 
@@ -1792,22 +1836,22 @@ __global__ __launch_bounds__(64) void k_dec_unpc(DecV1Args V)
 }
 
 // ---- un-mix + pack (gpu_unmixNN / gpu_copyPredictorToNN, codec/ALACDecoder.cu:193-495) ----
-template <int DEPTH, bool VERIFY>
+template <int DEPTH, PcmMode MODE>
 __device__ __forceinline__ void put_sample(const DecodeArgs &A, uint8_t *q, int32_t x)
 {
     if constexpr (DEPTH == 16) {
-        PCM_PUT(VERIFY, A, (int16_t *)q, (int16_t)x);
+        PCM_PUT(MODE, A, (int16_t *)q, (int16_t)x);
     } else if constexpr (DEPTH == 32) {
-        PCM_PUT(VERIFY, A, (int32_t *)q, x);
+        PCM_PUT(MODE, A, (int32_t *)q, x);
     } else {
         if constexpr (DEPTH == 20) x = (int32_t)((uint32_t)x << 4);
-        PCM_PUT(VERIFY, A, q, (uint8_t)x);
-        PCM_PUT(VERIFY, A, q + 1, (uint8_t)(x >> 8));
-        PCM_PUT(VERIFY, A, q + 2, (uint8_t)(x >> 16));
+        PCM_PUT(MODE, A, q, (uint8_t)x);
+        PCM_PUT(MODE, A, q + 1, (uint8_t)(x >> 8));
+        PCM_PUT(MODE, A, q + 2, (uint8_t)(x >> 16));
     }
 }
 
-template <int DEPTH, int CH, bool VERIFY>
+template <int DEPTH, int CH, PcmMode MODE>
 __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint32_t part, uint32_t bx)
 {
     const DecodeArgs &A = V.d;
@@ -1834,6 +1878,7 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
                 const I4 zz = {0, 0, 0, 0};
                 const I4 uu = absent ? zz : *(const I4 *)(u + j), vv = absent ? zz : *(const I4 *)(v + j);
                 U4 o;
+                int32_t fl[4], fr[4];  // float mode: the samples themselves
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     int32_t l, r;
@@ -1844,9 +1889,19 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
                         l = uu[k];
                         r = vv[k];
                     }
-                    o[k] = ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16);
+                    if constexpr (MODE == kPcmFloat) {
+                        fl[k] = l;
+                        fr[k] = r;
+                    } else {
+                        o[k] = ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16);
+                    }
                 }
-                PCM_PUT(VERIFY, A, (U4 *)(out + (uint64_t)j * 4), o);
+                if constexpr (MODE == kPcmFloat) {
+                    pcm_float_run<16>(pcm_float_row(A, V.outFirst, p), j, n4, fl);
+                    pcm_float_run<16>(pcm_float_row(A, V.outFirst + 1, p), j, n4, fr);
+                } else {
+                    PCM_PUT(MODE, A, (U4 *)(out + (uint64_t)j * 4), o);
+                }
             }
             // the last n mod 4 frames of a short packet
             for (uint32_t j = n4 + part * blockDim.x + threadIdx.x; j < n; j += bx * blockDim.x) {
@@ -1859,7 +1914,12 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
                     l = uu;
                     r = vv;
                 }
-                PCM_PUT(VERIFY, A, (uint32_t *)(out + (uint64_t)j * 4), ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16));
+                if constexpr (MODE == kPcmFloat) {
+                    pcm_float_row(A, V.outFirst, p)[j] = pcm_float<16>(l);
+                    pcm_float_row(A, V.outFirst + 1, p)[j] = pcm_float<16>(r);
+                } else {
+                    PCM_PUT(MODE, A, (uint32_t *)(out + (uint64_t)j * 4), ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16));
+                }
             }
             return;
         }
@@ -1891,6 +1951,7 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
                     x[1] = sh ? (w1 << sh) | (w2 >> (32 - sh)) : w1;
                 }
                 uint32_t s[8];  // L0 R0 L1 R1 L2 R2 L3 R3 as 24-bit little-endian fields
+                int32_t fl[4], fr[4];  // float mode: the samples themselves, before the 20-bit left-justification
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     int32_t l, r;
@@ -1906,6 +1967,11 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
                         l = (int32_t)(((uint32_t)l << 8) | ((xx >> 8) & 0xffu));
                         r = (int32_t)(((uint32_t)r << 8) | (xx & 0xffu));
                     }
+                    if constexpr (MODE == kPcmFloat) {
+                        fl[k] = l;
+                        fr[k] = r;
+                        continue;
+                    }
                     if constexpr (DEPTH == 20) {
                         l = (int32_t)((uint32_t)l << 4);
                         r = (int32_t)((uint32_t)r << 4);
@@ -1913,20 +1979,25 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
                     s[2 * k] = (uint32_t)l & 0xffffffu;
                     s[2 * k + 1] = (uint32_t)r & 0xffffffu;
                 }
-                // four 3-byte fields make three words
-                U2 *q = (U2 *)(out + (uint64_t)j * 6);
+                if constexpr (MODE == kPcmFloat) {
+                    pcm_float_run<DEPTH>(pcm_float_row(A, V.outFirst, p), j, n4, fl);
+                    pcm_float_run<DEPTH>(pcm_float_row(A, V.outFirst + 1, p), j, n4, fr);
+                } else {
+                    // four 3-byte fields make three words
+                    U2 *q = (U2 *)(out + (uint64_t)j * 6);
 #pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const uint32_t a0 = s[4 * h], a1 = s[4 * h + 1], a2 = s[4 * h + 2], a3 = s[4 * h + 3];
-                    const uint32_t d0 = a0 | (a1 << 24), d1 = (a1 >> 8) | (a2 << 16), d2 = (a2 >> 16) | (a3 << 8);
-                    if (h == 0) {
-                        const U2 t0 = {d0, d1};
-                        PCM_PUT(VERIFY, A, q, t0);
-                        s[0] = d2;  // first half of the middle store
-                    } else {
-                        const U2 t1 = {s[0], d0}, t2 = {d1, d2};
-                        PCM_PUT(VERIFY, A, q + 1, t1);
-                        PCM_PUT(VERIFY, A, q + 2, t2);
+                    for (int h = 0; h < 2; h++) {
+                        const uint32_t a0 = s[4 * h], a1 = s[4 * h + 1], a2 = s[4 * h + 2], a3 = s[4 * h + 3];
+                        const uint32_t d0 = a0 | (a1 << 24), d1 = (a1 >> 8) | (a2 << 16), d2 = (a2 >> 16) | (a3 << 8);
+                        if (h == 0) {
+                            const U2 t0 = {d0, d1};
+                            PCM_PUT(MODE, A, q, t0);
+                            s[0] = d2;  // first half of the middle store
+                        } else {
+                            const U2 t1 = {s[0], d0}, t2 = {d1, d2};
+                            PCM_PUT(MODE, A, q + 1, t1);
+                            PCM_PUT(MODE, A, q + 2, t2);
+                        }
                     }
                 }
             }
@@ -1954,12 +2025,17 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
             l = (int32_t)(((uint32_t)l << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
             if constexpr (CH == 2) r = (int32_t)(((uint32_t)r << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
         }
-        uint8_t *q = out + (uint64_t)j * och * BPS;
-        if (DEPTH == 16 && CH == 2 && och == 2) {
-            PCM_PUT(VERIFY, A, (uint32_t *)q, ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16));
+        if constexpr (MODE == kPcmFloat) {
+            pcm_float_row(A, V.outFirst, p)[j] = pcm_float<DEPTH>(l);
+            if constexpr (CH == 2) pcm_float_row(A, V.outFirst + 1, p)[j] = pcm_float<DEPTH>(r);
         } else {
-            put_sample<DEPTH, VERIFY>(A, q, l);
-            if constexpr (CH == 2) put_sample<DEPTH, VERIFY>(A, q + BPS, r);
+            uint8_t *q = out + (uint64_t)j * och * BPS;
+            if (DEPTH == 16 && CH == 2 && och == 2) {
+                PCM_PUT(MODE, A, (uint32_t *)q, ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16));
+            } else {
+                put_sample<DEPTH, MODE>(A, q, l);
+                if constexpr (CH == 2) put_sample<DEPTH, MODE>(A, q + BPS, r);
+            }
         }
     }
 }
@@ -1967,33 +2043,34 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
 // Fused launch: workgroup = (packet, part of the frame).  Separate launches: the workgroups walk k_dec_header's list of the
 // packets nobody else writes (with pairs and direct uncompressed elements that is none of the benchmark's packets; launching
 // a workgroup per packet just to read a record and leave cost 0.5 ms at 125 000 packets).
-template <int DEPTH, int CH, bool VERIFY>
+template <int DEPTH, int CH, PcmMode MODE>
 __global__ __launch_bounds__(256) void k_dec_unmix(DecV1Args V)
 {
     const uint32_t bx = blocks_per_packet(V.d.frameSize);
     if (!V.lists) {
-        unmix_part<DEPTH, CH, VERIFY>(V, blockIdx.x / bx, blockIdx.x % bx, bx);
+        unmix_part<DEPTH, CH, MODE>(V, blockIdx.x / bx, blockIdx.x % bx, bx);
         return;
     }
     const DecLists L = dec_lists(V);
     const uint64_t work = (uint64_t)L.cnt[5] * bx;
-    for (uint64_t i = blockIdx.x; i < work; i += gridDim.x) unmix_part<DEPTH, CH, VERIFY>(V, L.rest[i / bx], (uint32_t)(i % bx), bx);
+    for (uint64_t i = blockIdx.x; i < work; i += gridDim.x) unmix_part<DEPTH, CH, MODE>(V, L.rest[i / bx], (uint32_t)(i % bx), bx);
 }
 
-template <int DEPTH, bool VERIFY>
+template <int DEPTH, PcmMode MODE>
 static void launch_unmix_v1(const DecV1Args &V, hipStream_t st)
 {
     const uint64_t all = (uint64_t)blocks_per_packet(V.d.frameSize) * V.d.numPackets;
     dim3 grid((uint32_t)(V.lists && all > 8192 ? 8192 : all));
     if (V.d.numChannels == 2)
-        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 2, VERIFY>), grid, dim3(256), 0, st, V);
+        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 2, MODE>), grid, dim3(256), 0, st, V);
     else
-        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 1, VERIFY>), grid, dim3(256), 0, st, V);
+        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 1, MODE>), grid, dim3(256), 0, st, V);
 }
 
 // one pass of the pipeline over the elements V describes, after the staging of the stream (stageFirst: the pass stages it
-// itself); VERIFY: the instantiations whose PCM store sites compare instead (alac_hip_verify)
-template <bool VERIFY>
+// itself); MODE: the instantiations whose PCM store sites store, compare (alac_hip_verify) or write planar floats
+// (alac_hip_decode_float)
+template <PcmMode MODE>
 static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stageFirst)
 {
     DecV1Args V = V0;
@@ -2051,9 +2128,9 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stage
     const uint32_t nEnt = (da.numPackets + 63) / 64;
     if (fused) {
         const uint32_t nEntWg = (da.numPackets + kFusedPpw - 1) / kFusedPpw;
-        hipLaunchKernelGGL(k_dec_fused_wg<VERIFY>, dim3(nEntWg + (da.numPackets + 3) / 4), dim3(256), 0, st, V, nEntWg);
+        hipLaunchKernelGGL(k_dec_fused_wg<MODE>, dim3(nEntWg + (da.numPackets + 3) / 4), dim3(256), 0, st, V, nEntWg);
     } else {
-        hipLaunchKernelGGL(k_dec_raw<VERIFY>, dim3(da.numPackets < 4096u ? da.numPackets : 4096u), dim3(256), 0, st, V);
+        hipLaunchKernelGGL(k_dec_raw<MODE>, dim3(da.numPackets < 4096u ? da.numPackets : 4096u), dim3(256), 0, st, V);
         // deferred residual stores, four 16-byte stores per round of sixteen consecutive residuals (round 2, 4-byte stores:
         // paid only up to two entropy waves per SIMD; with the wide stores, measured whole decode pass at 125 000 / 250 000 /
         // 500 000 packets: 9.31 -> 8.19, 19.4 -> 14.2, 38.1 -> 26.5 ms — the kernel was bound by the number of store
@@ -2065,25 +2142,29 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stage
         // chains sorted by tap count, one lane per chain
         // (five lists, each rounded up to whole waves)
         const dim3 ugrid(((uint32_t)((lanes + 63) / 64) + 6 + kEntWavesPerWg - 1) / kEntWavesPerWg), ublock(64 * kEntWavesPerWg);
-        if (da.bitDepth == 24) hipLaunchKernelGGL((k_dec_unpc_wide<24, VERIFY>), ugrid, ublock, 0, st, V);
-        else if (da.bitDepth == 20) hipLaunchKernelGGL((k_dec_unpc_wide<20, VERIFY>), ugrid, ublock, 0, st, V);
-        else hipLaunchKernelGGL((k_dec_unpc_wide<16, VERIFY>), ugrid, ublock, 0, st, V);
+        if (da.bitDepth == 24) hipLaunchKernelGGL((k_dec_unpc_wide<24, MODE>), ugrid, ublock, 0, st, V);
+        else if (da.bitDepth == 20) hipLaunchKernelGGL((k_dec_unpc_wide<20, MODE>), ugrid, ublock, 0, st, V);
+        else hipLaunchKernelGGL((k_dec_unpc_wide<16, MODE>), ugrid, ublock, 0, st, V);
     }
     hipLaunchKernelGGL(k_dec_unpc, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, st, V);
     switch (da.bitDepth) {
-    case 16: launch_unmix_v1<16, VERIFY>(V, st); break;
-    case 20: launch_unmix_v1<20, VERIFY>(V, st); break;
-    case 24: launch_unmix_v1<24, VERIFY>(V, st); break;
-    case 32: launch_unmix_v1<32, VERIFY>(V, st); break;
+    case 16: launch_unmix_v1<16, MODE>(V, st); break;
+    case 20: launch_unmix_v1<20, MODE>(V, st); break;
+    case 24: launch_unmix_v1<24, MODE>(V, st); break;
+    case 32: launch_unmix_v1<32, MODE>(V, st); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
-// verify mode (alac_hip_verify) when the caller passes its first-mismatch words
 static hipError_t run_decode_v1_pass(const DecV1Args &V, hipStream_t st, bool stageFirst)
 {
-    return V.d.firstMismatch ? decode_v1_pass<true>(V, st, stageFirst) : decode_v1_pass<false>(V, st, stageFirst);
+    switch (V.d.pcmMode) {
+    case kPcmStore: return decode_v1_pass<kPcmStore>(V, st, stageFirst);
+    case kPcmVerify: return decode_v1_pass<kPcmVerify>(V, st, stageFirst);  // alac_hip_verify
+    case kPcmFloat: return decode_v1_pass<kPcmFloat>(V, st, stageFirst);    // alac_hip_decode_float
+    default: return hipErrorInvalidValue;
+    }
 }
 
 static DecV1Args decode_v1_args(const DecodeArgs &da, uint32_t *words, uint64_t capWords, int32_t *plane, uint32_t *prog)

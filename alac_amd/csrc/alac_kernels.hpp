@@ -211,13 +211,19 @@ struct DecodeArgs {
     HandoffCtl ho;
     int32_t optFused = -1, optPair = 1, optDirect = 1;  // AlacOptions::decFused / decPair / decDirect (host-side launch choices)
     int32_t *resid;  // [ch][frameSize][numPackets] residuals, then samples, in place
-    uint8_t *pcmOut;  // verify mode: the caller's EXPECTED PCM, only ever read (alac_verify.hpp)
+    uint8_t *pcmOut;  // verify mode: the caller's EXPECTED PCM, only ever read; float mode: the planar float32 output (alac_verify.hpp)
     uint32_t *numSamplesOut;
     int32_t *statusOut;
-    // verify mode (alac_hip_verify) when non-null: [numPackets] lowest sample-frame whose bytes differ, lowered with atomicMin
-    // by every store site of the PCM (pcm_put, alac_verify.hpp), which loads and compares instead of storing
-    uint32_t *firstMismatch = nullptr;
+    // The two modes' own words share one slot, and the mode sits in the struct's tail padding: the layout of DecodeArgs (and of
+    // DecV1Args behind it) is the one the store and verify instantiations were compiled against, so their code is unchanged.
+    union {
+        // verify mode (alac_hip_verify): [numPackets] lowest sample-frame whose bytes differ, lowered with atomicMin by every
+        // store site of the PCM (PCM_PUT, alac_verify.hpp), which loads and compares instead of storing
+        uint32_t *firstMismatch = nullptr;
+        uint64_t channelStride;  // float mode (alac_hip_decode_float): floats between two channels' rows of pcmOut
+    };
     uint32_t frameBytes = 0;  // verify mode: bytes of one whole output frame (all channels)
+    uint32_t pcmMode = 0;     // PcmMode (alac_verify.hpp): what the PCM store sites do
 };
 
 hipError_t launch_decode(const DecodeArgs &da, hipStream_t st);

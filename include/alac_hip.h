@@ -219,6 +219,39 @@ int32_t alac_hip_decode(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t coo
                         uint32_t num_packets, void *d_workspace, uint64_t workspace_bytes,
                         uint8_t *d_pcm_out, uint32_t *d_num_samples_out, int32_t *d_status);
 
+/* ---- batch decode to planar float32 ----------------------------------------------------------------------------------
+ * alac_hip_decode with every PCM store site writing the sample as a float instead of its integer bytes: what a PyTorch
+ * caller wants (a [channels, frames] float32 tensor scaled to [-1, 1), the shape torchaudio.load returns) without a second
+ * pass over the output.  No reference counterpart.  Asynchronous like alac_hip_decode, same decoder options.
+ *   d_out             planar float32, 4-byte aligned: sample i of channel c of packet p at
+ *                     d_out[c * channel_stride + p * frame_size + i].  Channel c is the c-th sample of a frame as
+ *                     alac_hip_decode interleaves it.
+ *   channel_stride    floats between two channels' rows: at least num_packets * frame_size
+ *   d_workspace       exactly alac_hip_decode_workspace_bytes_stream bytes suffice (there is no PCM plane), 256-byte aligned
+ *   d_num_samples_out, d_status: as alac_hip_decode
+ * Value: (float)s * 2^-(bit_depth - 1), s the decoded sample sign-extended at the stream's own depth (a 20-bit sample is
+ * scaled by 2^-19, not taken from its left-justified 3-byte container).  The conversion rounds to nearest even and the scale
+ * is a power of two, so 16-, 20- and 24-bit samples are exact and -2^(bit_depth - 1) gives -1.0.  32-bit samples round to
+ * 24 significant bits: full-scale positive ones (2^31 - 64 and up) give 1.0.
+ * Written are exactly the samples alac_hip_decode writes bytes for: num_samples frames of every decoded packet, 0.0 where
+ * decode writes zero samples, nothing behind a short packet's frames and nothing between num_packets * frame_size and
+ * channel_stride.  A failed in-launch hand-off is reported like decode's (kALAC_MemFullError at the next synchronize).
+ * kALAC_ParamError, with nothing written, for a null or misaligned d_out, a channel_stride below num_packets * frame_size or
+ * one whose channel_stride * num_channels * 4 bytes overflow, and whatever alac_hip_decode refuses.
+ */
+int32_t alac_hip_decode_float(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size,
+                              const uint8_t *d_stream, const uint64_t *d_packet_offsets, uint32_t num_packets,
+                              void *d_workspace, uint64_t workspace_bytes,
+                              float *d_out, uint64_t channel_stride,
+                              uint32_t *d_num_samples_out, int32_t *d_status);
+/* Host-buffer form (synchronous, like alac_hip_decode_host): packets back to back with sizes h_packet_bytes; h_out in the
+ * layout above, rows channel_stride floats apart; samples decode does not write come back as 0.0, the gap behind each row
+ * is left as it was. */
+int32_t alac_hip_decode_float_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size,
+                                   const uint8_t *h_stream, const uint32_t *h_packet_bytes, uint32_t num_packets,
+                                   float *h_out, uint64_t channel_stride,
+                                   uint32_t *h_num_samples_out, int32_t *h_status);
+
 /* ---- batch verify: decode and compare with the PCM the stream was encoded from, on the device ----------------------
  * What a caller of ALACDecoder::Decode (codec/ALACDecoder.cu:571-1002) does by hand before trusting an encode — decode, then
  * compare the output of fillWriteBuffer (:497-563) with the source — without writing the decoded PCM anywhere: every kernel
