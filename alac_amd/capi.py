@@ -54,6 +54,11 @@ SIGNATURES = {
                                _vp, _u64, _vp, _vp]),
     "alac_hip_encode_segmented": (_i32, [_vp, C.POINTER(Format), _vp, _vp, _u32, _vp, _u32, _u32, _vp, _i32, _vp, _u64,
                                          _vp, _u64, _vp, _vp]),
+    "alac_hip_encode_float_workspace_bytes": (_u64, [C.POINTER(Format), _u32, _u32]),
+    "alac_hip_encode_float": (_i32, [_vp, C.POINTER(Format), _vp, _u64, _u64, _vp, _u32, _vp, _u32, _u32, _vp, _i32, _vp, _u64,
+                                     _vp, _u64, _vp, _vp, _vp]),
+    "alac_hip_encode_float_host": (_i32, [_vp, C.POINTER(Format), _vp, _u64, _u64, _vp, _u32, _vp, _u32, _vp, _i32, _vp, _u64,
+                                          _vp, C.POINTER(_u64), _vp]),
     "alac_hip_profile_begin": (_i32, [_vp, _u32]),
     "alac_hip_profile_end": (_i32, [_vp, C.POINTER(_u32), C.POINTER(C.c_float), C.POINTER(_u32)]),
     "alac_hip_num_stages": (_u32, []),
@@ -318,6 +323,45 @@ class Context:
             for x in bufs.values():
                 if hasattr(x, "record_stream"):
                     x.record_stream(cur)
+            return bufs
+
+    def encode_float(self, fmt, x, num_samples=None, seg_first=None, state=None, state_in=False, bufs=None,
+                     max_segment_packets=0, clipped=False):
+        """encode() from float32 PCM (alac_hip_encode_float): x is a float32 cuda tensor [channels, frames] with any strides
+        (x.stride() is passed through: a contiguous [C, T] tensor and the transposed view of a [T, C] one need no copy),
+        quantized on the device by the rule of include/alac_hip.h (rint(x * 2^(bit_depth - 1)), saturated, NaN -> 0).
+        num_packets = ceil(frames / frame_size); num_samples=None gives the last packet frames mod frame_size frames
+        when that is not 0.  Returns encode()'s buffers dict; clipped=True adds "clipped", an int32 [num_packets] tensor of
+        the clipped samples per packet."""
+        with self._call() as cur:
+            t = self.torch
+            if not (x.is_cuda and x.dtype == t.float32 and x.dim() == 2 and x.shape[0] == fmt.num_channels):
+                raise ValueError("encode_float: x must be a float32 cuda tensor [channels, frames]")
+            frames = int(x.shape[1])
+            num_packets = (frames + fmt.frame_size - 1) // fmt.frame_size
+            if num_samples is None and frames % fmt.frame_size:
+                ns = [fmt.frame_size] * (num_packets - 1) + [frames % fmt.frame_size]
+                num_samples = t.tensor(ns, dtype=t.int32).to(self.device, non_blocking=True)
+            nseg = num_packets if seg_first is None else seg_first.numel() - 1
+            bufs = bufs or self.encode_buffers(fmt, num_packets)
+            if clipped and "clipped" not in bufs:
+                bufs["clipped"] = t.empty(num_packets, dtype=t.int32, device=self.device)
+            wsb = int(self.lib.alac_hip_encode_float_workspace_bytes(C.byref(fmt), num_packets,
+                                                                     num_packets if self.get_option("lpc") else nseg))
+            ws = self._workspace(wsb)
+            rc = self.lib.alac_hip_encode_float(
+                self.h, C.byref(fmt), x.data_ptr(), int(x.stride(0)), int(x.stride(1)),
+                None if num_samples is None else num_samples.data_ptr(), num_packets,
+                None if seg_first is None else seg_first.data_ptr(), nseg, int(max_segment_packets),
+                None if state is None else state.data_ptr(), 1 if state_in else 0,
+                ws.data_ptr(), ws.numel(), bufs["out"].data_ptr(), bufs["out"].numel(),
+                bufs["sizes"].data_ptr(), bufs["offsets"].data_ptr(), bufs["clipped"].data_ptr() if clipped else None)
+            self._check(rc)
+            for v in bufs.values():
+                if hasattr(v, "record_stream"):
+                    v.record_stream(cur)
+            if num_samples is not None:
+                num_samples.record_stream(cur)
             return bufs
 
     def encode_to_host(self, fmt, pcm, num_packets, **kw):

@@ -400,6 +400,66 @@ int32_t upload_stream(alac_hip_ctx *ctx, const alac_hip_format &fmt, const uint8
     return ALAC_HIP_noErr;
 }
 
+// The host forms of the encode calls: the checks of the tables, the tables and the state staged to the device, `launch` (the
+// device call on the staged buffers: (maxSeg, num samples, segment table, state, workspace, out, sizes, offsets) -> status),
+// the results copied back.  wsBytes: the device call's workspace.
+template <class Launch>
+int32_t encode_host_common(alac_hip_ctx *ctx, const alac_hip_format *fmt, const uint32_t *h_num_samples, uint32_t num_packets,
+                           const uint32_t *h_seg_first, uint32_t num_segments, int16_t *h_state, int32_t state_in,
+                           uint8_t *h_out, uint64_t out_capacity, uint32_t *h_packet_bytes, uint64_t *out_total_bytes,
+                           uint64_t wsBytes, Launch launch)
+{
+    const uint32_t np = num_packets, nseg = num_segments;
+    const uint64_t stateBytes = (uint64_t)nseg * alac_hip_state_int16(fmt) * 2;
+    const uint64_t outMax = alac_hip_encode_max_output_bytes(fmt, np);
+
+    DevBuf dNs, dSeg, dState, dWs, dOut, dSizes, dOffs;
+    hipError_t e;
+    if ((e = dNs.alloc(np * 4ull)) || (e = dSeg.alloc((nseg + 1) * 4ull)) || (e = dState.alloc(stateBytes)) ||
+        (e = dWs.alloc(wsBytes)) || (e = dOut.alloc(outMax)) || (e = dSizes.alloc(np * 4ull)) ||
+        (e = dOffs.alloc((np + 1) * 8ull)))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    hipStream_t st = ctx->stream;
+    if ((e = hipMemcpyAsync(dNs.p, h_num_samples, np * 4ull, hipMemcpyHostToDevice, st)) ||
+        (e = hipMemcpyAsync(dSeg.p, h_seg_first, (nseg + 1) * 4ull, hipMemcpyHostToDevice, st)))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    if (h_state && state_in)
+        if ((e = hipMemcpyAsync(dState.p, h_state, stateBytes, hipMemcpyHostToDevice, st)))
+            return fail(ctx, ALAC_HIP_ParamError, "H2D state", e);
+    uint32_t maxSeg = 1;
+    for (uint32_t s2 = 0; s2 < nseg; s2++) maxSeg = h_seg_first[s2 + 1] - h_seg_first[s2] > maxSeg ? h_seg_first[s2 + 1] - h_seg_first[s2] : maxSeg;
+    int32_t rc = launch(maxSeg, (const uint32_t *)dNs.p, (const uint32_t *)dSeg.p, (int16_t *)dState.p,
+                        (h_state && state_in) ? 1 : 0, dWs.p, (uint8_t *)dOut.p, outMax, (uint32_t *)dSizes.p,
+                        (uint64_t *)dOffs.p);
+    if (rc != ALAC_HIP_noErr) return rc;
+    uint64_t total = 0;
+    if ((e = hipMemcpyAsync(&total, (uint64_t *)dOffs.p + np, 8, hipMemcpyDeviceToHost, st)) ||
+        (e = hipStreamSynchronize(st)))
+        return fail(ctx, ALAC_HIP_ParamError, "encode execution", e);
+    if (total > out_capacity) return fail(ctx, ALAC_HIP_MemFullError, "host output buffer too small");
+    if ((e = hipMemcpyAsync(h_out, dOut.p, total, hipMemcpyDeviceToHost, st)) ||
+        (e = hipMemcpyAsync(h_packet_bytes, dSizes.p, np * 4ull, hipMemcpyDeviceToHost, st)))
+        return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
+    if (h_state)
+        if ((e = hipMemcpyAsync(h_state, dState.p, stateBytes, hipMemcpyDeviceToHost, st)))
+            return fail(ctx, ALAC_HIP_ParamError, "D2H state", e);
+    if ((e = hipStreamSynchronize(st))) return fail(ctx, ALAC_HIP_ParamError, "sync", e);
+    if (int32_t hrc = check_handoff(ctx)) return hrc;
+    if (out_total_bytes) *out_total_bytes = total;
+    return ALAC_HIP_noErr;
+}
+
+// the checks of a host segment table every host form makes
+int32_t host_segment_refusal(alac_hip_ctx *ctx, const uint32_t *h_seg_first, uint32_t num_segments, uint32_t num_packets)
+{
+    if (h_seg_first[0] != 0 || h_seg_first[num_segments] != num_packets)
+        return fail(ctx, ALAC_HIP_ParamError, "segment table must start at 0 and end at num_packets");
+    for (uint32_t s = 0; s < num_segments; s++)
+        if (h_seg_first[s] > h_seg_first[s + 1]) return fail(ctx, ALAC_HIP_ParamError, "segment table not ascending");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    return ALAC_HIP_noErr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -539,6 +599,60 @@ uint64_t alac_hip_encode_max_output_bytes(const alac_hip_format *fmt, uint32_t n
     return max_output_bytes(fmt, num_packets);
 }
 
+// The refusals of alac_hip_encode_segmented that need no device work, in its order (the format is checked already); 0 when
+// the call may go ahead.  alac_hip_encode_float runs them before it enqueues its conversion.
+static int32_t encode_refusal(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm, uint32_t num_packets,
+                              const uint32_t *d_seg_first, uint32_t num_segments, const void *d_workspace,
+                              uint64_t workspace_bytes, const uint8_t *d_out, uint64_t out_capacity,
+                              const uint32_t *d_packet_bytes, const uint64_t *d_packet_offsets)
+{
+    const bool mc = fmt->num_channels > 2, lpc = ctx->opt.lpc != 0;
+    if (mc && lpc) return fail(ctx, ALAC_HIP_ParamError, "option lpc: mono and stereo streams only");
+    if (lpc) {
+        if (ctx->opt.fastMode) return fail(ctx, ALAC_HIP_ParamError, "options lpc and fast_mode exclude each other");
+        if ((uint64_t)fmt->frame_size * fmt->num_channels * 4 > 65536)
+            return fail(ctx, ALAC_HIP_ParamError, "option lpc: frame_size x channels above 16 384");
+        d_seg_first = nullptr;
+    }
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (!d_pcm || !d_workspace || !d_out || !d_packet_bytes || !d_packet_offsets)
+        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if (!d_seg_first) num_segments = num_packets;
+    if (num_segments == 0 || num_segments > num_packets) return fail(ctx, ALAC_HIP_ParamError, "bad segment count");
+    if (mc) {
+        if (((uintptr_t)d_workspace & 255)) return fail(ctx, ALAC_HIP_ParamError, "misaligned workspace (256 B)");
+        if ((uint64_t)num_packets * kMaxChannels > 0x7fffffffull) return fail(ctx, ALAC_HIP_ParamError, "too many packets");
+        if (workspace_bytes < mc_layout(fmt, num_packets, num_segments).total)
+            return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    } else {
+        if (((uintptr_t)d_out & 3) || ((uintptr_t)d_workspace & 255) || ((uintptr_t)d_pcm & 15))
+            return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer (out 4 B, pcm 16 B, workspace 256 B)");
+        if (workspace_bytes < enc_layout(fmt, num_packets, num_segments).total + (lpc ? lpc_table_bytes(num_packets) : 0))
+            return fail(ctx, ALAC_HIP_ParamError, lpc ? "workspace too small (option lpc: size it for num_segments = num_packets)"
+                                                      : "workspace too small");
+    }
+    if (out_capacity < max_output_bytes(fmt, num_packets))
+        return fail(ctx, ALAC_HIP_ParamError, "output capacity below alac_hip_encode_max_output_bytes");
+    return ALAC_HIP_noErr;
+}
+
+// the longest segment of a device segment table, read back (a host wait); refuses a table that is not ascending inside
+// [0, num_packets]
+static int32_t read_max_segment(alac_hip_ctx *ctx, const uint32_t *d_seg_first, uint32_t num_segments, uint32_t num_packets,
+                                uint32_t &maxSeg)
+{
+    std::vector<uint32_t> sf(num_segments + 1);
+    if (hipMemcpyAsync(sf.data(), d_seg_first, (num_segments + 1) * 4ull, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess)
+        return fail(ctx, ALAC_HIP_ParamError, "reading d_seg_first");
+    maxSeg = 0;
+    for (uint32_t s = 0; s < num_segments; s++) {
+        if (sf[s + 1] < sf[s] || sf[s + 1] > num_packets) return fail(ctx, ALAC_HIP_ParamError, "bad d_seg_first");
+        maxSeg = sf[s + 1] - sf[s] > maxSeg ? sf[s + 1] - sf[s] : maxSeg;
+    }
+    return ALAC_HIP_noErr;
+}
+
 static int32_t encode_elements(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm,
                                const uint32_t *d_num_samples, uint32_t num_packets, const uint32_t *d_seg_first,
                                uint32_t num_segments, int16_t *d_state, int32_t state_in, void *d_workspace,
@@ -579,24 +693,86 @@ int32_t alac_hip_encode(alac_hip_ctx *ctx, const alac_hip_format *fmt, const voi
                                      d_workspace, workspace_bytes, d_out, out_capacity, d_packet_bytes, d_packet_offsets);
 }
 
+// ---- float32 input: quantize into a stage at the end of the workspace, then alac_hip_encode_segmented on it -------------
+// the staged integer PCM of a batch (+ 64: slack behind the last packet, like the gathered copies of a > 2-channel batch)
+static uint64_t float_stage_bytes(const alac_hip_format *fmt, uint32_t num_packets)
+{
+    return align_up((uint64_t)num_packets * fmt->frame_size * fmt->num_channels * bytes_per_sample(fmt->bit_depth) + 64, 256);
+}
+
+uint64_t alac_hip_encode_float_workspace_bytes(const alac_hip_format *fmt, uint32_t num_packets, uint32_t num_segments)
+{
+    if (!format_ok(fmt)) return 0;
+    return align_up(alac_hip_encode_workspace_bytes(fmt, num_packets, num_segments), 256) + float_stage_bytes(fmt, num_packets);
+}
+
+int32_t alac_hip_encode_float(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *d_in, uint64_t channel_stride,
+                              uint64_t frame_stride, const uint32_t *d_num_samples, uint32_t num_packets,
+                              const uint32_t *d_seg_first, uint32_t num_segments, uint32_t max_segment_packets,
+                              int16_t *d_state, int32_t state_in, void *d_workspace, uint64_t workspace_bytes, uint8_t *d_out,
+                              uint64_t out_capacity, uint32_t *d_packet_bytes, uint64_t *d_packet_offsets,
+                              uint32_t *d_clipped)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
+    if (num_packets == 0)
+        return encode_refusal(ctx, fmt, nullptr, 0, d_seg_first, num_segments, d_workspace, workspace_bytes, d_out,
+                              out_capacity, d_packet_bytes, d_packet_offsets);
+    const uint32_t C = fmt->num_channels;
+    if (!d_in) return fail(ctx, ALAC_HIP_ParamError, "null d_in");
+    if ((uintptr_t)d_in & 3) return fail(ctx, ALAC_HIP_ParamError, "misaligned d_in (4 B)");
+    if (frame_stride == 0) return fail(ctx, ALAC_HIP_ParamError, "frame_stride 0");
+    if (channel_stride == 0 && C > 1) return fail(ctx, ALAC_HIP_ParamError, "channel_stride 0 with more than one channel");
+    // the largest index the conversion can form, and its byte offset: (C - 1) * channel_stride + (frames - 1) * frame_stride
+    uint64_t rows, cols, last;
+    if (__builtin_mul_overflow((uint64_t)(C - 1), channel_stride, &rows) ||
+        __builtin_mul_overflow((uint64_t)num_packets * fmt->frame_size - 1, frame_stride, &cols) ||
+        __builtin_add_overflow(rows, cols, &last) || last > UINT64_MAX / sizeof(float))
+        return fail(ctx, ALAC_HIP_ParamError, "the largest index into d_in overflows 64 bits");
+    // the stage: the last whole 256-byte blocks of the workspace; the encoder gets everything in front of it
+    const uint64_t stage = float_stage_bytes(fmt, num_packets);
+    if (workspace_bytes < stage) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    const uint64_t encBytes = (workspace_bytes - stage) & ~255ull;
+    uint8_t *pcm = d_workspace ? (uint8_t *)d_workspace + encBytes : nullptr;
+    if (int32_t rc = encode_refusal(ctx, fmt, pcm, num_packets, d_seg_first, num_segments, d_workspace, encBytes, d_out,
+                                    out_capacity, d_packet_bytes, d_packet_offsets))
+        return rc;
+    // the encoder's own read-back of a segment table without a bound (tap-parallel path) may refuse it: run that check before
+    // anything is enqueued (the encoder reads the table again)
+    if (d_seg_first && !max_segment_packets && C <= 2 && !ctx->opt.lpc && !use_lane_encoder(ctx)) {
+        uint32_t maxSeg = 0;
+        if (int32_t rc = read_max_segment(ctx, d_seg_first, num_segments, num_packets, maxSeg)) return rc;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    FloatInArgs a;
+    a.in = d_in;
+    a.channelStride = channel_stride;
+    a.frameStride = frame_stride;
+    a.numSamples = d_num_samples;
+    a.numPackets = num_packets;
+    a.frameSize = fmt->frame_size;
+    a.channels = C;
+    a.pcm = pcm;
+    a.clipped = d_clipped;
+    const hipError_t e = launch_float_to_pcm(fmt->bit_depth, a, ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "float conversion launch", e);
+    return alac_hip_encode_segmented(ctx, fmt, pcm, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets,
+                                     d_state, state_in, d_workspace, encBytes, d_out, out_capacity, d_packet_bytes,
+                                     d_packet_offsets);
+}
+
 static int32_t encode_elements(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm,
                                const uint32_t *d_num_samples, uint32_t num_packets, const uint32_t *d_seg_first,
                                uint32_t num_segments, int16_t *d_state, int32_t state_in, void *d_workspace,
                                uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
                                uint32_t *d_packet_bytes, uint64_t *d_packet_offsets, uint32_t maxSegHint)
 {
-    if (ctx->opt.lpc) return fail(ctx, ALAC_HIP_ParamError, "option lpc: mono and stereo streams only");
+    if (int32_t rc = encode_refusal(ctx, fmt, d_pcm, num_packets, d_seg_first, num_segments, d_workspace, workspace_bytes,
+                                    d_out, out_capacity, d_packet_bytes, d_packet_offsets))
+        return rc;
     if (num_packets == 0) return ALAC_HIP_noErr;
-    if (!d_pcm || !d_workspace || !d_out || !d_packet_bytes || !d_packet_offsets)
-        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
     if (!d_seg_first) num_segments = num_packets;
-    if (num_segments == 0 || num_segments > num_packets) return fail(ctx, ALAC_HIP_ParamError, "bad segment count");
-    if (((uintptr_t)d_workspace & 255)) return fail(ctx, ALAC_HIP_ParamError, "misaligned workspace (256 B)");
-    if ((uint64_t)num_packets * kMaxChannels > 0x7fffffffull) return fail(ctx, ALAC_HIP_ParamError, "too many packets");
     const McLayout M = mc_layout(fmt, num_packets, num_segments);
-    if (workspace_bytes < M.total) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
-    if (out_capacity < max_output_bytes(fmt, num_packets))
-        return fail(ctx, ALAC_HIP_ParamError, "output capacity below alac_hip_encode_max_output_bytes");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
     uint8_t *ws = (uint8_t *)d_workspace;
     const uint32_t bps = bytes_per_sample(fmt->bit_depth);
@@ -728,29 +904,19 @@ static int32_t encode_core(alac_hip_ctx *ctx, const alac_hip_format *fmt, const 
 {
     // LPC mode: every packet is its own segment, whatever table the caller passes; the coefficient state is neither read
     // nor written
+    if (int32_t rc = encode_refusal(ctx, fmt, d_pcm, num_packets, d_seg_first, num_segments, d_workspace, workspace_bytes,
+                                    d_out, out_capacity, d_packet_bytes, d_packet_offsets))
+        return rc;
     const bool lpc = ctx->opt.lpc != 0;
     if (lpc) {
-        if (ctx->opt.fastMode) return fail(ctx, ALAC_HIP_ParamError, "options lpc and fast_mode exclude each other");
-        if ((uint64_t)fmt->frame_size * fmt->num_channels * 4 > 65536)
-            return fail(ctx, ALAC_HIP_ParamError, "option lpc: frame_size x channels above 16 384");
         d_seg_first = nullptr;
         d_state = nullptr;
         state_in = 0;
         maxSegHint = 0;
     }
     if (num_packets == 0) return ALAC_HIP_noErr;
-    if (!d_pcm || !d_workspace || !d_out || !d_packet_bytes || !d_packet_offsets)
-        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
     if (!d_seg_first) num_segments = num_packets;
-    if (num_segments == 0 || num_segments > num_packets) return fail(ctx, ALAC_HIP_ParamError, "bad segment count");
-    if (((uintptr_t)d_out & 3) || ((uintptr_t)d_workspace & 255) || ((uintptr_t)d_pcm & 15))
-        return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer (out 4 B, pcm 16 B, workspace 256 B)");
     const EncLayout L = enc_layout(fmt, num_packets, num_segments);
-    if (workspace_bytes < L.total + (lpc ? lpc_table_bytes(num_packets) : 0))
-        return fail(ctx, ALAC_HIP_ParamError, lpc ? "workspace too small (option lpc: size it for num_segments = num_packets)"
-                                                  : "workspace too small");
-    if (out_capacity < alac_hip_encode_max_output_bytes(fmt, num_packets))
-        return fail(ctx, ALAC_HIP_ParamError, "output capacity below alac_hip_encode_max_output_bytes");
 
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
     uint8_t *ws = (uint8_t *)d_workspace;
@@ -812,16 +978,7 @@ static int32_t encode_core(alac_hip_ctx *ctx, const alac_hip_format *fmt, const 
             // host wait.  The bound is checked on the device; a table that contradicts it fails the next synchronize.
             maxSeg = maxSegHint < num_packets ? maxSegHint : num_packets;
         } else if (d_seg_first) {
-            std::vector<uint32_t> sf(num_segments + 1);
-            if (hipMemcpyAsync(sf.data(), d_seg_first, (num_segments + 1) * 4ull, hipMemcpyDeviceToHost, ctx->stream) !=
-                    hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess)
-                return fail(ctx, ALAC_HIP_ParamError, "reading d_seg_first");
-            maxSeg = 0;
-            for (uint32_t s = 0; s < num_segments; s++) {
-                if (sf[s + 1] < sf[s] || sf[s + 1] > num_packets) return fail(ctx, ALAC_HIP_ParamError, "bad d_seg_first");
-                maxSeg = sf[s + 1] - sf[s] > maxSeg ? sf[s + 1] - sf[s] : maxSeg;
-            }
+            if (int32_t rc = read_max_segment(ctx, d_seg_first, num_segments, num_packets, maxSeg)) return rc;
         }
         const V1Plan P = v1_plan(fmt->num_channels, num_segments, maxSeg, fmt->frame_size, ctx->opt);
         const V1Args A = v1_args(ctx, ea, L, ws, P, d_state == nullptr);
@@ -1227,53 +1384,73 @@ int32_t alac_hip_encode_host_segments(alac_hip_ctx *ctx, const alac_hip_format *
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!h_pcm || !h_out || !h_packet_bytes || !h_num_samples || !h_seg_first || num_segments == 0)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (h_seg_first[0] != 0 || h_seg_first[num_segments] != num_packets)
-        return fail(ctx, ALAC_HIP_ParamError, "segment table must start at 0 and end at num_packets");
-    for (uint32_t s = 0; s < num_segments; s++)
-        if (h_seg_first[s] > h_seg_first[s + 1]) return fail(ctx, ALAC_HIP_ParamError, "segment table not ascending");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    if (int32_t rc = host_segment_refusal(ctx, h_seg_first, num_segments, num_packets)) return rc;
 
     const uint32_t bpf = fmt->num_channels * bytes_per_sample(fmt->bit_depth);
     const uint32_t np = num_packets, nseg = num_segments;
-    const uint64_t stateBytes = (uint64_t)nseg * alac_hip_state_int16(fmt) * 2;
     const uint64_t pcmBytes = (uint64_t)np * fmt->frame_size * bpf;
     const uint64_t wsBytes = alac_hip_encode_workspace_bytes(fmt, np, ctx->opt.lpc ? np : nseg);
-    const uint64_t outMax = alac_hip_encode_max_output_bytes(fmt, np);
-
-    DevBuf dPcm, dNs, dSeg, dState, dWs, dOut, dSizes, dOffs;
+    DevBuf dPcm;
     hipError_t e;
-    if ((e = dPcm.alloc(pcmBytes)) || (e = dNs.alloc(np * 4ull)) || (e = dSeg.alloc((nseg + 1) * 4ull)) ||
-        (e = dState.alloc(stateBytes)) || (e = dWs.alloc(wsBytes)) || (e = dOut.alloc(outMax)) ||
-        (e = dSizes.alloc(np * 4ull)) || (e = dOffs.alloc((np + 1) * 8ull)))
-        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
-    hipStream_t st = ctx->stream;
-    if ((e = hipMemcpyAsync(dPcm.p, h_pcm, pcmBytes, hipMemcpyHostToDevice, st)) ||
-        (e = hipMemcpyAsync(dNs.p, h_num_samples, np * 4ull, hipMemcpyHostToDevice, st)) ||
-        (e = hipMemcpyAsync(dSeg.p, h_seg_first, (nseg + 1) * 4ull, hipMemcpyHostToDevice, st)))
+    if ((e = dPcm.alloc(pcmBytes))) return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if ((e = hipMemcpyAsync(dPcm.p, h_pcm, pcmBytes, hipMemcpyHostToDevice, ctx->stream)))
         return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    if (h_state && state_in)
-        if ((e = hipMemcpyAsync(dState.p, h_state, stateBytes, hipMemcpyHostToDevice, st)))
-            return fail(ctx, ALAC_HIP_ParamError, "H2D state", e);
-    uint32_t maxSeg = 1;
-    for (uint32_t s2 = 0; s2 < nseg; s2++) maxSeg = h_seg_first[s2 + 1] - h_seg_first[s2] > maxSeg ? h_seg_first[s2 + 1] - h_seg_first[s2] : maxSeg;
-    int32_t rc = alac_hip_encode_segmented(ctx, fmt, dPcm.p, (const uint32_t *)dNs.p, np, (const uint32_t *)dSeg.p, nseg, maxSeg,
-                                           (int16_t *)dState.p, (h_state && state_in) ? 1 : 0, dWs.p, wsBytes,
-                                           (uint8_t *)dOut.p, outMax, (uint32_t *)dSizes.p, (uint64_t *)dOffs.p);
-    if (rc != ALAC_HIP_noErr) return rc;
-    uint64_t total = 0;
-    if ((e = hipMemcpyAsync(&total, (uint64_t *)dOffs.p + np, 8, hipMemcpyDeviceToHost, st)) ||
-        (e = hipStreamSynchronize(st)))
-        return fail(ctx, ALAC_HIP_ParamError, "encode execution", e);
-    if (total > out_capacity) return fail(ctx, ALAC_HIP_MemFullError, "host output buffer too small");
-    if ((e = hipMemcpyAsync(h_out, dOut.p, total, hipMemcpyDeviceToHost, st)) ||
-        (e = hipMemcpyAsync(h_packet_bytes, dSizes.p, np * 4ull, hipMemcpyDeviceToHost, st)))
+    return encode_host_common(ctx, fmt, h_num_samples, np, h_seg_first, nseg, h_state, state_in, h_out, out_capacity,
+                              h_packet_bytes, out_total_bytes, wsBytes,
+                              [&](uint32_t maxSeg, const uint32_t *ns, const uint32_t *seg, int16_t *state, int32_t stIn,
+                                  void *ws, uint8_t *out, uint64_t outMax, uint32_t *sizes, uint64_t *offs) {
+                                  return alac_hip_encode_segmented(ctx, fmt, dPcm.p, ns, np, seg, nseg, maxSeg, state, stIn,
+                                                                   ws, wsBytes, out, outMax, sizes, offs);
+                              });
+}
+
+int32_t alac_hip_encode_float_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *h_in, uint64_t channel_stride,
+                                   uint64_t frame_stride, const uint32_t *h_num_samples, uint32_t num_packets,
+                                   const uint32_t *h_seg_first, uint32_t num_segments, int16_t *h_state, int32_t state_in,
+                                   uint8_t *h_out, uint64_t out_capacity, uint32_t *h_packet_bytes, uint64_t *out_total_bytes,
+                                   uint32_t *h_clipped)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
+    if (out_total_bytes) *out_total_bytes = 0;
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (!h_in || !h_out || !h_packet_bytes || !h_num_samples || !h_seg_first || num_segments == 0)
+        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if (int32_t rc = host_segment_refusal(ctx, h_seg_first, num_segments, num_packets)) return rc;
+    const uint32_t np = num_packets, nseg = num_segments, fs = fmt->frame_size;
+    // the floats the conversion reads lie in [0, span): up to the last frame a packet's num_samples covers.  The same
+    // strides then address the copy on the device (alac_hip_encode_float checks them).
+    uint64_t span = 0;
+    for (uint32_t p = 0; p < np; p++) {
+        const uint32_t n = h_num_samples[p] < fs ? h_num_samples[p] : fs;
+        if (!n) continue;
+        uint64_t rows, cols, last;
+        if (__builtin_mul_overflow((uint64_t)(fmt->num_channels - 1), channel_stride, &rows) ||
+            __builtin_mul_overflow((uint64_t)p * fs + n - 1, frame_stride, &cols) || __builtin_add_overflow(rows, cols, &last) ||
+            last >= UINT64_MAX / sizeof(float))
+            return fail(ctx, ALAC_HIP_ParamError, "the largest index into h_in overflows 64 bits");
+        span = last + 1 > span ? last + 1 : span;
+    }
+    const uint64_t wsBytes = alac_hip_encode_float_workspace_bytes(fmt, np, ctx->opt.lpc ? np : nseg);
+    DevBuf dIn, dClip;
+    hipError_t e;
+    if ((e = dIn.alloc(span * sizeof(float))) || (e = dClip.alloc(np * 4ull)))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if ((e = hipMemcpyAsync(dIn.p, h_in, span * sizeof(float), hipMemcpyHostToDevice, ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    int32_t rc = encode_host_common(
+        ctx, fmt, h_num_samples, np, h_seg_first, nseg, h_state, state_in, h_out, out_capacity, h_packet_bytes,
+        out_total_bytes, wsBytes,
+        [&](uint32_t maxSeg, const uint32_t *ns, const uint32_t *seg, int16_t *state, int32_t stIn, void *ws, uint8_t *out,
+            uint64_t outMax, uint32_t *sizes, uint64_t *offs) {
+            return alac_hip_encode_float(ctx, fmt, (const float *)dIn.p, channel_stride, frame_stride, ns, np, seg, nseg, maxSeg,
+                                         state, stIn, ws, wsBytes, out, outMax, sizes, offs,
+                                         h_clipped ? (uint32_t *)dClip.p : nullptr);
+        });
+    if (rc != ALAC_HIP_noErr || !h_clipped) return rc;
+    if ((e = hipMemcpyAsync(h_clipped, dClip.p, np * 4ull, hipMemcpyDeviceToHost, ctx->stream)) ||
+        (e = hipStreamSynchronize(ctx->stream)))
         return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
-    if (h_state)
-        if ((e = hipMemcpyAsync(h_state, dState.p, stateBytes, hipMemcpyDeviceToHost, st)))
-            return fail(ctx, ALAC_HIP_ParamError, "D2H state", e);
-    if ((e = hipStreamSynchronize(st))) return fail(ctx, ALAC_HIP_ParamError, "sync", e);
-    if (int32_t hrc = check_handoff(ctx)) return hrc;
-    if (out_total_bytes) *out_total_bytes = total;
     return ALAC_HIP_noErr;
 }
 

@@ -1,0 +1,200 @@
+// alac_float_in.hip — float32 PCM -> the packed interleaved integer PCM alac_hip_encode reads (alac_hip_encode_float).
+// One streaming pass in front of the unchanged encoder: quantize by the rule of include/alac_hip.h, pack, count clips.
+#include "alac_dev.hpp"
+#include "alac_kernels.hpp"
+
+namespace alacdev {
+
+// the rule of alac_hip_encode_float: r = rint(x * 2^(DEPTH-1)) (the product is exact), saturated; NaN -> 0.  r is an
+// integer, so "r > 2^(DEPTH-1) - 1" is "r >= 2^(DEPTH-1)", a comparison with an exact float even at 32 bits.
+template <int DEPTH>
+__device__ __forceinline__ int32_t quantize(float x, uint32_t &clips)
+{
+    constexpr float kScale = (float)(1ull << (DEPTH - 1));
+    constexpr int32_t kMax = (int32_t)((1ull << (DEPTH - 1)) - 1);
+    const float r = rintf(x * kScale);
+    const bool nan = x != x, hi = r >= kScale;
+    clips += (nan || hi || r < -kScale) ? 1u : 0u;
+    // fmaxf(NaN, y) = y, so the conversion only ever sees a value in [-2^(DEPTH-1), 2^(DEPTH-1))
+    const int32_t s = (int32_t)fmaxf(r, -kScale);
+    return nan ? 0 : (hi ? kMax : s);
+}
+
+// a sample as it sits in its container: 20-bit left-justified in 3 bytes (task_load / load_sample read it back >> 4)
+template <int DEPTH>
+__device__ __forceinline__ uint32_t container(int32_t s)
+{
+    return DEPTH == 20 ? (uint32_t)s << 4 : (uint32_t)s;
+}
+
+// N interleaved samples (N a multiple of 4) -> their N * bytes_per_sample(DEPTH) / 4 little-endian dwords
+template <int DEPTH, int N>
+__device__ __forceinline__ void pack_dwords(const int32_t (&s)[N], uint32_t (&w)[N * (int)bytes_per_sample(DEPTH) / 4])
+{
+    if constexpr (DEPTH == 16) {
+#pragma unroll
+        for (int k = 0; k < N / 2; k++) w[k] = ((uint32_t)s[2 * k] & 0xffffu) | ((uint32_t)s[2 * k + 1] << 16);
+    } else if constexpr (DEPTH == 32) {
+#pragma unroll
+        for (int k = 0; k < N; k++) w[k] = (uint32_t)s[k];
+    } else {
+#pragma unroll
+        for (int q = 0; q < N / 4; q++) {
+            const uint32_t v0 = container<DEPTH>(s[4 * q]) & 0xffffffu, v1 = container<DEPTH>(s[4 * q + 1]) & 0xffffffu;
+            const uint32_t v2 = container<DEPTH>(s[4 * q + 2]) & 0xffffffu, v3 = container<DEPTH>(s[4 * q + 3]) & 0xffffffu;
+            w[3 * q] = v0 | (v1 << 24);
+            w[3 * q + 1] = (v1 >> 8) | (v2 << 16);
+            w[3 * q + 2] = (v2 >> 16) | (v3 << 8);
+        }
+    }
+}
+
+// W dwords to dst, as 16-byte stores where W allows it, else 8-byte, else dword (dst is aligned to 4 * W bytes' largest
+// power-of-two divisor up to 16: a whole 4-frame group at a 4-frame-aligned position of the 256-byte aligned stage)
+template <int W>
+__device__ __forceinline__ void store_dwords(uint8_t *dst, const uint32_t (&w)[W])
+{
+    if constexpr (W % 4 == 0) {
+#pragma unroll
+        for (int k = 0; k < W / 4; k++) ((uint4 *)dst)[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+    } else if constexpr (W % 2 == 0) {
+#pragma unroll
+        for (int k = 0; k < W / 2; k++) ((uint2 *)dst)[k] = make_uint2(w[2 * k], w[2 * k + 1]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < W; k++) ((uint32_t *)dst)[k] = w[k];
+    }
+}
+
+template <int DEPTH>
+__device__ __forceinline__ void store_sample(uint8_t *dst, int32_t s)
+{
+    if constexpr (DEPTH == 16) {
+        *(uint16_t *)dst = (uint16_t)s;
+    } else if constexpr (DEPTH == 32) {
+        *(uint32_t *)dst = (uint32_t)s;
+    } else {
+        const uint32_t v = container<DEPTH>(s);
+        dst[0] = (uint8_t)v;
+        dst[1] = (uint8_t)(v >> 8);
+        dst[2] = (uint8_t)(v >> 16);
+    }
+}
+
+enum FloatLayout : int {
+    kFloatPlanar = 0,       // frameStride 1: each channel's row contiguous (16-byte loads per channel)
+    kFloatInterleaved = 1,  // channelStride 1, frameStride CH: frames contiguous (16-byte loads over the frame)
+    kFloatGeneral = 2,      // any strides, any channel count: one load and one store per sample
+};
+
+// One lane: 4 consecutive frames of one packet; a block: 1 024 frames of one packet (blocksPerPacket blocks per packet, a
+// grid-stride loop over them).  Frames at or behind n = min(numSamples[p], frameSize) are not read and staged as zero.
+// CH: 1 or 2 (the vector layouts, frameSize % 4 == 0, aligned strides and base: the host checks) or 0 (kFloatGeneral,
+// a.channels at run time).  Clipped samples: per lane <= 4 * kMaxChannels; the wave sums them with one ballot per bit
+// of the lane's count and adds the total to clipped[p] with one atomic (a block, hence a wave, lies in one packet).
+template <int DEPTH, int CH, int LAYOUT>
+__global__ __launch_bounds__(256) void k_float_to_pcm(FloatInArgs a, uint64_t blocksPerPacket)
+{
+    constexpr uint32_t BPS = bytes_per_sample(DEPTH);
+    constexpr int CNT_BITS = CH == 1 ? 3 : (CH == 2 ? 4 : 6);  // bits of a lane's clip count: <= 4, 8, 32
+    const uint64_t totalBlocks = (uint64_t)a.numPackets * blocksPerPacket;
+    for (uint64_t vb = blockIdx.x; vb < totalBlocks; vb += gridDim.x) {
+        const uint32_t p = (uint32_t)(vb / blocksPerPacket);
+        const uint32_t i0 = (uint32_t)(vb % blocksPerPacket) * 1024u + threadIdx.x * 4u;
+        const uint32_t fs = a.frameSize;
+        uint32_t n = a.numSamples ? a.numSamples[p] : fs;
+        n = n < fs ? n : fs;
+        const uint64_t f0 = (uint64_t)p * fs + i0;  // frame index of the lane's first frame in the batch
+        uint32_t clips = 0;
+        if constexpr (LAYOUT == kFloatGeneral) {
+            const uint32_t C = a.channels;
+            for (uint32_t k = 0; k < 4; k++) {
+                const uint32_t i = i0 + k;
+                if (i >= fs) break;
+                uint8_t *dst = a.pcm + (f0 + k) * C * BPS;
+                for (uint32_t c = 0; c < C; c++) {
+                    const float x = i < n ? a.in[c * a.channelStride + (f0 + k) * a.frameStride] : 0.0f;
+                    store_sample<DEPTH>(dst + c * BPS, quantize<DEPTH>(x, clips));
+                }
+            }
+        } else if (i0 < fs) {  // vector layouts: frameSize % 4 == 0, so the lane's 4 frames lie in the packet
+            float x[CH][4];
+            if (i0 + 4 <= n) {
+                if constexpr (LAYOUT == kFloatPlanar) {
+#pragma unroll
+                    for (int c = 0; c < CH; c++) {
+                        const float4 v = *(const float4 *)(a.in + c * a.channelStride + f0);
+                        x[c][0] = v.x, x[c][1] = v.y, x[c][2] = v.z, x[c][3] = v.w;
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < CH; q++) {
+                        const float4 v = *(const float4 *)(a.in + f0 * CH + 4 * q);
+                        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                        for (int k = 0; k < 4; k++) x[(4 * q + k) % CH][(4 * q + k) / CH] = e[k];
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < CH; c++)
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        x[c][k] = i0 + k < n ? a.in[c * a.channelStride + (f0 + k) * a.frameStride] : 0.0f;
+            }
+            int32_t s[4 * CH];
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+#pragma unroll
+                for (int c = 0; c < CH; c++) s[k * CH + c] = quantize<DEPTH>(x[c][k], clips);
+            uint32_t w[CH * BPS];
+            pack_dwords<DEPTH, 4 * CH>(s, w);
+            store_dwords<CH * BPS>(a.pcm + f0 * (CH * BPS), w);
+        }
+        if (a.clipped) {
+            uint32_t total = 0;
+#pragma unroll
+            for (int b = 0; b < CNT_BITS; b++) total += (uint32_t)__popcll(__ballot((clips >> b) & 1u)) << b;
+            if ((threadIdx.x & 63) == 0 && total) atomicAdd(a.clipped + p, total);
+        }
+    }
+}
+
+template <int DEPTH>
+static void launch_depth(const FloatInArgs &a, FloatLayout layout, dim3 grid, uint64_t bpp, hipStream_t st)
+{
+    if (layout == kFloatGeneral)
+        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 0, kFloatGeneral>), grid, dim3(256), 0, st, a, bpp);
+    else if (a.channels == 1)
+        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 1, kFloatPlanar>), grid, dim3(256), 0, st, a, bpp);
+    else if (layout == kFloatPlanar)
+        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 2, kFloatPlanar>), grid, dim3(256), 0, st, a, bpp);
+    else
+        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 2, kFloatInterleaved>), grid, dim3(256), 0, st, a, bpp);
+}
+
+hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t st)
+{
+    if (a.numPackets == 0) return hipSuccess;
+    if (a.clipped) {
+        const hipError_t e = hipMemsetAsync(a.clipped, 0, (uint64_t)a.numPackets * 4, st);
+        if (e != hipSuccess) return e;
+    }
+    // the vector paths: whole 4-frame groups inside a packet, 16-byte aligned float4 loads at every group
+    const bool vecFrames = a.frameSize % 4 == 0 && ((uintptr_t)a.in & 15) == 0 && a.channels <= 2;
+    FloatLayout layout = kFloatGeneral;
+    if (vecFrames && a.frameStride == 1 && (a.channels == 1 || a.channelStride % 4 == 0)) layout = kFloatPlanar;
+    else if (vecFrames && a.channels == 2 && a.channelStride == 1 && a.frameStride == 2) layout = kFloatInterleaved;
+    const uint64_t bpp = ((uint64_t)a.frameSize + 1023) / 1024;
+    const uint64_t blocks = (uint64_t)a.numPackets * bpp;
+    const dim3 grid((uint32_t)(blocks < (1u << 22) ? blocks : (1u << 22)));
+    switch (depth) {
+    case 16: launch_depth<16>(a, layout, grid, bpp, st); break;
+    case 20: launch_depth<20>(a, layout, grid, bpp, st); break;
+    case 24: launch_depth<24>(a, layout, grid, bpp, st); break;
+    default: launch_depth<32>(a, layout, grid, bpp, st); break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace alacdev

@@ -280,6 +280,20 @@ hipError_t launch_decode_v1_elements(const DecodeArgs &da, const McElement *el, 
                                      uint64_t capWords, int32_t *plane, uint32_t *prog, uint32_t *elemBit,
                                      uint32_t *mismatch, hipStream_t st);
 
+// ---- float32 input (alac_float_in.hip): alac_hip_encode_float's quantize pass in front of the encoder ----
+// sample i of channel c of packet p is in[c * channelStride + (p * frameSize + i) * frameStride]; pcm gets the packed
+// interleaved integer PCM of every packet at the full-packet stride (frames at or behind min(numSamples[p], frameSize) are
+// not read and staged as zero); clipped (nullable) gets the count of clipped samples per packet (zeroed by the launcher)
+struct FloatInArgs {
+    const float *in;
+    uint64_t channelStride, frameStride;
+    const uint32_t *numSamples;  // null: every packet frameSize frames
+    uint32_t numPackets, frameSize, channels;
+    uint8_t *pcm;
+    uint32_t *clipped;
+};
+hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t st);
+
 // ---- stage-level ----
 hipError_t launch_pc_block(const int32_t *in, int32_t *pc, uint32_t rows, uint32_t stride, int32_t num,
                            int16_t *coefs, int32_t numactive, uint32_t chanbits, uint32_t denshift,

@@ -119,7 +119,7 @@ size_t find_caf_chunk(const Bytes &f, const char *want, uint32_t *sizeLow)
 // ---------------------------------------------------------------------------------------------
 // sniffing
 // ---------------------------------------------------------------------------------------------
-std::string sniff_input(const Bytes &f, InputInfo &info)
+std::string sniff_input(const Bytes &f, InputInfo &info, bool acceptFloat)
 {
     memset(&info, 0, sizeof(info));
     const std::string cannot = "Cannot determine what format file is";
@@ -145,6 +145,7 @@ std::string sniff_input(const Bytes &f, InputInfo &info)
                 } else if (formatID == 0x6c70636du) {  // 'lpcm'
                     info.isAlac = false;
                     info.bigEndianPcm = (flags & 2u) == 0;  // CAF flag bit 1 = little endian (:428-436)
+                    info.isFloat = acceptFloat && (flags & 1u) != 0;  // kCAFLinearPCMFormatFlagIsFloat
                 } else {
                     return "data format is of an unsupported type";  // main.cu:145-149
                 }
@@ -180,7 +181,16 @@ std::string sniff_input(const Bytes &f, InputInfo &info)
             if (tag_is(&f[pos], "fmt ")) {
                 if (pos + 24 > f.size()) return cannot;
                 const uint8_t *b = &f[pos + 4];  // the 20 bytes the reference reads: size(4) then the format fields
-                if (b[4] != 1 || b[5] != 0) return cannot;  // only WAVE_FORMAT_PCM (:229-234)
+                const uint32_t tag = (uint32_t)b[4] | ((uint32_t)b[5] << 8);
+                if (acceptFloat && tag == 3) {  // WAVE_FORMAT_IEEE_FLOAT
+                    info.isFloat = true;
+                } else if (acceptFloat && tag == 0xFFFEu) {  // WAVE_FORMAT_EXTENSIBLE: the subformat GUID at body + 24
+                    static const uint8_t kFloatGuid[16] = {3, 0, 0, 0, 0, 0, 0x10, 0, 0x80, 0, 0, 0xAA, 0, 0x38, 0x9B, 0x71};
+                    if (le32(b) < 40 || pos + 8 + 40 > f.size() || memcmp(b + 4 + 24, kFloatGuid, 16) != 0) return cannot;
+                    info.isFloat = true;
+                } else if (b[4] != 1 || b[5] != 0) {
+                    return cannot;  // only WAVE_FORMAT_PCM (:229-234)
+                }
                 info.isAlac = false;
                 info.channels = b[6];
                 info.sampleRate = (double)le32(b + 8);

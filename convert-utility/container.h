@@ -25,6 +25,7 @@ struct InputInfo {
     FileKind kind;
     bool isAlac;          /* 'alac' (decode) vs 'lpcm' (encode) */
     bool bigEndianPcm;    /* CAF lpcm without the little-endian flag: samples are swapped on the way in */
+    bool isFloat;         /* acceptFloat only: IEEE float PCM (WAVE tag 3 or EXTENSIBLE float, CAF lpcm float flag) */
     double sampleRate;
     uint32_t channels;
     uint32_t bitsPerChannel;   /* lpcm: sample width; alac: 0 */
@@ -34,8 +35,10 @@ struct InputInfo {
     uint64_t dataSize;         /* payload bytes, clamped to what the file really holds */
 };
 
-/* returns an empty string on success, else the reference's diagnostic text */
-std::string sniff_input(const Bytes &file, InputInfo &info);
+/* returns an empty string on success, else the reference's diagnostic text.  acceptFloat (alacconvert --float-bits): a
+ * WAVE file of format tag 3 (IEEE float) or WAVE_FORMAT_EXTENSIBLE with the IEEE-float subformat is accepted too, and a
+ * CAF lpcm description with the float flag (bit 0) sets isFloat; without it every file is sniffed as the reference does. */
+std::string sniff_input(const Bytes &file, InputInfo &info, bool acceptFloat = false);
 
 /* ---- BER-style variable length integers of the CAF packet table (CAFFileALAC.cpp:189-260) ---- */
 void append_ber(Bytes &out, uint32_t value);

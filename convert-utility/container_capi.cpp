@@ -18,11 +18,13 @@ struct alacfile_info {
 };
 
 /* returns 0 on success, -1 with the diagnostic in err[errcap] */
-int32_t alacfile_sniff(const uint8_t *file, uint64_t size, alacfile_info *out, char *err, uint32_t errcap)
+static int32_t sniff(const uint8_t *file, uint64_t size, alacfile_info *out, char *err, uint32_t errcap, bool acceptFloat,
+                     int32_t *is_float)
 {
     Bytes f(file, file + size);
     InputInfo info;
-    const std::string e = sniff_input(f, info);
+    const std::string e = sniff_input(f, info, acceptFloat);
+    if (is_float) *is_float = info.isFloat ? 1 : 0;
     if (err && errcap) {
         strncpy(err, e.c_str(), errcap - 1);
         err[errcap - 1] = 0;
@@ -38,6 +40,18 @@ int32_t alacfile_sniff(const uint8_t *file, uint64_t size, alacfile_info *out, c
     out->data_pos = info.dataPos;
     out->data_size = info.dataSize;
     return e.empty() ? 0 : -1;
+}
+
+int32_t alacfile_sniff(const uint8_t *file, uint64_t size, alacfile_info *out, char *err, uint32_t errcap)
+{
+    return sniff(file, size, out, err, errcap, false, nullptr);
+}
+
+/* the sniffing of alacconvert --float-bits: float WAVE / CAF accepted, *is_float = 1 for them */
+int32_t alacfile_sniff_float(const uint8_t *file, uint64_t size, alacfile_info *out, int32_t *is_float, char *err,
+                             uint32_t errcap)
+{
+    return sniff(file, size, out, err, errcap, true, is_float);
 }
 
 static uint64_t give(const Bytes &b, uint8_t *out, uint64_t cap)

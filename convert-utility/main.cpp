@@ -29,6 +29,12 @@
  *                                             output bytes are those of the same command without --verify
  *   --compare <in.caf|in.m4a> <reference.wav> decode an ALAC file and compare it with a WAV / PCM CAF on the GPU, writing
  *                                             nothing: exit 0 if every frame matches, 1 otherwise (or on an error)
+ *   --float-bits N                            encode only, N = 16, 20, 24 or 32: the inputs are 32-bit IEEE-float PCM (WAVE
+ *                                             format tag 3 or EXTENSIBLE float, CAF lpcm with the float flag, either byte
+ *                                             order), quantized on the GPU (alac_hip_encode_float) and encoded at N bits.  The
+ *                                             output is the file an integer input holding the quantized samples gives; a
+ *                                             clip count is a warning on stderr.  Integer or 64-bit float inputs and
+ *                                             --verify are refused
  *
  * A single chained file is serial by construction: one file runs as one chain of dependent
  * packets; the GPU pays off with --batch or --segment-packets.
@@ -58,6 +64,9 @@ struct Job {
     Bytes file;
     InputInfo info;
     Bytes result;
+    // --float-bits: info describes the integer file of the quantized samples; the floats are at floatPos in `file`
+    bool floatIn = false, floatBigEndian = false;
+    uint64_t floatPos = 0;
 };
 
 void usage()
@@ -76,6 +85,7 @@ void usage()
     printf("        alacconvert --lpc [--batch] <input wav or caf file> <output caf or m4a file> ...\n");
     printf("        alacconvert --verify [--batch] [--lpc] ... <input wav or caf file> <output caf or m4a file> ...\n");
     printf("        alacconvert --compare <input caf or m4a file> <reference wav or caf file>\n");
+    printf("        alacconvert --float-bits N [--batch] [--lpc] ... <input float wav or caf file> <output caf or m4a file> ...\n");
     printf("\n");
 }
 
@@ -173,10 +183,38 @@ bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, b
         if (s == 0 || segFirst[s] != segs.back()) segs.push_back(segFirst[s]);
     const uint32_t np = (uint32_t)numSamples.size();
 
-    Bytes pcm((size_t)np * packetBytes, 0), stream;
+    const bool floatIn = jobs[0]->floatIn;
+    Bytes pcm(floatIn ? 0 : (size_t)np * packetBytes, 0), stream;
     std::vector<uint32_t> sizes(np, 0);
     uint64_t total = 0;
-    if (np) {
+    if (np && floatIn) {
+        // interleaved floats at the full-packet stride: channel_stride 1, frame_stride ch
+        std::vector<float> fl((size_t)np * frame * ch, 0.0f);
+        for (size_t j = 0; j < jobs.size(); j++) {
+            Job &J = *jobs[j];
+            uint8_t *dst = (uint8_t *)(fl.data() + (size_t)firstPacket[j] * frame * ch);
+            const uint64_t bytes = J.info.dataSize / bytesPerFrame * ch * sizeof(float);
+            memcpy(dst, J.file.data() + J.floatPos, (size_t)bytes);
+            if (J.floatBigEndian) alacfile::swap_samples_in_place(dst, bytes, 32);
+        }
+        stream.resize((size_t)np * (packetBytes + kALACMaxEscapeHeaderBytes));
+        std::vector<uint32_t> clipped(np, 0);
+        const int32_t rc = enc.EncodeSegmentsFloat(fl.data(), 1, ch, numSamples.data(), np, segs.data(),
+                                                   (uint32_t)segs.size() - 1, stream.data(), stream.size(), sizes.data(),
+                                                   &total, clipped.data());
+        if (rc != ALAC_noErr) {
+            fprintf(stderr, " Encoding failed (status %d)\n", rc);
+            return false;
+        }
+        for (size_t j = 0; j < jobs.size(); j++) {
+            const uint32_t p0 = firstPacket[j], p1 = j + 1 < jobs.size() ? firstPacket[j + 1] : np;
+            uint64_t clips = 0;
+            for (uint32_t p = p0; p < p1; p++) clips += clipped[p];
+            if (clips)
+                fprintf(stderr, " Warning: %llu samples clipped to %u bits: \"%s\"\n", (unsigned long long)clips,
+                        first.bitsPerChannel, jobs[j]->in.c_str());
+        }
+    } else if (np) {
         for (size_t j = 0; j < jobs.size(); j++) {
             Job &J = *jobs[j];
             uint8_t *dst = pcm.data() + (size_t)firstPacket[j] * packetBytes;
@@ -384,7 +422,7 @@ int main(int argc, char *argv[])
 {
     std::vector<std::string> files;
     bool batch = false, lpc = false, verify = false, compare = false, malformed = argc < 2;
-    uint32_t segmentPackets = 0, devices = 0;
+    uint32_t segmentPackets = 0, devices = 0, floatBits = 0;
     for (int i = 1; i < argc && !malformed; i++) {
         const std::string a = argv[i];
         if (a == "-h") {
@@ -400,6 +438,9 @@ int main(int argc, char *argv[])
         } else if (a == "--segment-packets" && i + 1 < argc) {
             segmentPackets = (uint32_t)strtoul(argv[++i], nullptr, 10);
             if (segmentPackets == 0) malformed = true;
+        } else if (a == "--float-bits" && i + 1 < argc) {
+            floatBits = (uint32_t)strtoul(argv[++i], nullptr, 10);
+            if (floatBits != 16 && floatBits != 20 && floatBits != 24 && floatBits != 32) malformed = true;
         } else if (a == "--devices" && i + 1 < argc) {
             devices = (uint32_t)strtoul(argv[++i], nullptr, 10);
             if (devices == 0) malformed = true;
@@ -413,12 +454,16 @@ int main(int argc, char *argv[])
     if (!malformed && (files.size() < 2 || (files.size() & 1) || (!batch && files.size() != 2))) malformed = true;
     if (!malformed && devices && !batch) malformed = true;  // one file is one serial chain: nothing to deal out
     // --compare stands alone: two files, no other option
-    if (!malformed && compare && (batch || lpc || verify || segmentPackets || devices)) malformed = true;
+    if (!malformed && compare && (batch || lpc || verify || segmentPackets || devices || floatBits)) malformed = true;
     if (malformed) {
         usage();
         return 1;
     }
     if (compare) return compare_files(files[0], files[1]);
+    if (floatBits && verify) {
+        fprintf(stderr, " --verify does not take float input (--float-bits): \"%s\"\n", files[0].c_str());
+        return 1;
+    }
 
     std::vector<Job> jobs(files.size() / 2);
     for (size_t j = 0; j < jobs.size(); j++) {
@@ -431,10 +476,29 @@ int main(int argc, char *argv[])
         }
         printf("Input file: %s\n", J.in.c_str());
         printf("Output file: %s\n", J.out.c_str());
-        const std::string err = alacfile::sniff_input(J.file, J.info);
+        const std::string err = alacfile::sniff_input(J.file, J.info, floatBits != 0);
         if (!err.empty()) {
             fprintf(stderr, " %s: \"%s\"\n", err.c_str(), J.in.c_str());
             return 1;
+        }
+        if (floatBits) {
+            if (!J.info.isFloat) {
+                fprintf(stderr, " --float-bits takes float PCM input, not integer PCM or ALAC: \"%s\"\n", J.in.c_str());
+                return 1;
+            }
+            if (J.info.bitsPerChannel != 32 || J.info.channels < 1 || J.info.channels > 8) {
+                fprintf(stderr, " %u-bit %u-channel float input is not supported (32-bit float, 1 to 8 channels): \"%s\"\n",
+                        J.info.bitsPerChannel, J.info.channels, J.in.c_str());
+                return 1;
+            }
+            // from here on the file is the integer file of its quantized samples; the floats stay where they are
+            const uint64_t frames = J.info.dataSize / (4ull * J.info.channels);
+            J.floatIn = true;
+            J.floatPos = J.info.dataPos;
+            J.floatBigEndian = J.info.bigEndianPcm;
+            J.info.isFloat = J.info.bigEndianPcm = false;
+            J.info.bitsPerChannel = floatBits;
+            J.info.dataSize = frames * J.info.channels * ((floatBits + 7) >> 3);
         }
         if (!J.info.isAlac) {
             const uint32_t b = J.info.bitsPerChannel;

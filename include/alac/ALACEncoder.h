@@ -58,6 +58,12 @@ public:
     int32_t EncodeSegments(const void *pcm, const uint32_t *numSamples, uint32_t numPackets, const uint32_t *segFirst,
                            uint32_t numSegments, uint8_t *out, uint64_t outCapacity, uint32_t *packetBytes,
                            uint64_t *outTotalBytes);
+    /* EncodeSegments from float32 PCM (alac_hip_encode_float_host): sample i of channel c of packet p at
+     * pcm[c * channelStride + (p * frameSize + i) * frameStride], quantized to the encoder's bit depth on the GPU by the
+     * rule of alac_hip.h; clipped: [numPackets] clipped samples per packet, or NULL.  No reference counterpart. */
+    int32_t EncodeSegmentsFloat(const float *pcm, uint64_t channelStride, uint64_t frameStride, const uint32_t *numSamples,
+                                uint32_t numPackets, const uint32_t *segFirst, uint32_t numSegments, uint8_t *out,
+                                uint64_t outCapacity, uint32_t *packetBytes, uint64_t *outTotalBytes, uint32_t *clipped);
 
     int32_t LastStatus() const { return mLastStatus; }
 

@@ -168,6 +168,60 @@ int32_t alac_hip_encode_segmented(alac_hip_ctx *ctx, const alac_hip_format *fmt,
                                   void *d_workspace, uint64_t workspace_bytes, uint8_t *d_out,
                                   uint64_t out_capacity, uint32_t *d_packet_bytes, uint64_t *d_packet_offsets);
 
+/* ---- batch encode from float32 PCM ------------------------------------------------------------------------------------
+ * The encode-side counterpart of alac_hip_decode_float: a PyTorch caller holding a float32 [channels, frames] tensor (or a
+ * WAV file's interleaved [frames, channels] floats) encodes it without quantizing, interleaving and packing it first.  No
+ * reference counterpart.  The call means "quantize by the rule below, then alac_hip_encode_segmented on the result": every
+ * encode option (lpc, fast_mode, the regime keys), the segment table, max_segment_packets and the state rules are those of
+ * alac_hip_encode_segmented, and the bytes, sizes, offsets and final state are what it gives for the quantized PCM.
+ * Asynchronous like alac_hip_encode_segmented.
+ * Quantization, for bit depth b in {16, 20, 24, 32} and an input float x:
+ *     r = rint(x * 2^(b-1))                 # round half to even; the product is exact (power-of-two scale)
+ *     s = 0                 if x is NaN
+ *         2^(b-1) - 1       if r >  2^(b-1) - 1   (+inf included)
+ *         -2^(b-1)          if r < -2^(b-1)       (-inf included)
+ *         (int) r           otherwise
+ *     clipped(x) = x is NaN or r was outside [-2^(b-1), 2^(b-1) - 1]
+ *   x = 1.0 clips to 2^(b-1) - 1 and counts as clipped; x = -1.0 is exact; -0.0 and denormals give 0.  At 32 bits the
+ *   float product is exact and every finite x < 1.0 is at most 2^31 - 128, so it never clips.  A 20-bit sample goes into
+ *   its 3-byte container left-justified (s << 4), as alac_hip_encode reads it.  So alac_hip_decode_float(alac_hip_encode_float
+ *   (x)) == x bit for bit whenever x * 2^(b-1) is an integer in range.
+ *   d_in              float32, 4-byte aligned: sample i of channel c of packet p at
+ *                     d_in[c * channel_stride + (p * frame_size + i) * frame_stride].  Planar [C, T] is (channel_stride >= T,
+ *                     frame_stride = 1), interleaved [T, C] is (channel_stride = 1, frame_stride = C); both take 16-byte
+ *                     vector loads when frame_size is a multiple of 4, d_in is 16-byte aligned and (planar) channel_stride
+ *                     is a multiple of 4; any other layout takes one load per sample.
+ *   d_num_samples     as alac_hip_encode.  Only min(num_samples[p], frame_size) frames of packet p are read: nothing between
+ *                     rows, nothing behind a short last packet (a tensor of exactly T frames is safe); the staged frames
+ *                     behind them are zero.
+ *   d_workspace       alac_hip_encode_float_workspace_bytes bytes, 256-byte aligned: the encode workspace followed by the
+ *                     staged integer PCM (the last whole 256-byte blocks of workspace_bytes hold the stage, the encoder gets
+ *                     the rest).  Option lpc: size it for num_segments = num_packets, as for alac_hip_encode.
+ *   d_clipped         [num_packets] count of clipped samples per packet, or NULL (not counted)
+ *   the other arguments as alac_hip_encode_segmented.
+ * kALAC_ParamError, checked before anything is enqueued and with nothing written: a null or misaligned d_in, frame_stride 0,
+ * channel_stride 0 with more than one channel, a largest index (num_channels - 1) * channel_stride + (num_packets *
+ * frame_size - 1) * frame_stride whose byte offset overflows 64 bits, a workspace too small, and whatever
+ * alac_hip_encode_segmented refuses (a segment table without a bound is read back and checked first, where that call reads
+ * it back).
+ */
+uint64_t alac_hip_encode_float_workspace_bytes(const alac_hip_format *fmt, uint32_t num_packets, uint32_t num_segments);
+int32_t alac_hip_encode_float(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *d_in,
+                              uint64_t channel_stride, uint64_t frame_stride,
+                              const uint32_t *d_num_samples, uint32_t num_packets,
+                              const uint32_t *d_seg_first, uint32_t num_segments, uint32_t max_segment_packets,
+                              int16_t *d_state, int32_t state_in, void *d_workspace, uint64_t workspace_bytes,
+                              uint8_t *d_out, uint64_t out_capacity, uint32_t *d_packet_bytes,
+                              uint64_t *d_packet_offsets, uint32_t *d_clipped);
+/* Host-buffer form (synchronous, like alac_hip_encode_host_segments, whose table rules it shares): h_in in the layout above;
+ * the floats up to the last frame that h_num_samples covers are staged to the device.  h_clipped: [num_packets] or NULL. */
+int32_t alac_hip_encode_float_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *h_in,
+                                   uint64_t channel_stride, uint64_t frame_stride,
+                                   const uint32_t *h_num_samples, uint32_t num_packets,
+                                   const uint32_t *h_seg_first, uint32_t num_segments, int16_t *h_state,
+                                   int32_t state_in, uint8_t *h_out, uint64_t out_capacity,
+                                   uint32_t *h_packet_bytes, uint64_t *out_total_bytes, uint32_t *h_clipped);
+
 /* Per-kernel timing with HIP events recorded on the context's stream around the three kernels of
  * alac_hip_encode (the instrumented counterpart of the dead cudaEvent timing in
  * codec/CudaAlacEncoder.cu:52-65).  begin() arms up to max_calls encode calls; end() synchronises and

@@ -1,0 +1,96 @@
+"""Cost of encoding straight from planar float32 (alac_hip_encode_float) against encoding PCM that is already integer and
+against the conversion a torch user writes today:  python tools/encode_float_timing.py [--out result.json]
+For 10 000 and 125 000 synthetic packets (BASELINE configs[1] / the configs[3] shard), 16-bit and 24-bit stereo, every
+packet independent, from a float32 [2, T] device tensor on the grid (the synthetic PCM scaled by 2^-(bit_depth - 1)):
+  encode           alac_hip_encode on the integer PCM (interleaved packed bytes, already on the device)
+  encode_float     alac_hip_encode_float on the float tensor (and on the same floats interleaved, a transposed [T, 2])
+  torch+encode     nan_to_num / scale / round / clamp / cast / interleave / pack to 2 or 3 bytes in torch, then encode
+Times are device-synchronised wall times per call (best of 4 x 5 calls; inputs and outputs on the device, allocated once).
+The conversion kernel's own time (k_float_to_pcm) comes from a rocprofv3 --kernel-trace --stats run of this script."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+import alac_amd  # noqa: E402
+
+
+def best_of(ctx, fn, reps=5, rounds=4):
+    ctx.synchronize()
+    best = 1e9
+    for _ in range(rounds):
+        t = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        ctx.synchronize()
+        best = min(best, (time.perf_counter() - t) / reps)
+    return best
+
+
+def to_float(pcm, depth, channels):
+    """interleaved integer bytes -> float32 [channels, frames] (the tool's input, not timed)"""
+    if depth == 16:
+        s = pcm.view(torch.int16).to(torch.int32)
+    else:
+        b = pcm.view(-1, 3).to(torch.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        s = v - ((v & 0x800000) << 1)
+    return (s.float() * (2.0 ** -(depth - 1))).view(-1, channels).t().contiguous()
+
+
+def torch_pack(x, depth):
+    """float32 [channels, frames] -> the packed interleaved bytes alac_hip_encode reads: what a caller writes in torch"""
+    top = float(2 ** (depth - 1))
+    s = torch.nan_to_num(x, nan=0.0).mul(top).round().clamp(-top, top - 1).to(torch.int32).t().contiguous().view(-1)
+    if depth == 16:
+        return s.to(torch.int16).view(torch.uint8)
+    return torch.stack([s & 0xFF, (s >> 8) & 0xFF, (s >> 16) & 0xFF], dim=1).to(torch.uint8).view(-1)
+
+
+def measure(ctx, n, depth):
+    fmt = alac_amd.make_format(4096, depth, 2, 44100)
+    d_pcm = ctx.synth_pcm(0, n, fmt)
+    r = {"packets": n, "bit_depth": depth, "channels": 2}
+    with torch.cuda.stream(ctx.stream):
+        x = to_float(d_pcm, depth, 2)
+        bufs = ctx.encode_buffers(fmt, n)
+        ref = ctx.encode(fmt, d_pcm, n, bufs=ctx.encode_buffers(fmt, n))
+        got = ctx.encode_float(fmt, x, bufs=bufs)
+        ctx.synchronize()
+        total = int(ref["offsets"][-1].item())
+        assert torch.equal(got["offsets"], ref["offsets"]) and torch.equal(got["out"][:total], ref["out"][:total]), \
+            "encode_float differs from encode"
+        assert torch.equal(torch_pack(x, depth), d_pcm[:n * fmt.packet_bytes]), "torch packing differs"
+        r["encode_ms"] = best_of(ctx, lambda: ctx.encode(fmt, d_pcm, n, bufs=bufs)) * 1e3
+        r["encode_float_ms"] = best_of(ctx, lambda: ctx.encode_float(fmt, x, bufs=bufs)) * 1e3
+        xi = x.t().contiguous().t()  # the same floats interleaved: a [T, 2] tensor viewed as [2, T]
+        r["encode_float_interleaved_ms"] = best_of(ctx, lambda: ctx.encode_float(fmt, xi, bufs=bufs)) * 1e3
+        r["torch_encode_ms"] = best_of(ctx, lambda: ctx.encode(fmt, torch_pack(x, depth), n, bufs=bufs)) * 1e3
+    r["float_minus_encode_ms"] = r["encode_float_ms"] - r["encode_ms"]
+    r["float_over_torch"] = r["encode_float_ms"] / r["torch_encode_ms"]
+    # bytes the conversion moves: 4 read + 2 or 3 written per sample
+    r["conversion_bytes"] = n * 4096 * 2 * (4 + alac_amd.capi.BPS[depth])
+    print(json.dumps(r), flush=True)
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--packets", default="10000,125000")
+    ap.add_argument("--depths", default="16,24")
+    a = ap.parse_args()
+    ctx = alac_amd.Context(0)
+    res = [measure(ctx, int(n), int(d)) for d in a.depths.split(",") for n in a.packets.split(",")]
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
