@@ -3,7 +3,7 @@
 #include "alac/ALACDecoder.h"
 #include "alac_hip.h"
 
-#include <hip/hip_runtime.h>
+#include "alac_host.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -128,42 +128,39 @@ void ALACDecoder::fillWriteBuffer(void *deviceSampleBuffer, uint32_t /*numChanne
     const uint32_t bpf = mConfig.numChannels * bps_of(mConfig.bitDepth);
     if ((uint32_t)theOutputPacketBytes != mConfig.frameLength * bpf) return;
     const uint32_t np = (uint32_t)mQueuedSizes.size();
-    std::vector<uint64_t> offs(np + 1, 0);
-    for (uint32_t i = 0; i < np; i++) offs[i + 1] = offs[i] + mQueuedSizes[i];
     alac_hip_format fmt = {mConfig.frameLength, mConfig.bitDepth, mConfig.numChannels, mConfig.sampleRate};
-    const uint64_t wsBytes = alac_hip_decode_workspace_bytes_stream(&fmt, np, offs[np]);
-    void *dStream = nullptr, *dOffs = nullptr, *dWs = nullptr, *dNs = nullptr, *dSt = nullptr;
     hipStream_t st = (hipStream_t)alac_hip_stream(mCtx);
-    bool ok = hipMalloc(&dStream, offs[np] + 16) == hipSuccess && hipMalloc(&dOffs, (np + 1) * 8ull) == hipSuccess &&
-              hipMalloc(&dWs, wsBytes) == hipSuccess && hipMalloc(&dNs, np * 4ull) == hipSuccess &&
-              hipMalloc(&dSt, np * 4ull) == hipSuccess;
-    if (ok)
-        ok = hipMemcpyAsync(dStream, mQueued.data(), offs[np], hipMemcpyHostToDevice, st) == hipSuccess &&
-             hipMemcpyAsync(dOffs, offs.data(), (np + 1) * 8ull, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok) {
-        mLastStatus = alac_hip_decode(mCtx, mCookie.data(), (uint32_t)mCookie.size(), (const uint8_t *)dStream,
-                                      (const uint64_t *)dOffs, np, dWs, wsBytes, (uint8_t *)deviceSampleBuffer,
-                                      (uint32_t *)dNs, (int32_t *)dSt);
+    alachost::DevStream d;
+    alachost::DevBuf dWs, dNs, dSt;
+    uint64_t wsBytes = 0;
+    // a failed staging step is kALAC_MemFullError here, whichever it is
+    if (alachost::upload_stream(mQueued.data(), mQueuedSizes.data(), np, st, d,
+                                [](int32_t, const char *, hipError_t) { return (int32_t)kALAC_MemFullError; }) ||
+        dWs.alloc(wsBytes = alac_hip_decode_workspace_bytes_stream(&fmt, np, d.total)) || dNs.alloc(np * 4ull) ||
+        dSt.alloc(np * 4ull)) {
+        mLastStatus = kALAC_MemFullError;
+    } else {
+        mLastStatus = alac_hip_decode(mCtx, mCookie.data(), (uint32_t)mCookie.size(), (const uint8_t *)d.bytes.p,
+                                      (const uint64_t *)d.offs.p, np, dWs.p, wsBytes, (uint8_t *)deviceSampleBuffer,
+                                      (uint32_t *)dNs.p, (int32_t *)dSt.p);
         if (mLastStatus == ALAC_HIP_noErr && alac_hip_synchronize(mCtx) != ALAC_HIP_noErr) mLastStatus = kALAC_ParamError;
         // per-packet results: a packet that failed to decode must not pass for audio — its slot in the caller's buffer is
         // zeroed and the first failure becomes the status of the call (what Decode returned for that packet in the
         // reference's per-packet loop, convert-utility/main.cu:719-724)
         if (mLastStatus == ALAC_HIP_noErr) {
             std::vector<int32_t> stv(np, 0);
-            if (hipMemcpy(stv.data(), dSt, np * 4ull, hipMemcpyDeviceToHost) != hipSuccess) {
-                mLastStatus = kALAC_ParamError;
-            } else {
-                for (uint32_t i = 0; i < np; i++) {
-                    if (stv[i] == 0) continue;
-                    if (mLastStatus == ALAC_HIP_noErr) mLastStatus = stv[i];
-                    (void)hipMemset((uint8_t *)deviceSampleBuffer + (size_t)i * theOutputPacketBytes, 0, (size_t)theOutputPacketBytes);
-                }
+            if (hipMemcpy(stv.data(), dSt.p, np * 4ull, hipMemcpyDeviceToHost) != hipSuccess) mLastStatus = kALAC_ParamError;
+            int32_t first = ALAC_HIP_noErr;
+            for (uint32_t i = 0; i < np && mLastStatus == ALAC_HIP_noErr; i++) {
+                if (stv[i] == 0) continue;
+                if (first == ALAC_HIP_noErr) first = stv[i];
+                if (hipMemset((uint8_t *)deviceSampleBuffer + (size_t)i * theOutputPacketBytes, 0,
+                              (size_t)theOutputPacketBytes) != hipSuccess)
+                    mLastStatus = kALAC_ParamError;
             }
+            if (mLastStatus == ALAC_HIP_noErr) mLastStatus = first;
         }
-    } else {
-        mLastStatus = kALAC_MemFullError;
     }
-    (void)hipFree(dStream); (void)hipFree(dOffs); (void)hipFree(dWs); (void)hipFree(dNs); (void)hipFree(dSt);
     mQueued.clear();
     mQueuedSizes.clear();
 }

@@ -4,16 +4,26 @@
 #include "alac/ALACEncoder.h"
 #include "alac_hip.h"
 
-#include <hip/hip_runtime.h>
+#include "alac_host.hpp"
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 
 namespace {
 inline uint32_t bps_of(int depth) { return depth == 16 ? 2u : (depth == 32 ? 4u : 3u); }
 inline uint32_t be32(uint32_t v) { return __builtin_bswap32(v); }
 inline uint16_t be16(uint16_t v) { return (uint16_t)((v << 8) | (v >> 8)); }
+
+// SetFastMode (EncodeStereoFast, codec/ALACEncoder.cu:998-1001) and SetLPCMode onto the context, and the calls' format
+int32_t prepare(alac_hip_ctx *ctx, bool fast, bool lpc, uint32_t frameSize, int16_t bitDepth, uint32_t channels, uint32_t rate,
+                alac_hip_format &fmt)
+{
+    fmt = {frameSize, (uint32_t)bitDepth, channels, rate};
+    const int32_t rc = alac_hip_set_option(ctx, "fast_mode", fast ? 1 : 0);
+    return rc != ALAC_HIP_noErr ? rc : alac_hip_set_option(ctx, "lpc", lpc ? 1 : 0);
+}
 }  // namespace
 
 ALACEncoder::ALACEncoder()
@@ -107,10 +117,9 @@ void ALACEncoder::account(uint32_t outputSize)
 int32_t ALACEncoder::EncodeBatch(const void *pcm, uint64_t totalSamples, uint32_t segmentPackets, uint8_t *out,
                                  uint64_t outCapacity, uint32_t *packetBytes, uint64_t *outTotalBytes)
 {
-    if (!mCtx) return kALAC_ParamError;
-    (void)alac_hip_set_option(mCtx, "fast_mode", mFastMode ? 1 : 0);  // SetFastMode: EncodeStereoFast, codec/ALACEncoder.cu:998-1001
-    (void)alac_hip_set_option(mCtx, "lpc", mLPCMode ? 1 : 0);
-    alac_hip_format fmt = {mFrameSize, (uint32_t)mBitDepth, mNumChannels, mOutputSampleRate};
+    alac_hip_format fmt;  // (a null context: kALAC_ParamError from the first option call)
+    if ((mLastStatus = prepare(mCtx, mFastMode, mLPCMode, mFrameSize, mBitDepth, mNumChannels, mOutputSampleRate, fmt)))
+        return mLastStatus;
     const uint64_t np = (totalSamples + mFrameSize - 1) / mFrameSize;
     const uint64_t nseg = segmentPackets ? (np + segmentPackets - 1) / segmentPackets : 1;
     const uint32_t stateInt16 = alac_hip_state_int16(&fmt);  // 64 per element of a packet
@@ -134,10 +143,9 @@ int32_t ALACEncoder::EncodeSegments(const void *pcm, const uint32_t *numSamples,
                                     const uint32_t *segFirst, uint32_t numSegments, uint8_t *out, uint64_t outCapacity,
                                     uint32_t *packetBytes, uint64_t *outTotalBytes)
 {
-    if (!mCtx) return kALAC_ParamError;
-    (void)alac_hip_set_option(mCtx, "fast_mode", mFastMode ? 1 : 0);
-    (void)alac_hip_set_option(mCtx, "lpc", mLPCMode ? 1 : 0);
-    alac_hip_format fmt = {mFrameSize, (uint32_t)mBitDepth, mNumChannels, mOutputSampleRate};
+    alac_hip_format fmt;  // (a null context: kALAC_ParamError from the first option call)
+    if ((mLastStatus = prepare(mCtx, mFastMode, mLPCMode, mFrameSize, mBitDepth, mNumChannels, mOutputSampleRate, fmt)))
+        return mLastStatus;
     uint64_t total = 0;
     mLastStatus = alac_hip_encode_host_segments(mCtx, &fmt, pcm, numSamples, numPackets, segFirst, numSegments, nullptr, 0,
                                                 out, outCapacity, packetBytes, &total);
@@ -152,10 +160,9 @@ int32_t ALACEncoder::EncodeSegmentsFloat(const float *pcm, uint64_t channelStrid
                                          uint32_t numSegments, uint8_t *out, uint64_t outCapacity, uint32_t *packetBytes,
                                          uint64_t *outTotalBytes, uint32_t *clipped)
 {
-    if (!mCtx) return kALAC_ParamError;
-    (void)alac_hip_set_option(mCtx, "fast_mode", mFastMode ? 1 : 0);
-    (void)alac_hip_set_option(mCtx, "lpc", mLPCMode ? 1 : 0);
-    alac_hip_format fmt = {mFrameSize, (uint32_t)mBitDepth, mNumChannels, mOutputSampleRate};
+    alac_hip_format fmt;  // (a null context: kALAC_ParamError from the first option call)
+    if ((mLastStatus = prepare(mCtx, mFastMode, mLPCMode, mFrameSize, mBitDepth, mNumChannels, mOutputSampleRate, fmt)))
+        return mLastStatus;
     uint64_t total = 0;
     mLastStatus = alac_hip_encode_float_host(mCtx, &fmt, pcm, channelStride, frameStride, numSamples, numPackets, segFirst,
                                              numSegments, nullptr, 0, out, outCapacity, packetBytes, &total, clipped);
@@ -184,61 +191,32 @@ void ALACEncoder::InitializeSampling(void *d_ip, AudioFormatDescription theInput
     }
     const uint32_t np = (uint32_t)ns.size();
     if (np == 0) return;
-    (void)alac_hip_set_option(mCtx, "fast_mode", mFastMode ? 1 : 0);
-    (void)alac_hip_set_option(mCtx, "lpc", mLPCMode ? 1 : 0);
-    alac_hip_format fmt = {mFrameSize, (uint32_t)mBitDepth, mNumChannels, mOutputSampleRate};
+    alac_hip_format fmt;
+    if ((mLastStatus = prepare(mCtx, mFastMode, mLPCMode, mFrameSize, mBitDepth, mNumChannels, mOutputSampleRate, fmt))) return;
     const uint32_t segFirst[2] = {0, np};
-    const uint64_t stateBytes = alac_hip_state_int16(&fmt) * 2ull;
     const uint64_t wsBytes = alac_hip_encode_workspace_bytes(&fmt, np, mLPCMode ? np : 1);
     const uint64_t outMax = alac_hip_encode_max_output_bytes(&fmt, np);
-    void *dNs = nullptr, *dSeg = nullptr, *dState = nullptr, *dWs = nullptr, *dOut = nullptr, *dSizes = nullptr,
-         *dOffs = nullptr;
-    hipStream_t st = (hipStream_t)alac_hip_stream(mCtx);
-    bool ok = hipMalloc(&dNs, np * 4ull) == hipSuccess && hipMalloc(&dSeg, 8) == hipSuccess &&
-              hipMalloc(&dState, stateBytes) == hipSuccess && hipMalloc(&dWs, wsBytes) == hipSuccess &&
-              hipMalloc(&dOut, outMax) == hipSuccess && hipMalloc(&dSizes, np * 4ull) == hipSuccess &&
-              hipMalloc(&dOffs, (np + 1) * 8ull) == hipSuccess;
-    if (ok) {
-        ok = hipMemcpyAsync(dNs, ns.data(), np * 4ull, hipMemcpyHostToDevice, st) == hipSuccess &&
-             hipMemcpyAsync(dSeg, segFirst, 8, hipMemcpyHostToDevice, st) == hipSuccess;
-        if (ok && mStateValid) ok = hipMemcpyAsync(dState, mState, stateBytes, hipMemcpyHostToDevice, st) == hipSuccess;
-    }
-    if (ok) {
-        // one chained segment of np packets: the bound is known here, so the library does not read the table back
-        mLastStatus = alac_hip_encode_segmented(mCtx, &fmt, d_ip, (const uint32_t *)dNs, np, (const uint32_t *)dSeg, 1, np,
-                                                (int16_t *)dState, mStateValid ? 1 : 0, dWs, wsBytes, (uint8_t *)dOut, outMax,
-                                      (uint32_t *)dSizes, (uint64_t *)dOffs);
-        ok = (mLastStatus == ALAC_HIP_noErr);
-    } else {
-        mLastStatus = kALAC_MemFullError;
-    }
-    if (ok) {
-        mBatchSizes.resize(np);
-        mBatchOffsets.resize(np + 1);
-        ok = hipMemcpyAsync(mBatchSizes.data(), dSizes, np * 4ull, hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(mBatchOffsets.data(), dOffs, (np + 1) * 8ull, hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(mState, dState, stateBytes, hipMemcpyDeviceToHost, st) == hipSuccess;
-        // alac_hip_synchronize, not a bare stream sync: it also reads the context's hand-off error word — a consumer wave
-        // that gave up waiting for its producer has coded garbage, and the batch must fail instead of being handed out
-        int32_t syncRc = ALAC_HIP_noErr;
-        if (ok) {
-            syncRc = alac_hip_synchronize(mCtx);
-            ok = syncRc == ALAC_HIP_noErr;
-        }
-        if (ok) {
-            mBatchStream.resize(mBatchOffsets[np]);
-            ok = hipMemcpy(mBatchStream.data(), dOut, mBatchOffsets[np], hipMemcpyDeviceToHost) == hipSuccess;
-        }
-        if (ok) mStateValid = true;
-        mLastStatus = ok ? ALAC_noErr : (syncRc != ALAC_HIP_noErr ? syncRc : kALAC_ParamError);
-    }
-    if (!ok) {
-        mBatchStream.clear();
-        mBatchSizes.clear();
-        mBatchOffsets.clear();
-    }
-    (void)hipFree(dNs); (void)hipFree(dSeg); (void)hipFree(dState); (void)hipFree(dWs);
-    (void)hipFree(dOut); (void)hipFree(dSizes); (void)hipFree(dOffs);
+    std::unique_ptr<uint8_t[]> out(new uint8_t[outMax]);  // (not value-initialised: only the stream's bytes are written)
+    mBatchSizes.assign(np, 0);
+    uint64_t total = 0;
+    // one chained segment of np packets from the caller's device buffer: its bound is known, so the library does not read
+    // the table back.  alac_hip_synchronize reads the context's hand-off error word: a consumer wave that gave up waiting for
+    // its producer has coded garbage, and the batch must fail instead of being handed out.
+    mLastStatus = alachost::encode_host_common(
+        (hipStream_t)alac_hip_stream(mCtx), &fmt, ns.data(), np, segFirst, 1, mState, mStateValid ? 1 : 0, out.get(), outMax,
+        mBatchSizes.data(), &total, wsBytes,
+        [&](uint32_t maxSeg, const uint32_t *dNs, const uint32_t *dSeg, int16_t *dState, int32_t stIn, void *dWs, uint8_t *dOut,
+            uint64_t cap, uint32_t *dSizes, uint64_t *dOffs) {
+            return alac_hip_encode_segmented(mCtx, &fmt, d_ip, dNs, np, dSeg, 1, maxSeg, dState, stIn, dWs, wsBytes, dOut, cap,
+                                             dSizes, dOffs);
+        },
+        [](int32_t code, const char *, hipError_t) { return code; }, [&] { return alac_hip_synchronize(mCtx); });
+    const bool ok = mLastStatus == ALAC_HIP_noErr;  // (a failed batch hands out nothing)
+    mBatchStream.assign(out.get(), out.get() + (ok ? total : 0));
+    mBatchSizes.resize(ok ? np : 0);
+    mBatchOffsets.assign(ok ? np + 1 : 0, 0);
+    for (uint32_t p = 0; p < mBatchSizes.size(); p++) mBatchOffsets[p + 1] = mBatchOffsets[p] + mBatchSizes[p];
+    mStateValid = mStateValid || ok;
 }
 
 // codec/ALACEncoder.cu:973-1057

@@ -6,6 +6,7 @@
 #include "alac_kernels.hpp"
 #include "alac_verify.hpp"
 #include "alac_encode_v1_types.hpp"
+#include "alac_host.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +16,7 @@
 #include <vector>
 
 using namespace alacdev;
+using namespace alachost;
 
 struct alac_hip_ctx {
     int device = 0;
@@ -43,46 +45,49 @@ struct alac_hip_ctx {
 
 namespace alacdev {
 
-static int env_int(const char *name, int dflt)
-{
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
-
-AlacOptions alac_options_from_env()
-{
-    AlacOptions o;
-    o.thru = env_int("ALAC_HIP_THRU", o.thru);
-    o.narrow = env_int("ALAC_HIP_NARROW", o.narrow);
-    o.splitCoder = env_int("ALAC_HIP_SPLIT_CODER", o.splitCoder) != 0;
-    o.overlapPos = env_int("ALAC_HIP_OVERLAP_POS", o.overlapPos) != 0;
-    o.fused = env_int("ALAC_HIP_FUSED", o.fused) != 0;
-    o.fold = env_int("ALAC_HIP_FOLD", o.fold) != 0;
-    if (const char *e = getenv("ALAC_HIP_ENCODER")) o.laneEncoder = strcmp(e, "lane") == 0;
-    if (const char *e = getenv("ALAC_HIP_DECODER")) o.laneDecoder = strcmp(e, "lane") == 0;
-    if (const char *e = getenv("ALAC_HIP_DEC_FUSED")) o.decFused = *e ? (e[0] == '0' ? 0 : 1) : -1;
-    o.decPair = env_int("ALAC_HIP_DEC_PAIR", o.decPair) != 0;
-    o.decDirect = env_int("ALAC_HIP_DEC_DIRECT", o.decDirect) != 0;
-    o.stageTaps = env_int("ALAC_HIP_STAGE_TAPS", o.stageTaps) != 0;
-    o.loseHandoff = env_int("ALAC_HIP_DEBUG_LOSE_HANDOFF", o.loseHandoff) == 1;
-    return o;
-}
-
-// key -> slot and the range alac_hip_set_option accepts (include/alac_hip.h documents exactly these)
+// key -> the variable of its default, slot and the range alac_hip_set_option accepts (include/alac_hip.h documents exactly
+// these)
 const AlacOptionKey *alac_option_keys(uint32_t *count)
 {
     static const AlacOptionKey table[] = {
-        {"thru", &AlacOptions::thru, -1, 1},           {"narrow", &AlacOptions::narrow, -1, 1},
-        {"split_coder", &AlacOptions::splitCoder, 0, 1}, {"overlap_pos", &AlacOptions::overlapPos, 0, 1},
-        {"fused", &AlacOptions::fused, 0, 1},          {"fold", &AlacOptions::fold, 0, 1},
-        {"fast_mode", &AlacOptions::fastMode, 0, 1},   {"encoder_lane", &AlacOptions::laneEncoder, 0, 1},
-        {"decoder_lane", &AlacOptions::laneDecoder, 0, 1}, {"dec_fused", &AlacOptions::decFused, -1, 1},
-        {"dec_pair", &AlacOptions::decPair, 0, 1},     {"dec_direct", &AlacOptions::decDirect, 0, 2},
-        {"stage_taps", &AlacOptions::stageTaps, 0, 1},  {"lpc", &AlacOptions::lpc, 0, 1},
-        {"debug_lose_handoff", &AlacOptions::loseHandoff, 0, 1}, {"debug_waves", &AlacOptions::debugWaves, 0, 1},
+        {"thru", "ALAC_HIP_THRU", &AlacOptions::thru, -1, 1},
+        {"narrow", "ALAC_HIP_NARROW", &AlacOptions::narrow, -1, 1},
+        {"split_coder", "ALAC_HIP_SPLIT_CODER", &AlacOptions::splitCoder, 0, 1},
+        {"overlap_pos", "ALAC_HIP_OVERLAP_POS", &AlacOptions::overlapPos, 0, 1},
+        {"fused", "ALAC_HIP_FUSED", &AlacOptions::fused, 0, 1},
+        {"fold", "ALAC_HIP_FOLD", &AlacOptions::fold, 0, 1},
+        {"fast_mode", nullptr, &AlacOptions::fastMode, 0, 1},
+        {"encoder_lane", "ALAC_HIP_ENCODER", &AlacOptions::laneEncoder, 0, 1},
+        {"decoder_lane", "ALAC_HIP_DECODER", &AlacOptions::laneDecoder, 0, 1},
+        {"dec_fused", "ALAC_HIP_DEC_FUSED", &AlacOptions::decFused, -1, 1},
+        {"dec_pair", "ALAC_HIP_DEC_PAIR", &AlacOptions::decPair, 0, 1},
+        {"dec_direct", "ALAC_HIP_DEC_DIRECT", &AlacOptions::decDirect, 0, 2},
+        {"stage_taps", "ALAC_HIP_STAGE_TAPS", &AlacOptions::stageTaps, 0, 1},
+        {"lpc", nullptr, &AlacOptions::lpc, 0, 1},
+        {"debug_lose_handoff", "ALAC_HIP_DEBUG_LOSE_HANDOFF", &AlacOptions::loseHandoff, 0, 1},
+        {"debug_waves", nullptr, &AlacOptions::debugWaves, 0, 1},
     };
     if (count) *count = (uint32_t)(sizeof(table) / sizeof(table[0]));
     return table;
+}
+
+// The defaults of a new context: a key's variable counts when it is an integer inside the key's range
+// (ALAC_HIP_ENCODER=lane / ALAC_HIP_DECODER=lane: 1); anything else leaves the built-in default.
+AlacOptions alac_options_from_env()
+{
+    AlacOptions o;
+    uint32_t n = 0;
+    const AlacOptionKey *t = alac_option_keys(&n);
+    for (uint32_t i = 0; i < n; i++) {
+        const char *v = t[i].env ? getenv(t[i].env) : nullptr;
+        if (!v || !*v) continue;
+        const bool lane = t[i].slot == &AlacOptions::laneEncoder || t[i].slot == &AlacOptions::laneDecoder;
+        if (lane && strcmp(v, "lane") == 0) v = "1";
+        char *end = nullptr;
+        const long x = strtol(v, &end, 10);
+        if (*end == '\0' && x >= t[i].lo && x <= t[i].hi) o.*(t[i].slot) = (int32_t)x;
+    }
+    return o;
 }
 
 const AlacOptionKey *alac_option_find(const char *key)
@@ -111,6 +116,9 @@ int32_t fail(alac_hip_ctx *ctx, int32_t code, const char *what, hipError_t e = h
     return code;
 }
 
+// fail() in the form the staging steps of alac_host.hpp report through
+auto on_fail(alac_hip_ctx *ctx) { return [ctx](int32_t code, const char *what, hipError_t e) { return fail(ctx, code, what, e); }; }
+
 bool format_ok(const alac_hip_format *f)
 {
     if (!f) return false;
@@ -122,14 +130,21 @@ bool format_ok(const alac_hip_format *f)
 
 inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
-// the ALACSpecificConfig inside a cookie: ALACDecoder::Init skips legacy 'frma' and 'alac' atoms (codec/ALACDecoder.cu:123-134)
-const uint8_t *cookie_config(const uint8_t *ck, uint32_t &size)
+// The ALACSpecificConfig inside a cookie, and the format it holds; nullptr for a cookie the library cannot read.
+// ALACDecoder::Init skips legacy 'frma' and 'alac' atoms (codec/ALACDecoder.cu:123-134).
+const uint8_t *read_cookie(const uint8_t *ck, uint32_t size, alac_hip_format *out)
 {
+    if (!ck || !out) return nullptr;
     for (const char *atom : {"frma", "alac"})
         if (size >= 12 && memcmp(ck + 4, atom, 4) == 0) {
             ck += 12;
             size -= 12;
         }
+    if (size < 24 || ck[4] > 0) return nullptr;  // compatibleVersion <= kALACVersion (:153)
+    out->frame_size = ((uint32_t)ck[0] << 24) | ((uint32_t)ck[1] << 16) | ((uint32_t)ck[2] << 8) | ck[3];
+    out->bit_depth = ck[5];
+    out->num_channels = ck[9];
+    out->sample_rate = ((uint32_t)ck[20] << 24) | ((uint32_t)ck[21] << 16) | ((uint32_t)ck[22] << 8) | ck[23];
     return ck;
 }
 
@@ -368,87 +383,6 @@ uint64_t lpc_table_bytes(uint32_t numPackets) { return align_up((uint64_t)numPac
 
 bool use_lane_decoder(const alac_hip_ctx *ctx) { return ctx->opt.laneDecoder != 0; }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(uint64_t n) { return hipMalloc(&p, n ? n : 4); }
-};
-
-// alac_hip_decode_host / alac_hip_verify_host: the packets back to back and their offsets (prefix sum of the sizes) on the device
-struct DevStream {
-    DevBuf bytes, offs;
-    uint64_t total = 0;     // stream bytes
-    uint64_t pcmBytes = 0;  // of the decoded batch
-};
-int32_t upload_stream(alac_hip_ctx *ctx, const alac_hip_format &fmt, const uint8_t *h_stream, const uint32_t *h_packet_bytes,
-                      uint32_t num_packets, DevStream &d)
-{
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
-    d.pcmBytes = (uint64_t)num_packets * fmt.frame_size * fmt.num_channels * bytes_per_sample(fmt.bit_depth);
-    std::vector<uint64_t> offs(num_packets + 1, 0);
-    for (uint32_t i = 0; i < num_packets; i++) offs[i + 1] = offs[i] + h_packet_bytes[i];
-    d.total = offs[num_packets];
-    hipError_t e;
-    if ((e = d.bytes.alloc(d.total + 16)) || (e = d.offs.alloc((num_packets + 1) * 8ull)))
-        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
-    if ((e = hipMemcpyAsync(d.bytes.p, h_stream, d.total, hipMemcpyHostToDevice, ctx->stream)) ||
-        (e = hipMemcpyAsync(d.offs.p, offs.data(), (num_packets + 1) * 8ull, hipMemcpyHostToDevice, ctx->stream)))
-        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    return ALAC_HIP_noErr;
-}
-
-// The host forms of the encode calls: the checks of the tables, the tables and the state staged to the device, `launch` (the
-// device call on the staged buffers: (maxSeg, num samples, segment table, state, workspace, out, sizes, offsets) -> status),
-// the results copied back.  wsBytes: the device call's workspace.
-template <class Launch>
-int32_t encode_host_common(alac_hip_ctx *ctx, const alac_hip_format *fmt, const uint32_t *h_num_samples, uint32_t num_packets,
-                           const uint32_t *h_seg_first, uint32_t num_segments, int16_t *h_state, int32_t state_in,
-                           uint8_t *h_out, uint64_t out_capacity, uint32_t *h_packet_bytes, uint64_t *out_total_bytes,
-                           uint64_t wsBytes, Launch launch)
-{
-    const uint32_t np = num_packets, nseg = num_segments;
-    const uint64_t stateBytes = (uint64_t)nseg * alac_hip_state_int16(fmt) * 2;
-    const uint64_t outMax = alac_hip_encode_max_output_bytes(fmt, np);
-
-    DevBuf dNs, dSeg, dState, dWs, dOut, dSizes, dOffs;
-    hipError_t e;
-    if ((e = dNs.alloc(np * 4ull)) || (e = dSeg.alloc((nseg + 1) * 4ull)) || (e = dState.alloc(stateBytes)) ||
-        (e = dWs.alloc(wsBytes)) || (e = dOut.alloc(outMax)) || (e = dSizes.alloc(np * 4ull)) ||
-        (e = dOffs.alloc((np + 1) * 8ull)))
-        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
-    hipStream_t st = ctx->stream;
-    if ((e = hipMemcpyAsync(dNs.p, h_num_samples, np * 4ull, hipMemcpyHostToDevice, st)) ||
-        (e = hipMemcpyAsync(dSeg.p, h_seg_first, (nseg + 1) * 4ull, hipMemcpyHostToDevice, st)))
-        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    if (h_state && state_in)
-        if ((e = hipMemcpyAsync(dState.p, h_state, stateBytes, hipMemcpyHostToDevice, st)))
-            return fail(ctx, ALAC_HIP_ParamError, "H2D state", e);
-    uint32_t maxSeg = 1;
-    for (uint32_t s2 = 0; s2 < nseg; s2++) maxSeg = h_seg_first[s2 + 1] - h_seg_first[s2] > maxSeg ? h_seg_first[s2 + 1] - h_seg_first[s2] : maxSeg;
-    int32_t rc = launch(maxSeg, (const uint32_t *)dNs.p, (const uint32_t *)dSeg.p, (int16_t *)dState.p,
-                        (h_state && state_in) ? 1 : 0, dWs.p, (uint8_t *)dOut.p, outMax, (uint32_t *)dSizes.p,
-                        (uint64_t *)dOffs.p);
-    if (rc != ALAC_HIP_noErr) return rc;
-    uint64_t total = 0;
-    if ((e = hipMemcpyAsync(&total, (uint64_t *)dOffs.p + np, 8, hipMemcpyDeviceToHost, st)) ||
-        (e = hipStreamSynchronize(st)))
-        return fail(ctx, ALAC_HIP_ParamError, "encode execution", e);
-    if (total > out_capacity) return fail(ctx, ALAC_HIP_MemFullError, "host output buffer too small");
-    if ((e = hipMemcpyAsync(h_out, dOut.p, total, hipMemcpyDeviceToHost, st)) ||
-        (e = hipMemcpyAsync(h_packet_bytes, dSizes.p, np * 4ull, hipMemcpyDeviceToHost, st)))
-        return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
-    if (h_state)
-        if ((e = hipMemcpyAsync(h_state, dState.p, stateBytes, hipMemcpyDeviceToHost, st)))
-            return fail(ctx, ALAC_HIP_ParamError, "D2H state", e);
-    if ((e = hipStreamSynchronize(st))) return fail(ctx, ALAC_HIP_ParamError, "sync", e);
-    if (int32_t hrc = check_handoff(ctx)) return hrc;
-    if (out_total_bytes) *out_total_bytes = total;
-    return ALAC_HIP_noErr;
-}
-
 // the checks of a host segment table every host form makes
 int32_t host_segment_refusal(alac_hip_ctx *ctx, const uint32_t *h_seg_first, uint32_t num_segments, uint32_t num_packets)
 {
@@ -509,8 +443,8 @@ void alac_hip_destroy(alac_hip_ctx *ctx)
     if (!ctx) return;
     for (hipEvent_t e : ctx->events) (void)hipEventDestroy(e);
     ctx->events.clear();
+    (void)hipSetDevice(ctx->device);
     if (ctx->vsReady) {
-        (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->vs.side[0]);
         (void)hipStreamDestroy(ctx->vs.side[0]);
         for (uint32_t i = 0; i < kSideEvents; i++) {
@@ -520,14 +454,12 @@ void alac_hip_destroy(alac_hip_ctx *ctx)
         (void)hipEventDestroy(ctx->vs.fork);
     }
     if (ctx->mcReady) {
-        (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->mcStream);
         (void)hipStreamDestroy(ctx->mcStream);
         (void)hipEventDestroy(ctx->mcFork);
         (void)hipEventDestroy(ctx->mcJoin);
     }
     if (ctx->ownStream && ctx->stream) {
-        (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipStreamDestroy(ctx->stream);
     }
@@ -599,12 +531,54 @@ uint64_t alac_hip_encode_max_output_bytes(const alac_hip_format *fmt, uint32_t n
     return max_output_bytes(fmt, num_packets);
 }
 
-// The refusals of alac_hip_encode_segmented that need no device work, in its order (the format is checked already); 0 when
-// the call may go ahead.  alac_hip_encode_float runs them before it enqueues its conversion.
-static int32_t encode_refusal(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm, uint32_t num_packets,
-                              const uint32_t *d_seg_first, uint32_t num_segments, const void *d_workspace,
-                              uint64_t workspace_bytes, const uint8_t *d_out, uint64_t out_capacity,
-                              const uint32_t *d_packet_bytes, const uint64_t *d_packet_offsets)
+// ---- encode: each public call is checked and described once; encode_core / encode_elements run the description ----------
+// How a call knows its longest segment (the tap-parallel pipeline runs once per packet position of a segment)
+enum class SegKind {
+    Host,    // no table (1), or a table the library read back and checked on the host: no device check
+    Bound,   // the caller's max_segment_packets: the kernels check the table against it (launch_check_segments)
+    Unread,  // a table without a bound: the tap-parallel path reads it back (a host wait)
+};
+
+// one encode batch: its format and buffers, the LPC overrides, the resolved segment count, the stream it runs on
+struct EncodeCall {
+    alac_hip_format fmt;
+    const void *pcm;
+    const uint32_t *numSamples;
+    uint32_t numPackets;
+    const uint32_t *segFirst;  // nullptr: every packet is its own segment (in LPC mode whatever table the caller passes)
+    uint32_t numSegments;      // numPackets without a table
+    SegKind segKind;
+    uint32_t maxSeg;           // Host: the longest segment; Bound: the caller's bound (clamped to numPackets where used)
+    int16_t *state;            // nullptr in LPC mode: the coefficient state is neither read nor written
+    int32_t stateIn;
+    uint8_t *ws, *out;
+    uint32_t *packetBytes;
+    uint64_t *offsets;
+    hipStream_t stream;
+    bool lpc;
+    bool fast;   // SetFastMode applies (2-channel streams; not the stereo elements of a 3..8-channel stream)
+    bool timed;  // may consume a slot of the armed stage timing
+};
+
+// the description of an encode call under the context's options (no checks)
+static EncodeCall describe_encode(const alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *pcm,
+                                  const uint32_t *num_samples, uint32_t num_packets, const uint32_t *seg_first,
+                                  uint32_t num_segments, uint32_t max_segment_packets, int16_t *state, int32_t state_in,
+                                  void *ws, uint8_t *out, uint32_t *packet_bytes, uint64_t *offsets)
+{
+    const bool lpc = ctx->opt.lpc != 0;
+    const uint32_t *seg = lpc ? nullptr : seg_first;
+    const SegKind kind = !seg ? SegKind::Host : max_segment_packets ? SegKind::Bound : SegKind::Unread;
+    return {*fmt, pcm, num_samples, num_packets, seg, seg ? num_segments : num_packets, kind, seg ? max_segment_packets : 1,
+            lpc ? nullptr : state, lpc ? 0 : state_in, (uint8_t *)ws, out, packet_bytes, offsets, ctx->stream, lpc,
+            ctx->opt.fastMode != 0, true};
+}
+
+// The refusals of an encode call in their order; 0 when it may go ahead (num_packets = 0: after the option refusals).
+// num_segments: resolved (num_packets without a table and in LPC mode).  b: the call with the caller's device buffers, which
+// are checked too (nulls, alignment, workspace, output capacity); nullptr for the host forms, which allocate them themselves.
+static int32_t encode_refusal(alac_hip_ctx *ctx, const alac_hip_format *fmt, uint32_t np, uint32_t num_segments,
+                              const EncodeCall *b, uint64_t workspace_bytes, uint64_t out_capacity)
 {
     const bool mc = fmt->num_channels > 2, lpc = ctx->opt.lpc != 0;
     if (mc && lpc) return fail(ctx, ALAC_HIP_ParamError, "option lpc: mono and stereo streams only");
@@ -612,244 +586,41 @@ static int32_t encode_refusal(alac_hip_ctx *ctx, const alac_hip_format *fmt, con
         if (ctx->opt.fastMode) return fail(ctx, ALAC_HIP_ParamError, "options lpc and fast_mode exclude each other");
         if ((uint64_t)fmt->frame_size * fmt->num_channels * 4 > 65536)
             return fail(ctx, ALAC_HIP_ParamError, "option lpc: frame_size x channels above 16 384");
-        d_seg_first = nullptr;
     }
-    if (num_packets == 0) return ALAC_HIP_noErr;
-    if (!d_pcm || !d_workspace || !d_out || !d_packet_bytes || !d_packet_offsets)
-        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (!d_seg_first) num_segments = num_packets;
-    if (num_segments == 0 || num_segments > num_packets) return fail(ctx, ALAC_HIP_ParamError, "bad segment count");
+    if (np == 0) return ALAC_HIP_noErr;
+    if (b && (!b->pcm || !b->ws || !b->out || !b->packetBytes || !b->offsets)) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if (num_segments == 0 || num_segments > np) return fail(ctx, ALAC_HIP_ParamError, "bad segment count");
     if (mc) {
-        if (((uintptr_t)d_workspace & 255)) return fail(ctx, ALAC_HIP_ParamError, "misaligned workspace (256 B)");
-        if ((uint64_t)num_packets * kMaxChannels > 0x7fffffffull) return fail(ctx, ALAC_HIP_ParamError, "too many packets");
-        if (workspace_bytes < mc_layout(fmt, num_packets, num_segments).total)
+        if (b && ((uintptr_t)b->ws & 255)) return fail(ctx, ALAC_HIP_ParamError, "misaligned workspace (256 B)");
+        if ((uint64_t)np * kMaxChannels > 0x7fffffffull) return fail(ctx, ALAC_HIP_ParamError, "too many packets");
+        if (b && workspace_bytes < mc_layout(fmt, np, num_segments).total)
             return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
-    } else {
-        if (((uintptr_t)d_out & 3) || ((uintptr_t)d_workspace & 255) || ((uintptr_t)d_pcm & 15))
+    } else if (b) {
+        if (((uintptr_t)b->out & 3) || ((uintptr_t)b->ws & 255) || ((uintptr_t)b->pcm & 15))
             return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer (out 4 B, pcm 16 B, workspace 256 B)");
-        if (workspace_bytes < enc_layout(fmt, num_packets, num_segments).total + (lpc ? lpc_table_bytes(num_packets) : 0))
+        if (workspace_bytes < enc_layout(fmt, np, num_segments).total + (lpc ? lpc_table_bytes(np) : 0))
             return fail(ctx, ALAC_HIP_ParamError, lpc ? "workspace too small (option lpc: size it for num_segments = num_packets)"
                                                       : "workspace too small");
     }
-    if (out_capacity < max_output_bytes(fmt, num_packets))
+    if (b && out_capacity < max_output_bytes(fmt, np))
         return fail(ctx, ALAC_HIP_ParamError, "output capacity below alac_hip_encode_max_output_bytes");
     return ALAC_HIP_noErr;
 }
 
-// the longest segment of a device segment table, read back (a host wait); refuses a table that is not ascending inside
-// [0, num_packets]
-static int32_t read_max_segment(alac_hip_ctx *ctx, const uint32_t *d_seg_first, uint32_t num_segments, uint32_t num_packets,
-                                uint32_t &maxSeg)
+// the longest segment of a device segment table, read back (a host wait on `st`); refuses a table that is not ascending
+// inside [0, num_packets]
+static int32_t read_max_segment(alac_hip_ctx *ctx, hipStream_t st, const uint32_t *d_seg_first, uint32_t num_segments,
+                                uint32_t num_packets, uint32_t &maxSeg)
 {
     std::vector<uint32_t> sf(num_segments + 1);
-    if (hipMemcpyAsync(sf.data(), d_seg_first, (num_segments + 1) * 4ull, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess)
+    if (hipMemcpyAsync(sf.data(), d_seg_first, (num_segments + 1) * 4ull, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
         return fail(ctx, ALAC_HIP_ParamError, "reading d_seg_first");
     maxSeg = 0;
     for (uint32_t s = 0; s < num_segments; s++) {
         if (sf[s + 1] < sf[s] || sf[s + 1] > num_packets) return fail(ctx, ALAC_HIP_ParamError, "bad d_seg_first");
         maxSeg = sf[s + 1] - sf[s] > maxSeg ? sf[s + 1] - sf[s] : maxSeg;
     }
-    return ALAC_HIP_noErr;
-}
-
-static int32_t encode_elements(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm,
-                               const uint32_t *d_num_samples, uint32_t num_packets, const uint32_t *d_seg_first,
-                               uint32_t num_segments, int16_t *d_state, int32_t state_in, void *d_workspace,
-                               uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
-                               uint32_t *d_packet_bytes, uint64_t *d_packet_offsets, uint32_t maxSegHint);
-
-// one mono / stereo batch; `timed` = this call may consume a slot of the armed stage timing
-static int32_t encode_core(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm,
-                           const uint32_t *d_num_samples, uint32_t num_packets, const uint32_t *d_seg_first,
-                           uint32_t num_segments, int16_t *d_state, int32_t state_in, void *d_workspace,
-                           uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
-                           uint32_t *d_packet_bytes, uint64_t *d_packet_offsets, bool timed, uint32_t maxSegHint);
-
-int32_t alac_hip_encode_segmented(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm,
-                                  const uint32_t *d_num_samples, uint32_t num_packets, const uint32_t *d_seg_first,
-                                  uint32_t num_segments, uint32_t max_segment_packets, int16_t *d_state, int32_t state_in,
-                                  void *d_workspace, uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
-                                  uint32_t *d_packet_bytes, uint64_t *d_packet_offsets)
-{
-    if (!ctx) return ALAC_HIP_ParamError;
-    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
-    if (fmt->num_channels > 2)
-        return encode_elements(ctx, fmt, d_pcm, d_num_samples, num_packets, d_seg_first, num_segments, d_state, state_in,
-                               d_workspace, workspace_bytes, d_out, out_capacity, d_packet_bytes, d_packet_offsets,
-                               max_segment_packets);
-    return encode_core(ctx, fmt, d_pcm, d_num_samples, num_packets, d_seg_first, num_segments, d_state, state_in,
-                       d_workspace, workspace_bytes, d_out, out_capacity, d_packet_bytes, d_packet_offsets, true,
-                       max_segment_packets);
-}
-
-int32_t alac_hip_encode(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm,
-                        const uint32_t *d_num_samples, uint32_t num_packets, const uint32_t *d_seg_first,
-                        uint32_t num_segments, int16_t *d_state, int32_t state_in, void *d_workspace,
-                        uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
-                        uint32_t *d_packet_bytes, uint64_t *d_packet_offsets)
-{
-    return alac_hip_encode_segmented(ctx, fmt, d_pcm, d_num_samples, num_packets, d_seg_first, num_segments, 0, d_state, state_in,
-                                     d_workspace, workspace_bytes, d_out, out_capacity, d_packet_bytes, d_packet_offsets);
-}
-
-// ---- float32 input: quantize into a stage at the end of the workspace, then alac_hip_encode_segmented on it -------------
-// the staged integer PCM of a batch (+ 64: slack behind the last packet, like the gathered copies of a > 2-channel batch)
-static uint64_t float_stage_bytes(const alac_hip_format *fmt, uint32_t num_packets)
-{
-    return align_up((uint64_t)num_packets * fmt->frame_size * fmt->num_channels * bytes_per_sample(fmt->bit_depth) + 64, 256);
-}
-
-uint64_t alac_hip_encode_float_workspace_bytes(const alac_hip_format *fmt, uint32_t num_packets, uint32_t num_segments)
-{
-    if (!format_ok(fmt)) return 0;
-    return align_up(alac_hip_encode_workspace_bytes(fmt, num_packets, num_segments), 256) + float_stage_bytes(fmt, num_packets);
-}
-
-int32_t alac_hip_encode_float(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *d_in, uint64_t channel_stride,
-                              uint64_t frame_stride, const uint32_t *d_num_samples, uint32_t num_packets,
-                              const uint32_t *d_seg_first, uint32_t num_segments, uint32_t max_segment_packets,
-                              int16_t *d_state, int32_t state_in, void *d_workspace, uint64_t workspace_bytes, uint8_t *d_out,
-                              uint64_t out_capacity, uint32_t *d_packet_bytes, uint64_t *d_packet_offsets,
-                              uint32_t *d_clipped)
-{
-    if (!ctx) return ALAC_HIP_ParamError;
-    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
-    if (num_packets == 0)
-        return encode_refusal(ctx, fmt, nullptr, 0, d_seg_first, num_segments, d_workspace, workspace_bytes, d_out,
-                              out_capacity, d_packet_bytes, d_packet_offsets);
-    const uint32_t C = fmt->num_channels;
-    if (!d_in) return fail(ctx, ALAC_HIP_ParamError, "null d_in");
-    if ((uintptr_t)d_in & 3) return fail(ctx, ALAC_HIP_ParamError, "misaligned d_in (4 B)");
-    if (frame_stride == 0) return fail(ctx, ALAC_HIP_ParamError, "frame_stride 0");
-    if (channel_stride == 0 && C > 1) return fail(ctx, ALAC_HIP_ParamError, "channel_stride 0 with more than one channel");
-    // the largest index the conversion can form, and its byte offset: (C - 1) * channel_stride + (frames - 1) * frame_stride
-    uint64_t rows, cols, last;
-    if (__builtin_mul_overflow((uint64_t)(C - 1), channel_stride, &rows) ||
-        __builtin_mul_overflow((uint64_t)num_packets * fmt->frame_size - 1, frame_stride, &cols) ||
-        __builtin_add_overflow(rows, cols, &last) || last > UINT64_MAX / sizeof(float))
-        return fail(ctx, ALAC_HIP_ParamError, "the largest index into d_in overflows 64 bits");
-    // the stage: the last whole 256-byte blocks of the workspace; the encoder gets everything in front of it
-    const uint64_t stage = float_stage_bytes(fmt, num_packets);
-    if (workspace_bytes < stage) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
-    const uint64_t encBytes = (workspace_bytes - stage) & ~255ull;
-    uint8_t *pcm = d_workspace ? (uint8_t *)d_workspace + encBytes : nullptr;
-    if (int32_t rc = encode_refusal(ctx, fmt, pcm, num_packets, d_seg_first, num_segments, d_workspace, encBytes, d_out,
-                                    out_capacity, d_packet_bytes, d_packet_offsets))
-        return rc;
-    // the encoder's own read-back of a segment table without a bound (tap-parallel path) may refuse it: run that check before
-    // anything is enqueued (the encoder reads the table again)
-    if (d_seg_first && !max_segment_packets && C <= 2 && !ctx->opt.lpc && !use_lane_encoder(ctx)) {
-        uint32_t maxSeg = 0;
-        if (int32_t rc = read_max_segment(ctx, d_seg_first, num_segments, num_packets, maxSeg)) return rc;
-    }
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
-    FloatInArgs a;
-    a.in = d_in;
-    a.channelStride = channel_stride;
-    a.frameStride = frame_stride;
-    a.numSamples = d_num_samples;
-    a.numPackets = num_packets;
-    a.frameSize = fmt->frame_size;
-    a.channels = C;
-    a.pcm = pcm;
-    a.clipped = d_clipped;
-    const hipError_t e = launch_float_to_pcm(fmt->bit_depth, a, ctx->stream);
-    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "float conversion launch", e);
-    return alac_hip_encode_segmented(ctx, fmt, pcm, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets,
-                                     d_state, state_in, d_workspace, encBytes, d_out, out_capacity, d_packet_bytes,
-                                     d_packet_offsets);
-}
-
-static int32_t encode_elements(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm,
-                               const uint32_t *d_num_samples, uint32_t num_packets, const uint32_t *d_seg_first,
-                               uint32_t num_segments, int16_t *d_state, int32_t state_in, void *d_workspace,
-                               uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
-                               uint32_t *d_packet_bytes, uint64_t *d_packet_offsets, uint32_t maxSegHint)
-{
-    if (int32_t rc = encode_refusal(ctx, fmt, d_pcm, num_packets, d_seg_first, num_segments, d_workspace, workspace_bytes,
-                                    d_out, out_capacity, d_packet_bytes, d_packet_offsets))
-        return rc;
-    if (num_packets == 0) return ALAC_HIP_noErr;
-    if (!d_seg_first) num_segments = num_packets;
-    const McLayout M = mc_layout(fmt, num_packets, num_segments);
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
-    uint8_t *ws = (uint8_t *)d_workspace;
-    const uint32_t bps = bytes_per_sample(fmt->bit_depth);
-    hipStream_t mainStream = ctx->stream;
-
-    // the stereo batch runs on the context's stream, the mono batch beside it on a second stream (both are bound by
-    // the latency of one wave, not by the machine)
-    const bool both = M.g[0].count && M.g[1].count;
-    bool side = both;
-    if (side && !ensure_second_stream(ctx)) return fail(ctx, ALAC_HIP_MemFullError, "creating the second stream");
-    if (side) {
-        (void)hipEventRecord(ctx->mcFork, mainStream);
-        (void)hipStreamWaitEvent(ctx->mcStream, ctx->mcFork, 0);
-    }
-    int32_t rc = ALAC_HIP_noErr;
-    hipError_t copyErr = hipSuccess;
-    // SetFastMode is consulted for 2-channel STREAMS only (codec/ALACEncoder.cu:998-1001): the stereo elements of a
-    // > 2-channel stream are searched like everything else
-    const int32_t fastModeOfCtx = ctx->opt.fastMode;
-    ctx->opt.fastMode = 0;
-    struct Restore {
-        alac_hip_ctx *c;
-        int32_t v;
-        ~Restore() { c->opt.fastMode = v; }
-    } restoreFast{ctx, fastModeOfCtx};
-    for (int gi = 0; gi < 2 && rc == ALAC_HIP_noErr; gi++) {
-        const McGroup &G = M.g[gi];
-        if (!G.count) continue;
-        hipStream_t st = (side && gi == 1) ? ctx->mcStream : mainStream;
-        const alac_hip_format gf = element_format(fmt, G.channels);
-        const uint64_t elemPcm = (uint64_t)num_packets * fmt->frame_size * G.channels * bps;
-        for (uint32_t k = 0; k < G.count; k++)
-            launch_mc_gather((const uint8_t *)d_pcm, ws + G.gather + k * elemPcm, d_num_samples, num_packets, fmt->frame_size,
-                             fmt->num_channels, M.el[G.elem[k]].first, G.channels, bps, st);
-        uint32_t *ns = d_num_samples ? (uint32_t *)(ws + G.ns) : nullptr;
-        uint32_t *seg = d_seg_first ? (uint32_t *)(ws + G.seg) : nullptr;
-        launch_mc_tables(d_num_samples, num_packets, d_seg_first, num_segments, G.count, ns, seg, st);
-        // coefficient rows: the caller's [element][segment][64] <-> the batch's [k][segment][64]
-        int16_t *gstate = d_state ? (int16_t *)(ws + G.state) : nullptr;
-        const uint64_t rowBytes = (uint64_t)num_segments * ALAC_HIP_STATE_INT16 * 2;
-        if (gstate && state_in)
-            for (uint32_t k = 0; k < G.count && copyErr == hipSuccess; k++)
-                copyErr = hipMemcpyAsync((uint8_t *)gstate + k * rowBytes, (const uint8_t *)d_state + G.elem[k] * rowBytes,
-                                         rowBytes, hipMemcpyDeviceToDevice, st);
-        ctx->stream = st;
-        rc = encode_core(ctx, &gf, ws + G.gather, ns, G.count * num_packets, seg, G.count * num_segments, gstate, state_in,
-                         ws + G.sub, G.subBytes, ws + G.out, G.outCap, (uint32_t *)(ws + G.sizes), (uint64_t *)(ws + G.offs),
-                         false, maxSegHint);
-        ctx->stream = mainStream;
-        if (gstate && rc == ALAC_HIP_noErr)
-            for (uint32_t k = 0; k < G.count && copyErr == hipSuccess; k++)
-                copyErr = hipMemcpyAsync((uint8_t *)d_state + G.elem[k] * rowBytes, (const uint8_t *)gstate + k * rowBytes,
-                                         rowBytes, hipMemcpyDeviceToDevice, st);
-    }
-    if (side) {
-        (void)hipEventRecord(ctx->mcJoin, ctx->mcStream);
-        (void)hipStreamWaitEvent(mainStream, ctx->mcJoin, 0);
-    }
-    // (the second stream is joined above whatever happened, so the context's stream stays the only one to wait on)
-    if (rc != ALAC_HIP_noErr) return rc;
-    if (copyErr != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "coefficient state copy", copyErr);
-    McSpliceArgs sa;
-    sa.numElements = M.numElements;
-    sa.numPackets = num_packets;
-    for (uint32_t e = 0; e < M.numElements; e++) {
-        const McGroup &G = M.g[M.groupOf[e]];
-        sa.el[e] = M.el[e];
-        sa.src[e] = ws + G.out;
-        sa.srcOffsets[e] = (const uint64_t *)(ws + G.offs) + (uint64_t)M.indexInGroup[e] * num_packets;
-    }
-    sa.elemBits = (uint32_t *)(ws + M.elemBits);
-    sa.packetBytes = d_packet_bytes;
-    sa.offsets = d_packet_offsets;
-    sa.out = d_out;
-    launch_mc_splice(sa, mainStream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "splice launch", e);
     return ALAC_HIP_noErr;
 }
 
@@ -896,71 +667,54 @@ static V1Args v1_args(const alac_hip_ctx *ctx, const EncodeArgs &ea, const EncLa
     return A;
 }
 
-static int32_t encode_core(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm,
-                           const uint32_t *d_num_samples, uint32_t num_packets, const uint32_t *d_seg_first,
-                           uint32_t num_segments, int16_t *d_state, int32_t state_in, void *d_workspace,
-                           uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
-                           uint32_t *d_packet_bytes, uint64_t *d_packet_offsets, bool timed, uint32_t maxSegHint)
+// one mono / stereo batch
+static int32_t encode_core(alac_hip_ctx *ctx, const EncodeCall &c)
 {
-    // LPC mode: every packet is its own segment, whatever table the caller passes; the coefficient state is neither read
-    // nor written
-    if (int32_t rc = encode_refusal(ctx, fmt, d_pcm, num_packets, d_seg_first, num_segments, d_workspace, workspace_bytes,
-                                    d_out, out_capacity, d_packet_bytes, d_packet_offsets))
-        return rc;
-    const bool lpc = ctx->opt.lpc != 0;
-    if (lpc) {
-        d_seg_first = nullptr;
-        d_state = nullptr;
-        state_in = 0;
-        maxSegHint = 0;
-    }
-    if (num_packets == 0) return ALAC_HIP_noErr;
-    if (!d_seg_first) num_segments = num_packets;
-    const EncLayout L = enc_layout(fmt, num_packets, num_segments);
-
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
-    uint8_t *ws = (uint8_t *)d_workspace;
+    const alac_hip_format *fmt = &c.fmt;
+    const uint32_t num_packets = c.numPackets;
+    const EncLayout L = enc_layout(fmt, num_packets, c.numSegments);
+    uint8_t *ws = c.ws;
     EncodeArgs ea;
-    ea.pcm = (const uint8_t *)d_pcm;
-    ea.numSamples = d_num_samples;
-    ea.segFirst = d_seg_first;
-    ea.numSegments = num_segments;
+    ea.pcm = (const uint8_t *)c.pcm;
+    ea.numSamples = c.numSamples;
+    ea.segFirst = c.segFirst;
+    ea.numSegments = c.numSegments;
     ea.frameSize = fmt->frame_size;
-    ea.state = d_state;
-    ea.stateIn = state_in;
+    ea.state = c.state;
+    ea.stateIn = c.stateIn;
     ea.pred = (int32_t *)(ws + L.pred);
     ea.predStride = L.predStride;
     ea.bitWords = (uint32_t *)(ws + L.bitWords);
     ea.wcap = L.wcap;
     ea.recs = (PacketRec *)(ws + L.recs);
-    ea.packetBytes = d_packet_bytes;
-    // a table with the caller's bound (alac_hip_encode_segmented) is not read back: the kernels test every entry they use
-    const bool unread = d_seg_first && maxSegHint;
+    ea.packetBytes = c.packetBytes;
+    // a table with the caller's bound is not read back (no host wait): the kernels test every entry they use, and a table that
+    // contradicts the bound fails the next synchronize
+    const bool bound = c.segKind == SegKind::Bound;
     ea.numPackets = num_packets;
-    ea.segMax = unread ? (maxSegHint < num_packets ? maxSegHint : num_packets) : 0xffffffffu;
-    ea.segBad = unread ? (uint32_t *)(ws + L.segBad) : nullptr;
+    ea.segMax = bound ? (c.maxSeg < num_packets ? c.maxSeg : num_packets) : 0xffffffffu;
+    ea.segBad = bound ? (uint32_t *)(ws + L.segBad) : nullptr;
     PackArgs pa;
     pa.pcm = ea.pcm;
     pa.recs = ea.recs;
     pa.bitWords = ea.bitWords;
     pa.wcap = L.wcap;
     pa.frameSize = fmt->frame_size;
-    pa.offsets = d_packet_offsets;
-    pa.out = d_out;
+    pa.offsets = c.offsets;
+    pa.out = c.out;
     pa.segBad = ea.segBad;
     constexpr uint32_t EV = kEventBlocks * (kNumStages + 1);
     hipEvent_t *ev = nullptr;
-    if (timed && ctx->profile && (uint64_t)(ctx->profCalls + 1) * EV <= ctx->events.size())
+    if (c.timed && ctx->profile && (uint64_t)(ctx->profCalls + 1) * EV <= ctx->events.size())
         ev = &ctx->events[ctx->profCalls++ * EV];
     hipError_t e;
-    // the caller's bound on the segment length (alac_hip_encode_segmented) is checked on the device whatever kernels run
-    if (unread)
-        launch_check_segments(d_seg_first, num_segments, num_packets, ea.segMax, ctx->errDev ? ctx->errDev + 1 : nullptr,
-                              ea.segBad, ctx->stream);
+    // the caller's bound on the segment length is checked on the device whatever kernels run
+    if (bound)
+        launch_check_segments(c.segFirst, c.numSegments, num_packets, ea.segMax, ctx->errDev ? ctx->errDev + 1 : nullptr,
+                              ea.segBad, c.stream);
     if (ev) ctx->profLane.push_back(use_lane_encoder(ctx));
     if (use_lane_encoder(ctx)) {
-        e = launch_encode(fmt->bit_depth, fmt->num_channels, ea, pa, num_packets, ctx->stream,
-                          ev ? ev + (kNumStages + 1) : nullptr);
+        e = launch_encode(fmt->bit_depth, fmt->num_channels, ea, pa, num_packets, c.stream, ev ? ev + (kNumStages + 1) : nullptr);
     } else {
         if (!ctx->vsReady) {
             bool ok = hipEventCreateWithFlags(&ctx->vs.fork, hipEventDisableTiming) == hipSuccess &&
@@ -972,40 +726,218 @@ static int32_t encode_core(alac_hip_ctx *ctx, const alac_hip_format *fmt, const 
             ctx->vsReady = true;
         }
         // packets per segment: the pipeline runs once per packet position (a chained segment is serial)
-        uint32_t maxSeg = 1;
-        if (d_seg_first && maxSegHint) {
-            // the caller knows how long its longest segment is (alac_hip_encode_segmented): no read-back of the table, no
-            // host wait.  The bound is checked on the device; a table that contradicts it fails the next synchronize.
-            maxSeg = maxSegHint < num_packets ? maxSegHint : num_packets;
-        } else if (d_seg_first) {
-            if (int32_t rc = read_max_segment(ctx, d_seg_first, num_segments, num_packets, maxSeg)) return rc;
-        }
-        const V1Plan P = v1_plan(fmt->num_channels, num_segments, maxSeg, fmt->frame_size, ctx->opt);
-        const V1Args A = v1_args(ctx, ea, L, ws, P, d_state == nullptr);
+        uint32_t maxSeg = bound ? ea.segMax : c.maxSeg;
+        if (c.segKind == SegKind::Unread)
+            if (int32_t rc = read_max_segment(ctx, c.stream, c.segFirst, c.numSegments, num_packets, maxSeg)) return rc;
+        AlacOptions opt = ctx->opt;
+        opt.fastMode = c.fast ? 1 : 0;
+        const V1Plan P = v1_plan(fmt->num_channels, c.numSegments, maxSeg, fmt->frame_size, opt);
+        const V1Args A = v1_args(ctx, ea, L, ws, P, c.state == nullptr);
         // rows that hold no caller state and are not taken as constants (V1Args::virgin) get init_coefs first
-        const bool initState = !(d_state && state_in) && !A.virgin;
-        e = launch_encode_v1(fmt->bit_depth, fmt->num_channels, A, P, initState, pa, ctx->vs, num_packets, maxSeg, ctx->stream, ev);
+        const bool initState = !(c.state && c.stateIn) && !A.virgin;
+        e = launch_encode_v1(fmt->bit_depth, fmt->num_channels, A, P, initState, pa, ctx->vs, num_packets, maxSeg, c.stream, ev);
     }
     if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "encode launch", e);
-    if (lpc) {
+    if (c.lpc) {
         // Apple's independent packets are in the records and bit strings: the LPC candidates replace channels they beat,
         // then the sizes are scanned and the packets packed again, with the LPC headers
         LpcArgs la;
         la.pcm = ea.pcm;
         la.frameSize = fmt->frame_size;
         la.recs = ea.recs;
-        la.packetBytes = d_packet_bytes;
+        la.packetBytes = c.packetBytes;
         la.bitWords = ea.bitWords;
         la.wcap = L.wcap;
         la.lpc = (LpcChan *)(ws + L.total);
-        e = launch_lpc(fmt->bit_depth, fmt->num_channels, la, num_packets, ctx->stream);
+        e = launch_lpc(fmt->bit_depth, fmt->num_channels, la, num_packets, c.stream);
         if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "lpc launch", e);
         pa.lpc = la.lpc;
-        launch_scan_pack(fmt->bit_depth, fmt->num_channels, d_packet_bytes, pa, num_packets, ctx->stream, nullptr);
+        launch_scan_pack(fmt->bit_depth, fmt->num_channels, c.packetBytes, pa, num_packets, c.stream, nullptr);
         e = hipGetLastError();
         if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "lpc pack launch", e);
     }
     return ALAC_HIP_noErr;
+}
+
+// 3..8 channels: each element group (stereo, mono) as one batch of its own, then the splice
+static int32_t encode_elements(alac_hip_ctx *ctx, const EncodeCall &c)
+{
+    const alac_hip_format *fmt = &c.fmt;
+    const uint32_t num_packets = c.numPackets;
+    const McLayout M = mc_layout(fmt, num_packets, c.numSegments);
+    uint8_t *ws = c.ws;
+    const uint32_t bps = bytes_per_sample(fmt->bit_depth);
+
+    // the stereo batch runs on the call's stream, the mono batch beside it on a second stream (both are bound by the latency
+    // of one wave, not by the machine)
+    const bool side = M.g[0].count && M.g[1].count;
+    if (side && !ensure_second_stream(ctx)) return fail(ctx, ALAC_HIP_MemFullError, "creating the second stream");
+    hipError_t e;
+    if (side && ((e = hipEventRecord(ctx->mcFork, c.stream)) || (e = hipStreamWaitEvent(ctx->mcStream, ctx->mcFork, 0))))
+        return fail(ctx, ALAC_HIP_ParamError, "forking the second stream", e);
+    int32_t rc = ALAC_HIP_noErr;
+    hipError_t copyErr = hipSuccess;
+    for (int gi = 0; gi < 2 && rc == ALAC_HIP_noErr; gi++) {
+        const McGroup &G = M.g[gi];
+        if (!G.count) continue;
+        hipStream_t st = (side && gi == 1) ? ctx->mcStream : c.stream;
+        const uint64_t elemPcm = (uint64_t)num_packets * fmt->frame_size * G.channels * bps;
+        for (uint32_t k = 0; k < G.count; k++)
+            launch_mc_gather((const uint8_t *)c.pcm, ws + G.gather + k * elemPcm, c.numSamples, num_packets, fmt->frame_size,
+                             fmt->num_channels, M.el[G.elem[k]].first, G.channels, bps, st);
+        uint32_t *ns = c.numSamples ? (uint32_t *)(ws + G.ns) : nullptr;
+        uint32_t *seg = c.segFirst ? (uint32_t *)(ws + G.seg) : nullptr;
+        launch_mc_tables(c.numSamples, num_packets, c.segFirst, c.numSegments, G.count, ns, seg, st);
+        // coefficient rows: the caller's [element][segment][64] <-> the batch's [k][segment][64]
+        int16_t *gstate = c.state ? (int16_t *)(ws + G.state) : nullptr;
+        const uint64_t rowBytes = (uint64_t)c.numSegments * ALAC_HIP_STATE_INT16 * 2;
+        if (gstate && c.stateIn)
+            for (uint32_t k = 0; k < G.count && copyErr == hipSuccess; k++)
+                copyErr = hipMemcpyAsync((uint8_t *)gstate + k * rowBytes, (const uint8_t *)c.state + G.elem[k] * rowBytes,
+                                         rowBytes, hipMemcpyDeviceToDevice, st);
+        // the group's segment tables are built on the device: with no bound they are read back (SegKind::Unread).  SetFastMode
+        // is consulted for 2-channel STREAMS only (codec/ALACEncoder.cu:998-1001): the stereo elements of a > 2-channel
+        // stream are searched like everything else; no LPC (refused), no stage timing.
+        const EncodeCall g{element_format(fmt, G.channels), ws + G.gather, ns, G.count * num_packets, seg,
+                           G.count * c.numSegments, c.segKind, c.maxSeg, gstate, c.stateIn, ws + G.sub, ws + G.out,
+                           (uint32_t *)(ws + G.sizes), (uint64_t *)(ws + G.offs), st, false, false, false};
+        rc = encode_core(ctx, g);
+        if (gstate && rc == ALAC_HIP_noErr)
+            for (uint32_t k = 0; k < G.count && copyErr == hipSuccess; k++)
+                copyErr = hipMemcpyAsync((uint8_t *)c.state + G.elem[k] * rowBytes, (const uint8_t *)gstate + k * rowBytes,
+                                         rowBytes, hipMemcpyDeviceToDevice, st);
+    }
+    // the second stream is joined whatever happened, so the call's stream stays the only one to wait on
+    if (side && ((e = hipEventRecord(ctx->mcJoin, ctx->mcStream)) || (e = hipStreamWaitEvent(c.stream, ctx->mcJoin, 0))) &&
+        rc == ALAC_HIP_noErr)
+        rc = fail(ctx, ALAC_HIP_ParamError, "joining the second stream", e);
+    if (rc != ALAC_HIP_noErr) return rc;
+    if (copyErr != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "coefficient state copy", copyErr);
+    McSpliceArgs sa;
+    sa.numElements = M.numElements;
+    sa.numPackets = num_packets;
+    for (uint32_t el = 0; el < M.numElements; el++) {
+        const McGroup &G = M.g[M.groupOf[el]];
+        sa.el[el] = M.el[el];
+        sa.src[el] = ws + G.out;
+        sa.srcOffsets[el] = (const uint64_t *)(ws + G.offs) + (uint64_t)M.indexInGroup[el] * num_packets;
+    }
+    sa.elemBits = (uint32_t *)(ws + M.elemBits);
+    sa.packetBytes = c.packetBytes;
+    sa.offsets = c.offsets;
+    sa.out = c.out;
+    launch_mc_splice(sa, c.stream);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "splice launch", e);
+    return ALAC_HIP_noErr;
+}
+
+// alac_hip_encode and alac_hip_encode_segmented
+static int32_t encode_device(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm, const uint32_t *d_num_samples,
+                             uint32_t num_packets, const uint32_t *d_seg_first, uint32_t num_segments,
+                             uint32_t max_segment_packets, int16_t *d_state, int32_t state_in, void *d_workspace,
+                             uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity, uint32_t *d_packet_bytes,
+                             uint64_t *d_packet_offsets)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
+    const EncodeCall c = describe_encode(ctx, fmt, d_pcm, d_num_samples, num_packets, d_seg_first, num_segments,
+                                         max_segment_packets, d_state, state_in, d_workspace, d_out, d_packet_bytes,
+                                         d_packet_offsets);
+    if (int32_t rc = encode_refusal(ctx, fmt, num_packets, c.numSegments, &c, workspace_bytes, out_capacity)) return rc;
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    return (c.fmt.num_channels > 2 ? encode_elements : encode_core)(ctx, c);
+}
+
+int32_t alac_hip_encode_segmented(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm,
+                                  const uint32_t *d_num_samples, uint32_t num_packets, const uint32_t *d_seg_first,
+                                  uint32_t num_segments, uint32_t max_segment_packets, int16_t *d_state, int32_t state_in,
+                                  void *d_workspace, uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
+                                  uint32_t *d_packet_bytes, uint64_t *d_packet_offsets)
+{
+    return encode_device(ctx, fmt, d_pcm, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets, d_state,
+                         state_in, d_workspace, workspace_bytes, d_out, out_capacity, d_packet_bytes, d_packet_offsets);
+}
+
+int32_t alac_hip_encode(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm,
+                        const uint32_t *d_num_samples, uint32_t num_packets, const uint32_t *d_seg_first,
+                        uint32_t num_segments, int16_t *d_state, int32_t state_in, void *d_workspace,
+                        uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
+                        uint32_t *d_packet_bytes, uint64_t *d_packet_offsets)
+{
+    return encode_device(ctx, fmt, d_pcm, d_num_samples, num_packets, d_seg_first, num_segments, 0, d_state, state_in,
+                         d_workspace, workspace_bytes, d_out, out_capacity, d_packet_bytes, d_packet_offsets);
+}
+
+// ---- float32 input: quantize into a stage at the end of the workspace, then encode from it ---------------------------------
+// the staged integer PCM of a batch (+ 64: slack behind the last packet, like the gathered copies of a > 2-channel batch)
+static uint64_t float_stage_bytes(const alac_hip_format *fmt, uint32_t num_packets)
+{
+    return align_up((uint64_t)num_packets * fmt->frame_size * fmt->num_channels * bytes_per_sample(fmt->bit_depth) + 64, 256);
+}
+
+uint64_t alac_hip_encode_float_workspace_bytes(const alac_hip_format *fmt, uint32_t num_packets, uint32_t num_segments)
+{
+    if (!format_ok(fmt)) return 0;
+    return align_up(alac_hip_encode_workspace_bytes(fmt, num_packets, num_segments), 256) + float_stage_bytes(fmt, num_packets);
+}
+
+// the strides of a float call: the largest index the conversion can form, (C - 1) * channel_stride + (frames - 1) *
+// frame_stride, must fit 64 bits as a byte offset
+static int32_t float_stride_refusal(alac_hip_ctx *ctx, const alac_hip_format *fmt, uint32_t num_packets, uint64_t channel_stride,
+                                    uint64_t frame_stride)
+{
+    const uint32_t C = fmt->num_channels;
+    if (frame_stride == 0) return fail(ctx, ALAC_HIP_ParamError, "frame_stride 0");
+    if (channel_stride == 0 && C > 1) return fail(ctx, ALAC_HIP_ParamError, "channel_stride 0 with more than one channel");
+    uint64_t rows, cols, last;
+    if (__builtin_mul_overflow((uint64_t)(C - 1), channel_stride, &rows) ||
+        __builtin_mul_overflow((uint64_t)num_packets * fmt->frame_size - 1, frame_stride, &cols) ||
+        __builtin_add_overflow(rows, cols, &last) || last > UINT64_MAX / sizeof(float))
+        return fail(ctx, ALAC_HIP_ParamError, "the largest index into d_in overflows 64 bits");
+    return ALAC_HIP_noErr;
+}
+
+// the conversion into the stage c.pcm, then the encode from it
+static int32_t encode_float_run(alac_hip_ctx *ctx, const EncodeCall &c, const float *d_in, uint64_t channel_stride,
+                                uint64_t frame_stride, uint32_t *d_clipped)
+{
+    const FloatInArgs a{d_in,        channel_stride,     frame_stride,    c.numSamples, c.numPackets, c.fmt.frame_size,
+                        c.fmt.num_channels, (uint8_t *)c.pcm, d_clipped};
+    const hipError_t e = launch_float_to_pcm(c.fmt.bit_depth, a, c.stream);
+    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "float conversion launch", e);
+    return (c.fmt.num_channels > 2 ? encode_elements : encode_core)(ctx, c);
+}
+
+int32_t alac_hip_encode_float(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *d_in, uint64_t channel_stride,
+                              uint64_t frame_stride, const uint32_t *d_num_samples, uint32_t num_packets,
+                              const uint32_t *d_seg_first, uint32_t num_segments, uint32_t max_segment_packets,
+                              int16_t *d_state, int32_t state_in, void *d_workspace, uint64_t workspace_bytes, uint8_t *d_out,
+                              uint64_t out_capacity, uint32_t *d_packet_bytes, uint64_t *d_packet_offsets,
+                              uint32_t *d_clipped)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
+    EncodeCall c = describe_encode(ctx, fmt, nullptr, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets,
+                                   d_state, state_in, d_workspace, d_out, d_packet_bytes, d_packet_offsets);
+    if (num_packets == 0) return encode_refusal(ctx, fmt, 0, c.numSegments, &c, workspace_bytes, out_capacity);
+    if (!d_in) return fail(ctx, ALAC_HIP_ParamError, "null d_in");
+    if ((uintptr_t)d_in & 3) return fail(ctx, ALAC_HIP_ParamError, "misaligned d_in (4 B)");
+    if (int32_t rc = float_stride_refusal(ctx, fmt, num_packets, channel_stride, frame_stride)) return rc;
+    // the stage: the last whole 256-byte blocks of the workspace; the encoder gets everything in front of it
+    const uint64_t stage = float_stage_bytes(fmt, num_packets);
+    if (workspace_bytes < stage) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    const uint64_t encBytes = (workspace_bytes - stage) & ~255ull;
+    c.pcm = d_workspace ? (uint8_t *)d_workspace + encBytes : nullptr;
+    if (int32_t rc = encode_refusal(ctx, fmt, num_packets, c.numSegments, &c, encBytes, out_capacity)) return rc;
+    // tap-parallel path: a table without a bound is read back and checked before anything is enqueued, and handed on
+    if (c.segKind == SegKind::Unread && fmt->num_channels <= 2 && !use_lane_encoder(ctx)) {
+        if (int32_t rc = read_max_segment(ctx, c.stream, c.segFirst, c.numSegments, num_packets, c.maxSeg)) return rc;
+        c.segKind = SegKind::Host;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    return encode_float_run(ctx, c, d_in, channel_stride, frame_stride, d_clipped);
 }
 
 uint32_t alac_hip_num_stages(void) { return kNumStages; }
@@ -1122,21 +1054,12 @@ uint32_t alac_hip_magic_cookie_full(const alac_hip_format *fmt, uint32_t max_fra
 
 int32_t alac_hip_format_from_cookie(const uint8_t *ck, uint32_t size, alac_hip_format *out)
 {
-    if (!ck || !out) return ALAC_HIP_ParamError;
-    ck = cookie_config(ck, size);
-    if (size < 24) return ALAC_HIP_ParamError;
-    if (ck[4] > 0) return ALAC_HIP_ParamError;  // compatibleVersion <= kALACVersion (:153)
-    out->frame_size = ((uint32_t)ck[0] << 24) | ((uint32_t)ck[1] << 16) | ((uint32_t)ck[2] << 8) | ck[3];
-    out->bit_depth = ck[5];
-    out->num_channels = ck[9];
-    out->sample_rate = ((uint32_t)ck[20] << 24) | ((uint32_t)ck[21] << 16) | ((uint32_t)ck[22] << 8) | ck[23];
-    return ALAC_HIP_noErr;
+    return read_cookie(ck, size, out) ? ALAC_HIP_noErr : ALAC_HIP_ParamError;
 }
 
 uint64_t alac_hip_decode_workspace_bytes(const alac_hip_format *fmt, uint32_t num_packets)
 {
-    if (!format_ok(fmt)) return 0;
-    return dec_layout(fmt, num_packets).total;
+    return alac_hip_decode_workspace_bytes_stream(fmt, num_packets, 0);
 }
 
 uint64_t alac_hip_decode_workspace_bytes_stream(const alac_hip_format *fmt, uint32_t num_packets, uint64_t stream_bytes)
@@ -1148,64 +1071,60 @@ uint64_t alac_hip_decode_workspace_bytes_stream(const alac_hip_format *fmt, uint
 }  // extern "C"
 
 namespace {
-int32_t cookie_format(alac_hip_ctx *ctx, const uint8_t *cookie, uint32_t size, alac_hip_format &fmt)
-{
-    if (alac_hip_format_from_cookie(cookie, size, &fmt) != ALAC_HIP_noErr) return fail(ctx, ALAC_HIP_ParamError, "bad magic cookie");
-    if (!format_ok(&fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format in cookie");
-    return ALAC_HIP_noErr;
-}
-
-// alac_hip_decode (kPcmStore), alac_hip_verify's decode pass (kPcmVerify: d_pcm_out is the expected PCM, only read, and
-// verifyMismatch the first-mismatch words) and alac_hip_decode_float (kPcmFloat: d_pcm_out is planar float32, channel rows
-// channelStride floats apart)
-int32_t decode_impl(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
-                    const uint64_t *d_packet_offsets, uint32_t num_packets, void *d_workspace, uint64_t workspace_bytes,
-                    uint8_t *d_pcm_out, uint32_t *d_num_samples_out, int32_t *d_status, PcmMode mode,
-                    uint32_t *verifyMismatch = nullptr, uint64_t channelStride = 0)
+// a decode call's cookie, parsed once: the format, and into `da` the format's fields and the AG parameters (pb / mb / kb)
+int32_t parse_cookie(alac_hip_ctx *ctx, const uint8_t *cookie, uint32_t size, alac_hip_format &fmt, DecodeArgs &da)
 {
     if (!ctx) return ALAC_HIP_ParamError;
-    alac_hip_format fmt;
-    if (int32_t rc = cookie_format(ctx, h_cookie, cookie_size, fmt)) return rc;
-    if (num_packets == 0) return ALAC_HIP_noErr;
-    if (!d_stream || !d_packet_offsets || !d_workspace || !d_pcm_out || !d_num_samples_out || !d_status)
-        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (((uintptr_t)d_workspace & 255) || ((uintptr_t)d_pcm_out & 3))
-        return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
-    DecLayout L = dec_layout(&fmt, num_packets);
-    if (workspace_bytes < L.total) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
-    L.capWords = (workspace_bytes - L.words) / 4;  // all of it: packets that do not fit the staged words get status -50
-    uint32_t size = cookie_size;
-    const uint8_t *ck = cookie_config(h_cookie, size);  // pb / mb / kb
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
-    uint8_t *ws = (uint8_t *)d_workspace;
-    DecodeArgs da;
-    da.stream = d_stream;
-    da.offsets = d_packet_offsets;
-    da.numPackets = num_packets;
+    const uint8_t *ck = read_cookie(cookie, size, &fmt);
+    if (!ck) return fail(ctx, ALAC_HIP_ParamError, "bad magic cookie");
+    if (!format_ok(&fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format in cookie");
     da.frameSize = fmt.frame_size;
     da.bitDepth = fmt.bit_depth;
     da.numChannels = fmt.num_channels;
     da.pb = ck[6];
     da.mb = ck[7];
     da.kb = ck[8];
+    da.frameBytes = fmt.num_channels * bytes_per_sample(fmt.bit_depth);
+    return ALAC_HIP_noErr;
+}
+
+// the buffers of a decode call (the modes other than kPcmStore set DecodeArgs::pcmMode and their own word: kPcmVerify,
+// pcmOut the expected PCM, only read, and firstMismatch; kPcmFloat, pcmOut planar float32, and channelStride)
+void decode_buffers(DecodeArgs &da, const uint8_t *stream, const uint64_t *offsets, uint32_t num_packets, const void *pcm_out,
+                    uint32_t *num_samples_out, int32_t *status)
+{
+    da.stream = stream;
+    da.offsets = offsets;
+    da.numPackets = num_packets;
+    da.pcmOut = (uint8_t *)pcm_out;
+    da.numSamplesOut = num_samples_out;
+    da.statusOut = status;
+}
+
+// the decode pass of every decode-family call: `da` as parse_cookie and decode_buffers filled it
+int32_t decode_impl(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs da, void *d_workspace, uint64_t workspace_bytes)
+{
+    const uint32_t num_packets = da.numPackets;
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (!da.stream || !da.offsets || !d_workspace || !da.pcmOut || !da.numSamplesOut || !da.statusOut)
+        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if (((uintptr_t)d_workspace & 255) || ((uintptr_t)da.pcmOut & 3)) return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
+    DecLayout L = dec_layout(&fmt, num_packets);
+    if (workspace_bytes < L.total) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    L.capWords = (workspace_bytes - L.words) / 4;  // all of it: packets that do not fit the staged words get status -50
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
     // Local hardening, NOT reference behaviour (codec/ag_dec.c:282-286 only checks its pointers; ALACDecoder::Init takes any
     // pb / mb / kb): the kernels shift by kb (k = min(lg3a, kb), m = (1 << k) - 1), so kb outside 1..16 would be an undefined
     // or zero-width shift, and pb = 0 freezes the mean at values the quotient code does not expect.  No encoder writes either.
     if (da.kb < 1 || da.kb > 16 || da.pb == 0) return fail(ctx, ALAC_HIP_ParamError, "bad AG parameters in cookie (pb / kb)");
+    uint8_t *ws = (uint8_t *)d_workspace;
     da.maxElems = L.maxElems;
     da.recs = (DecRec *)(ws + L.recs);
     da.resid = (int32_t *)(ws + L.resid);
-    da.pcmOut = d_pcm_out;
-    da.numSamplesOut = d_num_samples_out;
-    da.statusOut = d_status;
     da.ho = handoff_ctl(ctx);
     da.optFused = ctx->opt.decFused;
     da.optPair = ctx->opt.decPair;
     da.optDirect = ctx->opt.decDirect;
-    da.pcmMode = mode;
-    if (mode == kPcmVerify) da.firstMismatch = verifyMismatch;
-    if (mode == kPcmFloat) da.channelStride = channelStride;
-    da.frameBytes = fmt.num_channels * bytes_per_sample(fmt.bit_depth);
     hipError_t e;
     if (use_lane_decoder(ctx)) {
         e = launch_decode(da, ctx->stream);
@@ -1236,6 +1155,88 @@ int32_t decode_impl(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_
     if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "decode launch", e);
     return ALAC_HIP_noErr;
 }
+
+// ---- verify: the decode pass with the PCM store sites comparing against the caller's PCM ----------------------------------
+// Workspace: the decoder's own (dec_layout) + the decoded frame counts; no PCM plane on any path — every kernel that writes
+// PCM in alac_hip_decode has an instantiation that compares there instead (alac_verify.hpp), the lane decoder's too.
+// The decoded frame counts sit in FRONT of the decoder's workspace: the decoder takes everything behind its own layout as
+// staging words, so a longer stream only needs a larger workspace here too.
+uint64_t verify_ns_bytes(uint32_t numPackets) { return align_up((uint64_t)numPackets * 4, 256); }
+
+// alac_hip_verify after its cookie: the decode pass of `da` in verify mode
+int32_t verify_impl(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs da, uint32_t *d_first_mismatch,
+                    const uint32_t *d_num_samples_expected, void *d_workspace, uint64_t workspace_bytes, uint32_t *d_bad_packets)
+{
+    const uint32_t num_packets = da.numPackets;
+    da.pcmMode = kPcmVerify;
+    da.firstMismatch = d_first_mismatch;
+    if (!d_bad_packets) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    if (num_packets == 0) {
+        const hipError_t e = hipMemsetAsync(d_bad_packets, 0, 4, ctx->stream);
+        return e == hipSuccess ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
+    }
+    if (!da.stream || !da.offsets || !d_workspace || !da.pcmOut || !da.firstMismatch || !da.statusOut)
+        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if (((uintptr_t)d_workspace & 255) || ((uintptr_t)da.pcmOut & 3)) return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
+    const DecLayout L = dec_layout(&fmt, num_packets);
+    const uint64_t nsBytes = verify_ns_bytes(num_packets);
+    if (workspace_bytes < nsBytes + L.total) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    uint8_t *ws = (uint8_t *)d_workspace;
+    da.numSamplesOut = (uint32_t *)ws;
+    hipError_t e = launch_verify_init(da.firstMismatch, num_packets, d_bad_packets, ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
+    if (int32_t rc = decode_impl(ctx, fmt, da, ws + nsBytes, workspace_bytes - nsBytes)) return rc;
+    e = launch_verify_finish(da.statusOut, da.numSamplesOut, d_num_samples_expected, fmt.frame_size, num_packets,
+                             da.firstMismatch, d_bad_packets, ctx->stream);
+    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
+    return ALAC_HIP_noErr;
+}
+
+// The host forms of the decode calls after their own checks (bad != nullptr: verify).  Staged: the stream, its workspace, the
+// PCM side (verify: h_expected; else zeroed), the frame counts (h_ns_expected, if given), the statuses.  Then the decode pass
+// (verify: verify_impl, bad packets into *bad), the copies back (decode: the PCM into `rows` rows of h_out, pitch bytes apart
+// or one block for pitch 0, the frame counts; verify: the first mismatches), the statuses, one wait and the hand-off check.
+int32_t decode_host_common(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs &da, const uint8_t *h_stream,
+                           const uint32_t *h_packet_bytes, uint32_t num_packets, uint64_t pcmBytes, const void *h_expected,
+                           const uint32_t *h_ns_expected, void *h_out, uint32_t rows, uint64_t pitch, uint32_t *h_ns_out,
+                           uint32_t *h_fm, uint32_t *bad, int32_t *h_status)
+{
+    const bool verify = bad != nullptr;
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    const uint64_t n4 = num_packets * 4ull;
+    hipStream_t st = ctx->stream;
+    DevStream d;
+    if (int32_t rc = upload_stream(h_stream, h_packet_bytes, num_packets, st, d, on_fail(ctx))) return rc;
+    const uint64_t wsBytes = (verify ? alac_hip_verify_workspace_bytes_stream : alac_hip_decode_workspace_bytes_stream)(
+        &fmt, num_packets, d.total);
+    DevBuf dWs, dPcm, dNs, dSt, dFm, dBad;
+    hipError_t e;
+    if ((e = dWs.alloc(wsBytes)) || (e = dPcm.alloc(pcmBytes)) || (e = dNs.alloc(n4)) || (e = dSt.alloc(n4)) ||
+        (verify && ((e = dFm.alloc(n4)) || (e = dBad.alloc(4)))))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if ((e = verify ? hipMemcpyAsync(dPcm.p, h_expected, pcmBytes, hipMemcpyHostToDevice, st)
+                    : hipMemsetAsync(dPcm.p, 0, pcmBytes, st)) ||
+        (h_ns_expected && (e = hipMemcpyAsync(dNs.p, h_ns_expected, n4, hipMemcpyHostToDevice, st))))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    decode_buffers(da, (const uint8_t *)d.bytes.p, (const uint64_t *)d.offs.p, num_packets, dPcm.p, (uint32_t *)dNs.p,
+                   (int32_t *)dSt.p);
+    if (verify) {
+        const uint32_t *ns = h_ns_expected ? (const uint32_t *)dNs.p : nullptr;
+        if (int32_t rc = verify_impl(ctx, fmt, da, (uint32_t *)dFm.p, ns, dWs.p, wsBytes, (uint32_t *)dBad.p)) return rc;
+        if (!(e = hipMemcpyAsync(bad, dBad.p, 4, hipMemcpyDeviceToHost, st)) && h_fm)
+            e = hipMemcpyAsync(h_fm, dFm.p, n4, hipMemcpyDeviceToHost, st);
+    } else {
+        if (int32_t rc = decode_impl(ctx, fmt, da, dWs.p, wsBytes)) return rc;
+        const uint64_t w = pcmBytes / rows;
+        if (!(e = pitch ? hipMemcpy2DAsync(h_out, pitch, dPcm.p, w, w, rows, hipMemcpyDeviceToHost, st)
+                        : hipMemcpyAsync(h_out, dPcm.p, pcmBytes, hipMemcpyDeviceToHost, st)))
+            e = hipMemcpyAsync(h_ns_out, dNs.p, n4, hipMemcpyDeviceToHost, st);
+    }
+    if (e || (h_status && (e = hipMemcpyAsync(h_status, dSt.p, n4, hipMemcpyDeviceToHost, st))) || (e = hipStreamSynchronize(st)))
+        return fail(ctx, ALAC_HIP_ParamError, verify ? "verify execution" : "decode execution", e);
+    return check_handoff(ctx);
+}
 }  // namespace
 
 extern "C" {
@@ -1245,8 +1246,11 @@ int32_t alac_hip_decode(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t coo
                         uint64_t workspace_bytes, uint8_t *d_pcm_out, uint32_t *d_num_samples_out,
                         int32_t *d_status)
 {
-    return decode_impl(ctx, h_cookie, cookie_size, d_stream, d_packet_offsets, num_packets, d_workspace, workspace_bytes,
-                       d_pcm_out, d_num_samples_out, d_status, kPcmStore);
+    alac_hip_format fmt;
+    DecodeArgs da;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
+    decode_buffers(da, d_stream, d_packet_offsets, num_packets, d_pcm_out, d_num_samples_out, d_status);
+    return decode_impl(ctx, fmt, da, d_workspace, workspace_bytes);
 }
 
 // ---- decode to planar float32: alac_hip_decode with the PCM store sites writing scaled floats ----------------------------
@@ -1255,9 +1259,9 @@ int32_t alac_hip_decode_float(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32
                               uint64_t workspace_bytes, float *d_out, uint64_t channel_stride, uint32_t *d_num_samples_out,
                               int32_t *d_status)
 {
-    if (!ctx) return ALAC_HIP_ParamError;
     alac_hip_format fmt;
-    if (int32_t rc = cookie_format(ctx, h_cookie, cookie_size, fmt)) return rc;
+    DecodeArgs da;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!d_out) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
     if ((uintptr_t)d_out & 3) return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
@@ -1265,16 +1269,11 @@ int32_t alac_hip_decode_float(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32
         return fail(ctx, ALAC_HIP_ParamError, "channel_stride below num_packets * frame_size");
     if (channel_stride > UINT64_MAX / sizeof(float) / fmt.num_channels)
         return fail(ctx, ALAC_HIP_ParamError, "channel_stride * channels overflows");
-    return decode_impl(ctx, h_cookie, cookie_size, d_stream, d_packet_offsets, num_packets, d_workspace, workspace_bytes,
-                       (uint8_t *)d_out, d_num_samples_out, d_status, kPcmFloat, nullptr, channel_stride);
+    decode_buffers(da, d_stream, d_packet_offsets, num_packets, d_out, d_num_samples_out, d_status);
+    da.pcmMode = kPcmFloat;
+    da.channelStride = channel_stride;
+    return decode_impl(ctx, fmt, da, d_workspace, workspace_bytes);
 }
-
-// ---- verify: alac_hip_decode with the PCM store sites comparing against the caller's PCM ------------------------------
-// Workspace: the decoder's own (dec_layout) + the decoded frame counts; no PCM plane on any path — every kernel that writes
-// PCM in alac_hip_decode has an instantiation that compares there instead (alac_verify.hpp), the lane decoder's too.
-// The decoded frame counts sit in FRONT of the decoder's workspace: the decoder takes everything behind its own layout as
-// staging words, so a longer stream only needs a larger workspace here too.
-static uint64_t verify_ns_bytes(uint32_t numPackets) { return align_up((uint64_t)numPackets * 4, 256); }
 
 uint64_t alac_hip_verify_workspace_bytes_stream(const alac_hip_format *fmt, uint32_t num_packets, uint64_t stream_bytes)
 {
@@ -1287,62 +1286,39 @@ int32_t alac_hip_verify(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t coo
                         const uint32_t *d_num_samples_expected, void *d_workspace, uint64_t workspace_bytes,
                         uint32_t *d_first_mismatch, int32_t *d_status, uint32_t *d_bad_packets)
 {
-    if (!ctx) return ALAC_HIP_ParamError;
     alac_hip_format fmt;
-    if (int32_t rc = cookie_format(ctx, h_cookie, cookie_size, fmt)) return rc;
-    if (!d_bad_packets) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
-    if (num_packets == 0) {
-        const hipError_t e = hipMemsetAsync(d_bad_packets, 0, 4, ctx->stream);
-        return e == hipSuccess ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
-    }
-    if (!d_stream || !d_packet_offsets || !d_workspace || !d_pcm_expected || !d_first_mismatch || !d_status)
-        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (((uintptr_t)d_workspace & 255) || ((uintptr_t)d_pcm_expected & 3))
-        return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
-    const DecLayout L = dec_layout(&fmt, num_packets);
-    const uint64_t nsBytes = verify_ns_bytes(num_packets);
-    if (workspace_bytes < nsBytes + L.total) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
-    uint8_t *ws = (uint8_t *)d_workspace;
-    uint32_t *ns = (uint32_t *)ws;
-    hipError_t e = launch_verify_init(d_first_mismatch, num_packets, d_bad_packets, ctx->stream);
-    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
-    const int32_t rc = decode_impl(ctx, h_cookie, cookie_size, d_stream, d_packet_offsets, num_packets, ws + nsBytes,
-                                   workspace_bytes - nsBytes, const_cast<uint8_t *>(d_pcm_expected), ns, d_status,
-                                   kPcmVerify, d_first_mismatch);
-    if (rc != ALAC_HIP_noErr) return rc;
-    e = launch_verify_finish(d_status, ns, d_num_samples_expected, fmt.frame_size, num_packets, d_first_mismatch, d_bad_packets,
-                             ctx->stream);
-    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
-    return ALAC_HIP_noErr;
+    DecodeArgs da;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
+    decode_buffers(da, d_stream, d_packet_offsets, num_packets, d_pcm_expected, nullptr, d_status);
+    return verify_impl(ctx, fmt, da, d_first_mismatch, d_num_samples_expected, d_workspace, workspace_bytes, d_bad_packets);
 }
 
 // ---- stage level ---------------------------------------------------------------------------------
+
+static int32_t pc_block_any(alac_hip_ctx *ctx, const int32_t *d_in, int32_t *d_out, uint32_t num_rows, uint32_t row_stride,
+                            int32_t num, int16_t *d_coefs, int32_t numactive, uint32_t chanbits, uint32_t denshift, bool decode)
+{
+    if (!ctx || !d_in || !d_out) return ALAC_HIP_ParamError;
+    if (numactive < 0 || numactive > 31 || chanbits < 1 || chanbits > 32 || denshift > 15 || num < 0)
+        return fail(ctx, ALAC_HIP_ParamError, decode ? "bad unpc_block parameters" : "bad pc_block parameters");
+    if (numactive != 0 && numactive != 31 && !d_coefs) return fail(ctx, ALAC_HIP_ParamError, "null coefs");
+    hipError_t e = launch_pc_block(d_in, d_out, num_rows, row_stride, num, d_coefs, numactive, chanbits, denshift, decode,
+                                   ctx->stream, decode || ctx->opt.stageTaps != 0);
+    return e == hipSuccess ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, decode ? "unpc_block launch" : "pc_block launch", e);
+}
 
 int32_t alac_hip_pc_block(alac_hip_ctx *ctx, const int32_t *d_in, int32_t *d_pc, uint32_t num_rows,
                           uint32_t row_stride, int32_t num, int16_t *d_coefs, int32_t numactive, uint32_t chanbits,
                           uint32_t denshift)
 {
-    if (!ctx || !d_in || !d_pc) return ALAC_HIP_ParamError;
-    if (numactive < 0 || numactive > 31 || chanbits < 1 || chanbits > 32 || denshift > 15 || num < 0)
-        return fail(ctx, ALAC_HIP_ParamError, "bad pc_block parameters");
-    if (numactive != 0 && numactive != 31 && !d_coefs) return fail(ctx, ALAC_HIP_ParamError, "null coefs");
-    hipError_t e = launch_pc_block(d_in, d_pc, num_rows, row_stride, num, d_coefs, numactive, chanbits, denshift,
-                                   false, ctx->stream, ctx->opt.stageTaps != 0);
-    return e == hipSuccess ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "pc_block launch", e);
+    return pc_block_any(ctx, d_in, d_pc, num_rows, row_stride, num, d_coefs, numactive, chanbits, denshift, false);
 }
 
 int32_t alac_hip_unpc_block(alac_hip_ctx *ctx, const int32_t *d_pc, int32_t *d_out, uint32_t num_rows,
                             uint32_t row_stride, int32_t num, int16_t *d_coefs, int32_t numactive,
                             uint32_t chanbits, uint32_t denshift)
 {
-    if (!ctx || !d_pc || !d_out) return ALAC_HIP_ParamError;
-    if (numactive < 0 || numactive > 31 || chanbits < 1 || chanbits > 32 || denshift > 15 || num < 0)
-        return fail(ctx, ALAC_HIP_ParamError, "bad unpc_block parameters");
-    if (numactive != 0 && numactive != 31 && !d_coefs) return fail(ctx, ALAC_HIP_ParamError, "null coefs");
-    hipError_t e = launch_pc_block(d_pc, d_out, num_rows, row_stride, num, d_coefs, numactive, chanbits, denshift,
-                                   true, ctx->stream);
-    return e == hipSuccess ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "unpc_block launch", e);
+    return pc_block_any(ctx, d_pc, d_out, num_rows, row_stride, num, d_coefs, numactive, chanbits, denshift, true);
 }
 
 int32_t alac_hip_dyn_comp(alac_hip_ctx *ctx, uint32_t mb0, uint32_t pb, uint32_t kb, const int32_t *d_pc,
@@ -1373,6 +1349,37 @@ int32_t alac_hip_dyn_decomp(alac_hip_ctx *ctx, uint32_t mb0, uint32_t pb, uint32
 
 // ---- host-buffer convenience ---------------------------------------------------------------------
 
+// alac_hip_encode_host_segments after the format check (alac_hip_encode_host lands here too)
+static int32_t encode_host_segments(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *h_pcm,
+                                    const uint32_t *h_num_samples, uint32_t num_packets, const uint32_t *h_seg_first,
+                                    uint32_t num_segments, int16_t *h_state, int32_t state_in, uint8_t *h_out,
+                                    uint64_t out_capacity, uint32_t *h_packet_bytes, uint64_t *out_total_bytes)
+{
+    if (out_total_bytes) *out_total_bytes = 0;
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (!h_pcm || !h_out || !h_packet_bytes || !h_num_samples || !h_seg_first || num_segments == 0)
+        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if (int32_t rc = host_segment_refusal(ctx, h_seg_first, num_segments, num_packets)) return rc;
+    if (int32_t rc = encode_refusal(ctx, fmt, num_packets, ctx->opt.lpc ? num_packets : num_segments, nullptr, 0, 0)) return rc;
+    const uint32_t np = num_packets, nseg = num_segments;
+    const uint64_t pcmBytes = (uint64_t)np * fmt->frame_size * fmt->num_channels * bytes_per_sample(fmt->bit_depth);
+    const uint64_t wsBytes = alac_hip_encode_workspace_bytes(fmt, np, ctx->opt.lpc ? np : nseg);
+    DevBuf dPcm;
+    hipError_t e;
+    if ((e = dPcm.alloc(pcmBytes))) return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if ((e = hipMemcpyAsync(dPcm.p, h_pcm, pcmBytes, hipMemcpyHostToDevice, ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    return encode_host_common(
+        ctx->stream, fmt, h_num_samples, np, h_seg_first, nseg, h_state, state_in, h_out, out_capacity, h_packet_bytes,
+        out_total_bytes, wsBytes,
+        [&](uint32_t maxSeg, const uint32_t *ns, const uint32_t *seg, int16_t *state, int32_t stIn, void *ws, uint8_t *out,
+            uint64_t, uint32_t *sizes, uint64_t *offs) {
+            const EncodeCall c = describe_encode(ctx, fmt, dPcm.p, ns, np, seg, nseg, maxSeg, state, stIn, ws, out, sizes, offs);
+            return (c.fmt.num_channels > 2 ? encode_elements : encode_core)(ctx, c);
+        },
+        on_fail(ctx), [ctx] { return alac_hip_synchronize(ctx); });
+}
+
 int32_t alac_hip_encode_host_segments(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *h_pcm,
                                       const uint32_t *h_num_samples, uint32_t num_packets, const uint32_t *h_seg_first,
                                       uint32_t num_segments, int16_t *h_state, int32_t state_in, uint8_t *h_out,
@@ -1380,28 +1387,8 @@ int32_t alac_hip_encode_host_segments(alac_hip_ctx *ctx, const alac_hip_format *
 {
     if (!ctx) return ALAC_HIP_ParamError;
     if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
-    if (out_total_bytes) *out_total_bytes = 0;
-    if (num_packets == 0) return ALAC_HIP_noErr;
-    if (!h_pcm || !h_out || !h_packet_bytes || !h_num_samples || !h_seg_first || num_segments == 0)
-        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (int32_t rc = host_segment_refusal(ctx, h_seg_first, num_segments, num_packets)) return rc;
-
-    const uint32_t bpf = fmt->num_channels * bytes_per_sample(fmt->bit_depth);
-    const uint32_t np = num_packets, nseg = num_segments;
-    const uint64_t pcmBytes = (uint64_t)np * fmt->frame_size * bpf;
-    const uint64_t wsBytes = alac_hip_encode_workspace_bytes(fmt, np, ctx->opt.lpc ? np : nseg);
-    DevBuf dPcm;
-    hipError_t e;
-    if ((e = dPcm.alloc(pcmBytes))) return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
-    if ((e = hipMemcpyAsync(dPcm.p, h_pcm, pcmBytes, hipMemcpyHostToDevice, ctx->stream)))
-        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    return encode_host_common(ctx, fmt, h_num_samples, np, h_seg_first, nseg, h_state, state_in, h_out, out_capacity,
-                              h_packet_bytes, out_total_bytes, wsBytes,
-                              [&](uint32_t maxSeg, const uint32_t *ns, const uint32_t *seg, int16_t *state, int32_t stIn,
-                                  void *ws, uint8_t *out, uint64_t outMax, uint32_t *sizes, uint64_t *offs) {
-                                  return alac_hip_encode_segmented(ctx, fmt, dPcm.p, ns, np, seg, nseg, maxSeg, state, stIn,
-                                                                   ws, wsBytes, out, outMax, sizes, offs);
-                              });
+    return encode_host_segments(ctx, fmt, h_pcm, h_num_samples, num_packets, h_seg_first, num_segments, h_state, state_in,
+                                h_out, out_capacity, h_packet_bytes, out_total_bytes);
 }
 
 int32_t alac_hip_encode_float_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *h_in, uint64_t channel_stride,
@@ -1419,7 +1406,7 @@ int32_t alac_hip_encode_float_host(alac_hip_ctx *ctx, const alac_hip_format *fmt
     if (int32_t rc = host_segment_refusal(ctx, h_seg_first, num_segments, num_packets)) return rc;
     const uint32_t np = num_packets, nseg = num_segments, fs = fmt->frame_size;
     // the floats the conversion reads lie in [0, span): up to the last frame a packet's num_samples covers.  The same
-    // strides then address the copy on the device (alac_hip_encode_float checks them).
+    // strides then address the copy on the device.
     uint64_t span = 0;
     for (uint32_t p = 0; p < np; p++) {
         const uint32_t n = h_num_samples[p] < fs ? h_num_samples[p] : fs;
@@ -1431,7 +1418,10 @@ int32_t alac_hip_encode_float_host(alac_hip_ctx *ctx, const alac_hip_format *fmt
             return fail(ctx, ALAC_HIP_ParamError, "the largest index into h_in overflows 64 bits");
         span = last + 1 > span ? last + 1 : span;
     }
+    if (int32_t rc = float_stride_refusal(ctx, fmt, np, channel_stride, frame_stride)) return rc;
+    if (int32_t rc = encode_refusal(ctx, fmt, np, ctx->opt.lpc ? np : nseg, nullptr, 0, 0)) return rc;
     const uint64_t wsBytes = alac_hip_encode_float_workspace_bytes(fmt, np, ctx->opt.lpc ? np : nseg);
+    const uint64_t encBytes = (wsBytes - float_stage_bytes(fmt, np)) & ~255ull;  // the stage behind, as alac_hip_encode_float
     DevBuf dIn, dClip;
     hipError_t e;
     if ((e = dIn.alloc(span * sizeof(float))) || (e = dClip.alloc(np * 4ull)))
@@ -1439,14 +1429,16 @@ int32_t alac_hip_encode_float_host(alac_hip_ctx *ctx, const alac_hip_format *fmt
     if ((e = hipMemcpyAsync(dIn.p, h_in, span * sizeof(float), hipMemcpyHostToDevice, ctx->stream)))
         return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
     int32_t rc = encode_host_common(
-        ctx, fmt, h_num_samples, np, h_seg_first, nseg, h_state, state_in, h_out, out_capacity, h_packet_bytes,
+        ctx->stream, fmt, h_num_samples, np, h_seg_first, nseg, h_state, state_in, h_out, out_capacity, h_packet_bytes,
         out_total_bytes, wsBytes,
         [&](uint32_t maxSeg, const uint32_t *ns, const uint32_t *seg, int16_t *state, int32_t stIn, void *ws, uint8_t *out,
-            uint64_t outMax, uint32_t *sizes, uint64_t *offs) {
-            return alac_hip_encode_float(ctx, fmt, (const float *)dIn.p, channel_stride, frame_stride, ns, np, seg, nseg, maxSeg,
-                                         state, stIn, ws, wsBytes, out, outMax, sizes, offs,
-                                         h_clipped ? (uint32_t *)dClip.p : nullptr);
-        });
+            uint64_t, uint32_t *sizes, uint64_t *offs) {
+            const EncodeCall c = describe_encode(ctx, fmt, (uint8_t *)ws + encBytes, ns, np, seg, nseg, maxSeg, state, stIn, ws,
+                                                 out, sizes, offs);
+            return encode_float_run(ctx, c, (const float *)dIn.p, channel_stride, frame_stride,
+                                    h_clipped ? (uint32_t *)dClip.p : nullptr);
+        },
+        on_fail(ctx), [ctx] { return alac_hip_synchronize(ctx); });
     if (rc != ALAC_HIP_noErr || !h_clipped) return rc;
     if ((e = hipMemcpyAsync(h_clipped, dClip.p, np * 4ull, hipMemcpyDeviceToHost, ctx->stream)) ||
         (e = hipStreamSynchronize(ctx->stream)))
@@ -1484,118 +1476,62 @@ int32_t alac_hip_encode_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, cons
         memcpy(padded.data(), h_pcm, inBytes);
         src = padded.data();
     }
-    return alac_hip_encode_host_segments(ctx, fmt, src, ns.data(), np, segFirst.data(), nseg, h_state, state_in, h_out,
-                                         out_capacity, h_packet_bytes, out_total_bytes);
+    return encode_host_segments(ctx, fmt, src, ns.data(), np, segFirst.data(), nseg, h_state, state_in, h_out, out_capacity,
+                                h_packet_bytes, out_total_bytes);
 }
 
 int32_t alac_hip_decode_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size,
                              const uint8_t *h_stream, const uint32_t *h_packet_bytes, uint32_t num_packets,
                              uint8_t *h_pcm_out, uint32_t *h_num_samples_out, int32_t *h_status)
 {
-    if (!ctx) return ALAC_HIP_ParamError;
     alac_hip_format fmt;
-    if (alac_hip_format_from_cookie(h_cookie, cookie_size, &fmt) != ALAC_HIP_noErr || !format_ok(&fmt))
-        return fail(ctx, ALAC_HIP_ParamError, "bad magic cookie");
+    DecodeArgs da;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!h_stream || !h_packet_bytes || !h_pcm_out || !h_num_samples_out || !h_status)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    DevStream d;
-    if (int32_t rc = upload_stream(ctx, fmt, h_stream, h_packet_bytes, num_packets, d)) return rc;
-    const uint64_t pcmBytes = d.pcmBytes;
-    const uint64_t wsBytes = alac_hip_decode_workspace_bytes_stream(&fmt, num_packets, d.total);
-    DevBuf dWs, dPcm, dNs, dSt;
-    hipError_t e;
-    if ((e = dWs.alloc(wsBytes)) || (e = dPcm.alloc(pcmBytes)) || (e = dNs.alloc(num_packets * 4ull)) ||
-        (e = dSt.alloc(num_packets * 4ull)))
-        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
-    hipStream_t st = ctx->stream;
-    if ((e = hipMemsetAsync(dPcm.p, 0, pcmBytes, st))) return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    int32_t rc = alac_hip_decode(ctx, h_cookie, cookie_size, (const uint8_t *)d.bytes.p, (const uint64_t *)d.offs.p,
-                                 num_packets, dWs.p, wsBytes, (uint8_t *)dPcm.p, (uint32_t *)dNs.p,
-                                 (int32_t *)dSt.p);
-    if (rc != ALAC_HIP_noErr) return rc;
-    if ((e = hipMemcpyAsync(h_pcm_out, dPcm.p, pcmBytes, hipMemcpyDeviceToHost, st)) ||
-        (e = hipMemcpyAsync(h_num_samples_out, dNs.p, num_packets * 4ull, hipMemcpyDeviceToHost, st)) ||
-        (e = hipMemcpyAsync(h_status, dSt.p, num_packets * 4ull, hipMemcpyDeviceToHost, st)) ||
-        (e = hipStreamSynchronize(st)))
-        return fail(ctx, ALAC_HIP_ParamError, "decode execution", e);
-    return check_handoff(ctx);
+    const uint64_t pcmBytes = (uint64_t)num_packets * fmt.frame_size * fmt.num_channels * bytes_per_sample(fmt.bit_depth);
+    return decode_host_common(ctx, fmt, da, h_stream, h_packet_bytes, num_packets, pcmBytes, nullptr, nullptr, h_pcm_out, 1, 0,
+                              h_num_samples_out, nullptr, nullptr, h_status);
 }
 
 int32_t alac_hip_decode_float_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size,
                                    const uint8_t *h_stream, const uint32_t *h_packet_bytes, uint32_t num_packets, float *h_out,
                                    uint64_t channel_stride, uint32_t *h_num_samples_out, int32_t *h_status)
 {
-    if (!ctx) return ALAC_HIP_ParamError;
     alac_hip_format fmt;
-    if (alac_hip_format_from_cookie(h_cookie, cookie_size, &fmt) != ALAC_HIP_noErr || !format_ok(&fmt))
-        return fail(ctx, ALAC_HIP_ParamError, "bad magic cookie");
+    DecodeArgs da;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!h_stream || !h_packet_bytes || !h_out || !h_num_samples_out || !h_status)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    const uint64_t row = (uint64_t)num_packets * fmt.frame_size;  // floats of one channel
-    if (channel_stride < row) return fail(ctx, ALAC_HIP_ParamError, "channel_stride below num_packets * frame_size");
+    if (channel_stride < (uint64_t)num_packets * fmt.frame_size)
+        return fail(ctx, ALAC_HIP_ParamError, "channel_stride below num_packets * frame_size");
     if (channel_stride > UINT64_MAX / sizeof(float) / fmt.num_channels)
         return fail(ctx, ALAC_HIP_ParamError, "channel_stride * channels overflows");
-    DevStream d;
-    if (int32_t rc = upload_stream(ctx, fmt, h_stream, h_packet_bytes, num_packets, d)) return rc;
     // on the device the rows lie back to back; the copy back puts them channel_stride floats apart and leaves the gap alone
-    const uint64_t outBytes = row * fmt.num_channels * sizeof(float);
-    const uint64_t wsBytes = alac_hip_decode_workspace_bytes_stream(&fmt, num_packets, d.total);
-    DevBuf dWs, dOut, dNs, dSt;
-    hipError_t e;
-    if ((e = dWs.alloc(wsBytes)) || (e = dOut.alloc(outBytes)) || (e = dNs.alloc(num_packets * 4ull)) ||
-        (e = dSt.alloc(num_packets * 4ull)))
-        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
-    hipStream_t st = ctx->stream;
-    if ((e = hipMemsetAsync(dOut.p, 0, outBytes, st))) return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    int32_t rc = alac_hip_decode_float(ctx, h_cookie, cookie_size, (const uint8_t *)d.bytes.p, (const uint64_t *)d.offs.p,
-                                       num_packets, dWs.p, wsBytes, (float *)dOut.p, row, (uint32_t *)dNs.p, (int32_t *)dSt.p);
-    if (rc != ALAC_HIP_noErr) return rc;
-    if ((e = hipMemcpy2DAsync(h_out, channel_stride * sizeof(float), dOut.p, row * sizeof(float), row * sizeof(float),
-                              fmt.num_channels, hipMemcpyDeviceToHost, st)) ||
-        (e = hipMemcpyAsync(h_num_samples_out, dNs.p, num_packets * 4ull, hipMemcpyDeviceToHost, st)) ||
-        (e = hipMemcpyAsync(h_status, dSt.p, num_packets * 4ull, hipMemcpyDeviceToHost, st)) ||
-        (e = hipStreamSynchronize(st)))
-        return fail(ctx, ALAC_HIP_ParamError, "decode execution", e);
-    return check_handoff(ctx);
+    const uint64_t row = (uint64_t)num_packets * fmt.frame_size;  // floats of one channel
+    da.pcmMode = kPcmFloat;
+    da.channelStride = row;
+    return decode_host_common(ctx, fmt, da, h_stream, h_packet_bytes, num_packets, row * fmt.num_channels * sizeof(float), nullptr,
+                              nullptr, h_out, fmt.num_channels, channel_stride * sizeof(float), h_num_samples_out, nullptr,
+                              nullptr, h_status);
 }
+
 int32_t alac_hip_verify_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *h_stream,
                              const uint32_t *h_packet_bytes, uint32_t num_packets, const uint8_t *h_pcm_expected,
                              const uint32_t *h_num_samples_expected, uint32_t *h_first_mismatch, int32_t *h_status)
 {
-    if (!ctx) return ALAC_HIP_ParamError;
     alac_hip_format fmt;
-    if (alac_hip_format_from_cookie(h_cookie, cookie_size, &fmt) != ALAC_HIP_noErr || !format_ok(&fmt))
-        return fail(ctx, ALAC_HIP_ParamError, "bad magic cookie");
+    DecodeArgs da;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
     if (num_packets == 0) return 0;
     if (!h_stream || !h_packet_bytes || !h_pcm_expected) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
     if (num_packets > 0x7fffffffu) return fail(ctx, ALAC_HIP_ParamError, "more packets than the return value counts");
-    DevStream d;
-    if (int32_t rc = upload_stream(ctx, fmt, h_stream, h_packet_bytes, num_packets, d)) return rc;
-    const uint64_t pcmBytes = d.pcmBytes;
-    const uint64_t wsBytes = alac_hip_verify_workspace_bytes_stream(&fmt, num_packets, d.total);
-    DevBuf dWs, dPcm, dNs, dFm, dSt, dBad;
-    hipError_t e;
-    if ((e = dWs.alloc(wsBytes)) || (e = dPcm.alloc(pcmBytes)) || (h_num_samples_expected && (e = dNs.alloc(num_packets * 4ull))) ||
-        (e = dFm.alloc(num_packets * 4ull)) || (e = dSt.alloc(num_packets * 4ull)) || (e = dBad.alloc(4)))
-        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
-    hipStream_t st = ctx->stream;
-    if ((e = hipMemcpyAsync(dPcm.p, h_pcm_expected, pcmBytes, hipMemcpyHostToDevice, st)) ||
-        (h_num_samples_expected &&
-         (e = hipMemcpyAsync(dNs.p, h_num_samples_expected, num_packets * 4ull, hipMemcpyHostToDevice, st))))
-        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    int32_t rc = alac_hip_verify(ctx, h_cookie, cookie_size, (const uint8_t *)d.bytes.p, (const uint64_t *)d.offs.p, num_packets,
-                                 (const uint8_t *)dPcm.p, (const uint32_t *)dNs.p, dWs.p, wsBytes, (uint32_t *)dFm.p,
-                                 (int32_t *)dSt.p, (uint32_t *)dBad.p);
-    if (rc != ALAC_HIP_noErr) return rc;
+    const uint64_t pcmBytes = (uint64_t)num_packets * fmt.frame_size * fmt.num_channels * bytes_per_sample(fmt.bit_depth);
     uint32_t bad = 0;
-    if ((e = hipMemcpyAsync(&bad, dBad.p, 4, hipMemcpyDeviceToHost, st)) ||
-        (h_first_mismatch && (e = hipMemcpyAsync(h_first_mismatch, dFm.p, num_packets * 4ull, hipMemcpyDeviceToHost, st))) ||
-        (h_status && (e = hipMemcpyAsync(h_status, dSt.p, num_packets * 4ull, hipMemcpyDeviceToHost, st))) ||
-        (e = hipStreamSynchronize(st)))
-        return fail(ctx, ALAC_HIP_ParamError, "verify execution", e);
-    rc = check_handoff(ctx);
+    const int32_t rc = decode_host_common(ctx, fmt, da, h_stream, h_packet_bytes, num_packets, pcmBytes, h_pcm_expected,
+                                          h_num_samples_expected, nullptr, 1, 0, nullptr, h_first_mismatch, &bad, h_status);
     return rc != ALAC_HIP_noErr ? rc : (int32_t)bad;
 }
 

@@ -136,6 +136,7 @@ struct AlacOptions {
 AlacOptions alac_options_from_env();
 struct AlacOptionKey {
     const char *name;
+    const char *env;  // the ALAC_HIP_* variable that supplies the default (nullptr: none)
     int32_t AlacOptions::*slot;
     int32_t lo, hi;  // accepted values
 };

@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "alac/matrixlib.h"
+#include "alac_host.hpp"
 
 namespace {
 
@@ -68,11 +69,11 @@ bool on_device(const void *p)
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
 
-struct Staged {  // device twin of a host buffer
+struct Staged {  // device twin of a host buffer (a device buffer is used in place)
+    alachost::DevBuf own;
     void *d = nullptr;
     void *h = nullptr;
     size_t bytes = 0;
-    bool own = false;
     bool ok = true;
     Staged(void *p, size_t n, bool dev, bool copyIn) : h(p), bytes(n)
     {
@@ -81,16 +82,12 @@ struct Staged {  // device twin of a host buffer
             d = p;
             return;
         }
-        own = true;
-        ok = hipMalloc(&d, n) == hipSuccess && (!copyIn || hipMemcpy(d, p, n, hipMemcpyHostToDevice) == hipSuccess);
+        ok = own.alloc(n) == hipSuccess && (!copyIn || hipMemcpy(own.p, p, n, hipMemcpyHostToDevice) == hipSuccess);
+        d = own.p;
     }
     void back() const
     {
-        if (own && ok && d) (void)hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost);
-    }
-    ~Staged()
-    {
-        if (own && d) (void)hipFree(d);
+        if (own.p && ok) (void)hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost);
     }
 };
 

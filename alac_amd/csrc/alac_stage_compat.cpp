@@ -2,7 +2,6 @@
 // (codec/dplib.h:49-55, codec/aglib.h:70-74) for third-party code that links them; the arithmetic runs on the
 // GPU through the batched stage-level entry points of alac_hip.h as a one-row batch.  Meant for drop-in linking
 // and spot checks, not for throughput: every call is a host -> device -> host round trip.
-#include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -11,6 +10,7 @@
 #include "alac/aglib.h"
 #include "alac/dplib.h"
 #include "alac_hip.h"
+#include "alac_host.hpp"
 
 namespace {
 
@@ -24,11 +24,7 @@ alac_hip_ctx *compat_ctx()
     return ctx;
 }
 
-struct Dev {
-    void *p = nullptr;
-    explicit Dev(size_t n) { if (hipMalloc(&p, n ? n : 4) != hipSuccess) p = nullptr; }
-    ~Dev() { if (p) (void)hipFree(p); }
-};
+using alachost::DevBuf;
 
 // one row through the batched predictor entry points
 void run_pc(bool decode, int32_t *src, int32_t *dst, int32_t num, int16_t *coefs, int32_t numactive, uint32_t chanbits,
@@ -38,8 +34,8 @@ void run_pc(bool decode, int32_t *src, int32_t *dst, int32_t num, int16_t *coefs
     if (!ctx || num <= 0) return;
     const int32_t na = numactive == 31 ? 1 : numactive;
     const uint32_t stride = (uint32_t)((num > na + 1 ? num : na + 1) + 8);
-    Dev dIn(stride * 4), dOut(stride * 4), dCo(32 * 2);
-    if (!dIn.p || !dOut.p || !dCo.p) return;
+    DevBuf dIn, dOut, dCo;
+    if (dIn.alloc(stride * 4) || dOut.alloc(stride * 4) || dCo.alloc(32 * 2)) return;
     int16_t co[32] = {0};
     const int ncopy = numactive > 0 && numactive <= 32 ? numactive : 0;
     memcpy(co, coefs, ncopy * 2);
@@ -115,8 +111,8 @@ int32_t dyn_comp(AGParamRecPtr params, int32_t *pc, BitBuffer *bitstream, int32_
     if (!ctx) return kALAC_ParamError;
     if (numSamples <= 0) return ALAC_noErr;
     const uint32_t cap = ((uint32_t)numSamples * (9u + (uint32_t)bitSize + 25u) + 7) / 8 + 16;
-    Dev dPc((size_t)numSamples * 4), dBits(cap), dNum(4);
-    if (!dPc.p || !dBits.p || !dNum.p) return kALAC_MemFullError;
+    DevBuf dPc, dBits, dNum;
+    if (dPc.alloc((size_t)numSamples * 4) || dBits.alloc(cap) || dNum.alloc(4)) return kALAC_MemFullError;
     (void)hipMemcpy(dPc.p, pc, (size_t)numSamples * 4, hipMemcpyHostToDevice);
     (void)hipMemset(dBits.p, 0, cap);
     int32_t rc = alac_hip_dyn_comp(ctx, params->mb0, params->pb, params->kb, (const int32_t *)dPc.p, 1, (uint32_t)numSamples,
@@ -164,8 +160,8 @@ int32_t dyn_decomp(AGParamRecPtr params, BitBuffer *bitstream, int32_t *pc, int3
         shifted[i] = (uint8_t)(two >> (8 - bi));
     }
     const uint32_t nbytes = (uint32_t)avail;
-    Dev dBits(nbytes + 16), dPc((size_t)numSamples * 4), dNum(4), dSt(4);
-    if (!dBits.p || !dPc.p || !dNum.p || !dSt.p) return kALAC_MemFullError;
+    DevBuf dBits, dPc, dNum, dSt;
+    if (dBits.alloc(nbytes + 16) || dPc.alloc((size_t)numSamples * 4) || dNum.alloc(4) || dSt.alloc(4)) return kALAC_MemFullError;
     (void)hipMemset(dBits.p, 0, nbytes + 16);
     (void)hipMemcpy(dBits.p, shifted.data(), nbytes, hipMemcpyHostToDevice);
     int32_t rc = alac_hip_dyn_decomp(ctx, params->mb0, params->pb, params->kb, (const uint8_t *)dBits.p, nbytes + 16, 1,

@@ -56,3 +56,58 @@ def test_decode_reports_a_lost_handoff(gpu_ctx, oracle):
     out, ns, st, _ = gpu_ctx.decode(enc.cookie(), d_stream, offs, n)
     gpu_ctx.synchronize()
     assert int(st.abs().sum()) == 0 and np.array_equal(out.cpu().numpy(), pcm)
+
+
+HOST_FORMS = ["encode_host", "encode_host_segments", "encode_float_host", "decode_host", "decode_float_host", "verify_host"]
+
+
+@pytest.mark.parametrize("form", HOST_FORMS)
+def test_host_forms_report_a_lost_handoff(gpu_ctx, oracle, form):
+    """Every host-buffer entry point returns kALAC_MemFullError for a lost hand-off, and the next call on the same context
+    is bit-exact."""
+    import ctypes as C
+    lib, h = gpu_ctx.lib, gpu_ctx.h
+    fmt = alac_amd.make_format(4096, 16, 2)
+    n = 192
+    pcm = alac_amd.synth_pcm(0, n, fmt)
+    enc = oracle.encoder(4096, 16, 2)
+    ref, ref_sizes = enc.encode_stream(pcm, n * 4096, segment_packets=1)
+    cookie = enc.cookie()
+    ns = np.full(n, 4096, np.uint32)
+    seg = np.arange(n + 1, dtype=np.uint32)  # every packet its own segment, as segment_packets = 1
+    x = (pcm.view(np.int16).astype(np.float64) / 32768).astype(np.float32)  # interleaved, on the 16-bit grid
+    cap = int(lib.alac_hip_encode_max_output_bytes(C.byref(fmt), n))
+
+    def call():
+        if form.startswith("encode"):
+            out, sizes, total = np.zeros(cap, np.uint8), np.zeros(n, np.uint32), C.c_uint64(0)
+            if form == "encode_host":
+                rc = lib.alac_hip_encode_host(h, C.byref(fmt), pcm.ctypes.data, n * 4096, 1, None, 0, out.ctypes.data, cap,
+                                              sizes.ctypes.data, C.byref(total))
+            elif form == "encode_host_segments":
+                rc = lib.alac_hip_encode_host_segments(h, C.byref(fmt), pcm.ctypes.data, ns.ctypes.data, n, seg.ctypes.data, n,
+                                                       None, 0, out.ctypes.data, cap, sizes.ctypes.data, C.byref(total))
+            else:
+                rc = lib.alac_hip_encode_float_host(h, C.byref(fmt), x.ctypes.data, 1, 2, ns.ctypes.data, n, seg.ctypes.data, n,
+                                                    None, 0, out.ctypes.data, cap, sizes.ctypes.data, C.byref(total), None)
+            return rc, np.array_equal(sizes, ref_sizes) and np.array_equal(out[:total.value], ref)
+        got_ns, st = np.zeros(n, np.uint32), np.zeros(n, np.int32)
+        if form == "decode_host":
+            out = np.zeros(pcm.size, np.uint8)
+            rc = lib.alac_hip_decode_host(h, cookie.ctypes.data, cookie.size, ref.ctypes.data, ref_sizes.ctypes.data, n,
+                                          out.ctypes.data, got_ns.ctypes.data, st.ctypes.data)
+            return rc, np.array_equal(out, pcm) and (got_ns == 4096).all() and not st.any()
+        if form == "decode_float_host":
+            out = np.zeros((2, n * 4096), np.float32)
+            rc = lib.alac_hip_decode_float_host(h, cookie.ctypes.data, cookie.size, ref.ctypes.data, ref_sizes.ctypes.data, n,
+                                                out.ctypes.data, n * 4096, got_ns.ctypes.data, st.ctypes.data)
+            return rc, np.array_equal(out.T, x.reshape(-1, 2)) and (got_ns == 4096).all() and not st.any()
+        fm = np.zeros(n, np.uint32)
+        rc = lib.alac_hip_verify_host(h, cookie.ctypes.data, cookie.size, ref.ctypes.data, ref_sizes.ctypes.data, n,
+                                      pcm.ctypes.data, None, fm.ctypes.data, st.ctypes.data)
+        return rc, (fm == 0xFFFFFFFF).all() and not st.any()
+
+    with gpu_ctx.options(debug_lose_handoff=1):
+        assert call()[0] == -108
+    rc, exact = call()
+    assert rc == 0 and exact

@@ -83,3 +83,14 @@ def test_regime_table(opts, want):
             fmt = alac_amd.make_format(4096, 16, ch, 44100)
             got = [ctx.regime(fmt, s) for s in REGIME_SEGMENTS]
             assert got == [names[c] for c in row], (opts, ch)
+
+
+def test_environment_supplies_in_range_defaults(monkeypatch):
+    """The ALAC_HIP_<KEY> variables are read through the option table: an integer inside the key's range is the new context's
+    default (ALAC_HIP_ENCODER=lane / ALAC_HIP_DECODER=lane spell 1), anything else leaves the built-in default."""
+    monkeypatch.setenv("ALAC_HIP_DEC_DIRECT", "2")
+    monkeypatch.setenv("ALAC_HIP_DEC_FUSED", "-1")
+    monkeypatch.setenv("ALAC_HIP_THRU", "7")
+    monkeypatch.setenv("ALAC_HIP_ENCODER", "lane")
+    ctx = alac_amd.Context(0)
+    assert [ctx.get_option(k) for k in ("dec_direct", "dec_fused", "thru", "encoder_lane")] == [2, -1, -1, 1]
