@@ -30,6 +30,14 @@ class Format(C.Structure):
         return self.frame_size * self.bytes_per_frame
 
 
+DITHER_NONE, DITHER_TPDF = 0, 1
+
+
+class Dither(C.Structure):
+    """alac_hip_dither"""
+    _fields_ = [("mode", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
+
+
 def make_format(frame_size=4096, bit_depth=16, num_channels=2, sample_rate=44100):
     return Format(frame_size, bit_depth, num_channels, sample_rate)
 
@@ -59,6 +67,10 @@ SIGNATURES = {
                                      _vp, _u64, _vp, _vp, _vp]),
     "alac_hip_encode_float_host": (_i32, [_vp, C.POINTER(Format), _vp, _u64, _u64, _vp, _u32, _vp, _u32, _vp, _i32, _vp, _u64,
                                           _vp, C.POINTER(_u64), _vp]),
+    "alac_hip_encode_float_dither": (_i32, [_vp, C.POINTER(Format), _vp, _u64, _u64, _vp, _u32, _vp, _u32, _u32, _vp, _i32, _vp,
+                                            _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "alac_hip_encode_float_dither_host": (_i32, [_vp, C.POINTER(Format), _vp, _u64, _u64, _vp, _u32, _vp, _u32, _vp, _i32, _vp,
+                                                 _u64, _vp, C.POINTER(_u64), _vp, _vp, _vp]),
     "alac_hip_profile_begin": (_i32, [_vp, _u32]),
     "alac_hip_profile_end": (_i32, [_vp, C.POINTER(_u32), C.POINTER(C.c_float), C.POINTER(_u32)]),
     "alac_hip_num_stages": (_u32, []),
@@ -326,17 +338,26 @@ class Context:
             return bufs
 
     def encode_float(self, fmt, x, num_samples=None, seg_first=None, state=None, state_in=False, bufs=None,
-                     max_segment_packets=0, clipped=False):
+                     max_segment_packets=0, clipped=False, dither=None, seed=0, packet_origin=None):
         """encode() from float32 PCM (alac_hip_encode_float): x is a float32 cuda tensor [channels, frames] with any strides
         (x.stride() is passed through: a contiguous [C, T] tensor and the transposed view of a [T, C] one need no copy),
         quantized on the device by the rule of include/alac_hip.h (rint(x * 2^(bit_depth - 1)), saturated, NaN -> 0).
         num_packets = ceil(frames / frame_size); num_samples=None gives the last packet frames mod frame_size frames
         when that is not 0.  Returns encode()'s buffers dict; clipped=True adds "clipped", an int32 [num_packets] tensor of
-        the clipped samples per packet."""
+        the clipped samples per packet.
+        dither="tpdf" (alac_hip_encode_float_dither): triangular dither of +-1 LSB in front of the rounding, a pure function
+        of (seed, channel, stream frame index) generated on the device; 16, 20 and 24 bits.  packet_origin: an int64 /
+        uint64 cuda tensor [num_packets] of every packet's first stream frame index (None: packet p starts at
+        p * frame_size), so that a file encoded inside a batch gets the dither it gets alone."""
+        if dither not in (None, "none", "tpdf"):
+            raise ValueError('encode_float: dither must be None, "none" or "tpdf"')
         with self._call() as cur:
             t = self.torch
             if not (x.is_cuda and x.dtype == t.float32 and x.dim() == 2 and x.shape[0] == fmt.num_channels):
                 raise ValueError("encode_float: x must be a float32 cuda tensor [channels, frames]")
+            if packet_origin is not None and not (packet_origin.is_cuda and packet_origin.dtype in (t.int64, t.uint64) and
+                                                  packet_origin.is_contiguous()):
+                raise ValueError("encode_float: packet_origin must be a contiguous int64 / uint64 cuda tensor")
             frames = int(x.shape[1])
             num_packets = (frames + fmt.frame_size - 1) // fmt.frame_size
             if num_samples is None and frames % fmt.frame_size:
@@ -349,13 +370,20 @@ class Context:
             wsb = int(self.lib.alac_hip_encode_float_workspace_bytes(C.byref(fmt), num_packets,
                                                                      num_packets if self.get_option("lpc") else nseg))
             ws = self._workspace(wsb)
-            rc = self.lib.alac_hip_encode_float(
-                self.h, C.byref(fmt), x.data_ptr(), int(x.stride(0)), int(x.stride(1)),
-                None if num_samples is None else num_samples.data_ptr(), num_packets,
-                None if seg_first is None else seg_first.data_ptr(), nseg, int(max_segment_packets),
-                None if state is None else state.data_ptr(), 1 if state_in else 0,
-                ws.data_ptr(), ws.numel(), bufs["out"].data_ptr(), bufs["out"].numel(),
-                bufs["sizes"].data_ptr(), bufs["offsets"].data_ptr(), bufs["clipped"].data_ptr() if clipped else None)
+            args = (self.h, C.byref(fmt), x.data_ptr(), int(x.stride(0)), int(x.stride(1)),
+                    None if num_samples is None else num_samples.data_ptr(), num_packets,
+                    None if seg_first is None else seg_first.data_ptr(), nseg, int(max_segment_packets),
+                    None if state is None else state.data_ptr(), 1 if state_in else 0,
+                    ws.data_ptr(), ws.numel(), bufs["out"].data_ptr(), bufs["out"].numel(),
+                    bufs["sizes"].data_ptr(), bufs["offsets"].data_ptr(), bufs["clipped"].data_ptr() if clipped else None)
+            if dither is None:
+                rc = self.lib.alac_hip_encode_float(*args)
+            else:
+                if packet_origin is not None and packet_origin.numel() < num_packets:
+                    raise ValueError("encode_float: packet_origin too small")
+                dz = Dither(DITHER_TPDF if dither == "tpdf" else DITHER_NONE, 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+                rc = self.lib.alac_hip_encode_float_dither(*args, C.byref(dz),
+                                                           None if packet_origin is None else packet_origin.data_ptr())
             self._check(rc)
             for v in bufs.values():
                 if hasattr(v, "record_stream"):

@@ -160,12 +160,23 @@ int32_t ALACEncoder::EncodeSegmentsFloat(const float *pcm, uint64_t channelStrid
                                          uint32_t numSegments, uint8_t *out, uint64_t outCapacity, uint32_t *packetBytes,
                                          uint64_t *outTotalBytes, uint32_t *clipped)
 {
+    return EncodeSegmentsFloatAt(pcm, channelStride, frameStride, numSamples, numPackets, segFirst, numSegments, out,
+                                 outCapacity, packetBytes, outTotalBytes, clipped, nullptr);
+}
+
+int32_t ALACEncoder::EncodeSegmentsFloatAt(const float *pcm, uint64_t channelStride, uint64_t frameStride,
+                                           const uint32_t *numSamples, uint32_t numPackets, const uint32_t *segFirst,
+                                           uint32_t numSegments, uint8_t *out, uint64_t outCapacity, uint32_t *packetBytes,
+                                           uint64_t *outTotalBytes, uint32_t *clipped, const uint64_t *packetOrigin)
+{
     alac_hip_format fmt;  // (a null context: kALAC_ParamError from the first option call)
     if ((mLastStatus = prepare(mCtx, mFastMode, mLPCMode, mFrameSize, mBitDepth, mNumChannels, mOutputSampleRate, fmt)))
         return mLastStatus;
     uint64_t total = 0;
-    mLastStatus = alac_hip_encode_float_host(mCtx, &fmt, pcm, channelStride, frameStride, numSamples, numPackets, segFirst,
-                                             numSegments, nullptr, 0, out, outCapacity, packetBytes, &total, clipped);
+    const alac_hip_dither dither = {mDitherMode, 0, mDitherSeed};
+    mLastStatus = alac_hip_encode_float_dither_host(mCtx, &fmt, pcm, channelStride, frameStride, numSamples, numPackets,
+                                                    segFirst, numSegments, nullptr, 0, out, outCapacity, packetBytes, &total,
+                                                    clipped, &dither, packetOrigin);
     if (mLastStatus != ALAC_HIP_noErr) return mLastStatus;
     for (uint32_t p = 0; p < numPackets; p++) account(packetBytes[p]);
     if (outTotalBytes) *outTotalBytes = total;

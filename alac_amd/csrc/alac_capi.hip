@@ -899,13 +899,33 @@ static int32_t float_stride_refusal(alac_hip_ctx *ctx, const alac_hip_format *fm
     return ALAC_HIP_noErr;
 }
 
-// the conversion into the stage c.pcm, then the encode from it
+// the dither of a call: what is wrong with the caller's struct (nullptr: nothing), and whether it asks for dither at all
+static const char *dither_refusal(const alac_hip_format *fmt, const alac_hip_dither *dither, const uint64_t *packet_origin)
+{
+    if (!dither) return nullptr;
+    if (dither->mode > ALAC_HIP_DITHER_TPDF) return "unknown dither mode";
+    if (dither->reserved != 0) return "alac_hip_dither.reserved is not 0";
+    if (dither->mode == ALAC_HIP_DITHER_NONE) return nullptr;
+    if (fmt->bit_depth == 32) return "no dither at 32 bits: a float32 carries nothing below a 32-bit LSB";
+    if ((uintptr_t)packet_origin & 7) return "misaligned packet origin table (8 B)";
+    return nullptr;
+}
+static bool dither_on(const alac_hip_dither *dither) { return dither && dither->mode == ALAC_HIP_DITHER_TPDF; }
+
+// the conversion into the stage c.pcm, then the encode from it.  dither (checked, nullptr or mode NONE: plain rounding) is
+// read here; d_origin is the device table of the packets' stream frame indices or nullptr.
 static int32_t encode_float_run(alac_hip_ctx *ctx, const EncodeCall &c, const float *d_in, uint64_t channel_stride,
-                                uint64_t frame_stride, uint32_t *d_clipped)
+                                uint64_t frame_stride, uint32_t *d_clipped, const alac_hip_dither *dither = nullptr,
+                                const uint64_t *d_origin = nullptr)
 {
     const FloatInArgs a{d_in,        channel_stride,     frame_stride,    c.numSamples, c.numPackets, c.fmt.frame_size,
                         c.fmt.num_channels, (uint8_t *)c.pcm, d_clipped};
-    const hipError_t e = launch_float_to_pcm(c.fmt.bit_depth, a, c.stream);
+    FloatDitherArgs dz = {};
+    if (dither_on(dither)) {
+        dz.origin = d_origin;
+        philox_round_keys(dither->seed, dz.roundKey);
+    }
+    const hipError_t e = launch_float_to_pcm(c.fmt.bit_depth, a, c.stream, dither_on(dither) ? &dz : nullptr);
     if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "float conversion launch", e);
     return (c.fmt.num_channels > 2 ? encode_elements : encode_core)(ctx, c);
 }
@@ -917,8 +937,22 @@ int32_t alac_hip_encode_float(alac_hip_ctx *ctx, const alac_hip_format *fmt, con
                               uint64_t out_capacity, uint32_t *d_packet_bytes, uint64_t *d_packet_offsets,
                               uint32_t *d_clipped)
 {
+    return alac_hip_encode_float_dither(ctx, fmt, d_in, channel_stride, frame_stride, d_num_samples, num_packets, d_seg_first,
+                                        num_segments, max_segment_packets, d_state, state_in, d_workspace, workspace_bytes,
+                                        d_out, out_capacity, d_packet_bytes, d_packet_offsets, d_clipped, nullptr, nullptr);
+}
+
+int32_t alac_hip_encode_float_dither(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *d_in, uint64_t channel_stride,
+                                     uint64_t frame_stride, const uint32_t *d_num_samples, uint32_t num_packets,
+                                     const uint32_t *d_seg_first, uint32_t num_segments, uint32_t max_segment_packets,
+                                     int16_t *d_state, int32_t state_in, void *d_workspace, uint64_t workspace_bytes,
+                                     uint8_t *d_out, uint64_t out_capacity, uint32_t *d_packet_bytes,
+                                     uint64_t *d_packet_offsets, uint32_t *d_clipped, const alac_hip_dither *dither,
+                                     const uint64_t *d_packet_origin)
+{
     if (!ctx) return ALAC_HIP_ParamError;
     if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
+    if (const char *why = dither_refusal(fmt, dither, d_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
     EncodeCall c = describe_encode(ctx, fmt, nullptr, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets,
                                    d_state, state_in, d_workspace, d_out, d_packet_bytes, d_packet_offsets);
     if (num_packets == 0) return encode_refusal(ctx, fmt, 0, c.numSegments, &c, workspace_bytes, out_capacity);
@@ -937,7 +971,7 @@ int32_t alac_hip_encode_float(alac_hip_ctx *ctx, const alac_hip_format *fmt, con
         c.segKind = SegKind::Host;
     }
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
-    return encode_float_run(ctx, c, d_in, channel_stride, frame_stride, d_clipped);
+    return encode_float_run(ctx, c, d_in, channel_stride, frame_stride, d_clipped, dither, d_packet_origin);
 }
 
 uint32_t alac_hip_num_stages(void) { return kNumStages; }
@@ -1397,8 +1431,21 @@ int32_t alac_hip_encode_float_host(alac_hip_ctx *ctx, const alac_hip_format *fmt
                                    uint8_t *h_out, uint64_t out_capacity, uint32_t *h_packet_bytes, uint64_t *out_total_bytes,
                                    uint32_t *h_clipped)
 {
+    return alac_hip_encode_float_dither_host(ctx, fmt, h_in, channel_stride, frame_stride, h_num_samples, num_packets,
+                                             h_seg_first, num_segments, h_state, state_in, h_out, out_capacity, h_packet_bytes,
+                                             out_total_bytes, h_clipped, nullptr, nullptr);
+}
+
+int32_t alac_hip_encode_float_dither_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *h_in,
+                                          uint64_t channel_stride, uint64_t frame_stride, const uint32_t *h_num_samples,
+                                          uint32_t num_packets, const uint32_t *h_seg_first, uint32_t num_segments,
+                                          int16_t *h_state, int32_t state_in, uint8_t *h_out, uint64_t out_capacity,
+                                          uint32_t *h_packet_bytes, uint64_t *out_total_bytes, uint32_t *h_clipped,
+                                          const alac_hip_dither *dither, const uint64_t *h_packet_origin)
+{
     if (!ctx) return ALAC_HIP_ParamError;
     if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
+    if (const char *why = dither_refusal(fmt, dither, h_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
     if (out_total_bytes) *out_total_bytes = 0;
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!h_in || !h_out || !h_packet_bytes || !h_num_samples || !h_seg_first || num_segments == 0)
@@ -1422,11 +1469,13 @@ int32_t alac_hip_encode_float_host(alac_hip_ctx *ctx, const alac_hip_format *fmt
     if (int32_t rc = encode_refusal(ctx, fmt, np, ctx->opt.lpc ? np : nseg, nullptr, 0, 0)) return rc;
     const uint64_t wsBytes = alac_hip_encode_float_workspace_bytes(fmt, np, ctx->opt.lpc ? np : nseg);
     const uint64_t encBytes = (wsBytes - float_stage_bytes(fmt, np)) & ~255ull;  // the stage behind, as alac_hip_encode_float
-    DevBuf dIn, dClip;
+    const bool origin = dither_on(dither) && h_packet_origin;
+    DevBuf dIn, dClip, dOrigin;
     hipError_t e;
-    if ((e = dIn.alloc(span * sizeof(float))) || (e = dClip.alloc(np * 4ull)))
+    if ((e = dIn.alloc(span * sizeof(float))) || (e = dClip.alloc(np * 4ull)) || (origin && (e = dOrigin.alloc(np * 8ull))))
         return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
-    if ((e = hipMemcpyAsync(dIn.p, h_in, span * sizeof(float), hipMemcpyHostToDevice, ctx->stream)))
+    if ((e = hipMemcpyAsync(dIn.p, h_in, span * sizeof(float), hipMemcpyHostToDevice, ctx->stream)) ||
+        (origin && (e = hipMemcpyAsync(dOrigin.p, h_packet_origin, np * 8ull, hipMemcpyHostToDevice, ctx->stream))))
         return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
     int32_t rc = encode_host_common(
         ctx->stream, fmt, h_num_samples, np, h_seg_first, nseg, h_state, state_in, h_out, out_capacity, h_packet_bytes,
@@ -1436,7 +1485,7 @@ int32_t alac_hip_encode_float_host(alac_hip_ctx *ctx, const alac_hip_format *fmt
             const EncodeCall c = describe_encode(ctx, fmt, (uint8_t *)ws + encBytes, ns, np, seg, nseg, maxSeg, state, stIn, ws,
                                                  out, sizes, offs);
             return encode_float_run(ctx, c, (const float *)dIn.p, channel_stride, frame_stride,
-                                    h_clipped ? (uint32_t *)dClip.p : nullptr);
+                                    h_clipped ? (uint32_t *)dClip.p : nullptr, dither, (const uint64_t *)dOrigin.p);
         },
         on_fail(ctx), [ctx] { return alac_hip_synchronize(ctx); });
     if (rc != ALAC_HIP_noErr || !h_clipped) return rc;

@@ -1,5 +1,6 @@
 // alac_float_in.hip — float32 PCM -> the packed interleaved integer PCM alac_hip_encode reads (alac_hip_encode_float).
-// One streaming pass in front of the unchanged encoder: quantize by the rule of include/alac_hip.h, pack, count clips.
+// One streaming pass in front of the unchanged encoder: quantize by the rule of include/alac_hip.h, pack, count clips;
+// for alac_hip_encode_float_dither with TPDF dither from a counter-based generator in front of the rounding.
 #include "alac_dev.hpp"
 #include "alac_kernels.hpp"
 
@@ -8,16 +9,74 @@ namespace alacdev {
 // the rule of alac_hip_encode_float: r = rint(x * 2^(DEPTH-1)) (the product is exact), saturated; NaN -> 0.  r is an
 // integer, so "r > 2^(DEPTH-1) - 1" is "r >= 2^(DEPTH-1)", a comparison with an exact float even at 32 bits.
 template <int DEPTH>
-__device__ __forceinline__ int32_t quantize(float x, uint32_t &clips)
+__device__ __forceinline__ int32_t saturate(bool nan, float r, uint32_t &clips)
 {
     constexpr float kScale = (float)(1ull << (DEPTH - 1));
     constexpr int32_t kMax = (int32_t)((1ull << (DEPTH - 1)) - 1);
-    const float r = rintf(x * kScale);
-    const bool nan = x != x, hi = r >= kScale;
+    const bool hi = r >= kScale;
     clips += (nan || hi || r < -kScale) ? 1u : 0u;
     // fmaxf(NaN, y) = y, so the conversion only ever sees a value in [-2^(DEPTH-1), 2^(DEPTH-1))
     const int32_t s = (int32_t)fmaxf(r, -kScale);
     return nan ? 0 : (hi ? kMax : s);
+}
+
+template <int DEPTH>
+__device__ __forceinline__ int32_t quantize(float x, uint32_t &clips)
+{
+    return saturate<DEPTH>(x != x, rintf(x * (float)(1ull << (DEPTH - 1))), clips);
+}
+
+// the rule of alac_hip_encode_float_dither: v = x * 2^(DEPTH-1) + d rounded once (the product is exact, so the fused form
+// and multiply-then-add agree), r = rint(v), then as above.  d = 0 gives quantize(x).
+template <int DEPTH>
+__device__ __forceinline__ int32_t quantize_dithered(float x, float d, uint32_t &clips)
+{
+    return saturate<DEPTH>(x != x, rintf(fmaf(x, (float)(1ull << (DEPTH - 1)), d)), clips);
+}
+
+// ---- TPDF dither: Philox4x32-10 (Salmon et al., Random123), a pure function of (seed, channel, frame index) ----
+constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u, kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
+
+void philox_round_keys(uint64_t seed, uint32_t (&roundKey)[10][2])
+{
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int r = 0; r < 10; r++, k0 += kPhiloxW0, k1 += kPhiloxW1) roundKey[r][0] = k0, roundKey[r][1] = k1;
+}
+
+// counter (T & 0xffffffff, T >> 32, c, 0): two 32 x 32 -> 64-bit products per round, both halves of each used
+__device__ __forceinline__ void philox(uint64_t T, uint32_t c, const FloatDitherArgs &d, uint32_t (&w)[4])
+{
+    uint32_t c0 = (uint32_t)T, c1 = (uint32_t)(T >> 32), c2 = c, c3 = 0;
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const uint64_t p0 = (uint64_t)kPhiloxM0 * c0, p1 = (uint64_t)kPhiloxM1 * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ d.roundKey[r][0], n2 = (uint32_t)(p0 >> 32) ^ c3 ^ d.roundKey[r][1];
+        c0 = n0, c1 = (uint32_t)p1, c2 = n2, c3 = (uint32_t)p0;
+    }
+    w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
+}
+
+// k * 2^-24 with k = (wa >> 8) - (wb >> 8): |k| < 2^24, so the conversion and the scaling are exact
+__device__ __forceinline__ float tpdf(uint32_t wa, uint32_t wb)
+{
+    return (float)((int32_t)(wa >> 8) - (int32_t)(wb >> 8)) * 0x1p-24f;
+}
+
+// the dither of channel c at stream frames t0 .. t0 + 3.  One Philox call serves frames 2T and 2T + 1: two calls when t0 is
+// even (every word used), three when it is odd (an odd packet origin; the same for a whole wave, so no divergence).
+__device__ __forceinline__ void dither4(uint64_t t0, uint32_t c, const FloatDitherArgs &d, float (&z)[4])
+{
+    const uint64_t T = t0 >> 1;
+    uint32_t u[4], v[4];
+    philox(T, c, d, u);
+    philox(T + 1, c, d, v);
+    if ((t0 & 1) == 0) {
+        z[0] = tpdf(u[0], u[1]), z[1] = tpdf(u[2], u[3]), z[2] = tpdf(v[0], v[1]), z[3] = tpdf(v[2], v[3]);
+    } else {
+        uint32_t w[4];
+        philox(T + 2, c, d, w);
+        z[0] = tpdf(u[2], u[3]), z[1] = tpdf(v[0], v[1]), z[2] = tpdf(v[2], v[3]), z[3] = tpdf(w[0], w[1]);
+    }
 }
 
 // a sample as it sits in its container: 20-bit left-justified in 3 bytes (task_load / load_sample read it back >> 4)
@@ -92,8 +151,10 @@ enum FloatLayout : int {
 // CH: 1 or 2 (the vector layouts, frameSize % 4 == 0, aligned strides and base: the host checks) or 0 (kFloatGeneral,
 // a.channels at run time).  Clipped samples: per lane <= 4 * kMaxChannels; the wave sums them with one ballot per bit
 // of the lane's count and adds the total to clipped[p] with one atomic (a block, hence a wave, lies in one packet).
-template <int DEPTH, int CH, int LAYOUT>
-__global__ __launch_bounds__(256) void k_float_to_pcm(FloatInArgs a, uint64_t blocksPerPacket)
+// DITHER: every frame in front of n gets dz's dither for its stream frame index and channel (dither4: two Philox calls
+// per channel and lane where the packet's origin is even); the staged zeros behind n stay zeros.  Without it dz is unused.
+template <int DEPTH, int CH, int LAYOUT, bool DITHER>
+__global__ __launch_bounds__(256) void k_float_to_pcm(FloatInArgs a, uint64_t blocksPerPacket, FloatDitherArgs dz)
 {
     constexpr uint32_t BPS = bytes_per_sample(DEPTH);
     constexpr int CNT_BITS = CH == 1 ? 3 : (CH == 2 ? 4 : 6);  // bits of a lane's clip count: <= 4, 8, 32
@@ -106,7 +167,25 @@ __global__ __launch_bounds__(256) void k_float_to_pcm(FloatInArgs a, uint64_t bl
         n = n < fs ? n : fs;
         const uint64_t f0 = (uint64_t)p * fs + i0;  // frame index of the lane's first frame in the batch
         uint32_t clips = 0;
-        if constexpr (LAYOUT == kFloatGeneral) {
+        uint64_t t0 = 0;  // stream frame index of the lane's first frame
+        if constexpr (DITHER) t0 = (dz.origin ? dz.origin[p] : (uint64_t)p * fs) + i0;
+        if constexpr (LAYOUT == kFloatGeneral && DITHER) {
+            const uint32_t C = a.channels;
+            for (uint32_t c = 0; c < C && i0 < fs; c++) {
+                float z[4];
+                dither4(t0, c, dz, z);
+#pragma unroll
+                for (uint32_t k = 0; k < 4; k++) {
+                    const uint32_t i = i0 + k;
+                    if (i < fs) {
+                        const bool live = i < n;
+                        const float x = live ? a.in[c * a.channelStride + (f0 + k) * a.frameStride] : 0.0f;
+                        store_sample<DEPTH>(a.pcm + ((f0 + k) * C + c) * BPS,
+                                            quantize_dithered<DEPTH>(x, live ? z[k] : 0.0f, clips));
+                    }
+                }
+            }
+        } else if constexpr (LAYOUT == kFloatGeneral) {
             const uint32_t C = a.channels;
             for (uint32_t k = 0; k < 4; k++) {
                 const uint32_t i = i0 + k;
@@ -143,10 +222,21 @@ __global__ __launch_bounds__(256) void k_float_to_pcm(FloatInArgs a, uint64_t bl
                         x[c][k] = i0 + k < n ? a.in[c * a.channelStride + (f0 + k) * a.frameStride] : 0.0f;
             }
             int32_t s[4 * CH];
+            if constexpr (DITHER) {
 #pragma unroll
-            for (int k = 0; k < 4; k++)
+                for (int c = 0; c < CH; c++) {
+                    float z[4];
+                    dither4(t0, c, dz, z);
 #pragma unroll
-                for (int c = 0; c < CH; c++) s[k * CH + c] = quantize<DEPTH>(x[c][k], clips);
+                    for (int k = 0; k < 4; k++)
+                        s[k * CH + c] = quantize_dithered<DEPTH>(x[c][k], i0 + k < n ? z[k] : 0.0f, clips);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+#pragma unroll
+                    for (int c = 0; c < CH; c++) s[k * CH + c] = quantize<DEPTH>(x[c][k], clips);
+            }
             uint32_t w[CH * BPS];
             pack_dwords<DEPTH, 4 * CH>(s, w);
             store_dwords<CH * BPS>(a.pcm + f0 * (CH * BPS), w);
@@ -160,21 +250,23 @@ __global__ __launch_bounds__(256) void k_float_to_pcm(FloatInArgs a, uint64_t bl
     }
 }
 
-template <int DEPTH>
-static void launch_depth(const FloatInArgs &a, FloatLayout layout, dim3 grid, uint64_t bpp, hipStream_t st)
+template <int DEPTH, bool DITHER>
+static void launch_depth(const FloatInArgs &a, const FloatDitherArgs &dz, FloatLayout layout, dim3 grid, uint64_t bpp,
+                         hipStream_t st)
 {
     if (layout == kFloatGeneral)
-        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 0, kFloatGeneral>), grid, dim3(256), 0, st, a, bpp);
+        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 0, kFloatGeneral, DITHER>), grid, dim3(256), 0, st, a, bpp, dz);
     else if (a.channels == 1)
-        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 1, kFloatPlanar>), grid, dim3(256), 0, st, a, bpp);
+        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 1, kFloatPlanar, DITHER>), grid, dim3(256), 0, st, a, bpp, dz);
     else if (layout == kFloatPlanar)
-        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 2, kFloatPlanar>), grid, dim3(256), 0, st, a, bpp);
+        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 2, kFloatPlanar, DITHER>), grid, dim3(256), 0, st, a, bpp, dz);
     else
-        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 2, kFloatInterleaved>), grid, dim3(256), 0, st, a, bpp);
+        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 2, kFloatInterleaved, DITHER>), grid, dim3(256), 0, st, a, bpp, dz);
 }
 
-hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t st)
+hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t st, const FloatDitherArgs *dither)
 {
+    if (dither && depth != 16 && depth != 20 && depth != 24) return hipErrorInvalidValue;  // no dither at 32 bits
     if (a.numPackets == 0) return hipSuccess;
     if (a.clipped) {
         const hipError_t e = hipMemsetAsync(a.clipped, 0, (uint64_t)a.numPackets * 4, st);
@@ -188,11 +280,20 @@ hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t
     const uint64_t bpp = ((uint64_t)a.frameSize + 1023) / 1024;
     const uint64_t blocks = (uint64_t)a.numPackets * bpp;
     const dim3 grid((uint32_t)(blocks < (1u << 22) ? blocks : (1u << 22)));
+    if (dither) {
+        switch (depth) {
+        case 16: launch_depth<16, true>(a, *dither, layout, grid, bpp, st); break;
+        case 20: launch_depth<20, true>(a, *dither, layout, grid, bpp, st); break;
+        default: launch_depth<24, true>(a, *dither, layout, grid, bpp, st); break;
+        }
+        return hipGetLastError();
+    }
+    const FloatDitherArgs none = {};
     switch (depth) {
-    case 16: launch_depth<16>(a, layout, grid, bpp, st); break;
-    case 20: launch_depth<20>(a, layout, grid, bpp, st); break;
-    case 24: launch_depth<24>(a, layout, grid, bpp, st); break;
-    default: launch_depth<32>(a, layout, grid, bpp, st); break;
+    case 16: launch_depth<16, false>(a, none, layout, grid, bpp, st); break;
+    case 20: launch_depth<20, false>(a, none, layout, grid, bpp, st); break;
+    case 24: launch_depth<24, false>(a, none, layout, grid, bpp, st); break;
+    default: launch_depth<32, false>(a, none, layout, grid, bpp, st); break;
     }
     return hipGetLastError();
 }

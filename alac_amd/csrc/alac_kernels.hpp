@@ -293,7 +293,16 @@ struct FloatInArgs {
     uint8_t *pcm;
     uint32_t *clipped;
 };
-hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t st);
+// TPDF dither in front of the rounding (alac_hip_encode_float_dither; depth 16, 20 or 24): the sample at stream frame
+// t = origin[p] + i (origin null: p * frameSize) of channel c gets the dither Philox4x32-10 gives for counter (t >> 1, c),
+// half of its four words by t's parity.  roundKey: the ten round keys of the seed (philox_round_keys), the same for every
+// sample, so the kernel reads them as scalars
+struct FloatDitherArgs {
+    const uint64_t *origin;  // [numPackets] or null
+    uint32_t roundKey[10][2];
+};
+void philox_round_keys(uint64_t seed, uint32_t (&roundKey)[10][2]);
+hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t st, const FloatDitherArgs *dither = nullptr);
 
 // ---- stage-level ----
 hipError_t launch_pc_block(const int32_t *in, int32_t *pc, uint32_t rows, uint32_t stride, int32_t num,

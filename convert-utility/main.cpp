@@ -35,6 +35,11 @@
  *                                             output is the file an integer input holding the quantized samples gives; a
  *                                             clip count is a warning on stderr.  Integer or 64-bit float inputs and
  *                                             --verify are refused
+ *   --dither [--dither-seed S]                with --float-bits 16, 20 or 24: triangular (TPDF) dither of +-1 LSB in front of
+ *                                             the rounding, generated on the GPU (alac_hip_encode_float_dither) from the seed S
+ *                                             (decimal or 0x-hex, default 0: two runs give the same file).  Every file's
+ *                                             frames count from 0, so a file's output is the same alone, in --batch and
+ *                                             with --devices N
  *
  * A single chained file is serial by construction: one file runs as one chain of dependent
  * packets; the GPU pays off with --batch or --segment-packets.
@@ -86,6 +91,7 @@ void usage()
     printf("        alacconvert --verify [--batch] [--lpc] ... <input wav or caf file> <output caf or m4a file> ...\n");
     printf("        alacconvert --compare <input caf or m4a file> <reference wav or caf file>\n");
     printf("        alacconvert --float-bits N [--batch] [--lpc] ... <input float wav or caf file> <output caf or m4a file> ...\n");
+    printf("        alacconvert --float-bits N --dither [--dither-seed S] ... <input float wav or caf file> <output caf or m4a file> ...\n");
     printf("\n");
 }
 
@@ -144,7 +150,14 @@ bool verify_group(std::vector<Job *> &jobs, ALACEncoder &enc, const std::vector<
     return false;
 }
 
-bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, bool verify, int device)
+// --dither: TPDF dither with this seed on the float inputs
+struct DitherOption {
+    bool on = false;
+    uint64_t seed = 0;
+};
+
+bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, bool verify, const DitherOption &dither,
+                  int device)
 {
     const InputInfo &first = jobs[0]->info;
     const uint32_t bps = (first.bitsPerChannel + 7) >> 3, ch = first.channels;  // 20 bits: 3-byte containers (container.cpp)
@@ -154,6 +167,7 @@ bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, b
     ALACEncoder enc;
     enc.SetFrameSize(frame);
     enc.SetLPCMode(lpc);
+    if (dither.on) enc.SetDither(ALAC_HIP_DITHER_TPDF, dither.seed);
     if (device >= 0) enc.SetDevice(device);
     AudioFormatDescription outFmt = alac_format(first);
     if (enc.InitializeEncoder(outFmt, 0) != ALAC_noErr) {
@@ -199,9 +213,14 @@ bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, b
         }
         stream.resize((size_t)np * (packetBytes + kALACMaxEscapeHeaderBytes));
         std::vector<uint32_t> clipped(np, 0);
-        const int32_t rc = enc.EncodeSegmentsFloat(fl.data(), 1, ch, numSamples.data(), np, segs.data(),
-                                                   (uint32_t)segs.size() - 1, stream.data(), stream.size(), sizes.data(),
-                                                   &total, clipped.data());
+        // every file's frames count from 0: its dither does not depend on the files beside it
+        std::vector<uint64_t> origin(np, 0);
+        for (size_t j = 0; j < jobs.size(); j++)
+            for (uint32_t p = firstPacket[j], p1 = j + 1 < jobs.size() ? firstPacket[j + 1] : np; p < p1; p++)
+                origin[p] = (uint64_t)(p - firstPacket[j]) * frame;
+        const int32_t rc = enc.EncodeSegmentsFloatAt(fl.data(), 1, ch, numSamples.data(), np, segs.data(),
+                                                     (uint32_t)segs.size() - 1, stream.data(), stream.size(), sizes.data(),
+                                                     &total, clipped.data(), origin.data());
         if (rc != ALAC_noErr) {
             fprintf(stderr, " Encoding failed (status %d)\n", rc);
             return false;
@@ -423,6 +442,7 @@ int main(int argc, char *argv[])
     std::vector<std::string> files;
     bool batch = false, lpc = false, verify = false, compare = false, malformed = argc < 2;
     uint32_t segmentPackets = 0, devices = 0, floatBits = 0;
+    DitherOption dither;
     for (int i = 1; i < argc && !malformed; i++) {
         const std::string a = argv[i];
         if (a == "-h") {
@@ -441,6 +461,12 @@ int main(int argc, char *argv[])
         } else if (a == "--float-bits" && i + 1 < argc) {
             floatBits = (uint32_t)strtoul(argv[++i], nullptr, 10);
             if (floatBits != 16 && floatBits != 20 && floatBits != 24 && floatBits != 32) malformed = true;
+        } else if (a == "--dither") {
+            dither.on = true;
+        } else if (a == "--dither-seed" && i + 1 < argc) {
+            char *end = nullptr;
+            dither.seed = strtoull(argv[++i], &end, 0);  // decimal or 0x-hex
+            if (end == argv[i] || *end) malformed = true;
         } else if (a == "--devices" && i + 1 < argc) {
             devices = (uint32_t)strtoul(argv[++i], nullptr, 10);
             if (devices == 0) malformed = true;
@@ -455,7 +481,13 @@ int main(int argc, char *argv[])
     if (!malformed && devices && !batch) malformed = true;  // one file is one serial chain: nothing to deal out
     // --compare stands alone: two files, no other option
     if (!malformed && compare && (batch || lpc || verify || segmentPackets || devices || floatBits)) malformed = true;
+    if (!malformed && compare && dither.on) malformed = true;
     if (malformed) {
+        usage();
+        return 1;
+    }
+    if (dither.on && floatBits != 16 && floatBits != 20 && floatBits != 24) {
+        fprintf(stderr, " --dither needs --float-bits 16, 20 or 24\n");
         usage();
         return 1;
     }
@@ -580,7 +612,7 @@ int main(int argc, char *argv[])
         const int device = firstDevice < 0 ? -1 : (int)(k % (uint32_t)visible);
         for (size_t i = 0; i < perWorker[k].size() && ok[k]; i++) {
             Work &w = perWorker[k][i];
-            ok[k] = w.decode ? decode_group(w.jobs, w.contents, device) : encode_group(w.jobs, segmentPackets, lpc, verify, device);
+            ok[k] = w.decode ? decode_group(w.jobs, w.contents, device) : encode_group(w.jobs, segmentPackets, lpc, verify, dither, device);
         }
     };
     if (workers == 1) {

@@ -36,6 +36,9 @@ public:
      * ALAC_HIP_DEVICE, else 0).  One object = one device = one stream; objects on different devices may be driven from
      * different threads (alacconvert --batch --devices N). */
     void SetDevice(int device) { mDevice = device; }
+    /* Extension: TPDF dither for the float encode methods (alac_hip_encode_float_dither; mode ALAC_HIP_DITHER_NONE = 0 or
+     * ALAC_HIP_DITHER_TPDF = 1, 16 / 20 / 24 bits).  Default: none.  The integer encode methods never dither. */
+    void SetDither(uint32_t mode, uint64_t seed) { mDitherMode = mode, mDitherSeed = seed; }
 
     void GetConfig(ALACSpecificConfig &config);
     uint32_t GetMagicCookieSize(uint32_t inNumChannels);
@@ -64,6 +67,13 @@ public:
     int32_t EncodeSegmentsFloat(const float *pcm, uint64_t channelStride, uint64_t frameStride, const uint32_t *numSamples,
                                 uint32_t numPackets, const uint32_t *segFirst, uint32_t numSegments, uint8_t *out,
                                 uint64_t outCapacity, uint32_t *packetBytes, uint64_t *outTotalBytes, uint32_t *clipped);
+    /* EncodeSegmentsFloat with every packet's first stream frame index, packetOrigin[numPackets] (NULL: packet p starts at
+     * p * frameSize): the dither set by SetDither is keyed on it, so a file whose packets count from 0 gets the same bytes
+     * alone and inside a batch.  Without dither the table is ignored and the result is EncodeSegmentsFloat's. */
+    int32_t EncodeSegmentsFloatAt(const float *pcm, uint64_t channelStride, uint64_t frameStride, const uint32_t *numSamples,
+                                  uint32_t numPackets, const uint32_t *segFirst, uint32_t numSegments, uint8_t *out,
+                                  uint64_t outCapacity, uint32_t *packetBytes, uint64_t *outTotalBytes, uint32_t *clipped,
+                                  const uint64_t *packetOrigin);
 
     int32_t LastStatus() const { return mLastStatus; }
 
@@ -71,6 +81,8 @@ protected:
     int16_t mBitDepth;
     bool mFastMode;
     bool mLPCMode = false;
+    uint32_t mDitherMode = 0;
+    uint64_t mDitherSeed = 0;
     uint32_t mTotalBytesGenerated, mAvgBitRate, mMaxFrameBytes;
     uint32_t mFrameSize, mMaxOutputBytes, mNumChannels, mOutputSampleRate;
 

@@ -185,7 +185,8 @@ int32_t alac_hip_encode_segmented(alac_hip_ctx *ctx, const alac_hip_format *fmt,
  *   x = 1.0 clips to 2^(b-1) - 1 and counts as clipped; x = -1.0 is exact; -0.0 and denormals give 0.  At 32 bits the
  *   float product is exact and every finite x < 1.0 is at most 2^31 - 128, so it never clips.  A 20-bit sample goes into
  *   its 3-byte container left-justified (s << 4), as alac_hip_encode reads it.  So alac_hip_decode_float(alac_hip_encode_float
- *   (x)) == x bit for bit whenever x * 2^(b-1) is an integer in range.
+ *   (x)) == x bit for bit whenever x * 2^(b-1) is an integer in range.  (Not with the dither of
+ *   alac_hip_encode_float_dither below: there the rounding is of x * 2^(b-1) + d.)
  *   d_in              float32, 4-byte aligned: sample i of channel c of packet p at
  *                     d_in[c * channel_stride + (p * frame_size + i) * frame_stride].  Planar [C, T] is (channel_stride >= T,
  *                     frame_stride = 1), interleaved [T, C] is (channel_stride = 1, frame_stride = C); both take 16-byte
@@ -221,6 +222,61 @@ int32_t alac_hip_encode_float_host(alac_hip_ctx *ctx, const alac_hip_format *fmt
                                    const uint32_t *h_seg_first, uint32_t num_segments, int16_t *h_state,
                                    int32_t state_in, uint8_t *h_out, uint64_t out_capacity,
                                    uint32_t *h_packet_bytes, uint64_t *out_total_bytes, uint32_t *h_clipped);
+
+/* ---- TPDF dither in front of the rounding of alac_hip_encode_float ------------------------------------------------------
+ * What every tool that reduces float audio to 16 bits adds by default: triangular dither of +-1 LSB, so that the error of
+ * the quantization has mean 0 and variance 1/4 LSB^2 whatever the input instead of following the signal.  The dither comes
+ * from a counter-based generator: it is a pure function of (seed, channel, frame index), generated on the device in the
+ * same pass that quantizes, and reproducible bit for bit on the host.  No reference counterpart.
+ * The rule, for bit depth b in {16, 20, 24}, seed S (64 bits), channel c (its index in the call, 0-based), and stream
+ * frame index t (64 bits) of the sample:
+ *     T  = t >> 1
+ *     w  = Philox4x32-10( counter = (T & 0xffffffff, T >> 32, c, 0),  key = (S & 0xffffffff, S >> 32) )   # 4 words
+ *     (wa, wb) = (w[0], w[1]) if t is even, (w[2], w[3]) if t is odd       # one Philox call serves two frames
+ *     k  = (int)(wa >> 8) - (int)(wb >> 8)                                  # -(2^24 - 1) .. 2^24 - 1, triangular
+ *     d  = (float)k * 2^-24                                                 # exact; strictly inside (-1, 1) LSB
+ *     v  = x * 2^(b-1) + d        rounded ONCE to float32  (the product is exact, so fmaf and mul-then-add agree)
+ *     r  = rint(v)                                                          # then exactly the existing rule:
+ *     s, clipped(x)  as alac_hip_encode_float defines them from r           # saturation, NaN -> 0 and clipped
+ *   Philox4x32-10 is the generator of Salmon et al. (Random123; multipliers 0xD2511F53 / 0xCD9E8D57, key increments
+ *   0x9E3779B9 / 0xBB67AE85, ten rounds).  t = origin[p] + i for sample-frame i of packet p, where origin is
+ *   d_packet_origin, an optional [num_packets] uint64 table (8-byte aligned), and p * frame_size when it is NULL.  The table
+ *   keeps a file's bytes the same whether it is encoded alone or as one of many in a batch (number every file's frames
+ *   from 0).  Frames at or behind num_samples[p] are staged as zero as in alac_hip_encode_float: no dither there.  Because
+ *   the key is the frame index and not the packet, the quantized PCM does not depend on frame_size, the layout of the
+ *   input, the segment table or the encode options.  Digital silence is dithered like everything else.
+ *   In float64 the sum x * 2^(b-1) + d is exact whenever |x * 2^(b-1)| < 2^29, which covers everything that does not
+ *   saturate, so float32(float64(x) * 2^(b-1) + float64(d)) is the host restatement (tests/dither_ref.py).
+ *   With dither on, alac_hip_decode_float(alac_hip_encode_float_dither(x)) == x no longer holds on the grid: that is the point.
+ * dither == NULL or mode ALAC_HIP_DITHER_NONE: exactly alac_hip_encode_float (d_packet_origin is ignored).  The workspace is
+ * that of alac_hip_encode_float_workspace_bytes.  Asynchronous like alac_hip_encode_float; *dither is read before the call
+ * returns.  kALAC_ParamError, checked before anything is enqueued and with nothing written: a mode above
+ * ALAC_HIP_DITHER_TPDF, reserved != 0, bit depth 32 with mode TPDF (a float32 carries nothing below a 32-bit LSB, and the
+ * one-rounding rule cannot be restated in float64 there), a d_packet_origin that is not 8-byte aligned, and everything
+ * alac_hip_encode_float refuses.
+ */
+enum { ALAC_HIP_DITHER_NONE = 0, ALAC_HIP_DITHER_TPDF = 1 };
+typedef struct alac_hip_dither {
+    uint32_t mode;     /* ALAC_HIP_DITHER_* */
+    uint32_t reserved; /* 0 */
+    uint64_t seed;
+} alac_hip_dither;
+int32_t alac_hip_encode_float_dither(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *d_in,
+                                     uint64_t channel_stride, uint64_t frame_stride,
+                                     const uint32_t *d_num_samples, uint32_t num_packets,
+                                     const uint32_t *d_seg_first, uint32_t num_segments, uint32_t max_segment_packets,
+                                     int16_t *d_state, int32_t state_in, void *d_workspace, uint64_t workspace_bytes,
+                                     uint8_t *d_out, uint64_t out_capacity, uint32_t *d_packet_bytes,
+                                     uint64_t *d_packet_offsets, uint32_t *d_clipped,
+                                     const alac_hip_dither *dither, const uint64_t *d_packet_origin);
+/* Host-buffer form: alac_hip_encode_float_host with the dither above; h_packet_origin: [num_packets] on the host, or NULL. */
+int32_t alac_hip_encode_float_dither_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *h_in,
+                                          uint64_t channel_stride, uint64_t frame_stride,
+                                          const uint32_t *h_num_samples, uint32_t num_packets,
+                                          const uint32_t *h_seg_first, uint32_t num_segments, int16_t *h_state,
+                                          int32_t state_in, uint8_t *h_out, uint64_t out_capacity,
+                                          uint32_t *h_packet_bytes, uint64_t *out_total_bytes, uint32_t *h_clipped,
+                                          const alac_hip_dither *dither, const uint64_t *h_packet_origin);
 
 /* Per-kernel timing with HIP events recorded on the context's stream around the three kernels of
  * alac_hip_encode (the instrumented counterpart of the dead cudaEvent timing in

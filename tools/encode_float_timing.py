@@ -5,6 +5,8 @@ packet independent, from a float32 [2, T] device tensor on the grid (the synthet
   encode           alac_hip_encode on the integer PCM (interleaved packed bytes, already on the device)
   encode_float     alac_hip_encode_float on the float tensor (and on the same floats interleaved, a transposed [T, 2])
   torch+encode     nan_to_num / scale / round / clamp / cast / interleave / pack to 2 or 3 bytes in torch, then encode
+  dither           alac_hip_encode_float_dither (TPDF, generated in the conversion kernel) on the float tensor
+  torch dither+encode   the torch route with TPDF dither from two torch.rand draws added in front of the rounding
 Times are device-synchronised wall times per call (best of 4 x 5 calls; inputs and outputs on the device, allocated once).
 The conversion kernel's own time (k_float_to_pcm) comes from a rocprofv3 --kernel-trace --stats run of this script."""
 import argparse
@@ -52,6 +54,16 @@ def torch_pack(x, depth):
     return torch.stack([s & 0xFF, (s >> 8) & 0xFF, (s >> 16) & 0xFF], dim=1).to(torch.uint8).view(-1)
 
 
+def torch_dither_pack(x, depth):
+    """torch_pack with TPDF dither of +-1 LSB in front of the rounding: what a caller writes in torch to get a dithered master"""
+    top = float(2 ** (depth - 1))
+    d = torch.rand_like(x).sub_(torch.rand_like(x))
+    s = torch.nan_to_num(x, nan=0.0).mul(top).add_(d).round().clamp(-top, top - 1).to(torch.int32).t().contiguous().view(-1)
+    if depth == 16:
+        return s.to(torch.int16).view(torch.uint8)
+    return torch.stack([s & 0xFF, (s >> 8) & 0xFF, (s >> 16) & 0xFF], dim=1).to(torch.uint8).view(-1)
+
+
 def measure(ctx, n, depth):
     fmt = alac_amd.make_format(4096, depth, 2, 44100)
     d_pcm = ctx.synth_pcm(0, n, fmt)
@@ -71,7 +83,17 @@ def measure(ctx, n, depth):
         xi = x.t().contiguous().t()  # the same floats interleaved: a [T, 2] tensor viewed as [2, T]
         r["encode_float_interleaved_ms"] = best_of(ctx, lambda: ctx.encode_float(fmt, xi, bufs=bufs)) * 1e3
         r["torch_encode_ms"] = best_of(ctx, lambda: ctx.encode(fmt, torch_pack(x, depth), n, bufs=bufs)) * 1e3
+        # the dithered samples differ from the grid by at most 1: same sizes of buffers, other bytes
+        r["dither_ms"] = best_of(ctx, lambda: ctx.encode_float(fmt, x, bufs=bufs, dither="tpdf", seed=1)) * 1e3
+        r["dither_interleaved_ms"] = best_of(ctx, lambda: ctx.encode_float(fmt, xi, bufs=bufs, dither="tpdf", seed=1)) * 1e3
+        r["torch_dither_encode_ms"] = best_of(ctx, lambda: ctx.encode(fmt, torch_dither_pack(x, depth), n, bufs=bufs)) * 1e3
+        # the encoder's share of the two dithered routes: encode of PCM that is already dithered (it compresses worse
+        # than the grid input above, so it is not encode_ms)
+        d_dith = torch_dither_pack(x, depth)
+        r["encode_dithered_pcm_ms"] = best_of(ctx, lambda: ctx.encode(fmt, d_dith, n, bufs=bufs)) * 1e3
     r["float_minus_encode_ms"] = r["encode_float_ms"] - r["encode_ms"]
+    r["dither_minus_float_ms"] = r["dither_ms"] - r["encode_float_ms"]
+    r["dither_over_torch_dither"] = r["dither_ms"] / r["torch_dither_encode_ms"]
     r["float_over_torch"] = r["encode_float_ms"] / r["torch_encode_ms"]
     # bytes the conversion moves: 4 read + 2 or 3 written per sample
     r["conversion_bytes"] = n * 4096 * 2 * (4 + alac_amd.capi.BPS[depth])
