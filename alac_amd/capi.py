@@ -97,6 +97,8 @@ SIGNATURES = {
     "alac_hip_verify_workspace_bytes_stream": (_u64, [C.POINTER(Format), _u32, _u64]),
     "alac_hip_verify": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "alac_hip_verify_host": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "alac_hip_verify_float": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "alac_hip_verify_float_host": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "alac_synth_frame": (None, [_u64, _u32, _u32, _u32, _vp]),
     "alac_synth_pcm": (None, [_u64, _u32, _u32, _u32, _u32, _vp]),
     "alac_hip_synth_pcm": (_i32, [_vp, _u64, _u32, C.POINTER(Format), _vp]),
@@ -532,6 +534,55 @@ class Context:
             self._check(rc)
             for x in (fm, st, bad):
                 x.record_stream(cur)
+            return fm, st, bad
+
+    def verify_float(self, cookie, stream, offsets, num_packets, x, num_samples=None, dither=None, seed=0,
+                     packet_origin=None):
+        """verify() against the float32 source of encode_float (alac_hip_verify_float): x is a float32 cuda tensor
+        [channels, frames] of any strides, passed through like encode_float's.  Every decoded sample is compared with what
+        the float encode path stages for its source float at the stream's bit depth — rounding, saturation, NaN -> 0 and,
+        with dither="tpdf", the dither of (seed, channel, stream frame index); packet_origin as in encode_float.
+        num_samples: expected frames per packet (int32 cuda [num_packets]); None = every packet full, the last one
+        frames mod frame_size where x ends inside it.  Only frames in front of a packet's expected count are read from
+        x, so with num_samples given x must hold those.  Returns verify()'s triple.  Asynchronous like decode()."""
+        if dither not in (None, "none", "tpdf"):
+            raise ValueError('verify_float: dither must be None, "none" or "tpdf"')
+        with self._call() as cur:
+            t = self.torch
+            ck = np.ascontiguousarray(cookie, np.uint8)
+            fmt = Format()
+            self._check(self.lib.alac_hip_format_from_cookie(ck.ctypes.data, ck.size, C.byref(fmt)))
+            if not (x.is_cuda and x.dtype == t.float32 and x.dim() == 2 and x.shape[0] == fmt.num_channels):
+                raise ValueError("verify_float: x must be a float32 cuda tensor [channels, frames]")
+            if packet_origin is not None and not (packet_origin.is_cuda and packet_origin.dtype in (t.int64, t.uint64) and
+                                                  packet_origin.is_contiguous() and packet_origin.numel() >= num_packets):
+                raise ValueError("verify_float: packet_origin must be a contiguous int64 / uint64 cuda tensor [num_packets]")
+            frames = int(x.shape[1])
+            if num_samples is None and frames < num_packets * fmt.frame_size:
+                full = frames // fmt.frame_size
+                ns = [fmt.frame_size] * full + [frames % fmt.frame_size] + [0] * (num_packets - full - 1)
+                num_samples = t.tensor(ns[:num_packets], dtype=t.int32).to(self.device, non_blocking=True)
+            if num_samples is not None and num_samples.numel() < num_packets:
+                raise ValueError("verify_float: num_samples too small")
+            fm = t.empty(num_packets, dtype=t.int32, device=self.device)
+            st = t.empty(num_packets, dtype=t.int32, device=self.device)
+            bad = t.empty(1, dtype=t.int32, device=self.device)
+            wsb = int(self.lib.alac_hip_verify_workspace_bytes_stream(C.byref(fmt), num_packets, int(stream.numel())))
+            ws = self._workspace(wsb)
+            dz = None
+            if dither is not None:
+                dz = Dither(DITHER_TPDF if dither == "tpdf" else DITHER_NONE, 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+            rc = self.lib.alac_hip_verify_float(self.h, ck.ctypes.data, ck.size, stream.data_ptr(), offsets.data_ptr(),
+                                                num_packets, x.data_ptr(), int(x.stride(0)), int(x.stride(1)),
+                                                None if num_samples is None else num_samples.data_ptr(),
+                                                None if dz is None else C.byref(dz),
+                                                None if packet_origin is None else packet_origin.data_ptr(),
+                                                ws.data_ptr(), ws.numel(), fm.data_ptr(), st.data_ptr(), bad.data_ptr())
+            self._check(rc)
+            for v in (fm, st, bad):
+                v.record_stream(cur)
+            if num_samples is not None:
+                num_samples.record_stream(cur)
             return fm, st, bad
 
     # ---- stage level ------------------------------------------------------------------------

@@ -86,6 +86,21 @@ int32_t ALACDecoder::VerifyBatch(const uint8_t *stream, const uint32_t *packetBy
     return mLastStatus;
 }
 
+int32_t ALACDecoder::VerifyBatchFloat(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets, const float *in,
+                                      uint64_t channelStride, uint64_t frameStride, const uint32_t *numSamplesExpected,
+                                      uint32_t ditherMode, uint64_t ditherSeed, const uint64_t *packetOrigin,
+                                      uint32_t *firstMismatchOut, int32_t *statusOut, uint32_t *badPacketsOut)
+{
+    if (!mCtx || mCookie.empty() || !firstMismatchOut || !statusOut) return kALAC_ParamError;
+    const alac_hip_dither dither = {ditherMode, 0, ditherSeed};
+    const int32_t bad = alac_hip_verify_float_host(mCtx, mCookie.data(), (uint32_t)mCookie.size(), stream, packetBytes, numPackets,
+                                                   in, channelStride, frameStride, numSamplesExpected, &dither, packetOrigin,
+                                                   firstMismatchOut, statusOut);
+    mLastStatus = bad < 0 ? bad : ALAC_noErr;
+    if (bad >= 0 && badPacketsOut) *badPacketsOut = (uint32_t)bad;
+    return mLastStatus;
+}
+
 int32_t ALACDecoder::Decode(BitBuffer *bits, uint8_t *sampleBuffer, uint32_t /*numSamples*/, uint32_t numChannels,
                             uint32_t *outNumSamples)
 {

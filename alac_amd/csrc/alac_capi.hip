@@ -912,6 +912,26 @@ static const char *dither_refusal(const alac_hip_format *fmt, const alac_hip_dit
 }
 static bool dither_on(const alac_hip_dither *dither) { return dither && dither->mode == ALAC_HIP_DITHER_TPDF; }
 
+// host forms: the floats a call reads lie in [0, span) of h_in — up to the last frame a packet's count covers (counts
+// null: every packet frame_size frames).  The same strides then address the copy on the device.
+static int32_t float_host_span(alac_hip_ctx *ctx, const alac_hip_format *fmt, const uint32_t *h_num_samples, uint32_t np,
+                               uint64_t channel_stride, uint64_t frame_stride, uint64_t &span)
+{
+    const uint32_t fs = fmt->frame_size;
+    span = 0;
+    for (uint32_t p = 0; p < np; p++) {
+        const uint32_t n = h_num_samples && h_num_samples[p] < fs ? h_num_samples[p] : fs;
+        if (!n) continue;
+        uint64_t rows, cols, last;
+        if (__builtin_mul_overflow((uint64_t)(fmt->num_channels - 1), channel_stride, &rows) ||
+            __builtin_mul_overflow((uint64_t)p * fs + n - 1, frame_stride, &cols) || __builtin_add_overflow(rows, cols, &last) ||
+            last >= UINT64_MAX / sizeof(float))
+            return fail(ctx, ALAC_HIP_ParamError, "the largest index into h_in overflows 64 bits");
+        span = last + 1 > span ? last + 1 : span;
+    }
+    return ALAC_HIP_noErr;
+}
+
 // the conversion into the stage c.pcm, then the encode from it.  dither (checked, nullptr or mode NONE: plain rounding) is
 // read here; d_origin is the device table of the packets' stream frame indices or nullptr.
 static int32_t encode_float_run(alac_hip_ctx *ctx, const EncodeCall &c, const float *d_in, uint64_t channel_stride,
@@ -1197,20 +1217,46 @@ int32_t decode_impl(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs da
 // staging words, so a longer stream only needs a larger workspace here too.
 uint64_t verify_ns_bytes(uint32_t numPackets) { return align_up((uint64_t)numPackets * 4, 256); }
 
-// alac_hip_verify after its cookie: the decode pass of `da` in verify mode
+// the words of a verify-float call from its (checked) arguments; the buffers verify_impl knows are filled in there
+VerifyFloatArgs verify_float_args(uint64_t channel_stride, uint64_t frame_stride, const alac_hip_dither *dither,
+                                  const uint64_t *d_origin)
+{
+    VerifyFloatArgs vf = {};
+    vf.channelStride = channel_stride;
+    vf.frameStride = frame_stride;
+    if (dither_on(dither)) {
+        vf.dither = 1;
+        vf.dz.origin = d_origin;
+        philox_round_keys(dither->seed, vf.dz.roundKey);
+    }
+    return vf;
+}
+
+// alac_hip_verify after its cookie: the decode pass of `da` in verify mode — or, with vf, in verify-float mode
+// (alac_hip_verify_float after its own checks: da.pcmOut is the float source)
 int32_t verify_impl(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs da, uint32_t *d_first_mismatch,
-                    const uint32_t *d_num_samples_expected, void *d_workspace, uint64_t workspace_bytes, uint32_t *d_bad_packets)
+                    const uint32_t *d_num_samples_expected, void *d_workspace, uint64_t workspace_bytes, uint32_t *d_bad_packets,
+                    const VerifyFloatArgs *vf = nullptr)
 {
     const uint32_t num_packets = da.numPackets;
-    da.pcmMode = kPcmVerify;
-    da.firstMismatch = d_first_mismatch;
+    VerifyFloatArgs block;  // lives until the last launch of this call: the launchers pass it by value
+    if (vf) {
+        block = *vf;
+        block.firstMismatch = d_first_mismatch;
+        block.numSamplesExpected = d_num_samples_expected;
+        da.pcmMode = kPcmVerifyFloat;
+        da.verifyFloat = &block;
+    } else {
+        da.pcmMode = kPcmVerify;
+        da.firstMismatch = d_first_mismatch;
+    }
     if (!d_bad_packets) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
     if (num_packets == 0) {
         const hipError_t e = hipMemsetAsync(d_bad_packets, 0, 4, ctx->stream);
         return e == hipSuccess ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
     }
-    if (!da.stream || !da.offsets || !d_workspace || !da.pcmOut || !da.firstMismatch || !da.statusOut)
+    if (!da.stream || !da.offsets || !d_workspace || !da.pcmOut || !d_first_mismatch || !da.statusOut)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
     if (((uintptr_t)d_workspace & 255) || ((uintptr_t)da.pcmOut & 3)) return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
     const DecLayout L = dec_layout(&fmt, num_packets);
@@ -1218,13 +1264,26 @@ int32_t verify_impl(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs da
     if (workspace_bytes < nsBytes + L.total) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
     uint8_t *ws = (uint8_t *)d_workspace;
     da.numSamplesOut = (uint32_t *)ws;
-    hipError_t e = launch_verify_init(da.firstMismatch, num_packets, d_bad_packets, ctx->stream);
+    hipError_t e = launch_verify_init(d_first_mismatch, num_packets, d_bad_packets, ctx->stream);
     if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
     if (int32_t rc = decode_impl(ctx, fmt, da, ws + nsBytes, workspace_bytes - nsBytes)) return rc;
     e = launch_verify_finish(da.statusOut, da.numSamplesOut, d_num_samples_expected, fmt.frame_size, num_packets,
-                             da.firstMismatch, d_bad_packets, ctx->stream);
+                             d_first_mismatch, d_bad_packets, ctx->stream);
     if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
     return ALAC_HIP_noErr;
+}
+
+// alac_hip_verify_float's own refusals, device and host form: the dither struct, then (a call with packets) the source
+// pointer and the strides by the checks of alac_hip_encode_float
+int32_t verify_float_refusal(alac_hip_ctx *ctx, const alac_hip_format &fmt, uint32_t num_packets, const float *in,
+                             uint64_t channel_stride, uint64_t frame_stride, const alac_hip_dither *dither,
+                             const uint64_t *packet_origin)
+{
+    if (const char *why = dither_refusal(&fmt, dither, packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (!in) return fail(ctx, ALAC_HIP_ParamError, "null d_in");
+    if ((uintptr_t)in & 3) return fail(ctx, ALAC_HIP_ParamError, "misaligned d_in (4 B)");
+    return float_stride_refusal(ctx, &fmt, num_packets, channel_stride, frame_stride);
 }
 
 // The host forms of the decode calls after their own checks (bad != nullptr: verify).  Staged: the stream, its workspace, the
@@ -1234,8 +1293,11 @@ int32_t verify_impl(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs da
 int32_t decode_host_common(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs &da, const uint8_t *h_stream,
                            const uint32_t *h_packet_bytes, uint32_t num_packets, uint64_t pcmBytes, const void *h_expected,
                            const uint32_t *h_ns_expected, void *h_out, uint32_t rows, uint64_t pitch, uint32_t *h_ns_out,
-                           uint32_t *h_fm, uint32_t *bad, int32_t *h_status)
+                           uint32_t *h_fm, uint32_t *bad, int32_t *h_status, const VerifyFloatArgs *vf = nullptr,
+                           const uint64_t *h_origin = nullptr)
 {
+    // vf (verify-float): h_expected is the float source, pcmBytes what of it the call may read, h_origin (nullable) the
+    // packets' stream frame indices
     const bool verify = bad != nullptr;
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
     const uint64_t n4 = num_packets * 4ull;
@@ -1244,11 +1306,13 @@ int32_t decode_host_common(alac_hip_ctx *ctx, const alac_hip_format &fmt, Decode
     if (int32_t rc = upload_stream(h_stream, h_packet_bytes, num_packets, st, d, on_fail(ctx))) return rc;
     const uint64_t wsBytes = (verify ? alac_hip_verify_workspace_bytes_stream : alac_hip_decode_workspace_bytes_stream)(
         &fmt, num_packets, d.total);
-    DevBuf dWs, dPcm, dNs, dSt, dFm, dBad;
+    DevBuf dWs, dPcm, dNs, dSt, dFm, dBad, dOrigin;
     hipError_t e;
     if ((e = dWs.alloc(wsBytes)) || (e = dPcm.alloc(pcmBytes)) || (e = dNs.alloc(n4)) || (e = dSt.alloc(n4)) ||
-        (verify && ((e = dFm.alloc(n4)) || (e = dBad.alloc(4)))))
+        (verify && ((e = dFm.alloc(n4)) || (e = dBad.alloc(4)))) || (h_origin && (e = dOrigin.alloc(num_packets * 8ull))))
         return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if (h_origin && (e = hipMemcpyAsync(dOrigin.p, h_origin, num_packets * 8ull, hipMemcpyHostToDevice, st)))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
     if ((e = verify ? hipMemcpyAsync(dPcm.p, h_expected, pcmBytes, hipMemcpyHostToDevice, st)
                     : hipMemsetAsync(dPcm.p, 0, pcmBytes, st)) ||
         (h_ns_expected && (e = hipMemcpyAsync(dNs.p, h_ns_expected, n4, hipMemcpyHostToDevice, st))))
@@ -1257,7 +1321,13 @@ int32_t decode_host_common(alac_hip_ctx *ctx, const alac_hip_format &fmt, Decode
                    (int32_t *)dSt.p);
     if (verify) {
         const uint32_t *ns = h_ns_expected ? (const uint32_t *)dNs.p : nullptr;
-        if (int32_t rc = verify_impl(ctx, fmt, da, (uint32_t *)dFm.p, ns, dWs.p, wsBytes, (uint32_t *)dBad.p)) return rc;
+        VerifyFloatArgs block;
+        if (vf) {
+            block = *vf;
+            block.dz.origin = h_origin ? (const uint64_t *)dOrigin.p : nullptr;
+        }
+        if (int32_t rc = verify_impl(ctx, fmt, da, (uint32_t *)dFm.p, ns, dWs.p, wsBytes, (uint32_t *)dBad.p, vf ? &block : nullptr))
+            return rc;
         if (!(e = hipMemcpyAsync(bad, dBad.p, 4, hipMemcpyDeviceToHost, st)) && h_fm)
             e = hipMemcpyAsync(h_fm, dFm.p, n4, hipMemcpyDeviceToHost, st);
     } else {
@@ -1325,6 +1395,23 @@ int32_t alac_hip_verify(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t coo
     if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
     decode_buffers(da, d_stream, d_packet_offsets, num_packets, d_pcm_expected, nullptr, d_status);
     return verify_impl(ctx, fmt, da, d_first_mismatch, d_num_samples_expected, d_workspace, workspace_bytes, d_bad_packets);
+}
+
+// ---- verify against the float32 source of alac_hip_encode_float / _dither: the store sites compare through the rule ----
+int32_t alac_hip_verify_float(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
+                              const uint64_t *d_packet_offsets, uint32_t num_packets, const float *d_in,
+                              uint64_t channel_stride, uint64_t frame_stride, const uint32_t *d_num_samples_expected,
+                              const alac_hip_dither *dither, const uint64_t *d_packet_origin, void *d_workspace,
+                              uint64_t workspace_bytes, uint32_t *d_first_mismatch, int32_t *d_status, uint32_t *d_bad_packets)
+{
+    alac_hip_format fmt;
+    DecodeArgs da;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
+    if (int32_t rc = verify_float_refusal(ctx, fmt, num_packets, d_in, channel_stride, frame_stride, dither, d_packet_origin))
+        return rc;
+    decode_buffers(da, d_stream, d_packet_offsets, num_packets, d_in, nullptr, d_status);
+    const VerifyFloatArgs vf = verify_float_args(channel_stride, frame_stride, dither, d_packet_origin);
+    return verify_impl(ctx, fmt, da, d_first_mismatch, d_num_samples_expected, d_workspace, workspace_bytes, d_bad_packets, &vf);
 }
 
 // ---- stage level ---------------------------------------------------------------------------------
@@ -1451,20 +1538,9 @@ int32_t alac_hip_encode_float_dither_host(alac_hip_ctx *ctx, const alac_hip_form
     if (!h_in || !h_out || !h_packet_bytes || !h_num_samples || !h_seg_first || num_segments == 0)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
     if (int32_t rc = host_segment_refusal(ctx, h_seg_first, num_segments, num_packets)) return rc;
-    const uint32_t np = num_packets, nseg = num_segments, fs = fmt->frame_size;
-    // the floats the conversion reads lie in [0, span): up to the last frame a packet's num_samples covers.  The same
-    // strides then address the copy on the device.
+    const uint32_t np = num_packets, nseg = num_segments;
     uint64_t span = 0;
-    for (uint32_t p = 0; p < np; p++) {
-        const uint32_t n = h_num_samples[p] < fs ? h_num_samples[p] : fs;
-        if (!n) continue;
-        uint64_t rows, cols, last;
-        if (__builtin_mul_overflow((uint64_t)(fmt->num_channels - 1), channel_stride, &rows) ||
-            __builtin_mul_overflow((uint64_t)p * fs + n - 1, frame_stride, &cols) || __builtin_add_overflow(rows, cols, &last) ||
-            last >= UINT64_MAX / sizeof(float))
-            return fail(ctx, ALAC_HIP_ParamError, "the largest index into h_in overflows 64 bits");
-        span = last + 1 > span ? last + 1 : span;
-    }
+    if (int32_t rc = float_host_span(ctx, fmt, h_num_samples, np, channel_stride, frame_stride, span)) return rc;
     if (int32_t rc = float_stride_refusal(ctx, fmt, np, channel_stride, frame_stride)) return rc;
     if (int32_t rc = encode_refusal(ctx, fmt, np, ctx->opt.lpc ? np : nseg, nullptr, 0, 0)) return rc;
     const uint64_t wsBytes = alac_hip_encode_float_workspace_bytes(fmt, np, ctx->opt.lpc ? np : nseg);
@@ -1581,6 +1657,32 @@ int32_t alac_hip_verify_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_
     uint32_t bad = 0;
     const int32_t rc = decode_host_common(ctx, fmt, da, h_stream, h_packet_bytes, num_packets, pcmBytes, h_pcm_expected,
                                           h_num_samples_expected, nullptr, 1, 0, nullptr, h_first_mismatch, &bad, h_status);
+    return rc != ALAC_HIP_noErr ? rc : (int32_t)bad;
+}
+
+int32_t alac_hip_verify_float_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *h_stream,
+                                   const uint32_t *h_packet_bytes, uint32_t num_packets, const float *h_in,
+                                   uint64_t channel_stride, uint64_t frame_stride, const uint32_t *h_num_samples_expected,
+                                   const alac_hip_dither *dither, const uint64_t *h_packet_origin, uint32_t *h_first_mismatch,
+                                   int32_t *h_status)
+{
+    alac_hip_format fmt;
+    DecodeArgs da;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
+    if (int32_t rc = verify_float_refusal(ctx, fmt, num_packets, h_in, channel_stride, frame_stride, dither, h_packet_origin))
+        return rc;
+    if (num_packets == 0) return 0;
+    if (!h_stream || !h_packet_bytes) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if (num_packets > 0x7fffffffu) return fail(ctx, ALAC_HIP_ParamError, "more packets than the return value counts");
+    uint64_t span = 0;
+    if (int32_t rc = float_host_span(ctx, &fmt, h_num_samples_expected, num_packets, channel_stride, frame_stride, span)) return rc;
+    // nothing expected anywhere: one float the kernels never load keeps the staged source a buffer
+    static const float kNone = 0.0f;
+    const VerifyFloatArgs vf = verify_float_args(channel_stride, frame_stride, dither, nullptr);
+    uint32_t bad = 0;
+    const int32_t rc = decode_host_common(ctx, fmt, da, h_stream, h_packet_bytes, num_packets, (span ? span : 1) * sizeof(float),
+                                          span ? h_in : &kNone, h_num_samples_expected, nullptr, 1, 0, nullptr, h_first_mismatch,
+                                          &bad, h_status, &vf, dither_on(dither) ? h_packet_origin : nullptr);
     return rc != ALAC_HIP_noErr ? rc : (int32_t)bad;
 }
 

@@ -296,7 +296,7 @@ __device__ __forceinline__ void store_sample(const DecodeArgs &A, uint8_t *p, in
 }
 
 template <int DEPTH, int CH, PcmMode MODE>
-__global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A)
+__global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A, VerifyFloatArgs F)
 {
     if (A.gate && *A.gate == 0) return;
     __shared__ int32_t tu[64][65];
@@ -353,9 +353,10 @@ __global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A)
             l = (int32_t)(((uint32_t)l << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
             if constexpr (CH == 2) r = (int32_t)(((uint32_t)r << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
         }
-        if constexpr (MODE == kPcmFloat) {
-            pcm_float_row(A, 0, p)[j] = pcm_float<DEPTH>(l);
-            if constexpr (CH == 2) pcm_float_row(A, 1, p)[j] = pcm_float<DEPTH>(r);
+        if constexpr (pcm_is_float(MODE)) {
+            const uint32_t lim = pcm_frames<MODE>(A, F, p, rec->numSamples);
+            pcm_float_put<DEPTH, MODE>(A, F, 0, p, j, lim, l);
+            if constexpr (CH == 2) pcm_float_put<DEPTH, MODE>(A, F, 1, p, j, lim, r);
         } else {
             store_sample<DEPTH, MODE>(A, op, l);
             if constexpr (CH == 2) store_sample<DEPTH, MODE>(A, op + BPS, r);
@@ -369,7 +370,7 @@ __global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A)
 // written at channel c (and c + 1) of the numChannels-interleaved frame (unmixNN / copyPredictorToNN with stride
 // numChannels, codec/ALACDecoder.cu:733-753,:900-935); channels no element carries are zero (:971-998).
 template <int DEPTH, PcmMode MODE>
-__global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A)
+__global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A, VerifyFloatArgs F)
 {
     if (A.gate && *A.gate == 0) return;
     __shared__ int32_t tu[64][65];
@@ -403,7 +404,7 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A)
             if (!rec) {
                 const uint32_t ns = A.recs[p].elementChannels ? A.recs[p].numSamples : A.frameSize;
                 if (j < ns) {
-                    if constexpr (MODE == kPcmFloat) pcm_float_row(A, c, p)[j] = 0.0f;
+                    if constexpr (pcm_is_float(MODE)) pcm_float_put<DEPTH, MODE>(A, F, c, p, j, pcm_frames<MODE>(A, F, p, ns), 0);
                     else store_sample<DEPTH, MODE>(A, op, 0);
                 }
                 continue;
@@ -426,9 +427,10 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A)
                 l = (int32_t)(((uint32_t)l << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
                 if (ech == 2) r = (int32_t)(((uint32_t)r << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
             }
-            if constexpr (MODE == kPcmFloat) {
-                pcm_float_row(A, c, p)[j] = pcm_float<DEPTH>(l);
-                if (ech == 2) pcm_float_row(A, c + 1, p)[j] = pcm_float<DEPTH>(r);
+            if constexpr (pcm_is_float(MODE)) {
+                const uint32_t lim = pcm_frames<MODE>(A, F, p, rec->numSamples);
+                pcm_float_put<DEPTH, MODE>(A, F, c, p, j, lim, l);
+                if (ech == 2) pcm_float_put<DEPTH, MODE>(A, F, c + 1, p, j, lim, r);
             } else {
                 store_sample<DEPTH, MODE>(A, op, l);
                 if (ech == 2) store_sample<DEPTH, MODE>(A, op + BPS, r);
@@ -442,17 +444,19 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A)
 template <int DEPTH, PcmMode MODE>
 static void launch_unmix_depth(const DecodeArgs &da, hipStream_t st)
 {
+    const VerifyFloatArgs vf = MODE == kPcmVerifyFloat ? *da.verifyFloat : VerifyFloatArgs{};
     dim3 grid((da.numPackets + 63) / 64, (da.frameSize + 63) / 64);
     if (da.gate) grid = dim3((uint32_t)std::min<uint64_t>((uint64_t)grid.x * grid.y, 2048), 1);  // (see k_decode_unmix)
     // two channels may arrive as one CPE or as two SCE / LFE elements (codec/ALACDecoder.cu:622-756): the per-element
     // kernel follows the records, k_decode_unmix<., 2> would take the packet for one pair
     if (da.numChannels >= 2)
-        hipLaunchKernelGGL((k_decode_unmix_mc<DEPTH, MODE>), grid, dim3(256), 0, st, da);
+        hipLaunchKernelGGL((k_decode_unmix_mc<DEPTH, MODE>), grid, dim3(256), 0, st, da, vf);
     else
-        hipLaunchKernelGGL((k_decode_unmix<DEPTH, 1, MODE>), grid, dim3(256), 0, st, da);
+        hipLaunchKernelGGL((k_decode_unmix<DEPTH, 1, MODE>), grid, dim3(256), 0, st, da, vf);
 }
 
-// MODE: the un-mix instantiations whose store sites store, compare or write planar floats (alac_verify.hpp)
+// MODE: the un-mix instantiations whose store sites store, compare, write planar floats or compare with a float source
+// (alac_verify.hpp)
 template <PcmMode MODE>
 static hipError_t launch_decode_lanes(const DecodeArgs &da, hipStream_t st)
 {
@@ -476,6 +480,7 @@ hipError_t launch_decode(const DecodeArgs &da, hipStream_t st)
     case kPcmStore: return launch_decode_lanes<kPcmStore>(da, st);
     case kPcmVerify: return launch_decode_lanes<kPcmVerify>(da, st);   // alac_hip_verify
     case kPcmFloat: return launch_decode_lanes<kPcmFloat>(da, st);     // alac_hip_decode_float
+    case kPcmVerifyFloat: return launch_decode_lanes<kPcmVerifyFloat>(da, st);  // alac_hip_verify_float
     default: return hipErrorInvalidValue;
     }
 }

@@ -501,7 +501,7 @@ __global__ __launch_bounds__(64 * kHdrWaves) void k_dec_header(DecV1Args V)
 // ---- k_dec_raw: uncompressed (escape) elements are fixed-width fields, i.e. not serial at all: one thread per
 // sample-frame reads its fields straight from the staged words (codec/ALACDecoder.cu:697-727 / :856-896)
 template <bool DIRECT, PcmMode MODE>
-__device__ __forceinline__ void raw_body(const DecV1Args &V, uint32_t p, uint32_t first, uint32_t step)
+__device__ __forceinline__ void raw_body(const DecV1Args &V, const VerifyFloatArgs &F, uint32_t p, uint32_t first, uint32_t step)
 {
     const DecodeArgs &A = V.d;
     const DecRec *rec = A.recs + p;
@@ -516,6 +516,7 @@ __device__ __forceinline__ void raw_body(const DecV1Args &V, uint32_t p, uint32_
     // written here as one word per frame instead of going through the plane and k_dec_unmix
     const bool direct = rec->pad2 != 0;
     uint32_t *pcm = (uint32_t *)(A.pcmOut + (uint64_t)p * A.frameSize * 4);
+    const uint32_t lim = pcm_frames<MODE>(A, F, p, n);  // float branches: the frames they may touch
     // four sample-frames per round, every load of the round issued before its first store: the loop is bound by the
     // chain of dependent round trips per wave, not by bytes (an iteration per frame took 1.24 ms for the 15 600 escape
     // packets of the 125 000-packet benchmark)
@@ -547,7 +548,7 @@ __device__ __forceinline__ void raw_body(const DecV1Args &V, uint32_t p, uint32_
                 const uint32_t v = (uint32_t)(((((uint64_t)x[k] << 32) | x[k + 1]) << s) >> 32);
                 o[k] = (v >> 16) | (v << 16);
             }
-            if constexpr (MODE == kPcmFloat) {
+            if constexpr (pcm_is_float(MODE)) {
                 // the four frames' L (high halves of v) and R (low halves), one 16-byte store per channel
                 int32_t fl[4], fr[4];
 #pragma unroll
@@ -555,8 +556,8 @@ __device__ __forceinline__ void raw_body(const DecV1Args &V, uint32_t p, uint32_
                     fl[k] = (int32_t)(o[k] & 0xffffu);
                     fr[k] = (int32_t)(o[k] >> 16);
                 }
-                pcm_float_run<16>(pcm_float_row(A, 0, p), 4 * g, n, fl);
-                pcm_float_run<16>(pcm_float_row(A, 1, p), 4 * g, n, fr);
+                pcm_float_run<16, MODE>(A, F, 0, p, 4 * g, lim, fl);
+                pcm_float_run<16, MODE>(A, F, 1, p, 4 * g, lim, fr);
             } else {
                 const U4 t4 = {o[0], o[1], o[2], o[3]};
                 PCM_PUT(MODE, A, (U4 *)(pcm + 4 * (uint64_t)g), t4);
@@ -591,10 +592,10 @@ __device__ __forceinline__ void raw_body(const DecV1Args &V, uint32_t p, uint32_
                     if (!direct) (rowU + c * A.frameSize)[j] = (int32_t)(v << (32 - w)) >> (32 - w);
                 }
             }
-            if constexpr (MODE == kPcmFloat) {
+            if constexpr (pcm_is_float(MODE)) {
                 if (direct && j < n) {  // direct: 16-bit fields (pad2)
-                    pcm_float_row(A, 0, p)[j] = pcm_float<16>((int32_t)f[0]);
-                    pcm_float_row(A, 1, p)[j] = pcm_float<16>((int32_t)f[1]);
+                    pcm_float_put<16, MODE>(A, F, 0, p, j, lim, (int32_t)f[0]);
+                    pcm_float_put<16, MODE>(A, F, 1, p, j, lim, (int32_t)f[1]);
                 }
             } else {
                 if (direct && j < n) PCM_PUT(MODE, A, pcm + j, f[0] | (f[1] << 16));
@@ -611,14 +612,14 @@ __device__ __host__ inline uint32_t blocks_per_packet(uint32_t frameSize) { retu
 // 500 000 workgroups at 125 000 packets, 15 600 of them with work.
 // (round 3: the packets come from k_dec_header's list of uncompressed elements, so nobody reads records to find them)
 template <PcmMode MODE>
-__global__ __launch_bounds__(256) void k_dec_raw(DecV1Args V)
+__global__ __launch_bounds__(256) void k_dec_raw(DecV1Args V, VerifyFloatArgs F)
 {
     const DecLists L = dec_lists(V);
     const uint32_t count = L.cnt[4];
     if (V.raw) {  // wave-uniform
-        for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) raw_body<true, MODE>(V, L.raw[i], threadIdx.x, blockDim.x);
+        for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) raw_body<true, MODE>(V, F, L.raw[i], threadIdx.x, blockDim.x);
     } else {
-        for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) raw_body<false, MODE>(V, L.raw[i], threadIdx.x, blockDim.x);
+        for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) raw_body<false, MODE>(V, F, L.raw[i], threadIdx.x, blockDim.x);
     }
 }
 
@@ -1544,7 +1545,7 @@ __device__ __forceinline__ int32_t lms_step_dec_pair(int32_t (&a)[T], int32_t (&
 }
 
 template <int T, int DEPTH = 16, PcmMode MODE = kPcmStore>
-__device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t block, uint32_t count)
+__device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, const VerifyFloatArgs &F, uint32_t block, uint32_t count)
 {
     const DecodeArgs &A = V.d;
     if (block * 32u >= count) return;
@@ -1555,6 +1556,7 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
     const DecRec *rec = A.recs + p;
     const bool active = idx < count && rec->status == 0;  // a packet the entropy lane gave up on keeps its PCM untouched
     const uint32_t n = active ? rec->numSamples : 0;
+    const uint32_t lim = pcm_frames<MODE>(A, F, p, n);  // float branches: the frames they may touch
     const uint32_t chanbits = A.bitDepth - (active ? rec->bytesShifted : 0) * 8 + 1;
     const bool is4 = T == 4 || !active || rec->c[ch].num == 4;
     const int32_t act = is4 ? 0 : -1;
@@ -1610,11 +1612,11 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
                         l = (int32_t)(((uint32_t)l << 8) | (xx >> 8));
                         r = (int32_t)(((uint32_t)r << 8) | (xx & 0xffu));
                     }
-                } else if constexpr (MODE != kPcmFloat) {
+                } else if constexpr (!pcm_is_float(MODE)) {
                     l = (int32_t)((uint32_t)l << 4);  // 20 bits, left-justified in three bytes (gpu_unmix20 :225-280)
                     r = (int32_t)((uint32_t)r << 4);
                 }
-                if constexpr (MODE == kPcmFloat) {
+                if constexpr (pcm_is_float(MODE)) {
                     fl[k] = l;
                     fr[k] = r;
                 } else {
@@ -1623,11 +1625,11 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
                 }
             }
             uint8_t *dst = pcm3 + (uint64_t)f0 * 6;
-            if constexpr (MODE == kPcmFloat) {
+            if constexpr (pcm_is_float(MODE)) {
                 // K / 2 frames of each channel: 16-byte stores, the last frames of a short packet one by one
                 if (active) {
-                    pcm_float_run<DEPTH>(pcm_float_row(A, 0, p), f0, n, fl);
-                    pcm_float_run<DEPTH>(pcm_float_row(A, 1, p), f0, n, fr);
+                    pcm_float_run<DEPTH, MODE>(A, F, 0, p, f0, lim, fl);
+                    pcm_float_run<DEPTH, MODE>(A, F, 1, p, f0, lim, fr);
                 }
             } else if (active && f0 + (uint32_t)(K / 2) <= n) {
                 // four 3-byte fields make three words; K fields = 3 K / 4 words = 3 K / 16 sixteen-byte stores
@@ -1672,7 +1674,7 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
             const int32_t uu = isU ? mine : recv, vv = isU ? recv : mine;
             const int32_t l = uu + ((vv - ((mixRes * vv) >> mixBits)) & mixMask);
             const int32_t r = mixRes != 0 ? l - vv : vv;
-            if constexpr (MODE == kPcmFloat) {
+            if constexpr (pcm_is_float(MODE)) {
                 fl[k] = l;
                 fr[k] = r;
             } else {
@@ -1680,10 +1682,10 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
             }
         }
         const uint32_t f0 = jb + (isU ? 0u : (uint32_t)(K / 2));
-        if constexpr (MODE == kPcmFloat) {
+        if constexpr (pcm_is_float(MODE)) {
             if (active) {
-                pcm_float_run<16>(pcm_float_row(A, 0, p), f0, n, fl);
-                pcm_float_run<16>(pcm_float_row(A, 1, p), f0, n, fr);
+                pcm_float_run<16, MODE>(A, F, 0, p, f0, lim, fl);
+                pcm_float_run<16, MODE>(A, F, 1, p, f0, lim, fr);
             }
         } else {
 #pragma unroll
@@ -1773,17 +1775,17 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, uint32_t bloc
 // DEPTH: what the pairs write (16: one word per frame; 20 / 24: six bytes per frame) — one instantiation per output format,
 // so that a launch carries four loop bodies, not eight (they share the CU's instruction cache)
 template <int DEPTH, PcmMode MODE>
-__global__ __launch_bounds__(64 * kEntWavesPerWg) void k_dec_unpc_wide(DecV1Args V)
+__global__ __launch_bounds__(64 * kEntWavesPerWg) void k_dec_unpc_wide(DecV1Args V, VerifyFloatArgs F)
 {
     const uint32_t *cnt = dec_lists(V).cnt;
     const uint32_t c4 = cnt[0], c8 = cnt[1], pA = cnt[2], pB = cnt[3], cAny = cnt[6];
     const uint32_t nbB = (pB + 31u) / 32u, nb8 = (c8 + 63u) / 64u, nbA = (pA + 31u) / 32u, nb4 = (c4 + 63u) / 64u;
     uint32_t b = blockIdx.x * (uint32_t)kEntWavesPerWg + (threadIdx.x >> 6);
-    if (b < nbB) return unpc_pair_body<8, DEPTH, MODE>(V, b, pB);
+    if (b < nbB) return unpc_pair_body<8, DEPTH, MODE>(V, F, b, pB);
     b -= nbB;
     if (b < nb8) return unpc_wide_body<8>(V, b, c8);
     b -= nb8;
-    if (b < nbA) return unpc_pair_body<4, DEPTH, MODE>(V, b, pA);
+    if (b < nbA) return unpc_pair_body<4, DEPTH, MODE>(V, F, b, pA);
     b -= nbA;
     if (b < nb4) return unpc_wide_body<4>(V, b, c4);
     b -= nb4;
@@ -1799,7 +1801,7 @@ __global__ __launch_bounds__(64 * kEntWavesPerWg) void k_dec_unpc_wide(DecV1Args
 // elements (nobody waits for them; their dispatch hides under the entropy chain instead of costing a launch of its own).
 constexpr int kFusedPpw = 48;
 template <PcmMode MODE>
-__global__ __launch_bounds__(256, 1) void k_dec_fused_wg(DecV1Args V, uint32_t nEnt)
+__global__ __launch_bounds__(256, 1) void k_dec_fused_wg(DecV1Args V, uint32_t nEnt, VerifyFloatArgs F)
 {
     __shared__ uint32_t ringOne[64 * kWinStride];
     __shared__ uint32_t progLds[kFusedPpw * 2];
@@ -1813,7 +1815,7 @@ __global__ __launch_bounds__(256, 1) void k_dec_fused_wg(DecV1Args V, uint32_t n
             unpc_fast_body<true, kFusedPpw>(V, blockIdx.x * 3u + (slot - 1), progLds);
     } else {
         const uint32_t p = (blockIdx.x - nEnt) * 4u + slot;
-        if (p < V.d.numPackets) raw_body<false, MODE>(V, p, threadIdx.x & 63, 64);
+        if (p < V.d.numPackets) raw_body<false, MODE>(V, F, p, threadIdx.x & 63, 64);
     }
 }
 
@@ -1852,7 +1854,7 @@ __device__ __forceinline__ void put_sample(const DecodeArgs &A, uint8_t *q, int3
 }
 
 template <int DEPTH, int CH, PcmMode MODE>
-__device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint32_t part, uint32_t bx)
+__device__ __forceinline__ void unmix_part(const DecV1Args &V, const VerifyFloatArgs &F, uint32_t p, uint32_t part, uint32_t bx)
 {
     const DecodeArgs &A = V.d;
     const DecRec *rec = A.recs + p;
@@ -1860,6 +1862,7 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
     // element rounds: a packet that ended before this element leaves these channels zero (codec/ALACDecoder.cu:971-998)
     const bool absent = V.elemBit && rec->elementChannels == 0;
     const uint32_t n = absent ? (V.round ? A.numSamplesOut[p] : A.frameSize) : rec->numSamples;
+    const uint32_t lim = pcm_frames<MODE>(A, F, p, n);  // float branches: the frames they may touch
     const uint32_t shb = absent ? 0 : rec->bytesShifted;
     const int32_t mixRes = rec->mixRes, mixBits = rec->mixBits;
     const int32_t *u = V.plane + (uint64_t)p * CH * A.frameSize;
@@ -1889,16 +1892,16 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
                         l = uu[k];
                         r = vv[k];
                     }
-                    if constexpr (MODE == kPcmFloat) {
+                    if constexpr (pcm_is_float(MODE)) {
                         fl[k] = l;
                         fr[k] = r;
                     } else {
                         o[k] = ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16);
                     }
                 }
-                if constexpr (MODE == kPcmFloat) {
-                    pcm_float_run<16>(pcm_float_row(A, V.outFirst, p), j, n4, fl);
-                    pcm_float_run<16>(pcm_float_row(A, V.outFirst + 1, p), j, n4, fr);
+                if constexpr (pcm_is_float(MODE)) {
+                    pcm_float_run<16, MODE>(A, F, V.outFirst, p, j, pcm_clamp<MODE>(n4, lim), fl);
+                    pcm_float_run<16, MODE>(A, F, V.outFirst + 1, p, j, pcm_clamp<MODE>(n4, lim), fr);
                 } else {
                     PCM_PUT(MODE, A, (U4 *)(out + (uint64_t)j * 4), o);
                 }
@@ -1914,9 +1917,9 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
                     l = uu;
                     r = vv;
                 }
-                if constexpr (MODE == kPcmFloat) {
-                    pcm_float_row(A, V.outFirst, p)[j] = pcm_float<16>(l);
-                    pcm_float_row(A, V.outFirst + 1, p)[j] = pcm_float<16>(r);
+                if constexpr (pcm_is_float(MODE)) {
+                    pcm_float_put<16, MODE>(A, F, V.outFirst, p, j, lim, l);
+                    pcm_float_put<16, MODE>(A, F, V.outFirst + 1, p, j, lim, r);
                 } else {
                     PCM_PUT(MODE, A, (uint32_t *)(out + (uint64_t)j * 4), ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16));
                 }
@@ -1967,7 +1970,7 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
                         l = (int32_t)(((uint32_t)l << 8) | ((xx >> 8) & 0xffu));
                         r = (int32_t)(((uint32_t)r << 8) | (xx & 0xffu));
                     }
-                    if constexpr (MODE == kPcmFloat) {
+                    if constexpr (pcm_is_float(MODE)) {
                         fl[k] = l;
                         fr[k] = r;
                         continue;
@@ -1979,9 +1982,9 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
                     s[2 * k] = (uint32_t)l & 0xffffffu;
                     s[2 * k + 1] = (uint32_t)r & 0xffffffu;
                 }
-                if constexpr (MODE == kPcmFloat) {
-                    pcm_float_run<DEPTH>(pcm_float_row(A, V.outFirst, p), j, n4, fl);
-                    pcm_float_run<DEPTH>(pcm_float_row(A, V.outFirst + 1, p), j, n4, fr);
+                if constexpr (pcm_is_float(MODE)) {
+                    pcm_float_run<DEPTH, MODE>(A, F, V.outFirst, p, j, pcm_clamp<MODE>(n4, lim), fl);
+                    pcm_float_run<DEPTH, MODE>(A, F, V.outFirst + 1, p, j, pcm_clamp<MODE>(n4, lim), fr);
                 } else {
                     // four 3-byte fields make three words
                     U2 *q = (U2 *)(out + (uint64_t)j * 6);
@@ -2025,9 +2028,9 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
             l = (int32_t)(((uint32_t)l << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
             if constexpr (CH == 2) r = (int32_t)(((uint32_t)r << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
         }
-        if constexpr (MODE == kPcmFloat) {
-            pcm_float_row(A, V.outFirst, p)[j] = pcm_float<DEPTH>(l);
-            if constexpr (CH == 2) pcm_float_row(A, V.outFirst + 1, p)[j] = pcm_float<DEPTH>(r);
+        if constexpr (pcm_is_float(MODE)) {
+            pcm_float_put<DEPTH, MODE>(A, F, V.outFirst, p, j, lim, l);
+            if constexpr (CH == 2) pcm_float_put<DEPTH, MODE>(A, F, V.outFirst + 1, p, j, lim, r);
         } else {
             uint8_t *q = out + (uint64_t)j * och * BPS;
             if (DEPTH == 16 && CH == 2 && och == 2) {
@@ -2044,27 +2047,27 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, uint32_t p, uint3
 // packets nobody else writes (with pairs and direct uncompressed elements that is none of the benchmark's packets; launching
 // a workgroup per packet just to read a record and leave cost 0.5 ms at 125 000 packets).
 template <int DEPTH, int CH, PcmMode MODE>
-__global__ __launch_bounds__(256) void k_dec_unmix(DecV1Args V)
+__global__ __launch_bounds__(256) void k_dec_unmix(DecV1Args V, VerifyFloatArgs F)
 {
     const uint32_t bx = blocks_per_packet(V.d.frameSize);
     if (!V.lists) {
-        unmix_part<DEPTH, CH, MODE>(V, blockIdx.x / bx, blockIdx.x % bx, bx);
+        unmix_part<DEPTH, CH, MODE>(V, F, blockIdx.x / bx, blockIdx.x % bx, bx);
         return;
     }
     const DecLists L = dec_lists(V);
     const uint64_t work = (uint64_t)L.cnt[5] * bx;
-    for (uint64_t i = blockIdx.x; i < work; i += gridDim.x) unmix_part<DEPTH, CH, MODE>(V, L.rest[i / bx], (uint32_t)(i % bx), bx);
+    for (uint64_t i = blockIdx.x; i < work; i += gridDim.x) unmix_part<DEPTH, CH, MODE>(V, F, L.rest[i / bx], (uint32_t)(i % bx), bx);
 }
 
 template <int DEPTH, PcmMode MODE>
-static void launch_unmix_v1(const DecV1Args &V, hipStream_t st)
+static void launch_unmix_v1(const DecV1Args &V, const VerifyFloatArgs &vf, hipStream_t st)
 {
     const uint64_t all = (uint64_t)blocks_per_packet(V.d.frameSize) * V.d.numPackets;
     dim3 grid((uint32_t)(V.lists && all > 8192 ? 8192 : all));
     if (V.d.numChannels == 2)
-        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 2, MODE>), grid, dim3(256), 0, st, V);
+        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 2, MODE>), grid, dim3(256), 0, st, V, vf);
     else
-        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 1, MODE>), grid, dim3(256), 0, st, V);
+        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 1, MODE>), grid, dim3(256), 0, st, V, vf);
 }
 
 // one pass of the pipeline over the elements V describes, after the staging of the stream (stageFirst: the pass stages it
@@ -2075,6 +2078,8 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stage
 {
     DecV1Args V = V0;
     const DecodeArgs &da = V.d;
+    // verify-float mode: its words, the last argument of every kernel that writes PCM (the other modes pass an empty block)
+    const VerifyFloatArgs vf = MODE == kPcmVerifyFloat ? *da.verifyFloat : VerifyFloatArgs{};
     const uint64_t planeBytes = (uint64_t)da.numPackets * da.numChannels * da.frameSize * 4;
     // One launch (entropy lanes followed by the predictor waves, producer/consumer through HBM) where the chains are few
     // enough that a stage is as slow as its longest serial chain; separate launches where every kernel fills the machine by
@@ -2128,9 +2133,9 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stage
     const uint32_t nEnt = (da.numPackets + 63) / 64;
     if (fused) {
         const uint32_t nEntWg = (da.numPackets + kFusedPpw - 1) / kFusedPpw;
-        hipLaunchKernelGGL(k_dec_fused_wg<MODE>, dim3(nEntWg + (da.numPackets + 3) / 4), dim3(256), 0, st, V, nEntWg);
+        hipLaunchKernelGGL(k_dec_fused_wg<MODE>, dim3(nEntWg + (da.numPackets + 3) / 4), dim3(256), 0, st, V, nEntWg, vf);
     } else {
-        hipLaunchKernelGGL(k_dec_raw<MODE>, dim3(da.numPackets < 4096u ? da.numPackets : 4096u), dim3(256), 0, st, V);
+        hipLaunchKernelGGL(k_dec_raw<MODE>, dim3(da.numPackets < 4096u ? da.numPackets : 4096u), dim3(256), 0, st, V, vf);
         // deferred residual stores, four 16-byte stores per round of sixteen consecutive residuals (round 2, 4-byte stores:
         // paid only up to two entropy waves per SIMD; with the wide stores, measured whole decode pass at 125 000 / 250 000 /
         // 500 000 packets: 9.31 -> 8.19, 19.4 -> 14.2, 38.1 -> 26.5 ms — the kernel was bound by the number of store
@@ -2142,16 +2147,16 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stage
         // chains sorted by tap count, one lane per chain
         // (five lists, each rounded up to whole waves)
         const dim3 ugrid(((uint32_t)((lanes + 63) / 64) + 6 + kEntWavesPerWg - 1) / kEntWavesPerWg), ublock(64 * kEntWavesPerWg);
-        if (da.bitDepth == 24) hipLaunchKernelGGL((k_dec_unpc_wide<24, MODE>), ugrid, ublock, 0, st, V);
-        else if (da.bitDepth == 20) hipLaunchKernelGGL((k_dec_unpc_wide<20, MODE>), ugrid, ublock, 0, st, V);
-        else hipLaunchKernelGGL((k_dec_unpc_wide<16, MODE>), ugrid, ublock, 0, st, V);
+        if (da.bitDepth == 24) hipLaunchKernelGGL((k_dec_unpc_wide<24, MODE>), ugrid, ublock, 0, st, V, vf);
+        else if (da.bitDepth == 20) hipLaunchKernelGGL((k_dec_unpc_wide<20, MODE>), ugrid, ublock, 0, st, V, vf);
+        else hipLaunchKernelGGL((k_dec_unpc_wide<16, MODE>), ugrid, ublock, 0, st, V, vf);
     }
     hipLaunchKernelGGL(k_dec_unpc, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, st, V);
     switch (da.bitDepth) {
-    case 16: launch_unmix_v1<16, MODE>(V, st); break;
-    case 20: launch_unmix_v1<20, MODE>(V, st); break;
-    case 24: launch_unmix_v1<24, MODE>(V, st); break;
-    case 32: launch_unmix_v1<32, MODE>(V, st); break;
+    case 16: launch_unmix_v1<16, MODE>(V, vf, st); break;
+    case 20: launch_unmix_v1<20, MODE>(V, vf, st); break;
+    case 24: launch_unmix_v1<24, MODE>(V, vf, st); break;
+    case 32: launch_unmix_v1<32, MODE>(V, vf, st); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -2163,6 +2168,7 @@ static hipError_t run_decode_v1_pass(const DecV1Args &V, hipStream_t st, bool st
     case kPcmStore: return decode_v1_pass<kPcmStore>(V, st, stageFirst);
     case kPcmVerify: return decode_v1_pass<kPcmVerify>(V, st, stageFirst);  // alac_hip_verify
     case kPcmFloat: return decode_v1_pass<kPcmFloat>(V, st, stageFirst);    // alac_hip_decode_float
+    case kPcmVerifyFloat: return decode_v1_pass<kPcmVerifyFloat>(V, st, stageFirst);  // alac_hip_verify_float
     default: return hipErrorInvalidValue;
     }
 }

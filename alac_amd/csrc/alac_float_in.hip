@@ -3,80 +3,15 @@
 // for alac_hip_encode_float_dither with TPDF dither from a counter-based generator in front of the rounding.
 #include "alac_dev.hpp"
 #include "alac_kernels.hpp"
+#include "alac_float_rule.hpp"
 
 namespace alacdev {
 
-// the rule of alac_hip_encode_float: r = rint(x * 2^(DEPTH-1)) (the product is exact), saturated; NaN -> 0.  r is an
-// integer, so "r > 2^(DEPTH-1) - 1" is "r >= 2^(DEPTH-1)", a comparison with an exact float even at 32 bits.
-template <int DEPTH>
-__device__ __forceinline__ int32_t saturate(bool nan, float r, uint32_t &clips)
-{
-    constexpr float kScale = (float)(1ull << (DEPTH - 1));
-    constexpr int32_t kMax = (int32_t)((1ull << (DEPTH - 1)) - 1);
-    const bool hi = r >= kScale;
-    clips += (nan || hi || r < -kScale) ? 1u : 0u;
-    // fmaxf(NaN, y) = y, so the conversion only ever sees a value in [-2^(DEPTH-1), 2^(DEPTH-1))
-    const int32_t s = (int32_t)fmaxf(r, -kScale);
-    return nan ? 0 : (hi ? kMax : s);
-}
-
-template <int DEPTH>
-__device__ __forceinline__ int32_t quantize(float x, uint32_t &clips)
-{
-    return saturate<DEPTH>(x != x, rintf(x * (float)(1ull << (DEPTH - 1))), clips);
-}
-
-// the rule of alac_hip_encode_float_dither: v = x * 2^(DEPTH-1) + d rounded once (the product is exact, so the fused form
-// and multiply-then-add agree), r = rint(v), then as above.  d = 0 gives quantize(x).
-template <int DEPTH>
-__device__ __forceinline__ int32_t quantize_dithered(float x, float d, uint32_t &clips)
-{
-    return saturate<DEPTH>(x != x, rintf(fmaf(x, (float)(1ull << (DEPTH - 1)), d)), clips);
-}
-
-// ---- TPDF dither: Philox4x32-10 (Salmon et al., Random123), a pure function of (seed, channel, frame index) ----
-constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u, kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
-
+// the ten round keys of a seed (the device side, philox, is in alac_float_rule.hpp)
 void philox_round_keys(uint64_t seed, uint32_t (&roundKey)[10][2])
 {
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     for (int r = 0; r < 10; r++, k0 += kPhiloxW0, k1 += kPhiloxW1) roundKey[r][0] = k0, roundKey[r][1] = k1;
-}
-
-// counter (T & 0xffffffff, T >> 32, c, 0): two 32 x 32 -> 64-bit products per round, both halves of each used
-__device__ __forceinline__ void philox(uint64_t T, uint32_t c, const FloatDitherArgs &d, uint32_t (&w)[4])
-{
-    uint32_t c0 = (uint32_t)T, c1 = (uint32_t)(T >> 32), c2 = c, c3 = 0;
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)kPhiloxM0 * c0, p1 = (uint64_t)kPhiloxM1 * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ d.roundKey[r][0], n2 = (uint32_t)(p0 >> 32) ^ c3 ^ d.roundKey[r][1];
-        c0 = n0, c1 = (uint32_t)p1, c2 = n2, c3 = (uint32_t)p0;
-    }
-    w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
-}
-
-// k * 2^-24 with k = (wa >> 8) - (wb >> 8): |k| < 2^24, so the conversion and the scaling are exact
-__device__ __forceinline__ float tpdf(uint32_t wa, uint32_t wb)
-{
-    return (float)((int32_t)(wa >> 8) - (int32_t)(wb >> 8)) * 0x1p-24f;
-}
-
-// the dither of channel c at stream frames t0 .. t0 + 3.  One Philox call serves frames 2T and 2T + 1: two calls when t0 is
-// even (every word used), three when it is odd (an odd packet origin; the same for a whole wave, so no divergence).
-__device__ __forceinline__ void dither4(uint64_t t0, uint32_t c, const FloatDitherArgs &d, float (&z)[4])
-{
-    const uint64_t T = t0 >> 1;
-    uint32_t u[4], v[4];
-    philox(T, c, d, u);
-    philox(T + 1, c, d, v);
-    if ((t0 & 1) == 0) {
-        z[0] = tpdf(u[0], u[1]), z[1] = tpdf(u[2], u[3]), z[2] = tpdf(v[0], v[1]), z[3] = tpdf(v[2], v[3]);
-    } else {
-        uint32_t w[4];
-        philox(T + 2, c, d, w);
-        z[0] = tpdf(u[2], u[3]), z[1] = tpdf(v[0], v[1]), z[2] = tpdf(v[2], v[3]), z[3] = tpdf(w[0], w[1]);
-    }
 }
 
 // a sample as it sits in its container: 20-bit left-justified in 3 bytes (task_load / load_sample read it back >> 4)

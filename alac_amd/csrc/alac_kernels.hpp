@@ -217,7 +217,11 @@ struct DecodeArgs {
     int32_t *statusOut;
     // The two modes' own words share one slot, and the mode sits in the struct's tail padding: the layout of DecodeArgs (and of
     // DecV1Args behind it) is the one the store and verify instantiations were compiled against, so their code is unchanged.
+    // Verify-float mode (alac_hip_verify_float) has more words than fit here; they travel in a VerifyFloatArgs block of their
+    // own, the LAST argument of every kernel that writes PCM (an argument behind the existing ones moves no offset).  On the
+    // host the block rides behind verifyFloat in this slot; the kernels of that mode never read the slot.
     union {
+        const struct VerifyFloatArgs *verifyFloat;  // verify-float mode, HOST pointer: what the launchers pass on by value
         // verify mode (alac_hip_verify): [numPackets] lowest sample-frame whose bytes differ, lowered with atomicMin by every
         // store site of the PCM (PCM_PUT, alac_verify.hpp), which loads and compares instead of storing
         uint32_t *firstMismatch = nullptr;
@@ -303,6 +307,19 @@ struct FloatDitherArgs {
 };
 void philox_round_keys(uint64_t seed, uint32_t (&roundKey)[10][2]);
 hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t st, const FloatDitherArgs *dither = nullptr);
+
+// ---- verify against a float32 source (alac_hip_verify_float): the words of PcmMode kPcmVerifyFloat (alac_verify.hpp) ----
+// DecodeArgs::pcmOut is the source: sample i of channel c of packet p at
+// pcmOut[c * channelStride + (p * frameSize + i) * frameStride] (floats); only frames i < min(numSamplesExpected[p], frameSize)
+// are ever loaded
+struct VerifyFloatArgs {
+    uint32_t *firstMismatch;             // [numPackets], as DecodeArgs::firstMismatch in verify mode
+    const uint32_t *numSamplesExpected;  // null: every packet frameSize frames
+    uint64_t channelStride, frameStride;
+    uint32_t dither;                     // != 0: TPDF by dz, as alac_hip_encode_float_dither
+    uint32_t pad;
+    FloatDitherArgs dz;
+};
 
 // ---- stage-level ----
 hipError_t launch_pc_block(const int32_t *in, int32_t *pc, uint32_t rows, uint32_t stride, int32_t num,

@@ -1,5 +1,5 @@
-// alac_verify.hpp — what the decoders' PCM store sites do: store (alac_hip_decode), verify (alac_hip_verify) or float
-// (alac_hip_decode_float).
+// alac_verify.hpp — what the decoders' PCM store sites do: store (alac_hip_decode), verify (alac_hip_verify), float
+// (alac_hip_decode_float) or verify against a float32 source (alac_hip_verify_float).
 //
 // Every kernel that writes PCM is instantiated once per PcmMode.  The integer sites write through PCM_PUT(MODE, A, ptr, value).
 // With kPcmStore that is the plain store `*ptr = value` it always was, through the site's own pointer type (its alignment
@@ -15,15 +15,25 @@
 // float branch of its own in front of the packing, on the sample values it holds; PCM_PUT refuses to compile in float mode,
 // so a site without one cannot slip through.  Where a lane holds four or more consecutive frames of a channel, the float
 // branch writes them with 16-byte stores (pcm_float_run).
+// With kPcmVerifyFloat, DecodeArgs::pcmOut is the caller's float32 SOURCE, only ever read, and the mode's own words travel
+// in a VerifyFloatArgs block that the PCM-writing kernels take as their last argument.  The mode lives in the float branches
+// (those hold sample values, channel and frame before any packing): through pcm_float_put / pcm_float_run a site loads the
+// source float of the sample it would have stored, computes the integer the float encode path stages for it
+// (alac_float_rule.hpp: the one spelling of the rule) and compares that with the decoded sample, sign-extended at the
+// stream's depth.  Every site passes the frame limit pcm_frames gave it — min(decoded, expected, frameSize) — and no
+// address is formed for a frame at or behind it, whatever the packet claims to hold.  Nothing is stored.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "alac_kernels.hpp"
+#include "alac_float_rule.hpp"
 
 namespace alacdev {
 
-enum PcmMode : int { kPcmStore = 0, kPcmVerify = 1, kPcmFloat = 2 };
+enum PcmMode : int { kPcmStore = 0, kPcmVerify = 1, kPcmFloat = 2, kPcmVerifyFloat = 3 };
+// the modes whose sites work on sample values per channel (their float branches)
+constexpr bool pcm_is_float(PcmMode m) { return m == kPcmFloat || m == kPcmVerifyFloat; }
 
 // float mode: a decoded sample as alac_hip_decode stores it (its low DEPTH bits, sign-extended — a 16-bit sample that a damaged
 // packet let grow past 16 bits wraps as the int16 store wraps it) times 2^-(DEPTH - 1).  The conversion rounds to nearest
@@ -65,6 +75,125 @@ __device__ __forceinline__ void pcm_float_run(float *row, uint32_t f0, uint32_t 
     }
 }
 
+// ---- verify-float mode (alac_hip_verify_float) ----
+
+// how many frames of packet p a site may touch when the decoder produced n: n itself, except in verify-float mode, where a
+// frame at or behind min(expected[p], frameSize) is never loaded from the source (a damaged or foreign packet may decode
+// more frames than the caller's tensor holds).  k_verify_finish settles the frames behind the shorter count.
+template <PcmMode MODE>
+__device__ __forceinline__ uint32_t pcm_frames(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t p, uint32_t n)
+{
+    if constexpr (MODE != kPcmVerifyFloat) return n;
+    const uint32_t e = F.numSamplesExpected ? F.numSamplesExpected[p] : A.frameSize;
+    return min(n, min(e, A.frameSize));
+}
+// a bound a site derived from n (n rounded down to whole groups), under the limit pcm_frames gave
+template <PcmMode MODE>
+__device__ __forceinline__ uint32_t pcm_clamp(uint32_t bound, uint32_t lim)
+{
+    if constexpr (MODE != kPcmVerifyFloat) return bound;
+    return min(bound, lim);
+}
+
+// the same "plain load of the current minimum, then atomicMin" as pcm_mismatch; the site knows packet and frame
+__device__ __forceinline__ void vf_mismatch(const VerifyFloatArgs &F, uint32_t p, uint32_t frame)
+{
+    uint32_t *slot = F.firstMismatch + p;
+    if (frame < __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(slot, frame);
+}
+// source float of frame j (of the batch: p * frameSize + i) of channel c
+__device__ __forceinline__ const float *vf_source(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint64_t j)
+{
+    return (const float *)A.pcmOut + c * F.channelStride + j * F.frameStride;
+}
+// stream frame index of frame 0 of packet p
+__device__ __forceinline__ uint64_t vf_origin(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t p)
+{
+    return F.dz.origin ? F.dz.origin[p] : (uint64_t)p * A.frameSize;
+}
+// does decoded sample `got` differ from what the float encode path stages for source x with dither d (0: no dither —
+// quantize_dithered(x, 0) is quantize(x))
+template <int DEPTH>
+__device__ __forceinline__ bool vf_differs(float x, float d, int32_t got)
+{
+    uint32_t clips = 0;
+    const int32_t s = DEPTH == 32 ? got : (int32_t)((uint32_t)got << (32 - DEPTH)) >> (32 - DEPTH);
+    return quantize_dithered<DEPTH>(x, d, clips) != s;
+}
+// one sample: frame j of channel c of packet p, decoded value x; nothing happens at or behind lim
+template <int DEPTH>
+__device__ __forceinline__ void vf_sample(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p, uint32_t j,
+                                          uint32_t lim, int32_t x)
+{
+    if (j >= lim) return;
+    const float src = *vf_source(A, F, c, (uint64_t)p * A.frameSize + j);
+    float d = 0.0f;
+    if (F.dither) {  // uniform
+        const uint64_t t = vf_origin(A, F, p) + j;
+        uint32_t w[4];
+        philox(t >> 1, c, F.dz, w);
+        d = (t & 1) ? tpdf(w[2], w[3]) : tpdf(w[0], w[1]);
+    }
+    if (vf_differs<DEPTH>(src, d, x)) vf_mismatch(F, p, j);
+}
+// NF consecutive frames f0 .. of one channel, those in front of lim.  A whole group of four: the source as one 16-byte
+// load where frameStride is 1 (4-byte alignment is all the input promises), the dither as dither4 spends it (two Philox
+// calls per four frames, three where the first stream frame index is odd).  frameStride and the dither switch are
+// uniform branches on kernel arguments, not template parameters: a template would double (twice) a mode that already
+// adds an instantiation of every PCM-writing kernel, for a branch that costs one scalar compare per group.
+template <int DEPTH, int NF>
+__device__ __forceinline__ void vf_run(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p, uint32_t f0,
+                                       uint32_t lim, const int32_t (&x)[NF])
+{
+    typedef float F4 __attribute__((ext_vector_type(4), aligned(4)));
+    static_assert(NF % 4 == 0, "whole groups of four frames");
+    if (f0 >= lim) return;
+    const uint64_t j0 = (uint64_t)p * A.frameSize;
+    const uint64_t t0 = F.dither ? vf_origin(A, F, p) : 0;
+#pragma unroll
+    for (int q = 0; q < NF / 4; q++) {
+        const uint32_t f = f0 + 4 * q;
+        if (f + 4 <= lim) {
+            float s[4];
+            if (F.frameStride == 1) {
+                const F4 t = *(const F4 *)vf_source(A, F, c, j0 + f);
+                s[0] = t.x, s[1] = t.y, s[2] = t.z, s[3] = t.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; e++) s[e] = *vf_source(A, F, c, j0 + f + e);
+            }
+            float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (F.dither) dither4(t0 + f, c, F.dz, z);
+            uint32_t first = 4;
+#pragma unroll
+            for (int e = 3; e >= 0; e--)
+                if (vf_differs<DEPTH>(s[e], z[e], x[4 * q + e])) first = (uint32_t)e;
+            if (first < 4) vf_mismatch(F, p, f + first);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++) vf_sample<DEPTH>(A, F, c, p, f + e, lim, x[4 * q + e]);
+        }
+    }
+}
+
+// ---- what a float branch calls: float mode stores, verify-float mode compares; lim = pcm_frames(...) of the packet ----
+template <int DEPTH, PcmMode MODE>
+__device__ __forceinline__ void pcm_float_put(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p, uint32_t j,
+                                              uint32_t lim, int32_t x)
+{
+    static_assert(pcm_is_float(MODE), "a float branch");
+    if constexpr (MODE == kPcmFloat) pcm_float_row(A, c, p)[j] = pcm_float<DEPTH>(x);
+    else vf_sample<DEPTH>(A, F, c, p, j, lim, x);
+}
+template <int DEPTH, PcmMode MODE, int NF>
+__device__ __forceinline__ void pcm_float_run(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p, uint32_t f0,
+                                              uint32_t lim, const int32_t (&x)[NF])
+{
+    static_assert(pcm_is_float(MODE), "a float branch");
+    if constexpr (MODE == kPcmFloat) pcm_float_run<DEPTH>(pcm_float_row(A, c, p), f0, lim, x);
+    else vf_run<DEPTH>(A, F, c, p, f0, lim, x);
+}
+
 // the frame that holds byte `at` of the expected PCM; a plain load first, so that a packet whose every frame differs
 // (a damaged packet) costs one atomic per lane only while its minimum is still falling.  Inlined: as a called function it
 // gave every verify kernel the call ABI — a 256-byte scratch frame, and the fused launch (whose entropy wave is the serial
@@ -101,7 +230,7 @@ __device__ __forceinline__ void pcm_compare(const DecodeArgs &A, const void *q, 
 
 #define PCM_PUT(MODE, A, ptr, value)                                                              \
     do {                                                                                          \
-        static_assert((MODE) != alacdev::kPcmFloat, "float mode: the site stores floats itself"); \
+        static_assert(!alacdev::pcm_is_float(MODE), "float modes: the site's float branch does the work"); \
         if constexpr ((MODE) == alacdev::kPcmVerify) alacdev::pcm_compare((A), (ptr), *(ptr), (value)); \
         else *(ptr) = (value);                                                                    \
     } while (0)

@@ -28,13 +28,24 @@
  *                                             a mismatch name the file, packet and frame, write nothing, exit 1.  The
  *                                             output bytes are those of the same command without --verify
  *   --compare <in.caf|in.m4a> <reference.wav> decode an ALAC file and compare it with a WAV / PCM CAF on the GPU, writing
- *                                             nothing: exit 0 if every frame matches, 1 otherwise (or on an error)
+ *                                             nothing: exit 0 if every frame matches, 1 otherwise (or on an error).  A 32-bit
+ *                                             float WAV / CAF reference is compared through the quantization rule at the
+ *                                             stream's bit depth; --dither [--dither-seed S] may be added for a file that was
+ *                                             encoded with it
  *   --float-bits N                            encode only, N = 16, 20, 24 or 32: the inputs are 32-bit IEEE-float PCM (WAVE
  *                                             format tag 3 or EXTENSIBLE float, CAF lpcm with the float flag, either byte
  *                                             order), quantized on the GPU (alac_hip_encode_float) and encoded at N bits.  The
  *                                             output is the file an integer input holding the quantized samples gives; a
  *                                             clip count is a warning on stderr.  Integer or 64-bit float inputs and
  *                                             --verify are refused
+ *   --verify-source                           with --float-bits N [--dither [--dither-seed S]]: after a group is encoded, decode
+ *                                             its stream on the device and compare it with the FLOAT data of the input files
+ *                                             through the quantization rule (alac_hip_verify_float: rounding, saturation,
+ *                                             NaN -> 0, the dither of the same seed; every file's frames count from 0) before
+ *                                             any file is written; on a mismatch name file, packet and frame, write nothing,
+ *                                             exit 1.  --verify is "against the PCM handed to the encoder", --verify-source
+ *                                             is "against the float file, through the rule"; a float encode has only the latter.
+ *                                             The output bytes are those of the same command without it
  *   --dither [--dither-seed S]                with --float-bits 16, 20 or 24: triangular (TPDF) dither of +-1 LSB in front of
  *                                             the rounding, generated on the GPU (alac_hip_encode_float_dither) from the seed S
  *                                             (decimal or 0x-hex, default 0: two runs give the same file).  Every file's
@@ -92,6 +103,10 @@ void usage()
     printf("        alacconvert --compare <input caf or m4a file> <reference wav or caf file>\n");
     printf("        alacconvert --float-bits N [--batch] [--lpc] ... <input float wav or caf file> <output caf or m4a file> ...\n");
     printf("        alacconvert --float-bits N --dither [--dither-seed S] ... <input float wav or caf file> <output caf or m4a file> ...\n");
+    printf("        alacconvert --float-bits N [--dither [--dither-seed S]] --verify-source ... <input float wav or caf file> <output caf or m4a file> ...\n");
+    printf("            (--verify checks against the PCM handed to the encoder, --verify-source against the float file through the\n");
+    printf("             quantization rule)\n");
+    printf("        alacconvert --compare [--dither [--dither-seed S]] <input caf or m4a file> <reference float wav or caf file>\n");
     printf("\n");
 }
 
@@ -156,8 +171,51 @@ struct DitherOption {
     uint64_t seed = 0;
 };
 
-bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, bool verify, const DitherOption &dither,
-                  int device)
+// --verify-source: decode the group's stream on `device` and compare it with the floats it was encoded from, through the rule
+// of the float encode (the same dither, every file's frames counted from 0: `origin`); names the first bad packet of every
+// file that fails
+bool verify_source_group(std::vector<Job *> &jobs, ALACEncoder &enc, const std::vector<uint32_t> &firstPacket,
+                         const std::vector<float> &fl, uint32_t ch, const std::vector<uint32_t> &numSamples,
+                         const DitherOption &dither, const std::vector<uint64_t> &origin, const Bytes &stream,
+                         const std::vector<uint32_t> &sizes, int device)
+{
+    const uint32_t np = (uint32_t)sizes.size();
+    if (np == 0) return true;
+    uint32_t cookieSize = enc.GetMagicCookieSize(ch);
+    Bytes cookie(cookieSize, 0);
+    enc.GetMagicCookie(cookie.data(), &cookieSize);
+    ALACDecoder dec;
+    if (device >= 0) dec.SetDevice(device);
+    if (dec.Init(cookie.data(), cookieSize, 0) != ALAC_noErr) {
+        fprintf(stderr, " Cannot initialise the decoder for --verify-source\n");
+        return false;
+    }
+    std::vector<uint32_t> firstMismatch(np, 0);
+    std::vector<int32_t> status(np, 0);
+    uint32_t bad = 0;
+    const int32_t rc = dec.VerifyBatchFloat(stream.data(), sizes.data(), np, fl.data(), 1, ch, numSamples.data(),
+                                            dither.on ? ALAC_HIP_DITHER_TPDF : ALAC_HIP_DITHER_NONE, dither.seed, origin.data(),
+                                            firstMismatch.data(), status.data(), &bad);
+    if (rc != ALAC_noErr) {
+        fprintf(stderr, " Verification failed to run (status %d)\n", rc);
+        return false;
+    }
+    if (bad == 0) return true;
+    for (size_t j = 0; j < jobs.size(); j++) {
+        const uint32_t p0 = firstPacket[j], p1 = j + 1 < jobs.size() ? firstPacket[j + 1] : np;
+        for (uint32_t p = p0; p < p1; p++) {
+            if (firstMismatch[p] != 0xffffffffu) {
+                fprintf(stderr, " Verify failed: \"%s\" -> \"%s\": packet %u, frame %u (status %d)\n", jobs[j]->in.c_str(),
+                        jobs[j]->out.c_str(), p - p0, firstMismatch[p], status[p]);
+                break;
+            }
+        }
+    }
+    return false;
+}
+
+bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, bool verify, bool verifySource,
+                  const DitherOption &dither, int device)
 {
     const InputInfo &first = jobs[0]->info;
     const uint32_t bps = (first.bitsPerChannel + 7) >> 3, ch = first.channels;  // 20 bits: 3-byte containers (container.cpp)
@@ -233,6 +291,8 @@ bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, b
                 fprintf(stderr, " Warning: %llu samples clipped to %u bits: \"%s\"\n", (unsigned long long)clips,
                         first.bitsPerChannel, jobs[j]->in.c_str());
         }
+        if (verifySource && !verify_source_group(jobs, enc, firstPacket, fl, ch, numSamples, dither, origin, stream, sizes, device))
+            return false;
     } else if (np) {
         for (size_t j = 0; j < jobs.size(); j++) {
             Job &J = *jobs[j];
@@ -291,7 +351,7 @@ void append_packets(const Job &J, const alacfile::AlacCafContents &c, Bytes &str
 }
 
 // ---- --compare <alac file> <reference pcm file>: decode and compare on the GPU, write nothing; 0 = identical ----
-int compare_files(const std::string &alacPath, const std::string &refPath)
+int compare_files(const std::string &alacPath, const std::string &refPath, const DitherOption &dither)
 {
     Job A, R;
     A.in = alacPath;
@@ -301,11 +361,20 @@ int compare_files(const std::string &alacPath, const std::string &refPath)
             fprintf(stderr, " Cannot open file \"%s\"\n", J->in.c_str());
             return 1;
         }
-        const std::string err = alacfile::sniff_input(J->file, J->info);
+        const std::string err = alacfile::sniff_input(J->file, J->info, J == &R);  // the reference may be float PCM
         if (!err.empty()) {
             fprintf(stderr, " %s: \"%s\"\n", err.c_str(), J->in.c_str());
             return 1;
         }
+    }
+    const bool floatRef = !R.info.isAlac && R.info.isFloat;
+    if (floatRef && R.info.bitsPerChannel != 32) {
+        fprintf(stderr, " %u-bit float reference is not supported (32-bit float): \"%s\"\n", R.info.bitsPerChannel, R.in.c_str());
+        return 1;
+    }
+    if (dither.on && !floatRef) {
+        fprintf(stderr, " --compare --dither needs a 32-bit float reference: \"%s\"\n", R.in.c_str());
+        return 1;
     }
     if (!A.info.isAlac || R.info.isAlac) {
         fprintf(stderr, " --compare takes an ALAC file (CAF or M4A) and a PCM reference (WAV or CAF)\n");
@@ -326,12 +395,17 @@ int compare_files(const std::string &alacPath, const std::string &refPath)
         return 1;
     }
     const uint32_t ch = dec.mConfig.numChannels, bits = dec.mConfig.bitDepth, frame = dec.mConfig.frameLength;
-    if (ch != R.info.channels || bits != R.info.bitsPerChannel) {
+    if (dither.on && bits == 32) {
+        fprintf(stderr, " --dither needs a 16-, 20- or 24-bit stream: \"%s\"\n", A.in.c_str());
+        return 1;
+    }
+    if (ch != R.info.channels || (!floatRef && bits != R.info.bitsPerChannel)) {
         printf("Compare: \"%s\" is %u-bit %u-channel, \"%s\" %u-bit %u-channel: different\n", A.in.c_str(), bits, ch,
                R.in.c_str(), R.info.bitsPerChannel, R.info.channels);
         return 1;
     }
-    const uint64_t bytesPerFrame = (uint64_t)ch * ((bits + 7) >> 3), packetBytes = bytesPerFrame * frame;
+    // bytes of one frame of the reference: float32 samples, or the stream's own integer containers
+    const uint64_t bytesPerFrame = floatRef ? (uint64_t)ch * 4 : (uint64_t)ch * ((bits + 7) >> 3), packetBytes = bytesPerFrame * frame;
     std::vector<uint32_t> sizes;
     Bytes stream;
     append_packets(A, c, stream, sizes);
@@ -348,12 +422,18 @@ int compare_files(const std::string &alacPath, const std::string &refPath)
         if (R.info.bigEndianPcm)
             alacfile::swap_samples_in_place(pcm.data() + (size_t)p * packetBytes, n * bytesPerFrame, R.info.bitsPerChannel);
     }
+    // (a float reference sits in `pcm` as interleaved floats at the full-packet stride: channel stride 1, frame stride ch;
+    // one file, so its frames count from 0 as the encode numbered them — no origin table)
     std::vector<uint32_t> firstMismatch(np, 0);
     std::vector<int32_t> status(np, 0);
     uint32_t bad = 0;
     if (np) {
-        const int32_t rc = dec.VerifyBatch(stream.data(), sizes.data(), np, pcm.data(), expected.data(), firstMismatch.data(),
-                                           status.data(), &bad);
+        const int32_t rc =
+            floatRef ? dec.VerifyBatchFloat(stream.data(), sizes.data(), np, (const float *)pcm.data(), 1, ch, expected.data(),
+                                            dither.on ? ALAC_HIP_DITHER_TPDF : ALAC_HIP_DITHER_NONE, dither.seed, nullptr,
+                                            firstMismatch.data(), status.data(), &bad)
+                     : dec.VerifyBatch(stream.data(), sizes.data(), np, pcm.data(), expected.data(), firstMismatch.data(),
+                                       status.data(), &bad);
         if (rc != ALAC_noErr) {
             fprintf(stderr, " Verification failed to run (status %d)\n", rc);
             return 1;
@@ -440,7 +520,7 @@ bool decode_group(std::vector<Job *> &jobs, const std::vector<alacfile::AlacCafC
 int main(int argc, char *argv[])
 {
     std::vector<std::string> files;
-    bool batch = false, lpc = false, verify = false, compare = false, malformed = argc < 2;
+    bool batch = false, lpc = false, verify = false, verifySource = false, compare = false, malformed = argc < 2;
     uint32_t segmentPackets = 0, devices = 0, floatBits = 0;
     DitherOption dither;
     for (int i = 1; i < argc && !malformed; i++) {
@@ -453,6 +533,8 @@ int main(int argc, char *argv[])
             lpc = true;
         } else if (a == "--verify") {
             verify = true;
+        } else if (a == "--verify-source") {
+            verifySource = true;
         } else if (a == "--compare") {
             compare = true;
         } else if (a == "--segment-packets" && i + 1 < argc) {
@@ -480,18 +562,22 @@ int main(int argc, char *argv[])
     if (!malformed && (files.size() < 2 || (files.size() & 1) || (!batch && files.size() != 2))) malformed = true;
     if (!malformed && devices && !batch) malformed = true;  // one file is one serial chain: nothing to deal out
     // --compare stands alone: two files, no other option
-    if (!malformed && compare && (batch || lpc || verify || segmentPackets || devices || floatBits)) malformed = true;
-    if (!malformed && compare && dither.on) malformed = true;
+    // (but --dither [--dither-seed S], for a float reference of a file that was encoded with it)
+    if (!malformed && compare && (batch || lpc || verify || verifySource || segmentPackets || devices || floatBits)) malformed = true;
     if (malformed) {
         usage();
         return 1;
     }
+    if (compare) return compare_files(files[0], files[1], dither);
     if (dither.on && floatBits != 16 && floatBits != 20 && floatBits != 24) {
         fprintf(stderr, " --dither needs --float-bits 16, 20 or 24\n");
         usage();
         return 1;
     }
-    if (compare) return compare_files(files[0], files[1]);
+    if (verifySource && !floatBits) {
+        fprintf(stderr, " --verify-source needs float input (--float-bits N); --verify checks an integer encode: \"%s\"\n", files[0].c_str());
+        return 1;
+    }
     if (floatBits && verify) {
         fprintf(stderr, " --verify does not take float input (--float-bits): \"%s\"\n", files[0].c_str());
         return 1;
@@ -612,7 +698,7 @@ int main(int argc, char *argv[])
         const int device = firstDevice < 0 ? -1 : (int)(k % (uint32_t)visible);
         for (size_t i = 0; i < perWorker[k].size() && ok[k]; i++) {
             Work &w = perWorker[k][i];
-            ok[k] = w.decode ? decode_group(w.jobs, w.contents, device) : encode_group(w.jobs, segmentPackets, lpc, verify, dither, device);
+            ok[k] = w.decode ? decode_group(w.jobs, w.contents, device) : encode_group(w.jobs, segmentPackets, lpc, verify, verifySource, dither, device);
         }
     };
     if (workers == 1) {

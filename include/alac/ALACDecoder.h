@@ -44,6 +44,16 @@ public:
     int32_t VerifyBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets, const uint8_t *pcmExpected,
                         const uint32_t *numSamplesExpected, uint32_t *firstMismatchOut, int32_t *statusOut,
                         uint32_t *badPacketsOut = nullptr);
+    /* batch extension (host buffers): VerifyBatch against the float32 SOURCE of a float encode (alac_hip_verify_float_host).
+     * Sample i of channel c of packet p is in[c * channelStride + (p * frameLength + i) * frameStride]; every decoded sample
+     * is compared with what ALACEncoder::EncodeSegmentsFloat(At) stages for that float at the stream's bit depth — rounding,
+     * saturation, NaN -> 0 and, with ditherMode ALAC_HIP_DITHER_TPDF, the dither of (ditherSeed, channel, packetOrigin[p] + i)
+     * (packetOrigin NULL: p * frameLength).  Only frames in front of numSamplesExpected[p] are read from `in`.  Outputs and
+     * return value as VerifyBatch. */
+    int32_t VerifyBatchFloat(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets, const float *in,
+                             uint64_t channelStride, uint64_t frameStride, const uint32_t *numSamplesExpected,
+                             uint32_t ditherMode, uint64_t ditherSeed, const uint64_t *packetOrigin,
+                             uint32_t *firstMismatchOut, int32_t *statusOut, uint32_t *badPacketsOut = nullptr);
 
     int32_t LastStatus() const { return mLastStatus; }
 

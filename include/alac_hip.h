@@ -402,6 +402,47 @@ int32_t alac_hip_verify_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_
                              const uint32_t *h_packet_bytes, uint32_t num_packets, const uint8_t *h_pcm_expected,
                              const uint32_t *h_num_samples_expected, uint32_t *h_first_mismatch, int32_t *h_status);
 
+/* ---- batch verify against a float32 source: what alac_hip_encode_float / _dither wrote, checked on the device -------
+ * A caller who encodes from float32 has no integer PCM to hand alac_hip_verify: a rounding, a saturation, a NaN rule and
+ * optionally a dither stand between the source and the stream.  This call decodes the stream and, at every place
+ * alac_hip_decode would store sample i of channel c of packet p, loads
+ *     x = d_in[c * channel_stride + (p * frame_size + i) * frame_stride],
+ * computes the sample the float encode path stages for it — the rule of alac_hip_encode_float, or that of
+ * alac_hip_encode_float_dither with t = origin[p] + i when dither has mode ALAC_HIP_DITHER_TPDF (origin = d_packet_origin,
+ * p * frame_size where it is NULL) — at the stream's own bit depth (from the cookie), and compares it with the decoded
+ * sample sign-extended at that depth.  The rule is the same device code the encode path runs, on every decoder path
+ * alac_hip_verify covers.  Nothing is written but the outputs below; the workspace is
+ * alac_hip_verify_workspace_bytes_stream (no PCM plane, no staged integer copy).  No reference counterpart.
+ *   h_cookie/size, d_stream, d_packet_offsets, d_workspace: as alac_hip_verify
+ *   d_in, channel_stride, frame_stride: the float32 source as alac_hip_encode_float reads it (any strides, 4-byte aligned)
+ *   d_num_samples_expected [num_packets] expected sample-frames per packet, or NULL = every packet frame_size frames
+ *   dither, d_packet_origin: as alac_hip_encode_float_dither; dither == NULL or mode ALAC_HIP_DITHER_NONE ignores the
+ *                          origin table.  *dither is read before the call returns.
+ *   d_first_mismatch, d_status, d_bad_packets: exactly alac_hip_verify's (lowest differing frame in any channel; 0xFFFFFFFF
+ *                          clean; 0 undecodable; min(decoded, expected) when the counts differ and no earlier frame does)
+ * Only frames i < min(expected[p], frame_size) of packet p are ever loaded from d_in (expected NULL: all frame_size),
+ * whatever a damaged or foreign packet claims to contain: a tensor of exactly T frames is safe, as it is for
+ * alac_hip_encode_float.  Every store site clamps by the expected count before it forms an address.
+ * Asynchronous like alac_hip_verify, same decoder options, same hand-off error.  A mismatch is data, not an error.
+ * kALAC_ParamError, checked before anything is enqueued and with nothing written: everything alac_hip_verify refuses; d_in
+ * null or not 4-byte aligned, frame_stride 0, channel_stride 0 with more than one channel, the largest index overflowing
+ * 64 bits (the checks of alac_hip_encode_float); a dither mode above ALAC_HIP_DITHER_TPDF, reserved != 0, mode TPDF on a
+ * 32-bit stream, a d_packet_origin that is not 8-byte aligned.
+ */
+int32_t alac_hip_verify_float(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
+                              const uint64_t *d_packet_offsets, uint32_t num_packets, const float *d_in,
+                              uint64_t channel_stride, uint64_t frame_stride, const uint32_t *d_num_samples_expected,
+                              const alac_hip_dither *dither, const uint64_t *d_packet_origin, void *d_workspace,
+                              uint64_t workspace_bytes, uint32_t *d_first_mismatch, int32_t *d_status,
+                              uint32_t *d_bad_packets);
+/* Host-buffer form (synchronous, like alac_hip_verify_host): returns the number of packets that failed (>= 0), or a
+ * negative status.  Stages only the floats the call may read: up to the last frame an expected count covers. */
+int32_t alac_hip_verify_float_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *h_stream,
+                                   const uint32_t *h_packet_bytes, uint32_t num_packets, const float *h_in,
+                                   uint64_t channel_stride, uint64_t frame_stride, const uint32_t *h_num_samples_expected,
+                                   const alac_hip_dither *dither, const uint64_t *h_packet_origin,
+                                   uint32_t *h_first_mismatch, int32_t *h_status);
+
 /* Parse a magic cookie into a format (host only). */
 int32_t alac_hip_format_from_cookie(const uint8_t *h_cookie, uint32_t cookie_size,
                                     alac_hip_format *out_fmt);
