@@ -627,7 +627,58 @@ __device__ __forceinline__ void lms_pass(LmsShared<LPC> &sh, const V1Args &A, co
             }
             if (!std::is_same<Sink, NoSink>::value && !dst) {
                 // the sink was the only consumer (k_class_final): no residual plane
+            } else if constexpr (LPC >= 2) {
+                // One wave per SIMD: nothing hides an LDS round trip, so a read that is waited for in front of its own store
+                // costs the lane's whole latency once per row.  The lane's cells (stride LPC: ds_read2_b32 pairs) are read as a
+                // batch, lds_order() keeps the compiler from sinking them back between the stores, and one round trip is
+                // exposed per batch.  Row address = wave-uniform row pointer (stepped with scalar adds) + the lane's 32-bit
+                // byte offset laneOff = 4 (half * streamStride + fStream) < 4 LPC streamStride (half < LPC, fStream < streamStride):
+                // at most 4 rows of at most 5 planes x chains x 4 bytes, a quarter of the 16 rows golf_stream's offsets already
+                // need below 2^32 (alac_golomb.hpp, load).
+                constexpr int CELLS = Geo<LPC>::TILE / LPC;
+                const int32_t *cell = sh.xs + fs * Geo<LPC>::STRIDE + (int)half;
+                const char *rowPtr = (const char *)(dst + (uint64_t)j0 * streamStride);
+                const uint64_t rowStep = (uint64_t)LPC * streamStride * 4u;
+                const uint32_t laneOff = voff * 4u;
+                if ((uint32_t)(j0 + Geo<LPC>::TILE) <= fPmin) {
+                    // every lane owns every row of the tile: no predicate, no branch
+                    int32_t v[CELLS];
+#pragma unroll
+                    for (int it = 0; it < CELLS; it++) v[it] = cell[it * LPC];
+                    lds_order();
+                    // The offset is pinned to this block: hoisted out of the tile loop, its zero-extension reaches the stores as
+                    // a 64-bit vector register and every store gets a 64-bit vector add in front; seen here, the stores take the
+                    // SGPR-base + 32-bit-VGPR-offset form.
+                    uint32_t off = laneOff;
+                    asm volatile("" : "+v"(off));
+#pragma unroll
+                    for (int it = 0; it < CELLS; it++) {
+                        put((int32_t *)(rowPtr + off), v[it]);
+                        rowPtr += rowStep;
+                    }
+                } else {
+                    // tiles that reach a packet's end (or idle lanes without idleFast): the same in groups of 8 rows per lane
+                    // (a predicated store is a block of its own and keeps its vector add)
+                    constexpr int GROUP = 8;
+                    static_assert(CELLS % GROUP == 0, "whole groups");
+#pragma unroll 1
+                    for (int g = 0; g < CELLS; g += GROUP) {
+                        int32_t v[GROUP];
+#pragma unroll
+                        for (int k = 0; k < GROUP; k++) v[k] = cell[(g + k) * LPC];
+                        lds_order();
+#pragma unroll
+                        for (int k = 0; k < GROUP; k++) {
+                            const uint32_t j = (uint32_t)(j0 + (g + k) * LPC) + half;
+                            if (j < fP) put((int32_t *)(rowPtr + laneOff), v[k]);
+                            rowPtr += rowStep;
+                        }
+                        lds_order();
+                    }
+                }
             } else if ((uint32_t)(j0 + Geo<LPC>::TILE) <= fPmin) {
+                // (LPC = 1: the callers that flush every tile are the throughput regime's, two waves per SIMD that hide each
+                // other's LDS latency and no registers to spare for a batch — the read-and-store form stays)
                 // every lane owns every row of the tile: scalar row base + lane column, no predicate, no branch
                 int32_t *tileBase = dst + (uint64_t)j0 * streamStride;
 #pragma unroll
