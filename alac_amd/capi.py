@@ -38,6 +38,12 @@ class Dither(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
 
 
+class FloatReport(C.Structure):
+    """alac_hip_float_report: one per segment of alac_hip_float_probe, 32 bytes"""
+    _fields_ = [("over_range", C.c_uint64), ("nan", C.c_uint64), ("need_bits", C.c_uint32), ("peak_bits", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
 def make_format(frame_size=4096, bit_depth=16, num_channels=2, sample_rate=44100):
     return Format(frame_size, bit_depth, num_channels, sample_rate)
 
@@ -99,6 +105,10 @@ SIGNATURES = {
     "alac_hip_verify_host": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "alac_hip_verify_float": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "alac_hip_verify_float_host": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "alac_hip_float_probe_workspace_bytes": (_u64, [_u32]),
+    "alac_hip_float_probe": (_i32, [_vp, _vp, _u32, _u64, _u64, _u64, _vp, _u32, _vp, _u64, _vp]),
+    "alac_hip_float_probe_host": (_i32, [_vp, _vp, _u32, _u64, _u64, _u64, _vp, _u32, _vp]),
+    "alac_hip_float_report_depth": (_u32, [_vp]),
     "alac_synth_frame": (None, [_u64, _u32, _u32, _u32, _vp]),
     "alac_synth_pcm": (None, [_u64, _u32, _u32, _u32, _u32, _vp]),
     "alac_hip_synth_pcm": (_i32, [_vp, _u64, _u32, C.POINTER(Format), _vp]),
@@ -393,6 +403,38 @@ class Context:
             if num_samples is not None:
                 num_samples.record_stream(cur)
             return bufs
+
+    def probe_float(self, x, seg_first_frame=None):
+        """alac_hip_float_probe: what names the lossless bit depth of float32 PCM, per segment of frames.  x is a float32
+        cuda tensor [channels, frames] with any strides, passed through like encode_float's; seg_first_frame a sequence of
+        num_segments + 1 ascending frame indices (None: one segment, all of x).  Returns an int32 cuda tensor
+        [num_segments, 8] viewing the alac_hip_float_report of every segment (words 0-1 over_range, 2-3 nan, 4 need_bits,
+        5 peak_bits).  A tensor without frames has only empty segments: reports of zeros.  Asynchronous."""
+        with self._call() as cur:
+            t = self.torch
+            if not (x.is_cuda and x.dtype == t.float32 and x.dim() == 2):
+                raise ValueError("probe_float: x must be a float32 cuda tensor [channels, frames]")
+            table = None if seg_first_frame is None else np.ascontiguousarray(seg_first_frame, dtype=np.uint64)
+            if table is not None and (table.ndim != 1 or table.size < 1):
+                raise ValueError("probe_float: seg_first_frame must hold num_segments + 1 frame indices")
+            nseg = 1 if table is None else table.size - 1
+            reports = t.empty((nseg, 8), dtype=t.int32, device=self.device)
+            ws = self._workspace(int(self.lib.alac_hip_float_probe_workspace_bytes(nseg)))
+            # a tensor without frames has no address; the call wants one, and reads nothing through it
+            base = x if x.shape[1] else t.zeros(4, dtype=t.float32, device=self.device)
+            self._check(self.lib.alac_hip_float_probe(
+                self.h, base.data_ptr(), int(x.shape[0]), int(x.stride(0)), int(x.stride(1)), int(x.shape[1]),
+                None if table is None else table.ctypes.data, nseg, ws.data_ptr(), ws.numel(), reports.data_ptr()))
+            reports.record_stream(cur)
+            return reports
+
+    def lossless_depth(self, x, seg_first_frame=None):
+        """The smallest bit depth of 16, 20, 24, 32 at which encode_float(x) is exactly lossless, per segment
+        (alac_hip_float_report_depth over probe_float's reports); 0 where there is none.  Synchronizes."""
+        reports = self.probe_float(x, seg_first_frame)
+        self.synchronize()
+        rows = np.ascontiguousarray(reports.cpu().numpy())
+        return [int(self.lib.alac_hip_float_report_depth(rows[s].ctypes.data)) for s in range(rows.shape[0])]
 
     def encode_to_host(self, fmt, pcm, num_packets, **kw):
         """Convenience for tests: returns (stream bytes ndarray, sizes ndarray)."""

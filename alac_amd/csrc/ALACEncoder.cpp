@@ -39,6 +39,25 @@ ALACEncoder::~ALACEncoder()
     if (mCtx) alac_hip_destroy(mCtx);
 }
 
+// the object's context, on SetDevice's device (else ALAC_HIP_DEVICE, else 0)
+int32_t ALACEncoder::ensureContext()
+{
+    if (mCtx) return ALAC_noErr;
+    const char *dev = getenv("ALAC_HIP_DEVICE");
+    const int32_t rc = alac_hip_create(&mCtx, mDevice >= 0 ? mDevice : (dev ? atoi(dev) : 0), nullptr);
+    return rc != ALAC_HIP_noErr ? kALAC_MemFullError : ALAC_noErr;
+}
+
+int32_t ALACEncoder::ProbeFloat(const float *pcm, uint32_t numChannels, uint64_t channelStride, uint64_t frameStride,
+                                uint64_t totalFrames, const uint64_t *segFirstFrame, uint32_t numSegments,
+                                alac_hip_float_report *reports)
+{
+    if ((mLastStatus = ensureContext())) return mLastStatus;
+    mLastStatus = alac_hip_float_probe_host(mCtx, pcm, numChannels, channelStride, frameStride, totalFrames, segFirstFrame,
+                                            numSegments, reports);
+    return mLastStatus;
+}
+
 // codec/ALACEncoder.cu:1457-1535
 int32_t ALACEncoder::InitializeEncoder(AudioFormatDescription theOutputFormat, int /*X*/)
 {
@@ -54,11 +73,7 @@ int32_t ALACEncoder::InitializeEncoder(AudioFormatDescription theOutputFormat, i
     if (!(mBitDepth == 16 || mBitDepth == 20 || mBitDepth == 24 || mBitDepth == 32)) return kALAC_ParamError;
     if (mNumChannels < 1 || mNumChannels > kALACMaxChannels) return kALAC_ParamError;
     mMaxOutputBytes = mFrameSize * mNumChannels * ((10 + 32) / 8) + 1;        // :1489
-    if (!mCtx) {
-        const char *dev = getenv("ALAC_HIP_DEVICE");
-        int32_t rc = alac_hip_create(&mCtx, mDevice >= 0 ? mDevice : (dev ? atoi(dev) : 0), nullptr);
-        if (rc != ALAC_HIP_noErr) return kALAC_MemFullError;
-    }
+    if (int32_t rc = ensureContext()) return rc;
     mStateValid = false;  // every row = init_coefs (:1524-1531)
     mBatchStream.clear();
     mBatchSizes.clear();

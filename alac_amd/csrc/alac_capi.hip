@@ -39,6 +39,11 @@ struct alac_hip_ctx {
     // store when a consumer's bounded wait runs out; read without a copy after a synchronize
     uint32_t *errHost = nullptr;
     uint32_t *errDev = nullptr;
+    // alac_hip_float_probe's segment table on its way to the device: pinned host memory of the context, so that the
+    // caller's table is done with when the call returns wherever it lies; tabDone: the last upload from it has finished
+    uint64_t *tabHost = nullptr;
+    uint64_t tabCap = 0;  // in entries
+    hipEvent_t tabDone = nullptr;
     // code-path switches of this context (alac_hip_set_option); defaults from the ALAC_HIP_* environment at creation
     AlacOptions opt;
 };
@@ -464,6 +469,8 @@ void alac_hip_destroy(alac_hip_ctx *ctx)
         (void)hipStreamDestroy(ctx->stream);
     }
     if (ctx->errHost) (void)hipHostFree(ctx->errHost);
+    if (ctx->tabDone) (void)hipEventDestroy(ctx->tabDone);
+    if (ctx->tabHost) (void)hipHostFree(ctx->tabHost);
     delete ctx;
 }
 
@@ -992,6 +999,93 @@ int32_t alac_hip_encode_float_dither(alac_hip_ctx *ctx, const alac_hip_format *f
     }
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
     return encode_float_run(ctx, c, d_in, channel_stride, frame_stride, d_clipped, dither, d_packet_origin);
+}
+
+// ---- float32 probe: the lossless bit depth of float PCM, per segment of frames ---------------------------------------------
+uint64_t alac_hip_float_probe_workspace_bytes(uint32_t num_segments)
+{
+    return num_segments ? align_up(((uint64_t)num_segments + 1) * 8, 256) : 0;
+}
+
+// everything alac_hip_float_probe refuses that does not depend on where the buffers live; [lo, hi): the frames the segments
+// cover.  Device and host form.
+static int32_t float_probe_refusal(alac_hip_ctx *ctx, const float *in, uint32_t num_channels, uint64_t channel_stride,
+                                   uint64_t frame_stride, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                                   uint32_t num_segments, uint64_t &lo, uint64_t &hi)
+{
+    if (!in) return fail(ctx, ALAC_HIP_ParamError, "null input");
+    if ((uintptr_t)in & 3) return fail(ctx, ALAC_HIP_ParamError, "misaligned input (4 B)");
+    if (num_channels < 1 || num_channels > kMaxChannels) return fail(ctx, ALAC_HIP_ParamError, "num_channels outside 1..8");
+    if (frame_stride == 0) return fail(ctx, ALAC_HIP_ParamError, "frame_stride 0");
+    if (channel_stride == 0 && num_channels > 1)
+        return fail(ctx, ALAC_HIP_ParamError, "channel_stride 0 with more than one channel");
+    uint64_t rows, cols, last;
+    if (total_frames &&
+        (__builtin_mul_overflow((uint64_t)(num_channels - 1), channel_stride, &rows) ||
+         __builtin_mul_overflow(total_frames - 1, frame_stride, &cols) || __builtin_add_overflow(rows, cols, &last) ||
+         last >= UINT64_MAX / sizeof(float)))
+        return fail(ctx, ALAC_HIP_ParamError, "the largest index into the input overflows 64 bits");
+    if (num_segments == 0) return fail(ctx, ALAC_HIP_ParamError, "num_segments 0");
+    lo = 0, hi = total_frames;
+    if (!h_seg_first_frame)
+        return num_segments == 1 ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "no segment table for more than one segment");
+    for (uint32_t s = 0; s < num_segments; s++)
+        if (h_seg_first_frame[s] > h_seg_first_frame[s + 1]) return fail(ctx, ALAC_HIP_ParamError, "segment table not ascending");
+    if (h_seg_first_frame[num_segments] > total_frames)
+        return fail(ctx, ALAC_HIP_ParamError, "segment table ends behind total_frames");
+    lo = h_seg_first_frame[0], hi = h_seg_first_frame[num_segments];
+    return ALAC_HIP_noErr;
+}
+
+// The segment table goes to the device through the context's pinned buffer: copied out of the caller's memory here, on the
+// host, so the caller may reuse the table at once even where it is pinned memory, from which hipMemcpyAsync reads later.
+// A call that follows while the last upload is still in flight waits for that upload (not for the probe behind it).
+static hipError_t upload_segment_table(alac_hip_ctx *ctx, const uint64_t *h_table, uint64_t entries, void *d_dst)
+{
+    hipError_t e;
+    if (!ctx->tabDone && (e = hipEventCreateWithFlags(&ctx->tabDone, hipEventDisableTiming))) return e;
+    if (ctx->tabHost && (e = hipEventSynchronize(ctx->tabDone))) return e;
+    if (entries > ctx->tabCap) {
+        if (ctx->tabHost) (void)hipHostFree(ctx->tabHost);
+        ctx->tabHost = nullptr, ctx->tabCap = 0;
+        const uint64_t cap = entries < 1024 ? 1024 : entries;
+        if ((e = hipHostMalloc((void **)&ctx->tabHost, cap * 8, hipHostMallocDefault))) return e;
+        ctx->tabCap = cap;
+    }
+    memcpy(ctx->tabHost, h_table, entries * 8);
+    if ((e = hipMemcpyAsync(d_dst, ctx->tabHost, entries * 8, hipMemcpyHostToDevice, ctx->stream))) return e;
+    return hipEventRecord(ctx->tabDone, ctx->stream);
+}
+
+int32_t alac_hip_float_probe(alac_hip_ctx *ctx, const float *d_in, uint32_t num_channels, uint64_t channel_stride,
+                             uint64_t frame_stride, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                             uint32_t num_segments, void *d_workspace, uint64_t workspace_bytes,
+                             alac_hip_float_report *d_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = float_probe_refusal(ctx, d_in, num_channels, channel_stride, frame_stride, total_frames, h_seg_first_frame,
+                                         num_segments, lo, hi))
+        return rc;
+    if (!d_reports || ((uintptr_t)d_reports & 7)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned d_reports (8 B)");
+    if (workspace_bytes < alac_hip_float_probe_workspace_bytes(num_segments))
+        return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    if (h_seg_first_frame && (!d_workspace || ((uintptr_t)d_workspace & 7)))
+        return fail(ctx, ALAC_HIP_ParamError, "null or misaligned workspace (8 B)");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    hipError_t e;
+    if (h_seg_first_frame && (e = upload_segment_table(ctx, h_seg_first_frame, (uint64_t)num_segments + 1, d_workspace)))
+        return fail(ctx, ALAC_HIP_ParamError, "segment table upload", e);
+    const FloatProbeArgs a{d_in, channel_stride, frame_stride, lo, hi, h_seg_first_frame ? (const uint64_t *)d_workspace : nullptr,
+                           num_segments, num_channels, (uint32_t *)d_reports};
+    if ((e = launch_float_probe(a, ctx->stream))) return fail(ctx, ALAC_HIP_ParamError, "float probe launch", e);
+    return ALAC_HIP_noErr;
+}
+
+uint32_t alac_hip_float_report_depth(const alac_hip_float_report *r)
+{
+    if (!r || r->nan || r->over_range || r->need_bits > 32) return 0;
+    return r->need_bits <= 16 ? 16 : r->need_bits <= 20 ? 20 : r->need_bits <= 24 ? 24 : 32;
 }
 
 uint32_t alac_hip_num_stages(void) { return kNumStages; }
@@ -1566,6 +1660,35 @@ int32_t alac_hip_encode_float_dither_host(alac_hip_ctx *ctx, const alac_hip_form
         on_fail(ctx), [ctx] { return alac_hip_synchronize(ctx); });
     if (rc != ALAC_HIP_noErr || !h_clipped) return rc;
     if ((e = hipMemcpyAsync(h_clipped, dClip.p, np * 4ull, hipMemcpyDeviceToHost, ctx->stream)) ||
+        (e = hipStreamSynchronize(ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
+    return ALAC_HIP_noErr;
+}
+
+int32_t alac_hip_float_probe_host(alac_hip_ctx *ctx, const float *h_in, uint32_t num_channels, uint64_t channel_stride,
+                                  uint64_t frame_stride, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                                  uint32_t num_segments, alac_hip_float_report *h_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = float_probe_refusal(ctx, h_in, num_channels, channel_stride, frame_stride, total_frames, h_seg_first_frame,
+                                         num_segments, lo, hi))
+        return rc;
+    if (!h_reports) return fail(ctx, ALAC_HIP_ParamError, "null h_reports");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    // the floats the call may read lie in [0, span) of h_in: up to the last frame of the last segment
+    const uint64_t span = hi > lo ? (num_channels - 1) * channel_stride + (hi - 1) * frame_stride + 1 : 0;
+    const uint64_t wsBytes = alac_hip_float_probe_workspace_bytes(num_segments), repBytes = (uint64_t)num_segments * 32;
+    DevBuf dIn, dWs, dRep;
+    hipError_t e;
+    if ((e = dIn.alloc(span * sizeof(float))) || (e = dWs.alloc(wsBytes)) || (e = dRep.alloc(repBytes)))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if (span && (e = hipMemcpyAsync(dIn.p, h_in, span * sizeof(float), hipMemcpyHostToDevice, ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    if (int32_t rc = alac_hip_float_probe(ctx, (const float *)dIn.p, num_channels, channel_stride, frame_stride, total_frames,
+                                          h_seg_first_frame, num_segments, dWs.p, wsBytes, (alac_hip_float_report *)dRep.p))
+        return rc;
+    if ((e = hipMemcpyAsync(h_reports, dRep.p, repBytes, hipMemcpyDeviceToHost, ctx->stream)) ||
         (e = hipStreamSynchronize(ctx->stream)))
         return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
     return ALAC_HIP_noErr;

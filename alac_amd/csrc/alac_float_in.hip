@@ -75,12 +75,6 @@ __device__ __forceinline__ void store_sample(uint8_t *dst, int32_t s)
     }
 }
 
-enum FloatLayout : int {
-    kFloatPlanar = 0,       // frameStride 1: each channel's row contiguous (16-byte loads per channel)
-    kFloatInterleaved = 1,  // channelStride 1, frameStride CH: frames contiguous (16-byte loads over the frame)
-    kFloatGeneral = 2,      // any strides, any channel count: one load and one store per sample
-};
-
 // One lane: 4 consecutive frames of one packet; a block: 1 024 frames of one packet (blocksPerPacket blocks per packet, a
 // grid-stride loop over them).  Frames at or behind n = min(numSamples[p], frameSize) are not read and staged as zero.
 // CH: 1 or 2 (the vector layouts, frameSize % 4 == 0, aligned strides and base: the host checks) or 0 (kFloatGeneral,
@@ -208,10 +202,8 @@ hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t
         if (e != hipSuccess) return e;
     }
     // the vector paths: whole 4-frame groups inside a packet, 16-byte aligned float4 loads at every group
-    const bool vecFrames = a.frameSize % 4 == 0 && ((uintptr_t)a.in & 15) == 0 && a.channels <= 2;
-    FloatLayout layout = kFloatGeneral;
-    if (vecFrames && a.frameStride == 1 && (a.channels == 1 || a.channelStride % 4 == 0)) layout = kFloatPlanar;
-    else if (vecFrames && a.channels == 2 && a.channelStride == 1 && a.frameStride == 2) layout = kFloatInterleaved;
+    const FloatLayout layout =
+        a.frameSize % 4 == 0 ? float_layout(a.in, a.channels, a.channelStride, a.frameStride) : kFloatGeneral;
     const uint64_t bpp = ((uint64_t)a.frameSize + 1023) / 1024;
     const uint64_t blocks = (uint64_t)a.numPackets * bpp;
     const dim3 grid((uint32_t)(blocks < (1u << 22) ? blocks : (1u << 22)));

@@ -306,7 +306,36 @@ struct FloatDitherArgs {
     uint32_t roundKey[10][2];
 };
 void philox_round_keys(uint64_t seed, uint32_t (&roundKey)[10][2]);
+// how a float pass walks its input; a lane takes 4 consecutive frames that start at a multiple of 4
+enum FloatLayout : int {
+    kFloatPlanar = 0,       // frameStride 1: each channel's row contiguous (16-byte loads per channel)
+    kFloatInterleaved = 1,  // channelStride 1, frameStride CH: frames contiguous (16-byte loads over the frame)
+    kFloatGeneral = 2,      // any strides, any channel count: one load per sample
+};
+// the vector layouts: 1 or 2 channels, 16-byte aligned float4 loads at every group of 4 frames
+inline FloatLayout float_layout(const float *in, uint32_t channels, uint64_t channelStride, uint64_t frameStride)
+{
+    const bool vec = ((uintptr_t)in & 15) == 0 && channels <= 2;
+    if (vec && frameStride == 1 && (channels == 1 || channelStride % 4 == 0)) return kFloatPlanar;
+    if (vec && channels == 2 && channelStride == 1 && frameStride == 2) return kFloatInterleaved;
+    return kFloatGeneral;
+}
 hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t st, const FloatDitherArgs *dither = nullptr);
+
+// ---- float32 probe (alac_float_probe.hip): alac_hip_float_probe's one pass over the floats ----
+// the sample of channel c and frame t is in[c * channelStride + t * frameStride]; segment s = frames [segFirst[s],
+// segFirst[s + 1]) adds to reports[s] (8 uint32 per segment: alac_hip_float_report).  segFirst: device table
+// [numSegments + 1], ascending inside [lo, hi]; null: one segment [lo, hi).  Only frames in [lo, hi) are read.
+struct FloatProbeArgs {
+    const float *in;
+    uint64_t channelStride, frameStride;
+    uint64_t lo, hi;           // first frame of the first segment, end of the last one
+    const uint64_t *segFirst;  // nullable
+    uint32_t numSegments, channels;
+    uint32_t *reports;
+};
+// zeroes the reports, then (hi > lo) the pass
+hipError_t launch_float_probe(const FloatProbeArgs &a, hipStream_t st);
 
 // ---- verify against a float32 source (alac_hip_verify_float): the words of PcmMode kPcmVerifyFloat (alac_verify.hpp) ----
 // DecodeArgs::pcmOut is the source: sample i of channel c of packet p at

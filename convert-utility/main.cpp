@@ -38,6 +38,13 @@
  *                                             output is the file an integer input holding the quantized samples gives; a
  *                                             clip count is a warning on stderr.  Integer or 64-bit float inputs and
  *                                             --verify are refused
+ *   --float-bits auto                         as --float-bits N, with N chosen per file: the smallest of 16, 20, 24, 32 at
+ *                                             which the file's floats encode losslessly (alac_hip_float_probe, one call per
+ *                                             channel count, one segment per file), printed per file.  A --batch of mixed
+ *                                             material comes out as 16-bit and 24-bit streams side by side.  A file that has
+ *                                             no such depth (off-grid samples, a sample at or above 1.0, a NaN) is named with
+ *                                             its need_bits, over_range and nan counts; nothing is written, exit 1: auto
+ *                                             promises lossless, a lossy reduction stays an explicit N.  Not with --dither
  *   --verify-source                           with --float-bits N [--dither [--dither-seed S]]: after a group is encoded, decode
  *                                             its stream on the device and compare it with the FLOAT data of the input files
  *                                             through the quantization rule (alac_hip_verify_float: rounding, saturation,
@@ -102,6 +109,9 @@ void usage()
     printf("        alacconvert --verify [--batch] [--lpc] ... <input wav or caf file> <output caf or m4a file> ...\n");
     printf("        alacconvert --compare <input caf or m4a file> <reference wav or caf file>\n");
     printf("        alacconvert --float-bits N [--batch] [--lpc] ... <input float wav or caf file> <output caf or m4a file> ...\n");
+    printf("        alacconvert --float-bits auto [--batch] [--lpc] [--verify-source] ... <input float wav or caf file> <output caf or m4a file> ...\n");
+    printf("            (every file at the smallest of 16, 20, 24, 32 bits at which it is lossless, probed on the GPU; a file that\n");
+    printf("             has none is refused; no --dither)\n");
     printf("        alacconvert --float-bits N --dither [--dither-seed S] ... <input float wav or caf file> <output caf or m4a file> ...\n");
     printf("        alacconvert --float-bits N [--dither [--dither-seed S]] --verify-source ... <input float wav or caf file> <output caf or m4a file> ...\n");
     printf("            (--verify checks against the PCM handed to the encoder, --verify-source against the float file through the\n");
@@ -212,6 +222,53 @@ bool verify_source_group(std::vector<Job *> &jobs, ALACEncoder &enc, const std::
         }
     }
     return false;
+}
+
+// --float-bits auto: every float job gets the smallest depth at which its encode is exactly lossless, found on the GPU
+// (alac_hip_float_probe: one call per channel count, one segment per file), and is from then on the integer file of its
+// samples at that depth.  A file without such a depth is named with what stands in the way; the run is then refused.
+bool probe_float_jobs(std::vector<Job> &jobs, int device)
+{
+    std::map<uint32_t, std::vector<Job *> > byChannels;
+    for (size_t j = 0; j < jobs.size(); j++) byChannels[jobs[j].info.channels].push_back(&jobs[j]);
+    ALACEncoder enc;
+    if (device >= 0) enc.SetDevice(device);
+    bool ok = true;
+    for (std::map<uint32_t, std::vector<Job *> >::iterator g = byChannels.begin(); g != byChannels.end(); ++g) {
+        const uint32_t ch = g->first;
+        std::vector<Job *> &v = g->second;
+        std::vector<uint64_t> first(1, 0);  // the files' frames back to back
+        for (size_t j = 0; j < v.size(); j++) first.push_back(first.back() + v[j]->info.dataSize / (4ull * ch));
+        // interleaved floats: channel_stride 1, frame_stride ch (one float where every file is empty)
+        std::vector<float> fl((size_t)(first.back() * ch) + 1, 0.0f);
+        for (size_t j = 0; j < v.size(); j++) {
+            uint8_t *dst = (uint8_t *)(fl.data() + (size_t)first[j] * ch);
+            const uint64_t bytes = (first[j + 1] - first[j]) * ch * sizeof(float);
+            memcpy(dst, v[j]->file.data() + v[j]->floatPos, (size_t)bytes);
+            if (v[j]->floatBigEndian) alacfile::swap_samples_in_place(dst, bytes, 32);
+        }
+        std::vector<alac_hip_float_report> reports(v.size());
+        const int32_t rc = enc.ProbeFloat(fl.data(), ch, 1, ch, first.back(), first.data(), (uint32_t)v.size(), reports.data());
+        if (rc != ALAC_noErr) {
+            fprintf(stderr, " Probing the float input failed (status %d)\n", rc);
+            return false;
+        }
+        for (size_t j = 0; j < v.size(); j++) {
+            Job &J = *v[j];
+            const alac_hip_float_report &r = reports[j];
+            const uint32_t depth = alac_hip_float_report_depth(&r);
+            if (depth == 0) {
+                fprintf(stderr, " --float-bits auto: no lossless bit depth (need_bits %u, over_range %llu, nan %llu): \"%s\"\n",
+                        r.need_bits, (unsigned long long)r.over_range, (unsigned long long)r.nan, J.in.c_str());
+                ok = false;
+                continue;
+            }
+            printf("Float input is lossless at %u bits: %s\n", depth, J.in.c_str());
+            J.info.bitsPerChannel = depth;
+            J.info.dataSize = (first[j + 1] - first[j]) * ch * ((depth + 7) >> 3);
+        }
+    }
+    return ok;
 }
 
 bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, bool verify, bool verifySource,
@@ -522,6 +579,7 @@ int main(int argc, char *argv[])
     std::vector<std::string> files;
     bool batch = false, lpc = false, verify = false, verifySource = false, compare = false, malformed = argc < 2;
     uint32_t segmentPackets = 0, devices = 0, floatBits = 0;
+    bool floatAuto = false;  // --float-bits auto: floatBits stays 0, every file gets its own depth from the probe
     DitherOption dither;
     for (int i = 1; i < argc && !malformed; i++) {
         const std::string a = argv[i];
@@ -541,8 +599,13 @@ int main(int argc, char *argv[])
             segmentPackets = (uint32_t)strtoul(argv[++i], nullptr, 10);
             if (segmentPackets == 0) malformed = true;
         } else if (a == "--float-bits" && i + 1 < argc) {
-            floatBits = (uint32_t)strtoul(argv[++i], nullptr, 10);
-            if (floatBits != 16 && floatBits != 20 && floatBits != 24 && floatBits != 32) malformed = true;
+            if (std::string(argv[i + 1]) == "auto") {
+                floatAuto = true, floatBits = 0, i++;
+            } else {
+                floatAuto = false;
+                floatBits = (uint32_t)strtoul(argv[++i], nullptr, 10);
+                if (floatBits != 16 && floatBits != 20 && floatBits != 24 && floatBits != 32) malformed = true;
+            }
         } else if (a == "--dither") {
             dither.on = true;
         } else if (a == "--dither-seed" && i + 1 < argc) {
@@ -563,22 +626,23 @@ int main(int argc, char *argv[])
     if (!malformed && devices && !batch) malformed = true;  // one file is one serial chain: nothing to deal out
     // --compare stands alone: two files, no other option
     // (but --dither [--dither-seed S], for a float reference of a file that was encoded with it)
-    if (!malformed && compare && (batch || lpc || verify || verifySource || segmentPackets || devices || floatBits)) malformed = true;
+    const bool floatInput = floatBits != 0 || floatAuto;
+    if (!malformed && compare && (batch || lpc || verify || verifySource || segmentPackets || devices || floatInput)) malformed = true;
     if (malformed) {
         usage();
         return 1;
     }
     if (compare) return compare_files(files[0], files[1], dither);
-    if (dither.on && floatBits != 16 && floatBits != 20 && floatBits != 24) {
+    if (dither.on && floatBits != 16 && floatBits != 20 && floatBits != 24) {  // auto promises lossless: no dither there
         fprintf(stderr, " --dither needs --float-bits 16, 20 or 24\n");
         usage();
         return 1;
     }
-    if (verifySource && !floatBits) {
+    if (verifySource && !floatInput) {
         fprintf(stderr, " --verify-source needs float input (--float-bits N); --verify checks an integer encode: \"%s\"\n", files[0].c_str());
         return 1;
     }
-    if (floatBits && verify) {
+    if (floatInput && verify) {
         fprintf(stderr, " --verify does not take float input (--float-bits): \"%s\"\n", files[0].c_str());
         return 1;
     }
@@ -594,12 +658,12 @@ int main(int argc, char *argv[])
         }
         printf("Input file: %s\n", J.in.c_str());
         printf("Output file: %s\n", J.out.c_str());
-        const std::string err = alacfile::sniff_input(J.file, J.info, floatBits != 0);
+        const std::string err = alacfile::sniff_input(J.file, J.info, floatInput);
         if (!err.empty()) {
             fprintf(stderr, " %s: \"%s\"\n", err.c_str(), J.in.c_str());
             return 1;
         }
-        if (floatBits) {
+        if (floatInput) {
             if (!J.info.isFloat) {
                 fprintf(stderr, " --float-bits takes float PCM input, not integer PCM or ALAC: \"%s\"\n", J.in.c_str());
                 return 1;
@@ -615,8 +679,9 @@ int main(int argc, char *argv[])
             J.floatPos = J.info.dataPos;
             J.floatBigEndian = J.info.bigEndianPcm;
             J.info.isFloat = J.info.bigEndianPcm = false;
-            J.info.bitsPerChannel = floatBits;
-            J.info.dataSize = frames * J.info.channels * ((floatBits + 7) >> 3);
+            // (auto: 32 bits until probe_float_jobs below has the file's own depth)
+            J.info.bitsPerChannel = floatAuto ? 32 : floatBits;
+            J.info.dataSize = frames * J.info.channels * ((J.info.bitsPerChannel + 7) >> 3);
         }
         if (!J.info.isAlac) {
             const uint32_t b = J.info.bitsPerChannel;
@@ -626,6 +691,8 @@ int main(int argc, char *argv[])
             }
         }
     }
+
+    if (floatAuto && !probe_float_jobs(jobs, devices ? 0 : -1)) return 1;
 
     // group: encode jobs by (depth, channels); decode jobs by cookie
     std::map<std::string, std::vector<Job *> > groups;

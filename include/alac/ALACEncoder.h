@@ -13,6 +13,7 @@
 #include "ALACAudioTypes.h"
 
 struct alac_hip_ctx;
+struct alac_hip_float_report;
 
 class ALACEncoder {
 public:
@@ -75,6 +76,14 @@ public:
                                   uint64_t outCapacity, uint32_t *packetBytes, uint64_t *outTotalBytes, uint32_t *clipped,
                                   const uint64_t *packetOrigin);
 
+    /* Extension: what names the lossless bit depth of float32 PCM (alac_hip_float_probe_host): the sample of channel c and
+     * frame t at pcm[c * channelStride + t * frameStride]; segment s = frames [segFirstFrame[s], segFirstFrame[s + 1]) (NULL
+     * with numSegments 1: all totalFrames) gets reports[s], which alac_hip_float_report_depth turns into 16, 20, 24, 32 or 0.
+     * Needs no InitializeEncoder: the channel count is the call's, and the object's context is created where it is missing. */
+    int32_t ProbeFloat(const float *pcm, uint32_t numChannels, uint64_t channelStride, uint64_t frameStride,
+                       uint64_t totalFrames, const uint64_t *segFirstFrame, uint32_t numSegments,
+                       alac_hip_float_report *reports);
+
     int32_t LastStatus() const { return mLastStatus; }
 
 protected:
@@ -96,6 +105,7 @@ private:
     std::vector<uint64_t> mBatchOffsets;
     int32_t mLastStatus;
     void account(uint32_t outputSize);
+    int32_t ensureContext();
 };
 
 #endif

@@ -443,6 +443,62 @@ int32_t alac_hip_verify_float_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, u
                                    const alac_hip_dither *dither, const uint64_t *h_packet_origin,
                                    uint32_t *h_first_mismatch, int32_t *h_status);
 
+/* ---- probe float32 PCM for its lossless bit depth ------------------------------------------------------------------------
+ * A float tensor is very often integer PCM in disguise (a 16-bit file loaded as float, the output of alac_hip_decode_float).
+ * This call finds, per segment of frames, what alac_hip_float_report_depth needs to name the smallest depth in
+ * {16, 20, 24, 32} at which alac_hip_encode_float is exactly lossless: one streaming pass over the floats that writes
+ * nothing but the reports.  No reference counterpart.
+ * The rule, on the bit pattern of a float32 x with biased exponent field E and mantissa field M:
+ *     sig = M,             lsb = -149       if E == 0          (zero and denormals)
+ *     sig = M | 0x800000,  lsb = E - 150    otherwise
+ *     need(x) = 0                                   if sig == 0        (+0.0 and -0.0)
+ *               max(0, 1 - (lsb + ctz(sig)))        if x is finite     (1 for -1.0, 2 for 0.5, 16 for 2^-15, 150 for the
+ *                                                                       smallest denormal)
+ *   x * 2^(b-1) is an integer exactly when need(x) <= b.  A set of samples encodes losslessly at depth b when no sample is
+ *   NaN, no sample has x >= 1.0 or x < -1.0 (infinities count here) and max need <= b (being on the grid and below 1.0 gives
+ *   the upper bound 1 - 2^-(b-1)).  Then alac_hip_decode_float(alac_hip_encode_float(x)) == x as floats: bit for bit, but
+ *   that -0.0 comes back as +0.0.
+ *   d_in, channel_stride, frame_stride: float32, 4-byte aligned, sample of channel c and frame t at
+ *                     d_in[c * channel_stride + t * frame_stride], exactly as alac_hip_encode_float indexes it (t = p *
+ *                     frame_size + i).  The same three layouts: planar and interleaved stereo take 16-byte loads when d_in is
+ *                     16-byte aligned (planar: and channel_stride is a multiple of 4), 1 or 2 channels; anything else takes
+ *                     one load per sample.
+ *   h_seg_first_frame HOST array [num_segments + 1] of ascending frame indices, the last one <= total_frames; segment s
+ *                     covers all channels of frames [first[s], first[s+1]) (it may be empty).  NULL (num_segments 1): one
+ *                     segment [0, total_frames).  Read and validated before the call returns, as *dither is: it is copied
+ *                     out on the host, so the caller may reuse it at once whether it is pageable or pinned memory (a call
+ *                     that finds the previous call's table still on its way to the device waits for that upload).  Frames
+ *                     outside every segment are not read.
+ *   d_workspace       alac_hip_float_probe_workspace_bytes(num_segments) bytes, 8-byte aligned: holds the uploaded table
+ *   d_reports         [num_segments] alac_hip_float_report, 8-byte aligned.  Every word is written by every call (a second
+ *                     call into the same buffer does not accumulate onto the first).
+ * Asynchronous on the context's stream.  kALAC_ParamError, with nothing enqueued and nothing written: a null or misaligned
+ * d_in, d_reports or (with a table) d_workspace, num_channels outside 1..8, frame_stride 0, channel_stride 0 with more than
+ * one channel, a largest index (num_channels - 1) * channel_stride + (total_frames - 1) * frame_stride whose byte offset
+ * overflows 64 bits, num_segments 0 (or not 1 without a table), a table that is not ascending or ends behind total_frames,
+ * a workspace too small.
+ */
+typedef struct alac_hip_float_report { /* one per segment, 32 bytes */
+    uint64_t over_range;  /* samples with x >= 1.0 or x < -1.0, infinities included */
+    uint64_t nan;         /* NaN samples */
+    uint32_t need_bits;   /* max need(x) over the finite samples; 0 for an empty or all-zero segment */
+    uint32_t peak_bits;   /* bit pattern of max |x| over the non-NaN samples (+inf possible), 0 if none */
+    uint32_t reserved[2]; /* written as 0 */
+} alac_hip_float_report;
+uint64_t alac_hip_float_probe_workspace_bytes(uint32_t num_segments);
+int32_t alac_hip_float_probe(alac_hip_ctx *ctx, const float *d_in, uint32_t num_channels, uint64_t channel_stride,
+                             uint64_t frame_stride, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                             uint32_t num_segments, void *d_workspace, uint64_t workspace_bytes,
+                             alac_hip_float_report *d_reports);
+/* Host-buffer form (synchronous): h_in in the layout above; the floats up to the last frame of the last segment are staged
+ * to the device, the reports come back in h_reports [num_segments]. */
+int32_t alac_hip_float_probe_host(alac_hip_ctx *ctx, const float *h_in, uint32_t num_channels, uint64_t channel_stride,
+                                  uint64_t frame_stride, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                                  uint32_t num_segments, alac_hip_float_report *h_reports);
+/* Host only: the smallest depth of 16, 20, 24, 32 at which the report's samples encode losslessly (an empty or all-zero
+ * segment: 16); 0 when none does (nan != 0, over_range != 0 or need_bits > 32) or r is NULL. */
+uint32_t alac_hip_float_report_depth(const alac_hip_float_report *r);
+
 /* Parse a magic cookie into a format (host only). */
 int32_t alac_hip_format_from_cookie(const uint8_t *h_cookie, uint32_t cookie_size,
                                     alac_hip_format *out_fmt);
