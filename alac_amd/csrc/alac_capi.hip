@@ -714,12 +714,12 @@ static int32_t encode_core(alac_hip_ctx *ctx, const EncodeCall &c)
     hipEvent_t *ev = nullptr;
     if (c.timed && ctx->profile && (uint64_t)(ctx->profCalls + 1) * EV <= ctx->events.size())
         ev = &ctx->events[ctx->profCalls++ * EV];
+    if (ev) ctx->profLane.push_back(use_lane_encoder(ctx));
     hipError_t e;
     // the caller's bound on the segment length is checked on the device whatever kernels run
-    if (bound)
-        launch_check_segments(c.segFirst, c.numSegments, num_packets, ea.segMax, ctx->errDev ? ctx->errDev + 1 : nullptr,
-                              ea.segBad, c.stream);
-    if (ev) ctx->profLane.push_back(use_lane_encoder(ctx));
+    if (bound && (e = launch_check_segments(c.segFirst, c.numSegments, num_packets, ea.segMax, ctx->errDev ? ctx->errDev + 1 : nullptr,
+                                            ea.segBad, c.stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "segment check launch", e);
     if (use_lane_encoder(ctx)) {
         e = launch_encode(fmt->bit_depth, fmt->num_channels, ea, pa, num_packets, c.stream, ev ? ev + (kNumStages + 1) : nullptr);
     } else {
@@ -759,8 +759,7 @@ static int32_t encode_core(alac_hip_ctx *ctx, const EncodeCall &c)
         e = launch_lpc(fmt->bit_depth, fmt->num_channels, la, num_packets, c.stream);
         if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "lpc launch", e);
         pa.lpc = la.lpc;
-        launch_scan_pack(fmt->bit_depth, fmt->num_channels, c.packetBytes, pa, num_packets, c.stream, nullptr);
-        e = hipGetLastError();
+        e = launch_scan_pack(fmt->bit_depth, fmt->num_channels, c.packetBytes, pa, num_packets, c.stream, nullptr);
         if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "lpc pack launch", e);
     }
     return ALAC_HIP_noErr;
@@ -789,12 +788,17 @@ static int32_t encode_elements(alac_hip_ctx *ctx, const EncodeCall &c)
         if (!G.count) continue;
         hipStream_t st = (side && gi == 1) ? ctx->mcStream : c.stream;
         const uint64_t elemPcm = (uint64_t)num_packets * fmt->frame_size * G.channels * bps;
-        for (uint32_t k = 0; k < G.count; k++)
-            launch_mc_gather((const uint8_t *)c.pcm, ws + G.gather + k * elemPcm, c.numSamples, num_packets, fmt->frame_size,
-                             fmt->num_channels, M.el[G.elem[k]].first, G.channels, bps, st);
+        e = hipSuccess;
+        for (uint32_t k = 0; k < G.count && e == hipSuccess; k++)
+            e = launch_mc_gather((const uint8_t *)c.pcm, ws + G.gather + k * elemPcm, c.numSamples, num_packets, fmt->frame_size,
+                                 fmt->num_channels, M.el[G.elem[k]].first, G.channels, bps, st);
         uint32_t *ns = c.numSamples ? (uint32_t *)(ws + G.ns) : nullptr;
         uint32_t *seg = c.segFirst ? (uint32_t *)(ws + G.seg) : nullptr;
-        launch_mc_tables(c.numSamples, num_packets, c.segFirst, c.numSegments, G.count, ns, seg, st);
+        if (e == hipSuccess) e = launch_mc_tables(c.numSamples, num_packets, c.segFirst, c.numSegments, G.count, ns, seg, st);
+        if (e != hipSuccess) {
+            rc = fail(ctx, ALAC_HIP_ParamError, "element gather launch", e);
+            break;
+        }
         // coefficient rows: the caller's [element][segment][64] <-> the batch's [k][segment][64]
         int16_t *gstate = c.state ? (int16_t *)(ws + G.state) : nullptr;
         const uint64_t rowBytes = (uint64_t)c.numSegments * ALAC_HIP_STATE_INT16 * 2;
@@ -833,8 +837,7 @@ static int32_t encode_elements(alac_hip_ctx *ctx, const EncodeCall &c)
     sa.packetBytes = c.packetBytes;
     sa.offsets = c.offsets;
     sa.out = c.out;
-    launch_mc_splice(sa, c.stream);
-    e = hipGetLastError();
+    e = launch_mc_splice(sa, c.stream);
     if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "splice launch", e);
     return ALAC_HIP_noErr;
 }

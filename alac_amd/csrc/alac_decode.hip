@@ -442,17 +442,15 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A, VerifyFlo
 }
 
 template <int DEPTH, PcmMode MODE>
-static void launch_unmix_depth(const DecodeArgs &da, hipStream_t st)
+static hipError_t launch_unmix_depth(const DecodeArgs &da, hipStream_t st)
 {
     const VerifyFloatArgs vf = MODE == kPcmVerifyFloat ? *da.verifyFloat : VerifyFloatArgs{};
     dim3 grid((da.numPackets + 63) / 64, (da.frameSize + 63) / 64);
     if (da.gate) grid = dim3((uint32_t)std::min<uint64_t>((uint64_t)grid.x * grid.y, 2048), 1);  // (see k_decode_unmix)
     // two channels may arrive as one CPE or as two SCE / LFE elements (codec/ALACDecoder.cu:622-756): the per-element
     // kernel follows the records, k_decode_unmix<., 2> would take the packet for one pair
-    if (da.numChannels >= 2)
-        hipLaunchKernelGGL((k_decode_unmix_mc<DEPTH, MODE>), grid, dim3(256), 0, st, da, vf);
-    else
-        hipLaunchKernelGGL((k_decode_unmix<DEPTH, 1, MODE>), grid, dim3(256), 0, st, da, vf);
+    if (da.numChannels >= 2) return launch_kernel(k_decode_unmix_mc<DEPTH, MODE>, grid, dim3(256), st, da, vf);
+    return launch_kernel(k_decode_unmix<DEPTH, 1, MODE>, grid, dim3(256), st, da, vf);
 }
 
 // MODE: the un-mix instantiations whose store sites store, compare, write planar floats or compare with a float source
@@ -460,17 +458,16 @@ static void launch_unmix_depth(const DecodeArgs &da, hipStream_t st)
 template <PcmMode MODE>
 static hipError_t launch_decode_lanes(const DecodeArgs &da, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_decode_entropy, dim3((da.numPackets + 63) / 64), dim3(64), 0, st, da);
+    ALAC_TRY(launch_kernel(k_decode_entropy, dim3((da.numPackets + 63) / 64), dim3(64), st, da));
     const uint64_t lanes = (uint64_t)da.numPackets * da.numChannels;
-    hipLaunchKernelGGL(k_decode_unpc, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, st, da);
+    ALAC_TRY(launch_kernel(k_decode_unpc, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), st, da));
     switch (da.bitDepth) {
-    case 16: launch_unmix_depth<16, MODE>(da, st); break;
-    case 20: launch_unmix_depth<20, MODE>(da, st); break;
-    case 24: launch_unmix_depth<24, MODE>(da, st); break;
-    case 32: launch_unmix_depth<32, MODE>(da, st); break;
+    case 16: return launch_unmix_depth<16, MODE>(da, st);
+    case 20: return launch_unmix_depth<20, MODE>(da, st);
+    case 24: return launch_unmix_depth<24, MODE>(da, st);
+    case 32: return launch_unmix_depth<32, MODE>(da, st);
     default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 hipError_t launch_decode(const DecodeArgs &da, hipStream_t st)
@@ -609,16 +606,10 @@ hipError_t launch_pc_block(const int32_t *in, int32_t *pc, uint32_t rows, uint32
     // encode direction, 5 taps and more: one chain per half wave, taps across the lanes (alac_stage_taps.hip);
     // fewer taps, or shapes outside that kernel's exact range: one lane per row (option "stage_taps" = 0 forces it)
     const bool noTaps = !allowTaps;
-    if (decode) {
-        hipLaunchKernelGGL(k_unpc_block, dim3((rows + 63) / 64), dim3(64), 0, st, in, pc, rows, stride, num, coefs,
-                           numactive, chanbits, denshift);
-    } else if (!noTaps && numactive >= 5 && pc_block_taps_ok(num, numactive, chanbits, denshift)) {
-        launch_pc_block_taps(in, pc, rows, stride, num, coefs, numactive, chanbits, denshift, st);
-    } else {
-        hipLaunchKernelGGL(k_pc_block, dim3((rows + 63) / 64), dim3(64), 0, st, in, pc, rows, stride, num, coefs,
-                           numactive, chanbits, denshift);
-    }
-    return hipGetLastError();
+    if (!decode && !noTaps && numactive >= 5 && pc_block_taps_ok(num, numactive, chanbits, denshift))
+        return launch_pc_block_taps(in, pc, rows, stride, num, coefs, numactive, chanbits, denshift, st);
+    return launch_kernel(decode ? k_unpc_block : k_pc_block, dim3((rows + 63) / 64), dim3(64), st, in, pc, rows, stride, num, coefs,
+                         numactive, chanbits, denshift);
 }
 
 hipError_t launch_dyn_comp(uint32_t mb0, uint32_t pb, uint32_t kb, const int32_t *pc, uint32_t rows, uint32_t stride,
@@ -626,13 +617,11 @@ hipError_t launch_dyn_comp(uint32_t mb0, uint32_t pb, uint32_t kb, const int32_t
                            uint32_t *numBits, hipStream_t st)
 {
     if (rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dyn_comp, dim3((rows + 63) / 64), dim3(64), 0, st, mb0, pb, kb, pc, rows, stride, numSamples,
-                       bitSize, (uint32_t *)bits, bytesStride / 4, numBits);
-    if (bits) {
-        const uint64_t n = (uint64_t)rows * (bytesStride / 4);
-        hipLaunchKernelGGL(k_bswap_words, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, (uint32_t *)bits, n);
-    }
-    return hipGetLastError();
+    ALAC_TRY(launch_kernel(k_dyn_comp, dim3((rows + 63) / 64), dim3(64), st, mb0, pb, kb, pc, rows, stride, numSamples, bitSize,
+                           (uint32_t *)bits, bytesStride / 4, numBits));
+    if (!bits) return hipSuccess;
+    const uint64_t n = (uint64_t)rows * (bytesStride / 4);
+    return launch_kernel(k_bswap_words, dim3((uint32_t)((n + 255) / 256)), dim3(256), st, (uint32_t *)bits, n);
 }
 
 hipError_t launch_dyn_decomp(uint32_t mb0, uint32_t pb, uint32_t kb, const uint8_t *bits, uint32_t bytesStride,
@@ -640,9 +629,8 @@ hipError_t launch_dyn_decomp(uint32_t mb0, uint32_t pb, uint32_t kb, const uint8
                              uint32_t *numBits, int32_t *status, hipStream_t st)
 {
     if (rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dyn_decomp, dim3((rows + 63) / 64), dim3(64), 0, st, mb0, pb, kb, bits, bytesStride, rows, pc,
-                       stride, numSamples, maxSize, numBits, status);
-    return hipGetLastError();
+    return launch_kernel(k_dyn_decomp, dim3((rows + 63) / 64), dim3(64), st, mb0, pb, kb, bits, bytesStride, rows, pc, stride,
+                         numSamples, maxSize, numBits, status);
 }
 
 }  // namespace alacdev

@@ -2060,14 +2060,12 @@ __global__ __launch_bounds__(256) void k_dec_unmix(DecV1Args V, VerifyFloatArgs 
 }
 
 template <int DEPTH, PcmMode MODE>
-static void launch_unmix_v1(const DecV1Args &V, const VerifyFloatArgs &vf, hipStream_t st)
+static hipError_t launch_unmix_v1(const DecV1Args &V, const VerifyFloatArgs &vf, hipStream_t st)
 {
     const uint64_t all = (uint64_t)blocks_per_packet(V.d.frameSize) * V.d.numPackets;
     dim3 grid((uint32_t)(V.lists && all > 8192 ? 8192 : all));
-    if (V.d.numChannels == 2)
-        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 2, MODE>), grid, dim3(256), 0, st, V, vf);
-    else
-        hipLaunchKernelGGL((k_dec_unmix<DEPTH, 1, MODE>), grid, dim3(256), 0, st, V, vf);
+    if (V.d.numChannels == 2) return launch_kernel(k_dec_unmix<DEPTH, 2, MODE>, grid, dim3(256), st, V, vf);
+    return launch_kernel(k_dec_unmix<DEPTH, 1, MODE>, grid, dim3(256), st, V, vf);
 }
 
 // one pass of the pipeline over the elements V describes, after the staging of the stream (stageFirst: the pass stages it
@@ -2095,7 +2093,7 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stage
     // (the runtime's fill: a kernel of this library in its place — 44 us for the 328 MB of 10 000 stereo packets, HBM write speed —
     // measured 1.745 against 1.733 ms per pass: no bubble in front of a fill that IS the pass's first real work, unlike the 4-byte
     // ones DecZero replaced.  The fill on a second stream beside the staging and header kernels: 1.978 against 1.952 ms)
-    if (fused) (void)hipMemsetAsync(V.plane, 0, planeBytes, st);
+    if (fused) ALAC_TRY(hipMemsetAsync(V.plane, 0, planeBytes, st));
     V.lists = fused ? 0u : 1u;
     V.pairs = (!fused && V.d.optPair != 0) ? 1u : 0u;
     // the pass's counters: cleared by its first kernel (k_dec_tail / k_dec_stage, see DecZero) where there is one
@@ -2104,8 +2102,8 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stage
     zero.nA = kDecCounters;
     zero.b = V.mismatch;
     if (!stageFirst) {
-        if (zero.b) (void)hipMemsetAsync(zero.b, 0, 4, st);
-        if (zero.a) (void)hipMemsetAsync(zero.a, 0, kDecCounters * 4, st);
+        if (zero.b) ALAC_TRY(hipMemsetAsync(zero.b, 0, 4, st));
+        if (zero.a) ALAC_TRY(hipMemsetAsync(zero.a, 0, kDecCounters * 4, st));
     }
     // DIRECT: separate launches of a mono / stereo stream whose buffer is dword aligned (the fused launch keeps the staged copy:
     // there the entropy wave is the launch's serial chain and the 38 us copy is cheaper than a swap per word on that chain)
@@ -2123,43 +2121,40 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stage
         V.raw = (const uint32_t *)da.stream;
         V.tail = V.words;                // the first words of the (otherwise unused) staging area
         V.capWords = 1ull << 40;         // no staging area, no truncation: the word limit is the stream's own end + 64
-        hipLaunchKernelGGL(k_dec_tail, dim3(1), dim3(kDecTailWords), 0, st, da.stream, da.offsets, da.numPackets, const_cast<uint32_t *>(V.words),
-                           zero);
+        ALAC_TRY(launch_kernel(k_dec_tail, dim3(1), dim3(kDecTailWords), st, da.stream, da.offsets, da.numPackets,
+                               const_cast<uint32_t *>(V.words), zero));
     } else if (stageFirst)
-        hipLaunchKernelGGL(k_dec_stage, dim3(2048), dim3(256), 0, st, da.stream, da.offsets, da.numPackets, const_cast<uint32_t *>(V.words),
-                           V.capWords, zero);
-    hipLaunchKernelGGL(k_dec_header, dim3((da.numPackets + 64 * kHdrWaves - 1) / (64 * kHdrWaves)), dim3(64 * kHdrWaves), 0, st, V);
+        ALAC_TRY(launch_kernel(k_dec_stage, dim3(2048), dim3(256), st, da.stream, da.offsets, da.numPackets,
+                               const_cast<uint32_t *>(V.words), V.capWords, zero));
+    ALAC_TRY(launch_kernel(k_dec_header, dim3((da.numPackets + 64 * kHdrWaves - 1) / (64 * kHdrWaves)), dim3(64 * kHdrWaves), st, V));
     const uint64_t lanes = (uint64_t)da.numPackets * da.numChannels;
     const uint32_t nEnt = (da.numPackets + 63) / 64;
     if (fused) {
         const uint32_t nEntWg = (da.numPackets + kFusedPpw - 1) / kFusedPpw;
-        hipLaunchKernelGGL(k_dec_fused_wg<MODE>, dim3(nEntWg + (da.numPackets + 3) / 4), dim3(256), 0, st, V, nEntWg, vf);
+        ALAC_TRY(launch_kernel(k_dec_fused_wg<MODE>, dim3(nEntWg + (da.numPackets + 3) / 4), dim3(256), st, V, nEntWg, vf));
     } else {
-        hipLaunchKernelGGL(k_dec_raw<MODE>, dim3(da.numPackets < 4096u ? da.numPackets : 4096u), dim3(256), 0, st, V, vf);
+        ALAC_TRY(launch_kernel(k_dec_raw<MODE>, dim3(da.numPackets < 4096u ? da.numPackets : 4096u), dim3(256), st, V, vf));
         // deferred residual stores, four 16-byte stores per round of sixteen consecutive residuals (round 2, 4-byte stores:
         // paid only up to two entropy waves per SIMD; with the wide stores, measured whole decode pass at 125 000 / 250 000 /
         // 500 000 packets: 9.31 -> 8.19, 19.4 -> 14.2, 38.1 -> 26.5 ms — the kernel was bound by the number of store
         // instructions whose 64 lanes hit 64 different cache lines, which a CU's address path takes one line at a time)
-        if (direct)
-            hipLaunchKernelGGL(k_dec_entropy_wide<true>, dim3((nEnt + kEntWavesPerWg - 1) / kEntWavesPerWg), dim3(64 * kEntWavesPerWg), 0, st, V, nEnt);
-        else
-            hipLaunchKernelGGL(k_dec_entropy_wide<false>, dim3((nEnt + kEntWavesPerWg - 1) / kEntWavesPerWg), dim3(64 * kEntWavesPerWg), 0, st, V, nEnt);
+        ALAC_TRY(launch_kernel(direct ? k_dec_entropy_wide<true> : k_dec_entropy_wide<false>,
+                               dim3((nEnt + kEntWavesPerWg - 1) / kEntWavesPerWg), dim3(64 * kEntWavesPerWg), st, V, nEnt));
         // chains sorted by tap count, one lane per chain
         // (five lists, each rounded up to whole waves)
         const dim3 ugrid(((uint32_t)((lanes + 63) / 64) + 6 + kEntWavesPerWg - 1) / kEntWavesPerWg), ublock(64 * kEntWavesPerWg);
-        if (da.bitDepth == 24) hipLaunchKernelGGL((k_dec_unpc_wide<24, MODE>), ugrid, ublock, 0, st, V, vf);
-        else if (da.bitDepth == 20) hipLaunchKernelGGL((k_dec_unpc_wide<20, MODE>), ugrid, ublock, 0, st, V, vf);
-        else hipLaunchKernelGGL((k_dec_unpc_wide<16, MODE>), ugrid, ublock, 0, st, V, vf);
+        if (da.bitDepth == 24) ALAC_TRY(launch_kernel(k_dec_unpc_wide<24, MODE>, ugrid, ublock, st, V, vf));
+        else if (da.bitDepth == 20) ALAC_TRY(launch_kernel(k_dec_unpc_wide<20, MODE>, ugrid, ublock, st, V, vf));
+        else ALAC_TRY(launch_kernel(k_dec_unpc_wide<16, MODE>, ugrid, ublock, st, V, vf));
     }
-    hipLaunchKernelGGL(k_dec_unpc, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), 0, st, V);
+    ALAC_TRY(launch_kernel(k_dec_unpc, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), st, V));
     switch (da.bitDepth) {
-    case 16: launch_unmix_v1<16, MODE>(V, vf, st); break;
-    case 20: launch_unmix_v1<20, MODE>(V, vf, st); break;
-    case 24: launch_unmix_v1<24, MODE>(V, vf, st); break;
-    case 32: launch_unmix_v1<32, MODE>(V, vf, st); break;
+    case 16: return launch_unmix_v1<16, MODE>(V, vf, st);
+    case 20: return launch_unmix_v1<20, MODE>(V, vf, st);
+    case 24: return launch_unmix_v1<24, MODE>(V, vf, st);
+    case 32: return launch_unmix_v1<32, MODE>(V, vf, st);
     default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 static hipError_t run_decode_v1_pass(const DecV1Args &V, hipStream_t st, bool stageFirst)
@@ -2217,9 +2212,10 @@ hipError_t launch_decode_v1_elements(const DecodeArgs &da, const McElement *el, 
                                      uint32_t *mismatch, hipStream_t st)
 {
     if (da.numPackets == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dec_stage, dim3(2048), dim3(256), 0, st, da.stream, da.offsets, da.numPackets, words, capWords, DecZero{nullptr, nullptr, 0});
-    (void)hipMemsetAsync(elemBit, 0, (size_t)da.numPackets * 4, st);
-    (void)hipMemsetAsync(mismatch, 0, 4, st);
+    ALAC_TRY(launch_kernel(k_dec_stage, dim3(2048), dim3(256), st, da.stream, da.offsets, da.numPackets, words, capWords,
+                           DecZero{nullptr, nullptr, 0}));
+    ALAC_TRY(hipMemsetAsync(elemBit, 0, (size_t)da.numPackets * 4, st));
+    ALAC_TRY(hipMemsetAsync(mismatch, 0, 4, st));
     for (uint32_t r = 0; r < numElements; r++) {
         DecodeArgs dr = da;
         dr.numChannels = el[r].channels;  // this round's elements as mono / stereo packets
@@ -2228,12 +2224,9 @@ hipError_t launch_decode_v1_elements(const DecodeArgs &da, const McElement *el, 
         V.round = r;
         V.outChannels = da.numChannels;
         V.outFirst = el[r].first;
-        const hipError_t e = run_decode_v1_pass(V, st, false);
-        if (e != hipSuccess) return e;
+        ALAC_TRY(run_decode_v1_pass(V, st, false));
     }
-    hipLaunchKernelGGL(k_dec_count_status, dim3((da.numPackets + 255) / 256), dim3(256), 0, st, da.statusOut, da.numPackets,
-                       -4, mismatch);
-    return hipGetLastError();
+    return launch_kernel(k_dec_count_status, dim3((da.numPackets + 255) / 256), dim3(256), st, da.statusOut, da.numPackets, -4, mismatch);
 }
 
 }  // namespace alacdev

@@ -928,13 +928,13 @@ __global__ __launch_bounds__(256) void k_pack(PackArgs A, uint32_t numPackets)
 // ------------------------------------------------------------------------------------------------
 
 template <int DEPTH>
-static void launch_scan_pack_depth(uint32_t channels, uint32_t *packetBytes, const PackArgs &pa, uint32_t numPackets,
-                                   hipStream_t st, hipEvent_t *ev, bool recordScan = true)
+static hipError_t launch_scan_pack_depth(uint32_t channels, uint32_t *packetBytes, const PackArgs &pa, uint32_t numPackets,
+                                         hipStream_t st, hipEvent_t *ev, bool recordScan = true)
 {
-    if (ev && recordScan) (void)hipEventRecord(ev[kStageScan], st);
-    hipLaunchKernelGGL(k_scan_sizes, dim3(numPackets / 1024 + 1), dim3(1024), 0, st, (const uint32_t *)packetBytes, (uint64_t *)pa.offsets,
-                       numPackets, pa.segBad);
-    if (ev) (void)hipEventRecord(ev[kStagePack], st);
+    if (ev && recordScan) ALAC_TRY(hipEventRecord(ev[kStageScan], st));
+    ALAC_TRY(launch_kernel(k_scan_sizes, dim3(numPackets / 1024 + 1), dim3(1024), st, (const uint32_t *)packetBytes,
+                           (uint64_t *)pa.offsets, numPackets, pa.segBad));
+    if (ev) ALAC_TRY(hipEventRecord(ev[kStagePack], st));
     // One workgroup of 128 threads per packet (ALAC_HIP_PACK_TPB / ALAC_HIP_PACK_WGS override; with fewer workgroups than
     // packets each walks several).  Measured at 10 000 16-bit packets / 125 000 (tools/dispatch_rate_microbench.hip for the
     // plain-copy floor): 64 threads 0.064 / 0.66 ms, 128: 0.064 / 0.66, 256: 0.067 / 0.74; 2048 persistent workgroups
@@ -946,55 +946,54 @@ static void launch_scan_pack_depth(uint32_t channels, uint32_t *packetBytes, con
     static const uint32_t wgs = getenv("ALAC_HIP_PACK_WGS") ? (uint32_t)atoi(getenv("ALAC_HIP_PACK_WGS")) : (1u << 20);
     const uint32_t grid = numPackets < wgs ? numPackets : wgs;
     if (channels == 2)
-        hipLaunchKernelGGL((k_pack<DEPTH, 2>), dim3(grid), dim3(tpb), 0, st, pa, numPackets);
+        ALAC_TRY(launch_kernel(k_pack<DEPTH, 2>, dim3(grid), dim3(tpb), st, pa, numPackets));
     else
-        hipLaunchKernelGGL((k_pack<DEPTH, 1>), dim3(grid), dim3(tpb), 0, st, pa, numPackets);
-    if (ev) (void)hipEventRecord(ev[kNumStages], st);
+        ALAC_TRY(launch_kernel(k_pack<DEPTH, 1>, dim3(grid), dim3(tpb), st, pa, numPackets));
+    return ev ? hipEventRecord(ev[kNumStages], st) : hipSuccess;
 }
 
-void launch_scan_sizes(const uint32_t *sizes, uint64_t *offsets, uint32_t n, hipStream_t st, const uint32_t *segBad)
+hipError_t launch_scan_sizes(const uint32_t *sizes, uint64_t *offsets, uint32_t n, hipStream_t st, const uint32_t *segBad)
 {
-    hipLaunchKernelGGL(k_scan_sizes, dim3(n / 1024 + 1), dim3(1024), 0, st, sizes, offsets, n, segBad);
+    return launch_kernel(k_scan_sizes, dim3(n / 1024 + 1), dim3(1024), st, sizes, offsets, n, segBad);
 }
 
-void launch_scan_pack(uint32_t depth, uint32_t channels, uint32_t *packetBytes, const PackArgs &pa, uint32_t numPackets,
-                      hipStream_t st, hipEvent_t *ev, bool recordScan)
+hipError_t launch_scan_pack(uint32_t depth, uint32_t channels, uint32_t *packetBytes, const PackArgs &pa, uint32_t numPackets,
+                            hipStream_t st, hipEvent_t *ev, bool recordScan)
 {
     switch (depth) {
-    case 16: launch_scan_pack_depth<16>(channels, packetBytes, pa, numPackets, st, ev, recordScan); break;
-    case 20: launch_scan_pack_depth<20>(channels, packetBytes, pa, numPackets, st, ev, recordScan); break;
-    case 24: launch_scan_pack_depth<24>(channels, packetBytes, pa, numPackets, st, ev, recordScan); break;
-    default: launch_scan_pack_depth<32>(channels, packetBytes, pa, numPackets, st, ev, recordScan); break;
+    case 16: return launch_scan_pack_depth<16>(channels, packetBytes, pa, numPackets, st, ev, recordScan);
+    case 20: return launch_scan_pack_depth<20>(channels, packetBytes, pa, numPackets, st, ev, recordScan);
+    case 24: return launch_scan_pack_depth<24>(channels, packetBytes, pa, numPackets, st, ev, recordScan);
+    default: return launch_scan_pack_depth<32>(channels, packetBytes, pa, numPackets, st, ev, recordScan);
     }
 }
 
 template <int DEPTH>
-static void launch_encode_depth(const EncodeArgs &ea, const PackArgs &pa, uint32_t channels,
-                                uint32_t numPackets, hipStream_t st, hipEvent_t *ev)
+static hipError_t launch_encode_depth(const EncodeArgs &ea, const PackArgs &pa, uint32_t channels,
+                                      uint32_t numPackets, hipStream_t st, hipEvent_t *ev)
 {
     if (ev)
-        for (int i = 0; i <= kStageLms3; i++) (void)hipEventRecord(ev[i], st);
+        for (int i = 0; i <= kStageLms3; i++) ALAC_TRY(hipEventRecord(ev[i], st));
     if (channels == 2) {
         const uint32_t lanes = ea.numSegments * 2;
-        hipLaunchKernelGGL(k_encode_stereo<DEPTH>, dim3((lanes + 63) / 64), dim3(64), 0, st, ea);
+        ALAC_TRY(launch_kernel(k_encode_stereo<DEPTH>, dim3((lanes + 63) / 64), dim3(64), st, ea));
     } else {
-        hipLaunchKernelGGL(k_encode_mono<DEPTH>, dim3((ea.numSegments + 63) / 64), dim3(64), 0, st, ea);
+        ALAC_TRY(launch_kernel(k_encode_mono<DEPTH>, dim3((ea.numSegments + 63) / 64), dim3(64), st, ea));
     }
-    if (ev) (void)hipEventRecord(ev[kStageGol3], st);
-    launch_scan_pack_depth<DEPTH>(channels, ea.packetBytes, pa, numPackets, st, ev);
+    if (ev) ALAC_TRY(hipEventRecord(ev[kStageGol3], st));
+    return launch_scan_pack_depth<DEPTH>(channels, ea.packetBytes, pa, numPackets, st, ev);
 }
 
 hipError_t launch_encode(uint32_t depth, uint32_t channels, const EncodeArgs &ea, const PackArgs &pa,
                          uint32_t numPackets, hipStream_t st, hipEvent_t *ev)
 {
     switch (depth) {
-    case 16: launch_encode_depth<16>(ea, pa, channels, numPackets, st, ev); break;
-    case 20: launch_encode_depth<20>(ea, pa, channels, numPackets, st, ev); break;
-    case 24: launch_encode_depth<24>(ea, pa, channels, numPackets, st, ev); break;
-    case 32: launch_encode_depth<32>(ea, pa, channels, numPackets, st, ev); break;
+    case 16: return launch_encode_depth<16>(ea, pa, channels, numPackets, st, ev);
+    case 20: return launch_encode_depth<20>(ea, pa, channels, numPackets, st, ev);
+    case 24: return launch_encode_depth<24>(ea, pa, channels, numPackets, st, ev);
+    case 32: return launch_encode_depth<32>(ea, pa, channels, numPackets, st, ev);
     default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 }  // namespace alacdev

@@ -25,12 +25,12 @@ __global__ void k_check_segments(const uint32_t *segFirst, uint32_t numSegments,
     if (bad && segBad) *segBad = 1u;  // what the launches behind this one on the stream test (EncodeArgs::segBad)
 }
 
-void launch_check_segments(const uint32_t *segFirst, uint32_t numSegments, uint32_t numPackets, uint32_t maxSeg, uint32_t *err,
-                           uint32_t *segBad, hipStream_t st)
+hipError_t launch_check_segments(const uint32_t *segFirst, uint32_t numSegments, uint32_t numPackets, uint32_t maxSeg, uint32_t *err,
+                                 uint32_t *segBad, hipStream_t st)
 {
-    if (segBad) (void)hipMemsetAsync(segBad, 0, 4, st);
-    hipLaunchKernelGGL(k_check_segments, dim3((numSegments + 255) / 256), dim3(256), 0, st, segFirst, numSegments, numPackets, maxSeg, err,
-                       segBad);
+    if (segBad) ALAC_TRY(hipMemsetAsync(segBad, 0, 4, st));
+    return launch_kernel(k_check_segments, dim3((numSegments + 255) / 256), dim3(256), st, segFirst, numSegments, numPackets, maxSeg,
+                         err, segBad);
 }
 
 // chains beyond what one 2-lane predictor wave per SIMD holds (1024 SIMDs x 32 chains x 2): throughput regime
@@ -104,14 +104,11 @@ hipError_t launch_encode_v1(uint32_t depth, uint32_t channels, const V1Args &A, 
                             const V1Streams &vs, uint32_t numPackets, uint32_t maxSegPackets, hipStream_t st, hipEvent_t *ev)
 {
     if (initState)
-        hipLaunchKernelGGL(k_init_state, dim3((A.S.numSegments * 64 + 255) / 256), dim3(256), 0, st, A.state, A.S.numSegments);
+        ALAC_TRY(launch_kernel(k_init_state, dim3((A.S.numSegments * 64 + 255) / 256), dim3(256), st, A.state, A.S.numSegments));
 #define V1_CASE(D)                                                                                   \
     case D:                                                                                          \
-        if (channels == 2)                                                                           \
-            launch_v1_typed<D, 2>(A, P, numPackets, maxSegPackets, st, ev, pa, vs);                  \
-        else                                                                                         \
-            launch_v1_typed<D, 1>(A, P, numPackets, maxSegPackets, st, ev, pa, vs);                  \
-        break;
+        return channels == 2 ? launch_v1_typed<D, 2>(A, P, numPackets, maxSegPackets, st, ev, pa, vs) \
+                             : launch_v1_typed<D, 1>(A, P, numPackets, maxSegPackets, st, ev, pa, vs);
     switch (depth) {
         V1_CASE(16)
         V1_CASE(20)
@@ -120,7 +117,6 @@ hipError_t launch_encode_v1(uint32_t depth, uint32_t channels, const V1Args &A, 
     default: return hipErrorInvalidValue;
     }
 #undef V1_CASE
-    return hipGetLastError();
 }
 
 }  // namespace alacdev

@@ -3,6 +3,6 @@
 #include "alac_encode_v1_impl.hpp"
 
 namespace alacdev {
-template void launch_v1_typed<20, 1>(const V1Args &, const V1Plan &, uint32_t, uint32_t, hipStream_t, hipEvent_t *, const PackArgs &, const V1Streams &);
-template void launch_v1_typed<20, 2>(const V1Args &, const V1Plan &, uint32_t, uint32_t, hipStream_t, hipEvent_t *, const PackArgs &, const V1Streams &);
+template hipError_t launch_v1_typed<20, 1>(const V1Args &, const V1Plan &, uint32_t, uint32_t, hipStream_t, hipEvent_t *, const PackArgs &, const V1Streams &);
+template hipError_t launch_v1_typed<20, 2>(const V1Args &, const V1Plan &, uint32_t, uint32_t, hipStream_t, hipEvent_t *, const PackArgs &, const V1Streams &);
 }  // namespace alacdev

@@ -1809,16 +1809,16 @@ __global__ void k_finalize(PacketRec *recs, uint32_t *packetBytes, uint32_t numP
 // throughput regime, the splice of the split coder, SetFastMode's decision) are compiled ONCE, in alac_encode_v1_common.hip,
 // which defines these launch wrappers; the four per-depth translation units only call them.  (Round 3 instantiated every one
 // of them in each of the four: 48 of the library's kernels were copies.)
-void v1c_decide_fast(uint32_t nseg, hipStream_t st, const V1Args &A);
-void v1c_gol_count1(int ch, uint32_t cblocks, hipStream_t st, const V1Args &A, uint32_t chanBits);
-void v1c_gol_count2(int ch, uint32_t cblocks, hipStream_t st, const V1Args &A, uint32_t chanBits);
-void v1c_gol_count2_w(int ch, uint32_t cblocks, hipStream_t st, const V1Args &A, uint32_t chanBits);
-void v1c_class_layout(int ch, uint32_t nseg, hipStream_t st, const V1Args &A, uint32_t *blockCnt);
-void v1c_splice_split(int ch, uint32_t nseg, hipStream_t st, const V1Args &A);
-void v1c_gol_final(int ch, uint32_t cblocks, hipStream_t st, const V1Args &A, uint32_t chanBits);
+hipError_t v1c_decide_fast(uint32_t nseg, hipStream_t st, const V1Args &A);
+hipError_t v1c_gol_count1(int ch, uint32_t cblocks, hipStream_t st, const V1Args &A, uint32_t chanBits);
+hipError_t v1c_gol_count2(int ch, uint32_t cblocks, hipStream_t st, const V1Args &A, uint32_t chanBits);
+hipError_t v1c_gol_count2_w(int ch, uint32_t cblocks, hipStream_t st, const V1Args &A, uint32_t chanBits);
+hipError_t v1c_class_layout(int ch, uint32_t nseg, hipStream_t st, const V1Args &A, uint32_t *blockCnt);
+hipError_t v1c_splice_split(int ch, uint32_t nseg, hipStream_t st, const V1Args &A);
+hipError_t v1c_gol_final(int ch, uint32_t cblocks, hipStream_t st, const V1Args &A, uint32_t chanBits);
 template <int DEPTH, int CH>
-void launch_v1_typed(const V1Args &A0, const V1Plan &P, uint32_t numPackets, uint32_t maxSegPackets, hipStream_t st, hipEvent_t *ev,
-                     const PackArgs &pa, const V1Streams &vs)
+hipError_t launch_v1_typed(const V1Args &A0, const V1Plan &P, uint32_t numPackets, uint32_t maxSegPackets, hipStream_t st,
+                           hipEvent_t *ev, const PackArgs &pa, const V1Streams &vs)
 {
     // Shapes (V1Plan, v1_plan in alac_encode_v1.hip):
     //  Tiny / Latency  at most ~one predictor wave per SIMD: a stage is as slow as its longest serial chain, so the predictor
@@ -1844,7 +1844,7 @@ void launch_v1_typed(const V1Args &A0, const V1Plan &P, uint32_t numPackets, uin
     const uint32_t nLms16 = (nseg * CH + 15) / 16;   // ... of 16 chains (four lanes per chain)
     const dim3 wg(64 * kWavesPerWg);
     auto wgs = [](uint32_t waves) { return dim3((waves + kWavesPerWg - 1) / kWavesPerWg); };
-    auto clear = [](uint32_t *words, uint32_t n, hipStream_t s) { (void)hipMemsetAsync(words, 0, ((size_t)n * 4 + 15) & ~(size_t)15, s); };
+    auto clear = [](uint32_t *words, uint32_t n, hipStream_t s) { return hipMemsetAsync(words, 0, ((size_t)n * 4 + 15) & ~(size_t)15, s); };
     const bool thru = P.shape == V1Shape::Throughput, tiny = P.shape == V1Shape::Tiny, fold = P.shape == V1Shape::Latency;
     V1Args A = A0;
     // Chained tiny batches (a file = one chain of packets): packet position p + 1's mixRes search only needs the 8-tap rows,
@@ -1855,132 +1855,133 @@ void launch_v1_typed(const V1Args &A0, const V1Plan &P, uint32_t numPackets, uin
     // disappears behind the final pass.
     if (P.overlap) {
         A.rowReady = A0.ovRowReady;
-        (void)hipMemsetAsync(A.rowReady, 0, (size_t)A0.chainsPad * 4, st);
+        ALAC_TRY(hipMemsetAsync(A.rowReady, 0, (size_t)A0.chainsPad * 4, st));
     }
     for (uint32_t pos = 0; pos < maxSegPackets; pos++) {
         A.S.pos = pos;
         A.virgin = pos == 0 ? A0.virgin : 0u;
         const hipStream_t sp = (P.overlap && (pos & 1)) ? vs.side[0] : st;
-        if (P.overlap && pos > 0) (void)hipStreamWaitEvent(sp, vs.stagger[(pos - 1) & 1], 0);  // decide2 of pos - 1
+        if (P.overlap && pos > 0) ALAC_TRY(hipStreamWaitEvent(sp, vs.stagger[(pos - 1) & 1], 0));  // decide2 of pos - 1
         hipEvent_t *e = pos + 1 == maxSegPackets ? ev : nullptr;  // stage events of the last position: block 0 of ev
-        auto mark = [&](EncodeStage k) {
-            if (e) (void)hipEventRecord(e[k], sp);
-        };
-        mark(kStageLms1);
-        if (fold) (void)hipMemsetAsync(A.flags, 0, (size_t)2 * (A0.chainsPad / 8 + 16) * 4, sp);  // both sets of progress words
+        auto mark = [&](EncodeStage k) { return e ? hipEventRecord(e[k], sp) : hipSuccess; };
+        ALAC_TRY(mark(kStageLms1));
+        if (fold) ALAC_TRY(hipMemsetAsync(A.flags, 0, (size_t)2 * (A0.chainsPad / 8 + 16) * 4, sp));  // both sets of progress words
         // ---- mixRes search (stereo) and numU / numV converge passes, or SetFastMode's decision
         if (P.fast) {
-            mark(kStageGol1);
-            mark(kStageLms2);
-            mark(kStageGol2);
-            v1c_decide_fast(nseg, sp, A);
+            ALAC_TRY(mark(kStageGol1));
+            ALAC_TRY(mark(kStageLms2));
+            ALAC_TRY(mark(kStageGol2));
+            ALAC_TRY(v1c_decide_fast(nseg, sp, A));
         } else {
             if constexpr (CH == 2) {
                 if (P.fusedSearch && tiny) {
-                    clear(A.flags, nLms16, sp);
-                    hipLaunchKernelGGL((k_search1_fused<DEPTH, 2, 4>), wgs(nLms16 + 5 * cblocks), wg, 0, sp, A, nLms16, cblocks, chanBits);
-                    mark(kStageGol1);
+                    ALAC_TRY(clear(A.flags, nLms16, sp));
+                    ALAC_TRY(launch_kernel(k_search1_fused<DEPTH, 2, 4>, wgs(nLms16 + 5 * cblocks), wg, sp, A, nLms16, cblocks,
+                                           chanBits));
+                    ALAC_TRY(mark(kStageGol1));
                 } else if (P.fusedSearch) {
-                    if (!fold) clear(A.flags, nLms, sp);
+                    if (!fold) ALAC_TRY(clear(A.flags, nLms, sp));
                     // ONE count wave per 64 chains walks the five planes behind its two producers (WALK)
-                    hipLaunchKernelGGL((k_search1_fused<DEPTH, 4, 2, true>), wgs(3 * cblocks), wg, 0, sp, A, nLms, cblocks, chanBits);
-                    mark(kStageGol1);
+                    ALAC_TRY(launch_kernel(k_search1_fused<DEPTH, 4, 2, true>, wgs(3 * cblocks), wg, sp, A, nLms, cblocks,
+                                           chanBits));
+                    ALAC_TRY(mark(kStageGol1));
                 } else if (thru) {
                     // predictor passes and their bit counts in one lane: no residual planes except the mixRes = 4 pass's
-                    hipLaunchKernelGGL((k_search1_lane<DEPTH>), dim3(cblocks), dim3(64), 0, sp, A, chanBits);
-                    mark(kStageGol1);
+                    ALAC_TRY(launch_kernel(k_search1_lane<DEPTH>, dim3(cblocks), dim3(64), sp, A, chanBits));
+                    ALAC_TRY(mark(kStageGol1));
                 } else {
-                    hipLaunchKernelGGL((k_lms_search1<DEPTH, 4, 2>), dim3(nLms), dim3(64), 0, sp, A);
-                    mark(kStageGol1);
-                    v1c_gol_count1(CH, cblocks, sp, A, chanBits);
+                    ALAC_TRY(launch_kernel(k_lms_search1<DEPTH, 4, 2>, dim3(nLms), dim3(64), sp, A));
+                    ALAC_TRY(mark(kStageGol1));
+                    ALAC_TRY(v1c_gol_count1(CH, cblocks, sp, A, chanBits));
                 }
             } else {
-                mark(kStageGol1);
+                ALAC_TRY(mark(kStageGol1));
             }
-            if (P.overlap && pos > 0) (void)hipStreamWaitEvent(sp, vs.join[(pos - 1) & 1], 0);  // final pass of pos - 1
-            mark(kStageLms2);
+            if (P.overlap && pos > 0) ALAC_TRY(hipStreamWaitEvent(sp, vs.join[(pos - 1) & 1], 0));  // final pass of pos - 1
+            ALAC_TRY(mark(kStageLms2));
             if (tiny)
-                hipLaunchKernelGGL((k_lms_search2<DEPTH, CH, 2, 2, 2, 4>), dim3(nLms + nLms16), dim3(64), 0, sp, A, nLms);
+                ALAC_TRY(launch_kernel(k_lms_search2<DEPTH, CH, 2, 2, 2, 4>, dim3(nLms + nLms16), dim3(64), sp, A, nLms));
             else if (thru)  // 64 chains per wave for both rows, two waves per SIMD; every lane counts its own residuals
-                hipLaunchKernelGGL((k_search2_lane<DEPTH, CH>), dim3(2 * cblocks), dim3(64), 0, sp, A, cblocks, chanBits);
+                ALAC_TRY(launch_kernel(k_search2_lane<DEPTH, CH>, dim3(2 * cblocks), dim3(64), sp, A, cblocks, chanBits));
             else if (P.fused())  // latency regime: workers (one wave per SIMD by construction)
-                hipLaunchKernelGGL((k_lms_search2_w<DEPTH, CH>), wgs(3 * cblocks), wg, 0, sp, A, cblocks, nLms);
+                ALAC_TRY(launch_kernel(k_lms_search2_w<DEPTH, CH>, wgs(3 * cblocks), wg, sp, A, cblocks, nLms));
             else
-                hipLaunchKernelGGL((k_lms_search2<DEPTH, CH>), dim3(cblocks + nLms), dim3(64), 0, sp, A, cblocks);
-            mark(kStageGol2);
+                ALAC_TRY(launch_kernel(k_lms_search2<DEPTH, CH>, dim3(cblocks + nLms), dim3(64), sp, A, cblocks));
+            ALAC_TRY(mark(kStageGol2));
             if (P.fused())
-                v1c_gol_count2_w(CH, cblocks, sp, A, chanBits);
+                ALAC_TRY(v1c_gol_count2_w(CH, cblocks, sp, A, chanBits));
             else if (!thru)
-                v1c_gol_count2(CH, cblocks, sp, A, chanBits);
-            if (!fold) hipLaunchKernelGGL((k_decide2<DEPTH, CH>), dim3((nseg + 255) / 256), dim3(256), 0, sp, A);
+                ALAC_TRY(v1c_gol_count2(CH, cblocks, sp, A, chanBits));
+            if (!fold) ALAC_TRY(launch_kernel(k_decide2<DEPTH, CH>, dim3((nseg + 255) / 256), dim3(256), sp, A));
         }
-        if (P.overlap) (void)hipEventRecord(vs.stagger[pos & 1], sp);
+        if (P.overlap) ALAC_TRY(hipEventRecord(vs.stagger[pos & 1], sp));
         // ---- final pass: predictor and entropy coder
-        mark(kStageLms3);
+        ALAC_TRY(mark(kStageLms3));
         switch (P.shape) {
         case V1Shape::Throughput: {
             // final pass by packet class: compact the packets that still need it (k_class_count, k_class_assign), then per class
             // the lane mapping that fits it — escaped packets cost nothing, all-4-tap packets run 64 chains per wave
             const uint32_t cwaves = (((nseg * CH + 63) & ~63u) + 64) / 64;  // worst case per region, + the padding
-            v1c_class_layout(CH, nseg, sp, A, (uint32_t *)(A0.cls + 1));
+            ALAC_TRY(v1c_class_layout(CH, nseg, sp, A, (uint32_t *)(A0.cls + 1)));
             // the two classes are independent from here on: predictor -> coder of the 4-tap class on a side stream beside
             // those of the 8-tap class.  Each kernel alone leaves the machine unevenly filled (a few thousand waves of
             // ~1 ms each on 1024 SIMDs, LDS-limited to 6 predictor waves per CU); side by side the light coder waves
             // of one class fill what the predictor waves of the other cannot use.
             hipStream_t s2 = vs.side[0];
-            (void)hipEventRecord(vs.fork, sp);
-            (void)hipStreamWaitEvent(s2, vs.fork, 0);
+            ALAC_TRY(hipEventRecord(vs.fork, sp));
+            ALAC_TRY(hipStreamWaitEvent(s2, vs.fork, 0));
             // predictor and coder of a chain in one lane: no residual plane (k_class_final)
-            hipLaunchKernelGGL((k_class_final<DEPTH, CH, 8>), dim3(cwaves), dim3(64), 0, sp, A, chanBits, 0u);
-            hipLaunchKernelGGL((k_class_final<DEPTH, CH, 4>), dim3(cwaves), dim3(64), 0, s2, A, chanBits, 1u);
-            (void)hipEventRecord(vs.join[0], s2);
-            (void)hipStreamWaitEvent(st, vs.join[0], 0);
-            mark(kStageGol3);
+            ALAC_TRY(launch_kernel(k_class_final<DEPTH, CH, 8>, dim3(cwaves), dim3(64), sp, A, chanBits, 0u));
+            ALAC_TRY(launch_kernel(k_class_final<DEPTH, CH, 4>, dim3(cwaves), dim3(64), s2, A, chanBits, 1u));
+            ALAC_TRY(hipEventRecord(vs.join[0], s2));
+            ALAC_TRY(hipStreamWaitEvent(st, vs.join[0], 0));
+            ALAC_TRY(mark(kStageGol3));
             break;
         }
         case V1Shape::Tiny:
-            clear(A.flagsF, nLms16, sp);
+            ALAC_TRY(clear(A.flagsF, nLms16, sp));
             if (P.split) {
-                hipLaunchKernelGGL((k_final_fused<DEPTH, CH, 2, 4, true>), wgs(nLms16 + 2 * cblocks), wg, 0, sp, A, nLms16, chanBits,
-                                   cblocks, nLms16 + 2 * cblocks);
-                v1c_splice_split(CH, nseg, sp, A);
+                ALAC_TRY(launch_kernel(k_final_fused<DEPTH, CH, 2, 4, true>, wgs(nLms16 + 2 * cblocks), wg, sp, A, nLms16, chanBits,
+                                       cblocks, nLms16 + 2 * cblocks));
+                ALAC_TRY(v1c_splice_split(CH, nseg, sp, A));
             } else {
-                hipLaunchKernelGGL((k_final_fused<DEPTH, CH, 2, 4>), wgs(5 * cblocks), wg, 0, sp, A, nLms16, chanBits, 0u, 5 * cblocks);
+                ALAC_TRY(launch_kernel(k_final_fused<DEPTH, CH, 2, 4>, wgs(5 * cblocks), wg, sp, A, nLms16, chanBits, 0u,
+                                       5 * cblocks));
             }
-            mark(kStageGol3);
+            ALAC_TRY(mark(kStageGol3));
             break;
         case V1Shape::Latency:
             // (LAZY = true, the throughput regime's "store completed words only, four at a time", was measured here in round 3
             // with the interleaved roles: coder waves 2.20 M instead of 1.70 M cycles, launch 0.95 instead of 0.75 ms — the
             // queue's selects and branch cost a lone wave more than the scattered stores it saves)
-            hipLaunchKernelGGL((k_final_fused<DEPTH, CH, 4, 2, false, true>), wgs(3 * cblocks), wg, 0, sp, A, nLms, chanBits, 0u,
-                               3 * cblocks);
-            mark(kStageGol3);
+            ALAC_TRY(launch_kernel(k_final_fused<DEPTH, CH, 4, 2, false, true>, wgs(3 * cblocks), wg, sp, A, nLms, chanBits, 0u,
+                                   3 * cblocks));
+            ALAC_TRY(mark(kStageGol3));
             break;
         case V1Shape::LatencyUnfolded:
-            clear(A.flagsF, nLms, sp);
-            hipLaunchKernelGGL((k_final_fused<DEPTH, CH>), wgs(3 * cblocks), wg, 0, sp, A, nLms, chanBits, 0u, 3 * cblocks);
-            mark(kStageGol3);
+            ALAC_TRY(clear(A.flagsF, nLms, sp));
+            ALAC_TRY(launch_kernel(k_final_fused<DEPTH, CH>, wgs(3 * cblocks), wg, sp, A, nLms, chanBits, 0u, 3 * cblocks));
+            ALAC_TRY(mark(kStageGol3));
             break;
         default:  // Stagewise (Lane never gets here)
-            hipLaunchKernelGGL((k_lms_final<DEPTH, CH>), dim3(nLms), dim3(64), 0, sp, A);
-            mark(kStageGol3);
-            v1c_gol_final(CH, cblocks, sp, A, chanBits);
+            ALAC_TRY(launch_kernel(k_lms_final<DEPTH, CH>, dim3(nLms), dim3(64), sp, A));
+            ALAC_TRY(mark(kStageGol3));
+            ALAC_TRY(v1c_gol_final(CH, cblocks, sp, A, chanBits));
             break;
         }
         if (P.overlap) {
-            (void)hipEventRecord(vs.join[pos & 1], sp);
-            if (pos + 1 == maxSegPackets && sp != st) (void)hipStreamWaitEvent(st, vs.join[pos & 1], 0);
+            ALAC_TRY(hipEventRecord(vs.join[pos & 1], sp));
+            if (pos + 1 == maxSegPackets && sp != st) ALAC_TRY(hipStreamWaitEvent(st, vs.join[pos & 1], 0));
         }
-        if (e) (void)hipEventRecord(e[kStageScan], st);  // end marker of the last stage
+        if (e) ALAC_TRY(hipEventRecord(e[kStageScan], st));  // end marker of the last stage
     }
     // sizes, scan, pack: once, on the caller's stream; their events live in block 1 of ev
     hipEvent_t *evt = ev ? ev + (size_t)(kNumStages + 1) : nullptr;
-    if (evt) (void)hipEventRecord(evt[kStageScan], st);
+    if (evt) ALAC_TRY(hipEventRecord(evt[kStageScan], st));
     if (!fold)  // (the folded final launches have written the packet sizes)
-        hipLaunchKernelGGL((k_finalize<DEPTH, CH>), dim3((numPackets + 255) / 256), dim3(256), 0, st, A0.recs, A0.packetBytes,
-                           numPackets, A0.S.frameSize, pa.segBad);
-    launch_scan_pack(DEPTH, CH, A0.packetBytes, pa, numPackets, st, evt, false);
+        ALAC_TRY(launch_kernel(k_finalize<DEPTH, CH>, dim3((numPackets + 255) / 256), dim3(256), st, A0.recs, A0.packetBytes,
+                               numPackets, A0.S.frameSize, pa.segBad));
+    return launch_scan_pack(DEPTH, CH, A0.packetBytes, pa, numPackets, st, evt, false);
 }
 
 }  // namespace alacdev

@@ -71,8 +71,8 @@ struct V1Args {
 // search + final passes of every packet position as the plan says, then finalize / scan / pack (alac_encode_v1_impl.hpp);
 // explicitly instantiated for DEPTH in {16, 20, 24, 32} x CH in {1, 2}
 template <int DEPTH, int CH>
-void launch_v1_typed(const V1Args &A0, const V1Plan &P, uint32_t numPackets, uint32_t maxSegPackets, hipStream_t st, hipEvent_t *ev,
-                     const PackArgs &pa, const V1Streams &vs);
+hipError_t launch_v1_typed(const V1Args &A0, const V1Plan &P, uint32_t numPackets, uint32_t maxSegPackets, hipStream_t st,
+                           hipEvent_t *ev, const PackArgs &pa, const V1Streams &vs);
 // the whole tap-parallel encode of a mono / stereo batch (alac_encode_v1.hip); initState: write init_coefs into the rows first
 // (rows that neither hold the caller's state nor are taken as constants, V1Args::virgin); ev (nullable): kEventBlocks blocks of
 // kNumStages + 1 events

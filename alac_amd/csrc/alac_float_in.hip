@@ -180,27 +180,20 @@ __global__ __launch_bounds__(256) void k_float_to_pcm(FloatInArgs a, uint64_t bl
 }
 
 template <int DEPTH, bool DITHER>
-static void launch_depth(const FloatInArgs &a, const FloatDitherArgs &dz, FloatLayout layout, dim3 grid, uint64_t bpp,
-                         hipStream_t st)
+static hipError_t launch_depth(const FloatInArgs &a, const FloatDitherArgs &dz, FloatLayout layout, dim3 grid, uint64_t bpp,
+                               hipStream_t st)
 {
-    if (layout == kFloatGeneral)
-        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 0, kFloatGeneral, DITHER>), grid, dim3(256), 0, st, a, bpp, dz);
-    else if (a.channels == 1)
-        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 1, kFloatPlanar, DITHER>), grid, dim3(256), 0, st, a, bpp, dz);
-    else if (layout == kFloatPlanar)
-        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 2, kFloatPlanar, DITHER>), grid, dim3(256), 0, st, a, bpp, dz);
-    else
-        hipLaunchKernelGGL((k_float_to_pcm<DEPTH, 2, kFloatInterleaved, DITHER>), grid, dim3(256), 0, st, a, bpp, dz);
+    if (layout == kFloatGeneral) return launch_kernel(k_float_to_pcm<DEPTH, 0, kFloatGeneral, DITHER>, grid, dim3(256), st, a, bpp, dz);
+    if (a.channels == 1) return launch_kernel(k_float_to_pcm<DEPTH, 1, kFloatPlanar, DITHER>, grid, dim3(256), st, a, bpp, dz);
+    if (layout == kFloatPlanar) return launch_kernel(k_float_to_pcm<DEPTH, 2, kFloatPlanar, DITHER>, grid, dim3(256), st, a, bpp, dz);
+    return launch_kernel(k_float_to_pcm<DEPTH, 2, kFloatInterleaved, DITHER>, grid, dim3(256), st, a, bpp, dz);
 }
 
 hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t st, const FloatDitherArgs *dither)
 {
     if (dither && depth != 16 && depth != 20 && depth != 24) return hipErrorInvalidValue;  // no dither at 32 bits
     if (a.numPackets == 0) return hipSuccess;
-    if (a.clipped) {
-        const hipError_t e = hipMemsetAsync(a.clipped, 0, (uint64_t)a.numPackets * 4, st);
-        if (e != hipSuccess) return e;
-    }
+    if (a.clipped) ALAC_TRY(hipMemsetAsync(a.clipped, 0, (uint64_t)a.numPackets * 4, st));
     // the vector paths: whole 4-frame groups inside a packet, 16-byte aligned float4 loads at every group
     const FloatLayout layout =
         a.frameSize % 4 == 0 ? float_layout(a.in, a.channels, a.channelStride, a.frameStride) : kFloatGeneral;
@@ -209,20 +202,18 @@ hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t
     const dim3 grid((uint32_t)(blocks < (1u << 22) ? blocks : (1u << 22)));
     if (dither) {
         switch (depth) {
-        case 16: launch_depth<16, true>(a, *dither, layout, grid, bpp, st); break;
-        case 20: launch_depth<20, true>(a, *dither, layout, grid, bpp, st); break;
-        default: launch_depth<24, true>(a, *dither, layout, grid, bpp, st); break;
+        case 16: return launch_depth<16, true>(a, *dither, layout, grid, bpp, st);
+        case 20: return launch_depth<20, true>(a, *dither, layout, grid, bpp, st);
+        default: return launch_depth<24, true>(a, *dither, layout, grid, bpp, st);
         }
-        return hipGetLastError();
     }
     const FloatDitherArgs none = {};
     switch (depth) {
-    case 16: launch_depth<16, false>(a, none, layout, grid, bpp, st); break;
-    case 20: launch_depth<20, false>(a, none, layout, grid, bpp, st); break;
-    case 24: launch_depth<24, false>(a, none, layout, grid, bpp, st); break;
-    default: launch_depth<32, false>(a, none, layout, grid, bpp, st); break;
+    case 16: return launch_depth<16, false>(a, none, layout, grid, bpp, st);
+    case 20: return launch_depth<20, false>(a, none, layout, grid, bpp, st);
+    case 24: return launch_depth<24, false>(a, none, layout, grid, bpp, st);
+    default: return launch_depth<32, false>(a, none, layout, grid, bpp, st);
     }
-    return hipGetLastError();
 }
 
 }  // namespace alacdev

@@ -195,21 +195,15 @@ constexpr uint32_t kProbeMaxBlocks = 1024;
 hipError_t launch_float_probe(const FloatProbeArgs &a, hipStream_t st)
 {
     if (a.numSegments == 0) return hipErrorInvalidValue;
-    const hipError_t e = hipMemsetAsync(a.reports, 0, (uint64_t)a.numSegments * 32, st);
-    if (e != hipSuccess) return e;
+    ALAC_TRY(hipMemsetAsync(a.reports, 0, (uint64_t)a.numSegments * 32, st));
     if (a.hi <= a.lo) return hipSuccess;
     const FloatLayout layout = float_layout(a.in, a.channels, a.channelStride, a.frameStride);
     const uint64_t blocks = (a.hi - (a.lo & ~3ull) + 1023) / 1024;
     const dim3 grid((uint32_t)(blocks < kProbeMaxBlocks ? blocks : kProbeMaxBlocks));
-    if (layout == kFloatGeneral)
-        hipLaunchKernelGGL((k_float_probe<0, kFloatGeneral>), grid, dim3(256), 0, st, a);
-    else if (a.channels == 1)
-        hipLaunchKernelGGL((k_float_probe<1, kFloatPlanar>), grid, dim3(256), 0, st, a);
-    else if (layout == kFloatPlanar)
-        hipLaunchKernelGGL((k_float_probe<2, kFloatPlanar>), grid, dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_float_probe<2, kFloatInterleaved>), grid, dim3(256), 0, st, a);
-    return hipGetLastError();
+    if (layout == kFloatGeneral) return launch_kernel(k_float_probe<0, kFloatGeneral>, grid, dim3(256), st, a);
+    if (a.channels == 1) return launch_kernel(k_float_probe<1, kFloatPlanar>, grid, dim3(256), st, a);
+    if (layout == kFloatPlanar) return launch_kernel(k_float_probe<2, kFloatPlanar>, grid, dim3(256), st, a);
+    return launch_kernel(k_float_probe<2, kFloatInterleaved>, grid, dim3(256), st, a);
 }
 
 }  // namespace alacdev

@@ -6,6 +6,27 @@
 
 namespace alacdev {
 
+// Every function that enqueues work returns hipError_t: the status of the FIRST runtime call or kernel launch in it that
+// failed, behind which it enqueues nothing more.  ALAC_TRY passes such a status up; launch_kernel is the one
+// place a kernel is launched from, and reads the launch's own status before any other call can overwrite it.
+#define ALAC_TRY(call)                          \
+    do {                                        \
+        const hipError_t try_e_ = (call);       \
+        if (try_e_ != hipSuccess) return try_e_; \
+    } while (0)
+// (k_lpc alone sizes its LDS at launch)
+template <typename K, typename... Args>
+inline hipError_t launch_kernel_lds(K kernel, dim3 grid, dim3 block, size_t ldsBytes, hipStream_t st, const Args &...args)
+{
+    hipLaunchKernelGGL(kernel, grid, block, ldsBytes, st, args...);
+    return hipGetLastError();
+}
+template <typename K, typename... Args>
+inline hipError_t launch_kernel(K kernel, dim3 grid, dim3 block, hipStream_t st, const Args &...args)
+{
+    return launch_kernel_lds(kernel, grid, block, 0, st, args...);
+}
+
 // per-channel part of a packet record
 struct ChanRec {
     uint32_t bits;      // entropy-coded bits of this channel
@@ -97,8 +118,8 @@ enum EncodeStage {
 hipError_t launch_encode(uint32_t depth, uint32_t channels, const EncodeArgs &ea, const PackArgs &pa,
                          uint32_t numPackets, hipStream_t st, hipEvent_t *ev);
 // finalize is the caller's; this launches the size scan and the packer (records ev[kStageScan..])
-void launch_scan_pack(uint32_t depth, uint32_t channels, uint32_t *packetBytes, const PackArgs &pa,
-                      uint32_t numPackets, hipStream_t st, hipEvent_t *ev, bool recordScan = true);
+hipError_t launch_scan_pack(uint32_t depth, uint32_t channels, uint32_t *packetBytes, const PackArgs &pa,
+                            uint32_t numPackets, hipStream_t st, hipEvent_t *ev, bool recordScan = true);
 
 // tap-parallel pipeline (alac_encode_v1.hip)
 // In-launch producer -> consumer hand-offs (alac_encode_v1.hip RowWait, alac_decode_v1.hip k_dec_fused): a consumer
@@ -154,9 +175,9 @@ struct V1Streams {
 // stage events of one timed call: block 0 = predictor / Golomb stages, block 1 = finalize + scan + pack
 constexpr uint32_t kEventBlocks = 2;
 // *err = 1 (system scope) unless segFirst[0 .. numSegments] ascends inside [0, numPackets] with no step above maxSeg
-void launch_check_segments(const uint32_t *segFirst, uint32_t numSegments, uint32_t numPackets, uint32_t maxSeg, uint32_t *err,
-                           uint32_t *segBad,
-                           hipStream_t st);
+hipError_t launch_check_segments(const uint32_t *segFirst, uint32_t numSegments, uint32_t numPackets, uint32_t maxSeg, uint32_t *err,
+                                 uint32_t *segBad,
+                                 hipStream_t st);
 // What one mono / stereo encode call launches, decided once on the host (v1_plan, alac_encode_v1.hip):
 //  Lane             the first-generation lane-per-chain encoder (option encoder_lane)
 //  Tiny             four lanes per chain, producer/consumer launches, the final coder split over two waves where it fits
@@ -266,16 +287,16 @@ struct McSpliceArgs {
     uint8_t *out;
 };
 // channels [first, first + channels) of an interleaved stream -> a compact mono / stereo stream (valid frames only)
-void launch_mc_gather(const uint8_t *pcm, uint8_t *out, const uint32_t *numSamples, uint32_t numPackets,
-                      uint32_t frameSize, uint32_t numChannels, uint32_t first, uint32_t channels, uint32_t bytesPerSample,
-                      hipStream_t st);
+hipError_t launch_mc_gather(const uint8_t *pcm, uint8_t *out, const uint32_t *numSamples, uint32_t numPackets,
+                            uint32_t frameSize, uint32_t numChannels, uint32_t first, uint32_t channels, uint32_t bytesPerSample,
+                            hipStream_t st);
 // the per-packet sample counts and the segment table of `count` elements batched behind each other
 // (sub-packet k * numPackets + p); either input may be null (then its output is not written)
-void launch_mc_tables(const uint32_t *numSamples, uint32_t numPackets, const uint32_t *segFirst, uint32_t numSegments,
-                      uint32_t count, uint32_t *numSamplesOut, uint32_t *segFirstOut, hipStream_t st);
+hipError_t launch_mc_tables(const uint32_t *numSamples, uint32_t numPackets, const uint32_t *segFirst, uint32_t numSegments,
+                            uint32_t count, uint32_t *numSamplesOut, uint32_t *segFirstOut, hipStream_t st);
 // sizes + exclusive scan + bit-granular concatenation of the element packets
-void launch_mc_splice(const McSpliceArgs &a, hipStream_t st);
-void launch_scan_sizes(const uint32_t *sizes, uint64_t *offsets, uint32_t n, hipStream_t st, const uint32_t *segBad = nullptr);
+hipError_t launch_mc_splice(const McSpliceArgs &a, hipStream_t st);
+hipError_t launch_scan_sizes(const uint32_t *sizes, uint64_t *offsets, uint32_t n, hipStream_t st, const uint32_t *segBad = nullptr);
 
 // a stream of 3..8 channels on the second-generation decoder: one pass per element of the channel count's element
 // sequence, element r of every packet decoded as the mono / stereo packet that starts where element r - 1 ended
@@ -356,8 +377,8 @@ hipError_t launch_pc_block(const int32_t *in, int32_t *pc, uint32_t rows, uint32
                            bool decode, hipStream_t st, bool allowTaps = true);
 // tap-parallel pc_block for any tap count (alac_stage_taps.hip); *_ok tells whether the shape is in its exact range
 bool pc_block_taps_ok(int32_t num, int32_t na, uint32_t chanbits, uint32_t denshift);
-void launch_pc_block_taps(const int32_t *in, int32_t *pc, uint32_t rows, uint32_t stride, int32_t num, int16_t *coefs,
-                          int32_t na, uint32_t chanbits, uint32_t denshift, hipStream_t st);
+hipError_t launch_pc_block_taps(const int32_t *in, int32_t *pc, uint32_t rows, uint32_t stride, int32_t num, int16_t *coefs,
+                                int32_t na, uint32_t chanbits, uint32_t denshift, hipStream_t st);
 hipError_t launch_dyn_comp(uint32_t mb0, uint32_t pb, uint32_t kb, const int32_t *pc, uint32_t rows,
                            uint32_t stride, int32_t numSamples, int32_t bitSize, uint8_t *bits,
                            uint32_t bytesStride, uint32_t *numBits, hipStream_t st);

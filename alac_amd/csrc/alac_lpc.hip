@@ -209,26 +209,23 @@ __global__ __launch_bounds__(kChanThreads * CH) void k_lpc(LpcArgs A)
 }
 
 template <int DEPTH>
-static void launch_lpc_depth(uint32_t channels, const LpcArgs &a, uint32_t numPackets, hipStream_t st)
+static hipError_t launch_lpc_depth(uint32_t channels, const LpcArgs &a, uint32_t numPackets, hipStream_t st)
 {
     const size_t lds = (size_t)channels * a.frameSize * 4;
-    if (channels == 2)
-        hipLaunchKernelGGL((k_lpc<DEPTH, 2>), dim3(numPackets), dim3(2 * kChanThreads), lds, st, a);
-    else
-        hipLaunchKernelGGL((k_lpc<DEPTH, 1>), dim3(numPackets), dim3(kChanThreads), lds, st, a);
+    if (channels == 2) return launch_kernel_lds(k_lpc<DEPTH, 2>, dim3(numPackets), dim3(2 * kChanThreads), lds, st, a);
+    return launch_kernel_lds(k_lpc<DEPTH, 1>, dim3(numPackets), dim3(kChanThreads), lds, st, a);
 }
 
 hipError_t launch_lpc(uint32_t depth, uint32_t channels, const LpcArgs &a, uint32_t numPackets, hipStream_t st)
 {
     if (numPackets == 0) return hipSuccess;
     switch (depth) {
-    case 16: launch_lpc_depth<16>(channels, a, numPackets, st); break;
-    case 20: launch_lpc_depth<20>(channels, a, numPackets, st); break;
-    case 24: launch_lpc_depth<24>(channels, a, numPackets, st); break;
-    case 32: launch_lpc_depth<32>(channels, a, numPackets, st); break;
+    case 16: return launch_lpc_depth<16>(channels, a, numPackets, st);
+    case 20: return launch_lpc_depth<20>(channels, a, numPackets, st);
+    case 24: return launch_lpc_depth<24>(channels, a, numPackets, st);
+    case 32: return launch_lpc_depth<32>(channels, a, numPackets, st);
     default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
 }
 
 }  // namespace alacdev

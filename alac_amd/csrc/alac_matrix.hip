@@ -11,8 +11,11 @@
 
 #include "alac/matrixlib.h"
 #include "alac_host.hpp"
+#include "alac_kernels.hpp"
 
 namespace {
+
+using alacdev::launch_kernel;
 
 // sample `idx` (channel-interleaved element index) of a packed little-endian PCM buffer, sign extended
 template <int DEPTH>
@@ -85,11 +88,15 @@ struct Staged {  // device twin of a host buffer (a device buffer is used in pla
         ok = own.alloc(n) == hipSuccess && (!copyIn || hipMemcpy(own.p, p, n, hipMemcpyHostToDevice) == hipSuccess);
         d = own.p;
     }
-    void back() const
-    {
-        if (own.p && ok) (void)hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost);
-    }
+    hipError_t back() const { return own.p && ok ? hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost) : hipSuccess; }
 };
+// host buffers: wait for the kernel, then copy back until a copy fails (the shims are void: a failure only ends them)
+void copy_back(std::initializer_list<const Staged *> outs)
+{
+    hipError_t e = hipDeviceSynchronize();
+    for (const Staged *s : outs)
+        if (e == hipSuccess) e = s->back();
+}
 
 template <int DEPTH>
 void mix_any(void *in, uint32_t stride, int32_t *u, int32_t *v, int32_t numSamples, int32_t mixbits, int32_t mixres,
@@ -103,14 +110,10 @@ void mix_any(void *in, uint32_t stride, int32_t *u, int32_t *v, int32_t numSampl
     Staged sIn(in, ((n - 1) * stride + 2) * BPS, dev, true), sU(u, n * 4, dev, false), sV(v, n * 4, dev, false),
         sS(ws ? shiftUV : nullptr, n * 4, dev, false);
     if (!sIn.ok || !sU.ok || !sV.ok || !sS.ok) return;
-    hipLaunchKernelGGL(k_mix<DEPTH>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, 0, (const uint8_t *)sIn.d, stride,
-                       (int32_t *)sU.d, (int32_t *)sV.d, (uint32_t)n, mixbits, mixres, (uint16_t *)sS.d, bytesShifted * 8, ws);
-    if (!dev) {
-        (void)hipDeviceSynchronize();
-        sU.back();
-        sV.back();
-        sS.back();
-    }
+    const hipError_t e = launch_kernel(k_mix<DEPTH>, dim3((uint32_t)((n + 255) / 256)), dim3(256), hipStream_t(0), (const uint8_t *)sIn.d,
+                                       stride, (int32_t *)sU.d, (int32_t *)sV.d, (uint32_t)n, mixbits, mixres, (uint16_t *)sS.d,
+                                       bytesShifted * 8, ws);
+    if (e == hipSuccess && !dev) copy_back({&sU, &sV, &sS});
 }
 
 }  // namespace
@@ -151,12 +154,9 @@ void copy20ToPredictor(uint8_t *in, uint32_t stride, int32_t *out, int32_t numSa
     const bool dev = on_device(in);
     Staged sIn(in, ((n - 1) * stride + 1) * 3, dev, true), sOut(out, n * 4, dev, false);
     if (!sIn.ok || !sOut.ok) return;
-    hipLaunchKernelGGL(k_copy20, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, 0, (const uint8_t *)sIn.d, stride,
-                       (int32_t *)sOut.d, (uint32_t)n);
-    if (!dev) {
-        (void)hipDeviceSynchronize();
-        sOut.back();
-    }
+    const hipError_t e = launch_kernel(k_copy20, dim3((uint32_t)((n + 255) / 256)), dim3(256), hipStream_t(0), (const uint8_t *)sIn.d,
+                                       stride, (int32_t *)sOut.d, (uint32_t)n);
+    if (e == hipSuccess && !dev) copy_back({&sOut});
 }
 
 }  // extern "C"

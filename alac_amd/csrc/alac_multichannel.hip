@@ -140,29 +140,29 @@ __global__ __launch_bounds__(256) void k_mc_splice(McSpliceArgs A)
 
 }  // namespace
 
-void launch_mc_gather(const uint8_t *pcm, uint8_t *out, const uint32_t *numSamples, uint32_t numPackets,
-                      uint32_t frameSize, uint32_t numChannels, uint32_t first, uint32_t channels, uint32_t bytesPerSample,
-                      hipStream_t st)
+hipError_t launch_mc_gather(const uint8_t *pcm, uint8_t *out, const uint32_t *numSamples, uint32_t numPackets,
+                            uint32_t frameSize, uint32_t numChannels, uint32_t first, uint32_t channels, uint32_t bytesPerSample,
+                            hipStream_t st)
 {
     const uint64_t totalFrames = (uint64_t)numPackets * frameSize;
-    hipLaunchKernelGGL(k_mc_gather, dim3((uint32_t)((totalFrames + 255) / 256)), dim3(256), 0, st, pcm, out, numSamples,
-                       totalFrames, frameSize, numChannels, first, channels, bytesPerSample);
+    return launch_kernel(k_mc_gather, dim3((uint32_t)((totalFrames + 255) / 256)), dim3(256), st, pcm, out, numSamples, totalFrames,
+                         frameSize, numChannels, first, channels, bytesPerSample);
 }
 
-void launch_mc_tables(const uint32_t *numSamples, uint32_t numPackets, const uint32_t *segFirst, uint32_t numSegments,
-                      uint32_t count, uint32_t *numSamplesOut, uint32_t *segFirstOut, hipStream_t st)
+hipError_t launch_mc_tables(const uint32_t *numSamples, uint32_t numPackets, const uint32_t *segFirst, uint32_t numSegments,
+                            uint32_t count, uint32_t *numSamplesOut, uint32_t *segFirstOut, hipStream_t st)
 {
-    if (!numSamples && !segFirst) return;
+    if (!numSamples && !segFirst) return hipSuccess;
     const uint64_t n = (uint64_t)count * numPackets + 1;
-    hipLaunchKernelGGL(k_mc_tables, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, numSamples, numPackets, segFirst,
-                       numSegments, count, numSamplesOut, segFirstOut);
+    return launch_kernel(k_mc_tables, dim3((uint32_t)((n + 255) / 256)), dim3(256), st, numSamples, numPackets, segFirst, numSegments,
+                         count, numSamplesOut, segFirstOut);
 }
 
-void launch_mc_splice(const McSpliceArgs &a, hipStream_t st)
+hipError_t launch_mc_splice(const McSpliceArgs &a, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_mc_sizes, dim3((a.numPackets + 255) / 256), dim3(256), 0, st, a);
-    launch_scan_sizes(a.packetBytes, a.offsets, a.numPackets, st);
-    hipLaunchKernelGGL(k_mc_splice, dim3(a.numPackets), dim3(256), 0, st, a);
+    ALAC_TRY(launch_kernel(k_mc_sizes, dim3((a.numPackets + 255) / 256), dim3(256), st, a));
+    ALAC_TRY(launch_scan_sizes(a.packetBytes, a.offsets, a.numPackets, st));
+    return launch_kernel(k_mc_splice, dim3(a.numPackets), dim3(256), st, a);
 }
 
 }  // namespace alacdev

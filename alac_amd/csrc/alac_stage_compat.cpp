@@ -11,6 +11,7 @@
 #include "alac/dplib.h"
 #include "alac_hip.h"
 #include "alac_host.hpp"
+#include "alac_kernels.hpp"
 
 namespace {
 
@@ -39,17 +40,22 @@ void run_pc(bool decode, int32_t *src, int32_t *dst, int32_t num, int16_t *coefs
     int16_t co[32] = {0};
     const int ncopy = numactive > 0 && numactive <= 32 ? numactive : 0;
     memcpy(co, coefs, ncopy * 2);
-    (void)hipMemset(dIn.p, 0, stride * 4);
-    (void)hipMemcpy(dIn.p, src, (size_t)(stride - 8) * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(dCo.p, co, sizeof(co), hipMemcpyHostToDevice);
+    auto stageIn = [&]() -> hipError_t {
+        ALAC_TRY(hipMemset(dIn.p, 0, stride * 4));
+        ALAC_TRY(hipMemcpy(dIn.p, src, (size_t)(stride - 8) * 4, hipMemcpyHostToDevice));
+        return hipMemcpy(dCo.p, co, sizeof(co), hipMemcpyHostToDevice);
+    };
+    if (stageIn() != hipSuccess) return;
     int32_t rc = decode ? alac_hip_unpc_block(ctx, (const int32_t *)dIn.p, (int32_t *)dOut.p, 1, stride, num,
                                               (int16_t *)dCo.p, numactive, chanbits, denshift)
                         : alac_hip_pc_block(ctx, (const int32_t *)dIn.p, (int32_t *)dOut.p, 1, stride, num, (int16_t *)dCo.p,
                                             numactive, chanbits, denshift);
-    if (rc != ALAC_HIP_noErr) return;
-    alac_hip_synchronize(ctx);
-    (void)hipMemcpy(dst, dOut.p, (size_t)num * 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(co, dCo.p, sizeof(co), hipMemcpyDeviceToHost);
+    if (rc != ALAC_HIP_noErr || alac_hip_synchronize(ctx) != ALAC_HIP_noErr) return;
+    auto stageOut = [&]() -> hipError_t {
+        ALAC_TRY(hipMemcpy(co, dCo.p, sizeof(co), hipMemcpyDeviceToHost));
+        return hipMemcpy(dst, dOut.p, (size_t)num * 4, hipMemcpyDeviceToHost);
+    };
+    if (stageOut() != hipSuccess) return;
     memcpy(coefs, co, ncopy * 2);
 }
 
@@ -113,16 +119,22 @@ int32_t dyn_comp(AGParamRecPtr params, int32_t *pc, BitBuffer *bitstream, int32_
     const uint32_t cap = ((uint32_t)numSamples * (9u + (uint32_t)bitSize + 25u) + 7) / 8 + 16;
     DevBuf dPc, dBits, dNum;
     if (dPc.alloc((size_t)numSamples * 4) || dBits.alloc(cap) || dNum.alloc(4)) return kALAC_MemFullError;
-    (void)hipMemcpy(dPc.p, pc, (size_t)numSamples * 4, hipMemcpyHostToDevice);
-    (void)hipMemset(dBits.p, 0, cap);
+    auto stageIn = [&]() -> hipError_t {
+        ALAC_TRY(hipMemcpy(dPc.p, pc, (size_t)numSamples * 4, hipMemcpyHostToDevice));
+        return hipMemset(dBits.p, 0, cap);
+    };
+    if (stageIn() != hipSuccess) return kALAC_ParamError;
     int32_t rc = alac_hip_dyn_comp(ctx, params->mb0, params->pb, params->kb, (const int32_t *)dPc.p, 1, (uint32_t)numSamples,
                                    numSamples, bitSize, (uint8_t *)dBits.p, cap, (uint32_t *)dNum.p);
-    if (rc != ALAC_HIP_noErr) return rc;
-    alac_hip_synchronize(ctx);
+    if (rc != ALAC_HIP_noErr || (rc = alac_hip_synchronize(ctx)) != ALAC_HIP_noErr) return rc;
     uint32_t nbits = 0;
-    (void)hipMemcpy(&nbits, dNum.p, 4, hipMemcpyDeviceToHost);
-    std::vector<uint8_t> bits((nbits + 7) / 8 + 1, 0);
-    (void)hipMemcpy(bits.data(), dBits.p, (nbits + 7) / 8, hipMemcpyDeviceToHost);
+    std::vector<uint8_t> bits;
+    auto stageOut = [&]() -> hipError_t {
+        ALAC_TRY(hipMemcpy(&nbits, dNum.p, 4, hipMemcpyDeviceToHost));
+        bits.assign((nbits + 7) / 8 + 1, 0);
+        return hipMemcpy(bits.data(), dBits.p, (nbits + 7) / 8, hipMemcpyDeviceToHost);
+    };
+    if (stageOut() != hipSuccess) return kALAC_ParamError;
     // splice at (cur, bitIndex), MSB first; the reference ORs into the buffer the same way (dyn_jam_noDeref)
     uint8_t *out = bitstream->cur;
     uint32_t bi = bitstream->bitIndex;
@@ -162,18 +174,23 @@ int32_t dyn_decomp(AGParamRecPtr params, BitBuffer *bitstream, int32_t *pc, int3
     const uint32_t nbytes = (uint32_t)avail;
     DevBuf dBits, dPc, dNum, dSt;
     if (dBits.alloc(nbytes + 16) || dPc.alloc((size_t)numSamples * 4) || dNum.alloc(4) || dSt.alloc(4)) return kALAC_MemFullError;
-    (void)hipMemset(dBits.p, 0, nbytes + 16);
-    (void)hipMemcpy(dBits.p, shifted.data(), nbytes, hipMemcpyHostToDevice);
+    auto stageIn = [&]() -> hipError_t {
+        ALAC_TRY(hipMemset(dBits.p, 0, nbytes + 16));
+        return hipMemcpy(dBits.p, shifted.data(), nbytes, hipMemcpyHostToDevice);
+    };
+    if (stageIn() != hipSuccess) return kALAC_ParamError;
     int32_t rc = alac_hip_dyn_decomp(ctx, params->mb0, params->pb, params->kb, (const uint8_t *)dBits.p, nbytes + 16, 1,
                                      (int32_t *)dPc.p, (uint32_t)numSamples, numSamples, maxSize, (uint32_t *)dNum.p,
                                      (int32_t *)dSt.p);
-    if (rc != ALAC_HIP_noErr) return rc;
-    alac_hip_synchronize(ctx);
+    if (rc != ALAC_HIP_noErr || (rc = alac_hip_synchronize(ctx)) != ALAC_HIP_noErr) return rc;
     uint32_t nbits = 0;
     int32_t status = 0;
-    (void)hipMemcpy(&nbits, dNum.p, 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(&status, dSt.p, 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(pc, dPc.p, (size_t)numSamples * 4, hipMemcpyDeviceToHost);
+    auto stageOut = [&]() -> hipError_t {
+        ALAC_TRY(hipMemcpy(&nbits, dNum.p, 4, hipMemcpyDeviceToHost));
+        ALAC_TRY(hipMemcpy(&status, dSt.p, 4, hipMemcpyDeviceToHost));
+        return hipMemcpy(pc, dPc.p, (size_t)numSamples * 4, hipMemcpyDeviceToHost);
+    };
+    if (stageOut() != hipSuccess) return kALAC_ParamError;
     const uint32_t end = bi + nbits;
     bitstream->cur += end >> 3;
     bitstream->bitIndex = end & 7;

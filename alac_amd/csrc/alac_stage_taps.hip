@@ -64,11 +64,10 @@ bool pc_block_taps_ok(int32_t num, int32_t na, uint32_t chanbits, uint32_t densh
     return na >= 1 && na <= 30 && chanbits >= 1 && chanbits <= 24 && denshift >= 5 && denshift <= 15 && num >= 0;
 }
 
-void launch_pc_block_taps(const int32_t *in, int32_t *pc, uint32_t rows, uint32_t stride, int32_t num, int16_t *coefs,
-                          int32_t na, uint32_t chanbits, uint32_t denshift, hipStream_t st)
+hipError_t launch_pc_block_taps(const int32_t *in, int32_t *pc, uint32_t rows, uint32_t stride, int32_t num, int16_t *coefs,
+                                int32_t na, uint32_t chanbits, uint32_t denshift, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_pc_block_taps, dim3((rows + 1) / 2), dim3(64), 0, st, in, pc, rows, stride, num, coefs, na,
-                       chanbits, denshift);
+    return launch_kernel(k_pc_block_taps, dim3((rows + 1) / 2), dim3(64), st, in, pc, rows, stride, num, coefs, na, chanbits, denshift);
 }
 
 }  // namespace alacdev

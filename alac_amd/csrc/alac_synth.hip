@@ -11,6 +11,7 @@
 #define ALAC_SYNTH_FN static __device__ __forceinline__
 #include "alac_synth_core.h"
 #include "alac_hip.h"
+#include "alac_kernels.hpp"
 
 namespace {
 
@@ -32,7 +33,7 @@ extern "C" int32_t alac_hip_synth_pcm(alac_hip_ctx *ctx, uint64_t first_frame, u
     if (!(fmt->bit_depth == 16 || fmt->bit_depth == 20 || fmt->bit_depth == 24 || fmt->bit_depth == 32)) return ALAC_HIP_ParamError;
     if (fmt->num_channels < 1 || fmt->num_channels > 2 || fmt->frame_size == 0) return ALAC_HIP_ParamError;
     if (num_frames == 0) return ALAC_HIP_noErr;
-    hipLaunchKernelGGL(k_synth, dim3((num_frames + 63) / 64), dim3(64), 0, (hipStream_t)alac_hip_stream(ctx), first_frame,
-                       num_frames, fmt->frame_size, fmt->bit_depth, fmt->num_channels, d_out);
-    return hipGetLastError() == hipSuccess ? ALAC_HIP_noErr : ALAC_HIP_ParamError;
+    const hipError_t e = alacdev::launch_kernel(k_synth, dim3((num_frames + 63) / 64), dim3(64), (hipStream_t)alac_hip_stream(ctx),
+                                                first_frame, num_frames, fmt->frame_size, fmt->bit_depth, fmt->num_channels, d_out);
+    return e == hipSuccess ? ALAC_HIP_noErr : ALAC_HIP_ParamError;
 }

@@ -35,17 +35,15 @@ __global__ __launch_bounds__(256) void k_verify_finish(const int32_t *status, co
 hipError_t launch_verify_init(uint32_t *firstMismatch, uint32_t numPackets, uint32_t *bad, hipStream_t st)
 {
     const uint32_t blocks = numPackets ? (numPackets + 255) / 256 : 1;
-    hipLaunchKernelGGL(k_verify_init, dim3(blocks), dim3(256), 0, st, firstMismatch, numPackets, bad);
-    return hipGetLastError();
+    return launch_kernel(k_verify_init, dim3(blocks), dim3(256), st, firstMismatch, numPackets, bad);
 }
 
 hipError_t launch_verify_finish(const int32_t *status, const uint32_t *numSamplesDecoded, const uint32_t *numSamplesExpected,
                                 uint32_t frameSize, uint32_t numPackets, uint32_t *firstMismatch, uint32_t *bad, hipStream_t st)
 {
     if (numPackets == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_verify_finish, dim3((numPackets + 255) / 256), dim3(256), 0, st, status, numSamplesDecoded,
-                       numSamplesExpected, frameSize, numPackets, firstMismatch, bad);
-    return hipGetLastError();
+    return launch_kernel(k_verify_finish, dim3((numPackets + 255) / 256), dim3(256), st, status, numSamplesDecoded, numSamplesExpected,
+                         frameSize, numPackets, firstMismatch, bad);
 }
 
 }  // namespace alacdev
