@@ -44,6 +44,19 @@ class FloatReport(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
+class PcmDigest(C.Structure):
+    """alac_hip_pcm_digest: one per range of alac_hip_pcm_crc32, 16 bytes"""
+    _fields_ = [("bytes", C.c_uint64), ("crc32", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# what a lane, a wave, a block and one pass of the whole grid of k_pcm_crc take (alac_kernels.hpp, alac_pcm_crc.hip): the sizes
+# at which the kernel changes path, for the tests
+PCM_CRC_LANE_BYTES = 64
+PCM_CRC_WAVE_BYTES = 64 * PCM_CRC_LANE_BYTES
+PCM_CRC_BLOCK_BYTES = 4 * PCM_CRC_WAVE_BYTES
+PCM_CRC_PASS_BYTES = 1024 * PCM_CRC_BLOCK_BYTES
+
+
 def make_format(frame_size=4096, bit_depth=16, num_channels=2, sample_rate=44100):
     return Format(frame_size, bit_depth, num_channels, sample_rate)
 
@@ -109,6 +122,10 @@ SIGNATURES = {
     "alac_hip_float_probe": (_i32, [_vp, _vp, _u32, _u64, _u64, _u64, _vp, _u32, _vp, _u64, _vp]),
     "alac_hip_float_probe_host": (_i32, [_vp, _vp, _u32, _u64, _u64, _u64, _vp, _u32, _vp]),
     "alac_hip_float_report_depth": (_u32, [_vp]),
+    "alac_hip_pcm_crc32_workspace_bytes": (_u64, [_u32]),
+    "alac_hip_pcm_crc32": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp]),
+    "alac_hip_pcm_crc32_host": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp]),
+    "alac_hip_crc32_combine": (_u32, [_u32, _u32, _u64]),
     "alac_synth_frame": (None, [_u64, _u32, _u32, _u32, _vp]),
     "alac_synth_pcm": (None, [_u64, _u32, _u32, _u32, _u32, _vp]),
     "alac_hip_synth_pcm": (_i32, [_vp, _u64, _u32, C.POINTER(Format), _vp]),
@@ -184,6 +201,12 @@ def shard_offsets(shard_bytes):
     if load_library().alac_hip_shard_offsets(src, n, dst) != 0:
         raise ValueError("bad shard sizes")
     return list(dst)
+
+
+def crc32_combine(crc_a, crc_b, len_b):
+    """zlib.crc32(A + B) from crc_a = zlib.crc32(A), crc_b = zlib.crc32(B) and len_b = len(B) (alac_hip_crc32_combine):
+    host only, no GPU needed"""
+    return int(load_library().alac_hip_crc32_combine(int(crc_a) & 0xFFFFFFFF, int(crc_b) & 0xFFFFFFFF, int(len_b)))
 
 
 def synth_pcm(first_frame, num_frames, fmt):
@@ -435,6 +458,35 @@ class Context:
         self.synchronize()
         rows = np.ascontiguousarray(reports.cpu().numpy())
         return [int(self.lib.alac_hip_float_report_depth(rows[s].ctypes.data)) for s in range(rows.shape[0])]
+
+    def pcm_crc32_device(self, pcm, ranges=None):
+        """alac_hip_pcm_crc32: zlib.crc32 of ranges of a uint8 cuda tensor, computed where it lies.  ranges: a sequence of
+        (offset, length) in bytes, ascending and non-overlapping (gaps and empty ranges allowed); None: all of pcm.
+        Returns an int32 cuda tensor [num_ranges, 4] viewing the alac_hip_pcm_digest of every range (words 0-1 bytes,
+        2 crc32, 3 zero).  Asynchronous."""
+        with self._call() as cur:
+            t = self.torch
+            if not (pcm.is_cuda and pcm.dtype == t.uint8 and pcm.dim() == 1 and pcm.is_contiguous()):
+                raise ValueError("pcm_crc32: pcm must be a contiguous one-dimensional uint8 cuda tensor")
+            table = None if ranges is None else np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
+            if table is not None and table.shape[0] < 1:
+                raise ValueError("pcm_crc32: ranges must hold at least one (offset, length)")
+            n = 1 if table is None else table.shape[0]
+            digests = t.empty((n, 4), dtype=t.int32, device=self.device)
+            ws = self._workspace(int(self.lib.alac_hip_pcm_crc32_workspace_bytes(n)))
+            self._check(self.lib.alac_hip_pcm_crc32(
+                self.h, pcm.data_ptr() if pcm.numel() else None, int(pcm.numel()),
+                None if table is None else table.ctypes.data, n, ws.data_ptr(), ws.numel(), digests.data_ptr()))
+            digests.record_stream(cur)
+            return digests
+
+    def pcm_crc32(self, pcm, ranges=None):
+        """pcm_crc32_device's digests on the host: a list of (crc32, bytes), one per range.  Synchronizes; only the digests
+        cross the bus."""
+        digests = self.pcm_crc32_device(pcm, ranges)
+        self.synchronize()
+        rows = digests.cpu().numpy().view(np.uint32)
+        return [(int(r[2]), int(r[0]) | (int(r[1]) << 32)) for r in rows]
 
     def encode_to_host(self, fmt, pcm, num_packets, **kw):
         """Convenience for tests: returns (stream bytes ndarray, sizes ndarray)."""

@@ -101,6 +101,81 @@ int32_t ALACDecoder::VerifyBatchFloat(const uint8_t *stream, const uint32_t *pac
     return mLastStatus;
 }
 
+int32_t ALACDecoder::TestBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets,
+                               const uint32_t *fileFirstPacket, uint32_t numFiles, alac_hip_pcm_digest *outDigests,
+                               uint32_t *outFrames, int32_t *outStatus)
+{
+    if (!mCtx || mCookie.empty() || !fileFirstPacket || !outDigests || !outFrames || !outStatus) return kALAC_ParamError;
+    if (numFiles == 0) return mLastStatus = ALAC_noErr;
+    for (uint32_t j = 0; j < numFiles; j++)
+        if (fileFirstPacket[j] > fileFirstPacket[j + 1]) return kALAC_ParamError;
+    if (fileFirstPacket[0] != 0 || fileFirstPacket[numFiles] != numPackets || (numPackets && (!stream || !packetBytes)))
+        return kALAC_ParamError;
+    const uint32_t np = numPackets, frame = mConfig.frameLength, bpf = mConfig.numChannels * bps_of(mConfig.bitDepth);
+    const uint64_t packetPcm = (uint64_t)frame * bpf;
+    alac_hip_format fmt = {mConfig.frameLength, mConfig.bitDepth, mConfig.numChannels, mConfig.sampleRate};
+    hipStream_t st = (hipStream_t)alac_hip_stream(mCtx);
+    alachost::DevStream d;
+    alachost::DevBuf dWs, dNs, dSt, dPcm, dTab, dDig;
+    uint64_t wsBytes = 0;
+    if (np) {
+        // a failed staging step is kALAC_MemFullError here, whichever it is
+        if (alachost::upload_stream(stream, packetBytes, np, st, d,
+                                    [](int32_t, const char *, hipError_t) { return (int32_t)kALAC_MemFullError; }) ||
+            dWs.alloc(wsBytes = alac_hip_decode_workspace_bytes_stream(&fmt, np, d.total)) || dNs.alloc(np * 4ull) ||
+            dSt.alloc(np * 4ull) || dPcm.alloc(np * packetPcm))
+            return mLastStatus = kALAC_MemFullError;
+        mLastStatus = alac_hip_decode(mCtx, mCookie.data(), (uint32_t)mCookie.size(), (const uint8_t *)d.bytes.p,
+                                      (const uint64_t *)d.offs.p, np, dWs.p, wsBytes, (uint8_t *)dPcm.p, (uint32_t *)dNs.p,
+                                      (int32_t *)dSt.p);
+        if (mLastStatus != ALAC_HIP_noErr) return mLastStatus;
+        // the frame counts come back before the table is built: a file's frames sit back to back only when all its packets
+        // but the last are full
+        if (hipMemcpyAsync(outFrames, dNs.p, np * 4ull, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(outStatus, dSt.p, np * 4ull, hipMemcpyDeviceToHost, st) != hipSuccess)
+            return mLastStatus = kALAC_ParamError;
+        if ((mLastStatus = alac_hip_synchronize(mCtx)) != ALAC_HIP_noErr) return mLastStatus;
+    }
+    // one range per file; a file with a short packet in front of its last one: one range per packet, joined below
+    std::vector<uint64_t> table;
+    std::vector<uint32_t> firstRange(numFiles + 1, 0);
+    for (uint32_t j = 0; j < numFiles; j++) {
+        const uint32_t p0 = fileFirstPacket[j], p1 = fileFirstPacket[j + 1];
+        bool packed = true;
+        uint64_t frames = 0;
+        for (uint32_t p = p0; p < p1; p++) {
+            if (outFrames[p] > frame) return mLastStatus = kALAC_ParamError;  // (the decoder never reports more)
+            packed = packed && (p + 1 == p1 || outFrames[p] == frame);
+            frames += outFrames[p];
+        }
+        if (packed) {
+            table.push_back(p0 * packetPcm), table.push_back(frames * bpf);
+        } else {
+            for (uint32_t p = p0; p < p1; p++) table.push_back(p * packetPcm), table.push_back((uint64_t)outFrames[p] * bpf);
+        }
+        firstRange[j + 1] = (uint32_t)(table.size() / 2);
+    }
+    const uint32_t nr = firstRange[numFiles];
+    const uint64_t tabBytes = alac_hip_pcm_crc32_workspace_bytes(nr);
+    std::vector<alac_hip_pcm_digest> dig(nr);
+    if (dTab.alloc(tabBytes) || dDig.alloc(nr * 16ull)) return mLastStatus = kALAC_MemFullError;
+    mLastStatus = alac_hip_pcm_crc32(mCtx, dPcm.p, np * packetPcm, table.data(), nr, dTab.p, tabBytes, (alac_hip_pcm_digest *)dDig.p);
+    if (mLastStatus != ALAC_HIP_noErr) return mLastStatus;
+    // only the digests cross the bus: the PCM stays on the device
+    if (hipMemcpyAsync(dig.data(), dDig.p, nr * 16ull, hipMemcpyDeviceToHost, st) != hipSuccess)
+        return mLastStatus = kALAC_ParamError;
+    if ((mLastStatus = alac_hip_synchronize(mCtx)) != ALAC_HIP_noErr) return mLastStatus;
+    for (uint32_t j = 0; j < numFiles; j++) {
+        alac_hip_pcm_digest sum = {0, 0, 0};
+        for (uint32_t r = firstRange[j]; r < firstRange[j + 1]; r++) {
+            sum.crc32 = alac_hip_crc32_combine(sum.crc32, dig[r].crc32, dig[r].bytes);
+            sum.bytes += dig[r].bytes;
+        }
+        outDigests[j] = sum;
+    }
+    return mLastStatus = ALAC_noErr;
+}
+
 int32_t ALACDecoder::Decode(BitBuffer *bits, uint8_t *sampleBuffer, uint32_t /*numSamples*/, uint32_t numChannels,
                             uint32_t *outNumSamples)
 {

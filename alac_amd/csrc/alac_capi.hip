@@ -39,8 +39,9 @@ struct alac_hip_ctx {
     // store when a consumer's bounded wait runs out; read without a copy after a synchronize
     uint32_t *errHost = nullptr;
     uint32_t *errDev = nullptr;
-    // alac_hip_float_probe's segment table on its way to the device: pinned host memory of the context, so that the
-    // caller's table is done with when the call returns wherever it lies; tabDone: the last upload from it has finished
+    // alac_hip_float_probe's segment table, or alac_hip_pcm_crc32's range table, on its way to the device: pinned host memory
+    // of the context, so that the caller's table is done with when the call returns wherever it lies; tabDone: the last
+    // upload from it has finished
     uint64_t *tabHost = nullptr;
     uint64_t tabCap = 0;  // in entries
     hipEvent_t tabDone = nullptr;
@@ -1091,6 +1092,60 @@ uint32_t alac_hip_float_report_depth(const alac_hip_float_report *r)
     return r->need_bits <= 16 ? 16 : r->need_bits <= 20 ? 20 : r->need_bits <= 24 ? 24 : 32;
 }
 
+// ---- CRC-32 of PCM: the fingerprint of a decode, per range of bytes ---------------------------------------------------------
+uint64_t alac_hip_pcm_crc32_workspace_bytes(uint32_t num_ranges)
+{
+    return num_ranges ? align_up((uint64_t)num_ranges * 16, 256) : 0;
+}
+
+// everything alac_hip_pcm_crc32 refuses that does not depend on where the buffers live; [lo, hi): from the first range's
+// first byte to the last one's end.  Device and host form.
+static int32_t pcm_crc_refusal(alac_hip_ctx *ctx, const void *pcm, uint64_t total_bytes, const uint64_t *h_ranges,
+                               uint32_t num_ranges, uint64_t &lo, uint64_t &hi)
+{
+    if (!pcm && total_bytes) return fail(ctx, ALAC_HIP_ParamError, "null PCM");
+    if (num_ranges == 0) return fail(ctx, ALAC_HIP_ParamError, "num_ranges 0");
+    lo = 0, hi = total_bytes;
+    if (!h_ranges) return num_ranges == 1 ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "no range table for more than one range");
+    uint64_t at = 0;
+    for (uint32_t s = 0; s < num_ranges; s++) {
+        uint64_t end;
+        if (h_ranges[2 * s] < at) return fail(ctx, ALAC_HIP_ParamError, "range table not ascending, or ranges overlap");
+        if (__builtin_add_overflow(h_ranges[2 * s], h_ranges[2 * s + 1], &end))
+            return fail(ctx, ALAC_HIP_ParamError, "a range's end overflows 64 bits");
+        at = end;
+    }
+    if (at > total_bytes) return fail(ctx, ALAC_HIP_ParamError, "range table ends behind total_bytes");
+    lo = h_ranges[0], hi = at;
+    return ALAC_HIP_noErr;
+}
+
+int32_t alac_hip_pcm_crc32(alac_hip_ctx *ctx, const void *d_pcm, uint64_t total_bytes, const uint64_t *h_ranges,
+                           uint32_t num_ranges, void *d_workspace, uint64_t workspace_bytes, alac_hip_pcm_digest *d_digests)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = pcm_crc_refusal(ctx, d_pcm, total_bytes, h_ranges, num_ranges, lo, hi)) return rc;
+    if (!d_digests || ((uintptr_t)d_digests & 7)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned d_digests (8 B)");
+    if (h_ranges && workspace_bytes < alac_hip_pcm_crc32_workspace_bytes(num_ranges))
+        return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    if (h_ranges && (!d_workspace || ((uintptr_t)d_workspace & 7)))
+        return fail(ctx, ALAC_HIP_ParamError, "null or misaligned workspace (8 B)");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    hipError_t e;
+    if (h_ranges && (e = upload_segment_table(ctx, h_ranges, (uint64_t)num_ranges * 2, d_workspace)))
+        return fail(ctx, ALAC_HIP_ParamError, "range table upload", e);
+    const PcmCrcArgs a{(const uint8_t *)d_pcm, lo, hi, h_ranges ? (const uint64_t *)d_workspace : nullptr, num_ranges,
+                       (uint32_t *)d_digests};
+    if ((e = launch_pcm_crc(a, ctx->stream))) return fail(ctx, ALAC_HIP_ParamError, "pcm crc launch", e);
+    return ALAC_HIP_noErr;
+}
+
+uint32_t alac_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b)
+{
+    return crc_mul_host(crc_a, crc_x8_pow(len_b)) ^ crc_b;
+}
+
 uint32_t alac_hip_num_stages(void) { return kNumStages; }
 
 const char *alac_hip_stage_name(uint32_t stage)
@@ -1692,6 +1747,30 @@ int32_t alac_hip_float_probe_host(alac_hip_ctx *ctx, const float *h_in, uint32_t
                                           h_seg_first_frame, num_segments, dWs.p, wsBytes, (alac_hip_float_report *)dRep.p))
         return rc;
     if ((e = hipMemcpyAsync(h_reports, dRep.p, repBytes, hipMemcpyDeviceToHost, ctx->stream)) ||
+        (e = hipStreamSynchronize(ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
+    return ALAC_HIP_noErr;
+}
+
+int32_t alac_hip_pcm_crc32_host(alac_hip_ctx *ctx, const void *h_pcm, uint64_t total_bytes, const uint64_t *h_ranges,
+                                uint32_t num_ranges, alac_hip_pcm_digest *h_digests)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = pcm_crc_refusal(ctx, h_pcm, total_bytes, h_ranges, num_ranges, lo, hi)) return rc;
+    if (!h_digests) return fail(ctx, ALAC_HIP_ParamError, "null h_digests");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    // the bytes the call may read lie in [0, hi) of h_pcm: up to the last range's end
+    const uint64_t wsBytes = h_ranges ? alac_hip_pcm_crc32_workspace_bytes(num_ranges) : 0, digBytes = (uint64_t)num_ranges * 16;
+    DevBuf dPcm, dWs, dDig;
+    hipError_t e;
+    if ((e = dPcm.alloc(hi)) || (e = dWs.alloc(wsBytes)) || (e = dDig.alloc(digBytes)))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if (hi && (e = hipMemcpyAsync(dPcm.p, h_pcm, hi, hipMemcpyHostToDevice, ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    if (int32_t rc = alac_hip_pcm_crc32(ctx, dPcm.p, hi, h_ranges, num_ranges, dWs.p, wsBytes, (alac_hip_pcm_digest *)dDig.p))
+        return rc;
+    if ((e = hipMemcpyAsync(h_digests, dDig.p, digBytes, hipMemcpyDeviceToHost, ctx->stream)) ||
         (e = hipStreamSynchronize(ctx->stream)))
         return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
     return ALAC_HIP_noErr;

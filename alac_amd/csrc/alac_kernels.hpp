@@ -358,6 +358,28 @@ struct FloatProbeArgs {
 // zeroes the reports, then (hi > lo) the pass
 hipError_t launch_float_probe(const FloatProbeArgs &a, hipStream_t st);
 
+// ---- CRC-32 of PCM (alac_pcm_crc.hip): alac_hip_pcm_crc32's one pass over the bytes ----
+// range s = bytes [ranges[2s], ranges[2s] + ranges[2s + 1]) of pcm adds to digests[4s ..] (alac_hip_pcm_digest).  ranges:
+// device table, ascending and non-overlapping inside [lo, hi), lo = ranges[0], hi = the last range's end (the host checks);
+// null: the one range [lo, hi).  Only bytes inside a range are read.
+struct PcmCrcArgs {
+    const uint8_t *pcm;
+    uint64_t lo, hi;
+    const uint64_t *ranges;  // nullable
+    uint32_t numRanges;
+    uint32_t *digests;
+};
+// what a lane, a wave and a block of k_pcm_crc take per iteration (alac_amd/capi.py mirrors them for the tests)
+constexpr uint32_t kPcmCrcLaneShift = 6;
+constexpr uint32_t kPcmCrcLaneBytes = 1u << kPcmCrcLaneShift;
+constexpr uint32_t kPcmCrcWaveBytes = 64 * kPcmCrcLaneBytes;
+constexpr uint32_t kPcmCrcBlockBytes = 4 * kPcmCrcWaveBytes;
+// zeroes the digests, then (hi > lo) the pass, then the per-range finish
+hipError_t launch_pcm_crc(const PcmCrcArgs &a, hipStream_t st);
+// host: x^(8 * bytes) in GF(2)[x] / 0xEDB88320 (reflected), and the product of two such words
+uint32_t crc_x8_pow(uint64_t bytes);
+uint32_t crc_mul_host(uint32_t a, uint32_t b);
+
 // ---- verify against a float32 source (alac_hip_verify_float): the words of PcmMode kPcmVerifyFloat (alac_verify.hpp) ----
 // DecodeArgs::pcmOut is the source: sample i of channel c of packet p at
 // pcmOut[c * channelStride + (p * frameSize + i) * frameStride] (floats); only frames i < min(numSamplesExpected[p], frameSize)

@@ -58,6 +58,19 @@
  *                                             (decimal or 0x-hex, default 0: two runs give the same file).  Every file's
  *                                             frames count from 0, so a file's output is the same alone, in --batch and
  *                                             with --devices N
+ *   --crc <file> [<file> ...]                 print one line per file, "%08x  <frames>  <path>": the CRC-32 (zlib's) of the file's
+ *                                             PCM and its sample-frames, and write nothing.  The PCM is what decoding gives, in
+ *                                             the layout of the `data` chunk of the WAV `alacconvert <file> out.wav` writes:
+ *                                             little-endian, interleaved, 20-bit samples left-justified in 3 bytes.  ALAC files
+ *                                             (CAF, M4A) are decoded and hashed on the GPU (ALACDecoder::TestBatch: the PCM never
+ *                                             comes back to the host), files of one cookie in one batch; integer PCM files (WAV,
+ *                                             CAF) have their sample bytes hashed there (alac_hip_pcm_crc32_host), so a file and
+ *                                             its encode print the same value.  Float PCM is refused.  A file with an
+ *                                             undecodable packet is named with the packet's index; exit 1.  With --devices N the
+ *                                             files are dealt to N GPUs.  No other option
+ *   --crc-check <list>                        read lines of that format, compute every file's value again and print
+ *                                             "<path>: OK", "<path>: FAILED" or "<path>: FAILED open"; exit 1 if any line
+ *                                             failed (the flow of sha256sum -c).  With --devices N; no other option
  *
  * A single chained file is serial by construction: one file runs as one chain of dependent
  * packets; the GPU pays off with --batch or --segment-packets.
@@ -65,6 +78,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <map>
 #include <string>
 #include <thread>
@@ -117,6 +131,9 @@ void usage()
     printf("            (--verify checks against the PCM handed to the encoder, --verify-source against the float file through the\n");
     printf("             quantization rule)\n");
     printf("        alacconvert --compare [--dither [--dither-seed S]] <input caf or m4a file> <reference float wav or caf file>\n");
+    printf("        alacconvert --crc [--devices N] <wav, caf or m4a file> ...\n");
+    printf("            (one line per file: CRC-32 of its PCM, sample-frames, path; ALAC is decoded and hashed on the GPU)\n");
+    printf("        alacconvert --crc-check [--devices N] <list written by --crc>\n");
     printf("\n");
 }
 
@@ -572,6 +589,232 @@ bool decode_group(std::vector<Job *> &jobs, const std::vector<alacfile::AlacCafC
     return true;
 }
 
+// ---- --crc / --crc-check: the CRC-32 of every file's PCM, computed on the GPU; nothing is written ----
+struct CrcJob {
+    Job job;
+    alacfile::AlacCafContents contents;  // ALAC files
+    bool opened = false, done = false;
+    uint32_t crc = 0;
+    uint64_t frames = 0;
+};
+
+// ALAC files of one cookie: one TestBatch, one range per file
+void crc_alac_group(std::vector<CrcJob *> &jobs, int device)
+{
+    ALACDecoder dec;
+    if (device >= 0) dec.SetDevice(device);
+    Bytes cookie(jobs[0]->contents.cookie);
+    if (dec.Init(cookie.data(), (uint32_t)cookie.size(), 0) != ALAC_noErr) {
+        fprintf(stderr, " Cannot initialise the decoder from the magic cookie: \"%s\"\n", jobs[0]->job.in.c_str());
+        return;
+    }
+    const uint32_t ch = dec.mConfig.numChannels, bits = dec.mConfig.bitDepth;
+    const uint32_t bytesPerFrame = ch * ((bits + 7) >> 3);
+    std::vector<CrcJob *> take;
+    for (size_t j = 0; j < jobs.size(); j++) {  // as decode_group: the cookie decides what the decoder writes
+        if (!(bits == 16 || bits == 20 || bits == 24 || bits == 32) || source_bits(jobs[j]->job.info.alacSourceFlag) != bits)
+            fprintf(stderr, " Magic cookie bit depth %u does not match the file description: \"%s\"\n", bits, jobs[j]->job.in.c_str());
+        else
+            take.push_back(jobs[j]);
+    }
+    if (take.empty()) return;
+    std::vector<uint32_t> sizes, firstPacket;
+    Bytes stream;
+    for (size_t j = 0; j < take.size(); j++) {
+        firstPacket.push_back((uint32_t)sizes.size());
+        append_packets(take[j]->job, take[j]->contents, stream, sizes);
+    }
+    const uint32_t np = (uint32_t)sizes.size();
+    firstPacket.push_back(np);
+    std::vector<alac_hip_pcm_digest> digests(take.size());
+    std::vector<uint32_t> frames(np, 0);
+    std::vector<int32_t> status(np, 0);
+    const int32_t rc = dec.TestBatch(stream.data(), sizes.data(), np, firstPacket.data(), (uint32_t)take.size(), digests.data(),
+                                     frames.data(), status.data());
+    if (rc != ALAC_noErr) {
+        fprintf(stderr, " Decoding failed (status %d): \"%s\"\n", rc, take[0]->job.in.c_str());
+        return;
+    }
+    for (size_t j = 0; j < take.size(); j++) {
+        CrcJob &J = *take[j];
+        bool good = true;
+        for (uint32_t p = firstPacket[j]; p < firstPacket[j + 1] && good; p++) {
+            if (status[p] != 0) {
+                fprintf(stderr, " Cannot decode packet %u (status %d): \"%s\"\n", p - firstPacket[j], status[p], J.job.in.c_str());
+                good = false;
+            }
+        }
+        if (!good) continue;
+        J.crc = digests[j].crc32;
+        J.frames = digests[j].bytes / bytesPerFrame;
+        J.done = true;
+    }
+}
+
+// integer PCM files: the sample bytes of all of them staged in one buffer, one range per file
+void crc_pcm_group(std::vector<CrcJob *> &jobs, int device)
+{
+    std::vector<uint64_t> ranges;
+    Bytes pcm;
+    for (size_t j = 0; j < jobs.size(); j++) {
+        const InputInfo &in = jobs[j]->job.info;
+        const uint64_t bytesPerFrame = (uint64_t)in.channels * ((in.bitsPerChannel + 7) >> 3);
+        // whole frames only: the encoder drops a trailing fraction of a frame (ALACEncoder.cu:984)
+        const uint64_t bytes = in.dataSize / bytesPerFrame * bytesPerFrame;
+        ranges.push_back(pcm.size()), ranges.push_back(bytes);
+        jobs[j]->frames = bytes / bytesPerFrame;
+        pcm.insert(pcm.end(), jobs[j]->job.file.begin() + in.dataPos, jobs[j]->job.file.begin() + in.dataPos + bytes);
+        if (in.bigEndianPcm) alacfile::swap_samples_in_place(pcm.data() + pcm.size() - bytes, bytes, in.bitsPerChannel);
+    }
+    alac_hip_ctx *ctx = nullptr;
+    const char *dev = getenv("ALAC_HIP_DEVICE");
+    if (alac_hip_create(&ctx, device >= 0 ? device : (dev ? atoi(dev) : 0), nullptr) != ALAC_HIP_noErr) {
+        fprintf(stderr, " Cannot create a GPU context\n");
+        return;
+    }
+    std::vector<alac_hip_pcm_digest> digests(jobs.size());
+    const int32_t rc = alac_hip_pcm_crc32_host(ctx, pcm.data(), pcm.size(), ranges.data(), (uint32_t)jobs.size(), digests.data());
+    if (rc != ALAC_HIP_noErr) fprintf(stderr, " Hashing failed (status %d): %s\n", rc, alac_hip_last_error(ctx));
+    alac_hip_destroy(ctx);
+    if (rc != ALAC_HIP_noErr) return;
+    for (size_t j = 0; j < jobs.size(); j++) {
+        jobs[j]->crc = digests[j].crc32;
+        jobs[j]->done = true;
+    }
+}
+
+// opens, sniffs and hashes every job; a job that cannot be done is named on stderr and keeps done == false
+void crc_run(std::vector<CrcJob> &jobs, uint32_t devices)
+{
+    std::map<std::string, std::vector<CrcJob *> > groups;  // ALAC files by cookie ("D..."), all PCM files ("P")
+    for (size_t j = 0; j < jobs.size(); j++) {
+        CrcJob &J = jobs[j];
+        if (!alacfile::read_file(J.job.in, J.job.file)) {
+            fprintf(stderr, " Cannot open file \"%s\"\n", J.job.in.c_str());
+            continue;
+        }
+        J.opened = true;
+        InputInfo &info = J.job.info;
+        std::string err = alacfile::sniff_input(J.job.file, info, true);
+        if (err.empty() && info.isAlac) {
+            InputInfo again;
+            err = info.kind == alacfile::kM4aFile ? alacfile::parse_alac_m4a(J.job.file, again, J.contents)
+                                                  : alacfile::parse_alac_caf(J.job.file, info, J.contents);
+        }
+        if (!err.empty()) {
+            fprintf(stderr, " %s: \"%s\"\n", err.c_str(), J.job.in.c_str());
+            continue;
+        }
+        if (!info.isAlac && info.isFloat) {
+            fprintf(stderr, " --crc does not take float PCM: \"%s\"\n", J.job.in.c_str());
+            continue;
+        }
+        const uint32_t b = info.bitsPerChannel;
+        if (!info.isAlac && ((b != 16 && b != 20 && b != 24 && b != 32) || info.channels < 1 || info.channels > 8)) {
+            fprintf(stderr, " File \"%s\'s\" data format is of an unsupported type\n", J.job.in.c_str());
+            continue;
+        }
+        groups[info.isAlac ? "D" + std::string(J.contents.cookie.begin(), J.contents.cookie.end()) : std::string("P")].push_back(&J);
+    }
+    // the files of every group dealt round-robin to the workers, as the conversions are
+    struct Work {
+        std::vector<CrcJob *> jobs;
+        bool alac;
+    };
+    const uint32_t workers = devices ? devices : 1;
+    const int32_t visible = devices ? alac_hip_device_count() : 1;
+    std::vector<std::vector<Work> > perWorker(workers);
+    uint32_t next = 0;
+    for (std::map<std::string, std::vector<CrcJob *> >::iterator g = groups.begin(); g != groups.end(); ++g) {
+        std::vector<Work> parts(workers);
+        for (size_t j = 0; j < g->second.size(); j++) {
+            Work &w = parts[(next + j) % workers];
+            w.alac = g->second[j]->job.info.isAlac;
+            w.jobs.push_back(g->second[j]);
+        }
+        for (uint32_t k = 0; k < workers; k++)
+            if (!parts[k].jobs.empty()) perWorker[k].push_back(parts[k]);
+        next = (uint32_t)((next + g->second.size()) % workers);
+    }
+    auto run = [&](uint32_t k) {
+        const int device = devices ? (int)(k % (uint32_t)visible) : -1;
+        for (size_t i = 0; i < perWorker[k].size(); i++)
+            (perWorker[k][i].alac ? crc_alac_group : crc_pcm_group)(perWorker[k][i].jobs, device);
+    };
+    if (workers == 1) {
+        run(0);
+    } else {
+        std::vector<std::thread> threads;
+        for (uint32_t k = 0; k < workers; k++) threads.emplace_back(run, k);
+        for (size_t k = 0; k < threads.size(); k++) threads[k].join();
+    }
+}
+
+// --devices N as the conversions take it
+bool crc_devices_ok(uint32_t devices)
+{
+    if (!devices) return true;
+    const int32_t have = alac_hip_device_count();
+    if (have < 1 || ((int32_t)devices > have && !getenv("ALACCONVERT_SHARE_DEVICES"))) {
+        fprintf(stderr, " --devices %u: only %d GPU(s) visible\n", devices, have);
+        return false;
+    }
+    return true;
+}
+
+int crc_files(const std::vector<std::string> &paths, uint32_t devices)
+{
+    if (!crc_devices_ok(devices)) return 1;
+    std::vector<CrcJob> jobs(paths.size());
+    for (size_t j = 0; j < jobs.size(); j++) jobs[j].job.in = paths[j];
+    crc_run(jobs, devices);
+    int rc = 0;
+    for (size_t j = 0; j < jobs.size(); j++) {
+        if (jobs[j].done) printf("%08x  %llu  %s\n", jobs[j].crc, (unsigned long long)jobs[j].frames, jobs[j].job.in.c_str());
+        else rc = 1;
+    }
+    return rc;
+}
+
+int crc_check(const std::string &listPath, uint32_t devices)
+{
+    if (!crc_devices_ok(devices)) return 1;
+    std::ifstream list(listPath.c_str());
+    if (!list) {
+        fprintf(stderr, " Cannot open file \"%s\"\n", listPath.c_str());
+        return 1;
+    }
+    std::vector<CrcJob> jobs;
+    std::vector<uint32_t> wantCrc;
+    std::vector<uint64_t> wantFrames;
+    int rc = 0;
+    std::string line;
+    for (unsigned n = 1; std::getline(list, line); n++) {
+        if (line.empty()) continue;
+        // "%08x  <frames>  <path>": the path is everything behind the second pair of blanks
+        const size_t a = line.find("  "), b = a == std::string::npos ? a : line.find("  ", a + 2);
+        char *endCrc = nullptr, *endFrames = nullptr;
+        const unsigned long crc = strtoul(line.c_str(), &endCrc, 16);
+        const unsigned long long frames = a == std::string::npos ? 0 : strtoull(line.c_str() + a + 2, &endFrames, 10);
+        if (a != 8 || b == std::string::npos || b + 2 >= line.size() || endCrc != line.c_str() + a || endFrames != line.c_str() + b) {
+            fprintf(stderr, " %s: line %u is not \"<crc32>  <frames>  <path>\"\n", listPath.c_str(), n);
+            rc = 1;
+            continue;
+        }
+        jobs.push_back(CrcJob());
+        jobs.back().job.in = line.substr(b + 2);
+        wantCrc.push_back((uint32_t)crc);
+        wantFrames.push_back(frames);
+    }
+    crc_run(jobs, devices);
+    for (size_t j = 0; j < jobs.size(); j++) {
+        const bool ok = jobs[j].done && jobs[j].crc == wantCrc[j] && jobs[j].frames == wantFrames[j];
+        printf("%s: %s\n", jobs[j].job.in.c_str(), ok ? "OK" : jobs[j].opened ? "FAILED" : "FAILED open");
+        if (!ok) rc = 1;
+    }
+    return rc;
+}
+
 }  // namespace
 
 int main(int argc, char *argv[])
@@ -579,6 +822,8 @@ int main(int argc, char *argv[])
     std::vector<std::string> files;
     bool batch = false, lpc = false, verify = false, verifySource = false, compare = false, malformed = argc < 2;
     uint32_t segmentPackets = 0, devices = 0, floatBits = 0;
+    bool crc = false;
+    std::string crcList;  // --crc-check <list>
     bool floatAuto = false;  // --float-bits auto: floatBits stays 0, every file gets its own depth from the probe
     DitherOption dither;
     for (int i = 1; i < argc && !malformed; i++) {
@@ -595,6 +840,11 @@ int main(int argc, char *argv[])
             verifySource = true;
         } else if (a == "--compare") {
             compare = true;
+        } else if (a == "--crc") {
+            crc = true;
+        } else if (a == "--crc-check" && i + 1 < argc) {
+            crcList = argv[++i];
+            if (crcList.empty()) malformed = true;
         } else if (a == "--segment-packets" && i + 1 < argc) {
             segmentPackets = (uint32_t)strtoul(argv[++i], nullptr, 10);
             if (segmentPackets == 0) malformed = true;
@@ -622,8 +872,14 @@ int main(int argc, char *argv[])
             files.push_back(a);
         }
     }
-    if (!malformed && (files.size() < 2 || (files.size() & 1) || (!batch && files.size() != 2))) malformed = true;
-    if (!malformed && devices && !batch) malformed = true;  // one file is one serial chain: nothing to deal out
+    // --crc and --crc-check stand alone (but --devices N): any number of inputs resp. one list, no output files
+    const bool crcMode = crc || !crcList.empty();
+    if (!malformed && crcMode &&
+        (batch || lpc || verify || verifySource || compare || segmentPackets || floatBits || floatAuto || dither.on ||
+         (crc && !crcList.empty()) || (crc ? files.empty() : !files.empty())))
+        malformed = true;
+    if (!malformed && !crcMode && (files.size() < 2 || (files.size() & 1) || (!batch && files.size() != 2))) malformed = true;
+    if (!malformed && !crcMode && devices && !batch) malformed = true;  // one file is one serial chain: nothing to deal out
     // --compare stands alone: two files, no other option
     // (but --dither [--dither-seed S], for a float reference of a file that was encoded with it)
     const bool floatInput = floatBits != 0 || floatAuto;
@@ -632,6 +888,8 @@ int main(int argc, char *argv[])
         usage();
         return 1;
     }
+    if (crc) return crc_files(files, devices);
+    if (!crcList.empty()) return crc_check(crcList, devices);
     if (compare) return compare_files(files[0], files[1], dither);
     if (dither.on && floatBits != 16 && floatBits != 20 && floatBits != 24) {  // auto promises lossless: no dither there
         fprintf(stderr, " --dither needs --float-bits 16, 20 or 24\n");

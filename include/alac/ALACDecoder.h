@@ -12,6 +12,7 @@
 #include "ALACAudioTypes.h"
 
 struct alac_hip_ctx;
+struct alac_hip_pcm_digest;
 
 class ALACDecoder {
 public:
@@ -54,6 +55,17 @@ public:
                              uint64_t channelStride, uint64_t frameStride, const uint32_t *numSamplesExpected,
                              uint32_t ditherMode, uint64_t ditherSeed, const uint64_t *packetOrigin,
                              uint32_t *firstMismatchOut, int32_t *statusOut, uint32_t *badPacketsOut = nullptr);
+
+    /* batch extension (host buffers): the CRC-32 of the PCM of whole files, with the PCM never leaving the device.  File j is
+     * packets [fileFirstPacket[j], fileFirstPacket[j + 1]) of the batch (fileFirstPacket: numFiles + 1 entries, from 0 to
+     * numPackets); the packets are decoded into a device buffer and alac_hip_pcm_crc32 runs over it with one range per file:
+     * outDigests[j].crc32 is zlib's crc32 of the bytes DecodeBatch would give for the file's packets with every packet's
+     * frames back to back (the `data` chunk of its WAV), outDigests[j].bytes their count.  A file with a short packet in
+     * front of its last one gets one range per packet, joined with alac_hip_crc32_combine.  Only the digests, outFrames
+     * [numPackets] (decoded frames per packet) and outStatus [numPackets] (as DecodeBatch) are copied back.  Returns
+     * ALAC_noErr or a parameter / HIP error — an undecodable packet is reported in outStatus, not by the return value. */
+    int32_t TestBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets, const uint32_t *fileFirstPacket,
+                      uint32_t numFiles, alac_hip_pcm_digest *outDigests, uint32_t *outFrames, int32_t *outStatus);
 
     int32_t LastStatus() const { return mLastStatus; }
 

@@ -499,6 +499,50 @@ int32_t alac_hip_float_probe_host(alac_hip_ctx *ctx, const float *h_in, uint32_t
  * segment: 16); 0 when none does (nan != 0, over_range != 0 or need_bits > 32) or r is NULL. */
 uint32_t alac_hip_float_report_depth(const alac_hip_float_report *r);
 
+/* ---- CRC-32 of PCM: the fingerprint of a decode, computed where the PCM lies -----------------------------------------------
+ * ALAC carries no digest of its PCM.  This call gives one for PCM in device memory — the output of alac_hip_decode — so that
+ * only the digests cross the bus: per range of bytes, the CRC-32 that zlib's crc32() gives (polynomial 0xEDB88320 reflected,
+ * initial value and final XOR 0xFFFFFFFF), which is what rippers and players print for the raw PCM of a track.  One streaming
+ * pass that writes nothing but the digests.  No reference counterpart.
+ * The rule, in GF(2)[x] / P on reflected 32-bit words (P = 0xEDB88320; bit 31 of a word is x^0, x^8 is 0x00800000; * is the
+ * product of two words mod P), with pure(A) the register after the bytes A with initial value 0 and no final XOR:
+ *     pure(A || B)   = pure(A) * x^(8|B|)  ^  pure(B)
+ *     crc32(A)       = pure(A)  ^  0xFFFFFFFF * x^(8|A|)  ^  0xFFFFFFFF
+ *     crc32(A || B)  = crc32(A) * x^(8|B|)  ^  crc32(B)          (alac_hip_crc32_combine; zlib's crc32_combine)
+ *   crc32 of no bytes is 0, of 4 zero bytes 0x2144df1c, of 8 zero bytes 0x6522df69: the length counts even for zeros.
+ *   pure() is linear, so the pieces of a range are hashed independently, each is moved to the range's end by a power of x,
+ *   and they are joined with XOR: the result is the same bits whatever the grid and the scheduling.
+ *   d_pcm, total_bytes the bytes, any alignment (d_pcm may be NULL when total_bytes is 0)
+ *   h_ranges          HOST array of num_ranges pairs {offset, length} (uint64 each), ascending and non-overlapping:
+ *                     offset[i] + length[i] <= offset[i + 1], the last end <= total_bytes.  Gaps, empty ranges and any byte
+ *                     alignment are allowed.  NULL (num_ranges 1): the one range [0, total_bytes).  Read and validated
+ *                     before the call returns and copied out on the host, as alac_hip_float_probe's table is: the caller
+ *                     may reuse it at once.  Bytes outside every range are not read.
+ *   d_workspace       alac_hip_pcm_crc32_workspace_bytes(num_ranges) bytes, 8-byte aligned: holds the uploaded table (not
+ *                     looked at without a table)
+ *   d_digests         [num_ranges] alac_hip_pcm_digest, 8-byte aligned.  Every field is written by every call (a second call
+ *                     into the same buffer does not accumulate onto the first).  crc32 of an empty range is 0.
+ * Asynchronous on the context's stream.  kALAC_ParamError, with nothing enqueued and nothing written: a null or misaligned
+ * d_digests, a null d_pcm with total_bytes > 0, with a table a null or misaligned d_workspace or one too small,
+ * num_ranges 0 (or not 1 without a table), a table that is not ascending, overlaps, has an end that overflows 64 bits or
+ * ends behind total_bytes.
+ */
+typedef struct alac_hip_pcm_digest { /* one per range, 16 bytes */
+    uint64_t bytes;    /* the range's length */
+    uint32_t crc32;    /* zlib.crc32 of the range's bytes */
+    uint32_t reserved; /* written as 0 */
+} alac_hip_pcm_digest;
+uint64_t alac_hip_pcm_crc32_workspace_bytes(uint32_t num_ranges);
+int32_t alac_hip_pcm_crc32(alac_hip_ctx *ctx, const void *d_pcm, uint64_t total_bytes, const uint64_t *h_ranges,
+                           uint32_t num_ranges, void *d_workspace, uint64_t workspace_bytes, alac_hip_pcm_digest *d_digests);
+/* Host-buffer form (synchronous): the bytes up to the last range's end are staged to the device, the digests come back in
+ * h_digests [num_ranges]. */
+int32_t alac_hip_pcm_crc32_host(alac_hip_ctx *ctx, const void *h_pcm, uint64_t total_bytes, const uint64_t *h_ranges,
+                                uint32_t num_ranges, alac_hip_pcm_digest *h_digests);
+/* Host only, no context: crc32(A || B) from crc_a = crc32(A), crc_b = crc32(B) and len_b = |B| — the digests of consecutive
+ * pieces (a long file decoded in chunks) joined without touching the PCM again. */
+uint32_t alac_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
 /* Parse a magic cookie into a format (host only). */
 int32_t alac_hip_format_from_cookie(const uint8_t *h_cookie, uint32_t cookie_size,
                                     alac_hip_format *out_fmt);
