@@ -81,7 +81,6 @@
 #include <fstream>
 #include <map>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "alac_hip.h"
@@ -90,9 +89,12 @@
 #include "ALACDecoder.h"
 #include "ALACEncoder.h"
 #include "container.h"
+#include "plan.h"
 
 using alacfile::Bytes;
 using alacfile::InputInfo;
+using plan::bytes_per_sample;
+using plan::Options;
 
 namespace {
 
@@ -100,44 +102,22 @@ struct Job {
     std::string in, out;
     Bytes file;
     InputInfo info;
+    alacfile::AlacCafContents contents;  // ALAC inputs: the cookie and the packets (parse_alac)
     Bytes result;
     // --float-bits: info describes the integer file of the quantized samples; the floats are at floatPos in `file`
     bool floatIn = false, floatBigEndian = false;
     uint64_t floatPos = 0;
+    // --crc / --crc-check: done only if the file could be hashed
+    bool opened = false, done = false;
+    uint32_t crc = 0;
+    uint64_t crcFrames = 0;
 };
-
-void usage()
-{
-    // main.cu:181-189
-    printf("Usage:\n");
-    printf("Encode:\n");
-    printf("        alacconvert <input wav or caf file> <output caf file>\n");
-    printf("Decode:\n");
-    printf("        alacconvert <input caf file> <output wav or caf file>\n");
-    printf("\n");
-    printf("Extensions:\n");
-    printf("        alacconvert --batch <in1> <out1> [<in2> <out2> ...]\n");
-    printf("        alacconvert --segment-packets K <input wav or caf file> <output caf file>\n");
-    printf("        alacconvert --batch --devices N <in1> <out1> [<in2> <out2> ...]\n");
-    printf("        alacconvert --lpc [--batch] <input wav or caf file> <output caf or m4a file> ...\n");
-    printf("        alacconvert --verify [--batch] [--lpc] ... <input wav or caf file> <output caf or m4a file> ...\n");
-    printf("        alacconvert --compare <input caf or m4a file> <reference wav or caf file>\n");
-    printf("        alacconvert --float-bits N [--batch] [--lpc] ... <input float wav or caf file> <output caf or m4a file> ...\n");
-    printf("        alacconvert --float-bits auto [--batch] [--lpc] [--verify-source] ... <input float wav or caf file> <output caf or m4a file> ...\n");
-    printf("            (every file at the smallest of 16, 20, 24, 32 bits at which it is lossless, probed on the GPU; a file that\n");
-    printf("             has none is refused; no --dither)\n");
-    printf("        alacconvert --float-bits N --dither [--dither-seed S] ... <input float wav or caf file> <output caf or m4a file> ...\n");
-    printf("        alacconvert --float-bits N [--dither [--dither-seed S]] --verify-source ... <input float wav or caf file> <output caf or m4a file> ...\n");
-    printf("            (--verify checks against the PCM handed to the encoder, --verify-source against the float file through the\n");
-    printf("             quantization rule)\n");
-    printf("        alacconvert --compare [--dither [--dither-seed S]] <input caf or m4a file> <reference float wav or caf file>\n");
-    printf("        alacconvert --crc [--devices N] <wav, caf or m4a file> ...\n");
-    printf("            (one line per file: CRC-32 of its PCM, sample-frames, path; ALAC is decoded and hashed on the GPU)\n");
-    printf("        alacconvert --crc-check [--devices N] <list written by --crc>\n");
-    printf("\n");
-}
+typedef std::map<std::string, std::vector<Job *> > Groups;  // files that go through the GPU in one call
 
 uint32_t source_bits(uint32_t flag) { return flag == 1 ? 16 : flag == 2 ? 20 : flag == 3 ? 24 : flag == 4 ? 32 : 0; }
+uint64_t frame_bytes(const InputInfo &in) { return (uint64_t)in.channels * bytes_per_sample(in.bitsPerChannel); }
+// ALAC files of one cookie decode in one call
+std::string cookie_key(const Job &J) { return "D" + std::string(J.contents.cookie.begin(), J.contents.cookie.end()); }
 
 AudioFormatDescription alac_format(const InputInfo &in)
 {
@@ -152,93 +132,139 @@ AudioFormatDescription alac_format(const InputInfo &in)
     return f;
 }
 
-// ---- encode: all jobs share bit depth and channel count; each file is one segment ----
-// --verify: decode the group's stream on `device` and compare it with the PCM it was encoded from; names the first bad
-// packet of every file that fails
-bool verify_group(std::vector<Job *> &jobs, ALACEncoder &enc, const std::vector<uint32_t> &firstPacket, const Bytes &pcm,
-                  const std::vector<uint32_t> &numSamples, const Bytes &stream, const std::vector<uint32_t> &sizes, int device)
+// ---- a file into its Job; whatever stands in the way is said on stderr ----
+bool read_job(Job &J)
 {
-    const uint32_t np = (uint32_t)sizes.size();
+    if (alacfile::read_file(J.in, J.file)) return true;
+    fprintf(stderr, " Cannot open file \"%s\"\n", J.in.c_str());
+    return false;
+}
+
+// the diagnostic of a sniffer or parser, if it gave one
+bool refused(const std::string &err, const Job &J)
+{
+    if (!err.empty()) fprintf(stderr, " %s: \"%s\"\n", err.c_str(), J.in.c_str());
+    return !err.empty();
+}
+
+// cookie and packet table of an ALAC file (sniff_input has filled J.info)
+std::string parse_alac(Job &J)
+{
+    InputInfo again;
+    return J.info.kind == alacfile::kM4aFile ? alacfile::parse_alac_m4a(J.file, again, J.contents)
+                                             : alacfile::parse_alac_caf(J.file, J.info, J.contents);
+}
+
+// an integer PCM file the encoder takes (kALACMaxChannels)
+bool pcm_format_ok(const Job &J)
+{
+    if (plan::pcm_depth_ok(J.info.bitsPerChannel) && J.info.channels >= 1 && J.info.channels <= 8) return true;
+    fprintf(stderr, " File \"%s\'s\" data format is of an unsupported type\n", J.in.c_str());
+    return false;
+}
+
+// the float payload of a --float-bits input, `frames` interleaved frames of it, in host byte order
+void stage_floats(const Job &J, uint64_t frames, float *dst)
+{
+    const uint64_t bytes = frames * J.info.channels * sizeof(float);
+    memcpy(dst, J.file.data() + J.floatPos, (size_t)bytes);
+    if (J.floatBigEndian) alacfile::swap_samples_in_place((uint8_t *)dst, bytes, 32);
+}
+
+// the packets of an ALAC file back to back
+void append_packets(const Job &J, Bytes &stream, std::vector<uint32_t> &sizes)
+{
+    const alacfile::AlacCafContents &c = J.contents;
+    uint64_t pos = c.dataPos;
+    for (size_t p = 0; p < c.packetBytes.size(); p++) {
+        const uint32_t sz = c.packetBytes[p];
+        if (!c.packetPos.empty()) pos = c.packetPos[p];  // M4A: chunks need not be contiguous
+        stream.insert(stream.end(), J.file.begin() + pos, J.file.begin() + pos + sz);
+        sizes.push_back(sz);
+        pos += sz;
+    }
+}
+
+// ... of several files; returns every file's first packet, and the packet count behind the last
+std::vector<uint32_t> gather_packets(const std::vector<Job *> &jobs, Bytes &stream, std::vector<uint32_t> &sizes)
+{
+    std::vector<uint32_t> firstPacket;
+    for (size_t j = 0; j < jobs.size(); j++) {
+        firstPacket.push_back((uint32_t)sizes.size());
+        append_packets(*jobs[j], stream, sizes);
+    }
+    firstPacket.push_back((uint32_t)sizes.size());
+    return firstPacket;
+}
+
+// ---- decoders ----
+bool open_decoder(ALACDecoder &dec, const Bytes &cookie, int device)
+{
+    if (device >= 0) dec.SetDevice(device);
+    Bytes copy(cookie);
+    return dec.Init(copy.data(), (uint32_t)copy.size(), 0) == ALAC_noErr;
+}
+
+// The 'desc' flag was checked by the sniffer, but the COOKIE decides what the decoder writes: refuse a cookie whose depth
+// contradicts the file's description.  20 bits: 3-byte samples, left-justified, as the library writes them.
+bool cookie_matches_description(uint32_t bits, const Job &J)
+{
+    if (plan::pcm_depth_ok(bits) && source_bits(J.info.alacSourceFlag) == bits) return true;
+    fprintf(stderr, " Magic cookie bit depth %u does not match the file description: \"%s\"\n", bits, J.in.c_str());
+    return false;
+}
+
+// what a verify batch says of every packet: the first frame that differs (0xffffffff: none) and the decode status
+struct Verdict {
+    std::vector<uint32_t> firstMismatch;
+    std::vector<int32_t> status;
+    uint32_t bad = 0;
+    explicit Verdict(uint32_t np) : firstMismatch(np, 0), status(np, 0) {}
+    bool ran(int32_t rc) const
+    {
+        if (rc != ALAC_noErr) fprintf(stderr, " Verification failed to run (status %d)\n", rc);
+        return rc == ALAC_noErr;
+    }
+    // the first packet of [p0, p1) that differs; p1 if none does
+    uint32_t first_bad(uint32_t p0, uint32_t p1) const
+    {
+        while (p0 < p1 && firstMismatch[p0] == 0xffffffffu) p0++;
+        return p0;
+    }
+};
+
+// names the first bad packet of every file that fails
+void report_mismatches(const std::vector<Job *> &jobs, const std::vector<uint32_t> &firstPacket, const Verdict &v)
+{
+    for (size_t j = 0; j < jobs.size(); j++) {
+        const uint32_t p0 = firstPacket[j], p = v.first_bad(p0, firstPacket[j + 1]);
+        if (p < firstPacket[j + 1])
+            fprintf(stderr, " Verify failed: \"%s\" -> \"%s\": packet %u, frame %u (status %d)\n", jobs[j]->in.c_str(),
+                    jobs[j]->out.c_str(), p - p0, v.firstMismatch[p], v.status[p]);
+    }
+}
+
+// --verify / --verify-source (`option`): decode the group's stream on `device` and compare it with what it was encoded from.
+// batch(dec, verdict) is the library call that does both: VerifyBatch against the PCM, VerifyBatchFloat against the floats.
+template <class Batch>
+bool verify_encoded(const std::vector<Job *> &jobs, ALACEncoder &enc, const std::vector<uint32_t> &firstPacket, int device,
+                    const char *option, Batch batch)
+{
+    const uint32_t np = firstPacket.back();
     if (np == 0) return true;
     uint32_t cookieSize = enc.GetMagicCookieSize(jobs[0]->info.channels);
     Bytes cookie(cookieSize, 0);
     enc.GetMagicCookie(cookie.data(), &cookieSize);
+    cookie.resize(cookieSize);
     ALACDecoder dec;
-    if (device >= 0) dec.SetDevice(device);
-    if (dec.Init(cookie.data(), cookieSize, 0) != ALAC_noErr) {
-        fprintf(stderr, " Cannot initialise the decoder for --verify\n");
+    if (!open_decoder(dec, cookie, device)) {
+        fprintf(stderr, " Cannot initialise the decoder for %s\n", option);
         return false;
     }
-    std::vector<uint32_t> firstMismatch(np, 0);
-    std::vector<int32_t> status(np, 0);
-    uint32_t bad = 0;
-    const int32_t rc = dec.VerifyBatch(stream.data(), sizes.data(), np, pcm.data(), numSamples.data(), firstMismatch.data(),
-                                       status.data(), &bad);
-    if (rc != ALAC_noErr) {
-        fprintf(stderr, " Verification failed to run (status %d)\n", rc);
-        return false;
-    }
-    if (bad == 0) return true;
-    for (size_t j = 0; j < jobs.size(); j++) {
-        const uint32_t p0 = firstPacket[j], p1 = j + 1 < jobs.size() ? firstPacket[j + 1] : np;
-        for (uint32_t p = p0; p < p1; p++) {
-            if (firstMismatch[p] != 0xffffffffu) {
-                fprintf(stderr, " Verify failed: \"%s\" -> \"%s\": packet %u, frame %u (status %d)\n", jobs[j]->in.c_str(),
-                        jobs[j]->out.c_str(), p - p0, firstMismatch[p], status[p]);
-                break;
-            }
-        }
-    }
-    return false;
-}
-
-// --dither: TPDF dither with this seed on the float inputs
-struct DitherOption {
-    bool on = false;
-    uint64_t seed = 0;
-};
-
-// --verify-source: decode the group's stream on `device` and compare it with the floats it was encoded from, through the rule
-// of the float encode (the same dither, every file's frames counted from 0: `origin`); names the first bad packet of every
-// file that fails
-bool verify_source_group(std::vector<Job *> &jobs, ALACEncoder &enc, const std::vector<uint32_t> &firstPacket,
-                         const std::vector<float> &fl, uint32_t ch, const std::vector<uint32_t> &numSamples,
-                         const DitherOption &dither, const std::vector<uint64_t> &origin, const Bytes &stream,
-                         const std::vector<uint32_t> &sizes, int device)
-{
-    const uint32_t np = (uint32_t)sizes.size();
-    if (np == 0) return true;
-    uint32_t cookieSize = enc.GetMagicCookieSize(ch);
-    Bytes cookie(cookieSize, 0);
-    enc.GetMagicCookie(cookie.data(), &cookieSize);
-    ALACDecoder dec;
-    if (device >= 0) dec.SetDevice(device);
-    if (dec.Init(cookie.data(), cookieSize, 0) != ALAC_noErr) {
-        fprintf(stderr, " Cannot initialise the decoder for --verify-source\n");
-        return false;
-    }
-    std::vector<uint32_t> firstMismatch(np, 0);
-    std::vector<int32_t> status(np, 0);
-    uint32_t bad = 0;
-    const int32_t rc = dec.VerifyBatchFloat(stream.data(), sizes.data(), np, fl.data(), 1, ch, numSamples.data(),
-                                            dither.on ? ALAC_HIP_DITHER_TPDF : ALAC_HIP_DITHER_NONE, dither.seed, origin.data(),
-                                            firstMismatch.data(), status.data(), &bad);
-    if (rc != ALAC_noErr) {
-        fprintf(stderr, " Verification failed to run (status %d)\n", rc);
-        return false;
-    }
-    if (bad == 0) return true;
-    for (size_t j = 0; j < jobs.size(); j++) {
-        const uint32_t p0 = firstPacket[j], p1 = j + 1 < jobs.size() ? firstPacket[j + 1] : np;
-        for (uint32_t p = p0; p < p1; p++) {
-            if (firstMismatch[p] != 0xffffffffu) {
-                fprintf(stderr, " Verify failed: \"%s\" -> \"%s\": packet %u, frame %u (status %d)\n", jobs[j]->in.c_str(),
-                        jobs[j]->out.c_str(), p - p0, firstMismatch[p], status[p]);
-                break;
-            }
-        }
-    }
-    return false;
+    Verdict v(np);
+    if (!v.ran(batch(dec, v))) return false;
+    if (v.bad) report_mismatches(jobs, firstPacket, v);
+    return v.bad == 0;
 }
 
 // --float-bits auto: every float job gets the smallest depth at which its encode is exactly lossless, found on the GPU
@@ -258,12 +284,7 @@ bool probe_float_jobs(std::vector<Job> &jobs, int device)
         for (size_t j = 0; j < v.size(); j++) first.push_back(first.back() + v[j]->info.dataSize / (4ull * ch));
         // interleaved floats: channel_stride 1, frame_stride ch (one float where every file is empty)
         std::vector<float> fl((size_t)(first.back() * ch) + 1, 0.0f);
-        for (size_t j = 0; j < v.size(); j++) {
-            uint8_t *dst = (uint8_t *)(fl.data() + (size_t)first[j] * ch);
-            const uint64_t bytes = (first[j + 1] - first[j]) * ch * sizeof(float);
-            memcpy(dst, v[j]->file.data() + v[j]->floatPos, (size_t)bytes);
-            if (v[j]->floatBigEndian) alacfile::swap_samples_in_place(dst, bytes, 32);
-        }
+        for (size_t j = 0; j < v.size(); j++) stage_floats(*v[j], first[j + 1] - first[j], fl.data() + (size_t)first[j] * ch);
         std::vector<alac_hip_float_report> reports(v.size());
         const int32_t rc = enc.ProbeFloat(fl.data(), ch, 1, ch, first.back(), first.data(), (uint32_t)v.size(), reports.data());
         if (rc != ALAC_noErr) {
@@ -282,24 +303,23 @@ bool probe_float_jobs(std::vector<Job> &jobs, int device)
             }
             printf("Float input is lossless at %u bits: %s\n", depth, J.in.c_str());
             J.info.bitsPerChannel = depth;
-            J.info.dataSize = (first[j + 1] - first[j]) * ch * ((depth + 7) >> 3);
+            J.info.dataSize = (first[j + 1] - first[j]) * frame_bytes(J.info);
         }
     }
     return ok;
 }
 
-bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, bool verify, bool verifySource,
-                  const DitherOption &dither, int device)
+// ---- encode: all jobs share bit depth and channel count; each file is one segment ----
+bool encode_group(std::vector<Job *> &jobs, const Options &o, int device)
 {
     const InputInfo &first = jobs[0]->info;
-    const uint32_t bps = (first.bitsPerChannel + 7) >> 3, ch = first.channels;  // 20 bits: 3-byte containers (container.cpp)
-    const uint32_t bytesPerFrame = bps * ch, frame = kALACDefaultFramesPerPacket;
+    const uint32_t ch = first.channels, bytesPerFrame = (uint32_t)frame_bytes(first), frame = kALACDefaultFramesPerPacket;
     const uint64_t packetBytes = (uint64_t)bytesPerFrame * frame;
 
     ALACEncoder enc;
     enc.SetFrameSize(frame);
-    enc.SetLPCMode(lpc);
-    if (dither.on) enc.SetDither(ALAC_HIP_DITHER_TPDF, dither.seed);
+    enc.SetLPCMode(o.lpc);
+    if (o.dither.on) enc.SetDither(ALAC_HIP_DITHER_TPDF, o.dither.seed);
     if (device >= 0) enc.SetDevice(device);
     AudioFormatDescription outFmt = alac_format(first);
     if (enc.InitializeEncoder(outFmt, 0) != ALAC_noErr) {
@@ -307,146 +327,102 @@ bool encode_group(std::vector<Job *> &jobs, uint32_t segmentPackets, bool lpc, b
         return false;
     }
 
-    // packets back to back at the full-packet stride; the reference cuts the payload into full packets plus one
-    // partial one (main.cu:476-545) and drops a trailing fraction of a frame (ALACEncoder.cu:984)
-    std::vector<uint32_t> numSamples, segFirst(1, 0), firstPacket;
-    for (size_t j = 0; j < jobs.size(); j++) {
-        const uint64_t n = jobs[j]->info.dataSize;
-        const uint64_t full = n / packetBytes, rest = n - full * packetBytes;
-        firstPacket.push_back((uint32_t)numSamples.size());
-        for (uint64_t p = 0; p < full; p++) numSamples.push_back(frame);
-        if (rest) numSamples.push_back((uint32_t)(rest / bytesPerFrame));
-        if (segmentPackets == 0) {
-            segFirst.push_back((uint32_t)numSamples.size());
-        } else {
-            for (uint32_t p = firstPacket.back() + segmentPackets; p < numSamples.size(); p += segmentPackets) segFirst.push_back(p);
-            segFirst.push_back((uint32_t)numSamples.size());
-        }
-    }
-    // files without payload contribute an empty segment; drop duplicates the segment table cannot hold
-    std::vector<uint32_t> segs;
-    for (size_t s = 0; s < segFirst.size(); s++)
-        if (s == 0 || segFirst[s] != segs.back()) segs.push_back(segFirst[s]);
+    // packets back to back at the full-packet stride
+    std::vector<uint64_t> dataBytes;
+    for (size_t j = 0; j < jobs.size(); j++) dataBytes.push_back(jobs[j]->info.dataSize);
+    const plan::PacketCut cut = plan::cut_packets(dataBytes, bytesPerFrame, frame, o.segmentPackets);
+    const std::vector<uint32_t> &numSamples = cut.numSamples, &firstPacket = cut.firstPacket, &segs = cut.segments;
     const uint32_t np = (uint32_t)numSamples.size();
 
-    const bool floatIn = jobs[0]->floatIn;
-    Bytes pcm(floatIn ? 0 : (size_t)np * packetBytes, 0), stream;
+    Bytes stream((size_t)np * (packetBytes + kALACMaxEscapeHeaderBytes));
     std::vector<uint32_t> sizes(np, 0);
     uint64_t total = 0;
-    if (np && floatIn) {
+    auto encoded = [](int32_t rc) {
+        if (rc != ALAC_noErr) fprintf(stderr, " Encoding failed (status %d)\n", rc);
+        return rc == ALAC_noErr;
+    };
+    if (np && jobs[0]->floatIn) {
         // interleaved floats at the full-packet stride: channel_stride 1, frame_stride ch
         std::vector<float> fl((size_t)np * frame * ch, 0.0f);
-        for (size_t j = 0; j < jobs.size(); j++) {
-            Job &J = *jobs[j];
-            uint8_t *dst = (uint8_t *)(fl.data() + (size_t)firstPacket[j] * frame * ch);
-            const uint64_t bytes = J.info.dataSize / bytesPerFrame * ch * sizeof(float);
-            memcpy(dst, J.file.data() + J.floatPos, (size_t)bytes);
-            if (J.floatBigEndian) alacfile::swap_samples_in_place(dst, bytes, 32);
-        }
-        stream.resize((size_t)np * (packetBytes + kALACMaxEscapeHeaderBytes));
         std::vector<uint32_t> clipped(np, 0);
         // every file's frames count from 0: its dither does not depend on the files beside it
         std::vector<uint64_t> origin(np, 0);
-        for (size_t j = 0; j < jobs.size(); j++)
-            for (uint32_t p = firstPacket[j], p1 = j + 1 < jobs.size() ? firstPacket[j + 1] : np; p < p1; p++)
-                origin[p] = (uint64_t)(p - firstPacket[j]) * frame;
-        const int32_t rc = enc.EncodeSegmentsFloatAt(fl.data(), 1, ch, numSamples.data(), np, segs.data(),
-                                                     (uint32_t)segs.size() - 1, stream.data(), stream.size(), sizes.data(),
-                                                     &total, clipped.data(), origin.data());
-        if (rc != ALAC_noErr) {
-            fprintf(stderr, " Encoding failed (status %d)\n", rc);
-            return false;
-        }
         for (size_t j = 0; j < jobs.size(); j++) {
-            const uint32_t p0 = firstPacket[j], p1 = j + 1 < jobs.size() ? firstPacket[j + 1] : np;
+            stage_floats(*jobs[j], jobs[j]->info.dataSize / bytesPerFrame, fl.data() + (size_t)firstPacket[j] * frame * ch);
+            for (uint32_t p = firstPacket[j]; p < firstPacket[j + 1]; p++) origin[p] = (uint64_t)(p - firstPacket[j]) * frame;
+        }
+        if (!encoded(enc.EncodeSegmentsFloatAt(fl.data(), 1, ch, numSamples.data(), np, segs.data(), (uint32_t)segs.size() - 1,
+                                               stream.data(), stream.size(), sizes.data(), &total, clipped.data(), origin.data())))
+            return false;
+        for (size_t j = 0; j < jobs.size(); j++) {
             uint64_t clips = 0;
-            for (uint32_t p = p0; p < p1; p++) clips += clipped[p];
+            for (uint32_t p = firstPacket[j]; p < firstPacket[j + 1]; p++) clips += clipped[p];
             if (clips)
                 fprintf(stderr, " Warning: %llu samples clipped to %u bits: \"%s\"\n", (unsigned long long)clips,
                         first.bitsPerChannel, jobs[j]->in.c_str());
         }
-        if (verifySource && !verify_source_group(jobs, enc, firstPacket, fl, ch, numSamples, dither, origin, stream, sizes, device))
+        if (o.verifySource &&
+            !verify_encoded(jobs, enc, firstPacket, device, "--verify-source", [&](ALACDecoder &dec, Verdict &v) {
+                return dec.VerifyBatchFloat(stream.data(), sizes.data(), np, fl.data(), 1, ch, numSamples.data(),
+                                            o.dither.on ? ALAC_HIP_DITHER_TPDF : ALAC_HIP_DITHER_NONE, o.dither.seed, origin.data(),
+                                            v.firstMismatch.data(), v.status.data(), &v.bad);
+            }))
             return false;
     } else if (np) {
+        Bytes pcm((size_t)np * packetBytes, 0);
         for (size_t j = 0; j < jobs.size(); j++) {
-            Job &J = *jobs[j];
+            const Job &J = *jobs[j];
             uint8_t *dst = pcm.data() + (size_t)firstPacket[j] * packetBytes;
             memcpy(dst, J.file.data() + J.info.dataPos, (size_t)J.info.dataSize);
             if (J.info.bigEndianPcm) alacfile::swap_samples_in_place(dst, J.info.dataSize, J.info.bitsPerChannel);
         }
-        stream.resize((size_t)np * (packetBytes + kALACMaxEscapeHeaderBytes));
-        const int32_t rc = enc.EncodeSegments(pcm.data(), numSamples.data(), np, segs.data(), (uint32_t)segs.size() - 1,
-                                              stream.data(), stream.size(), sizes.data(), &total);
-        if (rc != ALAC_noErr) {
-            fprintf(stderr, " Encoding failed (status %d)\n", rc);
+        if (!encoded(enc.EncodeSegments(pcm.data(), numSamples.data(), np, segs.data(), (uint32_t)segs.size() - 1, stream.data(),
+                                        stream.size(), sizes.data(), &total)))
             return false;
-        }
-        if (verify && !verify_group(jobs, enc, firstPacket, pcm, numSamples, stream, sizes, device)) return false;
+        if (o.verify &&
+            !verify_encoded(jobs, enc, firstPacket, device, "--verify", [&](ALACDecoder &dec, Verdict &v) {
+                return dec.VerifyBatch(stream.data(), sizes.data(), np, pcm.data(), numSamples.data(), v.firstMismatch.data(),
+                                       v.status.data(), &v.bad);
+            }))
+            return false;
     }
     // per file: cookie + container
     std::vector<uint64_t> offs(np + 1, 0);
     for (uint32_t p = 0; p < np; p++) offs[p + 1] = offs[p] + sizes[p];
     for (size_t j = 0; j < jobs.size(); j++) {
         Job &J = *jobs[j];
-        ALACEncoder cookieMaker;  // the cookie carries the file's own sample rate
-        cookieMaker.SetFrameSize(frame);
-        if (device >= 0) cookieMaker.SetDevice(device);
-        AudioFormatDescription f = alac_format(J.info);
-        cookieMaker.InitializeEncoder(f, 0);
-        uint32_t cookieSize = cookieMaker.GetMagicCookieSize(J.info.channels);
-        Bytes cookie(cookieSize, 0);
-        cookieMaker.GetMagicCookie(cookie.data(), &cookieSize);
-        cookie.resize(cookieSize);
-        const uint32_t p0 = firstPacket[j], p1 = j + 1 < jobs.size() ? firstPacket[j + 1] : np;
-        alacfile::AlacCafParams cp = {J.info.sampleRate, J.info.channels, J.info.bitsPerChannel, frame, J.info.dataSize};
-        std::vector<uint32_t> mine(sizes.begin() + p0, sizes.begin() + p1);
+        // the cookie carries the file's own sample rate; no packet size or bit rate in it, as a fresh encoder reports it
+        const alac_hip_format fmt = {frame, J.info.bitsPerChannel, J.info.channels, (uint32_t)J.info.sampleRate};
+        Bytes cookie(alac_hip_magic_cookie_size(&fmt), 0);
+        cookie.resize(alac_hip_magic_cookie_full(&fmt, 0, 0, cookie.data(), (uint32_t)cookie.size()));
+        const uint32_t p0 = firstPacket[j], p1 = firstPacket[j + 1];
+        const std::vector<uint32_t> mine(sizes.begin() + p0, sizes.begin() + p1);
         if (alacfile::has_m4a_extension(J.out)) {
             const alacfile::AlacM4aParams mp = {(uint32_t)J.info.sampleRate, J.info.channels, J.info.bitsPerChannel, frame,
                                                 J.info.dataSize / bytesPerFrame};
             J.result = alacfile::build_alac_m4a(mp, cookie, mine, stream.data() + offs[p0], offs[p1] - offs[p0]);
         } else {
+            const alacfile::AlacCafParams cp = {J.info.sampleRate, J.info.channels, J.info.bitsPerChannel, frame, J.info.dataSize};
             J.result = alacfile::build_alac_caf(cp, cookie, mine, stream.data() + offs[p0], offs[p1] - offs[p0]);
         }
     }
     return true;
 }
 
-// the packets of an ALAC file back to back
-void append_packets(const Job &J, const alacfile::AlacCafContents &c, Bytes &stream, std::vector<uint32_t> &sizes)
-{
-    uint64_t pos = c.dataPos;
-    for (size_t p = 0; p < c.packetBytes.size(); p++) {
-        const uint32_t sz = c.packetBytes[p];
-        if (!c.packetPos.empty()) pos = c.packetPos[p];  // M4A: chunks need not be contiguous
-        stream.insert(stream.end(), J.file.begin() + pos, J.file.begin() + pos + sz);
-        sizes.push_back(sz);
-        pos += sz;
-    }
-}
-
 // ---- --compare <alac file> <reference pcm file>: decode and compare on the GPU, write nothing; 0 = identical ----
-int compare_files(const std::string &alacPath, const std::string &refPath, const DitherOption &dither)
+int compare_files(const Options &o)
 {
     Job A, R;
-    A.in = alacPath;
-    R.in = refPath;
-    for (Job *J : {&A, &R}) {
-        if (!alacfile::read_file(J->in, J->file)) {
-            fprintf(stderr, " Cannot open file \"%s\"\n", J->in.c_str());
-            return 1;
-        }
-        const std::string err = alacfile::sniff_input(J->file, J->info, J == &R);  // the reference may be float PCM
-        if (!err.empty()) {
-            fprintf(stderr, " %s: \"%s\"\n", err.c_str(), J->in.c_str());
-            return 1;
-        }
-    }
+    A.in = o.files[0];
+    R.in = o.files[1];
+    for (Job *J : {&A, &R})  // the reference may be float PCM
+        if (!read_job(*J) || refused(alacfile::sniff_input(J->file, J->info, J == &R), *J)) return 1;
     const bool floatRef = !R.info.isAlac && R.info.isFloat;
     if (floatRef && R.info.bitsPerChannel != 32) {
         fprintf(stderr, " %u-bit float reference is not supported (32-bit float): \"%s\"\n", R.info.bitsPerChannel, R.in.c_str());
         return 1;
     }
-    if (dither.on && !floatRef) {
+    if (o.dither.on && !floatRef) {
         fprintf(stderr, " --compare --dither needs a 32-bit float reference: \"%s\"\n", R.in.c_str());
         return 1;
     }
@@ -454,22 +430,14 @@ int compare_files(const std::string &alacPath, const std::string &refPath, const
         fprintf(stderr, " --compare takes an ALAC file (CAF or M4A) and a PCM reference (WAV or CAF)\n");
         return 1;
     }
-    alacfile::AlacCafContents c;
-    InputInfo again;
-    const std::string err = A.info.kind == alacfile::kM4aFile ? alacfile::parse_alac_m4a(A.file, again, c)
-                                                              : alacfile::parse_alac_caf(A.file, A.info, c);
-    if (!err.empty()) {
-        fprintf(stderr, " %s: \"%s\"\n", err.c_str(), A.in.c_str());
-        return 1;
-    }
+    if (refused(parse_alac(A), A)) return 1;
     ALACDecoder dec;
-    Bytes cookie(c.cookie);
-    if (dec.Init(cookie.data(), (uint32_t)cookie.size(), 0) != ALAC_noErr) {
+    if (!open_decoder(dec, A.contents.cookie, -1)) {
         fprintf(stderr, " Cannot initialise the decoder from the magic cookie\n");
         return 1;
     }
     const uint32_t ch = dec.mConfig.numChannels, bits = dec.mConfig.bitDepth, frame = dec.mConfig.frameLength;
-    if (dither.on && bits == 32) {
+    if (o.dither.on && bits == 32) {
         fprintf(stderr, " --dither needs a 16-, 20- or 24-bit stream: \"%s\"\n", A.in.c_str());
         return 1;
     }
@@ -479,10 +447,10 @@ int compare_files(const std::string &alacPath, const std::string &refPath, const
         return 1;
     }
     // bytes of one frame of the reference: float32 samples, or the stream's own integer containers
-    const uint64_t bytesPerFrame = floatRef ? (uint64_t)ch * 4 : (uint64_t)ch * ((bits + 7) >> 3), packetBytes = bytesPerFrame * frame;
+    const uint64_t bytesPerFrame = (uint64_t)ch * (floatRef ? 4 : bytes_per_sample(bits)), packetBytes = bytesPerFrame * frame;
     std::vector<uint32_t> sizes;
     Bytes stream;
-    append_packets(A, c, stream, sizes);
+    append_packets(A, stream, sizes);
     const uint32_t np = (uint32_t)sizes.size();
     // the reference cut into packets as the encoder cuts it: full packets, then one partial packet
     const uint64_t refFrames = R.info.dataSize / bytesPerFrame;
@@ -498,27 +466,18 @@ int compare_files(const std::string &alacPath, const std::string &refPath, const
     }
     // (a float reference sits in `pcm` as interleaved floats at the full-packet stride: channel stride 1, frame stride ch;
     // one file, so its frames count from 0 as the encode numbered them — no origin table)
-    std::vector<uint32_t> firstMismatch(np, 0);
-    std::vector<int32_t> status(np, 0);
-    uint32_t bad = 0;
-    if (np) {
-        const int32_t rc =
-            floatRef ? dec.VerifyBatchFloat(stream.data(), sizes.data(), np, (const float *)pcm.data(), 1, ch, expected.data(),
-                                            dither.on ? ALAC_HIP_DITHER_TPDF : ALAC_HIP_DITHER_NONE, dither.seed, nullptr,
-                                            firstMismatch.data(), status.data(), &bad)
-                     : dec.VerifyBatch(stream.data(), sizes.data(), np, pcm.data(), expected.data(), firstMismatch.data(),
-                                       status.data(), &bad);
-        if (rc != ALAC_noErr) {
-            fprintf(stderr, " Verification failed to run (status %d)\n", rc);
-            return 1;
-        }
-    }
-    for (uint32_t p = 0; p < np && bad; p++) {
-        if (firstMismatch[p] != 0xffffffffu) {
-            printf("Compare: \"%s\" differs from \"%s\" at packet %u, frame %u (sample-frame %llu, status %d)\n", A.in.c_str(),
-                   R.in.c_str(), p, firstMismatch[p], (unsigned long long)((uint64_t)p * frame + firstMismatch[p]), status[p]);
-            return 1;
-        }
+    Verdict v(np);
+    if (np && !v.ran(floatRef ? dec.VerifyBatchFloat(stream.data(), sizes.data(), np, (const float *)pcm.data(), 1, ch, expected.data(),
+                                                     o.dither.on ? ALAC_HIP_DITHER_TPDF : ALAC_HIP_DITHER_NONE, o.dither.seed,
+                                                     nullptr, v.firstMismatch.data(), v.status.data(), &v.bad)
+                              : dec.VerifyBatch(stream.data(), sizes.data(), np, pcm.data(), expected.data(),
+                                                v.firstMismatch.data(), v.status.data(), &v.bad)))
+        return 1;
+    const uint32_t p = v.bad ? v.first_bad(0, np) : np;
+    if (p < np) {
+        printf("Compare: \"%s\" differs from \"%s\" at packet %u, frame %u (sample-frame %llu, status %d)\n", A.in.c_str(),
+               R.in.c_str(), p, v.firstMismatch[p], (unsigned long long)((uint64_t)p * frame + v.firstMismatch[p]), v.status[p]);
+        return 1;
     }
     if (refPackets != np) {
         printf("Compare: \"%s\" has %u packets, \"%s\" makes %llu\n", A.in.c_str(), np, R.in.c_str(),
@@ -530,32 +489,20 @@ int compare_files(const std::string &alacPath, const std::string &refPath, const
 }
 
 // ---- decode: jobs with identical cookies decode in one batch ----
-bool decode_group(std::vector<Job *> &jobs, const std::vector<alacfile::AlacCafContents> &contents, int device)
+bool decode_group(std::vector<Job *> &jobs, int device)
 {
-    const Bytes &cookie = contents[0].cookie;
     ALACDecoder dec;
-    if (device >= 0) dec.SetDevice(device);
-    Bytes cookieCopy(cookie);
-    if (dec.Init(cookieCopy.data(), (uint32_t)cookieCopy.size(), 0) != ALAC_noErr) {
+    if (!open_decoder(dec, jobs[0]->contents.cookie, device)) {
         fprintf(stderr, " Cannot initialise the decoder from the magic cookie\n");
         return false;
     }
     const uint32_t ch = dec.mConfig.numChannels, bits = dec.mConfig.bitDepth, frame = dec.mConfig.frameLength;
-    // The 'desc' flag was checked by the caller, but the COOKIE decides what the decoder writes: refuse a cookie whose depth
-    // contradicts the file's description.  20 bits: 3-byte samples, left-justified, as the library writes them.
-    for (size_t j = 0; j < jobs.size(); j++) {
-        if (!(bits == 16 || bits == 20 || bits == 24 || bits == 32) || source_bits(jobs[j]->info.alacSourceFlag) != bits) {
-            fprintf(stderr, " Magic cookie bit depth %u does not match the file description: \"%s\"\n", bits, jobs[j]->in.c_str());
-            return false;
-        }
-    }
-    const uint32_t bytesPerFrame = ch * ((bits + 7) >> 3);
-    std::vector<uint32_t> sizes, firstPacket;
+    for (size_t j = 0; j < jobs.size(); j++)
+        if (!cookie_matches_description(bits, *jobs[j])) return false;
+    const uint32_t bytesPerFrame = ch * bytes_per_sample(bits);
+    std::vector<uint32_t> sizes;
     Bytes stream;
-    for (size_t j = 0; j < jobs.size(); j++) {
-        firstPacket.push_back((uint32_t)sizes.size());
-        append_packets(*jobs[j], contents[j], stream, sizes);
-    }
+    const std::vector<uint32_t> firstPacket = gather_packets(jobs, stream, sizes);
     const uint32_t np = (uint32_t)sizes.size();
     Bytes pcm((size_t)np * frame * bytesPerFrame);
     std::vector<uint32_t> ns(np, 0);
@@ -569,9 +516,8 @@ bool decode_group(std::vector<Job *> &jobs, const std::vector<alacfile::AlacCafC
     }
     for (size_t j = 0; j < jobs.size(); j++) {
         Job &J = *jobs[j];
-        const uint32_t p0 = firstPacket[j], p1 = j + 1 < jobs.size() ? firstPacket[j + 1] : np;
         Bytes outPcm;
-        for (uint32_t p = p0; p < p1; p++) {
+        for (uint32_t p = firstPacket[j]; p < firstPacket[j + 1]; p++) {
             // main.cu:721-724: numFrames of every packet counts, whatever its status
             const uint8_t *src = pcm.data() + (size_t)p * frame * bytesPerFrame;
             outPcm.insert(outPcm.end(), src, src + (size_t)ns[p] * bytesPerFrame);
@@ -589,81 +535,100 @@ bool decode_group(std::vector<Job *> &jobs, const std::vector<alacfile::AlacCafC
     return true;
 }
 
-// ---- --crc / --crc-check: the CRC-32 of every file's PCM, computed on the GPU; nothing is written ----
-struct CrcJob {
-    Job job;
-    alacfile::AlacCafContents contents;  // ALAC files
-    bool opened = false, done = false;
-    uint32_t crc = 0;
-    uint64_t frames = 0;
-};
+// ---- --devices N ----
+bool devices_ok(uint32_t devices)
+{
+    if (!devices) return true;
+    const int32_t have = alac_hip_device_count();
+    // ALACCONVERT_SHARE_DEVICES=1 (tests on a one-GPU box): the N workers run side by side on the devices there are
+    if (have < 1 || ((int32_t)devices > have && !getenv("ALACCONVERT_SHARE_DEVICES"))) {
+        fprintf(stderr, " --devices %u: only %d GPU(s) visible\n", devices, have);
+        return false;
+    }
+    return true;
+}
 
+// The files of every group dealt to the workers (plan::deal): one host thread and one context per device, every Job with one
+// worker.  fn(jobs, device) runs on what one worker takes of one group; a worker stops at the first false, which is then
+// the answer.  Without --devices: one worker, device -1 (the classes' default, ALAC_HIP_DEVICE or 0).
+template <class F>
+bool run_dealt(const Groups &groups, uint32_t devices, F fn)
+{
+    std::vector<const std::vector<Job *> *> group;
+    std::vector<size_t> groupSizes;
+    for (Groups::const_iterator g = groups.begin(); g != groups.end(); ++g) {
+        group.push_back(&g->second);
+        groupSizes.push_back(g->second.size());
+    }
+    const uint32_t workers = devices ? devices : 1;
+    const int32_t visible = devices ? alac_hip_device_count() : 1;
+    const std::vector<std::vector<plan::Part> > perWorker = plan::deal(groupSizes, workers);
+    std::vector<int> ok(workers, 1);
+    plan::run_workers(workers, [&](uint32_t k) {
+        for (size_t i = 0; i < perWorker[k].size() && ok[k]; i++) {
+            std::vector<Job *> jobs;
+            for (size_t m : perWorker[k][i].members) jobs.push_back((*group[perWorker[k][i].group])[m]);
+            ok[k] = fn(jobs, devices ? (int)(k % (uint32_t)visible) : -1);
+        }
+    });
+    for (uint32_t k = 0; k < workers; k++)
+        if (!ok[k]) return false;
+    return true;
+}
+
+// ---- --crc / --crc-check: the CRC-32 of every file's PCM, computed on the GPU; nothing is written ----
 // ALAC files of one cookie: one TestBatch, one range per file
-void crc_alac_group(std::vector<CrcJob *> &jobs, int device)
+void crc_alac_group(std::vector<Job *> &jobs, int device)
 {
     ALACDecoder dec;
-    if (device >= 0) dec.SetDevice(device);
-    Bytes cookie(jobs[0]->contents.cookie);
-    if (dec.Init(cookie.data(), (uint32_t)cookie.size(), 0) != ALAC_noErr) {
-        fprintf(stderr, " Cannot initialise the decoder from the magic cookie: \"%s\"\n", jobs[0]->job.in.c_str());
+    if (!open_decoder(dec, jobs[0]->contents.cookie, device)) {
+        fprintf(stderr, " Cannot initialise the decoder from the magic cookie: \"%s\"\n", jobs[0]->in.c_str());
         return;
     }
-    const uint32_t ch = dec.mConfig.numChannels, bits = dec.mConfig.bitDepth;
-    const uint32_t bytesPerFrame = ch * ((bits + 7) >> 3);
-    std::vector<CrcJob *> take;
-    for (size_t j = 0; j < jobs.size(); j++) {  // as decode_group: the cookie decides what the decoder writes
-        if (!(bits == 16 || bits == 20 || bits == 24 || bits == 32) || source_bits(jobs[j]->job.info.alacSourceFlag) != bits)
-            fprintf(stderr, " Magic cookie bit depth %u does not match the file description: \"%s\"\n", bits, jobs[j]->job.in.c_str());
-        else
-            take.push_back(jobs[j]);
-    }
+    const uint32_t bits = dec.mConfig.bitDepth, bytesPerFrame = dec.mConfig.numChannels * bytes_per_sample(bits);
+    std::vector<Job *> take;
+    for (size_t j = 0; j < jobs.size(); j++)
+        if (cookie_matches_description(bits, *jobs[j])) take.push_back(jobs[j]);
     if (take.empty()) return;
-    std::vector<uint32_t> sizes, firstPacket;
+    std::vector<uint32_t> sizes;
     Bytes stream;
-    for (size_t j = 0; j < take.size(); j++) {
-        firstPacket.push_back((uint32_t)sizes.size());
-        append_packets(take[j]->job, take[j]->contents, stream, sizes);
-    }
+    const std::vector<uint32_t> firstPacket = gather_packets(take, stream, sizes);
     const uint32_t np = (uint32_t)sizes.size();
-    firstPacket.push_back(np);
     std::vector<alac_hip_pcm_digest> digests(take.size());
     std::vector<uint32_t> frames(np, 0);
     std::vector<int32_t> status(np, 0);
     const int32_t rc = dec.TestBatch(stream.data(), sizes.data(), np, firstPacket.data(), (uint32_t)take.size(), digests.data(),
                                      frames.data(), status.data());
     if (rc != ALAC_noErr) {
-        fprintf(stderr, " Decoding failed (status %d): \"%s\"\n", rc, take[0]->job.in.c_str());
+        fprintf(stderr, " Decoding failed (status %d): \"%s\"\n", rc, take[0]->in.c_str());
         return;
     }
     for (size_t j = 0; j < take.size(); j++) {
-        CrcJob &J = *take[j];
-        bool good = true;
-        for (uint32_t p = firstPacket[j]; p < firstPacket[j + 1] && good; p++) {
-            if (status[p] != 0) {
-                fprintf(stderr, " Cannot decode packet %u (status %d): \"%s\"\n", p - firstPacket[j], status[p], J.job.in.c_str());
-                good = false;
-            }
+        Job &J = *take[j];
+        uint32_t p = firstPacket[j];
+        while (p < firstPacket[j + 1] && status[p] == 0) p++;
+        if (p < firstPacket[j + 1]) {
+            fprintf(stderr, " Cannot decode packet %u (status %d): \"%s\"\n", p - firstPacket[j], status[p], J.in.c_str());
+            continue;
         }
-        if (!good) continue;
         J.crc = digests[j].crc32;
-        J.frames = digests[j].bytes / bytesPerFrame;
+        J.crcFrames = digests[j].bytes / bytesPerFrame;
         J.done = true;
     }
 }
 
 // integer PCM files: the sample bytes of all of them staged in one buffer, one range per file
-void crc_pcm_group(std::vector<CrcJob *> &jobs, int device)
+void crc_pcm_group(std::vector<Job *> &jobs, int device)
 {
     std::vector<uint64_t> ranges;
     Bytes pcm;
     for (size_t j = 0; j < jobs.size(); j++) {
-        const InputInfo &in = jobs[j]->job.info;
-        const uint64_t bytesPerFrame = (uint64_t)in.channels * ((in.bitsPerChannel + 7) >> 3);
+        const InputInfo &in = jobs[j]->info;
         // whole frames only: the encoder drops a trailing fraction of a frame (ALACEncoder.cu:984)
-        const uint64_t bytes = in.dataSize / bytesPerFrame * bytesPerFrame;
+        const uint64_t bytes = in.dataSize / frame_bytes(in) * frame_bytes(in);
         ranges.push_back(pcm.size()), ranges.push_back(bytes);
-        jobs[j]->frames = bytes / bytesPerFrame;
-        pcm.insert(pcm.end(), jobs[j]->job.file.begin() + in.dataPos, jobs[j]->job.file.begin() + in.dataPos + bytes);
+        jobs[j]->crcFrames = bytes / frame_bytes(in);
+        pcm.insert(pcm.end(), jobs[j]->file.begin() + in.dataPos, jobs[j]->file.begin() + in.dataPos + bytes);
         if (in.bigEndianPcm) alacfile::swap_samples_in_place(pcm.data() + pcm.size() - bytes, bytes, in.bitsPerChannel);
     }
     alac_hip_ctx *ctx = nullptr;
@@ -684,244 +649,93 @@ void crc_pcm_group(std::vector<CrcJob *> &jobs, int device)
 }
 
 // opens, sniffs and hashes every job; a job that cannot be done is named on stderr and keeps done == false
-void crc_run(std::vector<CrcJob> &jobs, uint32_t devices)
+void crc_run(std::vector<Job> &jobs, uint32_t devices)
 {
-    std::map<std::string, std::vector<CrcJob *> > groups;  // ALAC files by cookie ("D..."), all PCM files ("P")
+    Groups groups;  // ALAC files by cookie ("D..."), all PCM files ("P")
     for (size_t j = 0; j < jobs.size(); j++) {
-        CrcJob &J = jobs[j];
-        if (!alacfile::read_file(J.job.in, J.job.file)) {
-            fprintf(stderr, " Cannot open file \"%s\"\n", J.job.in.c_str());
-            continue;
-        }
+        Job &J = jobs[j];
+        if (!read_job(J)) continue;
         J.opened = true;
-        InputInfo &info = J.job.info;
-        std::string err = alacfile::sniff_input(J.job.file, info, true);
-        if (err.empty() && info.isAlac) {
-            InputInfo again;
-            err = info.kind == alacfile::kM4aFile ? alacfile::parse_alac_m4a(J.job.file, again, J.contents)
-                                                  : alacfile::parse_alac_caf(J.job.file, info, J.contents);
-        }
-        if (!err.empty()) {
-            fprintf(stderr, " %s: \"%s\"\n", err.c_str(), J.job.in.c_str());
+        std::string err = alacfile::sniff_input(J.file, J.info, true);
+        if (err.empty() && J.info.isAlac) err = parse_alac(J);
+        if (refused(err, J)) continue;
+        if (!J.info.isAlac && J.info.isFloat) {
+            fprintf(stderr, " --crc does not take float PCM: \"%s\"\n", J.in.c_str());
             continue;
         }
-        if (!info.isAlac && info.isFloat) {
-            fprintf(stderr, " --crc does not take float PCM: \"%s\"\n", J.job.in.c_str());
-            continue;
-        }
-        const uint32_t b = info.bitsPerChannel;
-        if (!info.isAlac && ((b != 16 && b != 20 && b != 24 && b != 32) || info.channels < 1 || info.channels > 8)) {
-            fprintf(stderr, " File \"%s\'s\" data format is of an unsupported type\n", J.job.in.c_str());
-            continue;
-        }
-        groups[info.isAlac ? "D" + std::string(J.contents.cookie.begin(), J.contents.cookie.end()) : std::string("P")].push_back(&J);
+        if (!J.info.isAlac && !pcm_format_ok(J)) continue;
+        groups[J.info.isAlac ? cookie_key(J) : std::string("P")].push_back(&J);
     }
-    // the files of every group dealt round-robin to the workers, as the conversions are
-    struct Work {
-        std::vector<CrcJob *> jobs;
-        bool alac;
-    };
-    const uint32_t workers = devices ? devices : 1;
-    const int32_t visible = devices ? alac_hip_device_count() : 1;
-    std::vector<std::vector<Work> > perWorker(workers);
-    uint32_t next = 0;
-    for (std::map<std::string, std::vector<CrcJob *> >::iterator g = groups.begin(); g != groups.end(); ++g) {
-        std::vector<Work> parts(workers);
-        for (size_t j = 0; j < g->second.size(); j++) {
-            Work &w = parts[(next + j) % workers];
-            w.alac = g->second[j]->job.info.isAlac;
-            w.jobs.push_back(g->second[j]);
-        }
-        for (uint32_t k = 0; k < workers; k++)
-            if (!parts[k].jobs.empty()) perWorker[k].push_back(parts[k]);
-        next = (uint32_t)((next + g->second.size()) % workers);
-    }
-    auto run = [&](uint32_t k) {
-        const int device = devices ? (int)(k % (uint32_t)visible) : -1;
-        for (size_t i = 0; i < perWorker[k].size(); i++)
-            (perWorker[k][i].alac ? crc_alac_group : crc_pcm_group)(perWorker[k][i].jobs, device);
-    };
-    if (workers == 1) {
-        run(0);
-    } else {
-        std::vector<std::thread> threads;
-        for (uint32_t k = 0; k < workers; k++) threads.emplace_back(run, k);
-        for (size_t k = 0; k < threads.size(); k++) threads[k].join();
-    }
+    run_dealt(groups, devices, [](std::vector<Job *> &part, int device) {
+        (part[0]->info.isAlac ? crc_alac_group : crc_pcm_group)(part, device);
+        return true;
+    });
 }
 
-// --devices N as the conversions take it
-bool crc_devices_ok(uint32_t devices)
+int crc_files(const Options &o)
 {
-    if (!devices) return true;
-    const int32_t have = alac_hip_device_count();
-    if (have < 1 || ((int32_t)devices > have && !getenv("ALACCONVERT_SHARE_DEVICES"))) {
-        fprintf(stderr, " --devices %u: only %d GPU(s) visible\n", devices, have);
-        return false;
-    }
-    return true;
-}
-
-int crc_files(const std::vector<std::string> &paths, uint32_t devices)
-{
-    if (!crc_devices_ok(devices)) return 1;
-    std::vector<CrcJob> jobs(paths.size());
-    for (size_t j = 0; j < jobs.size(); j++) jobs[j].job.in = paths[j];
-    crc_run(jobs, devices);
+    if (!devices_ok(o.devices)) return 1;
+    std::vector<Job> jobs(o.files.size());
+    for (size_t j = 0; j < jobs.size(); j++) jobs[j].in = o.files[j];
+    crc_run(jobs, o.devices);
     int rc = 0;
     for (size_t j = 0; j < jobs.size(); j++) {
-        if (jobs[j].done) printf("%08x  %llu  %s\n", jobs[j].crc, (unsigned long long)jobs[j].frames, jobs[j].job.in.c_str());
+        if (jobs[j].done) printf("%08x  %llu  %s\n", jobs[j].crc, (unsigned long long)jobs[j].crcFrames, jobs[j].in.c_str());
         else rc = 1;
     }
     return rc;
 }
 
-int crc_check(const std::string &listPath, uint32_t devices)
+int crc_check(const Options &o)
 {
-    if (!crc_devices_ok(devices)) return 1;
-    std::ifstream list(listPath.c_str());
+    if (!devices_ok(o.devices)) return 1;
+    std::ifstream list(o.crcList.c_str());
     if (!list) {
-        fprintf(stderr, " Cannot open file \"%s\"\n", listPath.c_str());
+        fprintf(stderr, " Cannot open file \"%s\"\n", o.crcList.c_str());
         return 1;
     }
-    std::vector<CrcJob> jobs;
+    std::vector<Job> jobs;
     std::vector<uint32_t> wantCrc;
     std::vector<uint64_t> wantFrames;
     int rc = 0;
     std::string line;
     for (unsigned n = 1; std::getline(list, line); n++) {
         if (line.empty()) continue;
-        // "%08x  <frames>  <path>": the path is everything behind the second pair of blanks
-        const size_t a = line.find("  "), b = a == std::string::npos ? a : line.find("  ", a + 2);
-        char *endCrc = nullptr, *endFrames = nullptr;
-        const unsigned long crc = strtoul(line.c_str(), &endCrc, 16);
-        const unsigned long long frames = a == std::string::npos ? 0 : strtoull(line.c_str() + a + 2, &endFrames, 10);
-        if (a != 8 || b == std::string::npos || b + 2 >= line.size() || endCrc != line.c_str() + a || endFrames != line.c_str() + b) {
-            fprintf(stderr, " %s: line %u is not \"<crc32>  <frames>  <path>\"\n", listPath.c_str(), n);
+        Job J;
+        uint32_t crc = 0;
+        uint64_t frames = 0;
+        if (!plan::parse_crc_line(line, crc, frames, J.in)) {
+            fprintf(stderr, " %s: line %u is not \"<crc32>  <frames>  <path>\"\n", o.crcList.c_str(), n);
             rc = 1;
             continue;
         }
-        jobs.push_back(CrcJob());
-        jobs.back().job.in = line.substr(b + 2);
-        wantCrc.push_back((uint32_t)crc);
+        jobs.push_back(J);
+        wantCrc.push_back(crc);
         wantFrames.push_back(frames);
     }
-    crc_run(jobs, devices);
+    crc_run(jobs, o.devices);
     for (size_t j = 0; j < jobs.size(); j++) {
-        const bool ok = jobs[j].done && jobs[j].crc == wantCrc[j] && jobs[j].frames == wantFrames[j];
-        printf("%s: %s\n", jobs[j].job.in.c_str(), ok ? "OK" : jobs[j].opened ? "FAILED" : "FAILED open");
+        const bool ok = jobs[j].done && jobs[j].crc == wantCrc[j] && jobs[j].crcFrames == wantFrames[j];
+        printf("%s: %s\n", jobs[j].in.c_str(), ok ? "OK" : jobs[j].opened ? "FAILED" : "FAILED open");
         if (!ok) rc = 1;
     }
     return rc;
 }
 
-}  // namespace
-
-int main(int argc, char *argv[])
+// ---- the conversions: <in> <out> pairs, PCM in -> ALAC out, ALAC in -> PCM out ----
+int convert(const Options &o)
 {
-    std::vector<std::string> files;
-    bool batch = false, lpc = false, verify = false, verifySource = false, compare = false, malformed = argc < 2;
-    uint32_t segmentPackets = 0, devices = 0, floatBits = 0;
-    bool crc = false;
-    std::string crcList;  // --crc-check <list>
-    bool floatAuto = false;  // --float-bits auto: floatBits stays 0, every file gets its own depth from the probe
-    DitherOption dither;
-    for (int i = 1; i < argc && !malformed; i++) {
-        const std::string a = argv[i];
-        if (a == "-h") {
-            malformed = true;
-        } else if (a == "--batch") {
-            batch = true;
-        } else if (a == "--lpc") {
-            lpc = true;
-        } else if (a == "--verify") {
-            verify = true;
-        } else if (a == "--verify-source") {
-            verifySource = true;
-        } else if (a == "--compare") {
-            compare = true;
-        } else if (a == "--crc") {
-            crc = true;
-        } else if (a == "--crc-check" && i + 1 < argc) {
-            crcList = argv[++i];
-            if (crcList.empty()) malformed = true;
-        } else if (a == "--segment-packets" && i + 1 < argc) {
-            segmentPackets = (uint32_t)strtoul(argv[++i], nullptr, 10);
-            if (segmentPackets == 0) malformed = true;
-        } else if (a == "--float-bits" && i + 1 < argc) {
-            if (std::string(argv[i + 1]) == "auto") {
-                floatAuto = true, floatBits = 0, i++;
-            } else {
-                floatAuto = false;
-                floatBits = (uint32_t)strtoul(argv[++i], nullptr, 10);
-                if (floatBits != 16 && floatBits != 20 && floatBits != 24 && floatBits != 32) malformed = true;
-            }
-        } else if (a == "--dither") {
-            dither.on = true;
-        } else if (a == "--dither-seed" && i + 1 < argc) {
-            char *end = nullptr;
-            dither.seed = strtoull(argv[++i], &end, 0);  // decimal or 0x-hex
-            if (end == argv[i] || *end) malformed = true;
-        } else if (a == "--devices" && i + 1 < argc) {
-            devices = (uint32_t)strtoul(argv[++i], nullptr, 10);
-            if (devices == 0) malformed = true;
-        } else if (!a.empty() && a[0] == '-') {
-            printf("unknown option: %s\n", a.c_str());  // main.cu:92-96
-            malformed = true;
-        } else {
-            files.push_back(a);
-        }
-    }
-    // --crc and --crc-check stand alone (but --devices N): any number of inputs resp. one list, no output files
-    const bool crcMode = crc || !crcList.empty();
-    if (!malformed && crcMode &&
-        (batch || lpc || verify || verifySource || compare || segmentPackets || floatBits || floatAuto || dither.on ||
-         (crc && !crcList.empty()) || (crc ? files.empty() : !files.empty())))
-        malformed = true;
-    if (!malformed && !crcMode && (files.size() < 2 || (files.size() & 1) || (!batch && files.size() != 2))) malformed = true;
-    if (!malformed && !crcMode && devices && !batch) malformed = true;  // one file is one serial chain: nothing to deal out
-    // --compare stands alone: two files, no other option
-    // (but --dither [--dither-seed S], for a float reference of a file that was encoded with it)
-    const bool floatInput = floatBits != 0 || floatAuto;
-    if (!malformed && compare && (batch || lpc || verify || verifySource || segmentPackets || devices || floatInput)) malformed = true;
-    if (malformed) {
-        usage();
-        return 1;
-    }
-    if (crc) return crc_files(files, devices);
-    if (!crcList.empty()) return crc_check(crcList, devices);
-    if (compare) return compare_files(files[0], files[1], dither);
-    if (dither.on && floatBits != 16 && floatBits != 20 && floatBits != 24) {  // auto promises lossless: no dither there
-        fprintf(stderr, " --dither needs --float-bits 16, 20 or 24\n");
-        usage();
-        return 1;
-    }
-    if (verifySource && !floatInput) {
-        fprintf(stderr, " --verify-source needs float input (--float-bits N); --verify checks an integer encode: \"%s\"\n", files[0].c_str());
-        return 1;
-    }
-    if (floatInput && verify) {
-        fprintf(stderr, " --verify does not take float input (--float-bits): \"%s\"\n", files[0].c_str());
-        return 1;
-    }
-
-    std::vector<Job> jobs(files.size() / 2);
+    // every file opened and sniffed, in the order of the command line
+    std::vector<Job> jobs(o.files.size() / 2);
     for (size_t j = 0; j < jobs.size(); j++) {
         Job &J = jobs[j];
-        J.in = files[2 * j];
-        J.out = files[2 * j + 1];
-        if (!alacfile::read_file(J.in, J.file)) {
-            fprintf(stderr, " Cannot open file \"%s\"\n", J.in.c_str());
-            return 1;
-        }
+        J.in = o.files[2 * j];
+        J.out = o.files[2 * j + 1];
+        if (!read_job(J)) return 1;
         printf("Input file: %s\n", J.in.c_str());
         printf("Output file: %s\n", J.out.c_str());
-        const std::string err = alacfile::sniff_input(J.file, J.info, floatInput);
-        if (!err.empty()) {
-            fprintf(stderr, " %s: \"%s\"\n", err.c_str(), J.in.c_str());
-            return 1;
-        }
-        if (floatInput) {
+        if (refused(alacfile::sniff_input(J.file, J.info, o.floatInput()), J)) return 1;
+        if (o.floatInput()) {
             if (!J.info.isFloat) {
                 fprintf(stderr, " --float-bits takes float PCM input, not integer PCM or ALAC: \"%s\"\n", J.in.c_str());
                 return 1;
@@ -938,104 +752,27 @@ int main(int argc, char *argv[])
             J.floatBigEndian = J.info.bigEndianPcm;
             J.info.isFloat = J.info.bigEndianPcm = false;
             // (auto: 32 bits until probe_float_jobs below has the file's own depth)
-            J.info.bitsPerChannel = floatAuto ? 32 : floatBits;
-            J.info.dataSize = frames * J.info.channels * ((J.info.bitsPerChannel + 7) >> 3);
+            J.info.bitsPerChannel = o.floatAuto ? 32 : o.floatBits;
+            J.info.dataSize = frames * frame_bytes(J.info);
         }
-        if (!J.info.isAlac) {
-            const uint32_t b = J.info.bitsPerChannel;
-            if ((b != 16 && b != 20 && b != 24 && b != 32) || J.info.channels < 1 || J.info.channels > 8) {  // kALACMaxChannels
-                fprintf(stderr, " File \"%s\'s\" data format is of an unsupported type\n", J.in.c_str());
-                return 1;
-            }
-        }
+        if (!J.info.isAlac && !pcm_format_ok(J)) return 1;
     }
-
-    if (floatAuto && !probe_float_jobs(jobs, devices ? 0 : -1)) return 1;
+    if (o.floatAuto && !probe_float_jobs(jobs, o.devices ? 0 : -1)) return 1;
 
     // group: encode jobs by (depth, channels); decode jobs by cookie
-    std::map<std::string, std::vector<Job *> > groups;
+    Groups groups;
     for (size_t j = 0; j < jobs.size(); j++) {
         Job &J = jobs[j];
-        std::string key;
-        if (J.info.isAlac) {
-            alacfile::AlacCafContents c;
-            InputInfo again;
-            const std::string err = J.info.kind == alacfile::kM4aFile ? alacfile::parse_alac_m4a(J.file, again, c)
-                                                                      : alacfile::parse_alac_caf(J.file, J.info, c);
-            if (!err.empty()) {
-                fprintf(stderr, " %s: \"%s\"\n", err.c_str(), J.in.c_str());
-                return 1;
-            }
-            key = "D" + std::string(c.cookie.begin(), c.cookie.end());
-        } else {
-            char buf[64];
-            snprintf(buf, sizeof(buf), "E%u/%u", J.info.bitsPerChannel, J.info.channels);
-            key = buf;
-        }
-        groups[key].push_back(&J);
+        if (J.info.isAlac && refused(parse_alac(J), J)) return 1;
+        char key[64];
+        snprintf(key, sizeof(key), "E%u/%u", J.info.bitsPerChannel, J.info.channels);
+        groups[J.info.isAlac ? cookie_key(J) : std::string(key)].push_back(&J);
     }
-    // one unit of work = the jobs of one group that one device takes
-    struct Work {
-        std::vector<Job *> jobs;
-        std::vector<alacfile::AlacCafContents> contents;
-        bool decode;
-    };
-    uint32_t workers = 1;
-    int firstDevice = -1;  // -1: the classes' default (ALAC_HIP_DEVICE or 0), the single-device behaviour of every round before
-    if (devices) {
-        const int32_t have = alac_hip_device_count();
-        // ALACCONVERT_SHARE_DEVICES=1 (tests on a one-GPU box): the N workers run side by side on the devices there are
-        const bool share = getenv("ALACCONVERT_SHARE_DEVICES") != nullptr;
-        if (have < 1 || ((int32_t)devices > have && !share)) {
-            fprintf(stderr, " --devices %u: only %d GPU(s) visible\n", devices, have);
-            return 1;
-        }
-        workers = devices;
-        firstDevice = 0;
-    }
-    std::vector<std::vector<Work> > perWorker(workers);
-    const int32_t visible = devices ? alac_hip_device_count() : 1;
-    uint32_t next = 0;
-    for (std::map<std::string, std::vector<Job *> >::iterator g = groups.begin(); g != groups.end(); ++g) {
-        std::vector<Job *> &v = g->second;
-        const bool dec = v[0]->info.isAlac;
-        std::vector<Work> parts(workers);
-        for (size_t j = 0; j < v.size(); j++) {
-            Work &w = parts[(next + j) % workers];  // files dealt round-robin, continuing where the last group stopped
-            w.decode = dec;
-            w.jobs.push_back(v[j]);
-            if (dec) {
-                w.contents.push_back(alacfile::AlacCafContents());
-                if (v[j]->info.kind == alacfile::kM4aFile) {
-                    InputInfo again;
-                    alacfile::parse_alac_m4a(v[j]->file, again, w.contents.back());
-                } else {
-                    alacfile::parse_alac_caf(v[j]->file, v[j]->info, w.contents.back());
-                }
-            }
-        }
-        for (uint32_t k = 0; k < workers; k++)
-            if (!parts[(next + k) % workers].jobs.empty()) perWorker[(next + k) % workers].push_back(parts[(next + k) % workers]);
-        next = (uint32_t)((next + v.size()) % workers);
-    }
-    std::vector<int> ok(workers, 1);
-    auto run = [&](uint32_t k) {
-        const int device = firstDevice < 0 ? -1 : (int)(k % (uint32_t)visible);
-        for (size_t i = 0; i < perWorker[k].size() && ok[k]; i++) {
-            Work &w = perWorker[k][i];
-            ok[k] = w.decode ? decode_group(w.jobs, w.contents, device) : encode_group(w.jobs, segmentPackets, lpc, verify, verifySource, dither, device);
-        }
-    };
-    if (workers == 1) {
-        run(0);
-    } else {
-        // one host thread and one context per device; nothing is shared between them (every Job belongs to one Work)
-        std::vector<std::thread> threads;
-        for (uint32_t k = 0; k < workers; k++) threads.emplace_back(run, k);
-        for (size_t k = 0; k < threads.size(); k++) threads[k].join();
-    }
-    for (uint32_t k = 0; k < workers; k++)
-        if (!ok[k]) return 1;
+    if (!devices_ok(o.devices)) return 1;
+    if (!run_dealt(groups, o.devices, [&](std::vector<Job *> &part, int device) {
+            return part[0]->info.isAlac ? decode_group(part, device) : encode_group(part, o, device);
+        }))
+        return 1;
     for (size_t j = 0; j < jobs.size(); j++) {
         if (!alacfile::write_file(jobs[j].out, jobs[j].result)) {
             fprintf(stderr, " Cannot open file \"%s\"\n", jobs[j].out.c_str());
@@ -1043,4 +780,15 @@ int main(int argc, char *argv[])
         }
     }
     return 0;
+}
+
+}  // namespace
+
+int main(int argc, char *argv[])
+{
+    Options o;
+    if (!plan::parse_args(argc, argv, o)) return 1;
+    if (o.crc) return crc_files(o);
+    if (!o.crcList.empty()) return crc_check(o);
+    return o.compare ? compare_files(o) : convert(o);
 }
