@@ -73,7 +73,9 @@ int32_t alac_hip_synchronize(alac_hip_ctx *ctx);
  *                          mono: 10 240), and again from 21 761 to 34 816 chains (mono: 26 112), where the two-lane workers no
  *                          longer have a SIMD each
  *   "fused" (0/1)          encode: predictor || entropy coder as producer/consumer launches (latency and tiny regimes);
- *                          0 = one plain kernel per stage ("stagewise": also what frames above 524 287 samples get)
+ *                          0 = one plain kernel per stage ("stagewise").  Frames above 524 287 samples keep their regime
+ *                          and its fused final launch; only the mixRes search in front of it runs as plain launches
+ *                          (its progress word counts the rows of a pass in 16 bits), and "overlap_pos" is off with it
  *   "fold" (0/1)           latency regime: numU / numV / escape decision and the packet sizes inside the final launch
  *   "split_coder" (0/1)    tiny regime: the final coder of a chain on two waves
  *   "overlap_pos" (0/1)    chained tiny batches: packet position p + 1's search beside position p's final pass

@@ -22,6 +22,11 @@ Outputs (data only — inputs and expected outputs, no reference source):
                       (tests/test_gpu_wholefile.py) and the CPU suite can check them (tests/test_oracle.py)
   wav_headers.json    the bytes in front of the sample data of each of those WAV files: with the xz fixture, the whole
                       file (oracle_lib.reference_wav_bytes, tests/test_container.py)
+  long_runs.npz       zero runs around the 65 535-zero cap of the run code (ag_enc.c:333-349) as (value, repeat) recipes
+                      (oracle_lib.long_run_cases) with the bytes and bit counts of the reference's dyn_comp; written with
+                      fixed zip time stamps, so a second run gives the same file byte for byte
+
+One fixture alone:   python tests/golden/make_golden.py long_runs
 """
 import json
 import os
@@ -239,11 +244,44 @@ def make_known_answers(o, r):
     print("known_answers.json written")
 
 
+def save_npz_reproducible(path, arrays):
+    """np.savez_compressed with the time stamp of every member fixed: the same arrays give the same file"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as zf:
+        for name, a in arrays.items():
+            b = io.BytesIO()
+            np.lib.format.write_array(b, np.asanyarray(a), allow_pickle=False)
+            zi = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            zi.external_attr = 0o644 << 16
+            zf.writestr(zi, b.getvalue())
+
+
+def make_long_runs(o, r):
+    from oracle_lib import expand_recipe, long_run_cases
+    out, meta = {}, []
+    for i, c in enumerate(long_run_cases()):
+        pc = expand_recipe(c["recipe"])
+        data, nbits = o.dyn_comp(pc, c["bits"], start_bit=c["start_bit"], mb0=c["mb"], pb=c["pb"], kb=c["kb"],
+                                 fn=r.lib.ref_dyn_comp_flat)
+        st, back, nb2 = o.dyn_decomp(data, len(data), len(pc), c["bits"], start_bit=c["start_bit"], mb0=c["mb"], pb=c["pb"],
+                                     kb=c["kb"], fn=r.lib.ref_dyn_decomp_flat)
+        assert st == 0 and nb2 == nbits and np.array_equal(back, pc), c  # the reference round-trips its own bits
+        out[f"r{i}"] = np.asarray(c["recipe"], np.int32).reshape(-1, 2)
+        out[f"b{i}"] = data
+        meta.append(dict(id=i, n=int(len(pc)), bits=c["bits"], mb=c["mb"], pb=c["pb"], kb=c["kb"], start_bit=c["start_bit"],
+                         nbits=int(nbits)))
+    out["meta"] = np.frombuffer(json.dumps(meta).encode(), np.uint8)
+    path = os.path.join(HERE, "long_runs.npz")
+    save_npz_reproducible(path, out)
+    print("long_runs.npz:", len(meta), "cases,", os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
     o, r = Oracle(), Ref()
-    make_stage_vectors(o, r)
-    make_packets(o, r)
-    make_known_answers(o, r)
-    make_forged(o, r)
-    make_wav_pcm_fixtures()
-    make_caf_headers()
+    makers = dict(stage_vectors=lambda: make_stage_vectors(o, r), packets=lambda: make_packets(o, r),
+                  known_answers=lambda: make_known_answers(o, r), forged=lambda: make_forged(o, r),
+                  wav_pcm=make_wav_pcm_fixtures, caf_headers=make_caf_headers, long_runs=lambda: make_long_runs(o, r))
+    for name in sys.argv[1:] or list(makers):
+        makers[name]()

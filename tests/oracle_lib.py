@@ -376,3 +376,84 @@ def splice_elements(packets):
         bits.append(e)
     bits.append(np.array([1, 1, 1], np.uint8))
     return np.packbits(np.concatenate(bits))
+
+
+# ---- long zero runs: the 65 535-zero cap of the adaptive Golomb run code (ag_enc.c:333-349) ---------------------
+
+LONG_RUN_BITS = (16, 20, 24, 32)
+LONG_RUN_PARAMS = ((10, 40, 14), (30, 63, 16))  # (mb, pb, kb): the encoder's own, and a foreign cookie's
+
+
+def expand_recipe(recipe):
+    """[(value, repeat)] -> int32 residual vector"""
+    r = np.asarray(recipe, np.int64).reshape(-1, 2)
+    return np.repeat(r[:, 0], r[:, 1]).astype(np.int32)
+
+
+def long_run_recipes():
+    """The residual vectors of tests/golden/long_runs.npz as (value, repeat) recipes: zero runs around the first firing of
+    the cap (65 533..65 538 zeros) behind a few non-zero symbols, at the very start, and ending the vector (the open run
+    closed by the end of the stream); around the second firing (131 070..131 073); and 200 000 zeros followed by symbols
+    and a second long run."""
+    out = []
+    for z in range(65533, 65539):
+        out.append([(7, 1), (-2, 1), (1, 1), (0, z), (3, 1), (-1, 1)])
+        out.append([(0, z), (2, 1)])
+        out.append([(4, 1), (0, z)])
+        out.append([(0, z)])
+    for z in range(131070, 131074):
+        out.append([(3, 1), (0, z), (-5, 1)])
+        out.append([(3, 1), (0, z)])
+    out.append([(1, 1), (0, 200000), (9, 1), (-9, 1), (0, 70000), (1, 1)])
+    return out
+
+
+def long_run_cases():
+    """every recipe at every bit size with the encoder's (mb, pb, kb), and with the foreign triple at one bit size that
+    rotates with the recipe; the start bit offset alternates 0 / 5 -> [dict(recipe, bits, mb, pb, kb, start_bit)]"""
+    cases = []
+    own, foreign = LONG_RUN_PARAMS
+    for ri, rec in enumerate(long_run_recipes()):
+        combos = [(bits, own) for bits in LONG_RUN_BITS] + [(LONG_RUN_BITS[ri % len(LONG_RUN_BITS)], foreign)]
+        for ci, (bits, (mb, pb, kb)) in enumerate(combos):
+            cases.append(dict(recipe=rec, bits=bits, mb=mb, pb=pb, kb=kb, start_bit=5 * ((ri + ci) & 1)))
+    return cases
+
+
+def load_long_runs():
+    """tests/golden/long_runs.npz -> [dict(recipe int64 [k][2], bits, mb, pb, kb, start_bit, nbits, data uint8)]"""
+    import json
+    z = np.load(os.path.join(GOLDEN_DIR, "long_runs.npz"))
+    meta = json.loads(bytes(z["meta"]).decode())
+    return [dict(m, recipe=z[f"r{m['id']}"], data=z[f"b{m['id']}"]) for m in meta]
+
+
+def coded_zero_runs(residuals, mb0=10, pb=40, maxrun=65535):
+    """The zero runs dyn_comp codes for a residual vector, as [(index of the run's first zero, zeros swallowed)]: the mean
+    tracker and the run rule of ag_enc.c:285-358 walked in Python, without the bit writer.  A stretch of zero residuals is NOT
+    one run: its first zeros are ordinary symbols until the mean has decayed (mb < QB / 4), and a run that swallows `maxrun`
+    zeros is closed there.  For tests that must prove their inputs reach the cap; checked against closed forms in
+    tests/test_long_runs.py."""
+    r = np.asarray(residuals, np.int64)
+    n = len(r)
+    nz_at = np.flatnonzero(r)
+    t2 = np.where(r < 0, -2 * r - 1, 2 * r)  # the zig-zag image: 2|r| - (r < 0)
+    mb, zmode, c, runs = mb0, 0, 0, []
+    while c < n:
+        sym = int(t2[c]) - zmode
+        c += 1
+        mb = pb * (sym + zmode) + mb - ((pb * mb) >> 9)
+        if sym > 0xffff:
+            mb = 0xffff
+        zmode = 0
+        if (mb << 2) < 512 and c < n:
+            zmode = 1
+            k = int(np.searchsorted(nz_at, c))
+            end = int(nz_at[k]) if k < len(nz_at) else n  # the next non-zero residual, or the end of the vector
+            nz = end - c
+            if nz >= maxrun:
+                nz, zmode = maxrun, 0
+            runs.append((c, nz))
+            c += nz
+            mb = 0
+    return runs
