@@ -1217,24 +1217,8 @@ __device__ __forceinline__ int32_t lms_step_dec_wide(int32_t (&a)[T], int32_t (&
 #pragma unroll
     for (int i = 0; i < T; i++) s = __mul24((int32_t)(int16_t)a[i], b[i]) + s;
     const int32_t out = __builtin_amdgcn_sbfe(del + tp - (s >> kDenShift), 0, chanbits);
-    // coefficient update, driven by del: the threshold form of the walk (alac_lms.hpp), weights T - i
-    const int32_t nd = -del;
-    const int32_t adel = max(del, nd);
-    const int32_t nsg = sign3(nd);
-    const int32_t rc = (del >> 31) & ((1 << kDenShift) - 1);
-    int32_t sb[T];
-    uint32_t t[T];
-#pragma unroll
-    for (int i = 0; i < T; i++) {
-        sb[i] = sign3(b[i]);
-        t[i] = (uint32_t)(__mul24(sb[i], b[i]) + rc) >> kDenShift;
-    }
-    int32_t S[T];
-    S[T - 1] = 0;
-#pragma unroll
-    for (int i = T - 1; i > 0; i--) S[i - 1] = (int32_t)__umul24(t[i], (uint32_t)(T - i)) + S[i];
-#pragma unroll
-    for (int i = 0; i < T; i++) a[i] = __mul24(adel > S[i] ? nsg : 0, sb[i]) + a[i];
+    lms_adapt_thresholds<T>(a, b, del, (1 << kDenShift) - 1, kDenShift, [](int, int32_t sg) { return sg; },
+                            [](int i) { return (uint32_t)(T - i); });
     tp = w[T - 1];
 #pragma unroll
     for (int i = T - 1; i > 0; i--) w[i] = w[i - 1];
@@ -1306,8 +1290,6 @@ __device__ __forceinline__ void unpc_wide_body(const DecV1Args &V, uint32_t bloc
         w[i] = o16[15 - i];  // out[j - 1 - i] at j = 16
     }
     int32_t tp = o16[15 - T];  // out[j - T - 1]
-
-    // ---- 32-step blocks (load32) ----
     const uint32_t nMax = wave_max_u32(n);
     int32_t dA[32], dB[32];
     if (32 < nMax) load32(row, 32, dA);
@@ -1364,23 +1346,8 @@ __device__ __forceinline__ int32_t lms_step_dec_any(int32_t (&a)[8], int32_t (&w
 #pragma unroll
     for (int i = 0; i < 8; i++) s = __mul24((int32_t)(int16_t)a[i], b[i]) + s;  // (dead taps: a = 0)
     const int32_t out = __builtin_amdgcn_sbfe(del + tp + ((L.denhalf - s) >> L.ds), 0, chanbits);
-    const int32_t nd = -del;
-    const int32_t adel = max(del, nd);
-    const int32_t nsg = sign3(nd);
-    const int32_t rc = (del >> 31) & L.rcMask;
-    int32_t sb[8];
-    uint32_t t[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        sb[i] = sign3(b[i]) & L.am[i];
-        t[i] = (uint32_t)(__mul24(sb[i], b[i]) + rc) >> L.ds;
-    }
-    int32_t S[8];
-    S[7] = 0;
-#pragma unroll
-    for (int i = 7; i > 0; i--) S[i - 1] = (int32_t)__umul24(t[i], L.wg[i]) + S[i];
-#pragma unroll
-    for (int i = 0; i < 8; i++) a[i] = __mul24(adel > S[i] ? nsg : 0, sb[i]) + a[i];
+    lms_adapt_thresholds<8>(a, b, del, L.rcMask, L.ds, [&](int i, int32_t sg) { return sg & L.am[i]; },
+                            [&](int i) { return L.wg[i]; });
     int32_t leaving = w[0];
 #pragma unroll
     for (int i = 1; i < 8; i++) leaving = (L.na - 1 == i) ? w[i] : leaving;
@@ -1516,27 +1483,9 @@ __device__ __forceinline__ int32_t lms_step_dec_pair(int32_t (&a)[T], int32_t (&
 #pragma unroll
     for (int i = 0; i < T; i++) s = __mul24((int32_t)(int16_t)a[i], b[i]) + s;
     const int32_t out = __builtin_amdgcn_sbfe(del + tp - (s >> kDenShift), 0, chanbits);
-    const int32_t nd = -del;
-    const int32_t adel = max(del, nd);
-    const int32_t nsg = sign3(nd);
-    const int32_t rc = (del >> 31) & ((1 << kDenShift) - 1);
-    int32_t sb[T];
-    uint32_t t[T];
-#pragma unroll
-    for (int i = 0; i < T; i++) {
-        sb[i] = sign3(b[i]);
-        if (T == 8 && i >= 4) sb[i] &= act;
-        t[i] = (uint32_t)(__mul24(sb[i], b[i]) + rc) >> kDenShift;
-    }
-    int32_t S[T];
-    S[T - 1] = 0;
-#pragma unroll
-    for (int i = T - 1; i > 0; i--) {
-        const uint32_t weight = T == 4 ? (uint32_t)(T - i) : (i < 4 ? wg[i] : (uint32_t)(T - i));
-        S[i - 1] = (int32_t)__umul24(t[i], weight) + S[i];
-    }
-#pragma unroll
-    for (int i = 0; i < T; i++) a[i] = __mul24(adel > S[i] ? nsg : 0, sb[i]) + a[i];
+    lms_adapt_thresholds<T>(
+        a, b, del, (1 << kDenShift) - 1, kDenShift, [&](int i, int32_t sg) { return (T == 8 && i >= 4) ? (sg & act) : sg; },
+        [&](int i) { return T == 4 ? (uint32_t)(T - i) : (i < 4 ? wg[i] : (uint32_t)(T - i)); });
     tp = T == 4 ? w[3] : (is4 ? w[3] : w[7]);
 #pragma unroll
     for (int i = T - 1; i > 0; i--) w[i] = w[i - 1];
@@ -1736,7 +1685,6 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, const VerifyF
         w[i] = o16[15 - i];
     }
     int32_t tp = T == 4 ? o16[11] : (is4 ? o16[11] : o16[7]);
-
     const uint32_t nMax = wave_max_u32(n);
     int32_t dA[32], dB[32];
     if (32 < nMax) load32(row, 32, dA);

@@ -15,10 +15,18 @@
 // |del| > S_k := sum_{i > k} (na - i) * t_i, because the partial sums only grow.
 #pragma once
 
+#include <stdint.h>
+#if defined(__HIPCC__)
 #include "alac_dev.hpp"
+#define ALAC_RULE_FN __device__ __forceinline__
+#else  // a host compiler sees lms_adapt_thresholds alone (tests/cpp/lms_rule.cpp): its qualifiers and primitives in plain C++
+#include <algorithm>
+#define ALAC_RULE_FN inline
+#endif
 
 namespace alacdev {
 
+#if defined(__HIPCC__)
 constexpr int kDppXor1 = 0xB1;  // quad_perm:[1,0,3,2]: partner lane of a 2-lane chain
 
 __device__ __forceinline__ int32_t dpp_xor1(int32_t src)
@@ -40,7 +48,46 @@ __device__ __forceinline__ int32_t sign3(int32_t x)
     asm("v_med3_i32 %0, %1, -1, 1" : "=v"(r) : "v"(x));
     return r;
 }
+#else
+using std::max;
+inline int32_t sign3(int32_t x) { return x > 0 ? 1 : (x < 0 ? -1 : 0); }
+// v_mul_i32_i24 / v_mul_u32_u24: the low 24 bits of each operand, the low 32 bits of the product
+inline int32_t __mul24(int32_t x, int32_t y) { return (int32_t)(uint32_t)((int64_t)((int32_t)((uint32_t)x << 8) >> 8) * ((int32_t)((uint32_t)y << 8) >> 8)); }
+inline uint32_t __umul24(uint32_t x, uint32_t y) { return (uint32_t)((uint64_t)(x & 0xffffffu) * (y & 0xffffffu)); }
+#endif
 
+// ---- the coefficient update of a step, the walk in threshold form (top of this file): the one spelling of the decoder's
+// one-lane steps (lms_step_dec_wide / _any / _pair, alac_decode_v1.hip).  b[i] = top - in[j - 1 - k] for the tap k of slot i,
+// a[i] its coefficient (an int16 value in an int32); sign(i, sg): sg, or 0 for a slot that holds no tap; weight(i): na - k.
+// No term may wrap: |b| < 2^23 (chanBits <= 23).  Two steps keep their own copy: lms4_step_dec below was joined (its carry
+// one more callable) and taken out again — k_dec_fused_wg's step loop then split two v_add_u32_dpp into v_mov_b32_dpp +
+// v_add_u32 and the fused launch measured 0.3 % slower at 10 000 packets; joining the encoder's lms_step was not tried.
+template <int T, typename Sign, typename Weight>
+ALAC_RULE_FN void lms_adapt_thresholds(int32_t (&a)[T], const int32_t (&b)[T], int32_t del, int32_t rcMask, int32_t ds, Sign sign,
+                                       Weight weight)
+{
+    // t_i = (|b_i| + rc) >> ds with rc = 2^ds - 1 for del < 0 (the arithmetic shift of a negative product rounds away from
+    // zero, dp_enc.c:176), S_{i-1} = t_i * weight_i + S_i, tap i is touched iff |del| > S_i
+    const int32_t nd = -del;
+    const int32_t adel = max(del, nd);
+    const int32_t nsg = sign3(nd);  // -sign(del): what a touched tap adds per sign(b)
+    const int32_t rc = (del >> 31) & rcMask;
+    int32_t sb[T];
+    uint32_t t[T];
+#pragma unroll
+    for (int i = 0; i < T; i++) {
+        sb[i] = sign(i, sign3(b[i]));
+        t[i] = (uint32_t)(__mul24(sb[i], b[i]) + rc) >> ds;  // |b| = sign(b) * b
+    }
+    int32_t S[T];  // in-lane part of S_k, from the top tap down
+    S[T - 1] = 0;
+#pragma unroll
+    for (int i = T - 1; i > 0; i--) S[i - 1] = (int32_t)__umul24(t[i], weight(i)) + S[i];
+#pragma unroll
+    for (int i = 0; i < T; i++) a[i] = __mul24(adel > S[i] ? nsg : 0, sb[i]) + a[i];
+}
+
+#if defined(__HIPCC__)
 // ---- lane mappings --------------------------------------------------------------------------------------
 // A chain owns L adjacent lanes (L = 1, 2 or 4, inside one DPP quad), each lane T taps: <T, L> covers T * L >= na taps.
 //   <4, 1>  4-tap rows, one lane per chain (64 chains per wave)
@@ -246,4 +293,8 @@ __device__ __forceinline__ int32_t lms4_step_dec(int32_t (&a)[4], int32_t (&w)[4
     return out;
 }
 
+#endif  // __HIPCC__
+
 }  // namespace alacdev
+
+#undef ALAC_RULE_FN

@@ -1,9 +1,15 @@
 """GPU parity, decode direction: HIP decode of oracle-encoded streams == the PCM that was encoded and ==
 the oracle decoder, incl. partial packets, escapes, shift-off bytes, every bit depth."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 import alac_amd
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+import forge  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -470,3 +476,51 @@ def test_stream_at_any_byte_alignment(gpu_ctx, oracle, depth, separate):
     finally:
         gpu_ctx.set_option("dec_fused", keep_fused)
         gpu_ctx.set_option("dec_direct", keep_direct)
+
+
+WALKER_NS = [16, 17, 24, 31, 32, 33, 47, 48, 63, 64, 65, 95, 96, 97, 104]
+
+
+@pytest.mark.parametrize("stream,depth,pair", [("mono", 16, 1), ("stereo", 16, 1), ("stereo", 16, 0), ("stereo", 24, 1), ("stereo", 24, 0),
+                                               ("any", 16, 1)])
+def test_one_lane_walker_edges(gpu_ctx, oracle, stream, depth, pair):
+    """the one-lane predictors of the separate launches (dec_fused = 0) walk a row as samples 16 .. 31, then 32-step blocks,
+    with stores predicated per lane: 192 packets of frame size 104 whose sample counts cycle through lengths that
+    end in the 16-sample head, inside samples 16 .. 31 and on either side of each edge of a 32-step block, so that every wave
+    mixes all of them.  mono: wide-4 and wide-8 chains; stereo: pairs of 4 + 4, 8 + 8 and 4 + 8 taps (a 4-tap chain in the 8-tap
+    class), or with dec_pair = 0 the same chains one by one; any: taps 1 .. 8 with denShift 4, 9 and 12 (unpc_any_body).  Byte
+    for byte the oracle's decode, and the bytes behind a packet's own frames keep the fill they had before the call."""
+    import torch
+    frame, n = 104, 192
+    channels = 1 if stream == "mono" else 2
+    rng = np.random.default_rng(depth * 7 + channels + pair)
+    f = forge.Forger(oracle)
+    ns = [WALKER_NS[i % len(WALKER_NS)] for i in range(n)]
+    pk = []
+    for i in range(n):
+        if stream == "any":
+            shape = [(1 + (i + 3 * c) % 8, (4, 9, 12)[(i // 8 + c) % 3]) for c in range(channels)]
+        else:
+            shape = [((4, 8)[((i >> c) & 1)], 9) for c in range(channels)]  # stereo: 4 + 4, 8 + 4, 4 + 8, 8 + 8
+        params = [forge.ChannelParams(num, den, 4, 0, forge.default_coefs(num, den)) for num, den in shape]
+        pcm = forge.test_signal(rng, int(rng.integers(0, 5)), ns[i], depth, channels, headroom_bits=1)
+        pk.append(f.element(pcm, ns[i], depth, channels, frame, params, mix_bits=2, mix_res=int(rng.integers(0, 5)) if channels == 2 else 0,
+                            bytes_shifted=1 if depth == 24 else 0))
+    ck = forge.cookie(frame, depth, channels)
+    fmt = alac_amd.make_format(frame, depth, channels)
+    bpf = fmt.bytes_per_frame
+    packets = np.concatenate(pk)
+    offs = np.concatenate([[0], np.cumsum([len(x) for x in pk])]).astype(np.int64)
+    fill = torch.full((n * fmt.packet_bytes,), 0xA7, dtype=torch.uint8, device="cuda")
+    bufs = (fill, torch.zeros(n, dtype=torch.int32, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda"))
+    with gpu_ctx.options(dec_fused=0, dec_pair=pair):
+        out, dns, st, _ = gpu_ctx.decode(ck, torch.from_numpy(packets).cuda(), torch.from_numpy(offs).cuda(), n, out=bufs)
+        gpu_ctx.synchronize()
+    assert st.cpu().tolist() == [0] * n and dns.cpu().tolist() == ns
+    got = out.cpu().numpy().reshape(n, fmt.packet_bytes)
+    dec = oracle.decoder(ck)
+    for p in range(n):
+        ost, want, m = dec.decode_packet(pk[p], bpf)
+        assert ost == 0 and m == ns[p]
+        assert np.array_equal(got[p, :m * bpf], want), (p, ns[p])
+        assert (got[p, m * bpf:] == 0xA7).all(), ("bytes written behind the packet's frames", p, ns[p])
