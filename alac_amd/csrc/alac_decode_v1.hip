@@ -315,7 +315,8 @@ __global__ __launch_bounds__(64 * kHdrWaves) void k_dec_header(DecV1Args V)
             case 3:    // ID_LFE
             case 1: {  // ID_CPE
                 ech = (tag == 1) ? 2u : 1u;
-                if (ech != A.numChannels) {  // > 2-channel layouts (several elements) are not built yet
+                if (ech != A.numChannels) {  // not the element this pass decodes (> 2 channels: one pass per element of the
+                                             // layout, launch_decode_v1_elements): another sequence, the lane decoder's
                     status = -4;
                     break;
                 }

@@ -977,7 +977,9 @@ __global__ __launch_bounds__(64) void k_gol_count1(V1Args A, uint32_t chanBits)
     GolF g;
     golf_reset(g);
     golf_stream<false>(g, n8, wave_max(n8), chanBits, recip, one_plane(plane, stride, chain));
-    if (active) A.bits1[t] = g.bits;
+    // a packet of fewer than 8 samples has no search residuals: its lane sits out the count like a pad lane and, beside
+    // longer packets, leaves whatever the unchecked blocks coded in g.bits (golf_stream) — the reference counts 0 bits
+    if (active) A.bits1[t] = n8 ? g.bits : 0u;
 }
 
 // ---- k_search1_fused: k_lms_search1 and k_gol_count1 in one launch.  Workgroups [0, nLms) walk the five
@@ -1021,7 +1023,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg, 1) void k_search1_fused(V1Args A,
             golf_reset(g);
             wait.base = r << 16;
             golf_stream<false>(g, n8, nMax, chanBits, recip, one_plane(A.resA + (uint64_t)r * A.chainsPad, stride, chain), wait);
-            if (active) A.bits1[r * A.chainsPad + chain] = g.bits;
+            if (active) A.bits1[r * A.chainsPad + chain] = n8 ? g.bits : 0u;  // (see k_gol_count1)
         }
         return;
     }
@@ -1048,7 +1050,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg, 1) void k_search1_fused(V1Args A,
         wait.base = r << 16;
         wait.ho = A.ho;
         golf_stream<false>(g, n8, wave_max(n8), chanBits, recip, one_plane(plane, stride, chain), wait);
-        if (active) A.bits1[t] = g.bits;
+        if (active) A.bits1[t] = n8 ? g.bits : 0u;  // (see k_gol_count1)
     }
 }
 
@@ -1091,7 +1093,8 @@ __device__ __forceinline__ void count2_body(const V1Args &A, uint32_t chain, uin
             return j < P2 ? b : a;
         }, need);
     }
-    if (active) A.cost2[t] = g.bits * 8 + 16 * na;  // :438, :447 / :899
+    // (n8 = 0, a packet of fewer than 8 samples: no residuals were counted, see k_gol_count1)
+    if (active) A.cost2[t] = (n8 ? g.bits : 0u) * 8 + 16 * na;  // :438, :447 / :899
 }
 
 template <int CH>

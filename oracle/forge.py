@@ -19,6 +19,10 @@ The forger is the ENCODER-side inverse of exactly the decoder's steps, built fro
         -> [mode != 0: pc_block(.., 31)]                            (first difference: inverse of unpc_block(.., 31, ..))
         -> dyn_comp(mb, (pb * pbFactor) / 4, kb)                    (codec/ag_enc.c:249-367)
 
+Packets of 3..8 channels: `element(..., end=False, buf=, pos=)` and `escape_element` (an UNCOMPRESSED element: escape bit,
+the samples at the stream's depth, codec/ALACDecoder.cu:697-727, :856-896) append to one bit buffer, `finish` closes it;
+`forge_batch_mc` walks the element sequence of the channel count and chooses every element on its own.
+
 Losslessness holds whenever u, v fit `chanBits` signed bits (the caller picks amplitudes accordingly); where they do not,
 the decoder's sign extension wraps identically in the oracle and on the GPU, which is what the parity tests compare.
 """
@@ -170,6 +174,35 @@ class Forger:
             return None
         return self.finish(buf, pos)
 
+    def escape_element(self, pcm, n, depth, channels, frame_size, instance=0, lfe=False, force_partial=False, end=True,
+                       buf=None, pos=None):
+        """One UNCOMPRESSED element for `channels` in (1, 2): the header with the escape bit set, numSamples when partial,
+        then the samples interleaved at `depth` bits each — what the decoder's uncompressed branch reads
+        (codec/ALACDecoder.cu:697-727 mono, :856-896 stereo).  Lossless for any sample values.  Returns like element()."""
+        assert channels in (1, 2) and n <= frame_size
+        x = pcm_to_channels(pcm, depth, channels, n)
+        if buf is None:
+            buf = np.zeros(n * channels * 4 + 64, np.uint8)
+            pos = C.c_uint64(0)
+        partial = 1 if (n != frame_size or force_partial) else 0
+        self._put(buf, pos, (3 if lfe else 0) if channels == 1 else 1, 3)
+        self._put(buf, pos, instance, 4)
+        self._put(buf, pos, 0, 12)
+        self._put(buf, pos, (partial << 3) | 1, 4)
+        if partial:
+            self._put(buf, pos, n, 32)
+        for z in range(n):
+            for c in range(channels):
+                v = int(x[c][z]) & ((1 << depth) - 1)
+                if depth > 16:  # the writer takes up to 16 bits at a time where the reader does (:714-721)
+                    self._put(buf, pos, v >> (depth - 16), 16)
+                    self._put(buf, pos, v & ((1 << (depth - 16)) - 1), depth - 16)
+                else:
+                    self._put(buf, pos, v, depth)
+        if not end:
+            return None
+        return self.finish(buf, pos)
+
     def finish(self, buf, pos):
         """ID_END + byte alignment (codec/ALACEncoder.cu:1034-1039)"""
         self._put(buf, pos, 7, 3)
@@ -255,46 +288,70 @@ def test_signal(rng, kind, n, depth, channels, headroom_bits=2):
     return channels_to_pcm(np.stack(cols), depth)
 
 
+def choose_shape(rng, depth, channels, hostile=True):
+    """The header shape of one forged element, drawn before its samples: (signal kind, bytesShifted, lossless, mixBits,
+    mixRes, headroom bits the samples have to leave)."""
+    kind = int(rng.integers(0, 5))
+    shifted = 0
+    if depth >= 24 and rng.random() < 0.6:
+        shifted = int(rng.integers(1, 3)) if depth == 32 else 1
+    if depth == 32 and shifted == 0:
+        shifted = 2 if channels == 2 else int(rng.integers(0, 3))  # stereo chanBits = 33 would not exist
+    ok = True
+    if depth in (16, 20) and hostile and rng.random() < 0.08:
+        shifted = 1  # the decoder parses the shift bytes; its 16-/20-bit output routines ignore them (ALACDecoder.cu:193-280)
+        ok = False
+    mix_bits = int(rng.integers(0, 5))
+    mix_res = int(rng.choice([0, 1, 2, 3, 4, -1, -2, -3, -7, 5, 9, 15, -16])) if channels == 2 else int(rng.integers(-128, 128))
+    if channels == 1 and rng.random() < 0.5:
+        mix_bits = int(rng.integers(0, 256))  # mono: read and ignored (:657-659)
+    # full-scale samples wherever the mix is an interpolation (0 <= mixRes <= 2^mixBits: u lies between L and R), so
+    # that predictor differences reach chanBits + 1 bits; extrapolating weights get the headroom they need
+    headroom = 0 if rng.random() < 0.7 else 2
+    if channels == 2 and (mix_res < 0 or mix_res > (1 << mix_bits)):
+        headroom = 2 + int(np.ceil(np.log2(abs(mix_res) / (1 << mix_bits) + 1)))
+    if depth - 8 * shifted - 1 - headroom < 2:
+        headroom = max(depth - 8 * shifted - 3, 0)
+        ok = ok and (channels == 1 or mix_res == 0 or abs(mix_res) <= (1 << mix_bits))
+    return kind, shifted, ok, mix_bits, mix_res, headroom
+
+
+def choose_params(rng, i, channels, mix_bits, mix_res, hostile=True):
+    """The predictor parameters of forged element number i, drawn after its samples: ([ChannelParams], mixBits, mixRes).
+    Every seventh (i % 7 == 3) is shaped exactly like this library's encoder writes them: 4 or 8 taps, denShift 9,
+    pbFactor 4, mode 0, mixBits 2, mixRes 0..4."""
+    params = [random_params(rng) if (hostile or rng.random() < 0.8) else ChannelParams(8, 9, 4, 0, default_coefs(8, 9))
+              for _ in range(channels)]
+    if i % 7 == 3:  # next to the foreign ones
+        params = [ChannelParams(int(rng.choice([4, 8])), 9, 4, 0) for _ in range(channels)]
+        for cp in params:
+            cp.coefs[:] = default_coefs(cp.num, 9)
+        if channels == 2:
+            mix_bits, mix_res = 2, int(rng.integers(0, 5))
+    return params, mix_bits, mix_res
+
+
+def batch_sizes(frame_size):
+    """the sample counts forge_batch deals out: full frames, one sample, odd counts, counts below 16"""
+    return [frame_size, frame_size, frame_size // 2 + 3, 1, 2, 5, 17, 33, frame_size - 1, 100 % (frame_size + 1) or 1]
+
+
+def batch_size(sizes, i, frame_size):
+    n = int(sizes[i % len(sizes)]) if i % 4 else frame_size
+    return max(1, min(n, frame_size))
+
+
 def forge_batch(forger, rng, count, depth, channels, frame_size, pb=40, mb=10, kb=14, hostile=True):
     """`count` forged packets of one stream format (one cookie).  Returns (packets, pcm, lossless): packets[i] bytes,
     pcm[i] the packed source PCM of its n_i sample-frames, lossless[i] True where decode(packet) must equal pcm[i]
     (samples with headroom, a shift path the depth's output routine has, mixBits small enough for the headroom)."""
     packets, pcms, lossless = [], [], Flags()
-    sizes = [frame_size, frame_size, frame_size // 2 + 3, 1, 2, 5, 17, 33, frame_size - 1, 100 % (frame_size + 1) or 1]
+    sizes = batch_sizes(frame_size)
     for i in range(count):
-        n = int(sizes[i % len(sizes)]) if i % 4 else frame_size
-        n = max(1, min(n, frame_size))
-        kind = int(rng.integers(0, 5))
-        shifted = 0
-        if depth >= 24 and rng.random() < 0.6:
-            shifted = int(rng.integers(1, 3)) if depth == 32 else 1
-        if depth == 32 and shifted == 0:
-            shifted = 2 if channels == 2 else int(rng.integers(0, 3))  # stereo chanBits = 33 would not exist
-        ok = True
-        if depth in (16, 20) and hostile and rng.random() < 0.08:
-            shifted = 1  # the decoder parses the shift bytes; its 16-/20-bit output routines ignore them (ALACDecoder.cu:193-280)
-            ok = False
-        mix_bits = int(rng.integers(0, 5))
-        mix_res = int(rng.choice([0, 1, 2, 3, 4, -1, -2, -3, -7, 5, 9, 15, -16])) if channels == 2 else int(rng.integers(-128, 128))
-        if channels == 1 and rng.random() < 0.5:
-            mix_bits = int(rng.integers(0, 256))  # mono: read and ignored (:657-659)
-        # full-scale samples wherever the mix is an interpolation (0 <= mixRes <= 2^mixBits: u lies between L and R), so
-        # that predictor differences reach chanBits + 1 bits; extrapolating weights get the headroom they need
-        headroom = 0 if rng.random() < 0.7 else 2
-        if channels == 2 and (mix_res < 0 or mix_res > (1 << mix_bits)):
-            headroom = 2 + int(np.ceil(np.log2(abs(mix_res) / (1 << mix_bits) + 1)))
-        if depth - 8 * shifted - 1 - headroom < 2:
-            headroom = max(depth - 8 * shifted - 3, 0)
-            ok = ok and (channels == 1 or mix_res == 0 or abs(mix_res) <= (1 << mix_bits))
+        n = batch_size(sizes, i, frame_size)
+        kind, shifted, ok, mix_bits, mix_res, headroom = choose_shape(rng, depth, channels, hostile)
         pcm = test_signal(rng, kind, n, depth, channels, headroom_bits=headroom)
-        params = [random_params(rng) if (hostile or rng.random() < 0.8) else ChannelParams(8, 9, 4, 0, default_coefs(8, 9))
-                  for _ in range(channels)]
-        if i % 7 == 3:  # a packet exactly like this library's encoder writes them, next to the foreign ones
-            params = [ChannelParams(int(rng.choice([4, 8])), 9, 4, 0) for _ in range(channels)]
-            for cp in params:
-                cp.coefs[:] = default_coefs(cp.num, 9)
-            if channels == 2:
-                mix_bits, mix_res = 2, int(rng.integers(0, 5))
+        params, mix_bits, mix_res = choose_params(rng, i, channels, mix_bits, mix_res, hostile)
         pk = forger.element(pcm, n, depth, channels, frame_size, params, mix_bits=mix_bits if channels == 2 else mix_bits & 0xff,
                             mix_res=mix_res, bytes_shifted=shifted, instance=int(rng.integers(0, 16)), pb=pb, mb=mb, kb=kb,
                             lfe=(channels == 1 and rng.random() < 0.2), force_partial=bool(rng.random() < 0.1))
@@ -303,6 +360,69 @@ def forge_batch(forger, rng, count, depth, channels, frame_size, pb=40, mb=10, k
         lossless.append(ok)
         lossless.info.append(dict(n=n, shifted=shifted, mix=(mix_bits, mix_res), lfe=pk[0] >> 5 == 3,
                                   chans=[(cp.num, cp.den_shift, cp.pb_factor, cp.mode) for cp in params]))
+    return packets, pcms, lossless
+
+
+def element_sequence(oracle, channels):
+    """[(channels of the element, is ID_LFE)] in packet order for a stream of `channels`, from sChannelMaps
+    (codec/ALACEncoder.cu:97-107)"""
+    m, out, ci = oracle.lib.oalac_channel_map(channels), [], 0
+    while ci < channels:
+        tag = (m >> (3 * ci)) & 7
+        out.append((2 if tag == 1 else 1, tag == 3))
+        ci += out[-1][0]
+    return out
+
+
+def forge_batch_mc(forger, rng, count, depth, channels, frame_size, pb=40, mb=10, kb=14, sequence=None):
+    """`count` forged packets of one 3..8-channel stream format, every packet a sequence of elements in ONE bit buffer:
+    sChannelMaps' sequence for `channels`, or `sequence` (channels per element, e.g. [1, 1, 1]).  Every element is chosen
+    on its own, as forge_batch chooses a packet: foreign header parameters (every seventh element own-shaped), about one in
+    five UNCOMPRESSED (escape_element), about one in ten silent.  All elements of a packet carry the same n.  Returns
+    (packets, pcm, lossless): pcm[i] the interleaved source of all channels, lossless[i] True only where every element of
+    packet i is lossless; lossless.info[i] is a list of per-element dicts (escape, n, shifted, mix, chans)."""
+    seq = [(e, False) if isinstance(e, (int, np.integer)) else tuple(e) for e in (sequence or element_sequence(forger.o, channels))]
+    assert sum(e for e, _ in seq) == channels
+    bps = BPS[depth]
+    packets, pcms, lossless = [], [], Flags()
+    sizes = batch_sizes(frame_size)
+    serial = 0  # elements forged so far: the own-shaped ones land at every position of the sequence
+    for i in range(count):
+        n = batch_size(sizes, i, frame_size)
+        # the source frame: every element's channels drawn with the headroom its shape needs, interleaved
+        shapes, cols = [], []
+        for ech, _ in seq:
+            escape, silent = bool(rng.random() < 0.2), bool(rng.random() < 0.1)
+            shape = choose_shape(rng, depth, ech)
+            kind, headroom = shape[0], (0 if escape else shape[5])
+            part = np.zeros(n * ech * bps, np.uint8) if silent else test_signal(rng, kind, n, depth, ech, headroom_bits=headroom)
+            shapes.append((escape,) + shape)
+            cols.append(part.reshape(n, ech * bps))
+        frame = np.concatenate(cols, axis=1)
+        buf = np.zeros(n * channels * 8 + 4096 * len(seq), np.uint8)
+        pos = C.c_uint64(0)
+        first, all_ok, info = 0, True, []
+        for (ech, lfe), (escape, kind, shifted, ok, mix_bits, mix_res, headroom) in zip(seq, shapes):
+            src = np.ascontiguousarray(frame[:, first * bps:(first + ech) * bps]).reshape(-1)
+            first += ech
+            instance, partial = int(rng.integers(0, 16)), bool(rng.random() < 0.1)
+            if escape:
+                forger.escape_element(src, n, depth, ech, frame_size, instance=instance, lfe=lfe, force_partial=partial,
+                                      end=False, buf=buf, pos=pos)
+                info.append(dict(escape=True, n=n, shifted=0, mix=(0, 0), chans=[]))
+                continue
+            params, mix_bits, mix_res = choose_params(rng, serial, ech, mix_bits, mix_res)
+            serial += 1
+            forger.element(src, n, depth, ech, frame_size, params, mix_bits=mix_bits & 0xff, mix_res=mix_res,
+                           bytes_shifted=shifted, instance=instance, pb=pb, mb=mb, kb=kb, lfe=lfe, force_partial=partial,
+                           end=False, buf=buf, pos=pos)
+            all_ok = all_ok and ok
+            info.append(dict(escape=False, n=n, shifted=shifted, mix=(mix_bits, mix_res),
+                             chans=[(cp.num, cp.den_shift, cp.pb_factor, cp.mode) for cp in params]))
+        packets.append(forger.finish(buf, pos))
+        pcms.append(frame.reshape(-1))
+        lossless.append(all_ok)
+        lossless.info.append(info)
     return packets, pcms, lossless
 
 

@@ -15,6 +15,8 @@ Outputs (data only — inputs and expected outputs, no reference source):
   forged.npz          packets with FOREIGN header / cookie parameters (oracle/forge.py run over the reference's compiled
                       pc_block / dyn_comp / BitBufferWrite) and the PCM the decoder driver produces from them over the
                       reference's dyn_decomp / unpc_block: the pin of the decoder's general paths
+  forged_mc.npz       the same for packets of 3..8 channels: several elements per packet (oracle/forge.py forge_batch_mc), foreign,
+                      uncompressed and silent ones side by side; reproducible byte for byte like long_runs.npz
   caf_headers.json    chunk bytes, BER codes and base packet tables from the reference's own CAFFileALAC.cpp
   wav50_pcm.xz,       the sample data of the reference's audio/50.wav (stereo, 237 packets), audio/05.wav (mono, 302
   wav05_pcm.xz,       packets) and audio/70.wav (stereo, near silence, 227 packets), xz-compressed: the INPUTS of the
@@ -176,6 +178,41 @@ def make_forged(o, r):
     print("forged.npz:", sum(m["packets"] for m in meta), "packets,", os.path.getsize(os.path.join(HERE, "forged.npz")), "bytes")
 
 
+FORGED_MC_STREAMS = [  # (depth, channels, frame size, cookie pb, mb, kb, packets): several elements per packet
+    (16, 3, 128, 40, 10, 14, 16), (16, 6, 128, 20, 5, 9, 16), (24, 6, 96, 40, 10, 14, 12), (20, 5, 96, 50, 8, 13, 12),
+    (32, 8, 64, 40, 10, 14, 8),
+]
+
+
+def make_forged_mc(o, r):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle"))
+    import forge
+    fr = forge.Forger(o, dict(pc_block=r.lib.pc_block, dyn_comp=r.lib.ref_dyn_comp_flat, put_bits=r.lib.ref_put_bits))
+    out, meta = {}, []
+    for si, (depth, ch, frame, pb, mb, kb, count) in enumerate(FORGED_MC_STREAMS):
+        rng = np.random.default_rng(5000 + si)
+        pk, pcm, ok = forge.forge_batch_mc(fr, rng, count, depth, ch, frame, pb, mb, kb)
+        ck = forge.cookie(frame, depth, ch, pb, mb, kb)
+        dec = o.decoder(ck, hooks=r.hooks())
+        bpf = ch * forge.BPS[depth]
+        want = []
+        for a, p, k in zip(pk, pcm, ok):
+            st, w, n = dec.decode_packet(a, bpf)
+            assert st == 0 and n * bpf == len(p)
+            assert (not k) or np.array_equal(w, p)
+            want.append(w)
+        out[f"s{si}_stream"] = np.concatenate(pk)
+        out[f"s{si}_sizes"] = np.array([len(a) for a in pk], np.uint32)
+        out[f"s{si}_pcm"] = np.concatenate(want)
+        out[f"s{si}_cookie"] = ck
+        meta.append(dict(id=si, depth=depth, channels=ch, frame=frame, pb=pb, mb=mb, kb=kb, packets=count,
+                         lossless=[bool(k) for k in ok], elements=ok.info))
+    out["meta"] = np.frombuffer(json.dumps(meta).encode(), np.uint8)
+    path = os.path.join(HERE, "forged_mc.npz")
+    save_npz_reproducible(path, out)
+    print("forged_mc.npz:", sum(m["packets"] for m in meta), "packets,", os.path.getsize(path), "bytes")
+
+
 def make_wav_pcm_fixtures():
     import lzma
     headers = {}
@@ -282,6 +319,7 @@ if __name__ == "__main__":
     o, r = Oracle(), Ref()
     makers = dict(stage_vectors=lambda: make_stage_vectors(o, r), packets=lambda: make_packets(o, r),
                   known_answers=lambda: make_known_answers(o, r), forged=lambda: make_forged(o, r),
+                  forged_mc=lambda: make_forged_mc(o, r),
                   wav_pcm=make_wav_pcm_fixtures, caf_headers=make_caf_headers, long_runs=lambda: make_long_runs(o, r))
     for name in sys.argv[1:] or list(makers):
         makers[name]()

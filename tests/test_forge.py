@@ -15,14 +15,18 @@ import forge  # noqa: E402
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def load_forged():
-    z = np.load(os.path.join(GOLD, "forged.npz"))
+def load_forged(name="forged.npz"):
+    z = np.load(os.path.join(GOLD, name))
     return z, json.loads(bytes(z["meta"]).decode())
 
 
 def test_forged_golden_decodes_to_reference_pcm(oracle):
     z, meta = load_forged()
     assert sum(m["packets"] for m in meta) >= 150
+    decode_golden(oracle, z, meta)
+
+
+def decode_golden(oracle, z, meta):
     for m in meta:
         si = m["id"]
         dec = oracle.decoder(z[f"s{si}_cookie"])
@@ -47,6 +51,60 @@ def test_forger_is_reproducible_against_golden(oracle):
         pk, pcm, ok = forge.forge_batch(f, np.random.default_rng(4000 + si), count, depth, ch, frame, pb, mb, kb)
         assert np.array_equal(np.concatenate(pk), z[f"s{si}_stream"]), si
         assert ok == meta[si]["lossless"]
+
+
+def test_forged_mc_golden_decodes_to_reference_pcm(oracle):
+    """forged_mc.npz: packets of 3..8 channels, several foreign / uncompressed / silent elements each"""
+    z, meta = load_forged("forged_mc.npz")
+    assert [m["channels"] for m in meta] == [3, 6, 6, 5, 8] and sum(m["packets"] for m in meta) >= 40
+    decode_golden(oracle, z, meta)
+
+
+def test_forger_mc_is_reproducible_against_golden(oracle):
+    from golden.make_golden import FORGED_MC_STREAMS
+    z, meta = load_forged("forged_mc.npz")
+    f = forge.Forger(oracle)
+    for si, (depth, ch, frame, pb, mb, kb, count) in enumerate(FORGED_MC_STREAMS):
+        pk, pcm, ok = forge.forge_batch_mc(f, np.random.default_rng(5000 + si), count, depth, ch, frame, pb, mb, kb)
+        assert np.array_equal(np.concatenate(pk), z[f"s{si}_stream"]), si
+        assert ok == meta[si]["lossless"]
+
+
+@pytest.mark.parametrize("channels,depth", [(3, 16), (6, 24), (8, 16), (5, 20), (7, 32)])
+def test_forged_multi_element_packets_decode_in_the_oracle(oracle, channels, depth):
+    """escape_element / forge_batch_mc against the oracle decoder's element loop: status, sample count, and the source
+    wherever every element of the packet is lossless"""
+    frame, bpf = 200, channels * forge.BPS[depth]
+    pk, pcm, ok = forge.forge_batch_mc(forge.Forger(oracle), np.random.default_rng(depth * 100 + channels), 30, depth, channels, frame)
+    dec = oracle.decoder(forge.cookie(frame, depth, channels))
+    for a, p, k, info in zip(pk, pcm, ok, ok.info):
+        st, out, n = dec.decode_packet(a, bpf)
+        assert st == 0 and n == info[0]["n"] == len(p) // bpf, info
+        if k:
+            assert np.array_equal(out, p), info
+    assert sum(ok) >= len(ok) // 2
+    assert any(e["escape"] for info in ok.info for e in info) and any(not e["escape"] for info in ok.info for e in info)
+
+
+@pytest.mark.parametrize("channels,depth", [(3, 16), (6, 24), (8, 16), (5, 20), (7, 32)])
+def test_forged_multi_element_packets_live_against_reference_objects(oracle, ref, channels, depth):
+    fr = forge.Forger(oracle, dict(pc_block=ref.lib.pc_block, dyn_comp=ref.lib.ref_dyn_comp_flat, put_bits=ref.lib.ref_put_bits))
+    fo = forge.Forger(oracle)
+    frame, bpf = 200, channels * forge.BPS[depth]
+    for pb, mb, kb in ((40, 10, 14), (17, 3, 7), (255, 255, 16)):
+        seed = depth * 1000 + channels * 100 + pb
+        pk, pcm, ok = forge.forge_batch_mc(fo, np.random.default_rng(seed), 20, depth, channels, frame, pb, mb, kb)
+        pk2, _, _ = forge.forge_batch_mc(fr, np.random.default_rng(seed), 20, depth, channels, frame, pb, mb, kb)
+        ck = forge.cookie(frame, depth, channels, pb, mb, kb)
+        d_own, d_ref = oracle.decoder(ck), oracle.decoder(ck, hooks=ref.hooks())
+        for a, b, p, k in zip(pk, pk2, pcm, ok):
+            assert np.array_equal(a, b)
+            st, out, n = d_own.decode_packet(a, bpf)
+            st2, out2, n2 = d_ref.decode_packet(a, bpf)
+            assert st == st2 == 0 and n == n2 == len(p) // bpf
+            assert np.array_equal(out, out2)
+            if k:
+                assert np.array_equal(out, p)
 
 
 @pytest.mark.parametrize("depth,channels", [(16, 2), (16, 1), (24, 2), (24, 1), (20, 2), (32, 2), (32, 1)])

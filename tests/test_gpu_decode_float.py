@@ -146,8 +146,9 @@ def test_chained_reference_audio(gpu_ctx, name):
     assert_float_equals_decode(gpu_ctx, c, name)
 
 
-def test_forged_foreign_packets(gpu_ctx):
-    z = np.load(os.path.join(GOLD, "forged.npz"))
+@pytest.mark.parametrize("fixture", ["forged.npz", "forged_mc.npz"])
+def test_forged_foreign_packets(gpu_ctx, fixture):
+    z = np.load(os.path.join(GOLD, fixture))
     meta = json.loads(bytes(z["meta"]).decode())
     for m in meta:
         si = m["id"]

@@ -47,6 +47,40 @@ def test_partial_packets_match_oracle(gpu_ctx, oracle, depth, channels):
     assert off == len(stream)
 
 
+@pytest.mark.parametrize("depth,channels", [(16, 2), (20, 1), (20, 2), (24, 2)])
+def test_packets_below_eight_samples_that_stay_compressed(gpu_ctx, oracle, depth, channels):
+    """A quiet packet of 5..7 samples between full ones.  Its search passes run over N / 8 = 0 samples, so the reference's
+    estimate is the header alone and the packet stays compressed (most packets that short are escaped whatever the estimate
+    says, which is why test_partial_packets_match_oracle never saw this).  The count lane of such a packet sits in a wave
+    with lanes that have residuals; what it counts there must not reach the decision.  Every call follows an encode of
+    full-scale noise of the same shape, so that anything left behind in the workspace is as loud as it gets."""
+    import torch
+    frame, n = 512, 16
+    fmt = alac_amd.make_format(frame, depth, channels)
+    pcm = alac_amd.synth_pcm(20, n, fmt)  # packet 2: sparse impulses on silence
+    noise = np.random.default_rng(depth + channels).integers(0, 256, n * fmt.packet_bytes, dtype=np.uint8)
+    if depth == 20:
+        noise[0::3] &= 0xF0
+    enc = oracle.encoder(frame, depth, channels)
+    compressed = 0
+    for short in (5, 6, 7):
+        sizes_in = [frame] * n
+        sizes_in[2] = short
+        gpu_ctx.encode_to_host(fmt, torch.from_numpy(noise).cuda(), n)
+        ns = torch.tensor(sizes_in, dtype=torch.int32).cuda()
+        stream, sizes = gpu_ctx.encode_to_host(fmt, torch.from_numpy(pcm).cuda(), n, num_samples=ns)
+        off = 0
+        for p, N in enumerate(sizes_in):
+            enc.reset()
+            pk = enc.encode_packet(pcm[p * fmt.packet_bytes:p * fmt.packet_bytes + N * fmt.bytes_per_frame], N)
+            compressed += p == 2 and not enc.last_info()["escape"]
+            assert sizes[p] == len(pk), (short, p, N)
+            assert np.array_equal(stream[off:off + len(pk)], pk), (short, p, N)
+            off += len(pk)
+        assert off == len(stream)
+    assert compressed >= 1  # on the CPU: the case is there
+
+
 @pytest.mark.parametrize("depth,channels", [(16, 2), (24, 2), (16, 1)])
 def test_chained_segments_and_state(gpu_ctx, oracle, depth, channels):
     """segments of different lengths chained through the coefficient state; state out == oracle state;

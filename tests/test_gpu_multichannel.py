@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 import alac_amd
-from oracle_lib import channel_elements, interleave_channels
+from oracle_lib import channel_elements, interleave_channels, take_channels
 
 pytestmark = pytest.mark.gpu
 
@@ -37,6 +37,63 @@ def test_independent_packets_and_round_trip(gpu_ctx, oracle, channels, depth):
     assert off == len(stream)
     cookie = gpu_ctx.magic_cookie(fmt)
     assert np.array_equal(cookie, oracle.encoder(4096, depth, channels).cookie())  # fetched before encoding
+    offs = np.concatenate([[0], np.cumsum(sizes.astype(np.int64))])
+    out, nso, st, f2 = gpu_ctx.decode(cookie, torch.from_numpy(stream).cuda(), torch.from_numpy(offs).cuda(), n)
+    gpu_ctx.synchronize()
+    assert f2.num_channels == channels and not st.cpu().numpy().any()
+    assert np.array_equal(nso.cpu().numpy(), np.array(sizes_in))
+    out = out.cpu().numpy()
+    for p, N in enumerate(sizes_in):
+        a = p * fmt.packet_bytes
+        assert np.array_equal(out[a:a + N * fmt.bytes_per_frame], pcm[a:a + N * fmt.bytes_per_frame]), p
+
+
+@pytest.mark.parametrize("channels,depth", [(3, 16), (6, 16), (6, 24), (5, 20), (8, 32)])
+def test_elements_of_different_signal_classes(gpu_ctx, oracle, channels, depth):
+    """_pcm gives every element of a packet the same synth class (16 * k is 0 mod 8).  Here element k starts 19 * k + 1
+    frames on, so one packet holds an escaped element next to a coded one, a silent one next to a coded one, ...: the
+    encoder splices an uncompressed payload and a Golomb payload at bit granularity (k_mc_sizes / k_mc_splice), the
+    decoder's element rounds hand the position on from either kind."""
+    import os
+    import sys
+    import torch
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+    import forge
+    frame, n = 512, 16
+    fmt = alac_amd.make_format(frame, depth, channels)
+    sizes_in = [frame] * n
+    sizes_in[2], sizes_in[9], sizes_in[15] = 5, 200, 511
+    elements = channel_elements(oracle, channels)
+    pcm = interleave_channels([(alac_amd.synth_pcm(16 * k + 3 * k + 1, n, alac_amd.make_format(frame, depth, ech)), ech)
+                               for k, (ci, ech) in enumerate(elements)], depth)
+    # on the CPU: what the packets hold, from the oracle's encode of every element alone
+    mixed = silent_beside_coded = 0
+    bps = fmt.bytes_per_frame // channels
+    for p, N in enumerate(sizes_in):
+        src = pcm[p * fmt.packet_bytes:p * fmt.packet_bytes + N * fmt.bytes_per_frame]
+        esc, silent = [], []
+        for ci, ech in elements:
+            part = take_channels(src, channels, ci, ech, depth)
+            e = oracle.encoder(frame, depth, ech)
+            esc.append(forge.parse_header(e.encode_packet(part, N), ech)[0])
+            silent.append(not part.any())
+        mixed += any(esc) and not all(esc)
+        silent_beside_coded += any(silent) and any(not a and not b for a, b in zip(esc, silent))
+    assert mixed >= 4 and silent_beside_coded >= 1, (mixed, silent_beside_coded)
+
+    ns = torch.tensor(sizes_in, dtype=torch.int32).cuda()
+    stream, sizes = gpu_ctx.encode_to_host(fmt, torch.from_numpy(pcm).cuda(), n, num_samples=ns)
+    enc = oracle.encoder(frame, depth, channels)
+    off = 0
+    for p, N in enumerate(sizes_in):
+        enc.reset()
+        pk = enc.encode_packet(pcm[p * fmt.packet_bytes:p * fmt.packet_bytes + N * fmt.bytes_per_frame], N)
+        assert sizes[p] == len(pk), (p, N)
+        assert np.array_equal(stream[off:off + len(pk)], pk), (p, N)
+        off += len(pk)
+    assert off == len(stream)
+    cookie = gpu_ctx.magic_cookie(fmt)
+    assert np.array_equal(cookie, oracle.encoder(frame, depth, channels).cookie())
     offs = np.concatenate([[0], np.cumsum(sizes.astype(np.int64))])
     out, nso, st, f2 = gpu_ctx.decode(cookie, torch.from_numpy(stream).cuda(), torch.from_numpy(offs).cuda(), n)
     gpu_ctx.synchronize()

@@ -12,7 +12,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILES = ["tests/test_gpu_encode.py", "tests/test_gpu_decode.py", "tests/test_gpu_foreign.py", "tests/test_gpu_fuzz.py",
-         "tests/test_gpu_multichannel.py", "tests/test_gpu_wholefile.py", "tests/test_gpu_chained.py"]
+         "tests/test_gpu_multichannel.py", "tests/test_gpu_foreign_multichannel.py", "tests/test_gpu_wholefile.py",
+         "tests/test_gpu_chained.py"]
 
 VARIANTS = {
     "first-generation": {"encoder_lane": 1, "decoder_lane": 1},

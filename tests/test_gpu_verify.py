@@ -171,10 +171,12 @@ def test_clean_escaped_and_wrapping_packets(gpu_ctx, kind):
     assert_clean(gpu_ctx, c, kind)
 
 
-def test_clean_forged_foreign_packets(gpu_ctx):
-    """the committed foreign packets against the reference objects' own PCM (tests/golden/forged.npz)"""
+@pytest.mark.parametrize("fixture", ["forged.npz", "forged_mc.npz"])
+def test_clean_forged_foreign_packets(gpu_ctx, fixture):
+    """the committed foreign packets against the reference objects' own PCM (tests/golden/forged.npz; forged_mc.npz:
+    several elements per packet of 3..8 channels, so the store sites write behind outFirst > 0)"""
     import torch
-    z = np.load(os.path.join(GOLD, "forged.npz"))
+    z = np.load(os.path.join(GOLD, fixture))
     meta = json.loads(bytes(z["meta"]).decode())
     for m in meta:
         si = m["id"]

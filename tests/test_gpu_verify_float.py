@@ -286,8 +286,9 @@ def test_wrong_key_equals_host(gpu_ctx, depth, channels):
 
 # ---- 5: other streams -------------------------------------------------------------------------------------------------------
 
-def test_forged_foreign_packets_equal_host(gpu_ctx):
-    z = np.load(os.path.join(GOLD, "forged.npz"))
+@pytest.mark.parametrize("fixture", ["forged.npz", "forged_mc.npz"])
+def test_forged_foreign_packets_equal_host(gpu_ctx, fixture):
+    z = np.load(os.path.join(GOLD, fixture))
     meta = json.loads(bytes(z["meta"]).decode())
     for m in meta:
         si = m["id"]
