@@ -62,6 +62,7 @@ const AlacOptionKey *alac_option_keys(uint32_t *count)
         {"overlap_pos", "ALAC_HIP_OVERLAP_POS", &AlacOptions::overlapPos, 0, 1},
         {"fused", "ALAC_HIP_FUSED", &AlacOptions::fused, 0, 1},
         {"fold", "ALAC_HIP_FOLD", &AlacOptions::fold, 0, 1},
+        {"pub_every", "ALAC_HIP_PUB_EVERY", &AlacOptions::pubEvery, 1, 8, true},
         {"fast_mode", nullptr, &AlacOptions::fastMode, 0, 1},
         {"encoder_lane", "ALAC_HIP_ENCODER", &AlacOptions::laneEncoder, 0, 1},
         {"decoder_lane", "ALAC_HIP_DECODER", &AlacOptions::laneDecoder, 0, 1},
@@ -91,9 +92,14 @@ AlacOptions alac_options_from_env()
         if (lane && strcmp(v, "lane") == 0) v = "1";
         char *end = nullptr;
         const long x = strtol(v, &end, 10);
-        if (*end == '\0' && x >= t[i].lo && x <= t[i].hi) o.*(t[i].slot) = (int32_t)x;
+        if (*end == '\0' && alac_option_accepts(t[i], x)) o.*(t[i].slot) = (int32_t)x;
     }
     return o;
+}
+
+bool alac_option_accepts(const AlacOptionKey &k, long v)
+{
+    return v >= k.lo && v <= k.hi && (!k.pow2 || (v & (v - 1)) == 0);
 }
 
 const AlacOptionKey *alac_option_find(const char *key)
@@ -198,7 +204,7 @@ struct EncLayout {
     uint64_t recs, bitWords, pred, total;
     uint32_t wcap;
     uint64_t predStride;
-    // tap-parallel pipeline: residual planes [sample][stream], decision scratch, working state
+    // tap-parallel pipeline: residual planes [sample / 4][stream][4] (alac_plane_index.hpp), decision scratch, working state
     uint64_t resA, resB, resC, bits1, cost2, state, flags, rowReady, cls, colChain;
     uint64_t bitWordsB, bitsB;  // tiny batches only (0: absent): second coder wave of the split final coder
     uint64_t segBad;            // one word: k_check_segments refused the caller's segment table (EncodeArgs::segBad)
@@ -231,8 +237,9 @@ EncLayout enc_layout(const alac_hip_format *f, uint32_t numPackets, uint32_t num
     L.pred = off;
     off = align_up(off + (uint64_t)(f->frame_size / 8 + 1) * lanes * 4, 256);
     L.chainsPad = (uint32_t)lanes;
-    // +16 rows: the coder waves read whole 16-row blocks up to the wave's longest chain
-    const uint64_t n8 = f->frame_size / 8 + 1 + 16;
+    // whole cells of four rows (plane_rows: at most three rows more per plane), +16 rows: the coder waves read whole 16-row
+    // blocks up to the wave's longest chain
+    const uint64_t n8 = plane_rows(f->frame_size / 8 + 1) + 16;
     L.resA = off;
     off = align_up(off + (f->num_channels == 2 ? n8 * 5 * lanes * 4 : 0), 256);
     L.resB = off;
@@ -240,7 +247,7 @@ EncLayout enc_layout(const alac_hip_format *f, uint32_t numPackets, uint32_t num
     // final residuals: columns handed out per packet class (k_class_assign), two regions padded to 64 -> up to 128 spare
     L.colsPad = (uint32_t)lanes + 256;  // the two class regions of the final pass are padded to whole waves
     L.resC = off;
-    off = align_up(off + ((uint64_t)f->frame_size + 16) * L.colsPad * 4, 256);
+    off = align_up(off + (plane_rows(f->frame_size) + 16) * L.colsPad * 4, 256);
     L.bits1 = off;
     off = align_up(off + 5 * lanes * 4, 256);
     L.cost2 = off;
@@ -488,7 +495,7 @@ int32_t alac_hip_set_option(alac_hip_ctx *ctx, const char *key, int32_t value)
     if (!ctx) return ALAC_HIP_ParamError;
     const AlacOptionKey *k = alac_option_find(key);
     if (!k) return fail(ctx, ALAC_HIP_ParamError, "unknown option");
-    if (value < k->lo || value > k->hi) return fail(ctx, ALAC_HIP_ParamError, "option value outside its documented range");
+    if (!alac_option_accepts(*k, value)) return fail(ctx, ALAC_HIP_ParamError, "option value outside its documented range");
     ctx->opt.*(k->slot) = value;
     return ALAC_HIP_noErr;
 }
@@ -661,7 +668,9 @@ static V1Args v1_args(const alac_hip_ctx *ctx, const EncodeArgs &ea, const EncLa
     // in fast mode, where no search launch takes them as constants
     A.virgin = stateInternal && !P.fast ? 1u : 0u;
     A.foldDecide = P.shape == V1Shape::Latency ? 1u : 0u;
-    // pubMask 0: producers publish after every tile, rows written through (a release fence per publish cost ~11 us)
+    // producers publish after every pub_every tiles (1, 2, 4 or 8), rows written through: bit 31, a release fence per publish,
+    // stays clear (it cost ~11 us each)
+    A.pubMask = (uint32_t)ctx->opt.pubEvery - 1u;
     A.idleFast = P.shape == V1Shape::Throughput ? 0u : 1u;
     A.ho = handoff_ctl(ctx);
     A.cls = (ClassInfo *)(ws + L.cls);

@@ -14,8 +14,8 @@
 // then once: k_finalize (sizes + the "too big -> escape" rule), k_scan_sizes, k_pack (alac_encode.hip).
 //
 // The LPC+mix kernels are the tap-parallel form of alac_lms.hpp: one wave = 8 chains x 8 taps,
-// inputs staged in LDS tile by tile, residual tiles flushed to HBM in [sample][stream] order so that
-// the lane-per-stream Golomb kernels read them coalesced.
+// inputs staged in LDS tile by tile, residual tiles flushed to HBM in [sample / 4][stream][4] order (alac_plane_index.hpp) so
+// that the lane-per-stream Golomb kernels read them coalesced, 16 bytes per lane.
 //
 // Reference control flow: codec/ALACEncoder.cu:290-558 (EncodeStereo), :812-963 (EncodeMono).
 #pragma once
@@ -108,11 +108,11 @@ __device__ __forceinline__ Worker worker_id()
 __device__ __forceinline__ void lds_order() { asm volatile("" ::: "memory"); }
 
 // ---- producer -> consumer hand-off inside one launch (cdna_hip_programming.md Guideline 16) ----
-// The residual rows are stored with agent-scope atomic stores (global_store ... sc1: written through the
-// XCD's L2), so once `s_waitcnt vmcnt(0)` has seen them complete there is nothing left in this L2 for a
+// The residual rows are stored written through the XCD's L2 (global_store_dwordx4 ... sc1, what an agent-scope
+// atomic store compiles to; lms_pass, put4), so once `s_waitcnt vmcnt(0)` has seen them complete there is nothing left in this L2 for a
 // release to write back, and the flag can follow directly.  Measured: an agent-scope release fence here
 // (buffer_wbl2 of the WHOLE L2, which also holds the coder waves' dirty bit words) costs ~11 us per
-// publish; ALAC_HIP_PUBFENCE=1 puts it back (and publishes every 4 tiles instead of every tile).
+// publish; bit 31 of V1Args::pubMask puts it back (no option sets it).
 __device__ __forceinline__ void publish_rows(uint32_t *flag, uint32_t rows, int lane, bool fence, uint32_t lose = 0)
 {
     if (lose) return;  // ALAC_HIP_DEBUG_LOSE_HANDOFF: the consumers must notice
@@ -515,7 +515,7 @@ struct ChainJob {
 };
 
 // A pass = one pc_block call over every chain of the wave: `num` samples adapt the row, residual positions
-// j < P go to dst[j * streamStride + stream] when store is set.
+// j < P go to dst[plane_index(j, streamStride, stream)] when store is set.
 // ZZ: residuals leave as their zig-zag image 2|del| - (del < 0) (what the final entropy coder starts from)
 // Sink: where the residual tile goes.  NoSink = the HBM plane `dst` (the flush below); any other type is a functor
 // sink(j0, row) called once per tile with the lane's own LDS row (row[i] = residual of position j0 + i, i < TILE; only
@@ -614,37 +614,54 @@ __device__ __forceinline__ void lms_pass(LmsShared<LPC> &sh, const V1Args &A, co
                     sh.xs[fs * Geo<LPC>::STRIDE + pos] = sh.xs[fs * Geo<LPC>::STRIDE + Geo<LPC>::ROWLEN + pos];
                 lds_order();
             }
-            // residual tile -> HBM, [sample][stream]: consecutive lanes = consecutive streams.  WT (fused launches):
-            // agent-scope stores, written through so that publish_rows has nothing to write back.
-            auto put = [&](int32_t *q, int32_t v) {
-                if constexpr (ZZ) v = (int32_t)(((uint32_t)v << 1) ^ (uint32_t)(v >> 31));
-                if constexpr (WT) __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else *q = v;
+            // residual tile -> HBM, [sample / 4][stream][4] (alac_plane_index.hpp): a lane stores whole cells, four consecutive
+            // residuals of one chain in one 16-byte store; consecutive lanes = consecutive streams = consecutive cells.  WT (fused
+            // launches): the store is written through (sc1, what an agent-scope atomic store of a dword compiles to — the
+            // atomic builtins do not reach 16 bytes) so that publish_rows has nothing to write back; the s_nop covers the
+            // wait states a store of more than 8 bytes needs before its data registers may be written again, which the
+            // compiler cannot see inside the asm.
+            // A cell whose first row is below the lane's P is stored whole: its cells past P are never read (the readers ignore
+            // rows at or beyond the lane's own length) and the planes hold whole cells (plane_rows).
+            using Cell = int32_t __attribute__((ext_vector_type(4)));
+            auto put4 = [&](const char *rowBase, uint32_t off, const int32_t *v) {
+                auto zz = [](int32_t x) { return ZZ ? (int32_t)(((uint32_t)x << 1) ^ (uint32_t)(x >> 31)) : x; };
+                Cell c;
+                c.x = zz(v[0]);
+                c.y = zz(v[1]);
+                c.z = zz(v[2]);
+                c.w = zz(v[3]);
+                if constexpr (WT)
+                    asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" : : "v"(off), "v"(c), "s"(rowBase) : "memory");
+                else
+                    *(Cell *)(rowBase + off) = c;
             };
             if constexpr (!std::is_same<Sink, NoSink>::value) {
                 static_assert(LPC == 1, "a tile sink reads the lane's own row");
                 (*sink)(j0, sh.xs + fs * Geo<LPC>::STRIDE);
             }
+            // Group-row address = wave-uniform pointer (stepped with scalar adds) + the lane's 32-bit byte offset
+            // laneOff = 16 (half * streamStride + fStream) < 16 LPC streamStride (half < LPC, fStream < streamStride): at most
+            // 4 group rows of at most 5 planes x chains x 16 bytes = 320 bytes per chain, exactly the four group rows
+            // golf_stream's offsets need below 2^32 (alac_golomb.hpp, load).
+            constexpr int CELLS = Geo<LPC>::TILE / 4 / LPC;  // cells per lane and tile: lane (fs, half) takes cells it * LPC + half
+            const int32_t *cell = sh.xs + fs * Geo<LPC>::STRIDE + 4 * (int)half;
+            const char *rowPtr = dst ? (const char *)(dst + (uint64_t)j0 * streamStride) : nullptr;  // (j0 / 4) group rows
+            const uint64_t rowStep = (uint64_t)LPC * streamStride * 16u;
+            const uint32_t laneOff = voff * 16u;
             if (!std::is_same<Sink, NoSink>::value && !dst) {
                 // the sink was the only consumer (k_class_final): no residual plane
             } else if constexpr (LPC >= 2) {
                 // One wave per SIMD: nothing hides an LDS round trip, so a read that is waited for in front of its own store
-                // costs the lane's whole latency once per row.  The lane's cells (stride LPC: ds_read2_b32 pairs) are read as a
-                // batch, lds_order() keeps the compiler from sinking them back between the stores, and one round trip is
-                // exposed per batch.  Row address = wave-uniform row pointer (stepped with scalar adds) + the lane's 32-bit
-                // byte offset laneOff = 4 (half * streamStride + fStream) < 4 LPC streamStride (half < LPC, fStream < streamStride):
-                // at most 4 rows of at most 5 planes x chains x 4 bytes, a quarter of the 16 rows golf_stream's offsets already
-                // need below 2^32 (alac_golomb.hpp, load).
-                constexpr int CELLS = Geo<LPC>::TILE / LPC;
-                const int32_t *cell = sh.xs + fs * Geo<LPC>::STRIDE + (int)half;
-                const char *rowPtr = (const char *)(dst + (uint64_t)j0 * streamStride);
-                const uint64_t rowStep = (uint64_t)LPC * streamStride * 4u;
-                const uint32_t laneOff = voff * 4u;
+                // costs the lane's whole latency once per cell.  The lane's cells (STRIDE is odd: ds_read2_b32 pairs) are read as
+                // a batch, lds_order() keeps the compiler from sinking them back between the stores, and one round trip is
+                // exposed per batch.
                 if ((uint32_t)(j0 + Geo<LPC>::TILE) <= fPmin) {
                     // every lane owns every row of the tile: no predicate, no branch
-                    int32_t v[CELLS];
+                    int32_t v[CELLS][4];
 #pragma unroll
-                    for (int it = 0; it < CELLS; it++) v[it] = cell[it * LPC];
+                    for (int it = 0; it < CELLS; it++)
+#pragma unroll
+                        for (int k = 0; k < 4; k++) v[it][k] = cell[it * 4 * LPC + k];
                     lds_order();
                     // The offset is pinned to this block: hoisted out of the tile loop, its zero-extension reaches the stores as
                     // a 64-bit vector register and every store gets a 64-bit vector add in front; seen here, the stores take the
@@ -653,48 +670,54 @@ __device__ __forceinline__ void lms_pass(LmsShared<LPC> &sh, const V1Args &A, co
                     asm volatile("" : "+v"(off));
 #pragma unroll
                     for (int it = 0; it < CELLS; it++) {
-                        put((int32_t *)(rowPtr + off), v[it]);
+                        put4(rowPtr, off, v[it]);
                         rowPtr += rowStep;
                     }
                 } else {
-                    // tiles that reach a packet's end (or idle lanes without idleFast): the same in groups of 8 rows per lane
-                    // (a predicated store is a block of its own and keeps its vector add)
-                    constexpr int GROUP = 8;
+                    // tiles that reach a packet's end (or idle lanes without idleFast): the same, two cells per lane at a time
+                    constexpr int GROUP = 2;
                     static_assert(CELLS % GROUP == 0, "whole groups");
 #pragma unroll 1
                     for (int g = 0; g < CELLS; g += GROUP) {
-                        int32_t v[GROUP];
+                        int32_t v[GROUP][4];
 #pragma unroll
-                        for (int k = 0; k < GROUP; k++) v[k] = cell[(g + k) * LPC];
+                        for (int k = 0; k < GROUP; k++)
+#pragma unroll
+                            for (int e = 0; e < 4; e++) v[k][e] = cell[(g + k) * 4 * LPC + e];
                         lds_order();
 #pragma unroll
                         for (int k = 0; k < GROUP; k++) {
-                            const uint32_t j = (uint32_t)(j0 + (g + k) * LPC) + half;
-                            if (j < fP) put((int32_t *)(rowPtr + laneOff), v[k]);
+                            const uint32_t j = (uint32_t)(j0 + 4 * ((g + k) * LPC + (int)half));  // the cell's first row
+                            if (j < fP) put4(rowPtr, laneOff, v[k]);
                             rowPtr += rowStep;
                         }
                         lds_order();
                     }
                 }
-            } else if ((uint32_t)(j0 + Geo<LPC>::TILE) <= fPmin) {
-                // (LPC = 1: the callers that flush every tile are the throughput regime's, two waves per SIMD that hide each
-                // other's LDS latency and no registers to spare for a batch — the read-and-store form stays)
-                // every lane owns every row of the tile: scalar row base + lane column, no predicate, no branch
-                int32_t *tileBase = dst + (uint64_t)j0 * streamStride;
-#pragma unroll
-                for (int it = 0; it < Geo<LPC>::TILE / LPC; it++)
-                    put(tileBase + (uint64_t)(it * LPC) * streamStride + voff, sh.xs[fs * Geo<LPC>::STRIDE + it * LPC + (int)half]);
             } else {
-#pragma unroll 4
-                for (int it = 0; it < Geo<LPC>::TILE / LPC; it++) {
-                    const int jj = it * LPC + lane / SLOTS;
-                    const uint32_t j = (uint32_t)(j0 + jj);
-                    const int32_t v = sh.xs[fs * Geo<LPC>::STRIDE + jj];
-                    if (j < fP) put(dst + (uint64_t)j * streamStride + fStream, v);
+                // (LPC = 1, the lane is the chain: the callers that flush every tile are the throughput regime's, two waves per
+                // SIMD that hide each other's LDS latency and no registers to spare for a batch — read and store, cell by cell;
+                // eight 16-byte stores per 32-step tile)
+                const bool whole = (uint32_t)(j0 + Geo<LPC>::TILE) <= fPmin;  // every lane owns every row of the tile
+#pragma unroll
+                for (int it = 0; it < CELLS; it++) {
+                    int32_t v[4];
+#pragma unroll
+                    for (int k = 0; k < 4; k++) v[k] = cell[it * 4 + k];
+                    if (whole || (uint32_t)(j0 + 4 * it) < fP) put4(rowPtr, laneOff, v);
+                    rowPtr += rowStep;
                 }
             }
-            // fused final kernel: tell the coder waves how many residual rows are complete (every 4 tiles)
-            if (flag && ((((j0 / Geo<LPC>::TILE) & A.pubMask & 0xff) == (A.pubMask & 0xff)) || !more)) publish_rows(flag, flagBase + (uint32_t)min(j0 + Geo<LPC>::TILE, (int)runTo), lane, (A.pubMask >> 31) != 0, A.ho.lose);
+            // fused launches: tell the consumer waves how many residual rows are complete.  Every publish pays the drain of the
+            // write-through stores (publish_rows), so the producer publishes after tiles K - 1, 2 K - 1, ... (K = low byte of
+            // pubMask + 1, a power of two: option "pub_every") — and after every one of the last K tiles of the pass, where a
+            // consumer that is told late would lengthen the launch by up to K - 1 tiles of coding.
+            if (flag) {
+                const uint32_t pm = A.pubMask & 0xffu;
+                const uint32_t tile = (uint32_t)j0 / (uint32_t)Geo<LPC>::TILE;
+                if ((tile & pm) == pm || (uint32_t)j0 + (pm + 1) * (uint32_t)Geo<LPC>::TILE >= runTo)
+                    publish_rows(flag, flagBase + (uint32_t)min(j0 + Geo<LPC>::TILE, (int)runTo), lane, (A.pubMask >> 31) != 0, A.ho.lose);
+            }
         }
         lds_order();
         if (fastNext) {
@@ -957,7 +980,7 @@ __global__ __launch_bounds__(64) void k_lms_final(V1Args A)
 }
 
 // ================================================================================================
-// Golomb kernels: one lane per stream, residuals read coalesced from the [sample][stream] planes
+// Golomb kernels: one lane per stream, residuals read coalesced from the [sample / 4][stream][4] planes
 // ================================================================================================
 
 // search1 counts: stream = r * chainsPad + chain, n8 symbols each -> bits1[stream]
@@ -972,7 +995,7 @@ __global__ __launch_bounds__(64) void k_gol_count1(V1Args A, uint32_t chanBits)
     uint32_t p, N;
     const bool active = seg_packet(A.S, chain / CH, p, N);
     const uint32_t n8 = active ? N / 8 : 0;
-    const int32_t *plane = A.resA + (uint64_t)r * A.chainsPad;
+    const int32_t *plane = plane_from_stream(A.resA, (uint64_t)r * A.chainsPad);
     const uint64_t stride = 5ull * A.chainsPad;
     GolF g;
     golf_reset(g);
@@ -1022,7 +1045,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg, 1) void k_search1_fused(V1Args A,
             GolF g;
             golf_reset(g);
             wait.base = r << 16;
-            golf_stream<false>(g, n8, nMax, chanBits, recip, one_plane(A.resA + (uint64_t)r * A.chainsPad, stride, chain), wait);
+            golf_stream<false>(g, n8, nMax, chanBits, recip, one_plane(plane_from_stream(A.resA, (uint64_t)r * A.chainsPad), stride, chain), wait);
             if (active) A.bits1[r * A.chainsPad + chain] = n8 ? g.bits : 0u;  // (see k_gol_count1)
         }
         return;
@@ -1039,7 +1062,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg, 1) void k_search1_fused(V1Args A,
         uint32_t p, N;
         const bool active = seg_packet(A.S, chain >> 1, p, N);
         const uint32_t n8 = active ? N / 8 : 0;
-        const int32_t *plane = A.resA + (uint64_t)r * A.chainsPad;
+        const int32_t *plane = plane_from_stream(A.resA, (uint64_t)r * A.chainsPad);
         const uint64_t stride = 5ull * A.chainsPad;
         GolF g;
         golf_reset(g);
@@ -1075,7 +1098,7 @@ __device__ __forceinline__ void count2_body(const V1Args &A, uint32_t chain, uin
     // Rows below P2 come from the last converge pass (resB), the tail from the mixRes = 4 search pass (resA).  P2 is
     // the same for every full packet, so normally the row ADDRESS is picked with scalar selects and one load is
     // issued per row; only waves that mix packet lengths read both planes and pick per lane.
-    const int32_t *planeB = A.resB + (uint64_t)rs * A.chainsPad, *planeA = A.resA + (uint64_t)kMaxRes * A.chainsPad;
+    const int32_t *planeB = plane_from_stream(A.resB, (uint64_t)rs * A.chainsPad), *planeA = plane_from_stream(A.resA, (uint64_t)kMaxRes * A.chainsPad);
     const uint32_t nMax = wave_max(n8);
     const uint32_t p2lo = wave_min_u32(active ? P2 : 0xffffffffu), p2hi = wave_max(active ? P2 : 0u);
     if (CH == 1 || p2lo >= p2hi) {
@@ -1086,10 +1109,11 @@ __device__ __forceinline__ void count2_body(const V1Args &A, uint32_t chain, uin
         rs2.s1 = strideA;
         rs2.split = CH == 1 ? 0xffffffffu : p2hi;
         rs2.col = chain;
+        rs2.org = 0;
         golf_stream<false>(g, n8, nMax, chanBits, recip, rs2, need);
     } else {
         golf_stream_fn<false>(g, n8, nMax, chanBits, recip, [&](uint32_t j) {
-            const int32_t b = (planeB + j * strideB)[chain], a = (planeA + j * strideA)[chain];
+            const int32_t b = planeB[plane_index(j, strideB, chain)], a = planeA[plane_index(j, strideA, chain)];
             return j < P2 ? b : a;
         }, need);
     }
@@ -1402,8 +1426,8 @@ __global__ __launch_bounds__(64 * kWavesPerWg, 1) void k_final_fused(V1Args A, u
                 uint32_t *slot = A.bitWordsB + slotIdx * A.wcap;
                 golf_open(g, slot, A.wcap);
                 wait.base = a;
-                golf_stream<true, true>(g, nB, wave_max(nB), chanBits, recip, one_plane(plane + (uint64_t)a * stride, stride, chain),
-                                        wait, A.idleFast != 0, true);
+                golf_stream<true, true>(g, nB, wave_max(nB), chanBits, recip, one_plane(plane, stride, chain, a), wait,
+                                        A.idleFast != 0, true);
                 golf_flush<true>(g);
                 if (have) A.bitsB[slotIdx] = (active && nB) ? golf_written_bits(g, slot) : 0u;
             }
@@ -1564,17 +1588,17 @@ __device__ __forceinline__ void search2_lane_body(LmsShared<1> &sh, const uint32
     store_row<1, T>(J, a, lane);
     if (CH == 2) {
         // the tail [P2, n8) comes from the mixRes = 4 search pass (plane 4 of resA), codec/ALACEncoder.cu:433-445
-        const int32_t *planeA = A.resA + (uint64_t)kMaxRes * A.chainsPad;
+        const int32_t *planeA = plane_from_stream(A.resA, (uint64_t)kMaxRes * A.chainsPad);
         const uint64_t strideA = 5ull * A.chainsPad;
         const uint32_t nTail = J.active ? n8 - P2 : 0;
         const uint32_t p2lo = wave_min_u32(J.active ? P2 : 0xffffffffu), p2hi = wave_max(J.active ? P2 : 0u);
         if (p2lo >= p2hi) {
             // (idleFast off: a lane whose stream ended with the converge pass must not count rows of the tail)
-            golf_stream<false>(g, nTail, wave_max(nTail), chanBits, recip, one_plane(planeA + (uint64_t)p2hi * strideA, strideA, chain),
-                               NoWait(), false, false);
+            golf_stream<false>(g, nTail, wave_max(nTail), chanBits, recip, one_plane(planeA, strideA, chain, p2hi), NoWait(),
+                               false, false);
         } else {
             golf_stream_fn<false>(g, nTail, wave_max(nTail), chanBits, recip,
-                                  [&](uint32_t j) { return (planeA + (uint64_t)(P2 + j) * strideA)[chain]; }, NoWait(), false, false);
+                                  [&](uint32_t j) { return planeA[plane_index(P2 + j, strideA, chain)]; }, NoWait(), false, false);
         }
     }
     // the stream ends here whether or not it had a tail (a packet of fewer than ~80 samples has none: n8 <= P2) — a run the last
@@ -1833,8 +1857,8 @@ hipError_t launch_v1_typed(const V1Args &A0, const V1Plan &P, uint32_t numPacket
     //                  escape and the packet sizes itself (k_final_fused<.., FOLD>), and ONE memset clears the progress
     //                  words of both producer/consumer launches of the position.
     //  Throughput      many waves per SIMD: every kernel fills the machine by itself, so the stages run as separate launches
-    //                  with plain coalesced stores (the 4-byte write-through hand-off stores of the fused launches are one
-    //                  fabric write each and cap them at ~1 TB/s), a chain's taps sit in one lane (fewest instructions per
+    //                  with plain coalesced stores (the write-through hand-off stores of the fused launches go to the
+    //                  fabric one by one), a chain's taps sit in one lane (fewest instructions per
     //                  chain step), the final pass runs per packet class and the coder stores only completed words.
     //                  125 000 packets: 15.8 -> 10.1 ms.
     //  Stagewise       one kernel per stage (option fused = 0).

@@ -4,6 +4,7 @@
 #pragma once
 #include "alac_dev.hpp"
 #include "alac_kernels.hpp"
+#include "alac_plane_index.hpp"
 
 namespace alacdev {
 
@@ -32,9 +33,10 @@ struct V1Args {
     SegView S;
     int16_t *state;        // [segment][64] working coefficient rows
     PacketRec *recs;
-    int32_t *resA;         // search1 residuals [j < n8][5 * chainsPad]   stream = r * chainsPad + chain
-    int32_t *resB;         // search2 residuals [j < n8][2 * chainsPad]   stream = rowsel * chainsPad + chain
-    int32_t *resC;         // final residuals   [j < N][chainsPad]
+    // residual planes, all three [sample / 4][stream][4] (alac_plane_index.hpp: plane_index(j, streams, stream))
+    int32_t *resA;         // search1 residuals, j < n8, 5 * chainsPad streams   stream = r * chainsPad + chain
+    int32_t *resB;         // search2 residuals, j < n8, 2 * chainsPad streams   stream = rowsel * chainsPad + chain
+    int32_t *resC;         // final residuals,   j < N,  chainsPad streams       stream = chain
     uint32_t *bits1;       // [5 * chainsPad]
     uint32_t *cost2;       // [2 * chainsPad]
     uint32_t chainsPad;    // numSegments * channels rounded up to 64
@@ -49,7 +51,8 @@ struct V1Args {
                            // load_row takes init_coefs instead of reading them
     uint32_t foldDecide;   // 1: k_final_fused<.., FOLD> decides numU / numV / escape and the packet size itself (no k_decide2,
                            // no k_finalize launch)
-    uint32_t pubMask;      // producers publish after every (low byte + 1) tiles; bit 31: with a release fence
+    uint32_t pubMask;      // producers publish after every (low byte + 1) tiles (a power of two, option "pub_every") and after each of
+                           // the last (low byte + 1) tiles of a pass; bit 31: with a release fence
     uint32_t idleFast;     // 1: lanes without work do not force the checked paths (latency regime, see launcher)
     HandoffCtl ho;         // error word / spin bound / test switch of the in-launch hand-offs
     uint32_t thru;         // 1: V1Shape::Throughput (no kernel reads it)

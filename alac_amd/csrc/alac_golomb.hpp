@@ -12,6 +12,7 @@
 #pragma once
 
 #include "alac_dev.hpp"
+#include "alac_plane_index.hpp"
 
 namespace alacdev {
 
@@ -244,9 +245,9 @@ __device__ __forceinline__ void golf_finish(GolF &g, bool active, const uint32_t
     g.inrun = 0;
 }
 
-// Walk one stream of `n` residuals.  `fetch(j)` returns this lane's residual of row j, with j WAVE-UNIFORM: every
-// lane loads every row up to the wave's longest stream (rows beyond a lane's own length are ignored, never
-// branched around), so the address is a scalar row base plus the lane's column.  Three 16-sample register
+// Walk one stream of `n` residuals.  Row j is WAVE-UNIFORM: every lane loads every row up to the wave's longest stream
+// (rows beyond a lane's own length are ignored, never branched around), so the address is a scalar group-row base plus the
+// lane's cell.  Three 16-sample register
 // buffers rotate so that a block's loads are issued two blocks (32 symbols) before it is coded: the bit-word
 // stores of the coder share the vector-memory counter with the loads, so the compiler can only wait for
 // "everything outstanding" (vmcnt(0)) — with two blocks of distance that wait finds the loads done.
@@ -263,22 +264,25 @@ struct NoWait {
     __device__ __forceinline__ void operator()(uint32_t) const {}
 };
 
-// Row source of golf_stream: rows below `split` come from plane p0 (row stride s0 elements), the rest from p1/s1;
-// the lane reads column `col` of a row.  Row addresses are scalar and advance by one add per row (no multiply).
+// Row source of golf_stream: row j of the stream is sample org + j of the lane's stream `col`; samples below `split`
+// come from plane p0 (s0 streams per group row), the rest from p1 / s1 (alac_plane_index.hpp: [sample / 4][stream][4]).
+// Group-row addresses are scalar and advance by one add per group (no multiply).
 struct RowSrc {
     const int32_t *p0, *p1;
     uint64_t s0, s1;
     uint32_t split;  // 0xffffffff: single plane p0
     uint32_t col;
+    uint32_t org;    // first sample of the stream inside the plane
 };
 
-__device__ __forceinline__ RowSrc one_plane(const int32_t *plane, uint64_t stride, uint32_t col)
+__device__ __forceinline__ RowSrc one_plane(const int32_t *plane, uint64_t stride, uint32_t col, uint32_t org = 0)
 {
     RowSrc r;
     r.p0 = r.p1 = plane;
     r.s0 = r.s1 = stride;
     r.split = 0xffffffffu;
     r.col = col;
+    r.org = org;
     return r;
 }
 
@@ -291,27 +295,37 @@ __device__ __forceinline__ void golf_stream(GolF &g, uint32_t n, uint32_t nMaxWa
 {
     constexpr int B = 16;
     int32_t bufA[B], bufB[B], bufC[B];
+    static_assert(B % kPlaneGroup == 0, "a block is whole cells");
     auto load = [&](int32_t (&buf)[B], uint32_t jb) {
         if (jb < nMaxWave) {
             need(min(jb + B, nMaxWave));
-            if (jb + B <= R.split || jb >= R.split) {
-                const bool first = jb + B <= R.split;
+            const uint32_t j0 = R.org + jb;  // first sample of the block inside the plane
+            if ((j0 & (kPlaneGroup - 1)) == 0 && (j0 + B <= R.split || j0 >= R.split)) {
+                const bool first = j0 + B <= R.split;
                 const uint64_t st = first ? R.s0 : R.s1;
-                // scalar row base + the lane's 32-bit byte offset: a global load with an SGPR base and a VGPR offset, no
-                // 64-bit vector address arithmetic per row
-                const char *base = (const char *)((first ? R.p0 : R.p1) + (uint64_t)jb * st);
-                const uint32_t rowBytes = (uint32_t)st * 4u;  // < 2^32: a row is at most 5 planes x chains x 4 bytes
-                uint32_t off = R.col * 4u;                     // 16 rows stay below 2^32 bytes as well
+                // The block is four whole cells of the lane's stream: four 16-byte loads.  Scalar group-row base + the lane's
+                // 32-bit byte offset (a global load with an SGPR base and a VGPR offset, no 64-bit vector address arithmetic),
+                // one add per group.  off < 4 group rows = 64 st bytes: at most 5 planes x chains x 64 bytes, the same bound
+                // as 16 rows of 4-byte elements.
+                const char *base = (const char *)((first ? R.p0 : R.p1) + (uint64_t)j0 * st);  // (j0 / 4) * st cells
+                const uint32_t groupBytes = (uint32_t)st * 16u;
+                uint32_t off = R.col * 16u;
 #pragma unroll
-                for (int s = 0; s < B; s++) {
-                    buf[s] = *(const int32_t *)(base + off);
-                    off += rowBytes;
+                for (int s = 0; s < B; s += 4) {
+                    const int4 v = *(const int4 *)(base + off);
+                    buf[s] = v.x;
+                    buf[s + 1] = v.y;
+                    buf[s + 2] = v.z;
+                    buf[s + 3] = v.w;
+                    off += groupBytes;
                 }
-            } else {  // the block straddles the split (never with 4096-sample packets: split = 128)
+            } else {
+                // a block that does not start on a cell (a stream that begins at P2 inside one) or that straddles the split
+                // (never with 4096-sample packets: split = 128): element by element
 #pragma unroll
                 for (int s = 0; s < B; s++) {
-                    const uint32_t j = jb + s;
-                    buf[s] = (j < R.split ? R.p0 + (uint64_t)j * R.s0 : R.p1 + (uint64_t)j * R.s1)[R.col];
+                    const uint32_t j = j0 + s;
+                    buf[s] = j < R.split ? R.p0[plane_index(j, R.s0, R.col)] : R.p1[plane_index(j, R.s1, R.col)];
                 }
             }
         }

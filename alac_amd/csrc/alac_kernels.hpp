@@ -135,12 +135,15 @@ struct HandoffCtl {
 // Per-context switches that select code paths (alac_hip_set_option; the ALAC_HIP_* environment variables of the same
 // names are only the DEFAULTS a context starts from, read once in alac_hip_create).  -1 = automatic (chosen per call
 // from the batch shape).
+constexpr int32_t kPubEveryDefault = 1;
 struct AlacOptions {
     int32_t thru = -1;         // "thru"         ALAC_HIP_THRU        encode: throughput (1) / latency (0) regime, -1 = by batch size
     int32_t narrow = -1;       // "narrow"       ALAC_HIP_NARROW      four lanes per chain, -1 = by batch size (v1_narrow_regime)
     int32_t splitCoder = 1;    // "split_coder"  ALAC_HIP_SPLIT_CODER tiny batches: final coder of a chain on two waves
     int32_t overlapPos = 1;    // "overlap_pos"  ALAC_HIP_OVERLAP_POS chained batches: position p + 1's search beside p's final pass
     int32_t fused = 1;         // "fused"        ALAC_HIP_FUSED       producer/consumer launches (latency regime); 0 = one kernel per stage
+    int32_t pubEvery = kPubEveryDefault;  // "pub_every" ALAC_HIP_PUB_EVERY  fused launches: producers publish every 1 / 2 / 4 / 8 tiles (and every tile
+                               // at the end of a pass)
     int32_t fold = 1;          // "fold"         ALAC_HIP_FOLD        latency regime: decision and packet sizes inside the final launch
     int32_t fastMode = 0;      // "fast_mode"    (no env)             ALACEncoder::SetFastMode: stereo elements without the search (EncodeStereoFast)
     int32_t laneEncoder = 0;   // "encoder_lane" ALAC_HIP_ENCODER=lane first-generation lane-per-chain encoder
@@ -160,9 +163,11 @@ struct AlacOptionKey {
     const char *env;  // the ALAC_HIP_* variable that supplies the default (nullptr: none)
     int32_t AlacOptions::*slot;
     int32_t lo, hi;  // accepted values
+    bool pow2 = false;  // ... of which only the powers of two
 };
 const AlacOptionKey *alac_option_keys(uint32_t *count);
 const AlacOptionKey *alac_option_find(const char *key);  // nullptr for an unknown key
+bool alac_option_accepts(const AlacOptionKey &k, long v);
 
 // side stream and fork/join events (owned by the context): the second packet class of the throughput regime's final pass runs
 // beside the first, and consecutive packet positions of a chained tiny batch alternate between the two streams

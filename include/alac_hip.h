@@ -77,6 +77,8 @@ int32_t alac_hip_synchronize(alac_hip_ctx *ctx);
  *                          and its fused final launch; only the mixRes search in front of it runs as plain launches
  *                          (its progress word counts the rows of a pass in 16 bits), and "overlap_pos" is off with it
  *   "fold" (0/1)           latency regime: numU / numV / escape decision and the packet sizes inside the final launch
+ *   "pub_every" (1/2/4/8)  latency and tiny regimes: the predictor waves of the producer/consumer launches tell their consumers
+ *                          about finished residual rows every 1, 2, 4 or 8 tiles, and after every tile at the end of a pass
  *   "split_coder" (0/1)    tiny regime: the final coder of a chain on two waves
  *   "overlap_pos" (0/1)    chained tiny batches: packet position p + 1's search beside position p's final pass
  *   "fast_mode" (0/1)      ALACEncoder::SetFastMode: the search-free stereo path (EncodeStereoFast)
