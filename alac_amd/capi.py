@@ -38,6 +38,12 @@ class Dither(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
 
 
+class IntSource(C.Structure):
+    """alac_hip_int_source: the containers of an integer source, their significant bits and their strides (in containers)"""
+    _fields_ = [("container_bytes", C.c_uint32), ("bits", C.c_uint32), ("left_justified", C.c_uint32),
+                ("reserved", C.c_uint32), ("channel_stride", C.c_uint64), ("frame_stride", C.c_uint64)]
+
+
 class FloatReport(C.Structure):
     """alac_hip_float_report: one per segment of alac_hip_float_probe, 32 bytes"""
     _fields_ = [("over_range", C.c_uint64), ("nan", C.c_uint64), ("need_bits", C.c_uint32), ("peak_bits", C.c_uint32),
@@ -90,6 +96,13 @@ SIGNATURES = {
                                             _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "alac_hip_encode_float_dither_host": (_i32, [_vp, C.POINTER(Format), _vp, _u64, _u64, _vp, _u32, _vp, _u32, _vp, _i32, _vp,
                                                  _u64, _vp, C.POINTER(_u64), _vp, _vp, _vp]),
+    "alac_hip_pcm_requantize": (_i32, [_vp, C.POINTER(Format), _vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "alac_hip_pcm_requantize_host": (_i32, [_vp, C.POINTER(Format), _vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "alac_hip_encode_int_workspace_bytes": (_u64, [C.POINTER(Format), _u32, _u32]),
+    "alac_hip_encode_int": (_i32, [_vp, C.POINTER(Format), _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _i32, _vp, _u64, _vp, _u64,
+                                   _vp, _vp, _vp, _vp, _vp]),
+    "alac_hip_encode_int_host": (_i32, [_vp, C.POINTER(Format), _vp, _vp, _vp, _u32, _vp, _u32, _vp, _i32, _vp, _u64, _vp,
+                                        C.POINTER(_u64), _vp, _vp, _vp]),
     "alac_hip_profile_begin": (_i32, [_vp, _u32]),
     "alac_hip_profile_end": (_i32, [_vp, C.POINTER(_u32), C.POINTER(C.c_float), C.POINTER(_u32)]),
     "alac_hip_num_stages": (_u32, []),
@@ -420,6 +433,100 @@ class Context:
                 rc = self.lib.alac_hip_encode_float_dither(*args, C.byref(dz),
                                                            None if packet_origin is None else packet_origin.data_ptr())
             self._check(rc)
+            for v in bufs.values():
+                if hasattr(v, "record_stream"):
+                    v.record_stream(cur)
+            if num_samples is not None:
+                num_samples.record_stream(cur)
+            return bufs
+
+    def _int_source(self, what, fmt, x, bits, left_justified, container_bytes, channel_stride, frame_stride, dither,
+                    seed, packet_origin, num_samples):
+        """the checks and the alac_hip_int_source that requantize() and encode_int() share ->
+        (source struct, frames, num_packets, num_samples, dither struct or None)"""
+        t = self.torch
+        if dither not in (None, "none", "tpdf"):
+            raise ValueError('%s: dither must be None, "none" or "tpdf"' % what)
+        if packet_origin is not None and not (packet_origin.is_cuda and packet_origin.dtype in (t.int64, t.uint64) and
+                                              packet_origin.is_contiguous()):
+            raise ValueError("%s: packet_origin must be a contiguous int64 / uint64 cuda tensor" % what)
+        if x.is_cuda and x.dtype in (t.int16, t.int32) and x.dim() == 2 and x.shape[0] == fmt.num_channels:
+            cb = 2 if x.dtype == t.int16 else 4
+            if container_bytes not in (None, cb) or channel_stride is not None or frame_stride is not None:
+                raise ValueError("%s: the container and the strides of an int16 / int32 tensor are the tensor's own" % what)
+            frames, cs, fst = int(x.shape[1]), int(x.stride(0)), int(x.stride(1))
+        elif x.is_cuda and x.dtype == t.uint8 and x.dim() == 1 and x.is_contiguous() and container_bytes == 3:
+            if channel_stride is None or frame_stride is None or frame_stride < 1:
+                raise ValueError("%s: packed 3-byte sources need channel_stride= and frame_stride=" % what)
+            cb, cs, fst = 3, int(channel_stride), int(frame_stride)
+            # the frames the bytes hold: the last channel's row ends inside x
+            frames = max(0, (x.numel() // 3 - (fmt.num_channels - 1) * cs - 1) // fst + 1) if x.numel() >= 3 else 0
+        else:
+            raise ValueError("%s: x must be an int16 / int32 cuda tensor [channels, frames], or a 1-D uint8 cuda tensor "
+                             "with container_bytes=3, channel_stride= and frame_stride=" % what)
+        num_packets = (frames + fmt.frame_size - 1) // fmt.frame_size
+        if num_samples is None and frames % fmt.frame_size:
+            ns = [fmt.frame_size] * (num_packets - 1) + [frames % fmt.frame_size]
+            num_samples = t.tensor(ns, dtype=t.int32).to(self.device, non_blocking=True)
+        if packet_origin is not None and packet_origin.numel() < num_packets:
+            raise ValueError("%s: packet_origin too small" % what)
+        src = IntSource(cb, 8 * cb if bits is None else int(bits), 1 if left_justified else 0, 0, cs, fst)
+        dz = None if dither is None else Dither(DITHER_TPDF if dither == "tpdf" else DITHER_NONE, 0,
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF)
+        return src, frames, num_packets, num_samples, dz
+
+    def requantize(self, fmt, x, bits=None, left_justified=True, dither=None, seed=0, packet_origin=None, num_samples=None,
+                   clipped=False, container_bytes=None, channel_stride=None, frame_stride=None):
+        """Integer PCM of any layout, container and depth -> the packed interleaved PCM of fmt that encode() reads and
+        verify() expects (alac_hip_pcm_requantize; the rule is in include/alac_hip.h).  x is an int16 or int32 cuda tensor
+        [channels, frames] with any strides (x.stride() is passed through), of which `bits` (default: the dtype's width) are
+        significant, left-justified (the sample is x >> (width - bits)) or right-justified (values outside the range of
+        `bits` saturate and count as clipped); or, for packed little-endian 3-byte containers, a 1-D uint8 cuda tensor with
+        container_bytes=3, channel_stride= and frame_stride= in containers.  bits <= fmt.bit_depth widens exactly; a larger
+        `bits` is reduced with round half to even, and dither="tpdf" adds the TPDF dither of encode_float (seed,
+        packet_origin as there) in front of that rounding.  Returns the uint8 cuda tensor [num_packets * fmt.packet_bytes];
+        clipped=True returns (pcm, int32 [num_packets] clipped samples per packet)."""
+        with self._call() as cur:
+            t = self.torch
+            src, _, num_packets, num_samples, dz = self._int_source("requantize", fmt, x, bits, left_justified, container_bytes,
+                                                                   channel_stride, frame_stride, dither, seed, packet_origin,
+                                                                   num_samples)
+            pcm = t.empty(num_packets * fmt.packet_bytes, dtype=t.uint8, device=self.device)
+            clip = t.empty(num_packets, dtype=t.int32, device=self.device) if clipped else None
+            self._check(self.lib.alac_hip_pcm_requantize(
+                self.h, C.byref(fmt), x.data_ptr(), C.byref(src), None if num_samples is None else num_samples.data_ptr(),
+                num_packets, pcm.data_ptr(), pcm.numel(), None if clip is None else clip.data_ptr(),
+                None if dz is None else C.byref(dz), None if packet_origin is None else packet_origin.data_ptr()))
+            for v in (pcm, clip, num_samples):
+                if v is not None:
+                    v.record_stream(cur)
+            return (pcm, clip) if clipped else pcm
+
+    def encode_int(self, fmt, x, bits=None, left_justified=True, num_samples=None, seg_first=None, state=None, state_in=False,
+                   bufs=None, max_segment_packets=0, clipped=False, dither=None, seed=0, packet_origin=None,
+                   container_bytes=None, channel_stride=None, frame_stride=None):
+        """encode() from integer PCM of any layout, container and depth (alac_hip_encode_int): requantize(x) into the tail of
+        the workspace, then the encode of it.  x, bits, left_justified, dither, seed, packet_origin and the packed 3-byte
+        form as in requantize(); the other arguments and the result as in encode_float()."""
+        with self._call() as cur:
+            t = self.torch
+            src, _, num_packets, num_samples, dz = self._int_source("encode_int", fmt, x, bits, left_justified, container_bytes,
+                                                                   channel_stride, frame_stride, dither, seed, packet_origin,
+                                                                   num_samples)
+            nseg = num_packets if seg_first is None else seg_first.numel() - 1
+            bufs = bufs or self.encode_buffers(fmt, num_packets)
+            if clipped and "clipped" not in bufs:
+                bufs["clipped"] = t.empty(num_packets, dtype=t.int32, device=self.device)
+            wsb = int(self.lib.alac_hip_encode_int_workspace_bytes(C.byref(fmt), num_packets,
+                                                                   num_packets if self.get_option("lpc") else nseg))
+            ws = self._workspace(wsb)
+            self._check(self.lib.alac_hip_encode_int(
+                self.h, C.byref(fmt), x.data_ptr(), C.byref(src), None if num_samples is None else num_samples.data_ptr(),
+                num_packets, None if seg_first is None else seg_first.data_ptr(), nseg, int(max_segment_packets),
+                None if state is None else state.data_ptr(), 1 if state_in else 0, ws.data_ptr(), ws.numel(),
+                bufs["out"].data_ptr(), bufs["out"].numel(), bufs["sizes"].data_ptr(), bufs["offsets"].data_ptr(),
+                bufs["clipped"].data_ptr() if clipped else None, None if dz is None else C.byref(dz),
+                None if packet_origin is None else packet_origin.data_ptr()))
             for v in bufs.values():
                 if hasattr(v, "record_stream"):
                     v.record_stream(cur)

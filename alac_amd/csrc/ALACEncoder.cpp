@@ -198,6 +198,24 @@ int32_t ALACEncoder::EncodeSegmentsFloatAt(const float *pcm, uint64_t channelStr
     return ALAC_noErr;
 }
 
+int32_t ALACEncoder::EncodeSegmentsInt(const void *pcm, const alac_hip_int_source &src, const uint32_t *numSamples,
+                                       uint32_t numPackets, const uint32_t *segFirst, uint32_t numSegments, uint8_t *out,
+                                       uint64_t outCapacity, uint32_t *packetBytes, uint64_t *outTotalBytes, uint32_t *clipped,
+                                       const uint64_t *packetOrigin)
+{
+    alac_hip_format fmt;  // (a null context: kALAC_ParamError from the first option call)
+    if ((mLastStatus = prepare(mCtx, mFastMode, mLPCMode, mFrameSize, mBitDepth, mNumChannels, mOutputSampleRate, fmt)))
+        return mLastStatus;
+    uint64_t total = 0;
+    const alac_hip_dither dither = {mDitherMode, 0, mDitherSeed};
+    mLastStatus = alac_hip_encode_int_host(mCtx, &fmt, pcm, &src, numSamples, numPackets, segFirst, numSegments, nullptr, 0, out,
+                                           outCapacity, packetBytes, &total, clipped, &dither, packetOrigin);
+    if (mLastStatus != ALAC_HIP_noErr) return mLastStatus;
+    for (uint32_t p = 0; p < numPackets; p++) account(packetBytes[p]);
+    if (outTotalBytes) *outTotalBytes = total;
+    return ALAC_noErr;
+}
+
 // codec/ALACEncoder.cu:1385-1451
 void ALACEncoder::InitializeSampling(void *d_ip, AudioFormatDescription theInputFormat, int X, int32_t *outBytes)
 {

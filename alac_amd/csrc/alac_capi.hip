@@ -952,23 +952,65 @@ static int32_t float_host_span(alac_hip_ctx *ctx, const alac_hip_format *fmt, co
     return ALAC_HIP_noErr;
 }
 
-// the conversion into the stage c.pcm, then the encode from it.  dither (checked, nullptr or mode NONE: plain rounding) is
-// read here; d_origin is the device table of the packets' stream frame indices or nullptr.
-static int32_t encode_float_run(alac_hip_ctx *ctx, const EncodeCall &c, const float *d_in, uint64_t channel_stride,
-                                uint64_t frame_stride, uint32_t *d_clipped, const alac_hip_dither *dither = nullptr,
-                                const uint64_t *d_origin = nullptr)
+// the Philox words of a call's dither (checked; nullptr or mode NONE: none), d_origin the device table or nullptr
+static bool dither_args(const alac_hip_dither *dither, const uint64_t *d_origin, FloatDitherArgs &dz)
 {
-    const FloatInArgs a{d_in,        channel_stride,     frame_stride,    c.numSamples, c.numPackets, c.fmt.frame_size,
-                        c.fmt.num_channels, (uint8_t *)c.pcm, d_clipped};
-    FloatDitherArgs dz = {};
-    if (dither_on(dither)) {
-        dz.origin = d_origin;
-        philox_round_keys(dither->seed, dz.roundKey);
-    }
-    const hipError_t e = launch_float_to_pcm(c.fmt.bit_depth, a, c.stream, dither_on(dither) ? &dz : nullptr);
-    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "float conversion launch", e);
+    dz = {};
+    if (!dither_on(dither)) return false;
+    dz.origin = d_origin;
+    philox_round_keys(dither->seed, dz.roundKey);
+    return true;
+}
+
+// the float conversion into `pcm`.  dither (checked, nullptr or mode NONE: plain rounding) is read here
+static int32_t float_to_pcm_run(alac_hip_ctx *ctx, const alac_hip_format &fmt, hipStream_t st, const float *d_in,
+                                uint64_t channel_stride, uint64_t frame_stride, const uint32_t *d_num_samples, uint32_t np,
+                                void *pcm, uint32_t *d_clipped, const alac_hip_dither *dither, const uint64_t *d_origin)
+{
+    const FloatInArgs a{d_in, channel_stride, frame_stride, d_num_samples, np, fmt.frame_size, fmt.num_channels, (uint8_t *)pcm,
+                        d_clipped};
+    FloatDitherArgs dz;
+    const bool on = dither_args(dither, d_origin, dz);
+    const hipError_t e = launch_float_to_pcm(fmt.bit_depth, a, st, on ? &dz : nullptr);
+    return e == hipSuccess ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "float conversion launch", e);
+}
+
+// the encode of a (checked) call from its stage c.pcm, which the conversion in front of it has filled
+static int32_t encode_staged(alac_hip_ctx *ctx, const EncodeCall &c)
+{
     return (c.fmt.num_channels > 2 ? encode_elements : encode_core)(ctx, c);
 }
+
+// A device encode call whose source is converted into a stage first (alac_hip_encode_float_dither, alac_hip_encode_int).
+// sourceRefusal(): the checks of the source; convert(c): the conversion into c.pcm, enqueued on c.stream.
+extern "C++" {  // (a template: the one piece of this block without C linkage)
+template <class SourceRefusal, class Convert>
+static int32_t encode_through_stage(alac_hip_ctx *ctx, const alac_hip_format *fmt, const uint32_t *d_num_samples,
+                                    uint32_t num_packets, const uint32_t *d_seg_first, uint32_t num_segments,
+                                    uint32_t max_segment_packets, int16_t *d_state, int32_t state_in, void *d_workspace,
+                                    uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity, uint32_t *d_packet_bytes,
+                                    uint64_t *d_packet_offsets, SourceRefusal sourceRefusal, Convert convert)
+{
+    EncodeCall c = describe_encode(ctx, fmt, nullptr, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets,
+                                   d_state, state_in, d_workspace, d_out, d_packet_bytes, d_packet_offsets);
+    if (num_packets == 0) return encode_refusal(ctx, fmt, 0, c.numSegments, &c, workspace_bytes, out_capacity);
+    if (int32_t rc = sourceRefusal()) return rc;
+    // the stage: the last whole 256-byte blocks of the workspace; the encoder gets everything in front of it
+    const uint64_t stage = float_stage_bytes(fmt, num_packets);
+    if (workspace_bytes < stage) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    const uint64_t encBytes = (workspace_bytes - stage) & ~255ull;
+    c.pcm = d_workspace ? (uint8_t *)d_workspace + encBytes : nullptr;
+    if (int32_t rc = encode_refusal(ctx, fmt, num_packets, c.numSegments, &c, encBytes, out_capacity)) return rc;
+    // tap-parallel path: a table without a bound is read back and checked before anything is enqueued, and handed on
+    if (c.segKind == SegKind::Unread && fmt->num_channels <= 2 && !use_lane_encoder(ctx)) {
+        if (int32_t rc = read_max_segment(ctx, c.stream, c.segFirst, c.numSegments, num_packets, c.maxSeg)) return rc;
+        c.segKind = SegKind::Host;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    if (int32_t rc = convert(c)) return rc;
+    return encode_staged(ctx, c);
+}
+}  // extern "C++"
 
 int32_t alac_hip_encode_float(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *d_in, uint64_t channel_stride,
                               uint64_t frame_stride, const uint32_t *d_num_samples, uint32_t num_packets,
@@ -993,25 +1035,99 @@ int32_t alac_hip_encode_float_dither(alac_hip_ctx *ctx, const alac_hip_format *f
     if (!ctx) return ALAC_HIP_ParamError;
     if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
     if (const char *why = dither_refusal(fmt, dither, d_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
-    EncodeCall c = describe_encode(ctx, fmt, nullptr, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets,
-                                   d_state, state_in, d_workspace, d_out, d_packet_bytes, d_packet_offsets);
-    if (num_packets == 0) return encode_refusal(ctx, fmt, 0, c.numSegments, &c, workspace_bytes, out_capacity);
-    if (!d_in) return fail(ctx, ALAC_HIP_ParamError, "null d_in");
-    if ((uintptr_t)d_in & 3) return fail(ctx, ALAC_HIP_ParamError, "misaligned d_in (4 B)");
-    if (int32_t rc = float_stride_refusal(ctx, fmt, num_packets, channel_stride, frame_stride)) return rc;
-    // the stage: the last whole 256-byte blocks of the workspace; the encoder gets everything in front of it
-    const uint64_t stage = float_stage_bytes(fmt, num_packets);
-    if (workspace_bytes < stage) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
-    const uint64_t encBytes = (workspace_bytes - stage) & ~255ull;
-    c.pcm = d_workspace ? (uint8_t *)d_workspace + encBytes : nullptr;
-    if (int32_t rc = encode_refusal(ctx, fmt, num_packets, c.numSegments, &c, encBytes, out_capacity)) return rc;
-    // tap-parallel path: a table without a bound is read back and checked before anything is enqueued, and handed on
-    if (c.segKind == SegKind::Unread && fmt->num_channels <= 2 && !use_lane_encoder(ctx)) {
-        if (int32_t rc = read_max_segment(ctx, c.stream, c.segFirst, c.numSegments, num_packets, c.maxSeg)) return rc;
-        c.segKind = SegKind::Host;
-    }
+    return encode_through_stage(
+        ctx, fmt, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets, d_state, state_in, d_workspace,
+        workspace_bytes, d_out, out_capacity, d_packet_bytes, d_packet_offsets,
+        [&]() -> int32_t {
+            if (!d_in) return fail(ctx, ALAC_HIP_ParamError, "null d_in");
+            if ((uintptr_t)d_in & 3) return fail(ctx, ALAC_HIP_ParamError, "misaligned d_in (4 B)");
+            return float_stride_refusal(ctx, fmt, num_packets, channel_stride, frame_stride);
+        },
+        [&](const EncodeCall &c) {
+            return float_to_pcm_run(ctx, c.fmt, c.stream, d_in, channel_stride, frame_stride, c.numSamples, c.numPackets,
+                                    (void *)c.pcm, d_clipped, dither, d_packet_origin);
+        });
+}
+
+// ---- integer input of any layout, container and depth: requantize by the integer rule, then encode from the result ------
+// what is wrong with a call's integer source; `in` the device or host pointer.  After dither_refusal.
+static int32_t int_source_refusal(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *in, const alac_hip_int_source *src,
+                                  uint32_t num_packets, const alac_hip_dither *dither)
+{
+    if (!in || !src) return fail(ctx, ALAC_HIP_ParamError, "null input or alac_hip_int_source");
+    const uint32_t cb = src->container_bytes, S = src->bits;
+    if (cb < 2 || cb > 4) return fail(ctx, ALAC_HIP_ParamError, "container_bytes is not 2, 3 or 4");
+    if ((S != 16 && S != 20 && S != 24 && S != 32) || S > 8 * cb)
+        return fail(ctx, ALAC_HIP_ParamError, "bits is not 16, 20, 24 or 32, or above 8 * container_bytes");
+    if (src->reserved != 0) return fail(ctx, ALAC_HIP_ParamError, "alac_hip_int_source.reserved is not 0");
+    if (src->left_justified > 1) return fail(ctx, ALAC_HIP_ParamError, "left_justified is not 0 or 1");
+    if (cb != 3 && ((uintptr_t)in & (cb - 1))) return fail(ctx, ALAC_HIP_ParamError, "input not aligned to its container");
+    if (src->frame_stride == 0) return fail(ctx, ALAC_HIP_ParamError, "frame_stride 0");
+    if (src->channel_stride == 0 && fmt->num_channels > 1)
+        return fail(ctx, ALAC_HIP_ParamError, "channel_stride 0 with more than one channel");
+    uint64_t rows, cols, last;
+    if (__builtin_mul_overflow((uint64_t)(fmt->num_channels - 1), src->channel_stride, &rows) ||
+        __builtin_mul_overflow((uint64_t)num_packets * fmt->frame_size - 1, src->frame_stride, &cols) ||
+        __builtin_add_overflow(rows, cols, &last) || last >= UINT64_MAX / cb)
+        return fail(ctx, ALAC_HIP_ParamError, "the largest index into the input overflows 64 bits");
+    if (dither_on(dither) && fmt->bit_depth >= S)
+        return fail(ctx, ALAC_HIP_ParamError, "dither where the target depth is not below the source's: nothing is rounded");
+    return ALAC_HIP_noErr;
+}
+
+// the integer conversion into `pcm`.  *src and dither (both checked) are read here
+static int32_t pcm_requantize_run(alac_hip_ctx *ctx, const alac_hip_format &fmt, hipStream_t st, const void *d_in,
+                                  const alac_hip_int_source &src, const uint32_t *d_num_samples, uint32_t np, void *pcm,
+                                  uint32_t *d_clipped, const alac_hip_dither *dither, const uint64_t *d_origin)
+{
+    const PcmInArgs a{d_in, src.channel_stride, src.frame_stride, d_num_samples, np, fmt.frame_size, fmt.num_channels,
+                      src.container_bytes, src.bits, src.left_justified, (uint8_t *)pcm, d_clipped};
+    FloatDitherArgs dz;
+    const bool on = dither_args(dither, d_origin, dz);
+    const hipError_t e = launch_pcm_requantize(fmt.bit_depth, a, st, on ? &dz : nullptr);
+    return e == hipSuccess ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "integer conversion launch", e);
+}
+
+int32_t alac_hip_pcm_requantize(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_in, const alac_hip_int_source *src,
+                                const uint32_t *d_num_samples, uint32_t num_packets, uint8_t *d_pcm_out, uint64_t pcm_capacity,
+                                uint32_t *d_clipped, const alac_hip_dither *dither, const uint64_t *d_packet_origin)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
+    if (const char *why = dither_refusal(fmt, dither, d_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (int32_t rc = int_source_refusal(ctx, fmt, d_in, src, num_packets, dither)) return rc;
+    if (!d_pcm_out || ((uintptr_t)d_pcm_out & 15)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned d_pcm_out (16 B)");
+    if (pcm_capacity < (uint64_t)num_packets * fmt->frame_size * fmt->num_channels * bytes_per_sample(fmt->bit_depth))
+        return fail(ctx, ALAC_HIP_ParamError, "pcm_capacity below num_packets packets");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
-    return encode_float_run(ctx, c, d_in, channel_stride, frame_stride, d_clipped, dither, d_packet_origin);
+    return pcm_requantize_run(ctx, *fmt, ctx->stream, d_in, *src, d_num_samples, num_packets, d_pcm_out, d_clipped, dither,
+                              d_packet_origin);
+}
+
+uint64_t alac_hip_encode_int_workspace_bytes(const alac_hip_format *fmt, uint32_t num_packets, uint32_t num_segments)
+{
+    return alac_hip_encode_float_workspace_bytes(fmt, num_packets, num_segments);  // the same stage behind the same workspace
+}
+
+int32_t alac_hip_encode_int(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_in, const alac_hip_int_source *src,
+                            const uint32_t *d_num_samples, uint32_t num_packets, const uint32_t *d_seg_first,
+                            uint32_t num_segments, uint32_t max_segment_packets, int16_t *d_state, int32_t state_in,
+                            void *d_workspace, uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
+                            uint32_t *d_packet_bytes, uint64_t *d_packet_offsets, uint32_t *d_clipped,
+                            const alac_hip_dither *dither, const uint64_t *d_packet_origin)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
+    if (const char *why = dither_refusal(fmt, dither, d_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
+    return encode_through_stage(
+        ctx, fmt, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets, d_state, state_in, d_workspace,
+        workspace_bytes, d_out, out_capacity, d_packet_bytes, d_packet_offsets,
+        [&] { return int_source_refusal(ctx, fmt, d_in, src, num_packets, dither); },
+        [&](const EncodeCall &c) {
+            return pcm_requantize_run(ctx, c.fmt, c.stream, d_in, *src, c.numSamples, c.numPackets, (void *)c.pcm, d_clipped,
+                                      dither, d_packet_origin);
+        });
 }
 
 // ---- float32 probe: the lossless bit depth of float PCM, per segment of frames ---------------------------------------------
@@ -1684,6 +1800,57 @@ int32_t alac_hip_encode_float_host(alac_hip_ctx *ctx, const alac_hip_format *fmt
                                              out_total_bytes, h_clipped, nullptr, nullptr);
 }
 
+// A host encode call whose source is converted into a stage first (the host forms of encode_through_stage's callers), after
+// the format and dither checks.  source(spanBytes): the checks of the source and the bytes of h_in the call may read;
+// convert(c, d_in, d_clipped, d_origin): the conversion of the staged source into c.pcm.
+extern "C++" {  // (a template: the one piece of this block without C linkage)
+template <class Source, class Convert>
+static int32_t encode_host_through_stage(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *h_in,
+                                         const uint32_t *h_num_samples, uint32_t num_packets, const uint32_t *h_seg_first,
+                                         uint32_t num_segments, int16_t *h_state, int32_t state_in, uint8_t *h_out,
+                                         uint64_t out_capacity, uint32_t *h_packet_bytes, uint64_t *out_total_bytes,
+                                         uint32_t *h_clipped, const alac_hip_dither *dither, const uint64_t *h_packet_origin,
+                                         Source source, Convert convert)
+{
+    if (out_total_bytes) *out_total_bytes = 0;
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (!h_in || !h_out || !h_packet_bytes || !h_num_samples || !h_seg_first || num_segments == 0)
+        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if (int32_t rc = host_segment_refusal(ctx, h_seg_first, num_segments, num_packets)) return rc;
+    const uint32_t np = num_packets, nseg = num_segments;
+    uint64_t spanBytes = 0;
+    if (int32_t rc = source(spanBytes)) return rc;
+    if (int32_t rc = encode_refusal(ctx, fmt, np, ctx->opt.lpc ? np : nseg, nullptr, 0, 0)) return rc;
+    const uint64_t wsBytes = alac_hip_encode_float_workspace_bytes(fmt, np, ctx->opt.lpc ? np : nseg);
+    const uint64_t encBytes = (wsBytes - float_stage_bytes(fmt, np)) & ~255ull;  // the stage behind, as alac_hip_encode_float
+    const bool origin = dither_on(dither) && h_packet_origin;
+    DevBuf dIn, dClip, dOrigin;
+    hipError_t e;
+    if ((e = dIn.alloc(spanBytes)) || (e = dClip.alloc(np * 4ull)) || (origin && (e = dOrigin.alloc(np * 8ull))))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if ((e = hipMemcpyAsync(dIn.p, h_in, spanBytes, hipMemcpyHostToDevice, ctx->stream)) ||
+        (origin && (e = hipMemcpyAsync(dOrigin.p, h_packet_origin, np * 8ull, hipMemcpyHostToDevice, ctx->stream))))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    int32_t rc = encode_host_common(
+        ctx->stream, fmt, h_num_samples, np, h_seg_first, nseg, h_state, state_in, h_out, out_capacity, h_packet_bytes,
+        out_total_bytes, wsBytes,
+        [&](uint32_t maxSeg, const uint32_t *ns, const uint32_t *seg, int16_t *state, int32_t stIn, void *ws, uint8_t *out,
+            uint64_t, uint32_t *sizes, uint64_t *offs) {
+            const EncodeCall c = describe_encode(ctx, fmt, (uint8_t *)ws + encBytes, ns, np, seg, nseg, maxSeg, state, stIn, ws,
+                                                 out, sizes, offs);
+            if (int32_t crc = convert(c, (const void *)dIn.p, h_clipped ? (uint32_t *)dClip.p : nullptr, (const uint64_t *)dOrigin.p))
+                return crc;
+            return encode_staged(ctx, c);
+        },
+        on_fail(ctx), [ctx] { return alac_hip_synchronize(ctx); });
+    if (rc != ALAC_HIP_noErr || !h_clipped) return rc;
+    if ((e = hipMemcpyAsync(h_clipped, dClip.p, np * 4ull, hipMemcpyDeviceToHost, ctx->stream)) ||
+        (e = hipStreamSynchronize(ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
+    return ALAC_HIP_noErr;
+}
+}  // extern "C++"
+
 int32_t alac_hip_encode_float_dither_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *h_in,
                                           uint64_t channel_stride, uint64_t frame_stride, const uint32_t *h_num_samples,
                                           uint32_t num_packets, const uint32_t *h_seg_first, uint32_t num_segments,
@@ -1694,42 +1861,93 @@ int32_t alac_hip_encode_float_dither_host(alac_hip_ctx *ctx, const alac_hip_form
     if (!ctx) return ALAC_HIP_ParamError;
     if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
     if (const char *why = dither_refusal(fmt, dither, h_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
-    if (out_total_bytes) *out_total_bytes = 0;
-    if (num_packets == 0) return ALAC_HIP_noErr;
-    if (!h_in || !h_out || !h_packet_bytes || !h_num_samples || !h_seg_first || num_segments == 0)
-        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (int32_t rc = host_segment_refusal(ctx, h_seg_first, num_segments, num_packets)) return rc;
-    const uint32_t np = num_packets, nseg = num_segments;
+    return encode_host_through_stage(
+        ctx, fmt, h_in, h_num_samples, num_packets, h_seg_first, num_segments, h_state, state_in, h_out, out_capacity,
+        h_packet_bytes, out_total_bytes, h_clipped, dither, h_packet_origin,
+        [&](uint64_t &spanBytes) -> int32_t {
+            uint64_t span = 0;
+            if (int32_t rc = float_host_span(ctx, fmt, h_num_samples, num_packets, channel_stride, frame_stride, span)) return rc;
+            spanBytes = span * sizeof(float);
+            return float_stride_refusal(ctx, fmt, num_packets, channel_stride, frame_stride);
+        },
+        [&](const EncodeCall &c, const void *d_in, uint32_t *d_clipped, const uint64_t *d_origin) {
+            return float_to_pcm_run(ctx, c.fmt, c.stream, (const float *)d_in, channel_stride, frame_stride, c.numSamples,
+                                    c.numPackets, (void *)c.pcm, d_clipped, dither, d_origin);
+        });
+}
+
+// the bytes of h_in an integer host call may read: float_host_span in containers (after int_source_refusal: no overflow)
+static uint64_t int_host_span_bytes(const alac_hip_format *fmt, const alac_hip_int_source *src, const uint32_t *h_num_samples,
+                                    uint32_t np)
+{
+    const uint32_t fs = fmt->frame_size;
     uint64_t span = 0;
-    if (int32_t rc = float_host_span(ctx, fmt, h_num_samples, np, channel_stride, frame_stride, span)) return rc;
-    if (int32_t rc = float_stride_refusal(ctx, fmt, np, channel_stride, frame_stride)) return rc;
-    if (int32_t rc = encode_refusal(ctx, fmt, np, ctx->opt.lpc ? np : nseg, nullptr, 0, 0)) return rc;
-    const uint64_t wsBytes = alac_hip_encode_float_workspace_bytes(fmt, np, ctx->opt.lpc ? np : nseg);
-    const uint64_t encBytes = (wsBytes - float_stage_bytes(fmt, np)) & ~255ull;  // the stage behind, as alac_hip_encode_float
+    for (uint32_t p = 0; p < np; p++) {
+        const uint32_t n = h_num_samples && h_num_samples[p] < fs ? h_num_samples[p] : fs;
+        if (!n) continue;
+        const uint64_t last = (uint64_t)(fmt->num_channels - 1) * src->channel_stride + ((uint64_t)p * fs + n - 1) * src->frame_stride;
+        span = last + 1 > span ? last + 1 : span;
+    }
+    return span * src->container_bytes;
+}
+
+int32_t alac_hip_pcm_requantize_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *h_in,
+                                     const alac_hip_int_source *src, const uint32_t *h_num_samples, uint32_t num_packets,
+                                     uint8_t *h_pcm_out, uint64_t pcm_capacity, uint32_t *h_clipped,
+                                     const alac_hip_dither *dither, const uint64_t *h_packet_origin)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
+    if (const char *why = dither_refusal(fmt, dither, h_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (int32_t rc = int_source_refusal(ctx, fmt, h_in, src, num_packets, dither)) return rc;
+    const uint32_t np = num_packets;
+    const uint64_t pcmBytes = (uint64_t)np * fmt->frame_size * fmt->num_channels * bytes_per_sample(fmt->bit_depth);
+    if (!h_pcm_out) return fail(ctx, ALAC_HIP_ParamError, "null h_pcm_out");
+    if (pcm_capacity < pcmBytes) return fail(ctx, ALAC_HIP_ParamError, "pcm_capacity below num_packets packets");
+    const uint64_t spanBytes = int_host_span_bytes(fmt, src, h_num_samples, np);
     const bool origin = dither_on(dither) && h_packet_origin;
-    DevBuf dIn, dClip, dOrigin;
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    DevBuf dIn, dNs, dPcm, dClip, dOrigin;
     hipError_t e;
-    if ((e = dIn.alloc(span * sizeof(float))) || (e = dClip.alloc(np * 4ull)) || (origin && (e = dOrigin.alloc(np * 8ull))))
+    if ((e = dIn.alloc(spanBytes)) || (h_num_samples && (e = dNs.alloc(np * 4ull))) || (e = dPcm.alloc(pcmBytes)) ||
+        (e = dClip.alloc(np * 4ull)) || (origin && (e = dOrigin.alloc(np * 8ull))))
         return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
-    if ((e = hipMemcpyAsync(dIn.p, h_in, span * sizeof(float), hipMemcpyHostToDevice, ctx->stream)) ||
+    if ((e = hipMemcpyAsync(dIn.p, h_in, spanBytes, hipMemcpyHostToDevice, ctx->stream)) ||
+        (h_num_samples && (e = hipMemcpyAsync(dNs.p, h_num_samples, np * 4ull, hipMemcpyHostToDevice, ctx->stream))) ||
         (origin && (e = hipMemcpyAsync(dOrigin.p, h_packet_origin, np * 8ull, hipMemcpyHostToDevice, ctx->stream))))
         return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    int32_t rc = encode_host_common(
-        ctx->stream, fmt, h_num_samples, np, h_seg_first, nseg, h_state, state_in, h_out, out_capacity, h_packet_bytes,
-        out_total_bytes, wsBytes,
-        [&](uint32_t maxSeg, const uint32_t *ns, const uint32_t *seg, int16_t *state, int32_t stIn, void *ws, uint8_t *out,
-            uint64_t, uint32_t *sizes, uint64_t *offs) {
-            const EncodeCall c = describe_encode(ctx, fmt, (uint8_t *)ws + encBytes, ns, np, seg, nseg, maxSeg, state, stIn, ws,
-                                                 out, sizes, offs);
-            return encode_float_run(ctx, c, (const float *)dIn.p, channel_stride, frame_stride,
-                                    h_clipped ? (uint32_t *)dClip.p : nullptr, dither, (const uint64_t *)dOrigin.p);
-        },
-        on_fail(ctx), [ctx] { return alac_hip_synchronize(ctx); });
-    if (rc != ALAC_HIP_noErr || !h_clipped) return rc;
-    if ((e = hipMemcpyAsync(h_clipped, dClip.p, np * 4ull, hipMemcpyDeviceToHost, ctx->stream)) ||
+    if (int32_t rc = pcm_requantize_run(ctx, *fmt, ctx->stream, dIn.p, *src, (const uint32_t *)dNs.p, np, dPcm.p,
+                                        h_clipped ? (uint32_t *)dClip.p : nullptr, dither, (const uint64_t *)dOrigin.p))
+        return rc;
+    if ((e = hipMemcpyAsync(h_pcm_out, dPcm.p, pcmBytes, hipMemcpyDeviceToHost, ctx->stream)) ||
+        (h_clipped && (e = hipMemcpyAsync(h_clipped, dClip.p, np * 4ull, hipMemcpyDeviceToHost, ctx->stream))) ||
         (e = hipStreamSynchronize(ctx->stream)))
         return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
     return ALAC_HIP_noErr;
+}
+
+int32_t alac_hip_encode_int_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *h_in, const alac_hip_int_source *src,
+                                 const uint32_t *h_num_samples, uint32_t num_packets, const uint32_t *h_seg_first,
+                                 uint32_t num_segments, int16_t *h_state, int32_t state_in, uint8_t *h_out,
+                                 uint64_t out_capacity, uint32_t *h_packet_bytes, uint64_t *out_total_bytes,
+                                 uint32_t *h_clipped, const alac_hip_dither *dither, const uint64_t *h_packet_origin)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
+    if (const char *why = dither_refusal(fmt, dither, h_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
+    return encode_host_through_stage(
+        ctx, fmt, h_in, h_num_samples, num_packets, h_seg_first, num_segments, h_state, state_in, h_out, out_capacity,
+        h_packet_bytes, out_total_bytes, h_clipped, dither, h_packet_origin,
+        [&](uint64_t &spanBytes) -> int32_t {
+            if (int32_t rc = int_source_refusal(ctx, fmt, h_in, src, num_packets, dither)) return rc;
+            spanBytes = int_host_span_bytes(fmt, src, h_num_samples, num_packets);
+            return ALAC_HIP_noErr;
+        },
+        [&](const EncodeCall &c, const void *d_in, uint32_t *d_clipped, const uint64_t *d_origin) {
+            return pcm_requantize_run(ctx, c.fmt, c.stream, d_in, *src, c.numSamples, c.numPackets, (void *)c.pcm, d_clipped,
+                                      dither, d_origin);
+        });
 }
 
 int32_t alac_hip_float_probe_host(alac_hip_ctx *ctx, const float *h_in, uint32_t num_channels, uint64_t channel_stride,

@@ -54,27 +54,43 @@ __device__ __forceinline__ void philox(uint64_t T, uint32_t c, const FloatDither
     w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
 }
 
-// k * 2^-24 with k = (wa >> 8) - (wb >> 8): |k| < 2^24, so the conversion and the scaling are exact
-__device__ __forceinline__ float tpdf(uint32_t wa, uint32_t wb)
+// the integer of the dither rule, k = (wa >> 8) - (wb >> 8): |k| < 2^24, triangular.  The integer rule of
+// alac_hip_pcm_requantize (alac_pcm_in.hip) adds it to a fixed-point accumulator as it is
+__device__ __forceinline__ int32_t tpdf_k(uint32_t wa, uint32_t wb)
 {
-    return (float)((int32_t)(wa >> 8) - (int32_t)(wb >> 8)) * 0x1p-24f;
+    return (int32_t)(wa >> 8) - (int32_t)(wb >> 8);
 }
 
-// the dither of channel c at stream frames t0 .. t0 + 3.  One Philox call serves frames 2T and 2T + 1: two calls when t0 is
+// k * 2^-24: |k| < 2^24, so the conversion and the scaling are exact
+__device__ __forceinline__ float tpdf(uint32_t wa, uint32_t wb)
+{
+    return (float)tpdf_k(wa, wb) * 0x1p-24f;
+}
+
+// the k of channel c at stream frames t0 .. t0 + 3.  One Philox call serves frames 2T and 2T + 1: two calls when t0 is
 // even (every word used), three when it is odd (an odd packet origin; the same for a whole wave, so no divergence).
-__device__ __forceinline__ void dither4(uint64_t t0, uint32_t c, const FloatDitherArgs &d, float (&z)[4])
+__device__ __forceinline__ void dither4_k(uint64_t t0, uint32_t c, const FloatDitherArgs &d, int32_t (&k)[4])
 {
     const uint64_t T = t0 >> 1;
     uint32_t u[4], v[4];
     philox(T, c, d, u);
     philox(T + 1, c, d, v);
     if ((t0 & 1) == 0) {
-        z[0] = tpdf(u[0], u[1]), z[1] = tpdf(u[2], u[3]), z[2] = tpdf(v[0], v[1]), z[3] = tpdf(v[2], v[3]);
+        k[0] = tpdf_k(u[0], u[1]), k[1] = tpdf_k(u[2], u[3]), k[2] = tpdf_k(v[0], v[1]), k[3] = tpdf_k(v[2], v[3]);
     } else {
         uint32_t w[4];
         philox(T + 2, c, d, w);
-        z[0] = tpdf(u[2], u[3]), z[1] = tpdf(v[0], v[1]), z[2] = tpdf(v[2], v[3]), z[3] = tpdf(w[0], w[1]);
+        k[0] = tpdf_k(u[2], u[3]), k[1] = tpdf_k(v[0], v[1]), k[2] = tpdf_k(v[2], v[3]), k[3] = tpdf_k(w[0], w[1]);
     }
+}
+
+// the same as the float d = k * 2^-24 of the float rule
+__device__ __forceinline__ void dither4(uint64_t t0, uint32_t c, const FloatDitherArgs &d, float (&z)[4])
+{
+    int32_t k[4];
+    dither4_k(t0, c, d, k);
+#pragma unroll
+    for (int j = 0; j < 4; j++) z[j] = (float)k[j] * 0x1p-24f;
 }
 
 }  // namespace alacdev

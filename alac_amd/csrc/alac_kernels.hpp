@@ -348,6 +348,34 @@ inline FloatLayout float_layout(const float *in, uint32_t channels, uint64_t cha
 }
 hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t st, const FloatDitherArgs *dither = nullptr);
 
+// ---- integer input (alac_pcm_in.hip): alac_hip_pcm_requantize, the conversion pass of alac_hip_encode_int ----
+// the container of sample i of channel c of packet p is at index c * channelStride + (p * frameSize + i) * frameStride of
+// in (containers of containerBytes bytes: 2 int16, 3 packed little-endian, 4 int32); srcBits of it are significant, left-
+// or right-justified (alac_hip_int_source).  pcm, numSamples and clipped as in FloatInArgs.
+struct PcmInArgs {
+    const void *in;
+    uint64_t channelStride, frameStride;
+    const uint32_t *numSamples;  // null: every packet frameSize frames
+    uint32_t numPackets, frameSize, channels;
+    uint32_t containerBytes, srcBits, leftJustified;
+    uint8_t *pcm;
+    uint32_t *clipped;
+};
+// the vector layouts of an integer pass (1 or 2 channels): planar and interleaved int32 with 16-byte loads at every group
+// of 4 frames, planar and interleaved int16 with 8-byte loads, interleaved packed 3-byte containers with dword loads
+inline FloatLayout pcm_in_layout(const void *in, uint32_t containerBytes, uint32_t channels, uint64_t channelStride,
+                                 uint64_t frameStride)
+{
+    const uintptr_t align = containerBytes == 4 ? 16 : containerBytes == 2 ? 8 : 4;
+    if (channels > 2 || ((uintptr_t)in & (align - 1))) return kFloatGeneral;
+    if (channels == 1) return frameStride == 1 ? kFloatPlanar : kFloatGeneral;
+    if (channelStride == 1 && frameStride == 2) return kFloatInterleaved;
+    if (containerBytes != 3 && frameStride == 1 && channelStride % 4 == 0) return kFloatPlanar;
+    return kFloatGeneral;
+}
+// depth: the target depth b.  dither (b < srcBits only): TPDF by the integer rule of include/alac_hip.h
+hipError_t launch_pcm_requantize(uint32_t depth, const PcmInArgs &a, hipStream_t st, const FloatDitherArgs *dither = nullptr);
+
 // ---- float32 probe (alac_float_probe.hip): alac_hip_float_probe's one pass over the floats ----
 // the sample of channel c and frame t is in[c * channelStride + t * frameStride]; segment s = frames [segFirst[s],
 // segFirst[s + 1]) adds to reports[s] (8 uint32 per segment: alac_hip_float_report).  segFirst: device table

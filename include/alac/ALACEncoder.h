@@ -14,6 +14,7 @@
 
 struct alac_hip_ctx;
 struct alac_hip_float_report;
+struct alac_hip_int_source;
 
 class ALACEncoder {
 public:
@@ -38,7 +39,8 @@ public:
      * different threads (alacconvert --batch --devices N). */
     void SetDevice(int device) { mDevice = device; }
     /* Extension: TPDF dither for the float encode methods (alac_hip_encode_float_dither; mode ALAC_HIP_DITHER_NONE = 0 or
-     * ALAC_HIP_DITHER_TPDF = 1, 16 / 20 / 24 bits).  Default: none.  The integer encode methods never dither. */
+     * ALAC_HIP_DITHER_TPDF = 1, 16 / 20 / 24 bits).  Default: none.  The integer encode methods never dither,
+     * except EncodeSegmentsInt where it reduces the bit depth. */
     void SetDither(uint32_t mode, uint64_t seed) { mDitherMode = mode, mDitherSeed = seed; }
 
     void GetConfig(ALACSpecificConfig &config);
@@ -75,6 +77,15 @@ public:
                                   uint32_t numPackets, const uint32_t *segFirst, uint32_t numSegments, uint8_t *out,
                                   uint64_t outCapacity, uint32_t *packetBytes, uint64_t *outTotalBytes, uint32_t *clipped,
                                   const uint64_t *packetOrigin);
+
+    /* EncodeSegments from integer PCM of any layout, container and depth (alac_hip_encode_int_host): src describes the
+     * containers of pcm, their significant bits and their strides; widened exactly or reduced to the encoder's bit depth on
+     * the GPU by the integer rule of alac_hip.h.  The dither set by SetDither applies where the depth is reduced (a call that
+     * widens or keeps the depth with dither set is refused, as by alac_hip_encode_int); packetOrigin as in
+     * EncodeSegmentsFloatAt, or NULL.  clipped: [numPackets] clipped samples per packet, or NULL.  No reference counterpart. */
+    int32_t EncodeSegmentsInt(const void *pcm, const alac_hip_int_source &src, const uint32_t *numSamples, uint32_t numPackets,
+                              const uint32_t *segFirst, uint32_t numSegments, uint8_t *out, uint64_t outCapacity,
+                              uint32_t *packetBytes, uint64_t *outTotalBytes, uint32_t *clipped, const uint64_t *packetOrigin);
 
     /* Extension: what names the lossless bit depth of float32 PCM (alac_hip_float_probe_host): the sample of channel c and
      * frame t at pcm[c * channelStride + t * frameStride]; segment s = frames [segFirstFrame[s], segFirstFrame[s + 1]) (NULL

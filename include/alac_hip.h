@@ -282,6 +282,92 @@ int32_t alac_hip_encode_float_dither_host(alac_hip_ctx *ctx, const alac_hip_form
                                           uint32_t *h_packet_bytes, uint64_t *out_total_bytes, uint32_t *h_clipped,
                                           const alac_hip_dither *dither, const uint64_t *h_packet_origin);
 
+/* ---- batch encode from integer PCM of any layout, container and depth ------------------------------------------------
+ * The integer counterpart of alac_hip_encode_float: a PyTorch caller holds planar [channels, frames] int16 / int32 tensors
+ * (torchaudio.load(normalize=False), soundfile.read(dtype="int32")), a 24-bit file arrives as int32, left- or right-
+ * justified, and a 24-bit master is reduced to 16 bits with dither.  alac_hip_pcm_requantize converts such a source into the
+ * packed interleaved PCM alac_hip_encode reads and alac_hip_verify expects (one streaming pass); alac_hip_encode_int means
+ * "alac_hip_pcm_requantize into the tail of the workspace, then alac_hip_encode_segmented on the result".  No reference
+ * counterpart.
+ * The source, alac_hip_int_source: containers of container_bytes bytes (2: int16, 3: packed little-endian, 4: int32), of which
+ * S = bits are significant.  Sample i of channel c of packet p is the container at index
+ *     c * channel_stride + (p * frame_size + i) * frame_stride            (in containers)
+ * exactly the indexing of alac_hip_encode_float, so planar, interleaved and transposed views all need no copy.
+ *     left_justified = 1:  s = container >> (8 * container_bytes - S), arithmetic; the bits below are not part of the sample
+ *     left_justified = 0:  s = the sign-extended container, expected in [-2^(S-1), 2^(S-1)); a container outside that range
+ *                          is saturated to it first, and the sample counts as clipped
+ * The rule, for the target depth b = fmt->bit_depth in {16, 20, 24, 32}:
+ *   widening and identity, b >= S:   r = s << (b - S), exact; nothing is rounded, so dither is refused here
+ *   reduction, b < S, D = S - b (4, 8, 12 or 16), in 64-bit integers:
+ *     k   = (int)(wa >> 8) - (int)(wb >> 8) of the dither rule above, for (seed, channel c, stream frame t = origin[p] + i):
+ *           the same Philox4x32-10 words, counters and one-call-serves-two-frames layout; without dither k = 0
+ *     acc = s * 2^(24 - D) + k                                              # |acc| < 2^52
+ *     q   = acc >> 24 (floor),  rem = acc & (2^24 - 1)
+ *     r   = q + (rem > 2^23  or  (rem == 2^23 and q is odd))                # round half to even of acc / 2^24
+ *     out = clamp(r, -2^(b-1), 2^(b-1) - 1)
+ *     clipped = the container was out of range, or r was outside that interval
+ *   A 20-bit result goes into its 3-byte container left-justified (out << 4), as everywhere else in the library.  Frames at
+ *   or behind min(num_samples[p], frame_size) are not read; they are staged as zero, with no dither.
+ *   Relation to the float rule.  Undithered and S <= 24 the result EQUALS that of alac_hip_encode_float on x = s * 2^-(S-1),
+ *   samples and clip flags alike (x and x * 2^(b-1) are exact floats, and both rules round half to even).  With dither the two
+ *   rules DIFFER in some samples (0.06 - 1 % of them): the float rule rounds the sum x * 2^(b-1) + d to float32 once before
+ *   rint, the integer rule rounds the exact sum.  The paths are not interchangeable under dither; a stream dithered here is
+ *   verified with alac_hip_pcm_requantize + alac_hip_verify, not with alac_hip_verify_float.  The error out - s / 2^D of the
+ *   dithered integer rule has mean 0 and variance 1/4 LSB^2 at all six (S, b) pairs.
+ * alac_hip_pcm_requantize: the conversion alone, asynchronous.
+ *   d_in              the containers; 2- and 4-byte containers aligned to their size.  1 and 2 channels take vector loads
+ *                     when frame_size is a multiple of 4 and base and strides are aligned: planar and interleaved int32
+ *                     (16-byte aligned d_in, planar channel_stride a multiple of 4), planar and interleaved int16 (8-byte
+ *                     aligned), interleaved packed 3-byte (4-byte aligned).  Everything else takes one load per sample.
+ *   d_num_samples     [num_packets] or NULL (every packet frame_size frames)
+ *   d_pcm_out         16-byte aligned, pcm_capacity >= num_packets * frame_size * num_channels * container bytes of b
+ *   d_clipped         [num_packets] count of clipped samples per packet, or NULL
+ *   dither, d_packet_origin   as alac_hip_encode_float_dither; mode TPDF only where b < S
+ * alac_hip_encode_int: the arguments of alac_hip_encode_float_dither with (d_in, src) for the float pointer and its strides;
+ *   the workspace is alac_hip_encode_int_workspace_bytes (the value of alac_hip_encode_float_workspace_bytes).  The encode
+ *   options, the segment table, max_segment_packets and the state rules are those of alac_hip_encode_segmented, and the bytes
+ *   are those of alac_hip_encode on the requantized PCM.  *src and *dither are read before the call returns.
+ * kALAC_ParamError, checked before anything is enqueued and with nothing written: null d_in or src; container_bytes not 2, 3
+ * or 4; bits not 16, 20, 24 or 32, or above 8 * container_bytes; reserved != 0; left_justified > 1; d_in not aligned to a 2-
+ * or 4-byte container; frame_stride 0; channel_stride 0 with more than one channel; a largest index whose byte offset
+ * overflows 64 bits; mode TPDF with b >= S; what alac_hip_encode_float_dither refuses in a dither struct or an origin table;
+ * a workspace or output that is too small or misaligned; and everything alac_hip_encode_segmented refuses.
+ */
+typedef struct alac_hip_int_source {
+    uint32_t container_bytes; /* 2 (int16), 3 (packed little-endian), 4 (int32) */
+    uint32_t bits;            /* S: significant bits, 16 / 20 / 24 / 32, S <= 8 * container_bytes */
+    uint32_t left_justified;  /* 1: sample = container >> (8*container_bytes - S), arithmetic; the bits below are not part of
+                                 the sample.  0: sample = the sign-extended container, expected in [-2^(S-1), 2^(S-1)) */
+    uint32_t reserved;        /* 0 */
+    uint64_t channel_stride;  /* in containers */
+    uint64_t frame_stride;    /* in containers */
+} alac_hip_int_source;
+int32_t alac_hip_pcm_requantize(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_in,
+                                const alac_hip_int_source *src, const uint32_t *d_num_samples, uint32_t num_packets,
+                                uint8_t *d_pcm_out, uint64_t pcm_capacity, uint32_t *d_clipped,
+                                const alac_hip_dither *dither, const uint64_t *d_packet_origin);
+uint64_t alac_hip_encode_int_workspace_bytes(const alac_hip_format *fmt, uint32_t num_packets, uint32_t num_segments);
+int32_t alac_hip_encode_int(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_in,
+                            const alac_hip_int_source *src, const uint32_t *d_num_samples, uint32_t num_packets,
+                            const uint32_t *d_seg_first, uint32_t num_segments, uint32_t max_segment_packets,
+                            int16_t *d_state, int32_t state_in, void *d_workspace, uint64_t workspace_bytes,
+                            uint8_t *d_out, uint64_t out_capacity, uint32_t *d_packet_bytes,
+                            uint64_t *d_packet_offsets, uint32_t *d_clipped,
+                            const alac_hip_dither *dither, const uint64_t *d_packet_origin);
+/* Host-buffer forms (synchronous): h_in in the layout above; only the containers up to the last frame that h_num_samples
+ * covers are staged to the device (h_num_samples NULL in alac_hip_pcm_requantize_host: every packet frame_size frames).
+ * alac_hip_encode_int_host shares the table rules of alac_hip_encode_host_segments. */
+int32_t alac_hip_pcm_requantize_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *h_in,
+                                     const alac_hip_int_source *src, const uint32_t *h_num_samples, uint32_t num_packets,
+                                     uint8_t *h_pcm_out, uint64_t pcm_capacity, uint32_t *h_clipped,
+                                     const alac_hip_dither *dither, const uint64_t *h_packet_origin);
+int32_t alac_hip_encode_int_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *h_in,
+                                 const alac_hip_int_source *src, const uint32_t *h_num_samples, uint32_t num_packets,
+                                 const uint32_t *h_seg_first, uint32_t num_segments, int16_t *h_state, int32_t state_in,
+                                 uint8_t *h_out, uint64_t out_capacity, uint32_t *h_packet_bytes,
+                                 uint64_t *out_total_bytes, uint32_t *h_clipped,
+                                 const alac_hip_dither *dither, const uint64_t *h_packet_origin);
+
 /* Per-kernel timing with HIP events recorded on the context's stream around the three kernels of
  * alac_hip_encode (the instrumented counterpart of the dead cudaEvent timing in
  * codec/CudaAlacEncoder.cu:52-65).  begin() arms up to max_calls encode calls; end() synchronises and
