@@ -467,6 +467,81 @@ __device__ __forceinline__ void run_block(int32_t (&a)[T], int32_t (&w)[T], cons
     }
 }
 
+// ---- LONE: the block of a wave that owns its SIMD (lms_step_lone, alac_lms.hpp).  The operands of a block's steps — b, sign3(b),
+// cu - tp: 9 instructions per step that depend on nothing the recurrence produces — are formed ahead of the block, one by one
+// in the gaps of the serial chain, instead of in a clump of their own in front of it.  Step s of a block forms
+//   the five differences of the NEXT block's step s - 1 (s = 0: of this block's own step 7) and
+//   the four signs of the next block's step s - 2 (s = 0, 1: of this block's steps 6, 7),
+// so that a sign is taken a step after its difference, and step 0, which stands in the shadow of the next block's LDS reads,
+// touches none of them.
+struct StepPrep {
+    int32_t b[8][4], sb[8][4], p[8];
+};
+
+// difference m of step t (m < 4: b of slot m, 4: cu - tp); w0 = the history window at the block's first step
+__device__ __forceinline__ void prep_sub(StepPrep &P, const StepOps &o, const int32_t (&w0)[4], int t, int m)
+{
+    if (m < 4) P.b[t][m] = o.tp[t] - (m < t ? o.nx[m < t ? t - 1 - m : 0] : w0[m < t ? 0 : m - t]);
+    else P.p[t] = o.cu[t] - o.tp[t];
+}
+
+struct LoneFill {
+    StepOps &co, &no;
+    StepPrep &cur, &nxt;
+    const int32_t (&w0)[4];
+    int s;             // the step of the running block
+    int m = 0, i = 0;  // the next difference and the next sign of the step
+    __device__ __forceinline__ void sub(int n)
+    {
+        const int32_t none[4] = {0, 0, 0, 0};  // step 7 reads no window cell
+        StepOps &o = s == 0 ? co : no;
+        StepPrep &P = s == 0 ? cur : nxt;
+        const int t = s == 0 ? 7 : s - 1;
+#pragma unroll
+        for (int r = 0; r < n; r++, m++) {
+            if (m > 4) break;
+            prep_sub(P, o, s == 0 ? none : w0, t, m);
+            if (m < 4) ALAC_PIN(P.b[t][m]);
+            else ALAC_PIN(P.p[t]);
+        }
+        // the differences to come stay behind this point: all of them read the step's top
+        if (m <= 4) ALAC_ARM(o.tp[t]);
+        else if (s < 7) ALAC_ARM(no.tp[s]);
+    }
+    __device__ __forceinline__ void sgn()
+    {
+        StepPrep &P = s < 2 ? cur : nxt;
+        const int t = s < 2 ? 6 + s : s - 2;
+        if (i < 4) P.sb[t][i] = sign3_pinned(P.b[t][i]);
+        i++;
+    }
+};
+
+template <int LPC, bool MASKED>
+__device__ __forceinline__ void run_block_lone(int32_t (&a)[4], LoneCarry &C, StepOps &co, StepPrep &cur, StepOps &no, StepPrep &nxt,
+                                               const int32_t (&w0)[4], const LmsLaneT<4> &L, int jb, int32_t *resAt, uint32_t chanbits)
+{
+    int32_t dPrev = 0;
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+        const int j = jb + s;
+        const int32_t liveMask = MASKED ? (((j >= L.jlo) & (j < L.jhi)) ? -1 : 0) : -1;
+        LoneFill fill{co, no, cur, nxt, w0, s};
+        const int32_t del = s < 7 ? lms_step_lone<LPC, MASKED>(a, C, cur.b[s], cur.sb[s], cur.p[s], cur.b[s < 7 ? s + 1 : 7], liveMask, L, chanbits, fill)
+                                  : lms_step_lone<LPC, MASKED>(a, C, cur.b[s], cur.sb[s], cur.p[s], nxt.b[0], liveMask, L, chanbits, fill);
+        fill.sub(5);  // (whatever a change of the step leaves over)
+#pragma unroll
+        for (int r = 0; r < 4; r++) fill.sgn();
+        if (s & 1) {
+            resAt[s - 1] = dPrev;
+            resAt[s] = del;
+            __builtin_amdgcn_sched_barrier(0);
+        } else {
+            dPrev = del;
+        }
+    }
+}
+
 // per-lane view of its chain inside the wave's LDS
 struct LaneView {
     const int32_t *row;   // xs row of the chain (x[j] at row[kHist + j - j0])
@@ -476,7 +551,7 @@ struct LaneView {
 };
 
 // one tile [j0, jEnd) of steps; the history windows are (re)loaded from LDS at the tile start
-template <int T, int LPC, bool DEAD = (T > 4)>
+template <int T, int LPC, bool DEAD = (T > 4), bool LONE = false>
 __device__ __forceinline__ void run_tile(int32_t (&a)[T], const LaneView &V, const LmsLaneT<T> &L, int j0, int jEnd,
                                          uint32_t chanbits)
 {
@@ -490,6 +565,38 @@ __device__ __forceinline__ void run_tile(int32_t (&a)[T], const LaneView &V, con
     for (int i = 0; i < T; i++) w[i] = V.feeds ? V.row[kHist - 1 - T * L.h - i] : 0;
     StepOps opA, opB;  // ping-pong: no register copies between blocks
     load_ops(opA, pn, pt, pc);
+    if constexpr (LONE) {
+        static_assert(T == 4 && !DEAD && LPC <= 2, "the lone-wave step is built for <4, 1> and <4, 2>");
+        // the first block's operands have no running block to hide in; from then on block i + 1 is prepared inside block i
+        StepPrep pA, pB;
+#pragma unroll
+        for (int t = 0; t < 7; t++) {
+#pragma unroll
+            for (int m = 0; m < 5; m++) prep_sub(pA, opA, w, t, m);
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (t < 6) pA.sb[t][i] = sign3(pA.b[t][i]);
+        }
+        LoneCarry C;
+        lone_products(C, a, pA.b[0], L);
+        auto block = [&](StepOps &curOps, StepPrep &cur, StepOps &nxtOps, StepPrep &nxt, int jb) {
+            const int o = jb - j0;
+            load_ops(nxtOps, pn + adv * (o + 8), pt + adv * (o + 8), pc + (o + 8));
+            int32_t w0[4];  // the window after this block's eight steps
+#pragma unroll
+            for (int i = 0; i < 4; i++) w0[i] = curOps.nx[7 - i];
+            const bool allLive = __all((jb >= L.jlo) & (jb + 8 <= L.jhi));  // wave-uniform
+            if (allLive)
+                run_block_lone<LPC, false>(a, C, curOps, cur, nxtOps, nxt, w0, L, jb, V.res + o, chanbits);
+            else
+                run_block_lone<LPC, true>(a, C, curOps, cur, nxtOps, nxt, w0, L, jb, V.res + o, chanbits);
+        };
+        for (int jb = j0; jb < jEnd; jb += 16) {
+            block(opA, pA, opB, pB, jb);
+            if (jb + 8 < jEnd) block(opB, pB, opA, pA, jb + 8);
+        }
+        return;
+    }
     auto block = [&](const StepOps &cur, StepOps &nxt, int jb) {
         const int o = jb - j0;
         load_ops(nxt, pn + adv * (o + 8), pt + adv * (o + 8), pc + (o + 8));
@@ -521,7 +628,8 @@ struct ChainJob {
 // sink(j0, row) called once per tile with the lane's own LDS row (row[i] = residual of position j0 + i, i < TILE; only
 // meaningful for LPC = 1 where lane == slot): the residuals never leave the CU (k_class_final).
 struct NoSink {};
-template <int DEPTH, int CH, int LPC, bool WT = false, bool ZZ = false, int T = 4, class Sink = NoSink, bool DEAD = (T > 4)>
+// LONE: the wave has its SIMD to itself: the steps run in the fixed order of lms_step_lone (<4, 1> and <4, 2> only)
+template <int DEPTH, int CH, int LPC, bool WT = false, bool ZZ = false, int T = 4, class Sink = NoSink, bool DEAD = (T > 4), bool LONE = false>
 __device__ __forceinline__ void lms_pass(LmsShared<LPC> &sh, const V1Args &A, const ChainJob &J, int32_t (&a)[T],
                                          uint32_t num, uint32_t P, bool store, int32_t *dst, uint64_t streamStride,
                                          uint32_t stream, int lane, uint32_t *flag = nullptr, uint32_t flagBase = 0,
@@ -606,7 +714,7 @@ __device__ __forceinline__ void lms_pass(LmsShared<LPC> &sh, const V1Args &A, co
             lds_order();
         }
         const int jEnd = min(j0 + Geo<LPC>::TILE, (int)((runTo + 7) & ~7u));
-        run_tile<T, LPC, DEAD>(a, V, L, j0, jEnd, chanBits);
+        run_tile<T, LPC, DEAD, LONE>(a, V, L, j0, jEnd, chanBits);
         lds_order();
         if (store) {
             if (j0 == 0) {
@@ -815,7 +923,7 @@ __device__ __forceinline__ void store_row(const ChainJob &J, const int32_t (&a)[
 
 // ---- k_lms_search1: the five mixRes passes over N/8 samples walking row 7 (codec/ALACEncoder.cu:353-379)
 // T taps per lane x L lanes per chain = 8 (alac_lms.hpp "lane mappings"): <4, 2> or <8, 1>
-template <int DEPTH, int T, int L>
+template <int DEPTH, int T, int L, bool LONE = false>
 __device__ __forceinline__ void search1_predictor(LmsShared<L> &sh, const V1Args &A, uint32_t block, int lane, uint32_t *flag)
 {
     constexpr int SLOTS = 64 / L;
@@ -859,7 +967,7 @@ __device__ __forceinline__ void search1_predictor(LmsShared<L> &sh, const V1Args
     for (int r = 0; r <= kMaxRes; r++) {
         lms_setup<L>(sh, J, r, lane);
         if (flag)
-            lms_pass<DEPTH, 2, L, true>(sh, A, J, a, n8, n8, true, A.resA, 5ull * A.chainsPad, (uint32_t)r * A.chainsPad + chain,
+            lms_pass<DEPTH, 2, L, true, false, T, NoSink, (T > 4), LONE>(sh, A, J, a, n8, n8, true, A.resA, 5ull * A.chainsPad, (uint32_t)r * A.chainsPad + chain,
                                         lane, flag, (uint32_t)r << 16, head, r == 0 ? 1 : 2);
         else
             lms_pass<DEPTH, 2, L>(sh, A, J, a, n8, n8, true, A.resA, 5ull * A.chainsPad, (uint32_t)r * A.chainsPad + chain, lane,
@@ -881,7 +989,7 @@ __global__ __launch_bounds__(64, L == 1 ? 2 : 1) void k_lms_search1(V1Args A)
 // RS = 0: row 3 (numUV = 4), RS = 1: row 7 (numUV = 8); T taps per lane x LPC lanes per chain
 // (round 3 measured the counts as trailing consumers of this launch — 0.231 ms against 0.152 + 0.082 separate — and round 4
 // removed that variant)
-template <int DEPTH, int CH, int RS, int T, int LPC>
+template <int DEPTH, int CH, int RS, int T, int LPC, bool LONE = false>
 __device__ __forceinline__ void search2_body(LmsShared<LPC> &sh, const V1Args &A, uint32_t block, int lane)
 {
     constexpr int SLOTS = 64 / LPC;
@@ -906,7 +1014,7 @@ __device__ __forceinline__ void search2_body(LmsShared<LPC> &sh, const V1Args &A
         const uint32_t num = (CH == 1 && last) ? n8 : n32;  // mono: the last pass runs N/8 (:893)
         uint32_t P = num > (uint32_t)(J.na + 1) ? num : (uint32_t)(J.na + 1);  // positions pc_block writes ...
         P = P < n8 ? P : n8;                                                   // ... that dyn_comp will read
-        lms_pass<DEPTH, CH, LPC>(sh, A, J, a, num, P, last, A.resB, 2ull * A.chainsPad, (uint32_t)rs * A.chainsPad + chain,
+        lms_pass<DEPTH, CH, LPC, false, false, T, NoSink, (T > 4), LONE>(sh, A, J, a, num, P, last, A.resB, 2ull * A.chainsPad, (uint32_t)rs * A.chainsPad + chain,
                                  lane, nullptr, 0, &head, pass == 0 ? 1 : 2);
     }
     store_row<LPC>(J, a, lane);
@@ -942,10 +1050,10 @@ __global__ __launch_bounds__(64 * kWavesPerWg, 1) void k_lms_search2_w(V1Args A,
     auto &sh = shAll[W.slot];
     const uint32_t t = W.id / 3, r = W.id % 3;
     if (r == 0) {
-        if (t < nb3) search2_body<DEPTH, CH, 0, 4, 1>(sh.s1, A, t, W.lane);
+        if (t < nb3) search2_body<DEPTH, CH, 0, 4, 1, true>(sh.s1, A, t, W.lane);
     } else {
         const uint32_t b = 2 * t + r - 1;
-        if (b < nb7) search2_body<DEPTH, CH, 1, 4, 2>(sh.s2, A, b, W.lane);
+        if (b < nb7) search2_body<DEPTH, CH, 1, 4, 2, true>(sh.s2, A, b, W.lane);
     }
 }
 
@@ -1024,7 +1132,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg, 1) void k_search1_fused(V1Args A,
         const uint32_t t = W.id / (L + 1), r0 = W.id % (L + 1);
         if (r0 < (uint32_t)L) {
             const uint32_t pw = (uint32_t)L * t + r0;
-            if (pw < nLms) search1_predictor<DEPTH, T, L>(sh, A, pw, lane, A.flags + pw);
+            if (pw < nLms) search1_predictor<DEPTH, T, L, (T == 4 && L == 2)>(sh, A, pw, lane, A.flags + pw);
             return;
         }
         gol_table_init(recip, lane);
@@ -1052,7 +1160,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg, 1) void k_search1_fused(V1Args A,
     }
     if (W.id >= nLms + 5 * cblocks) return;
     if (W.id < nLms) {
-        search1_predictor<DEPTH, T, L>(sh, A, W.id, lane, A.flags + W.id);
+        search1_predictor<DEPTH, T, L, (T == 4 && L == 2)>(sh, A, W.id, lane, A.flags + W.id);
     } else {
         gol_table_init(recip, lane);
         lds_order();
@@ -1335,7 +1443,7 @@ __global__ __launch_bounds__(64 * kWavesPerWg, 1) void k_final_fused(V1Args A, u
         }
         lms_setup<L>(sh, J, best, lane);
         uint32_t *flag = A.flagsF + wid;
-        lms_pass<DEPTH, CH, L, true, true>(sh, A, J, a, N, N, true, A.resC, A.chainsPad, chain, lane, flag);
+        lms_pass<DEPTH, CH, L, true, true, T, NoSink, (T > 4), (T == 4 && L == 2)>(sh, A, J, a, N, N, true, A.resC, A.chainsPad, chain, lane, flag);
         store_row<L>(J, a, lane);
         if (A.rowReady) {
             // the next position's search may be waiting for this row (see search1_predictor)

@@ -153,10 +153,14 @@ template <int T, int L, bool MASKED, bool DEAD = (T > 4)>
 __device__ __forceinline__ int32_t lms_step(int32_t (&a)[T], const int32_t (&w)[T], int32_t tp, int32_t cu,
                                             int32_t liveMask, const LmsLaneT<T> &R, uint32_t chanbits)
 {
-    // A wave that has a SIMD to itself pays for every instruction it issues (a wave64 integer instruction occupies
-    // the SIMD for ~4.3 cycles, tools/op_rate_microbench.hip), so the step is written for the fewest instructions,
-    // not for the shortest dependent chain: the residual first, then ONE set of thresholds with the rounding its
-    // sign selects (an earlier version evaluated both roundings ahead of del: 73 instructions per step against 50).
+    // The step is written for the fewest instructions: the residual first, then ONE set of thresholds with the rounding
+    // its sign selects (an earlier version evaluated both roundings ahead of del: 73 instructions per step against 50).
+    // Measured rule for a wave that has a SIMD to itself (DESIGN 4.0 "step schedule", profiles/step_schedule/): it pays about
+    // 6 cycles for every instruction it issues, a hazard pad included, whether or not the instruction reads what its
+    // neighbour wrote.  lms_step_lone below runs the same arithmetic in a fixed order with 2.5 instead of 14 directly
+    // dependent neighbours and 0.5 instead of 3.5 pads a step, the same instructions otherwise; the three launches gained
+    // 3.3 / 2.3 / 1.4 % (8 to 12 cycles a step): the worth of the pads.  The 2.6 cycles a dependent pair that the
+    // microbenchmark's two figures (7.4 dependent, 4.8 independent) suggest do not show in this loop.
     int32_t b[T];
 #pragma unroll
     for (int i = 0; i < T; i++) b[i] = tp - w[i];
@@ -204,6 +208,169 @@ __device__ __forceinline__ int32_t lms_step(int32_t (&a)[T], const int32_t (&w)[
     }
 #pragma unroll
     for (int i = 0; i < T; i++) a[i] = __mul24(adj > S[i] ? nsg : 0, sb[i]) + a[i];
+    return del;
+}
+
+// ---- the step of a wave that owns its SIMD (LONE), <4, 1> and <4, 2> ---------------------------------------------
+// The same arithmetic as lms_step in a fixed instruction order (what it bought: the comment in lms_step).  The order keeps
+// the instructions of the serial chain (tap sum -> del -> thresholds -> selects -> coefficients -> next tap sum) apart:
+// the step's own side values (nd, adel, nsg) and the caller's fillers sit between them — fill.sub(n): n of the plain
+// subtractions that form a LATER step's b = tp - w and cu - tp, fill.sgn(): one sign3(b) of a later step.  The four compares
+// come first and the four selects after them (no pad between a compare and its select), and two subtractions stand ahead
+// of each DPP exchange.  The operands b, sign3(b) and p = cu - tp come prepared; the products of the NEXT step (bn = its
+// b) are formed as the coefficients appear and carried to it in C.
+struct LoneCarry {
+    int32_t s1, m1, m0;  // m3 + m2 + c255 and the products of taps 1, 0 of the step to come
+};
+
+// ALAC_PIN(x): x is complete here and nothing crosses — the empty volatile asm keeps the instruction that forms x ahead of
+// this point, the barrier keeps the scheduler from moving anything over it.  The asm only READS x: one that also wrote it
+// would hide the instruction that did from the hazard checks, which then pad whatever reads x next.
+#define ALAC_PIN(x)                          \
+    do {                                     \
+        asm volatile("" : : "v"(x));         \
+        __builtin_amdgcn_sched_barrier(0);   \
+    } while (0)
+// ALAC_ARM(x): nothing that reads x is placed ahead of this point (the asm writes x in place: keep one instruction between
+// this and the reader)
+#define ALAC_ARM(x) asm volatile("" : "+v"(x))
+
+// sign3 as a filler: volatile, so that it stays in the gap it was written into (the hazard checks count an asm statement
+// as no instruction at all: this one fills a gap of the chain but never one of the two slots ahead of a DPP exchange)
+__device__ __forceinline__ int32_t sign3_pinned(int32_t x)
+{
+    int32_t r;
+    asm volatile("v_med3_i32 %0, %1, -1, 1" : "=v"(r) : "v"(x));
+    __builtin_amdgcn_sched_barrier(0);
+    return r;
+}
+
+__device__ __forceinline__ void lone_products(LoneCarry &C, const int32_t (&a)[4], const int32_t (&bn)[4], const LmsLaneT<4> &R)
+{
+    C.s1 = __mul24((int32_t)(int16_t)a[3], bn[3]) + __mul24((int32_t)(int16_t)a[2], bn[2]) + R.c255;
+    C.m1 = __mul24((int32_t)(int16_t)a[1], bn[1]);
+    C.m0 = __mul24((int32_t)(int16_t)a[0], bn[0]);
+}
+
+// fill.sub(): one (two for L = 1) of the plain subtractions b = tp - w / p = cu - tp, fill.sgn(): one sign3(b)
+template <int L, bool MASKED, class Fill>
+__device__ __forceinline__ int32_t lms_step_lone(int32_t (&a)[4], LoneCarry &C, const int32_t (&b)[4], const int32_t (&sb)[4],
+                                                 int32_t p, const int32_t (&bn)[4], int32_t liveMask, const LmsLaneT<4> &R,
+                                                 uint32_t chanbits, Fill &&fill)
+{
+    static_assert(L == 1 || L == 2, "the lone-wave mappings");
+    constexpr int32_t kRc = (1 << kDenShift) - 1;
+    int32_t s = C.s1 + C.m1 + C.m0;
+    ALAC_PIN(s);
+    if constexpr (L == 2) {
+        fill.sub(2);
+        s += dpp_xor1(s);
+        ALAC_PIN(s);
+    }
+    fill.sgn();
+    s >>= kDenShift;
+    ALAC_PIN(s);
+    fill.sgn();
+    s += p;
+    ALAC_PIN(s);
+    fill.sgn();
+    int32_t del = __builtin_amdgcn_sbfe(s, 0, chanbits);
+    ALAC_PIN(del);
+    fill.sgn();
+    int32_t nd = -del;
+    ALAC_PIN(nd);
+    int32_t rc = del >> 31;
+    ALAC_PIN(rc);
+    int32_t adel = max(del, nd);
+    ALAC_PIN(adel);
+    rc &= kRc;
+    ALAC_PIN(rc);
+    int32_t nsg = sign3_pinned(nd);  // -sign(del): what a touched tap adds per sign(b)
+    if constexpr (MASKED) {
+        nsg &= liveMask;  // steps outside [jlo, jhi) leave the coefficients alone
+        ALAC_PIN(nsg);
+    }
+    // thresholds from the top tap down (lms_adapt_thresholds): t_i = (|b_i| + rc) >> 9, S_{i-1} = t_i w_i + S_i
+    int32_t u3 = __mul24(sb[3], b[3]) + rc;
+    ALAC_PIN(u3);
+    int32_t u2 = __mul24(sb[2], b[2]) + rc;
+    ALAC_PIN(u2);
+    int32_t t3 = (int32_t)((uint32_t)u3 >> kDenShift);
+    ALAC_PIN(t3);
+    int32_t u1 = __mul24(sb[1], b[1]) + rc;
+    ALAC_PIN(u1);
+    int32_t t2 = (int32_t)((uint32_t)u2 >> kDenShift);
+    ALAC_PIN(t2);
+    int32_t S2 = (int32_t)__umul24((uint32_t)t3, (uint32_t)R.wg[3]);
+    ALAC_PIN(S2);
+    int32_t u0 = 0;
+    if constexpr (L == 2) {
+        u0 = __mul24(sb[0], b[0]) + rc;
+        ALAC_PIN(u0);
+    }
+    int32_t t1 = (int32_t)((uint32_t)u1 >> kDenShift);
+    ALAC_PIN(t1);
+    int32_t S1 = (int32_t)__umul24((uint32_t)t2, (uint32_t)R.wg[2]) + S2;
+    ALAC_PIN(S1);
+    int32_t S0, adj;
+    if constexpr (L == 2) {
+        // the lower taps also count everything the lane above holds: |del| > S + c  <=>  |del| - c > S
+        int32_t t0 = (int32_t)((uint32_t)u0 >> kDenShift);
+        ALAC_PIN(t0);
+        S0 = (int32_t)__umul24((uint32_t)t1, (uint32_t)R.wg[1]) + S1;
+        ALAC_PIN(S0);
+        fill.sub(1);
+        int32_t tot = (int32_t)__umul24((uint32_t)t0, (uint32_t)R.wg[0]) + S0;
+        ALAC_PIN(tot);
+        fill.sub(2);
+        int32_t up = dpp_xor1(tot) & R.carry1;
+        ALAC_PIN(up);
+        adj = adel - up;
+        ALAC_PIN(adj);
+    } else {
+        fill.sub(2);
+        S0 = (int32_t)__umul24((uint32_t)t1, (uint32_t)R.wg[1]) + S1;
+        ALAC_PIN(S0);
+        fill.sub(2);
+        adj = adel;
+    }
+    // four compares into four scalar pairs, then the selects: no select waits for its compare
+    const bool c3 = adj > 0;
+    __builtin_amdgcn_sched_barrier(0);
+    const bool c2 = adj > S2;
+    __builtin_amdgcn_sched_barrier(0);
+    const bool c1 = adj > S1;
+    __builtin_amdgcn_sched_barrier(0);
+    const bool c0 = adj > S0;
+    __builtin_amdgcn_sched_barrier(0);
+    // (one lane: adj is |del| itself, and nsg is already 0 where that is 0)
+    int32_t g3 = L == 1 ? nsg : (c3 ? nsg : 0);
+    if constexpr (L == 2) ALAC_PIN(g3);
+    int32_t g2 = c2 ? nsg : 0;
+    ALAC_PIN(g2);
+    a[3] = __mul24(g3, sb[3]) + a[3];
+    ALAC_PIN(a[3]);
+    int32_t g1 = c1 ? nsg : 0;
+    ALAC_PIN(g1);
+    a[2] = __mul24(g2, sb[2]) + a[2];
+    ALAC_PIN(a[2]);
+    int32_t n3 = __mul24((int32_t)(int16_t)a[3], bn[3]);
+    ALAC_PIN(n3);
+    int32_t g0 = c0 ? nsg : 0;
+    ALAC_PIN(g0);
+    a[1] = __mul24(g1, sb[1]) + a[1];
+    ALAC_PIN(a[1]);
+    int32_t n2 = __mul24((int32_t)(int16_t)a[2], bn[2]);
+    ALAC_PIN(n2);
+    a[0] = __mul24(g0, sb[0]) + a[0];
+    ALAC_PIN(a[0]);
+    C.m1 = __mul24((int32_t)(int16_t)a[1], bn[1]);
+    ALAC_PIN(C.m1);
+    C.s1 = n3 + n2 + R.c255;
+    ALAC_PIN(C.s1);
+    C.m0 = __mul24((int32_t)(int16_t)a[0], bn[0]);
+    ALAC_PIN(C.m0);
+    if constexpr (L == 1) fill.sub(1);
     return del;
 }
 
