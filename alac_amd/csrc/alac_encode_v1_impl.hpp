@@ -551,9 +551,10 @@ struct LaneView {
 };
 
 // one tile [j0, jEnd) of steps; the history windows are (re)loaded from LDS at the tile start
+// LONE: liveLo / liveHi (wave-uniform, scalar: the pass's wave_max(jlo) and wave_min(jhi)) bound the steps every lane adapts at
 template <int T, int LPC, bool DEAD = (T > 4), bool LONE = false>
 __device__ __forceinline__ void run_tile(int32_t (&a)[T], const LaneView &V, const LmsLaneT<T> &L, int j0, int jEnd,
-                                         uint32_t chanbits)
+                                         uint32_t chanbits, int liveLo = 0, int liveHi = 0)
 {
     const int adv = V.feeds ? 1 : 0;
     // x[j] lives at row[kHist + j - j0].  nx of step j = x[j - T h] enters the window for step j + 1
@@ -579,21 +580,51 @@ __device__ __forceinline__ void run_tile(int32_t (&a)[T], const LaneView &V, con
         }
         LoneCarry C;
         lone_products(C, a, pA.b[0], L);
-        auto block = [&](StepOps &curOps, StepPrep &cur, StepOps &nxtOps, StepPrep &nxt, int jb) {
-            const int o = jb - j0;
-            load_ops(nxtOps, pn + adv * (o + 8), pt + adv * (o + 8), pc + (o + 8));
+        // The blocks run in ping-pong pairs of 16 steps.  The operand pointers stand at the pair's first step and move once a
+        // pair, by a stride formed once (lanes fed zeros stay inside sh.zero: cells 8 .. 23 of its kZeroCells); the blocks of
+        // a pair read and write at constant offsets from them, the immediates of ds_read2_b32 / ds_write2_b32.
+        static_assert(kZeroCells >= 24, "a pair's operand prefetch reads cells 8 .. 23");
+        const int stride = V.feeds ? 16 : 0;
+        const int32_t *qn = pn, *qt = pt, *qc = pc;
+        int32_t *qr = V.res;
+        auto block = [&](auto masked, auto off, StepOps &curOps, StepPrep &cur, StepOps &nxtOps, StepPrep &nxt, int jb) {
+            constexpr int o = decltype(off)::value;
+            load_ops(nxtOps, qn + (o + 8), qt + (o + 8), qc + (o + 8));
             int32_t w0[4];  // the window after this block's eight steps
 #pragma unroll
             for (int i = 0; i < 4; i++) w0[i] = curOps.nx[7 - i];
-            const bool allLive = __all((jb >= L.jlo) & (jb + 8 <= L.jhi));  // wave-uniform
-            if (allLive)
-                run_block_lone<LPC, false>(a, C, curOps, cur, nxtOps, nxt, w0, L, jb, V.res + o, chanbits);
-            else
-                run_block_lone<LPC, true>(a, C, curOps, cur, nxtOps, nxt, w0, L, jb, V.res + o, chanbits);
+            run_block_lone<LPC, decltype(masked)::value>(a, C, curOps, cur, nxtOps, nxt, w0, L, jb, qr + o, chanbits);
         };
-        for (int jb = j0; jb < jEnd; jb += 16) {
-            block(opA, pA, opB, pB, jb);
-            if (jb + 8 < jEnd) block(opB, pB, opA, pA, jb + 8);
+        auto bump = [&] {
+            qn += stride;
+            qt += stride;
+            qc += 16;
+            qr += 16;
+        };
+        using Lo = std::integral_constant<int, 0>;
+        using Hi = std::integral_constant<int, 8>;
+        // Liveness is decided per stretch of pairs, with scalars: the pairs of [liveLo, hotEnd) are live in every lane and run
+        // the unmasked body in a loop that tests nothing but its own end.  Every other pair (the warm-up positions of a pass,
+        // the end of a search row, a packet that ends in the tile) runs the masked body, which is right for live steps too —
+        // as a whole pair, so that the ping-pong keeps its parity.
+        const int hotEnd = min(liveHi, jEnd);
+        int jb = j0;
+#pragma unroll 1
+        while (jb < jEnd) {
+            if (jb >= liveLo && jb + 16 <= hotEnd) {
+#pragma unroll 1
+                do {
+                    block(std::false_type{}, Lo{}, opA, pA, opB, pB, jb);
+                    block(std::false_type{}, Hi{}, opB, pB, opA, pA, jb + 8);
+                    bump();
+                    jb += 16;
+                } while (jb + 16 <= hotEnd);
+            } else {
+                block(std::true_type{}, Lo{}, opA, pA, opB, pB, jb);
+                if (jb + 8 < jEnd) block(std::true_type{}, Hi{}, opB, pB, opA, pA, jb + 8);
+                bump();
+                jb += 16;
+            }
         }
         return;
     }
@@ -650,6 +681,12 @@ __device__ __forceinline__ void lms_pass(LmsShared<LPC> &sh, const V1Args &A, co
     if (!J.active && A.idleFast) {
         L.jlo = 0;
         L.jhi = 0x7fffffff;
+    }
+    // the steps at which every lane of the wave adapts, once per pass and in scalars: run_tile's unmasked stretch
+    int liveLo = 0, liveHi = 0;
+    if constexpr (LONE) {
+        liveLo = (int)wave_max((uint32_t)max(L.jlo, 0));
+        liveHi = (int)wave_min_u32((uint32_t)max(L.jhi, 0));
     }
     LaneView V;
     V.feeds = J.active && (T * L.h < J.na);
@@ -714,7 +751,7 @@ __device__ __forceinline__ void lms_pass(LmsShared<LPC> &sh, const V1Args &A, co
             lds_order();
         }
         const int jEnd = min(j0 + Geo<LPC>::TILE, (int)((runTo + 7) & ~7u));
-        run_tile<T, LPC, DEAD, LONE>(a, V, L, j0, jEnd, chanBits);
+        run_tile<T, LPC, DEAD, LONE>(a, V, L, j0, jEnd, chanBits, liveLo, liveHi);
         lds_order();
         if (store) {
             if (j0 == 0) {

@@ -1,9 +1,22 @@
 #!/usr/bin/env python3
-"""Basic-block instruction histogram of one kernel in a hipcc -S dump: tools/isa_blocks.py FILE.s KERNEL_SUBSTR [top]"""
+"""Basic-block instruction histogram of one kernel in a hipcc -S dump: tools/isa_blocks.py FILE.s KERNEL_SUBSTR [top [flow]]
+tools/isa_blocks.py FILE.s --sizes: the instruction count of every function of the dump (two builds: diff the two lists)"""
 import re, sys, collections
 path, key = sys.argv[1], sys.argv[2]
 top = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 lines = open(path).read().splitlines()
+if key == "--sizes":
+    name, cnt = None, 0
+    for l in lines:
+        if re.match(r"^_Z\w+:", l):
+            name, cnt = l.split(":")[0], 0
+        elif name and (l.startswith("\t.end_amdhsa_kernel") or l.startswith(".Lfunc_end")):
+            print(f"{cnt:7d}  {name}")
+            name = None
+        elif name:
+            t = l.strip()
+            cnt += bool(t) and not t.startswith((";", "."))
+    sys.exit(0)
 start = next(i for i, l in enumerate(lines) if l.startswith("_Z") and key in l and l.rstrip().endswith(("E", ":")) or (l.startswith("_Z") and key in l and ":" in l))
 end = next(i for i in range(start + 1, len(lines)) if lines[i].startswith("\t.end_amdhsa_kernel") or lines[i].startswith(".Lfunc_end"))
 blocks, cur, name = [], [], "entry"
