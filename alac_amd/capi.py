@@ -50,6 +50,12 @@ class FloatReport(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
+class IntReport(C.Structure):
+    """alac_hip_int_report: one per segment of alac_hip_int_probe, 32 bytes"""
+    _fields_ = [("out_of_range", C.c_uint64), ("differing_frames", C.c_uint64), ("need_bits", C.c_uint32), ("peak", C.c_uint32),
+                ("pad_bits", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class PcmDigest(C.Structure):
     """alac_hip_pcm_digest: one per range of alac_hip_pcm_crc32, 16 bytes"""
     _fields_ = [("bytes", C.c_uint64), ("crc32", C.c_uint32), ("reserved", C.c_uint32)]
@@ -135,6 +141,10 @@ SIGNATURES = {
     "alac_hip_float_probe": (_i32, [_vp, _vp, _u32, _u64, _u64, _u64, _vp, _u32, _vp, _u64, _vp]),
     "alac_hip_float_probe_host": (_i32, [_vp, _vp, _u32, _u64, _u64, _u64, _vp, _u32, _vp]),
     "alac_hip_float_report_depth": (_u32, [_vp]),
+    "alac_hip_int_probe_workspace_bytes": (_u64, [_u32]),
+    "alac_hip_int_probe": (_i32, [_vp, _vp, _vp, _u32, _u64, _vp, _u32, _vp, _u64, _vp]),
+    "alac_hip_int_probe_host": (_i32, [_vp, _vp, _vp, _u32, _u64, _vp, _u32, _vp]),
+    "alac_hip_int_report_depth": (_u32, [_vp]),
     "alac_hip_pcm_crc32_workspace_bytes": (_u64, [_u32]),
     "alac_hip_pcm_crc32": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp]),
     "alac_hip_pcm_crc32_host": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp]),
@@ -440,6 +450,26 @@ class Context:
                 num_samples.record_stream(cur)
             return bufs
 
+    def _int_tensor(self, what, x, channels, container_bytes, channel_stride, frame_stride):
+        """the tensor forms of an integer source of `channels` channels -> (container bytes, channel stride, frame stride,
+        frames), strides in containers"""
+        t = self.torch
+        if x.is_cuda and x.dtype in (t.int16, t.int32) and x.dim() == 2 and x.shape[0] == channels:
+            cb = 2 if x.dtype == t.int16 else 4
+            if container_bytes not in (None, cb) or channel_stride is not None or frame_stride is not None:
+                raise ValueError("%s: the container and the strides of an int16 / int32 tensor are the tensor's own" % what)
+            frames, cs, fst = int(x.shape[1]), int(x.stride(0)), int(x.stride(1))
+        elif x.is_cuda and x.dtype == t.uint8 and x.dim() == 1 and x.is_contiguous() and container_bytes == 3:
+            if channel_stride is None or frame_stride is None or frame_stride < 1:
+                raise ValueError("%s: packed 3-byte sources need channel_stride= and frame_stride=" % what)
+            cb, cs, fst = 3, int(channel_stride), int(frame_stride)
+            # the frames the bytes hold: the last channel's row ends inside x
+            frames = max(0, (x.numel() // 3 - (channels - 1) * cs - 1) // fst + 1) if x.numel() >= 3 else 0
+        else:
+            raise ValueError("%s: x must be an int16 / int32 cuda tensor [channels, frames], or a 1-D uint8 cuda tensor "
+                             "with container_bytes=3, channel_stride= and frame_stride=" % what)
+        return cb, cs, fst, frames
+
     def _int_source(self, what, fmt, x, bits, left_justified, container_bytes, channel_stride, frame_stride, dither,
                     seed, packet_origin, num_samples):
         """the checks and the alac_hip_int_source that requantize() and encode_int() share ->
@@ -450,20 +480,7 @@ class Context:
         if packet_origin is not None and not (packet_origin.is_cuda and packet_origin.dtype in (t.int64, t.uint64) and
                                               packet_origin.is_contiguous()):
             raise ValueError("%s: packet_origin must be a contiguous int64 / uint64 cuda tensor" % what)
-        if x.is_cuda and x.dtype in (t.int16, t.int32) and x.dim() == 2 and x.shape[0] == fmt.num_channels:
-            cb = 2 if x.dtype == t.int16 else 4
-            if container_bytes not in (None, cb) or channel_stride is not None or frame_stride is not None:
-                raise ValueError("%s: the container and the strides of an int16 / int32 tensor are the tensor's own" % what)
-            frames, cs, fst = int(x.shape[1]), int(x.stride(0)), int(x.stride(1))
-        elif x.is_cuda and x.dtype == t.uint8 and x.dim() == 1 and x.is_contiguous() and container_bytes == 3:
-            if channel_stride is None or frame_stride is None or frame_stride < 1:
-                raise ValueError("%s: packed 3-byte sources need channel_stride= and frame_stride=" % what)
-            cb, cs, fst = 3, int(channel_stride), int(frame_stride)
-            # the frames the bytes hold: the last channel's row ends inside x
-            frames = max(0, (x.numel() // 3 - (fmt.num_channels - 1) * cs - 1) // fst + 1) if x.numel() >= 3 else 0
-        else:
-            raise ValueError("%s: x must be an int16 / int32 cuda tensor [channels, frames], or a 1-D uint8 cuda tensor "
-                             "with container_bytes=3, channel_stride= and frame_stride=" % what)
+        cb, cs, fst, frames = self._int_tensor(what, x, fmt.num_channels, container_bytes, channel_stride, frame_stride)
         num_packets = (frames + fmt.frame_size - 1) // fmt.frame_size
         if num_samples is None and frames % fmt.frame_size:
             ns = [fmt.frame_size] * (num_packets - 1) + [frames % fmt.frame_size]
@@ -565,6 +582,49 @@ class Context:
         self.synchronize()
         rows = np.ascontiguousarray(reports.cpu().numpy())
         return [int(self.lib.alac_hip_float_report_depth(rows[s].ctypes.data)) for s in range(rows.shape[0])]
+
+    def probe_int(self, x, bits=None, left_justified=True, seg_first_frame=None, container_bytes=None, channel_stride=None,
+                  frame_stride=None, num_channels=None):
+        """alac_hip_int_probe: what names the lossless bit depth of integer PCM, per segment of frames.  x, bits,
+        left_justified and the packed 3-byte form as in requantize(); the channel count is the tensor's, and for a packed
+        3-byte source num_channels= (default: frame_stride where channel_stride is 1, the interleaved form; else 1).
+        seg_first_frame as in probe_float().  Returns an int32 cuda tensor [num_segments, 8] viewing the alac_hip_int_report
+        of every segment (words 0-1 out_of_range, 2-3 differing_frames, 4 need_bits, 5 peak, 6 pad_bits, 7 zero).  A tensor
+        without frames has only empty segments: reports of zeros.  Asynchronous."""
+        with self._call() as cur:
+            t = self.torch
+            if x.dim() == 2:
+                channels = int(x.shape[0])
+            elif num_channels is not None:
+                channels = int(num_channels)
+            else:
+                channels = int(frame_stride) if channel_stride == 1 and frame_stride else 1
+            cb, cs, fst, frames = self._int_tensor("probe_int", x, channels, container_bytes, channel_stride, frame_stride)
+            src = IntSource(cb, 8 * cb if bits is None else int(bits), 1 if left_justified else 0, 0, cs, fst)
+            table = None if seg_first_frame is None else np.ascontiguousarray(seg_first_frame, dtype=np.uint64)
+            if table is not None and (table.ndim != 1 or table.size < 1):
+                raise ValueError("probe_int: seg_first_frame must hold num_segments + 1 frame indices")
+            nseg = 1 if table is None else table.size - 1
+            reports = t.empty((nseg, 8), dtype=t.int32, device=self.device)
+            ws = self._workspace(int(self.lib.alac_hip_int_probe_workspace_bytes(nseg)))
+            # a tensor without frames has no address; the call wants one, and reads nothing through it
+            base = x if x.numel() else t.zeros(4, dtype=t.int32, device=self.device)
+            self._check(self.lib.alac_hip_int_probe(
+                self.h, base.data_ptr(), C.byref(src), channels, frames, None if table is None else table.ctypes.data, nseg,
+                ws.data_ptr(), ws.numel(), reports.data_ptr()))
+            reports.record_stream(cur)
+            return reports
+
+    def lossless_depth_int(self, x, bits=None, left_justified=True, seg_first_frame=None, container_bytes=None,
+                           channel_stride=None, frame_stride=None, num_channels=None):
+        """The smallest bit depth of 16, 20, 24, 32 to which requantize(x) / encode_int(x) reduce the source without
+        rounding or saturating anything, per segment (alac_hip_int_report_depth over probe_int's reports); 0 where a
+        container is out of range or a pad bit is set.  Synchronizes."""
+        reports = self.probe_int(x, bits, left_justified, seg_first_frame, container_bytes, channel_stride, frame_stride,
+                                 num_channels)
+        self.synchronize()
+        rows = np.ascontiguousarray(reports.cpu().numpy())
+        return [int(self.lib.alac_hip_int_report_depth(rows[s].ctypes.data)) for s in range(rows.shape[0])]
 
     def pcm_crc32_device(self, pcm, ranges=None):
         """alac_hip_pcm_crc32: zlib.crc32 of ranges of a uint8 cuda tensor, computed where it lies.  ranges: a sequence of

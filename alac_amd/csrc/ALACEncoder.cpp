@@ -58,6 +58,26 @@ int32_t ALACEncoder::ProbeFloat(const float *pcm, uint32_t numChannels, uint64_t
     return mLastStatus;
 }
 
+int32_t ALACEncoder::ProbeInt(const void *pcm, const alac_hip_int_source &src, uint32_t numChannels, uint64_t totalFrames,
+                              const uint64_t *segFirstFrame, uint32_t numSegments, alac_hip_int_report *reports)
+{
+    if ((mLastStatus = ensureContext())) return mLastStatus;
+    mLastStatus = alac_hip_int_probe_host(mCtx, pcm, &src, numChannels, totalFrames, segFirstFrame, numSegments, reports);
+    return mLastStatus;
+}
+
+int32_t ALACEncoder::RequantizeInt(const void *pcm, const alac_hip_int_source &src, uint32_t numChannels, uint32_t bitDepth,
+                                   uint32_t frameSize, const uint32_t *numSamples, uint32_t numPackets, uint8_t *out,
+                                   uint64_t outCapacity, uint32_t *clipped, uint32_t ditherMode, uint64_t ditherSeed)
+{
+    if ((mLastStatus = ensureContext())) return mLastStatus;
+    const alac_hip_format fmt = {frameSize, bitDepth, numChannels, 44100};  // (the sample rate plays no part in the conversion)
+    const alac_hip_dither dither = {ditherMode, 0, ditherSeed};
+    mLastStatus = alac_hip_pcm_requantize_host(mCtx, &fmt, pcm, &src, numSamples, numPackets, out, outCapacity, clipped, &dither,
+                                               nullptr);
+    return mLastStatus;
+}
+
 // codec/ALACEncoder.cu:1457-1535
 int32_t ALACEncoder::InitializeEncoder(AudioFormatDescription theOutputFormat, int /*X*/)
 {

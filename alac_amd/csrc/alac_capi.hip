@@ -1050,9 +1050,10 @@ int32_t alac_hip_encode_float_dither(alac_hip_ctx *ctx, const alac_hip_format *f
 }
 
 // ---- integer input of any layout, container and depth: requantize by the integer rule, then encode from the result ------
-// what is wrong with a call's integer source; `in` the device or host pointer.  After dither_refusal.
-static int32_t int_source_refusal(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *in, const alac_hip_int_source *src,
-                                  uint32_t num_packets, const alac_hip_dither *dither)
+// what is wrong with an integer source of `channels` channels and `frames` frames; `in` the device or host pointer.  What
+// alac_hip_pcm_requantize and alac_hip_int_probe both refuse.
+static int32_t int_source_struct_refusal(alac_hip_ctx *ctx, const void *in, const alac_hip_int_source *src, uint32_t channels,
+                                         uint64_t frames)
 {
     if (!in || !src) return fail(ctx, ALAC_HIP_ParamError, "null input or alac_hip_int_source");
     const uint32_t cb = src->container_bytes, S = src->bits;
@@ -1063,14 +1064,22 @@ static int32_t int_source_refusal(alac_hip_ctx *ctx, const alac_hip_format *fmt,
     if (src->left_justified > 1) return fail(ctx, ALAC_HIP_ParamError, "left_justified is not 0 or 1");
     if (cb != 3 && ((uintptr_t)in & (cb - 1))) return fail(ctx, ALAC_HIP_ParamError, "input not aligned to its container");
     if (src->frame_stride == 0) return fail(ctx, ALAC_HIP_ParamError, "frame_stride 0");
-    if (src->channel_stride == 0 && fmt->num_channels > 1)
+    if (src->channel_stride == 0 && channels > 1)
         return fail(ctx, ALAC_HIP_ParamError, "channel_stride 0 with more than one channel");
     uint64_t rows, cols, last;
-    if (__builtin_mul_overflow((uint64_t)(fmt->num_channels - 1), src->channel_stride, &rows) ||
-        __builtin_mul_overflow((uint64_t)num_packets * fmt->frame_size - 1, src->frame_stride, &cols) ||
-        __builtin_add_overflow(rows, cols, &last) || last >= UINT64_MAX / cb)
+    if (frames && (__builtin_mul_overflow((uint64_t)(channels - 1), src->channel_stride, &rows) ||
+                   __builtin_mul_overflow(frames - 1, src->frame_stride, &cols) || __builtin_add_overflow(rows, cols, &last) ||
+                   last >= UINT64_MAX / cb))
         return fail(ctx, ALAC_HIP_ParamError, "the largest index into the input overflows 64 bits");
-    if (dither_on(dither) && fmt->bit_depth >= S)
+    return ALAC_HIP_noErr;
+}
+
+// what is wrong with a conversion call's integer source.  After dither_refusal.
+static int32_t int_source_refusal(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *in, const alac_hip_int_source *src,
+                                  uint32_t num_packets, const alac_hip_dither *dither)
+{
+    if (int32_t rc = int_source_struct_refusal(ctx, in, src, fmt->num_channels, (uint64_t)num_packets * fmt->frame_size)) return rc;
+    if (dither_on(dither) && fmt->bit_depth >= src->bits)
         return fail(ctx, ALAC_HIP_ParamError, "dither where the target depth is not below the source's: nothing is rounded");
     return ALAC_HIP_noErr;
 }
@@ -1136,6 +1145,22 @@ uint64_t alac_hip_float_probe_workspace_bytes(uint32_t num_segments)
     return num_segments ? align_up(((uint64_t)num_segments + 1) * 8, 256) : 0;
 }
 
+// what a probe call refuses in its host segment table; [lo, hi): the frames the segments cover
+static int32_t probe_table_refusal(alac_hip_ctx *ctx, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                                   uint32_t num_segments, uint64_t &lo, uint64_t &hi)
+{
+    if (num_segments == 0) return fail(ctx, ALAC_HIP_ParamError, "num_segments 0");
+    lo = 0, hi = total_frames;
+    if (!h_seg_first_frame)
+        return num_segments == 1 ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "no segment table for more than one segment");
+    for (uint32_t s = 0; s < num_segments; s++)
+        if (h_seg_first_frame[s] > h_seg_first_frame[s + 1]) return fail(ctx, ALAC_HIP_ParamError, "segment table not ascending");
+    if (h_seg_first_frame[num_segments] > total_frames)
+        return fail(ctx, ALAC_HIP_ParamError, "segment table ends behind total_frames");
+    lo = h_seg_first_frame[0], hi = h_seg_first_frame[num_segments];
+    return ALAC_HIP_noErr;
+}
+
 // everything alac_hip_float_probe refuses that does not depend on where the buffers live; [lo, hi): the frames the segments
 // cover.  Device and host form.
 static int32_t float_probe_refusal(alac_hip_ctx *ctx, const float *in, uint32_t num_channels, uint64_t channel_stride,
@@ -1154,16 +1179,7 @@ static int32_t float_probe_refusal(alac_hip_ctx *ctx, const float *in, uint32_t 
          __builtin_mul_overflow(total_frames - 1, frame_stride, &cols) || __builtin_add_overflow(rows, cols, &last) ||
          last >= UINT64_MAX / sizeof(float)))
         return fail(ctx, ALAC_HIP_ParamError, "the largest index into the input overflows 64 bits");
-    if (num_segments == 0) return fail(ctx, ALAC_HIP_ParamError, "num_segments 0");
-    lo = 0, hi = total_frames;
-    if (!h_seg_first_frame)
-        return num_segments == 1 ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "no segment table for more than one segment");
-    for (uint32_t s = 0; s < num_segments; s++)
-        if (h_seg_first_frame[s] > h_seg_first_frame[s + 1]) return fail(ctx, ALAC_HIP_ParamError, "segment table not ascending");
-    if (h_seg_first_frame[num_segments] > total_frames)
-        return fail(ctx, ALAC_HIP_ParamError, "segment table ends behind total_frames");
-    lo = h_seg_first_frame[0], hi = h_seg_first_frame[num_segments];
-    return ALAC_HIP_noErr;
+    return probe_table_refusal(ctx, total_frames, h_seg_first_frame, num_segments, lo, hi);
 }
 
 // The segment table goes to the device through the context's pinned buffer: copied out of the caller's memory here, on the
@@ -1186,6 +1202,23 @@ static hipError_t upload_segment_table(alac_hip_ctx *ctx, const uint64_t *h_tabl
     return hipEventRecord(ctx->tabDone, ctx->stream);
 }
 
+// what a probe call refuses in its workspace and report pointer; then the device is selected and the table, if there is one,
+// is on its way into the workspace
+static int32_t probe_table_to_device(alac_hip_ctx *ctx, const uint64_t *h_seg_first_frame, uint32_t num_segments,
+                                     void *d_workspace, uint64_t workspace_bytes, const void *d_reports)
+{
+    if (!d_reports || ((uintptr_t)d_reports & 7)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned d_reports (8 B)");
+    if (workspace_bytes < alac_hip_float_probe_workspace_bytes(num_segments))
+        return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    if (h_seg_first_frame && (!d_workspace || ((uintptr_t)d_workspace & 7)))
+        return fail(ctx, ALAC_HIP_ParamError, "null or misaligned workspace (8 B)");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    hipError_t e;
+    if (h_seg_first_frame && (e = upload_segment_table(ctx, h_seg_first_frame, (uint64_t)num_segments + 1, d_workspace)))
+        return fail(ctx, ALAC_HIP_ParamError, "segment table upload", e);
+    return ALAC_HIP_noErr;
+}
+
 int32_t alac_hip_float_probe(alac_hip_ctx *ctx, const float *d_in, uint32_t num_channels, uint64_t channel_stride,
                              uint64_t frame_stride, uint64_t total_frames, const uint64_t *h_seg_first_frame,
                              uint32_t num_segments, void *d_workspace, uint64_t workspace_bytes,
@@ -1196,15 +1229,8 @@ int32_t alac_hip_float_probe(alac_hip_ctx *ctx, const float *d_in, uint32_t num_
     if (int32_t rc = float_probe_refusal(ctx, d_in, num_channels, channel_stride, frame_stride, total_frames, h_seg_first_frame,
                                          num_segments, lo, hi))
         return rc;
-    if (!d_reports || ((uintptr_t)d_reports & 7)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned d_reports (8 B)");
-    if (workspace_bytes < alac_hip_float_probe_workspace_bytes(num_segments))
-        return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
-    if (h_seg_first_frame && (!d_workspace || ((uintptr_t)d_workspace & 7)))
-        return fail(ctx, ALAC_HIP_ParamError, "null or misaligned workspace (8 B)");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    if (int32_t rc = probe_table_to_device(ctx, h_seg_first_frame, num_segments, d_workspace, workspace_bytes, d_reports)) return rc;
     hipError_t e;
-    if (h_seg_first_frame && (e = upload_segment_table(ctx, h_seg_first_frame, (uint64_t)num_segments + 1, d_workspace)))
-        return fail(ctx, ALAC_HIP_ParamError, "segment table upload", e);
     const FloatProbeArgs a{d_in, channel_stride, frame_stride, lo, hi, h_seg_first_frame ? (const uint64_t *)d_workspace : nullptr,
                            num_segments, num_channels, (uint32_t *)d_reports};
     if ((e = launch_float_probe(a, ctx->stream))) return fail(ctx, ALAC_HIP_ParamError, "float probe launch", e);
@@ -1214,6 +1240,44 @@ int32_t alac_hip_float_probe(alac_hip_ctx *ctx, const float *d_in, uint32_t num_
 uint32_t alac_hip_float_report_depth(const alac_hip_float_report *r)
 {
     if (!r || r->nan || r->over_range || r->need_bits > 32) return 0;
+    return r->need_bits <= 16 ? 16 : r->need_bits <= 20 ? 20 : r->need_bits <= 24 ? 24 : 32;
+}
+
+// ---- integer probe: the lossless bit depth of integer PCM, per segment of frames ------------------------------------------
+uint64_t alac_hip_int_probe_workspace_bytes(uint32_t num_segments)
+{
+    return alac_hip_float_probe_workspace_bytes(num_segments);  // the same table
+}
+
+// everything alac_hip_int_probe refuses that does not depend on where the buffers live.  Device and host form.
+static int32_t int_probe_refusal(alac_hip_ctx *ctx, const void *in, const alac_hip_int_source *src, uint32_t num_channels,
+                                 uint64_t total_frames, const uint64_t *h_seg_first_frame, uint32_t num_segments, uint64_t &lo,
+                                 uint64_t &hi)
+{
+    if (num_channels < 1 || num_channels > kMaxChannels) return fail(ctx, ALAC_HIP_ParamError, "num_channels outside 1..8");
+    if (int32_t rc = int_source_struct_refusal(ctx, in, src, num_channels, total_frames)) return rc;
+    return probe_table_refusal(ctx, total_frames, h_seg_first_frame, num_segments, lo, hi);
+}
+
+int32_t alac_hip_int_probe(alac_hip_ctx *ctx, const void *d_in, const alac_hip_int_source *src, uint32_t num_channels,
+                           uint64_t total_frames, const uint64_t *h_seg_first_frame, uint32_t num_segments, void *d_workspace,
+                           uint64_t workspace_bytes, alac_hip_int_report *d_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = int_probe_refusal(ctx, d_in, src, num_channels, total_frames, h_seg_first_frame, num_segments, lo, hi))
+        return rc;
+    if (int32_t rc = probe_table_to_device(ctx, h_seg_first_frame, num_segments, d_workspace, workspace_bytes, d_reports)) return rc;
+    const IntProbeArgs a{d_in, src->channel_stride, src->frame_stride, lo, hi,
+                         h_seg_first_frame ? (const uint64_t *)d_workspace : nullptr, num_segments, num_channels,
+                         src->container_bytes, src->bits, src->left_justified, (uint32_t *)d_reports};
+    if (hipError_t e = launch_int_probe(a, ctx->stream)) return fail(ctx, ALAC_HIP_ParamError, "integer probe launch", e);
+    return ALAC_HIP_noErr;
+}
+
+uint32_t alac_hip_int_report_depth(const alac_hip_int_report *r)
+{
+    if (!r || r->out_of_range || r->pad_bits) return 0;
     return r->need_bits <= 16 ? 16 : r->need_bits <= 20 ? 20 : r->need_bits <= 24 ? 24 : 32;
 }
 
@@ -1972,6 +2036,35 @@ int32_t alac_hip_float_probe_host(alac_hip_ctx *ctx, const float *h_in, uint32_t
         return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
     if (int32_t rc = alac_hip_float_probe(ctx, (const float *)dIn.p, num_channels, channel_stride, frame_stride, total_frames,
                                           h_seg_first_frame, num_segments, dWs.p, wsBytes, (alac_hip_float_report *)dRep.p))
+        return rc;
+    if ((e = hipMemcpyAsync(h_reports, dRep.p, repBytes, hipMemcpyDeviceToHost, ctx->stream)) ||
+        (e = hipStreamSynchronize(ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
+    return ALAC_HIP_noErr;
+}
+
+int32_t alac_hip_int_probe_host(alac_hip_ctx *ctx, const void *h_in, const alac_hip_int_source *src, uint32_t num_channels,
+                                uint64_t total_frames, const uint64_t *h_seg_first_frame, uint32_t num_segments,
+                                alac_hip_int_report *h_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = int_probe_refusal(ctx, h_in, src, num_channels, total_frames, h_seg_first_frame, num_segments, lo, hi))
+        return rc;
+    if (!h_reports) return fail(ctx, ALAC_HIP_ParamError, "null h_reports");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    // the containers the call may read lie in [0, span) of h_in: up to the last frame of the last segment
+    const uint64_t span = hi > lo ? (num_channels - 1) * src->channel_stride + (hi - 1) * src->frame_stride + 1 : 0;
+    const uint64_t spanBytes = span * src->container_bytes;
+    const uint64_t wsBytes = alac_hip_int_probe_workspace_bytes(num_segments), repBytes = (uint64_t)num_segments * 32;
+    DevBuf dIn, dWs, dRep;
+    hipError_t e;
+    if ((e = dIn.alloc(spanBytes)) || (e = dWs.alloc(wsBytes)) || (e = dRep.alloc(repBytes)))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if (spanBytes && (e = hipMemcpyAsync(dIn.p, h_in, spanBytes, hipMemcpyHostToDevice, ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    if (int32_t rc = alac_hip_int_probe(ctx, dIn.p, src, num_channels, total_frames, h_seg_first_frame, num_segments, dWs.p,
+                                        wsBytes, (alac_hip_int_report *)dRep.p))
         return rc;
     if ((e = hipMemcpyAsync(h_reports, dRep.p, repBytes, hipMemcpyDeviceToHost, ctx->stream)) ||
         (e = hipStreamSynchronize(ctx->stream)))

@@ -3,6 +3,7 @@
 // the peak).  Reads what k_float_to_pcm (alac_float_in.hip) reads, in its three layouts, and writes only the reports.
 #include "alac_dev.hpp"
 #include "alac_kernels.hpp"
+#include "alac_probe_seg.hpp"
 
 namespace alacdev {
 
@@ -35,19 +36,6 @@ __device__ __forceinline__ void probe_merge(ProbeAcc &a, const ProbeAcc &b)
     a.nan += b.nan;
 }
 
-// the segment of frame f, first[0] <= f < first[n]: the largest s with first[s] <= f (empty segments in front of it are
-// passed over, and first[s + 1] > f)
-__device__ __forceinline__ uint32_t probe_segment(const uint64_t *first, uint32_t n, uint64_t f)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (first[mid] <= f) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // adds to one report (8 words: alac_hip_float_report); a field that would not move is not sent
 __device__ __forceinline__ void probe_add(uint32_t *report, uint32_t need, uint32_t peak, uint64_t over, uint64_t nan)
 {
@@ -71,8 +59,6 @@ __device__ __forceinline__ void probe_wave_reduce(const ProbeAcc &a, uint32_t &n
         nan += __shfl_xor((unsigned long long)nan, m);
     }
 }
-
-constexpr uint32_t kProbeNoSegment = 0xffffffffu;
 
 // One lane: the 4 consecutive frames [f0, f0 + 4) of every channel, f0 a multiple of 4; a wave: 256 consecutive frames; a
 // block: 1 024; a grid-stride loop over the blocks that cover [lo & ~3, hi).  CH: 1 or 2 (the vector layouts: aligned
@@ -184,13 +170,6 @@ __global__ __launch_bounds__(256) void k_float_probe(FloatProbeArgs a)
         if (seg != kProbeNoSegment) probe_add(a.reports + 8ull * seg, need, peak, over, nan);
     }
 }
-
-// blocks of a launch: few enough that the closing atomics of a one-segment call (two words of one report) stay a small
-// part of the pass.  Not tuned, and a value to revisit: 1 024 blocks are 4 waves per SIMD, which streams 4.1 GB from HBM
-// faster than k_float_to_pcm does but has too little in flight for a pass that lies in the Infinity Cache (328 MB: 88 us
-// against 75 us); 2 048 (8 waves per SIMD, what the registers allow) is the value to try.  The
-// tests' PASS constant (tests/test_gpu_float_probe.py) is 1 024 times this.
-constexpr uint32_t kProbeMaxBlocks = 1024;
 
 hipError_t launch_float_probe(const FloatProbeArgs &a, hipStream_t st)
 {

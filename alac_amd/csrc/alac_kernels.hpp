@@ -391,6 +391,21 @@ struct FloatProbeArgs {
 // zeroes the reports, then (hi > lo) the pass
 hipError_t launch_float_probe(const FloatProbeArgs &a, hipStream_t st);
 
+// ---- integer probe (alac_int_probe.hip): alac_hip_int_probe's one pass over the containers ----
+// the container of channel c and frame t is at index c * channelStride + t * frameStride of in (containers as in PcmInArgs);
+// segments, [lo, hi) and reports (8 uint32 per segment: alac_hip_int_report) as in FloatProbeArgs
+struct IntProbeArgs {
+    const void *in;
+    uint64_t channelStride, frameStride;
+    uint64_t lo, hi;
+    const uint64_t *segFirst;  // nullable
+    uint32_t numSegments, channels;
+    uint32_t containerBytes, srcBits, leftJustified;
+    uint32_t *reports;
+};
+// zeroes the reports, then (hi > lo) the pass
+hipError_t launch_int_probe(const IntProbeArgs &a, hipStream_t st);
+
 // ---- CRC-32 of PCM (alac_pcm_crc.hip): alac_hip_pcm_crc32's one pass over the bytes ----
 // range s = bytes [ranges[2s], ranges[2s] + ranges[2s + 1]) of pcm adds to digests[4s ..] (alac_hip_pcm_digest).  ranges:
 // device table, ascending and non-overlapping inside [lo, hi), lo = ranges[0], hi = the last range's end (the host checks);

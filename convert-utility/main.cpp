@@ -58,6 +58,20 @@
  *                                             (decimal or 0x-hex, default 0: two runs give the same file).  Every file's
  *                                             frames count from 0, so a file's output is the same alone, in --batch and
  *                                             with --devices N
+ *   --bits N [--dither [--dither-seed S]]     encode only, N = 16, 20, 24 or 32: the integer PCM inputs (WAV, PCM CAF) are converted
+ *                                             to N bits on the GPU by the integer rule of alac_hip.h (alac_hip_pcm_requantize_host:
+ *                                             widened exactly, or reduced with round half to even and, with --dither, TPDF dither;
+ *                                             every file's frames count from 0) and encoded as files of N bits.  The source of a
+ *                                             file: containers of its bytes per sample, its depth significant, a 20-bit file
+ *                                             left-justified in 3 bytes.  The output is the file an integer input holding the
+ *                                             converted samples gives; a clip count is a warning on stderr; --verify checks
+ *                                             against the converted PCM.  --dither needs N below every input's depth.  ALAC and
+ *                                             float inputs, --float-bits, --compare, --crc and --crc-check are refused
+ *   --bits auto                               as --bits N, with N chosen per file: the smallest of 16, 20, 24, 32 that holds the
+ *                                             file's samples exactly (alac_hip_int_probe: one call per depth and channel count, one
+ *                                             segment per file), printed per file, with "channels identical" for a stereo file
+ *                                             whose channels are.  A 24-bit file of 16-bit samples comes out as the 16-bit
+ *                                             file.  Not with --dither
  *   --crc <file> [<file> ...]                 print one line per file, "%08x  <frames>  <path>": the CRC-32 (zlib's) of the file's
  *                                             PCM and its sample-frames, and write nothing.  The PCM is what decoding gives, in
  *                                             the layout of the `data` chunk of the WAV `alacconvert <file> out.wav` writes:
@@ -107,6 +121,10 @@ struct Job {
     // --float-bits: info describes the integer file of the quantized samples; the floats are at floatPos in `file`
     bool floatIn = false, floatBigEndian = false;
     uint64_t floatPos = 0;
+    // --bits: info describes the integer file of the converted samples; the source's containers, srcBits deep, are at srcPos
+    bool intConv = false, srcBigEndian = false;
+    uint32_t srcBits = 0;
+    uint64_t srcPos = 0, srcFrames = 0;
     // --crc / --crc-check: done only if the file could be hashed
     bool opened = false, done = false;
     uint32_t crc = 0;
@@ -169,6 +187,21 @@ void stage_floats(const Job &J, uint64_t frames, float *dst)
     const uint64_t bytes = frames * J.info.channels * sizeof(float);
     memcpy(dst, J.file.data() + J.floatPos, (size_t)bytes);
     if (J.floatBigEndian) alacfile::swap_samples_in_place((uint8_t *)dst, bytes, 32);
+}
+
+// how the containers of a --bits input lie once staged: interleaved, the file's bytes per sample each, its depth significant
+// (a 20-bit file is left-justified in 3 bytes; the other depths fill their containers)
+alac_hip_int_source int_source_of(const Job &J)
+{
+    return alac_hip_int_source{bytes_per_sample(J.srcBits), J.srcBits, 1, 0, 1, J.info.channels};
+}
+
+// the payload of a --bits input, `frames` interleaved frames of it, little-endian
+void stage_source(const Job &J, uint64_t frames, uint8_t *dst)
+{
+    const uint64_t bytes = frames * J.info.channels * bytes_per_sample(J.srcBits);
+    memcpy(dst, J.file.data() + J.srcPos, (size_t)bytes);
+    if (J.srcBigEndian) alacfile::swap_samples_in_place(dst, bytes, J.srcBits);
 }
 
 // the packets of an ALAC file back to back
@@ -309,6 +342,49 @@ bool probe_float_jobs(std::vector<Job> &jobs, int device)
     return ok;
 }
 
+// --bits auto: every integer job gets the smallest depth that holds its samples exactly, found on the GPU
+// (alac_hip_int_probe: one call per source depth and channel count, one segment per file), and is from then on a file of that
+// depth.  A file without such a depth (a 20-bit file with bits set under its samples) is named; the run is then refused.
+bool probe_int_jobs(std::vector<Job> &jobs, int device)
+{
+    std::map<std::pair<uint32_t, uint32_t>, std::vector<Job *> > bySource;  // (depth, channels); the container follows the depth
+    for (size_t j = 0; j < jobs.size(); j++) bySource[std::make_pair(jobs[j].srcBits, jobs[j].info.channels)].push_back(&jobs[j]);
+    ALACEncoder enc;
+    if (device >= 0) enc.SetDevice(device);
+    bool ok = true;
+    for (auto g = bySource.begin(); g != bySource.end(); ++g) {
+        const uint32_t ch = g->first.second, frameBytes = ch * bytes_per_sample(g->first.first);
+        std::vector<Job *> &v = g->second;
+        std::vector<uint64_t> first(1, 0);  // the files' frames back to back
+        for (size_t j = 0; j < v.size(); j++) first.push_back(first.back() + v[j]->srcFrames);
+        Bytes pcm((size_t)(first.back() * frameBytes) + 4, 0);
+        for (size_t j = 0; j < v.size(); j++) stage_source(*v[j], v[j]->srcFrames, pcm.data() + (size_t)first[j] * frameBytes);
+        std::vector<alac_hip_int_report> reports(v.size());
+        const int32_t rc = enc.ProbeInt(pcm.data(), int_source_of(*v[0]), ch, first.back(), first.data(), (uint32_t)v.size(),
+                                        reports.data());
+        if (rc != ALAC_noErr) {
+            fprintf(stderr, " Probing the integer input failed (status %d)\n", rc);
+            return false;
+        }
+        for (size_t j = 0; j < v.size(); j++) {
+            Job &J = *v[j];
+            const alac_hip_int_report &r = reports[j];
+            const uint32_t depth = alac_hip_int_report_depth(&r);
+            if (depth == 0) {
+                fprintf(stderr, " --bits auto: no lossless bit depth (pad_bits 0x%x, out_of_range %llu): \"%s\"\n", r.pad_bits,
+                        (unsigned long long)r.out_of_range, J.in.c_str());
+                ok = false;
+                continue;
+            }
+            const bool dualMono = ch == 2 && J.srcFrames && r.differing_frames == 0;
+            printf("Integer input is lossless at %u bits%s: %s\n", depth, dualMono ? ", channels identical" : "", J.in.c_str());
+            J.info.bitsPerChannel = depth;
+            J.info.dataSize = J.srcFrames * frame_bytes(J.info);
+        }
+    }
+    return ok;
+}
+
 // ---- encode: all jobs share bit depth and channel count; each file is one segment ----
 bool encode_group(std::vector<Job *> &jobs, const Options &o, int device)
 {
@@ -373,8 +449,29 @@ bool encode_group(std::vector<Job *> &jobs, const Options &o, int device)
         for (size_t j = 0; j < jobs.size(); j++) {
             const Job &J = *jobs[j];
             uint8_t *dst = pcm.data() + (size_t)firstPacket[j] * packetBytes;
-            memcpy(dst, J.file.data() + J.info.dataPos, (size_t)J.info.dataSize);
-            if (J.info.bigEndianPcm) alacfile::swap_samples_in_place(dst, J.info.dataSize, J.info.bitsPerChannel);
+            const uint32_t mine = firstPacket[j + 1] - firstPacket[j];
+            if (J.intConv && mine) {
+                // --bits: the file's own containers through the integer rule into its packets; its frames count from 0
+                Bytes src((size_t)(J.srcFrames * ch * bytes_per_sample(J.srcBits)));
+                stage_source(J, J.srcFrames, src.data());
+                std::vector<uint32_t> clipped(mine, 0);
+                const int32_t rc = enc.RequantizeInt(src.data(), int_source_of(J), ch, first.bitsPerChannel, frame,
+                                                     numSamples.data() + firstPacket[j], mine, dst, (uint64_t)mine * packetBytes,
+                                                     clipped.data(), o.dither.on ? ALAC_HIP_DITHER_TPDF : ALAC_HIP_DITHER_NONE,
+                                                     o.dither.seed);
+                if (rc != ALAC_noErr) {
+                    fprintf(stderr, " Converting to %u bits failed (status %d): \"%s\"\n", first.bitsPerChannel, rc, J.in.c_str());
+                    return false;
+                }
+                uint64_t clips = 0;
+                for (uint32_t p = 0; p < mine; p++) clips += clipped[p];
+                if (clips)
+                    fprintf(stderr, " Warning: %llu samples clipped to %u bits: \"%s\"\n", (unsigned long long)clips,
+                            first.bitsPerChannel, J.in.c_str());
+            } else if (!J.intConv) {
+                memcpy(dst, J.file.data() + J.info.dataPos, (size_t)J.info.dataSize);
+                if (J.info.bigEndianPcm) alacfile::swap_samples_in_place(dst, J.info.dataSize, J.info.bitsPerChannel);
+            }
         }
         if (!encoded(enc.EncodeSegments(pcm.data(), numSamples.data(), np, segs.data(), (uint32_t)segs.size() - 1, stream.data(),
                                         stream.size(), sizes.data(), &total)))
@@ -734,7 +831,7 @@ int convert(const Options &o)
         if (!read_job(J)) return 1;
         printf("Input file: %s\n", J.in.c_str());
         printf("Output file: %s\n", J.out.c_str());
-        if (refused(alacfile::sniff_input(J.file, J.info, o.floatInput()), J)) return 1;
+        if (refused(alacfile::sniff_input(J.file, J.info, o.floatInput() || o.intConvert()), J)) return 1;
         if (o.floatInput()) {
             if (!J.info.isFloat) {
                 fprintf(stderr, " --float-bits takes float PCM input, not integer PCM or ALAC: \"%s\"\n", J.in.c_str());
@@ -756,8 +853,30 @@ int convert(const Options &o)
             J.info.dataSize = frames * frame_bytes(J.info);
         }
         if (!J.info.isAlac && !pcm_format_ok(J)) return 1;
+        if (o.intConvert()) {
+            if (J.info.isAlac || J.info.isFloat) {
+                fprintf(stderr, " --bits takes integer PCM input, not float PCM or ALAC: \"%s\"\n", J.in.c_str());
+                return 1;
+            }
+            if (o.dither.on && o.intBits >= J.info.bitsPerChannel) {
+                fprintf(stderr, " --dither with --bits %u would round nothing in a %u-bit file: \"%s\"\n", o.intBits,
+                        J.info.bitsPerChannel, J.in.c_str());
+                return 1;
+            }
+            // from here on the file is the integer file of its converted samples; the containers stay where they are
+            J.intConv = true;
+            J.srcBits = J.info.bitsPerChannel;
+            J.srcPos = J.info.dataPos;
+            J.srcBigEndian = J.info.bigEndianPcm;
+            J.srcFrames = J.info.dataSize / frame_bytes(J.info);
+            J.info.bigEndianPcm = false;
+            // (auto: the file's own depth until probe_int_jobs below has its lossless one)
+            if (!o.intAuto) J.info.bitsPerChannel = o.intBits;
+            J.info.dataSize = J.srcFrames * frame_bytes(J.info);
+        }
     }
     if (o.floatAuto && !probe_float_jobs(jobs, o.devices ? 0 : -1)) return 1;
+    if (o.intAuto && !probe_int_jobs(jobs, o.devices ? 0 : -1)) return 1;
 
     // group: encode jobs by (depth, channels); decode jobs by cookie
     Groups groups;

@@ -32,6 +32,11 @@ struct Options {
     bool floatAuto = false;  // --float-bits auto: floatBits stays 0, every file gets its own depth from the probe
     DitherOption dither;
     bool floatInput() const { return floatBits != 0 || floatAuto; }
+    // --bits N / --bits auto: integer PCM inputs are converted to N bits (auto: every file to its own lossless depth, intBits
+    // stays 0) in front of the encode; bitsNamed: the command line names --bits, whatever came of it
+    uint32_t intBits = 0;
+    bool intAuto = false, bitsNamed = false;
+    bool intConvert() const { return intBits != 0 || intAuto; }
 };
 
 inline void usage()
@@ -62,6 +67,17 @@ inline void usage()
     printf("        alacconvert --crc [--devices N] <wav, caf or m4a file> ...\n");
     printf("            (one line per file: CRC-32 of its PCM, sample-frames, path; ALAC is decoded and hashed on the GPU)\n");
     printf("        alacconvert --crc-check [--devices N] <list written by --crc>\n");
+    printf("\n");
+}
+
+// the lines of --bits, printed behind usage() where the command line names --bits (usage() itself prints what it always has)
+inline void usage_bits()
+{
+    printf("        alacconvert --bits N [--dither [--dither-seed S]] [--batch] [--lpc] [--verify] ... <input wav or caf file> <output caf or m4a file> ...\n");
+    printf("            (integer PCM inputs converted to N = 16, 20, 24 or 32 bits on the GPU by the integer rule: widened exactly, or\n");
+    printf("             reduced with round half to even and, with --dither, TPDF dither; --verify checks against the converted PCM)\n");
+    printf("        alacconvert --bits auto [--batch] [--lpc] [--verify] ... <input wav or caf file> <output caf or m4a file> ...\n");
+    printf("            (every file at the smallest of 16, 20, 24, 32 bits that holds its samples exactly, probed on the GPU; no --dither)\n");
     printf("\n");
 }
 
@@ -96,6 +112,18 @@ inline bool parse_args(int argc, char **argv, Options &o)
             o.floatAuto = std::string(argv[++i]) == "auto";
             o.floatBits = o.floatAuto ? 0 : (uint32_t)strtoul(argv[i], nullptr, 10);
             malformed = !o.floatAuto && !pcm_depth_ok(o.floatBits);
+        } else if (a == "--bits") {
+            o.bitsNamed = true;
+            if (!more) {
+                malformed = true;
+                continue;
+            }
+            o.intAuto = std::string(argv[++i]) == "auto";
+            o.intBits = o.intAuto ? 0 : (uint32_t)strtoul(argv[i], nullptr, 10);
+            if (!o.intAuto && !pcm_depth_ok(o.intBits)) {
+                fprintf(stderr, " --bits takes 16, 20, 24, 32 or auto, not \"%s\"\n", argv[i]);
+                return false;
+            }
         } else if (a == "--dither") {
             o.dither.on = true;
         } else if (a == "--dither-seed" && more) {
@@ -114,8 +142,13 @@ inline bool parse_args(int argc, char **argv, Options &o)
     }
     const size_t n = o.files.size();
     const bool crcMode = o.crc || !o.crcList.empty();
+    if (!malformed && o.bitsNamed && (o.floatInput() || o.compare || crcMode)) {
+        fprintf(stderr, " --bits converts integer PCM in front of an encode: not with %s\n",
+                o.floatInput() ? "--float-bits" : o.compare ? "--compare" : o.crc ? "--crc" : "--crc-check");
+        return false;
+    }
     // neither --crc / --crc-check nor --compare goes with one of these
-    const bool converting = o.batch || o.lpc || o.verify || o.verifySource || o.segmentPackets || o.floatInput();
+    const bool converting = o.batch || o.lpc || o.verify || o.verifySource || o.segmentPackets || o.floatInput() || o.intConvert();
     if (crcMode) {
         // --crc and --crc-check stand alone (but --devices N): any number of inputs resp. one list, no output files
         malformed = malformed || converting || o.compare || o.dither.on || (o.crc && !o.crcList.empty()) || (o.crc ? n == 0 : n != 0);
@@ -128,10 +161,21 @@ inline bool parse_args(int argc, char **argv, Options &o)
     malformed = malformed || (o.compare && (converting || o.devices));
     if (malformed) {
         usage();
+        if (o.bitsNamed) usage_bits();
         return false;
     }
     if (crcMode || o.compare) return true;
-    if (o.dither.on && (o.floatBits == 0 || o.floatBits == 32)) {  // auto promises lossless: no dither there
+    if (o.dither.on && o.intConvert() && (o.intAuto || o.intBits == 32)) {  // auto promises lossless: no dither there
+        fprintf(stderr, " --dither needs --bits 16, 20 or 24\n");
+        usage();
+        usage_bits();
+        return false;
+    }
+    if (o.intConvert() && o.verifySource) {
+        fprintf(stderr, " --verify-source needs float input (--float-bits N); with --bits, --verify checks against the converted PCM\n");
+        return false;
+    }
+    if (o.dither.on && !o.intConvert() && (o.floatBits == 0 || o.floatBits == 32)) {  // auto promises lossless: no dither there
         fprintf(stderr, " --dither needs --float-bits 16, 20 or 24\n");
         usage();
         return false;

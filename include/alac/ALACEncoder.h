@@ -14,6 +14,7 @@
 
 struct alac_hip_ctx;
 struct alac_hip_float_report;
+struct alac_hip_int_report;
 struct alac_hip_int_source;
 
 class ALACEncoder {
@@ -94,6 +95,21 @@ public:
     int32_t ProbeFloat(const float *pcm, uint32_t numChannels, uint64_t channelStride, uint64_t frameStride,
                        uint64_t totalFrames, const uint64_t *segFirstFrame, uint32_t numSegments,
                        alac_hip_float_report *reports);
+
+    /* Extension: what names the lossless bit depth of integer PCM (alac_hip_int_probe_host): src describes the containers of
+     * pcm as for EncodeSegmentsInt, the container of channel c and frame t at index c * src.channel_stride + t *
+     * src.frame_stride; segments and reports as in ProbeFloat, the reports read by alac_hip_int_report_depth.  Needs no
+     * InitializeEncoder. */
+    int32_t ProbeInt(const void *pcm, const alac_hip_int_source &src, uint32_t numChannels, uint64_t totalFrames,
+                     const uint64_t *segFirstFrame, uint32_t numSegments, alac_hip_int_report *reports);
+    /* Extension: the conversion of EncodeSegmentsInt alone (alac_hip_pcm_requantize_host): numPackets packets of frameSize
+     * frames of the source, packet p holding numSamples[p] of them (NULL: all full), into packed interleaved PCM of bitDepth
+     * bits in out (numPackets full packets; frames behind numSamples[p] are zero).  dither: ALAC_HIP_DITHER_TPDF where the depth
+     * is reduced; the packets' frames count from 0.  clipped: [numPackets] clipped samples per packet, or NULL.  Needs no
+     * InitializeEncoder: the format is the call's. */
+    int32_t RequantizeInt(const void *pcm, const alac_hip_int_source &src, uint32_t numChannels, uint32_t bitDepth,
+                          uint32_t frameSize, const uint32_t *numSamples, uint32_t numPackets, uint8_t *out,
+                          uint64_t outCapacity, uint32_t *clipped, uint32_t ditherMode, uint64_t ditherSeed);
 
     int32_t LastStatus() const { return mLastStatus; }
 

@@ -589,6 +589,58 @@ int32_t alac_hip_float_probe_host(alac_hip_ctx *ctx, const float *h_in, uint32_t
  * segment: 16); 0 when none does (nan != 0, over_range != 0 or need_bits > 32) or r is NULL. */
 uint32_t alac_hip_float_report_depth(const alac_hip_float_report *r);
 
+/* ---- probe integer PCM for its lossless bit depth -------------------------------------------------------------------------
+ * ALAC has no wasted-bits field: 16-bit audio delivered in 24-bit containers pays for the zero byte in every packet, and the
+ * only remedy is to encode the stream at the depth its samples really have.  This call finds, per segment of frames, what
+ * alac_hip_int_report_depth needs to name the smallest depth in {16, 20, 24, 32} to which alac_hip_pcm_requantize /
+ * alac_hip_encode_int reduce the source without rounding or saturating anything: one streaming pass over the containers that
+ * writes nothing but the reports.  The integer counterpart of alac_hip_float_probe.  No reference counterpart.
+ * The source is an alac_hip_int_source, read exactly as alac_hip_pcm_requantize reads it; the container of channel c and
+ * frame t is at index c * channel_stride + t * frame_stride (alac_hip_float_probe's indexing, t = p * frame_size + i: there is
+ * no packet structure).  The rule, per sign-extended container v, with S = bits and P = 8 * container_bytes - S:
+ *     left_justified = 1:  s = v >> P (arithmetic),  pad = v & (2^P - 1)
+ *     left_justified = 0:  s = clamp(v, -2^(S-1), 2^(S-1) - 1),  pad = 0;  the container is out of range when v != s
+ *     need(s) = 0                  if s == 0
+ *               S - ctz(s)         otherwise          (1 for -2^(S-1), S for an odd sample)
+ *   s = r << (S - b) for an integer r exactly when need(s) <= b, so alac_hip_pcm_requantize to a depth b < S has remainder 0
+ *   and rounds nothing (and b >= S is exact anyway).  For S <= 24 need(s) is alac_hip_float_probe's need(x) on
+ *   x = s * 2^-(S-1); s = -2^(S-1) gives 1, as -1.0 does.
+ *   d_in, src         as in alac_hip_pcm_requantize.  The same vector layouts for 1 and 2 channels: planar and interleaved
+ *                     int32 with 16-byte loads (16-byte aligned d_in, planar channel_stride a multiple of 4), planar and
+ *                     interleaved int16 with 8-byte loads (8-byte aligned), interleaved and mono packed 3-byte with 4-byte
+ *                     loads (4-byte aligned).  Everything else takes one load per sample.
+ *   h_seg_first_frame, d_workspace (alac_hip_int_probe_workspace_bytes), d_reports: as in alac_hip_float_probe, table
+ *                     semantics included (ascending, may start behind frame 0 and end before total_frames, empty segments
+ *                     allowed, copied out before the call returns, NULL with num_segments 1: all frames).  Frames outside
+ *                     every segment are not read.  Every word of every report is written by every call.
+ * Asynchronous on the context's stream.  kALAC_ParamError, with nothing enqueued and nothing written: everything
+ * alac_hip_pcm_requantize refuses in a source (null d_in or src; container_bytes not 2, 3 or 4; bits not 16, 20, 24 or 32, or
+ * above 8 * container_bytes; reserved != 0; left_justified > 1; d_in not aligned to a 2- or 4-byte container; frame_stride 0;
+ * channel_stride 0 with more than one channel; a largest index whose byte offset overflows 64 bits) and everything
+ * alac_hip_float_probe refuses in num_channels (outside 1..8), the table, the workspace and d_reports.
+ */
+typedef struct alac_hip_int_report { /* one per segment, 32 bytes */
+    uint64_t out_of_range;     /* right-justified containers outside [-2^(S-1), 2^(S-1)); 0 when left-justified */
+    uint64_t differing_frames; /* frames in which some channel's s differs from channel 0's; 0 for one channel.  0 on a stereo
+                                  segment: dual mono */
+    uint32_t need_bits;        /* max need(s); 0 for an empty or all-zero segment */
+    uint32_t peak;             /* max |s| after saturation (up to 2^(S-1)) */
+    uint32_t pad_bits;         /* OR of pad over the segment (left-justified); 0 when right-justified */
+    uint32_t reserved;         /* written as 0 */
+} alac_hip_int_report;
+uint64_t alac_hip_int_probe_workspace_bytes(uint32_t num_segments);
+int32_t alac_hip_int_probe(alac_hip_ctx *ctx, const void *d_in, const alac_hip_int_source *src, uint32_t num_channels,
+                           uint64_t total_frames, const uint64_t *h_seg_first_frame, uint32_t num_segments,
+                           void *d_workspace, uint64_t workspace_bytes, alac_hip_int_report *d_reports);
+/* Host-buffer form (synchronous): h_in in the layout above; only the containers up to the last frame of the last segment are
+ * staged to the device, the reports come back in h_reports [num_segments]. */
+int32_t alac_hip_int_probe_host(alac_hip_ctx *ctx, const void *h_in, const alac_hip_int_source *src, uint32_t num_channels,
+                                uint64_t total_frames, const uint64_t *h_seg_first_frame, uint32_t num_segments,
+                                alac_hip_int_report *h_reports);
+/* Host only: the smallest depth of 16, 20, 24, 32 that is >= need_bits (an empty or all-zero segment: 16); 0 when r is NULL,
+ * out_of_range != 0 or pad_bits != 0 (the declared S loses bits, or the encode would saturate). */
+uint32_t alac_hip_int_report_depth(const alac_hip_int_report *r);
+
 /* ---- CRC-32 of PCM: the fingerprint of a decode, computed where the PCM lies -----------------------------------------------
  * ALAC carries no digest of its PCM.  This call gives one for PCM in device memory — the output of alac_hip_decode — so that
  * only the digests cross the bus: per range of bytes, the CRC-32 that zlib's crc32() gives (polynomial 0xEDB88320 reflected,
