@@ -1,7 +1,8 @@
 // alac_float_rule.hpp — the float32 -> integer rule of alac_hip_encode_float / alac_hip_encode_float_dither as device code:
 // the quantization, the saturation, the NaN rule and the TPDF dither.  One spelling for both of its users: the quantize pass
-// in front of the encoder (alac_float_in.hip) and the verifier's store sites (alac_hip_verify_float, alac_verify.hpp).  What
-// pins the rule is the numpy restatement of the tests, not a second copy here.
+// in front of the encoder (alac_float_in.hip, the float source of pcm_walk, alac_pcm_walk.hpp) and the verifier's store
+// sites (alac_hip_verify_float, alac_verify.hpp).  What pins the rule is the numpy restatement of the tests, not a second
+// copy here.
 #pragma once
 
 #include <hip/hip_runtime.h>

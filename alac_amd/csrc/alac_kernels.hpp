@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace alacdev {
 
@@ -338,14 +339,6 @@ enum FloatLayout : int {
     kFloatInterleaved = 1,  // channelStride 1, frameStride CH: frames contiguous (16-byte loads over the frame)
     kFloatGeneral = 2,      // any strides, any channel count: one load per sample
 };
-// the vector layouts: 1 or 2 channels, 16-byte aligned float4 loads at every group of 4 frames
-inline FloatLayout float_layout(const float *in, uint32_t channels, uint64_t channelStride, uint64_t frameStride)
-{
-    const bool vec = ((uintptr_t)in & 15) == 0 && channels <= 2;
-    if (vec && frameStride == 1 && (channels == 1 || channelStride % 4 == 0)) return kFloatPlanar;
-    if (vec && channels == 2 && channelStride == 1 && frameStride == 2) return kFloatInterleaved;
-    return kFloatGeneral;
-}
 hipError_t launch_float_to_pcm(uint32_t depth, const FloatInArgs &a, hipStream_t st, const FloatDitherArgs *dither = nullptr);
 
 // ---- integer input (alac_pcm_in.hip): alac_hip_pcm_requantize, the conversion pass of alac_hip_encode_int ----
@@ -361,8 +354,9 @@ struct PcmInArgs {
     uint8_t *pcm;
     uint32_t *clipped;
 };
-// the vector layouts of an integer pass (1 or 2 channels): planar and interleaved int32 with 16-byte loads at every group
-// of 4 frames, planar and interleaved int16 with 8-byte loads, interleaved packed 3-byte containers with dword loads
+// the vector layouts of a pass over containers (1 or 2 channels): planar and interleaved int32 or float32 with 16-byte loads
+// at every group of 4 frames, planar and interleaved int16 with 8-byte loads, interleaved packed 3-byte containers with dword
+// loads
 inline FloatLayout pcm_in_layout(const void *in, uint32_t containerBytes, uint32_t channels, uint64_t channelStride,
                                  uint64_t frameStride)
 {
@@ -372,6 +366,17 @@ inline FloatLayout pcm_in_layout(const void *in, uint32_t containerBytes, uint32
     if (channelStride == 1 && frameStride == 2) return kFloatInterleaved;
     if (containerBytes != 3 && frameStride == 1 && channelStride % 4 == 0) return kFloatPlanar;
     return kFloatGeneral;
+}
+// the one ladder from a layout and a channel count to the <CH, LAYOUT> pair of a pass's kernels: f(CH, LAYOUT), both
+// std::integral_constant, CH 0 in the general layout
+template <typename F>
+inline hipError_t dispatch_layout(FloatLayout layout, uint32_t channels, F f)
+{
+    using std::integral_constant;
+    if (layout == kFloatGeneral) return f(integral_constant<int, 0>(), integral_constant<int, kFloatGeneral>());
+    if (channels == 1) return f(integral_constant<int, 1>(), integral_constant<int, kFloatPlanar>());
+    if (layout == kFloatInterleaved) return f(integral_constant<int, 2>(), integral_constant<int, kFloatInterleaved>());
+    return f(integral_constant<int, 2>(), integral_constant<int, kFloatPlanar>());
 }
 // depth: the target depth b.  dither (b < srcBits only): TPDF by the integer rule of include/alac_hip.h
 hipError_t launch_pcm_requantize(uint32_t depth, const PcmInArgs &a, hipStream_t st, const FloatDitherArgs *dither = nullptr);

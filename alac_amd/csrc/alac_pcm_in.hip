@@ -5,7 +5,7 @@
 #include "alac_dev.hpp"
 #include "alac_kernels.hpp"
 #include "alac_float_rule.hpp"
-#include "alac_pcm_pack.hpp"
+#include "alac_pcm_walk.hpp"
 #include "alac_pcm_load.hpp"
 
 namespace alacdev {
@@ -58,115 +58,62 @@ __device__ __forceinline__ int32_t requantize(int32_t v, int32_t k, const PcmInR
     return out;
 }
 
-// The geometry of k_float_to_pcm (alac_float_in.hip).  One lane: 4 consecutive frames of one packet; a block: 1 024 frames
-// of one packet (blocksPerPacket blocks per packet, a grid-stride loop over them).  Frames at or behind n =
-// min(numSamples[p], frameSize) are not read and staged as zero, without dither.  CB: the container's bytes.  CH: 1 or 2
-// (the vector layouts of pcm_in_layout, frameSize % 4 == 0: the host checks) or 0 (kFloatGeneral, a.channels at run time,
-// one load per sample).  Clipped samples: per lane <= 4 * kMaxChannels; the wave sums them with one ballot per bit of the
-// lane's count and adds the total to clipped[p] with one atomic (a block, hence a wave, lies in one packet).
+// the integer source of pcm_walk (alac_pcm_walk.hpp).  CB: the container's bytes
+template <int DEPTH, int CB, bool DITHER>
+struct IntSrc {
+    using Elem = int32_t;
+    static constexpr bool kDither = DITHER;
+    const void *in;
+    PcmInRule R;
+
+    __device__ __forceinline__ int32_t load1(uint64_t idx) const { return load_container<CB>(in, idx); }
+    template <int N>
+    __device__ __forceinline__ void load_run(uint64_t idx, int32_t (&e)[N]) const
+    {
+        alacdev::load_run<CB, N>((const uint8_t *)in + idx * CB, e);
+    }
+    __device__ __forceinline__ void convert4(const int32_t (&v)[4], const bool (&live)[4], uint64_t t0, uint32_t c,
+                                             const FloatDitherArgs &dz, int32_t (&s)[4], uint32_t &clips) const
+    {
+        int32_t z[4] = {0, 0, 0, 0};
+        if constexpr (DITHER) dither4_k(t0, c, dz, z);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) s[k] = requantize<DEPTH, DITHER>(v[k], live[k] ? z[k] : 0, R, clips);
+    }
+};
+
 template <int DEPTH, int CB, int CH, int LAYOUT, bool DITHER>
 __global__ __launch_bounds__(256) void k_pcm_requantize(PcmInArgs a, uint64_t blocksPerPacket, FloatDitherArgs dz)
 {
-    constexpr uint32_t BPS = bytes_per_sample(DEPTH);
-    constexpr int CNT_BITS = CH == 1 ? 3 : (CH == 2 ? 4 : 6);  // bits of a lane's clip count: <= 4, 8, 32
-    const PcmInRule R = pcm_in_rule<DEPTH, CB>(a);
-    const uint64_t totalBlocks = (uint64_t)a.numPackets * blocksPerPacket;
-    for (uint64_t vb = blockIdx.x; vb < totalBlocks; vb += gridDim.x) {
-        const uint32_t p = (uint32_t)(vb / blocksPerPacket);
-        const uint32_t i0 = (uint32_t)(vb % blocksPerPacket) * 1024u + threadIdx.x * 4u;
-        const uint32_t fs = a.frameSize;
-        uint32_t n = a.numSamples ? a.numSamples[p] : fs;
-        n = n < fs ? n : fs;
-        const uint64_t f0 = (uint64_t)p * fs + i0;  // frame index of the lane's first frame in the batch
-        uint32_t clips = 0;
-        uint64_t t0 = 0;  // stream frame index of the lane's first frame
-        if constexpr (DITHER) t0 = (dz.origin ? dz.origin[p] : (uint64_t)p * fs) + i0;
-        if constexpr (LAYOUT == kFloatGeneral) {
-            const uint32_t C = a.channels;
-            for (uint32_t c = 0; c < C && i0 < fs; c++) {
-                int32_t z[4] = {0, 0, 0, 0};
-                if constexpr (DITHER) dither4_k(t0, c, dz, z);
-#pragma unroll
-                for (uint32_t k = 0; k < 4; k++) {
-                    const uint32_t i = i0 + k;
-                    if (i < fs) {
-                        const bool live = i < n;
-                        const int32_t v = live ? load_container<CB>(a.in, c * a.channelStride + (f0 + k) * a.frameStride) : 0;
-                        store_sample<DEPTH>(a.pcm + ((f0 + k) * C + c) * BPS,
-                                            requantize<DEPTH, DITHER>(v, live ? z[k] : 0, R, clips));
-                    }
-                }
-            }
-        } else if (i0 < fs) {  // vector layouts: frameSize % 4 == 0, so the lane's 4 frames lie in the packet
-            int32_t v[CH][4];
-            if (i0 + 4 <= n) {
-                if constexpr (LAYOUT == kFloatPlanar) {
-#pragma unroll
-                    for (int c = 0; c < CH; c++) load_run<CB, 4>((const uint8_t *)a.in + (c * a.channelStride + f0) * CB, v[c]);
-                } else {
-                    int32_t e[4 * CH];
-                    load_run<CB, 4 * CH>((const uint8_t *)a.in + f0 * (CH * CB), e);
-#pragma unroll
-                    for (int j = 0; j < 4 * CH; j++) v[j % CH][j / CH] = e[j];
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < CH; c++)
-#pragma unroll
-                    for (int k = 0; k < 4; k++)
-                        v[c][k] = i0 + k < n ? load_container<CB>(a.in, c * a.channelStride + (f0 + k) * a.frameStride) : 0;
-            }
-            int32_t s[4 * CH];
-#pragma unroll
-            for (int c = 0; c < CH; c++) {
-                int32_t z[4] = {0, 0, 0, 0};
-                if constexpr (DITHER) dither4_k(t0, c, dz, z);
-#pragma unroll
-                for (int k = 0; k < 4; k++)
-                    s[k * CH + c] = requantize<DEPTH, DITHER>(v[c][k], i0 + k < n ? z[k] : 0, R, clips);
-            }
-            uint32_t w[CH * BPS];
-            pack_dwords<DEPTH, 4 * CH>(s, w);
-            store_dwords<CH * BPS>(a.pcm + f0 * (CH * BPS), w);
-        }
-        if (a.clipped) {
-            uint32_t total = 0;
-#pragma unroll
-            for (int b = 0; b < CNT_BITS; b++) total += (uint32_t)__popcll(__ballot((clips >> b) & 1u)) << b;
-            if ((threadIdx.x & 63) == 0 && total) atomicAdd(a.clipped + p, total);
-        }
-    }
+    pcm_walk<DEPTH, CH, LAYOUT>(IntSrc<DEPTH, CB, DITHER>{a.in, pcm_in_rule<DEPTH, CB>(a)}, a, blocksPerPacket, dz);
 }
 
 template <int DEPTH, int CB, bool DITHER>
-static hipError_t launch_layout(const PcmInArgs &a, const FloatDitherArgs &dz, FloatLayout layout, dim3 grid, uint64_t bpp,
-                                hipStream_t st)
+static hipError_t launch_layout(const PcmInArgs &a, const FloatDitherArgs &dz, hipStream_t st)
 {
-    if (layout == kFloatGeneral)
-        return launch_kernel(k_pcm_requantize<DEPTH, CB, 0, kFloatGeneral, DITHER>, grid, dim3(256), st, a, bpp, dz);
-    if (a.channels == 1) return launch_kernel(k_pcm_requantize<DEPTH, CB, 1, kFloatPlanar, DITHER>, grid, dim3(256), st, a, bpp, dz);
-    if (layout == kFloatInterleaved)
-        return launch_kernel(k_pcm_requantize<DEPTH, CB, 2, kFloatInterleaved, DITHER>, grid, dim3(256), st, a, bpp, dz);
-    if constexpr (CB != 3)  // pcm_in_layout names no planar layout of two rows of packed 3-byte containers
-        return launch_kernel(k_pcm_requantize<DEPTH, CB, 2, kFloatPlanar, DITHER>, grid, dim3(256), st, a, bpp, dz);
-    return hipErrorInvalidValue;
+    const FloatLayout layout = pcm_in_layout(a.in, CB, a.channels, a.channelStride, a.frameStride);
+    return launch_pcm_walk(a, layout, st, [&](auto ch, auto lay, dim3 grid, uint64_t bpp) {
+        constexpr int CH = decltype(ch)::value, LAYOUT = decltype(lay)::value;
+        // pcm_in_layout names no planar layout of two rows of packed 3-byte containers
+        if constexpr (CB == 3 && CH == 2 && LAYOUT == kFloatPlanar) return hipErrorInvalidValue;
+        else return launch_kernel(k_pcm_requantize<DEPTH, CB, CH, LAYOUT, DITHER>, grid, dim3(256), st, a, bpp, dz);
+    });
 }
 
 // dither is a reduction's: 3- and 4-byte containers (a 2-byte one holds 16 bits, the smallest target)
 template <int DEPTH>
-static hipError_t launch_container(const PcmInArgs &a, const FloatDitherArgs *dz, FloatLayout layout, dim3 grid, uint64_t bpp,
-                                   hipStream_t st)
+static hipError_t launch_container(const PcmInArgs &a, const FloatDitherArgs *dz, hipStream_t st)
 {
     const FloatDitherArgs none = {};
     if constexpr (DEPTH != 32) {
-        if (dz && a.containerBytes == 3) return launch_layout<DEPTH, 3, true>(a, *dz, layout, grid, bpp, st);
-        if (dz && a.containerBytes == 4) return launch_layout<DEPTH, 4, true>(a, *dz, layout, grid, bpp, st);
+        if (dz && a.containerBytes == 3) return launch_layout<DEPTH, 3, true>(a, *dz, st);
+        if (dz && a.containerBytes == 4) return launch_layout<DEPTH, 4, true>(a, *dz, st);
     }
     if (dz) return hipErrorInvalidValue;
     switch (a.containerBytes) {
-    case 2: return launch_layout<DEPTH, 2, false>(a, none, layout, grid, bpp, st);
-    case 3: return launch_layout<DEPTH, 3, false>(a, none, layout, grid, bpp, st);
-    default: return launch_layout<DEPTH, 4, false>(a, none, layout, grid, bpp, st);
+    case 2: return launch_layout<DEPTH, 2, false>(a, none, st);
+    case 3: return launch_layout<DEPTH, 3, false>(a, none, st);
+    default: return launch_layout<DEPTH, 4, false>(a, none, st);
     }
 }
 
@@ -176,19 +123,11 @@ hipError_t launch_pcm_requantize(uint32_t depth, const PcmInArgs &a, hipStream_t
     if ((depth != 16 && depth != 20 && depth != 24 && depth != 32) || (S != 16 && S != 20 && S != 24 && S != 32) ||
         CB < 2 || CB > 4 || S > 8 * CB || (dither && depth >= S))
         return hipErrorInvalidValue;
-    if (a.numPackets == 0) return hipSuccess;
-    if (a.clipped) ALAC_TRY(hipMemsetAsync(a.clipped, 0, (uint64_t)a.numPackets * 4, st));
-    // the vector paths: whole 4-frame groups inside a packet, aligned loads at every group
-    const FloatLayout layout =
-        a.frameSize % 4 == 0 ? pcm_in_layout(a.in, CB, a.channels, a.channelStride, a.frameStride) : kFloatGeneral;
-    const uint64_t bpp = ((uint64_t)a.frameSize + 1023) / 1024;
-    const uint64_t blocks = (uint64_t)a.numPackets * bpp;
-    const dim3 grid((uint32_t)(blocks < (1u << 22) ? blocks : (1u << 22)));
     switch (depth) {
-    case 16: return launch_container<16>(a, dither, layout, grid, bpp, st);
-    case 20: return launch_container<20>(a, dither, layout, grid, bpp, st);
-    case 24: return launch_container<24>(a, dither, layout, grid, bpp, st);
-    default: return launch_container<32>(a, dither, layout, grid, bpp, st);
+    case 16: return launch_container<16>(a, dither, st);
+    case 20: return launch_container<20>(a, dither, st);
+    case 24: return launch_container<24>(a, dither, st);
+    default: return launch_container<32>(a, dither, st);
     }
 }
 

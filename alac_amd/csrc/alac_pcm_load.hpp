@@ -1,5 +1,6 @@
-// alac_pcm_load.hpp — how the integer passes (alac_pcm_in.hip, alac_int_probe.hip) take containers out of memory: one
-// container by its index, and a run of consecutive ones with vector loads.  The layouts that allow the runs: pcm_in_layout
+// alac_pcm_load.hpp — how the integer passes (alac_pcm_in.hip, the integer source of pcm_walk, alac_pcm_walk.hpp; and
+// alac_int_probe.hip, the integer rule of probe_walk, alac_probe_walk.hpp) take containers out of memory: one container by
+// its index, and a run of consecutive ones with vector loads.  The layouts that allow the runs: pcm_in_layout
 // (alac_kernels.hpp).
 #pragma once
 #include "alac_dev.hpp"

@@ -1,6 +1,6 @@
 // alac_pcm_pack.hpp — integer samples -> the packed interleaved little-endian PCM alac_hip_encode reads, as device code.
-// One spelling for the two conversion passes in front of the encoder: alac_float_in.hip (float32 sources) and
-// alac_pcm_in.hip (integer sources).
+// The stores of pcm_walk (alac_pcm_walk.hpp), the one walk of the two conversion passes in front of the encoder:
+// alac_float_in.hip (float32 sources) and alac_pcm_in.hip (integer sources).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,7 +1,8 @@
 """Cost of encoding straight from planar float32 (alac_hip_encode_float) against encoding PCM that is already integer and
-against the conversion a torch user writes today:  python tools/encode_float_timing.py [--out result.json]
-For 10 000 and 125 000 synthetic packets (BASELINE configs[1] / the configs[3] shard), 16-bit and 24-bit stereo, every
-packet independent, from a float32 [2, T] device tensor on the grid (the synthetic PCM scaled by 2^-(bit_depth - 1)):
+against the conversion a torch user writes today:  python tools/encode_float_timing.py [--out result.json] [--channels N]
+For 10 000 and 125 000 synthetic packets (BASELINE configs[1] / the configs[3] shard), 16-bit and 24-bit, stereo or --channels
+N (3..8 channels are always the conversion's general layout), every packet independent, from a float32 [channels, T] device
+tensor on the grid (the synthetic PCM scaled by 2^-(bit_depth - 1)):
   encode           alac_hip_encode on the integer PCM (interleaved packed bytes, already on the device)
   encode_float     alac_hip_encode_float on the float tensor (and on the same floats interleaved, a transposed [T, 2])
   torch+encode     nan_to_num / scale / round / clamp / cast / interleave / pack to 2 or 3 bytes in torch, then encode
@@ -45,6 +46,16 @@ def to_float(pcm, depth, channels):
     return (s.float() * (2.0 ** -(depth - 1))).view(-1, channels).t().contiguous()
 
 
+def synth_float(ctx, n, depth, channels):
+    """float32 [channels, frames] on the grid: channel pairs from the stereo generator, a last odd channel from the mono one"""
+    rows, c = [], 0
+    while c < channels:
+        w = 2 if c + 2 <= channels else 1
+        rows.append(to_float(ctx.synth_pcm(len(rows) * n, n, alac_amd.make_format(4096, depth, w, 44100)), depth, w))
+        c += w
+    return torch.cat(rows).contiguous()
+
+
 def torch_pack(x, depth):
     """float32 [channels, frames] -> the packed interleaved bytes alac_hip_encode reads: what a caller writes in torch"""
     top = float(2 ** (depth - 1))
@@ -64,12 +75,12 @@ def torch_dither_pack(x, depth):
     return torch.stack([s & 0xFF, (s >> 8) & 0xFF, (s >> 16) & 0xFF], dim=1).to(torch.uint8).view(-1)
 
 
-def measure(ctx, n, depth):
-    fmt = alac_amd.make_format(4096, depth, 2, 44100)
-    d_pcm = ctx.synth_pcm(0, n, fmt)
-    r = {"packets": n, "bit_depth": depth, "channels": 2}
+def measure(ctx, n, depth, channels=2):
+    fmt = alac_amd.make_format(4096, depth, channels, 44100)
+    r = {"packets": n, "bit_depth": depth, "channels": channels}
     with torch.cuda.stream(ctx.stream):
-        x = to_float(d_pcm, depth, 2)
+        x = synth_float(ctx, n, depth, channels)
+        d_pcm = ctx.synth_pcm(0, n, fmt) if channels <= 2 else torch_pack(x, depth)
         bufs = ctx.encode_buffers(fmt, n)
         ref = ctx.encode(fmt, d_pcm, n, bufs=ctx.encode_buffers(fmt, n))
         got = ctx.encode_float(fmt, x, bufs=bufs)
@@ -80,7 +91,7 @@ def measure(ctx, n, depth):
         assert torch.equal(torch_pack(x, depth), d_pcm[:n * fmt.packet_bytes]), "torch packing differs"
         r["encode_ms"] = best_of(ctx, lambda: ctx.encode(fmt, d_pcm, n, bufs=bufs)) * 1e3
         r["encode_float_ms"] = best_of(ctx, lambda: ctx.encode_float(fmt, x, bufs=bufs)) * 1e3
-        xi = x.t().contiguous().t()  # the same floats interleaved: a [T, 2] tensor viewed as [2, T]
+        xi = x.t().contiguous().t()  # the same floats interleaved: a [T, channels] tensor viewed as [channels, T]
         r["encode_float_interleaved_ms"] = best_of(ctx, lambda: ctx.encode_float(fmt, xi, bufs=bufs)) * 1e3
         r["torch_encode_ms"] = best_of(ctx, lambda: ctx.encode(fmt, torch_pack(x, depth), n, bufs=bufs)) * 1e3
         # the dithered samples differ from the grid by at most 1: same sizes of buffers, other bytes
@@ -96,7 +107,7 @@ def measure(ctx, n, depth):
     r["dither_over_torch_dither"] = r["dither_ms"] / r["torch_dither_encode_ms"]
     r["float_over_torch"] = r["encode_float_ms"] / r["torch_encode_ms"]
     # bytes the conversion moves: 4 read + 2 or 3 written per sample
-    r["conversion_bytes"] = n * 4096 * 2 * (4 + alac_amd.capi.BPS[depth])
+    r["conversion_bytes"] = n * 4096 * channels * (4 + alac_amd.capi.BPS[depth])
     print(json.dumps(r), flush=True)
     return r
 
@@ -106,9 +117,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--packets", default="10000,125000")
     ap.add_argument("--depths", default="16,24")
+    ap.add_argument("--channels", type=int, default=2, help="3..8: the general layout of the conversion (k_float_to_pcm<.., 0, ..>)")
     a = ap.parse_args()
     ctx = alac_amd.Context(0)
-    res = [measure(ctx, int(n), int(d)) for d in a.depths.split(",") for n in a.packets.split(",")]
+    res = [measure(ctx, int(n), int(d), a.channels) for d in a.depths.split(",") for n in a.packets.split(",")]
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
