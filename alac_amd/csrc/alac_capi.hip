@@ -281,7 +281,9 @@ EncLayout enc_layout(const alac_hip_format *f, uint32_t numPackets, uint32_t num
 
 // option "encoder_lane" selects the fused lane-per-chain kernel (alac_encode.hip); default is the
 // tap-parallel pipeline (alac_encode_v1.hip).  Both are HIP paths; there is no CPU path.
-bool use_lane_encoder(const alac_hip_ctx *ctx) { return ctx->opt.laneEncoder != 0; }
+// SetFastMode has no first-generation form: a call it applies to (`fast`: a 2-channel stream with "fast_mode" = 1) runs on the
+// tap-parallel pipeline whatever "encoder_lane" says, so that the bytes are EncodeStereoFast's under every setting.
+bool use_lane_encoder(const alac_hip_ctx *ctx, bool fast = false) { return ctx->opt.laneEncoder != 0 && !fast; }
 
 // > 2 channels: the mono / stereo pipeline once per element over a gathered copy of its channels, then the splice
 // (alac_multichannel.hip)
@@ -724,13 +726,14 @@ static int32_t encode_core(alac_hip_ctx *ctx, const EncodeCall &c)
     hipEvent_t *ev = nullptr;
     if (c.timed && ctx->profile && (uint64_t)(ctx->profCalls + 1) * EV <= ctx->events.size())
         ev = &ctx->events[ctx->profCalls++ * EV];
-    if (ev) ctx->profLane.push_back(use_lane_encoder(ctx));
+    const bool lane = use_lane_encoder(ctx, c.fast && fmt->num_channels == 2);
+    if (ev) ctx->profLane.push_back(lane);
     hipError_t e;
     // the caller's bound on the segment length is checked on the device whatever kernels run
     if (bound && (e = launch_check_segments(c.segFirst, c.numSegments, num_packets, ea.segMax, ctx->errDev ? ctx->errDev + 1 : nullptr,
                                             ea.segBad, c.stream)))
         return fail(ctx, ALAC_HIP_ParamError, "segment check launch", e);
-    if (use_lane_encoder(ctx)) {
+    if (lane) {
         e = launch_encode(fmt->bit_depth, fmt->num_channels, ea, pa, num_packets, c.stream, ev ? ev + (kNumStages + 1) : nullptr);
     } else {
         if (!ctx->vsReady) {
@@ -1002,7 +1005,7 @@ static int32_t encode_through_stage(alac_hip_ctx *ctx, const alac_hip_format *fm
     c.pcm = d_workspace ? (uint8_t *)d_workspace + encBytes : nullptr;
     if (int32_t rc = encode_refusal(ctx, fmt, num_packets, c.numSegments, &c, encBytes, out_capacity)) return rc;
     // tap-parallel path: a table without a bound is read back and checked before anything is enqueued, and handed on
-    if (c.segKind == SegKind::Unread && fmt->num_channels <= 2 && !use_lane_encoder(ctx)) {
+    if (c.segKind == SegKind::Unread && fmt->num_channels <= 2 && !use_lane_encoder(ctx, c.fast && fmt->num_channels == 2)) {
         if (int32_t rc = read_max_segment(ctx, c.stream, c.segFirst, c.numSegments, num_packets, c.maxSeg)) return rc;
         c.segKind = SegKind::Host;
     }

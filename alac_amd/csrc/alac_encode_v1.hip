@@ -68,7 +68,7 @@ V1Plan v1_plan(uint32_t channels, uint32_t numSegments, uint32_t maxSegPackets, 
     const uint32_t ch = channels > 2 ? 2 : channels;
     const uint64_t chains = (uint64_t)numSegments * ch;
     P.fast = ch == 2 && opt.fastMode != 0;  // SetFastMode: no search passes at all (mono has no fast form)
-    if (opt.laneEncoder)
+    if (opt.laneEncoder && !(channels == 2 && opt.fastMode))  // (the lane kernel has no search-free form: use_lane_encoder)
         P.shape = V1Shape::Lane;
     else if (v1_throughput_regime(numSegments, ch, opt))
         P.shape = V1Shape::Throughput;

@@ -81,7 +81,9 @@ int32_t alac_hip_synchronize(alac_hip_ctx *ctx);
  *                          about finished residual rows every 1, 2, 4 or 8 tiles, and after every tile at the end of a pass
  *   "split_coder" (0/1)    tiny regime: the final coder of a chain on two waves
  *   "overlap_pos" (0/1)    chained tiny batches: packet position p + 1's search beside position p's final pass
- *   "fast_mode" (0/1)      ALACEncoder::SetFastMode: the search-free stereo path (EncodeStereoFast)
+ *   "fast_mode" (0/1)      ALACEncoder::SetFastMode: the search-free stereo path (EncodeStereoFast).  The first-generation
+ *                          encoder has no such form: 2-channel streams run on the tap-parallel pipeline while this is 1,
+ *                          whatever "encoder_lane" says
  *   "encoder_lane", "decoder_lane" (0/1)   the first-generation lane-per-chain kernels (a second, structurally different
  *                          implementation kept for differential testing)
  *   "dec_fused" (-1/0/1)   decode: entropy wave + its predictor waves in one launch; automatic up to 65 536 chains (mono: 49 152)

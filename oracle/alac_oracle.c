@@ -534,6 +534,7 @@ struct oalac_encoder {
     uint32_t workBytes;
     uint32_t totalBytes, maxFrameBytes;
     uint32_t info[6];
+    uint32_t dec[4]; /* oalac_encoder_last_decision */
     oalac_hooks hooks;
     int fastMode; /* SetFastMode, ALACEncoder.h:44 */
 };
@@ -621,6 +622,8 @@ void oalac_encoder_set_state(oalac_encoder *e, const int16_t *s)
 }
 
 void oalac_encoder_last_info(const oalac_encoder *e, uint32_t *info6) { memcpy(info6, e->info, sizeof(e->info)); }
+
+void oalac_encoder_last_decision(const oalac_encoder *e, uint32_t *dec4) { memcpy(dec4, e->dec, sizeof(e->dec)); }
 
 /* GetConfig/GetMagicCookie, ALACEncoder.cu:1082-1140 (<= 2 channels: 24 bytes, big-endian fields).
  * maxFrameBytes/avgBitRate carry the encoder's running stats (0 when fetched before encoding,
@@ -753,6 +756,7 @@ static int32_t encode_stereo(oalac_encoder *e, uint8_t *out, uint64_t *pos, cons
     if (bytesShifted != 0) minBits += numSamples * (bytesShifted * 8) * 2;
     uint32_t escapeBits = numSamples * e->bitDepth * 2 + (partial ? 32 : 0) + 2 * 8;
     int doEscape = (minBits >= escapeBits);
+    e->dec[0] = minBits; e->dec[1] = escapeBits; e->dec[2] = 0; e->dec[3] = doEscape ? 1 : 0;
 
     e->info[0] = 0; e->info[1] = (uint32_t)mixRes; e->info[2] = numU; e->info[3] = numV; e->info[4] = e->info[5] = 0;
 
@@ -790,9 +794,11 @@ static int32_t encode_stereo(oalac_encoder *e, uint8_t *out, uint64_t *pos, cons
 
         /* :537-543 compressed packet not smaller than an escape packet: rewind */
         minBits = (uint32_t)(*pos - startPos);
+        e->dec[2] = minBits;
         if (minBits >= escapeBits) {
             *pos = startPos;
             doEscape = 1;
+            e->dec[3] = 2;
         }
     }
     if (doEscape) {
@@ -855,7 +861,8 @@ static int32_t encode_stereo_fast(oalac_encoder *e, uint8_t *out, uint64_t *pos,
     uint32_t escapeBits = numSamples * e->bitDepth * 2 + (partial ? 32 : 0) + 2 * 8;
     int doEscape = (minBits >= escapeBits);
     /* :718-729 */
-    if (!doEscape && (uint32_t)(*pos - startPos) >= escapeBits) doEscape = 1;
+    e->dec[0] = minBits; e->dec[1] = escapeBits; e->dec[2] = (uint32_t)(*pos - startPos); e->dec[3] = doEscape ? 1 : 0;
+    if (!doEscape && (uint32_t)(*pos - startPos) >= escapeBits) { doEscape = 1; e->dec[3] = 2; }
     e->info[0] = (uint32_t)doEscape; e->info[1] = 0; e->info[2] = numU; e->info[3] = numV; e->info[4] = bits1; e->info[5] = bits2;
     if (doEscape) { /* :731-742 */
         *pos = startPos;
@@ -923,6 +930,7 @@ static int32_t encode_mono(oalac_encoder *e, uint8_t *out, uint64_t *pos, const 
     if (bytesShifted != 0) minBits += numSamples * (bytesShifted * 8);
     uint32_t escapeBits = numSamples * e->bitDepth + (partial ? 32 : 0) + 2 * 8;
     int doEscape = (minBits >= escapeBits);
+    e->dec[0] = minBits; e->dec[1] = escapeBits; e->dec[2] = 0; e->dec[3] = doEscape ? 1 : 0;
 
     e->info[0] = 0; e->info[1] = 0; e->info[2] = bestU; e->info[3] = 0; e->info[4] = e->info[5] = 0;
 
@@ -946,9 +954,11 @@ static int32_t encode_mono(oalac_encoder *e, uint8_t *out, uint64_t *pos, const 
         e->info[4] = bits1;
         /* :952-958 */
         minBits = (uint32_t)(*pos - startPos);
+        e->dec[2] = minBits;
         if (minBits >= escapeBits) {
             *pos = startPos;
             doEscape = 1;
+            e->dec[3] = 2;
         }
     }
     if (doEscape) {

@@ -100,6 +100,10 @@ int32_t oalac_encode_packet(oalac_encoder *e, const uint8_t *pcm, uint32_t numSa
 uint32_t oalac_max_packet_bytes(uint32_t frameSize, uint32_t bitDepth, uint32_t numChannels);
 /* debug/inspection of the last packet: [0]=escape [1]=mixRes [2]=numU [3]=numV [4]=bitsU [5]=bitsV */
 void oalac_encoder_last_info(const oalac_encoder *e, uint32_t *info6);
+/* the two escape decisions of the last element (ALACEncoder.cu:455-461, then :537-543 / :952-958; EncodeStereoFast :705-729):
+ * [0]=minBits of the estimate [1]=escapeBits [2]=bits of the element as written by the final pass, from its header on, before
+ * any rewind (0: the final pass did not run) [3]=which decision escaped: 0 none, 1 the estimate, 2 the written size (rewind) */
+void oalac_encoder_last_decision(const oalac_encoder *e, uint32_t *dec4);
 /* 24-byte magic cookie: codec/ALACEncoder.cu:1082-1140 (<=2 channels) */
 uint32_t oalac_magic_cookie(const oalac_encoder *e, uint8_t *cookie24);
 

@@ -81,6 +81,7 @@ class Oracle:
         lib.oalac_max_packet_bytes.argtypes = [C.c_uint32] * 3
         lib.oalac_max_packet_bytes.restype = C.c_uint32
         lib.oalac_encoder_last_info.argtypes = [C.c_void_p, u32p]
+        lib.oalac_encoder_last_decision.argtypes = [C.c_void_p, u32p]
         lib.oalac_magic_cookie.argtypes = [C.c_void_p, u8p]
         lib.oalac_magic_cookie.restype = C.c_uint32
         lib.oalac_magic_cookie_full.argtypes = [C.c_void_p, u8p]
@@ -223,6 +224,14 @@ class OracleEncoder:
         self.lib.oalac_encoder_last_info(self.h, _ptr(info, u32p))
         return dict(escape=int(info[0]), mixres=int(info[1]), numU=int(info[2]), numV=int(info[3]),
                     bitsU=int(info[4]), bitsV=int(info[5]))
+
+    def last_decision(self):
+        """the two escape decisions of the last element: min_bits (the estimate), escape_bits, body (bits the final pass wrote
+        from the element's header on, before any rewind; 0 if it did not run), decided (0 compressed, 1 escaped on the estimate,
+        2 escaped late, on the written size)"""
+        d = np.zeros(4, np.uint32)
+        self.lib.oalac_encoder_last_decision(self.h, _ptr(d, u32p))
+        return dict(min_bits=int(d[0]), escape_bits=int(d[1]), body=int(d[2]), decided=int(d[3]))
 
     def encode_stream(self, pcm_bytes, total_samples, segment_packets=0):
         """returns (stream bytes, packet sizes)."""

@@ -381,3 +381,50 @@ def test_fast_mode_restatement_round_trips_and_is_larger(oracle):
     m1 = oracle.encoder(4096, 16, 1, fast=True).encode_stream(pcm[:8 * 8192], 8 * 4096, 0)
     m0 = oracle.encoder(4096, 16, 1).encode_stream(pcm[:8 * 8192], 8 * 4096, 0)
     assert np.array_equal(m1[0], m0[0])
+
+
+@pytest.mark.parametrize("depth,channels", [(16, 2), (20, 1), (24, 2)])
+def test_last_decision_against_last_info(oracle, depth, channels):
+    """oalac_encoder_last_decision on a packet of each kind — compressed, escaped on the estimate (codec/ALACEncoder.cu:455-461),
+    rewound late (:537-543, :952-958) — against last_info(), the packet size and the header arithmetic of encode_stereo /
+    encode_mono, for a whole and a partial packet."""
+    frame = 512
+    rng = np.random.default_rng(depth + channels)
+    lo, hi = -(1 << (depth - 1)), 1 << (depth - 1)
+    shift = 8 if depth == 24 else 0
+
+    def pack(x):
+        a = x.astype(np.int64) << (4 if depth == 20 else 0)
+        return a.astype("<i2").view(np.uint8).reshape(-1) if depth == 16 else \
+            (a & 0xffffff).astype("<u4").view(np.uint8).reshape(-1, 4)[:, :3].reshape(-1).copy()
+
+    enc = oracle.encoder(frame, depth, channels)
+    for n in (frame, 200):
+        tone = np.round((hi >> 3) * np.sin(np.arange(n)[:, None] * (0.05, 0.07)[:channels])).astype(np.int64)
+        noise = rng.integers(lo, hi, (n, channels))
+        late = noise.copy()
+        late[:n // 8 + 8] = rng.integers(-3, 4, (n // 8 + 8, channels))
+        partial = 32 if n != frame else 0
+        for kind, x in ((0, tone), (1, noise), (2, late)):
+            enc.reset()
+            pk = enc.encode_packet(pack(x), n)
+            d, info = enc.last_decision(), enc.last_info()
+            assert d["decided"] == kind, (n, kind, d)
+            assert d["escape_bits"] == n * depth * channels + partial + 16
+            assert info["escape"] == (kind != 0)
+            assert (d["min_bits"] >= d["escape_bits"]) == (kind == 1)
+            if kind == 1:  # the final pass did not run
+                assert d["body"] == 0 and info["bitsU"] == 0 and info["bitsV"] == 0
+            else:  # header, per-channel coefficient words, shift-off bytes, then the two written streams
+                head = 16 + partial + 16 + sum(16 + 16 * k for k in (info["numU"], info["numV"])[:channels])
+                assert d["body"] == head + n * shift * channels + info["bitsU"] + info["bitsV"]
+                assert (d["body"] >= d["escape_bits"]) == (kind == 2)
+            written = d["body"] if kind == 0 else 16 + partial + n * depth * channels  # the element, or the escape element
+            assert len(pk) == (7 + written + 3 + 7) // 8
+    # EncodeStereoFast decides once, from the bits written: its estimate is the written size
+    if channels == 2:
+        fast = oracle.encoder(frame, depth, channels, fast=True)
+        for kind, x in ((0, tone), (1, noise)):
+            fast.encode_packet(pack(x), 200)
+            d = fast.last_decision()
+            assert d["decided"] == kind and d["min_bits"] == d["body"] > 0 and fast.last_info()["escape"] == kind
