@@ -132,6 +132,8 @@ SIGNATURES = {
     "alac_hip_decode_host": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
     "alac_hip_decode_float": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _u64, _vp, _vp]),
     "alac_hip_decode_float_host": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _vp]),
+    "alac_hip_decode_int": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "alac_hip_decode_int_host": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "alac_hip_verify_workspace_bytes_stream": (_u64, [C.POINTER(Format), _u32, _u64]),
     "alac_hip_verify": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "alac_hip_verify_host": (_i32, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
@@ -766,6 +768,74 @@ class Context:
             for x in (buf, ns, st):
                 x.record_stream(cur)
             pcm = buf.as_strided((fmt.num_channels, frames), (stride, 1))
+            return pcm, ns, st, fmt
+
+    def decode_int(self, cookie, stream, offsets, num_packets, dtype=None, layout="planar", bits=None, left_justified=True,
+                   zero_fill=True, out=None, channel_stride=None):
+        """decode() straight to integer PCM of the caller's layout (alac_hip_decode_int; the rule is in include/alac_hip.h):
+        what torchaudio.load(normalize=False) or soundfile.read(dtype="int32") return, or the containers of a 24-in-32
+        file.  dtype torch.int32 (the default) or torch.int16: a [channels, frames] tensor for layout="planar" (rows
+        channel_stride containers apart, default frames) or [frames, channels] for "interleaved"; dtype torch.uint8: packed
+        little-endian 3-byte containers, [frames, channels, 3] ([channels, frames, 3] for "planar").  The decoded sample
+        goes left-justified into its container (sample << (container bits - depth)) or, with left_justified=False,
+        right-justified at `bits` significant bits (sample << (bits - depth)), sign-extended.
+        bits defaults to the container's width when left_justified (32 / 16 / 24), else to the stream's depth.
+        zero_fill=False leaves the containers behind a short packet's frames uninitialised.  out=(tensor, num_samples,
+        status): write into these instead of allocating; tensor has the shape above and any strides in which no two
+        samples share a container (a view into a larger batch tensor works).
+        Returns (tensor, num_samples int32, status int32, fmt).  Asynchronous like decode()."""
+        with self._call() as cur:
+            t = self.torch
+            ck = np.ascontiguousarray(cookie, np.uint8)
+            fmt = Format()
+            self._check(self.lib.alac_hip_format_from_cookie(ck.ctypes.data, ck.size, C.byref(fmt)))
+            dtype = t.int32 if dtype is None else dtype
+            if dtype not in (t.int32, t.int16, t.uint8):
+                raise ValueError("decode_int: dtype must be torch.int32, torch.int16 or torch.uint8 (packed 3-byte containers)")
+            if layout not in ("planar", "interleaved"):
+                raise ValueError('decode_int: layout must be "planar" or "interleaved"')
+            cb = {t.int32: 4, t.int16: 2, t.uint8: 3}[dtype]
+            unit = 3 if cb == 3 else 1  # elements of the tensor per container
+            ch, frames = fmt.num_channels, num_packets * fmt.frame_size
+            planar = layout == "planar"
+            shape = ((ch, frames) if planar else (frames, ch)) + ((3,) if cb == 3 else ())
+            if out is not None:
+                pcm, ns, st = out
+                if channel_stride is not None:
+                    raise ValueError("decode_int: the strides of out= are the tensor's own")
+                if not pcm.is_cuda or pcm.dtype != dtype or tuple(pcm.shape) != shape:
+                    raise ValueError("decode_int: out tensor must be a cuda tensor of dtype %s and shape %s" % (dtype, shape))
+                if cb == 3 and (pcm.stride(2) != 1 or pcm.stride(0) % 3 or pcm.stride(1) % 3):
+                    raise ValueError("decode_int: packed 3-byte containers lie multiples of 3 bytes apart, their bytes together")
+                if ns.numel() < num_packets or st.numel() < num_packets:
+                    raise ValueError("decode_int: output tensors too small")
+                s0, s1 = pcm.stride(0) // unit, pcm.stride(1) // unit
+                cs, fst = (s0, s1) if planar else (s1, s0)
+            else:
+                alloc = t.zeros if zero_fill else t.empty
+                if planar:
+                    cs, fst = (frames if channel_stride is None else int(channel_stride)), 1
+                    if cs < frames:
+                        raise ValueError("decode_int: channel_stride below num_packets * frame_size")
+                    buf = alloc(ch * cs * unit, dtype=dtype, device=self.device)
+                    pcm = buf.as_strided(shape, (cs * unit, unit) + ((1,) if cb == 3 else ()))
+                else:
+                    if channel_stride is not None:
+                        raise ValueError("decode_int: channel_stride= belongs to the planar layout")
+                    cs, fst = 1, ch
+                    pcm = alloc(shape, dtype=dtype, device=self.device)
+                ns = t.zeros(num_packets, dtype=t.int32, device=self.device)
+                st = t.zeros(num_packets, dtype=t.int32, device=self.device)
+            S = (8 * cb if left_justified else fmt.bit_depth) if bits is None else int(bits)
+            dst = IntSource(cb, S, 1 if left_justified else 0, 0, cs, fst)
+            wsb = int(self.lib.alac_hip_decode_workspace_bytes_stream(C.byref(fmt), num_packets, int(stream.numel())))
+            ws = self._workspace(wsb)
+            rc = self.lib.alac_hip_decode_int(self.h, ck.ctypes.data, ck.size, stream.data_ptr(), offsets.data_ptr(),
+                                              num_packets, ws.data_ptr(), ws.numel(), pcm.data_ptr(), C.byref(dst),
+                                              ns.data_ptr(), st.data_ptr())
+            self._check(rc)
+            for x in (pcm, ns, st):
+                x.record_stream(cur)
             return pcm, ns, st, fmt
 
     def verify(self, cookie, stream, offsets, num_packets, pcm, num_samples=None):

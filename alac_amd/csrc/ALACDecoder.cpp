@@ -74,6 +74,15 @@ int32_t ALACDecoder::DecodeBatch(const uint8_t *stream, const uint32_t *packetBy
     return mLastStatus;
 }
 
+int32_t ALACDecoder::DecodeBatchInt(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets, void *out,
+                                    const alac_hip_int_source *dst, uint32_t *numSamplesOut, int32_t *statusOut)
+{
+    if (!mCtx || mCookie.empty()) return kALAC_ParamError;
+    mLastStatus = alac_hip_decode_int_host(mCtx, mCookie.data(), (uint32_t)mCookie.size(), stream, packetBytes, numPackets, out,
+                                           dst, numSamplesOut, statusOut);
+    return mLastStatus;
+}
+
 int32_t ALACDecoder::VerifyBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets,
                                  const uint8_t *pcmExpected, const uint32_t *numSamplesExpected, uint32_t *firstMismatchOut,
                                  int32_t *statusOut, uint32_t *badPacketsOut)

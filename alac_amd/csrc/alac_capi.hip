@@ -1054,18 +1054,18 @@ int32_t alac_hip_encode_float_dither(alac_hip_ctx *ctx, const alac_hip_format *f
 
 // ---- integer input of any layout, container and depth: requantize by the integer rule, then encode from the result ------
 // what is wrong with an integer source of `channels` channels and `frames` frames; `in` the device or host pointer.  What
-// alac_hip_pcm_requantize and alac_hip_int_probe both refuse.
+// alac_hip_pcm_requantize and alac_hip_int_probe both refuse, and alac_hip_decode_int in its destination.
 static int32_t int_source_struct_refusal(alac_hip_ctx *ctx, const void *in, const alac_hip_int_source *src, uint32_t channels,
                                          uint64_t frames)
 {
-    if (!in || !src) return fail(ctx, ALAC_HIP_ParamError, "null input or alac_hip_int_source");
+    if (!in || !src) return fail(ctx, ALAC_HIP_ParamError, "null buffer or alac_hip_int_source");
     const uint32_t cb = src->container_bytes, S = src->bits;
     if (cb < 2 || cb > 4) return fail(ctx, ALAC_HIP_ParamError, "container_bytes is not 2, 3 or 4");
     if ((S != 16 && S != 20 && S != 24 && S != 32) || S > 8 * cb)
         return fail(ctx, ALAC_HIP_ParamError, "bits is not 16, 20, 24 or 32, or above 8 * container_bytes");
     if (src->reserved != 0) return fail(ctx, ALAC_HIP_ParamError, "alac_hip_int_source.reserved is not 0");
     if (src->left_justified > 1) return fail(ctx, ALAC_HIP_ParamError, "left_justified is not 0 or 1");
-    if (cb != 3 && ((uintptr_t)in & (cb - 1))) return fail(ctx, ALAC_HIP_ParamError, "input not aligned to its container");
+    if (cb != 3 && ((uintptr_t)in & (cb - 1))) return fail(ctx, ALAC_HIP_ParamError, "buffer not aligned to its container");
     if (src->frame_stride == 0) return fail(ctx, ALAC_HIP_ParamError, "frame_stride 0");
     if (src->channel_stride == 0 && channels > 1)
         return fail(ctx, ALAC_HIP_ParamError, "channel_stride 0 with more than one channel");
@@ -1073,7 +1073,7 @@ static int32_t int_source_struct_refusal(alac_hip_ctx *ctx, const void *in, cons
     if (frames && (__builtin_mul_overflow((uint64_t)(channels - 1), src->channel_stride, &rows) ||
                    __builtin_mul_overflow(frames - 1, src->frame_stride, &cols) || __builtin_add_overflow(rows, cols, &last) ||
                    last >= UINT64_MAX / cb))
-        return fail(ctx, ALAC_HIP_ParamError, "the largest index into the input overflows 64 bits");
+        return fail(ctx, ALAC_HIP_ParamError, "the largest index into the buffer overflows 64 bits");
     return ALAC_HIP_noErr;
 }
 
@@ -1487,7 +1487,8 @@ int32_t parse_cookie(alac_hip_ctx *ctx, const uint8_t *cookie, uint32_t size, al
 }
 
 // the buffers of a decode call (the modes other than kPcmStore set DecodeArgs::pcmMode and their own word: kPcmVerify,
-// pcmOut the expected PCM, only read, and firstMismatch; kPcmFloat, pcmOut planar float32, and channelStride)
+// pcmOut the expected PCM, only read, and firstMismatch; kPcmFloat, pcmOut planar float32, and channelStride; kPcmInt,
+// pcmOut the integer destination, and verifyFloat, the block with its layout)
 void decode_buffers(DecodeArgs &da, const uint8_t *stream, const uint64_t *offsets, uint32_t num_packets, const void *pcm_out,
                     uint32_t *num_samples_out, int32_t *status)
 {
@@ -1506,7 +1507,9 @@ int32_t decode_impl(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs da
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!da.stream || !da.offsets || !d_workspace || !da.pcmOut || !da.numSamplesOut || !da.statusOut)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (((uintptr_t)d_workspace & 255) || ((uintptr_t)da.pcmOut & 3)) return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
+    // (int mode: the destination is aligned to its container, which alac_hip_decode_int has checked)
+    if (((uintptr_t)d_workspace & 255) || (da.pcmMode != kPcmInt && ((uintptr_t)da.pcmOut & 3)))
+        return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
     DecLayout L = dec_layout(&fmt, num_packets);
     if (workspace_bytes < L.total) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
     L.capWords = (workspace_bytes - L.words) / 4;  // all of it: packets that do not fit the staged words get status -50
@@ -1720,6 +1723,60 @@ int32_t alac_hip_decode_float(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32
     decode_buffers(da, d_stream, d_packet_offsets, num_packets, d_out, d_num_samples_out, d_status);
     da.pcmMode = kPcmFloat;
     da.channelStride = channel_stride;
+    return decode_impl(ctx, fmt, da, d_workspace, workspace_bytes);
+}
+
+}  // extern "C"
+
+namespace {
+// ---- decode to integer containers of any layout: alac_hip_decode with the PCM store sites writing into the caller's layout --
+// alac_hip_decode_int's own refusals, device and host form (a call with packets): the descriptor by the checks of
+// alac_hip_pcm_requantize, the depth, and a layout in which no two samples share a container
+int32_t int_dest_refusal(alac_hip_ctx *ctx, const alac_hip_format &fmt, uint32_t num_packets, const void *out,
+                         const alac_hip_int_dest *dst)
+{
+    const uint64_t T = (uint64_t)num_packets * fmt.frame_size, C = fmt.num_channels;
+    if (int32_t rc = int_source_struct_refusal(ctx, out, dst, fmt.num_channels, T)) return rc;
+    if (dst->bits < fmt.bit_depth)
+        return fail(ctx, ALAC_HIP_ParamError, "bits below the stream's depth: alac_hip_decode_int reduces nothing");
+    const uint64_t cs = dst->channel_stride, fs = dst->frame_stride;  // fs >= 1; cs >= 1 with more than one channel
+    uint64_t need;
+    const bool framesInner = !__builtin_mul_overflow(T, fs, &need) && cs >= need;
+    const bool channelsInner = !__builtin_mul_overflow(C, cs, &need) && fs >= need;
+    if (C > 1 && !framesInner && !channelsInner)
+        return fail(ctx, ALAC_HIP_ParamError,
+                    "two samples can share a container: neither channel_stride >= num_packets * frame_size * frame_stride "
+                    "nor frame_stride >= num_channels * channel_stride");
+    return ALAC_HIP_noErr;
+}
+
+// the words of a (checked) destination
+VerifyFloatArgs int_dest_args(const alac_hip_format &fmt, const alac_hip_int_dest &dst)
+{
+    VerifyFloatArgs b = {};
+    b.channelStride = dst.channel_stride;
+    b.frameStride = dst.frame_stride;
+    b.containerBytes = dst.container_bytes;
+    b.shift = (dst.left_justified ? 8 * dst.container_bytes : dst.bits) - fmt.bit_depth;
+    return b;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t alac_hip_decode_int(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
+                            const uint64_t *d_packet_offsets, uint32_t num_packets, void *d_workspace, uint64_t workspace_bytes,
+                            void *d_out, const alac_hip_int_dest *dst, uint32_t *d_num_samples_out, int32_t *d_status)
+{
+    alac_hip_format fmt;
+    DecodeArgs da;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (int32_t rc = int_dest_refusal(ctx, fmt, num_packets, d_out, dst)) return rc;
+    decode_buffers(da, d_stream, d_packet_offsets, num_packets, d_out, d_num_samples_out, d_status);
+    const VerifyFloatArgs block = int_dest_args(fmt, *dst);  // lives until the last launch of this call
+    da.pcmMode = kPcmInt;
+    da.verifyFloat = &block;
     return decode_impl(ctx, fmt, da, d_workspace, workspace_bytes);
 }
 
@@ -2169,6 +2226,37 @@ int32_t alac_hip_decode_float_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, u
     return decode_host_common(ctx, fmt, da, h_stream, h_packet_bytes, num_packets, row * fmt.num_channels * sizeof(float), nullptr,
                               nullptr, h_out, fmt.num_channels, channel_stride * sizeof(float), h_num_samples_out, nullptr,
                               nullptr, h_status);
+}
+
+int32_t alac_hip_decode_int_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *h_stream,
+                                 const uint32_t *h_packet_bytes, uint32_t num_packets, void *h_out, const alac_hip_int_dest *dst,
+                                 uint32_t *h_num_samples_out, int32_t *h_status)
+{
+    alac_hip_format fmt;
+    DecodeArgs da;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (!h_stream || !h_packet_bytes || !h_num_samples_out || !h_status) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if (int32_t rc = int_dest_refusal(ctx, fmt, num_packets, h_out, dst)) return rc;
+    // on the device the containers lie as planar rows back to back; the host puts each at the caller's index and leaves the
+    // bytes between containers alone
+    const uint64_t T = (uint64_t)num_packets * fmt.frame_size;
+    const uint32_t cb = dst->container_bytes;
+    alac_hip_int_dest rows = *dst;
+    rows.frame_stride = 1;
+    rows.channel_stride = T;
+    const VerifyFloatArgs block = int_dest_args(fmt, rows);
+    da.pcmMode = kPcmInt;
+    da.verifyFloat = &block;
+    std::vector<uint8_t> stage(T * fmt.num_channels * cb);
+    if (int32_t rc = decode_host_common(ctx, fmt, da, h_stream, h_packet_bytes, num_packets, stage.size(), nullptr, nullptr,
+                                        stage.data(), 1, 0, h_num_samples_out, nullptr, nullptr, h_status))
+        return rc;
+    const uint8_t *from = stage.data();
+    for (uint32_t c = 0; c < fmt.num_channels; c++)
+        for (uint64_t t = 0; t < T; t++, from += cb)
+            memcpy((uint8_t *)h_out + (c * dst->channel_stride + t * dst->frame_stride) * cb, from, cb);
+    return ALAC_HIP_noErr;
 }
 
 int32_t alac_hip_verify_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *h_stream,

@@ -353,7 +353,7 @@ __global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A, VerifyFloatA
             l = (int32_t)(((uint32_t)l << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
             if constexpr (CH == 2) r = (int32_t)(((uint32_t)r << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
         }
-        if constexpr (pcm_is_float(MODE)) {
+        if constexpr (pcm_by_sample(MODE)) {
             const uint32_t lim = pcm_frames<MODE>(A, F, p, rec->numSamples);
             pcm_float_put<DEPTH, MODE>(A, F, 0, p, j, lim, l);
             if constexpr (CH == 2) pcm_float_put<DEPTH, MODE>(A, F, 1, p, j, lim, r);
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A, VerifyFlo
             if (!rec) {
                 const uint32_t ns = A.recs[p].elementChannels ? A.recs[p].numSamples : A.frameSize;
                 if (j < ns) {
-                    if constexpr (pcm_is_float(MODE)) pcm_float_put<DEPTH, MODE>(A, F, c, p, j, pcm_frames<MODE>(A, F, p, ns), 0);
+                    if constexpr (pcm_by_sample(MODE)) pcm_float_put<DEPTH, MODE>(A, F, c, p, j, pcm_frames<MODE>(A, F, p, ns), 0);
                     else store_sample<DEPTH, MODE>(A, op, 0);
                 }
                 continue;
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A, VerifyFlo
                 l = (int32_t)(((uint32_t)l << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
                 if (ech == 2) r = (int32_t)(((uint32_t)r << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
             }
-            if constexpr (pcm_is_float(MODE)) {
+            if constexpr (pcm_by_sample(MODE)) {
                 const uint32_t lim = pcm_frames<MODE>(A, F, p, rec->numSamples);
                 pcm_float_put<DEPTH, MODE>(A, F, c, p, j, lim, l);
                 if (ech == 2) pcm_float_put<DEPTH, MODE>(A, F, c + 1, p, j, lim, r);
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A, VerifyFlo
 template <int DEPTH, PcmMode MODE>
 static hipError_t launch_unmix_depth(const DecodeArgs &da, hipStream_t st)
 {
-    const VerifyFloatArgs vf = MODE == kPcmVerifyFloat ? *da.verifyFloat : VerifyFloatArgs{};
+    const VerifyFloatArgs vf = pcm_has_block(MODE) ? *da.verifyFloat : VerifyFloatArgs{};
     dim3 grid((da.numPackets + 63) / 64, (da.frameSize + 63) / 64);
     if (da.gate) grid = dim3((uint32_t)std::min<uint64_t>((uint64_t)grid.x * grid.y, 2048), 1);  // (see k_decode_unmix)
     // two channels may arrive as one CPE or as two SCE / LFE elements (codec/ALACDecoder.cu:622-756): the per-element
@@ -453,8 +453,8 @@ static hipError_t launch_unmix_depth(const DecodeArgs &da, hipStream_t st)
     return launch_kernel(k_decode_unmix<DEPTH, 1, MODE>, grid, dim3(256), st, da, vf);
 }
 
-// MODE: the un-mix instantiations whose store sites store, compare, write planar floats or compare with a float source
-// (alac_verify.hpp)
+// MODE: the un-mix instantiations whose store sites store, compare, write planar floats, compare with a float source or
+// write integer containers (alac_verify.hpp)
 template <PcmMode MODE>
 static hipError_t launch_decode_lanes(const DecodeArgs &da, hipStream_t st)
 {
@@ -478,6 +478,7 @@ hipError_t launch_decode(const DecodeArgs &da, hipStream_t st)
     case kPcmVerify: return launch_decode_lanes<kPcmVerify>(da, st);   // alac_hip_verify
     case kPcmFloat: return launch_decode_lanes<kPcmFloat>(da, st);     // alac_hip_decode_float
     case kPcmVerifyFloat: return launch_decode_lanes<kPcmVerifyFloat>(da, st);  // alac_hip_verify_float
+    case kPcmInt: return launch_decode_lanes<kPcmInt>(da, st);         // alac_hip_decode_int
     default: return hipErrorInvalidValue;
     }
 }

@@ -549,7 +549,7 @@ __device__ __forceinline__ void raw_body(const DecV1Args &V, const VerifyFloatAr
                 const uint32_t v = (uint32_t)(((((uint64_t)x[k] << 32) | x[k + 1]) << s) >> 32);
                 o[k] = (v >> 16) | (v << 16);
             }
-            if constexpr (pcm_is_float(MODE)) {
+            if constexpr (pcm_by_sample(MODE)) {
                 // the four frames' L (high halves of v) and R (low halves), one 16-byte store per channel
                 int32_t fl[4], fr[4];
 #pragma unroll
@@ -593,7 +593,7 @@ __device__ __forceinline__ void raw_body(const DecV1Args &V, const VerifyFloatAr
                     if (!direct) (rowU + c * A.frameSize)[j] = (int32_t)(v << (32 - w)) >> (32 - w);
                 }
             }
-            if constexpr (pcm_is_float(MODE)) {
+            if constexpr (pcm_by_sample(MODE)) {
                 if (direct && j < n) {  // direct: 16-bit fields (pad2)
                     pcm_float_put<16, MODE>(A, F, 0, p, j, lim, (int32_t)f[0]);
                     pcm_float_put<16, MODE>(A, F, 1, p, j, lim, (int32_t)f[1]);
@@ -1562,11 +1562,11 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, const VerifyF
                         l = (int32_t)(((uint32_t)l << 8) | (xx >> 8));
                         r = (int32_t)(((uint32_t)r << 8) | (xx & 0xffu));
                     }
-                } else if constexpr (!pcm_is_float(MODE)) {
+                } else if constexpr (!pcm_by_sample(MODE)) {
                     l = (int32_t)((uint32_t)l << 4);  // 20 bits, left-justified in three bytes (gpu_unmix20 :225-280)
                     r = (int32_t)((uint32_t)r << 4);
                 }
-                if constexpr (pcm_is_float(MODE)) {
+                if constexpr (pcm_by_sample(MODE)) {
                     fl[k] = l;
                     fr[k] = r;
                 } else {
@@ -1575,7 +1575,7 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, const VerifyF
                 }
             }
             uint8_t *dst = pcm3 + (uint64_t)f0 * 6;
-            if constexpr (pcm_is_float(MODE)) {
+            if constexpr (pcm_by_sample(MODE)) {
                 // K / 2 frames of each channel: 16-byte stores, the last frames of a short packet one by one
                 if (active) {
                     pcm_float_run<DEPTH, MODE>(A, F, 0, p, f0, lim, fl);
@@ -1624,7 +1624,7 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, const VerifyF
             const int32_t uu = isU ? mine : recv, vv = isU ? recv : mine;
             const int32_t l = uu + ((vv - ((mixRes * vv) >> mixBits)) & mixMask);
             const int32_t r = mixRes != 0 ? l - vv : vv;
-            if constexpr (pcm_is_float(MODE)) {
+            if constexpr (pcm_by_sample(MODE)) {
                 fl[k] = l;
                 fr[k] = r;
             } else {
@@ -1632,7 +1632,7 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, const VerifyF
             }
         }
         const uint32_t f0 = jb + (isU ? 0u : (uint32_t)(K / 2));
-        if constexpr (pcm_is_float(MODE)) {
+        if constexpr (pcm_by_sample(MODE)) {
             if (active) {
                 pcm_float_run<16, MODE>(A, F, 0, p, f0, lim, fl);
                 pcm_float_run<16, MODE>(A, F, 1, p, f0, lim, fr);
@@ -1841,14 +1841,14 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, const VerifyFloat
                         l = uu[k];
                         r = vv[k];
                     }
-                    if constexpr (pcm_is_float(MODE)) {
+                    if constexpr (pcm_by_sample(MODE)) {
                         fl[k] = l;
                         fr[k] = r;
                     } else {
                         o[k] = ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16);
                     }
                 }
-                if constexpr (pcm_is_float(MODE)) {
+                if constexpr (pcm_by_sample(MODE)) {
                     pcm_float_run<16, MODE>(A, F, V.outFirst, p, j, pcm_clamp<MODE>(n4, lim), fl);
                     pcm_float_run<16, MODE>(A, F, V.outFirst + 1, p, j, pcm_clamp<MODE>(n4, lim), fr);
                 } else {
@@ -1866,7 +1866,7 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, const VerifyFloat
                     l = uu;
                     r = vv;
                 }
-                if constexpr (pcm_is_float(MODE)) {
+                if constexpr (pcm_by_sample(MODE)) {
                     pcm_float_put<16, MODE>(A, F, V.outFirst, p, j, lim, l);
                     pcm_float_put<16, MODE>(A, F, V.outFirst + 1, p, j, lim, r);
                 } else {
@@ -1919,7 +1919,7 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, const VerifyFloat
                         l = (int32_t)(((uint32_t)l << 8) | ((xx >> 8) & 0xffu));
                         r = (int32_t)(((uint32_t)r << 8) | (xx & 0xffu));
                     }
-                    if constexpr (pcm_is_float(MODE)) {
+                    if constexpr (pcm_by_sample(MODE)) {
                         fl[k] = l;
                         fr[k] = r;
                         continue;
@@ -1931,7 +1931,7 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, const VerifyFloat
                     s[2 * k] = (uint32_t)l & 0xffffffu;
                     s[2 * k + 1] = (uint32_t)r & 0xffffffu;
                 }
-                if constexpr (pcm_is_float(MODE)) {
+                if constexpr (pcm_by_sample(MODE)) {
                     pcm_float_run<DEPTH, MODE>(A, F, V.outFirst, p, j, pcm_clamp<MODE>(n4, lim), fl);
                     pcm_float_run<DEPTH, MODE>(A, F, V.outFirst + 1, p, j, pcm_clamp<MODE>(n4, lim), fr);
                 } else {
@@ -1977,7 +1977,7 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, const VerifyFloat
             l = (int32_t)(((uint32_t)l << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
             if constexpr (CH == 2) r = (int32_t)(((uint32_t)r << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
         }
-        if constexpr (pcm_is_float(MODE)) {
+        if constexpr (pcm_by_sample(MODE)) {
             pcm_float_put<DEPTH, MODE>(A, F, V.outFirst, p, j, lim, l);
             if constexpr (CH == 2) pcm_float_put<DEPTH, MODE>(A, F, V.outFirst + 1, p, j, lim, r);
         } else {
@@ -2018,15 +2018,16 @@ static hipError_t launch_unmix_v1(const DecV1Args &V, const VerifyFloatArgs &vf,
 }
 
 // one pass of the pipeline over the elements V describes, after the staging of the stream (stageFirst: the pass stages it
-// itself); MODE: the instantiations whose PCM store sites store, compare (alac_hip_verify) or write planar floats
-// (alac_hip_decode_float)
+// itself); MODE: the instantiations whose PCM store sites store, compare (alac_hip_verify), write planar floats
+// (alac_hip_decode_float), compare with a float source (alac_hip_verify_float) or write integer containers (alac_hip_decode_int)
 template <PcmMode MODE>
 static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stageFirst)
 {
     DecV1Args V = V0;
     const DecodeArgs &da = V.d;
-    // verify-float mode: its words, the last argument of every kernel that writes PCM (the other modes pass an empty block)
-    const VerifyFloatArgs vf = MODE == kPcmVerifyFloat ? *da.verifyFloat : VerifyFloatArgs{};
+    // verify-float and int modes: their words, the last argument of every kernel that writes PCM (the other modes pass an empty
+    // block)
+    const VerifyFloatArgs vf = pcm_has_block(MODE) ? *da.verifyFloat : VerifyFloatArgs{};
     const uint64_t planeBytes = (uint64_t)da.numPackets * da.numChannels * da.frameSize * 4;
     // One launch (entropy lanes followed by the predictor waves, producer/consumer through HBM) where the chains are few
     // enough that a stage is as slow as its longest serial chain; separate launches where every kernel fills the machine by
@@ -2113,6 +2114,7 @@ static hipError_t run_decode_v1_pass(const DecV1Args &V, hipStream_t st, bool st
     case kPcmVerify: return decode_v1_pass<kPcmVerify>(V, st, stageFirst);  // alac_hip_verify
     case kPcmFloat: return decode_v1_pass<kPcmFloat>(V, st, stageFirst);    // alac_hip_decode_float
     case kPcmVerifyFloat: return decode_v1_pass<kPcmVerifyFloat>(V, st, stageFirst);  // alac_hip_verify_float
+    case kPcmInt: return decode_v1_pass<kPcmInt>(V, st, stageFirst);        // alac_hip_decode_int
     default: return hipErrorInvalidValue;
     }
 }

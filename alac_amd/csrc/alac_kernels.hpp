@@ -248,7 +248,7 @@ struct DecodeArgs {
     // own, the LAST argument of every kernel that writes PCM (an argument behind the existing ones moves no offset).  On the
     // host the block rides behind verifyFloat in this slot; the kernels of that mode never read the slot.
     union {
-        const struct VerifyFloatArgs *verifyFloat;  // verify-float mode, HOST pointer: what the launchers pass on by value
+        const struct VerifyFloatArgs *verifyFloat;  // verify-float and int modes, HOST pointer: what the launchers pass on by value
         // verify mode (alac_hip_verify): [numPackets] lowest sample-frame whose bytes differ, lowered with atomicMin by every
         // store site of the PCM (PCM_PUT, alac_verify.hpp), which loads and compares instead of storing
         uint32_t *firstMismatch = nullptr;
@@ -437,12 +437,23 @@ uint32_t crc_mul_host(uint32_t a, uint32_t b);
 // DecodeArgs::pcmOut is the source: sample i of channel c of packet p at
 // pcmOut[c * channelStride + (p * frameSize + i) * frameStride] (floats); only frames i < min(numSamplesExpected[p], frameSize)
 // are ever loaded
+// The same block carries the words of PcmMode kPcmInt (alac_hip_decode_int), in the slots verify-float mode leaves it (the
+// block's layout, an argument of every PCM-writing kernel, stays what the other modes were compiled against):
+// DecodeArgs::pcmOut is the destination, the container of that sample at the same index, in containers of containerBytes
+// bytes (2 int16, 3 packed little-endian, 4 int32); the value is the decoded sample, sign-extended at the stream's depth,
+// shifted left by `shift` (left-justified: 8 * containerBytes - depth; right-justified at S bits: S - depth)
 struct VerifyFloatArgs {
     uint32_t *firstMismatch;             // [numPackets], as DecodeArgs::firstMismatch in verify mode
     const uint32_t *numSamplesExpected;  // null: every packet frameSize frames
     uint64_t channelStride, frameStride;
-    uint32_t dither;                     // != 0: TPDF by dz, as alac_hip_encode_float_dither
-    uint32_t pad;
+    union {
+        uint32_t dither;                 // != 0: TPDF by dz, as alac_hip_encode_float_dither
+        uint32_t containerBytes;         // int mode
+    };
+    union {
+        uint32_t pad;
+        uint32_t shift;                  // int mode
+    };
     FloatDitherArgs dz;
 };
 

@@ -1,5 +1,6 @@
 // alac_verify.hpp — what the decoders' PCM store sites do: store (alac_hip_decode), verify (alac_hip_verify), float
-// (alac_hip_decode_float) or verify against a float32 source (alac_hip_verify_float).
+// (alac_hip_decode_float), verify against a float32 source (alac_hip_verify_float) or store into integer containers of the
+// caller's layout (alac_hip_decode_int).
 //
 // Every kernel that writes PCM is instantiated once per PcmMode.  The integer sites write through PCM_PUT(MODE, A, ptr, value).
 // With kPcmStore that is the plain store `*ptr = value` it always was, through the site's own pointer type (its alignment
@@ -22,6 +23,10 @@
 // (alac_float_rule.hpp: the one spelling of the rule) and compares that with the decoded sample, sign-extended at the
 // stream's depth.  Every site passes the frame limit pcm_frames gave it — min(decoded, expected, frameSize) — and no
 // address is formed for a frame at or behind it, whatever the packet claims to hold.  Nothing is stored.
+// With kPcmInt, DecodeArgs::pcmOut is the caller's integer destination and the layout travels in the same trailing block
+// (alac_kernels.hpp).  It lives in the float branches too, behind the same two helpers: the sample a site holds, sign-extended
+// at the stream's depth and shifted, goes into its container — 2, 3 or 4 bytes, a packed 3-byte container as exactly its
+// three bytes.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -31,9 +36,11 @@
 
 namespace alacdev {
 
-enum PcmMode : int { kPcmStore = 0, kPcmVerify = 1, kPcmFloat = 2, kPcmVerifyFloat = 3 };
+enum PcmMode : int { kPcmStore = 0, kPcmVerify = 1, kPcmFloat = 2, kPcmVerifyFloat = 3, kPcmInt = 4 };
 // the modes whose sites work on sample values per channel (their float branches)
-constexpr bool pcm_is_float(PcmMode m) { return m == kPcmFloat || m == kPcmVerifyFloat; }
+constexpr bool pcm_by_sample(PcmMode m) { return m == kPcmFloat || m == kPcmVerifyFloat || m == kPcmInt; }
+// the modes whose words travel in the trailing VerifyFloatArgs block (the others pass an empty one)
+constexpr bool pcm_has_block(PcmMode m) { return m == kPcmVerifyFloat || m == kPcmInt; }
 
 // float mode: a decoded sample as alac_hip_decode stores it (its low DEPTH bits, sign-extended — a 16-bit sample that a damaged
 // packet let grow past 16 bits wraps as the int16 store wraps it) times 2^-(DEPTH - 1).  The conversion rounds to nearest
@@ -176,21 +183,88 @@ __device__ __forceinline__ void vf_run(const DecodeArgs &A, const VerifyFloatArg
     }
 }
 
-// ---- what a float branch calls: float mode stores, verify-float mode compares; lim = pcm_frames(...) of the packet ----
+// ---- int mode (alac_hip_decode_int) ----
+
+// the value of a container: the decoded sample as alac_hip_decode stores it (the wrap of pcm_float), shifted to its place;
+// the container is the low containerBytes bytes of this word (a right-justified sample arrives sign-extended in them)
+template <int DEPTH>
+__device__ __forceinline__ int32_t pcm_int(const VerifyFloatArgs &F, int32_t x)
+{
+    const int32_t s = DEPTH == 32 ? x : (int32_t)((uint32_t)x << (32 - DEPTH)) >> (32 - DEPTH);
+    return (int32_t)((uint32_t)s << F.shift);
+}
+// index (in containers) of frame 0 of packet p of channel c
+__device__ __forceinline__ uint64_t pi_origin(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p)
+{
+    return c * F.channelStride + (uint64_t)p * A.frameSize * F.frameStride;
+}
+// one container; the three bytes of a packed one as three byte stores (other lanes own the bytes on either side)
+__device__ __forceinline__ void pi_store(const DecodeArgs &A, const VerifyFloatArgs &F, uint64_t at, int32_t v)
+{
+    if (F.containerBytes == 4) {
+        ((int32_t *)A.pcmOut)[at] = v;
+    } else if (F.containerBytes == 2) {
+        ((int16_t *)A.pcmOut)[at] = (int16_t)v;
+    } else {
+        uint8_t *q = A.pcmOut + at * 3;
+        q[0] = (uint8_t)v;
+        q[1] = (uint8_t)(v >> 8);
+        q[2] = (uint8_t)(v >> 16);
+    }
+}
+// NF consecutive frames f0 .. of one channel, those in front of n.  A whole group of four where frameStride is 1: one 16-byte
+// store of int32 containers, one 8-byte store of int16 containers (the container's own alignment is all the output promises);
+// every other layout one store per sample.  Container width and strides are uniform branches on kernel arguments, for the
+// reason vf_run gives.
+template <int DEPTH, int NF>
+__device__ __forceinline__ void pi_run(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p, uint32_t f0,
+                                       uint32_t n, const int32_t (&x)[NF])
+{
+    typedef int32_t I4 __attribute__((ext_vector_type(4), aligned(4)));
+    typedef int16_t S4 __attribute__((ext_vector_type(4), aligned(2)));
+    static_assert(NF % 4 == 0, "whole groups of four frames");
+    if (f0 >= n) return;
+    const uint64_t at0 = pi_origin(A, F, c, p);
+    const bool rows = F.frameStride == 1 && F.containerBytes != 3;
+#pragma unroll
+    for (int q = 0; q < NF / 4; q++) {
+        const uint32_t f = f0 + 4 * q;
+        if (rows && f + 4 <= n) {
+            const int32_t v0 = pcm_int<DEPTH>(F, x[4 * q]), v1 = pcm_int<DEPTH>(F, x[4 * q + 1]);
+            const int32_t v2 = pcm_int<DEPTH>(F, x[4 * q + 2]), v3 = pcm_int<DEPTH>(F, x[4 * q + 3]);
+            if (F.containerBytes == 4) {
+                const I4 t = {v0, v1, v2, v3};
+                *(I4 *)((int32_t *)A.pcmOut + at0 + f) = t;
+            } else {
+                const S4 t = {(int16_t)v0, (int16_t)v1, (int16_t)v2, (int16_t)v3};
+                *(S4 *)((int16_t *)A.pcmOut + at0 + f) = t;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                if (f + e < n) pi_store(A, F, at0 + (uint64_t)(f + e) * F.frameStride, pcm_int<DEPTH>(F, x[4 * q + e]));
+        }
+    }
+}
+
+// ---- what a float branch calls: float mode stores, verify-float mode compares, int mode stores containers; lim =
+// pcm_frames(...) of the packet ----
 template <int DEPTH, PcmMode MODE>
 __device__ __forceinline__ void pcm_float_put(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p, uint32_t j,
                                               uint32_t lim, int32_t x)
 {
-    static_assert(pcm_is_float(MODE), "a float branch");
+    static_assert(pcm_by_sample(MODE), "a float branch");
     if constexpr (MODE == kPcmFloat) pcm_float_row(A, c, p)[j] = pcm_float<DEPTH>(x);
+    else if constexpr (MODE == kPcmInt) pi_store(A, F, pi_origin(A, F, c, p) + (uint64_t)j * F.frameStride, pcm_int<DEPTH>(F, x));
     else vf_sample<DEPTH>(A, F, c, p, j, lim, x);
 }
 template <int DEPTH, PcmMode MODE, int NF>
 __device__ __forceinline__ void pcm_float_run(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p, uint32_t f0,
                                               uint32_t lim, const int32_t (&x)[NF])
 {
-    static_assert(pcm_is_float(MODE), "a float branch");
+    static_assert(pcm_by_sample(MODE), "a float branch");
     if constexpr (MODE == kPcmFloat) pcm_float_run<DEPTH>(pcm_float_row(A, c, p), f0, lim, x);
+    else if constexpr (MODE == kPcmInt) pi_run<DEPTH>(A, F, c, p, f0, lim, x);
     else vf_run<DEPTH>(A, F, c, p, f0, lim, x);
 }
 
@@ -230,7 +304,7 @@ __device__ __forceinline__ void pcm_compare(const DecodeArgs &A, const void *q, 
 
 #define PCM_PUT(MODE, A, ptr, value)                                                              \
     do {                                                                                          \
-        static_assert(!alacdev::pcm_is_float(MODE), "float modes: the site's float branch does the work"); \
+        static_assert(!alacdev::pcm_by_sample(MODE), "sample modes: the site's float branch does the work"); \
         if constexpr ((MODE) == alacdev::kPcmVerify) alacdev::pcm_compare((A), (ptr), *(ptr), (value)); \
         else *(ptr) = (value);                                                                    \
     } while (0)

@@ -13,6 +13,7 @@
 
 struct alac_hip_ctx;
 struct alac_hip_pcm_digest;
+struct alac_hip_int_source;
 
 class ALACDecoder {
 public:
@@ -38,6 +39,13 @@ public:
     /* batch extension (host buffers) */
     int32_t DecodeBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets, uint8_t *pcmOut,
                         uint32_t *numSamplesOut, int32_t *statusOut);
+    /* batch extension (host buffers): DecodeBatch into integer containers of the caller's layout (alac_hip_decode_int_host).
+     * dst is an alac_hip_int_source read as a destination (alac_hip_int_dest): sample i of channel c of packet p goes to the
+     * container at index c * dst->channel_stride + (p * frameLength + i) * dst->frame_stride of `out`, left- or right-justified
+     * by the rule of include/alac_hip.h; containers decode does not write come back as zero, the bytes between containers
+     * are left alone.  numSamplesOut and statusOut as DecodeBatch. */
+    int32_t DecodeBatchInt(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets, void *out,
+                           const alac_hip_int_source *dst, uint32_t *numSamplesOut, int32_t *statusOut);
     /* batch extension (host buffers): decode on the device and compare with pcmExpected (the layout DecodeBatch writes)
      * without writing PCM anywhere (alac_hip_verify_host).  firstMismatchOut[p] = lowest differing sample-frame of packet p,
      * 0xFFFFFFFF if it matches; statusOut as DecodeBatch; numSamplesExpected NULL = every packet full; badPacketsOut may be

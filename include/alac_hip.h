@@ -454,6 +454,56 @@ int32_t alac_hip_decode_float_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, u
                                    float *h_out, uint64_t channel_stride,
                                    uint32_t *h_num_samples_out, int32_t *h_status);
 
+/* ---- batch decode to integer PCM of any layout and container ------------------------------------------------------------
+ * The decode counterpart of alac_hip_encode_int: alac_hip_decode with every PCM store site writing the decoded sample into
+ * an integer container of the caller's layout, what a PyTorch caller wants (an int32 or int16 [channels, frames] tensor, the
+ * shape torchaudio.load(normalize=False) and soundfile.read(dtype="int32") return), a writer of a 24-in-32 file, or a
+ * caller who must keep 32-bit streams exact (alac_hip_decode_float rounds those to 24 significant bits), without a second
+ * pass over the output.  No reference counterpart.  Asynchronous like alac_hip_decode, same decoder options.
+ * The destination is an alac_hip_int_source read as a destination (alac_hip_int_dest): containers of container_bytes bytes
+ * (2: int16, 3: packed little-endian, 4: int32), of which S = bits are significant.  Sample i of channel c of packet p goes to
+ * the container at index
+ *     c * channel_stride + (p * frame_size + i) * frame_stride            (in containers)
+ * Channel c is the c-th sample of a frame as alac_hip_decode interleaves it.
+ * The rule, for D = the stream's bit depth (from the cookie) and s = the decoded sample as alac_hip_decode stores it (its low
+ * D bits, sign-extended: the wrap alac_hip_decode_float applies to damaged packets):
+ *     left_justified = 1:  container = s << (8 * container_bytes - D)
+ *     left_justified = 0:  container = s << (S - D), sign-extended into the container
+ *   D <= S <= 8 * container_bytes.  There is no rounding, no dither and no reduction: S < D is refused, and a caller who wants
+ *   fewer bits composes alac_hip_decode with alac_hip_pcm_requantize.  The rule is the inverse of the source rule of
+ *   alac_hip_pcm_requantize: requantizing the output with the same descriptor at depth D gives alac_hip_decode's bytes, with
+ *   zero samples clipped.  The descriptor {container_bytes = the stream's own bytes per sample, bits = D, left_justified = 1,
+ *   channel_stride = 1, frame_stride = num_channels} reproduces alac_hip_decode's output byte for byte.
+ * Written are exactly the samples alac_hip_decode writes bytes for: num_samples frames of every decoded packet, a zero
+ * container where decode writes zero samples, nothing behind a short packet's frames and no byte outside the addressed
+ * containers (a packed 3-byte container is written as its three bytes).  Where frame_stride is 1, four consecutive frames of
+ * int32 or int16 containers go out as one 16- or 8-byte store; every other layout takes one store per sample.
+ *   d_out             the containers; 2- and 4-byte containers aligned to their size
+ *   d_workspace       exactly alac_hip_decode_workspace_bytes_stream bytes suffice (there is no PCM plane), 256-byte aligned
+ *   d_num_samples_out, d_status, the hand-off error: as alac_hip_decode.  *dst is read before the call returns.
+ * kALAC_ParamError, checked before anything is enqueued and with nothing written: everything alac_hip_decode refuses; null
+ * d_out or dst; container_bytes not 2, 3 or 4; bits not 16, 20, 24 or 32, above 8 * container_bytes or below D;
+ * left_justified > 1; reserved != 0; d_out not aligned to a 2- or 4-byte container; a largest index whose byte offset
+ * overflows 64 bits; and a layout in which two samples can share a container.  With T = num_packets * frame_size and C
+ * channels, exactly two families of layouts are accepted:
+ *     frame_stride >= 1 and channel_stride >= T * frame_stride      (frames inner; planar is frame_stride = 1)
+ *     channel_stride >= 1 and frame_stride >= C * channel_stride    (channels inner; interleaved is channel_stride = 1,
+ *                                                                    frame_stride = C)
+ *   With one channel only frame_stride >= 1 is required.
+ */
+typedef alac_hip_int_source alac_hip_int_dest;
+int32_t alac_hip_decode_int(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size,
+                            const uint8_t *d_stream, const uint64_t *d_packet_offsets, uint32_t num_packets,
+                            void *d_workspace, uint64_t workspace_bytes,
+                            void *d_out, const alac_hip_int_dest *dst,
+                            uint32_t *d_num_samples_out, int32_t *d_status);
+/* Host-buffer form (synchronous, like alac_hip_decode_float_host): h_out in the layout above; containers decode does not
+ * write come back as zero, the bytes between containers are left as they were. */
+int32_t alac_hip_decode_int_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size,
+                                 const uint8_t *h_stream, const uint32_t *h_packet_bytes, uint32_t num_packets,
+                                 void *h_out, const alac_hip_int_dest *dst,
+                                 uint32_t *h_num_samples_out, int32_t *h_status);
+
 /* ---- batch verify: decode and compare with the PCM the stream was encoded from, on the device ----------------------
  * What a caller of ALACDecoder::Decode (codec/ALACDecoder.cu:571-1002) does by hand before trusting an encode — decode, then
  * compare the output of fillWriteBuffer (:497-563) with the source — without writing the decoded PCM anywhere: every kernel
