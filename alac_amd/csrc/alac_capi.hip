@@ -294,6 +294,12 @@ alac_hip_format element_format(const alac_hip_format *f, uint32_t channels)
     return e;
 }
 
+// the bytes of num_packets whole packets of packed interleaved PCM
+uint64_t packed_pcm_bytes(const alac_hip_format *fmt, uint32_t num_packets)
+{
+    return (uint64_t)num_packets * fmt->frame_size * fmt->num_channels * bytes_per_sample(fmt->bit_depth);
+}
+
 uint64_t max_output_bytes(const alac_hip_format *fmt, uint32_t num_packets)
 {
     // escape elements: 7 + 16 + 32 + N*ch*depth bits each, + ID_END, rounded up; +8 so word stores may overhang
@@ -897,7 +903,7 @@ int32_t alac_hip_encode(alac_hip_ctx *ctx, const alac_hip_format *fmt, const voi
 // the staged integer PCM of a batch (+ 64: slack behind the last packet, like the gathered copies of a > 2-channel batch)
 static uint64_t float_stage_bytes(const alac_hip_format *fmt, uint32_t num_packets)
 {
-    return align_up((uint64_t)num_packets * fmt->frame_size * fmt->num_channels * bytes_per_sample(fmt->bit_depth) + 64, 256);
+    return align_up(packed_pcm_bytes(fmt, num_packets) + 64, 256);
 }
 
 uint64_t alac_hip_encode_float_workspace_bytes(const alac_hip_format *fmt, uint32_t num_packets, uint32_t num_segments)
@@ -1110,7 +1116,7 @@ int32_t alac_hip_pcm_requantize(alac_hip_ctx *ctx, const alac_hip_format *fmt, c
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (int32_t rc = int_source_refusal(ctx, fmt, d_in, src, num_packets, dither)) return rc;
     if (!d_pcm_out || ((uintptr_t)d_pcm_out & 15)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned d_pcm_out (16 B)");
-    if (pcm_capacity < (uint64_t)num_packets * fmt->frame_size * fmt->num_channels * bytes_per_sample(fmt->bit_depth))
+    if (pcm_capacity < packed_pcm_bytes(fmt, num_packets))
         return fail(ctx, ALAC_HIP_ParamError, "pcm_capacity below num_packets packets");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
     return pcm_requantize_run(ctx, *fmt, ctx->stream, d_in, *src, d_num_samples, num_packets, d_pcm_out, d_clipped, dither,
@@ -1469,48 +1475,81 @@ uint64_t alac_hip_decode_workspace_bytes_stream(const alac_hip_format *fmt, uint
 }  // extern "C"
 
 namespace {
-// a decode call's cookie, parsed once: the format, and into `da` the format's fields and the AG parameters (pb / mb / kb)
-int32_t parse_cookie(alac_hip_ctx *ctx, const uint8_t *cookie, uint32_t size, alac_hip_format &fmt, DecodeArgs &da)
+// ---- decode family: each public call is checked and described once; decode_impl / verify_impl run the description --------
+// One call of the ten (five PCM modes, alac_verify.hpp, each in a device and a host form): the format its cookie gives and
+// the kernels' arguments.  parse_cookie fills the format's part, a *_mode function the mode's, decode_buffers the buffers.
+struct DecodeCall {
+    alac_hip_format fmt;
+    DecodeArgs da;
+    PcmModeArgs pm = {};    // stays empty in the modes whose words fit in `da`
+    uint32_t pcmAlign = 4;  // what the mode asks of da.pcmOut's address, in bytes
+};
+
+// a call's cookie, parsed once: the format, and into c.da the format's fields and the AG parameters (pb / mb / kb)
+int32_t parse_cookie(alac_hip_ctx *ctx, const uint8_t *cookie, uint32_t size, DecodeCall &c)
 {
     if (!ctx) return ALAC_HIP_ParamError;
-    const uint8_t *ck = read_cookie(cookie, size, &fmt);
+    const uint8_t *ck = read_cookie(cookie, size, &c.fmt);
     if (!ck) return fail(ctx, ALAC_HIP_ParamError, "bad magic cookie");
-    if (!format_ok(&fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format in cookie");
-    da.frameSize = fmt.frame_size;
-    da.bitDepth = fmt.bit_depth;
-    da.numChannels = fmt.num_channels;
-    da.pb = ck[6];
-    da.mb = ck[7];
-    da.kb = ck[8];
-    da.frameBytes = fmt.num_channels * bytes_per_sample(fmt.bit_depth);
+    if (!format_ok(&c.fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format in cookie");
+    c.da.frameSize = c.fmt.frame_size;
+    c.da.bitDepth = c.fmt.bit_depth;
+    c.da.numChannels = c.fmt.num_channels;
+    c.da.pb = ck[6], c.da.mb = ck[7], c.da.kb = ck[8];
+    c.da.frameBytes = c.fmt.num_channels * bytes_per_sample(c.fmt.bit_depth);
     return ALAC_HIP_noErr;
 }
 
-// the buffers of a decode call (the modes other than kPcmStore set DecodeArgs::pcmMode and their own word: kPcmVerify,
-// pcmOut the expected PCM, only read, and firstMismatch; kPcmFloat, pcmOut planar float32, and channelStride; kPcmInt,
-// pcmOut the integer destination, and verifyFloat, the block with its layout)
-void decode_buffers(DecodeArgs &da, const uint8_t *stream, const uint64_t *offsets, uint32_t num_packets, const void *pcm_out,
-                    uint32_t *num_samples_out, int32_t *status)
+// The five modes, each from its call's checked arguments.  da.pcmOut is then: store, packed PCM as alac_hip_decode writes it;
+// verify, the same, expected and only read; float, planar rows channel_stride floats apart; verify-float, the float source at
+// these strides, only read (d_origin: device table, read with dither only); int, containers in the layout of `dst`, aligned
+// to their size (int_dest_refusal has checked it).  A host form passes the strides of the compact rows it stages on the device.
+void store_mode(DecodeCall &c) { c.da.pcmMode = kPcmStore; }
+void verify_mode(DecodeCall &c) { c.da.pcmMode = kPcmVerify; }
+void float_mode(DecodeCall &c, uint64_t channel_stride)
 {
-    da.stream = stream;
-    da.offsets = offsets;
-    da.numPackets = num_packets;
-    da.pcmOut = (uint8_t *)pcm_out;
-    da.numSamplesOut = num_samples_out;
-    da.statusOut = status;
+    c.da.pcmMode = kPcmFloat;
+    c.da.channelStride = channel_stride;
+}
+void verify_float_mode(DecodeCall &c, uint64_t channel_stride, uint64_t frame_stride, const alac_hip_dither *dither,
+                       const uint64_t *d_origin)
+{
+    c.da.pcmMode = kPcmVerifyFloat;
+    c.pm.channelStride = channel_stride, c.pm.frameStride = frame_stride;
+    c.pm.dither = dither_args(dither, d_origin, c.pm.dz);
+}
+void int_mode(DecodeCall &c, const alac_hip_int_dest &dst)
+{
+    c.da.pcmMode = kPcmInt;
+    c.pm.channelStride = dst.channel_stride, c.pm.frameStride = dst.frame_stride;
+    c.pm.containerBytes = dst.container_bytes;
+    c.pm.shift = (dst.left_justified ? 8 * dst.container_bytes : dst.bits) - c.fmt.bit_depth;
+    c.pcmAlign = dst.container_bytes == 3 ? 1 : dst.container_bytes;
 }
 
-// the decode pass of every decode-family call: `da` as parse_cookie and decode_buffers filled it
-int32_t decode_impl(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs da, void *d_workspace, uint64_t workspace_bytes)
+// the device buffers of a call (pcm: see the modes; num_samples_out: null in the verify family, whose counts go to its workspace)
+void decode_buffers(DecodeCall &c, const uint8_t *stream, const uint64_t *offsets, uint32_t num_packets, const void *pcm,
+                    uint32_t *num_samples_out, int32_t *status)
 {
+    c.da.stream = stream;
+    c.da.offsets = offsets;
+    c.da.numPackets = num_packets;
+    c.da.pcmOut = (uint8_t *)pcm;
+    c.da.numSamplesOut = num_samples_out;
+    c.da.statusOut = status;
+}
+
+// the decode pass of every decode-family call
+int32_t decode_impl(alac_hip_ctx *ctx, const DecodeCall &c, void *d_workspace, uint64_t workspace_bytes)
+{
+    DecodeArgs da = c.da;  // + the workspace and the context's options
     const uint32_t num_packets = da.numPackets;
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!da.stream || !da.offsets || !d_workspace || !da.pcmOut || !da.numSamplesOut || !da.statusOut)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    // (int mode: the destination is aligned to its container, which alac_hip_decode_int has checked)
-    if (((uintptr_t)d_workspace & 255) || (da.pcmMode != kPcmInt && ((uintptr_t)da.pcmOut & 3)))
+    if (((uintptr_t)d_workspace & 255) || ((uintptr_t)da.pcmOut & (c.pcmAlign - 1)))
         return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
-    DecLayout L = dec_layout(&fmt, num_packets);
+    DecLayout L = dec_layout(&c.fmt, num_packets);
     if (workspace_bytes < L.total) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
     L.capWords = (workspace_bytes - L.words) / 4;  // all of it: packets that do not fit the staged words get status -50
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
@@ -1528,33 +1567,32 @@ int32_t decode_impl(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs da
     da.optDirect = ctx->opt.decDirect;
     hipError_t e;
     if (use_lane_decoder(ctx)) {
-        e = launch_decode(da, ctx->stream);
-    } else if (fmt.num_channels > 2) {
+        e = launch_decode(da, c.pm, ctx->stream);
+    } else if (c.fmt.num_channels > 2) {
         // one pass per element of the channel count's sequence (the position of element k + 1 is only known once
         // element k is entropy-decoded); a stream with another sequence is decoded again by the lane decoder, which
         // follows whatever the packets carry.  This is the one place where the call waits for the GPU.
         McElement el[kMaxChannels];
-        const uint32_t nel = channel_elements(fmt.num_channels, el);
-        e = launch_decode_v1_elements(da, el, nel, (uint32_t *)(ws + L.words), L.capWords, da.resid, (uint32_t *)(ws + L.prog),
+        const uint32_t nel = channel_elements(c.fmt.num_channels, el);
+        e = launch_decode_v1_elements(da, c.pm, el, nel, (uint32_t *)(ws + L.words), L.capWords, da.resid, (uint32_t *)(ws + L.prog),
                                       (uint32_t *)(ws + L.elemBit), (uint32_t *)(ws + L.mismatch), ctx->stream);
         uint32_t mismatch = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&mismatch, ws + L.mismatch, 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess && mismatch) e = launch_decode(da, ctx->stream);
+        if (e == hipSuccess && mismatch) e = launch_decode(da, c.pm, ctx->stream);
     } else {
         // A mono / stereo stream whose packets carry another element sequence (two SCEs for two channels, fill in
         // front of ...: status -4 from the fast pipeline, counted by its header kernel) is decoded again by the lane decoder,
         // which follows whatever the packets carry.  No host round trip: its kernels are gated on that device-side count.
-        e = launch_decode_v1(da, (uint32_t *)(ws + L.words), L.capWords, da.resid, (uint32_t *)(ws + L.prog), ctx->stream,
+        e = launch_decode_v1(da, c.pm, (uint32_t *)(ws + L.words), L.capWords, da.resid, (uint32_t *)(ws + L.prog), ctx->stream,
                              (uint32_t *)(ws + L.mismatch));
         if (e == hipSuccess) {
             DecodeArgs dg = da;
             dg.gate = (const uint32_t *)(ws + L.mismatch);
-            e = launch_decode(dg, ctx->stream);
+            e = launch_decode(dg, c.pm, ctx->stream);
         }
     }
-    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "decode launch", e);
-    return ALAC_HIP_noErr;
+    return e == hipSuccess ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "decode launch", e);
 }
 
 // ---- verify: the decode pass with the PCM store sites comparing against the caller's PCM ----------------------------------
@@ -1564,39 +1602,15 @@ int32_t decode_impl(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs da
 // staging words, so a longer stream only needs a larger workspace here too.
 uint64_t verify_ns_bytes(uint32_t numPackets) { return align_up((uint64_t)numPackets * 4, 256); }
 
-// the words of a verify-float call from its (checked) arguments; the buffers verify_impl knows are filled in there
-VerifyFloatArgs verify_float_args(uint64_t channel_stride, uint64_t frame_stride, const alac_hip_dither *dither,
-                                  const uint64_t *d_origin)
+// The pass of a call in verify or verify-float mode with the verify family's two device tables.  Verify mode's store sites read
+// the first-mismatch table in DecodeArgs, verify-float mode's both tables in the block; each mode leaves the other's place unread.
+int32_t verify_impl(alac_hip_ctx *ctx, DecodeCall c, uint32_t *d_first_mismatch, const uint32_t *d_num_samples_expected,
+                    void *d_workspace, uint64_t workspace_bytes, uint32_t *d_bad_packets)
 {
-    VerifyFloatArgs vf = {};
-    vf.channelStride = channel_stride;
-    vf.frameStride = frame_stride;
-    if (dither_on(dither)) {
-        vf.dither = 1;
-        vf.dz.origin = d_origin;
-        philox_round_keys(dither->seed, vf.dz.roundKey);
-    }
-    return vf;
-}
-
-// alac_hip_verify after its cookie: the decode pass of `da` in verify mode — or, with vf, in verify-float mode
-// (alac_hip_verify_float after its own checks: da.pcmOut is the float source)
-int32_t verify_impl(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs da, uint32_t *d_first_mismatch,
-                    const uint32_t *d_num_samples_expected, void *d_workspace, uint64_t workspace_bytes, uint32_t *d_bad_packets,
-                    const VerifyFloatArgs *vf = nullptr)
-{
+    DecodeArgs &da = c.da;
     const uint32_t num_packets = da.numPackets;
-    VerifyFloatArgs block;  // lives until the last launch of this call: the launchers pass it by value
-    if (vf) {
-        block = *vf;
-        block.firstMismatch = d_first_mismatch;
-        block.numSamplesExpected = d_num_samples_expected;
-        da.pcmMode = kPcmVerifyFloat;
-        da.verifyFloat = &block;
-    } else {
-        da.pcmMode = kPcmVerify;
-        da.firstMismatch = d_first_mismatch;
-    }
+    da.firstMismatch = c.pm.firstMismatch = d_first_mismatch;
+    c.pm.numSamplesExpected = d_num_samples_expected;
     if (!d_bad_packets) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
     if (num_packets == 0) {
@@ -1605,19 +1619,18 @@ int32_t verify_impl(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs da
     }
     if (!da.stream || !da.offsets || !d_workspace || !da.pcmOut || !d_first_mismatch || !da.statusOut)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (((uintptr_t)d_workspace & 255) || ((uintptr_t)da.pcmOut & 3)) return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
-    const DecLayout L = dec_layout(&fmt, num_packets);
+    if (((uintptr_t)d_workspace & 255) || ((uintptr_t)da.pcmOut & (c.pcmAlign - 1)))
+        return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
+    const DecLayout L = dec_layout(&c.fmt, num_packets);
     const uint64_t nsBytes = verify_ns_bytes(num_packets);
     if (workspace_bytes < nsBytes + L.total) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
-    uint8_t *ws = (uint8_t *)d_workspace;
-    da.numSamplesOut = (uint32_t *)ws;
+    da.numSamplesOut = (uint32_t *)d_workspace;
     hipError_t e = launch_verify_init(d_first_mismatch, num_packets, d_bad_packets, ctx->stream);
     if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
-    if (int32_t rc = decode_impl(ctx, fmt, da, ws + nsBytes, workspace_bytes - nsBytes)) return rc;
-    e = launch_verify_finish(da.statusOut, da.numSamplesOut, d_num_samples_expected, fmt.frame_size, num_packets,
+    if (int32_t rc = decode_impl(ctx, c, (uint8_t *)d_workspace + nsBytes, workspace_bytes - nsBytes)) return rc;
+    e = launch_verify_finish(da.statusOut, da.numSamplesOut, d_num_samples_expected, c.fmt.frame_size, num_packets,
                              d_first_mismatch, d_bad_packets, ctx->stream);
-    if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
-    return ALAC_HIP_noErr;
+    return e == hipSuccess ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "verify launch", e);
 }
 
 // alac_hip_verify_float's own refusals, device and host form: the dither struct, then (a call with packets) the source
@@ -1633,103 +1646,16 @@ int32_t verify_float_refusal(alac_hip_ctx *ctx, const alac_hip_format &fmt, uint
     return float_stride_refusal(ctx, &fmt, num_packets, channel_stride, frame_stride);
 }
 
-// The host forms of the decode calls after their own checks (bad != nullptr: verify).  Staged: the stream, its workspace, the
-// PCM side (verify: h_expected; else zeroed), the frame counts (h_ns_expected, if given), the statuses.  Then the decode pass
-// (verify: verify_impl, bad packets into *bad), the copies back (decode: the PCM into `rows` rows of h_out, pitch bytes apart
-// or one block for pitch 0, the frame counts; verify: the first mismatches), the statuses, one wait and the hand-off check.
-int32_t decode_host_common(alac_hip_ctx *ctx, const alac_hip_format &fmt, DecodeArgs &da, const uint8_t *h_stream,
-                           const uint32_t *h_packet_bytes, uint32_t num_packets, uint64_t pcmBytes, const void *h_expected,
-                           const uint32_t *h_ns_expected, void *h_out, uint32_t rows, uint64_t pitch, uint32_t *h_ns_out,
-                           uint32_t *h_fm, uint32_t *bad, int32_t *h_status, const VerifyFloatArgs *vf = nullptr,
-                           const uint64_t *h_origin = nullptr)
+// alac_hip_decode_float's refusals of its channel stride, device and host form (a call with packets)
+int32_t float_dest_refusal(alac_hip_ctx *ctx, const alac_hip_format &fmt, uint32_t num_packets, uint64_t channel_stride)
 {
-    // vf (verify-float): h_expected is the float source, pcmBytes what of it the call may read, h_origin (nullable) the
-    // packets' stream frame indices
-    const bool verify = bad != nullptr;
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
-    const uint64_t n4 = num_packets * 4ull;
-    hipStream_t st = ctx->stream;
-    DevStream d;
-    if (int32_t rc = upload_stream(h_stream, h_packet_bytes, num_packets, st, d, on_fail(ctx))) return rc;
-    const uint64_t wsBytes = (verify ? alac_hip_verify_workspace_bytes_stream : alac_hip_decode_workspace_bytes_stream)(
-        &fmt, num_packets, d.total);
-    DevBuf dWs, dPcm, dNs, dSt, dFm, dBad, dOrigin;
-    hipError_t e;
-    if ((e = dWs.alloc(wsBytes)) || (e = dPcm.alloc(pcmBytes)) || (e = dNs.alloc(n4)) || (e = dSt.alloc(n4)) ||
-        (verify && ((e = dFm.alloc(n4)) || (e = dBad.alloc(4)))) || (h_origin && (e = dOrigin.alloc(num_packets * 8ull))))
-        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
-    if (h_origin && (e = hipMemcpyAsync(dOrigin.p, h_origin, num_packets * 8ull, hipMemcpyHostToDevice, st)))
-        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    if ((e = verify ? hipMemcpyAsync(dPcm.p, h_expected, pcmBytes, hipMemcpyHostToDevice, st)
-                    : hipMemsetAsync(dPcm.p, 0, pcmBytes, st)) ||
-        (h_ns_expected && (e = hipMemcpyAsync(dNs.p, h_ns_expected, n4, hipMemcpyHostToDevice, st))))
-        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    decode_buffers(da, (const uint8_t *)d.bytes.p, (const uint64_t *)d.offs.p, num_packets, dPcm.p, (uint32_t *)dNs.p,
-                   (int32_t *)dSt.p);
-    if (verify) {
-        const uint32_t *ns = h_ns_expected ? (const uint32_t *)dNs.p : nullptr;
-        VerifyFloatArgs block;
-        if (vf) {
-            block = *vf;
-            block.dz.origin = h_origin ? (const uint64_t *)dOrigin.p : nullptr;
-        }
-        if (int32_t rc = verify_impl(ctx, fmt, da, (uint32_t *)dFm.p, ns, dWs.p, wsBytes, (uint32_t *)dBad.p, vf ? &block : nullptr))
-            return rc;
-        if (!(e = hipMemcpyAsync(bad, dBad.p, 4, hipMemcpyDeviceToHost, st)) && h_fm)
-            e = hipMemcpyAsync(h_fm, dFm.p, n4, hipMemcpyDeviceToHost, st);
-    } else {
-        if (int32_t rc = decode_impl(ctx, fmt, da, dWs.p, wsBytes)) return rc;
-        const uint64_t w = pcmBytes / rows;
-        if (!(e = pitch ? hipMemcpy2DAsync(h_out, pitch, dPcm.p, w, w, rows, hipMemcpyDeviceToHost, st)
-                        : hipMemcpyAsync(h_out, dPcm.p, pcmBytes, hipMemcpyDeviceToHost, st)))
-            e = hipMemcpyAsync(h_ns_out, dNs.p, n4, hipMemcpyDeviceToHost, st);
-    }
-    if (e || (h_status && (e = hipMemcpyAsync(h_status, dSt.p, n4, hipMemcpyDeviceToHost, st))) || (e = hipStreamSynchronize(st)))
-        return fail(ctx, ALAC_HIP_ParamError, verify ? "verify execution" : "decode execution", e);
-    return check_handoff(ctx);
-}
-}  // namespace
-
-extern "C" {
-
-int32_t alac_hip_decode(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
-                        const uint64_t *d_packet_offsets, uint32_t num_packets, void *d_workspace,
-                        uint64_t workspace_bytes, uint8_t *d_pcm_out, uint32_t *d_num_samples_out,
-                        int32_t *d_status)
-{
-    alac_hip_format fmt;
-    DecodeArgs da;
-    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
-    decode_buffers(da, d_stream, d_packet_offsets, num_packets, d_pcm_out, d_num_samples_out, d_status);
-    return decode_impl(ctx, fmt, da, d_workspace, workspace_bytes);
-}
-
-// ---- decode to planar float32: alac_hip_decode with the PCM store sites writing scaled floats ----------------------------
-int32_t alac_hip_decode_float(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
-                              const uint64_t *d_packet_offsets, uint32_t num_packets, void *d_workspace,
-                              uint64_t workspace_bytes, float *d_out, uint64_t channel_stride, uint32_t *d_num_samples_out,
-                              int32_t *d_status)
-{
-    alac_hip_format fmt;
-    DecodeArgs da;
-    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
-    if (num_packets == 0) return ALAC_HIP_noErr;
-    if (!d_out) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if ((uintptr_t)d_out & 3) return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
     if (channel_stride < (uint64_t)num_packets * fmt.frame_size)
         return fail(ctx, ALAC_HIP_ParamError, "channel_stride below num_packets * frame_size");
     if (channel_stride > UINT64_MAX / sizeof(float) / fmt.num_channels)
         return fail(ctx, ALAC_HIP_ParamError, "channel_stride * channels overflows");
-    decode_buffers(da, d_stream, d_packet_offsets, num_packets, d_out, d_num_samples_out, d_status);
-    da.pcmMode = kPcmFloat;
-    da.channelStride = channel_stride;
-    return decode_impl(ctx, fmt, da, d_workspace, workspace_bytes);
+    return ALAC_HIP_noErr;
 }
 
-}  // extern "C"
-
-namespace {
-// ---- decode to integer containers of any layout: alac_hip_decode with the PCM store sites writing into the caller's layout --
 // alac_hip_decode_int's own refusals, device and host form (a call with packets): the descriptor by the checks of
 // alac_hip_pcm_requantize, the depth, and a layout in which no two samples share a container
 int32_t int_dest_refusal(alac_hip_ctx *ctx, const alac_hip_format &fmt, uint32_t num_packets, const void *out,
@@ -1750,34 +1676,117 @@ int32_t int_dest_refusal(alac_hip_ctx *ctx, const alac_hip_format &fmt, uint32_t
     return ALAC_HIP_noErr;
 }
 
-// the words of a (checked) destination
-VerifyFloatArgs int_dest_args(const alac_hip_format &fmt, const alac_hip_int_dest &dst)
+// The caller's side of a host form: what is staged in and where the results go.  What a mode does not use stays null.
+struct HostDecode {
+    const uint8_t *stream;
+    const uint32_t *packetBytes;
+    uint32_t numPackets;
+    uint64_t pcmBytes;  // of the PCM side on the device: the rows decoded into, or what is staged of `expected`
+    // verify family: the expected PCM / the float source, the expected frame counts and the packets' stream frame indices (both
+    // nullable) and the first mismatches (nullable)
+    const void *expected = nullptr;
+    const uint32_t *numSamplesExpected = nullptr;
+    const uint64_t *origin = nullptr;
+    uint32_t *firstMismatch = nullptr;
+    // decode modes: the PCM and the frame counts; pitch != 0: the PCM as one row per channel, pitch bytes apart
+    void *out = nullptr;
+    uint64_t pitch = 0;
+    uint32_t *numSamplesOut = nullptr;
+    int32_t *status = nullptr;  // every mode (nullable in the verify family)
+};
+
+// The host forms after their own checks, `c` with its mode set.  Staged: the stream, its workspace, the PCM side (verify
+// family: h.expected; else zeroed), the expected frame counts and origins (if given), the statuses.  Then the pass, the copies
+// back (decode modes: the PCM and the frame counts; verify family: the first mismatches), the statuses, one wait and the
+// hand-off check.  Returns a status, or in the verify family, where all went well, the count of bad packets.
+int32_t decode_host_common(alac_hip_ctx *ctx, DecodeCall &c, const HostDecode &h)
 {
-    VerifyFloatArgs b = {};
-    b.channelStride = dst.channel_stride;
-    b.frameStride = dst.frame_stride;
-    b.containerBytes = dst.container_bytes;
-    b.shift = (dst.left_justified ? 8 * dst.container_bytes : dst.bits) - fmt.bit_depth;
-    return b;
+    const bool verify = c.da.pcmMode == kPcmVerify || c.da.pcmMode == kPcmVerifyFloat;
+    const uint32_t num_packets = h.numPackets;
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    const uint64_t n4 = num_packets * 4ull;
+    hipStream_t st = ctx->stream;
+    DevStream d;
+    if (int32_t rc = upload_stream(h.stream, h.packetBytes, num_packets, st, d, on_fail(ctx))) return rc;
+    const uint64_t wsBytes = (verify ? alac_hip_verify_workspace_bytes_stream : alac_hip_decode_workspace_bytes_stream)(
+        &c.fmt, num_packets, d.total);
+    DevBuf dWs, dPcm, dNs, dSt, dFm, dBad, dOrigin;
+    uint32_t bad = 0;
+    hipError_t e;
+    if ((e = dWs.alloc(wsBytes)) || (e = dPcm.alloc(h.pcmBytes)) || (e = dNs.alloc(n4)) || (e = dSt.alloc(n4)) ||
+        (verify && ((e = dFm.alloc(n4)) || (e = dBad.alloc(4)))) || (h.origin && (e = dOrigin.alloc(num_packets * 8ull))))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if ((h.origin && (e = hipMemcpyAsync(dOrigin.p, h.origin, num_packets * 8ull, hipMemcpyHostToDevice, st))) ||
+        (e = verify ? hipMemcpyAsync(dPcm.p, h.expected, h.pcmBytes, hipMemcpyHostToDevice, st)
+                    : hipMemsetAsync(dPcm.p, 0, h.pcmBytes, st)) ||
+        (h.numSamplesExpected && (e = hipMemcpyAsync(dNs.p, h.numSamplesExpected, n4, hipMemcpyHostToDevice, st))))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    decode_buffers(c, (const uint8_t *)d.bytes.p, (const uint64_t *)d.offs.p, num_packets, dPcm.p, (uint32_t *)dNs.p,
+                   (int32_t *)dSt.p);
+    if (verify) {
+        if (h.origin) c.pm.dz.origin = (const uint64_t *)dOrigin.p;  // the device table the mode could not know yet
+        const uint32_t *ns = h.numSamplesExpected ? (const uint32_t *)dNs.p : nullptr;
+        if (int32_t rc = verify_impl(ctx, c, (uint32_t *)dFm.p, ns, dWs.p, wsBytes, (uint32_t *)dBad.p)) return rc;
+        if (!(e = hipMemcpyAsync(&bad, dBad.p, 4, hipMemcpyDeviceToHost, st)) && h.firstMismatch)
+            e = hipMemcpyAsync(h.firstMismatch, dFm.p, n4, hipMemcpyDeviceToHost, st);
+    } else {
+        if (int32_t rc = decode_impl(ctx, c, dWs.p, wsBytes)) return rc;
+        const uint32_t rows = c.fmt.num_channels;
+        const uint64_t w = h.pcmBytes / rows;
+        if (!(e = h.pitch ? hipMemcpy2DAsync(h.out, h.pitch, dPcm.p, w, w, rows, hipMemcpyDeviceToHost, st)
+                          : hipMemcpyAsync(h.out, dPcm.p, h.pcmBytes, hipMemcpyDeviceToHost, st)))
+            e = hipMemcpyAsync(h.numSamplesOut, dNs.p, n4, hipMemcpyDeviceToHost, st);
+    }
+    if (e || (h.status && (e = hipMemcpyAsync(h.status, dSt.p, n4, hipMemcpyDeviceToHost, st))) || (e = hipStreamSynchronize(st)))
+        return fail(ctx, ALAC_HIP_ParamError, verify ? "verify execution" : "decode execution", e);
+    const int32_t rc = check_handoff(ctx);
+    return rc != ALAC_HIP_noErr ? rc : (int32_t)bad;
 }
 }  // namespace
 
 extern "C" {
 
+int32_t alac_hip_decode(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
+                        const uint64_t *d_packet_offsets, uint32_t num_packets, void *d_workspace,
+                        uint64_t workspace_bytes, uint8_t *d_pcm_out, uint32_t *d_num_samples_out,
+                        int32_t *d_status)
+{
+    DecodeCall c;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, c)) return rc;
+    store_mode(c);
+    decode_buffers(c, d_stream, d_packet_offsets, num_packets, d_pcm_out, d_num_samples_out, d_status);
+    return decode_impl(ctx, c, d_workspace, workspace_bytes);
+}
+
+// ---- decode to planar float32: alac_hip_decode with the PCM store sites writing scaled floats ----------------------------
+int32_t alac_hip_decode_float(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
+                              const uint64_t *d_packet_offsets, uint32_t num_packets, void *d_workspace,
+                              uint64_t workspace_bytes, float *d_out, uint64_t channel_stride, uint32_t *d_num_samples_out,
+                              int32_t *d_status)
+{
+    DecodeCall c;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, c)) return rc;
+    if (num_packets == 0) return ALAC_HIP_noErr;
+    if (!d_out) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
+    if ((uintptr_t)d_out & 3) return fail(ctx, ALAC_HIP_ParamError, "misaligned buffer");
+    if (int32_t rc = float_dest_refusal(ctx, c.fmt, num_packets, channel_stride)) return rc;
+    float_mode(c, channel_stride);
+    decode_buffers(c, d_stream, d_packet_offsets, num_packets, d_out, d_num_samples_out, d_status);
+    return decode_impl(ctx, c, d_workspace, workspace_bytes);
+}
+
+// ---- decode to integer containers of any layout: alac_hip_decode with the PCM store sites writing into the caller's layout --
 int32_t alac_hip_decode_int(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *d_stream,
                             const uint64_t *d_packet_offsets, uint32_t num_packets, void *d_workspace, uint64_t workspace_bytes,
                             void *d_out, const alac_hip_int_dest *dst, uint32_t *d_num_samples_out, int32_t *d_status)
 {
-    alac_hip_format fmt;
-    DecodeArgs da;
-    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
+    DecodeCall c;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, c)) return rc;
     if (num_packets == 0) return ALAC_HIP_noErr;
-    if (int32_t rc = int_dest_refusal(ctx, fmt, num_packets, d_out, dst)) return rc;
-    decode_buffers(da, d_stream, d_packet_offsets, num_packets, d_out, d_num_samples_out, d_status);
-    const VerifyFloatArgs block = int_dest_args(fmt, *dst);  // lives until the last launch of this call
-    da.pcmMode = kPcmInt;
-    da.verifyFloat = &block;
-    return decode_impl(ctx, fmt, da, d_workspace, workspace_bytes);
+    if (int32_t rc = int_dest_refusal(ctx, c.fmt, num_packets, d_out, dst)) return rc;
+    int_mode(c, *dst);
+    decode_buffers(c, d_stream, d_packet_offsets, num_packets, d_out, d_num_samples_out, d_status);
+    return decode_impl(ctx, c, d_workspace, workspace_bytes);
 }
 
 uint64_t alac_hip_verify_workspace_bytes_stream(const alac_hip_format *fmt, uint32_t num_packets, uint64_t stream_bytes)
@@ -1791,11 +1800,11 @@ int32_t alac_hip_verify(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t coo
                         const uint32_t *d_num_samples_expected, void *d_workspace, uint64_t workspace_bytes,
                         uint32_t *d_first_mismatch, int32_t *d_status, uint32_t *d_bad_packets)
 {
-    alac_hip_format fmt;
-    DecodeArgs da;
-    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
-    decode_buffers(da, d_stream, d_packet_offsets, num_packets, d_pcm_expected, nullptr, d_status);
-    return verify_impl(ctx, fmt, da, d_first_mismatch, d_num_samples_expected, d_workspace, workspace_bytes, d_bad_packets);
+    DecodeCall c;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, c)) return rc;
+    verify_mode(c);
+    decode_buffers(c, d_stream, d_packet_offsets, num_packets, d_pcm_expected, nullptr, d_status);
+    return verify_impl(ctx, c, d_first_mismatch, d_num_samples_expected, d_workspace, workspace_bytes, d_bad_packets);
 }
 
 // ---- verify against the float32 source of alac_hip_encode_float / _dither: the store sites compare through the rule ----
@@ -1805,14 +1814,13 @@ int32_t alac_hip_verify_float(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32
                               const alac_hip_dither *dither, const uint64_t *d_packet_origin, void *d_workspace,
                               uint64_t workspace_bytes, uint32_t *d_first_mismatch, int32_t *d_status, uint32_t *d_bad_packets)
 {
-    alac_hip_format fmt;
-    DecodeArgs da;
-    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
-    if (int32_t rc = verify_float_refusal(ctx, fmt, num_packets, d_in, channel_stride, frame_stride, dither, d_packet_origin))
+    DecodeCall c;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, c)) return rc;
+    if (int32_t rc = verify_float_refusal(ctx, c.fmt, num_packets, d_in, channel_stride, frame_stride, dither, d_packet_origin))
         return rc;
-    decode_buffers(da, d_stream, d_packet_offsets, num_packets, d_in, nullptr, d_status);
-    const VerifyFloatArgs vf = verify_float_args(channel_stride, frame_stride, dither, d_packet_origin);
-    return verify_impl(ctx, fmt, da, d_first_mismatch, d_num_samples_expected, d_workspace, workspace_bytes, d_bad_packets, &vf);
+    verify_float_mode(c, channel_stride, frame_stride, dither, d_packet_origin);
+    decode_buffers(c, d_stream, d_packet_offsets, num_packets, d_in, nullptr, d_status);
+    return verify_impl(ctx, c, d_first_mismatch, d_num_samples_expected, d_workspace, workspace_bytes, d_bad_packets);
 }
 
 // ---- stage level ---------------------------------------------------------------------------------
@@ -1884,7 +1892,7 @@ static int32_t encode_host_segments(alac_hip_ctx *ctx, const alac_hip_format *fm
     if (int32_t rc = host_segment_refusal(ctx, h_seg_first, num_segments, num_packets)) return rc;
     if (int32_t rc = encode_refusal(ctx, fmt, num_packets, ctx->opt.lpc ? num_packets : num_segments, nullptr, 0, 0)) return rc;
     const uint32_t np = num_packets, nseg = num_segments;
-    const uint64_t pcmBytes = (uint64_t)np * fmt->frame_size * fmt->num_channels * bytes_per_sample(fmt->bit_depth);
+    const uint64_t pcmBytes = packed_pcm_bytes(fmt, np);
     const uint64_t wsBytes = alac_hip_encode_workspace_bytes(fmt, np, ctx->opt.lpc ? np : nseg);
     DevBuf dPcm;
     hipError_t e;
@@ -2026,7 +2034,7 @@ int32_t alac_hip_pcm_requantize_host(alac_hip_ctx *ctx, const alac_hip_format *f
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (int32_t rc = int_source_refusal(ctx, fmt, h_in, src, num_packets, dither)) return rc;
     const uint32_t np = num_packets;
-    const uint64_t pcmBytes = (uint64_t)np * fmt->frame_size * fmt->num_channels * bytes_per_sample(fmt->bit_depth);
+    const uint64_t pcmBytes = packed_pcm_bytes(fmt, np);
     if (!h_pcm_out) return fail(ctx, ALAC_HIP_ParamError, "null h_pcm_out");
     if (pcm_capacity < pcmBytes) return fail(ctx, ALAC_HIP_ParamError, "pcm_capacity below num_packets packets");
     const uint64_t spanBytes = int_host_span_bytes(fmt, src, h_num_samples, np);
@@ -2194,68 +2202,60 @@ int32_t alac_hip_decode_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_
                              const uint8_t *h_stream, const uint32_t *h_packet_bytes, uint32_t num_packets,
                              uint8_t *h_pcm_out, uint32_t *h_num_samples_out, int32_t *h_status)
 {
-    alac_hip_format fmt;
-    DecodeArgs da;
-    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
+    DecodeCall c;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, c)) return rc;
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!h_stream || !h_packet_bytes || !h_pcm_out || !h_num_samples_out || !h_status)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    const uint64_t pcmBytes = (uint64_t)num_packets * fmt.frame_size * fmt.num_channels * bytes_per_sample(fmt.bit_depth);
-    return decode_host_common(ctx, fmt, da, h_stream, h_packet_bytes, num_packets, pcmBytes, nullptr, nullptr, h_pcm_out, 1, 0,
-                              h_num_samples_out, nullptr, nullptr, h_status);
+    store_mode(c);
+    HostDecode h{h_stream, h_packet_bytes, num_packets, packed_pcm_bytes(&c.fmt, num_packets)};
+    h.out = h_pcm_out, h.numSamplesOut = h_num_samples_out, h.status = h_status;
+    return decode_host_common(ctx, c, h);
 }
 
 int32_t alac_hip_decode_float_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size,
                                    const uint8_t *h_stream, const uint32_t *h_packet_bytes, uint32_t num_packets, float *h_out,
                                    uint64_t channel_stride, uint32_t *h_num_samples_out, int32_t *h_status)
 {
-    alac_hip_format fmt;
-    DecodeArgs da;
-    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
+    DecodeCall c;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, c)) return rc;
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!h_stream || !h_packet_bytes || !h_out || !h_num_samples_out || !h_status)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (channel_stride < (uint64_t)num_packets * fmt.frame_size)
-        return fail(ctx, ALAC_HIP_ParamError, "channel_stride below num_packets * frame_size");
-    if (channel_stride > UINT64_MAX / sizeof(float) / fmt.num_channels)
-        return fail(ctx, ALAC_HIP_ParamError, "channel_stride * channels overflows");
+    if (int32_t rc = float_dest_refusal(ctx, c.fmt, num_packets, channel_stride)) return rc;
     // on the device the rows lie back to back; the copy back puts them channel_stride floats apart and leaves the gap alone
-    const uint64_t row = (uint64_t)num_packets * fmt.frame_size;  // floats of one channel
-    da.pcmMode = kPcmFloat;
-    da.channelStride = row;
-    return decode_host_common(ctx, fmt, da, h_stream, h_packet_bytes, num_packets, row * fmt.num_channels * sizeof(float), nullptr,
-                              nullptr, h_out, fmt.num_channels, channel_stride * sizeof(float), h_num_samples_out, nullptr,
-                              nullptr, h_status);
+    const uint64_t row = (uint64_t)num_packets * c.fmt.frame_size;  // floats of one channel
+    float_mode(c, row);
+    HostDecode h{h_stream, h_packet_bytes, num_packets, row * c.fmt.num_channels * sizeof(float)};
+    h.out = h_out, h.pitch = channel_stride * sizeof(float), h.numSamplesOut = h_num_samples_out, h.status = h_status;
+    return decode_host_common(ctx, c, h);
 }
 
 int32_t alac_hip_decode_int_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *h_stream,
                                  const uint32_t *h_packet_bytes, uint32_t num_packets, void *h_out, const alac_hip_int_dest *dst,
                                  uint32_t *h_num_samples_out, int32_t *h_status)
 {
-    alac_hip_format fmt;
-    DecodeArgs da;
-    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
+    DecodeCall c;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, c)) return rc;
     if (num_packets == 0) return ALAC_HIP_noErr;
     if (!h_stream || !h_packet_bytes || !h_num_samples_out || !h_status) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (int32_t rc = int_dest_refusal(ctx, fmt, num_packets, h_out, dst)) return rc;
+    if (int32_t rc = int_dest_refusal(ctx, c.fmt, num_packets, h_out, dst)) return rc;
     // on the device the containers lie as planar rows back to back; the host puts each at the caller's index and leaves the
     // bytes between containers alone
-    const uint64_t T = (uint64_t)num_packets * fmt.frame_size;
+    const uint64_t T = (uint64_t)num_packets * c.fmt.frame_size;
     const uint32_t cb = dst->container_bytes;
     alac_hip_int_dest rows = *dst;
     rows.frame_stride = 1;
     rows.channel_stride = T;
-    const VerifyFloatArgs block = int_dest_args(fmt, rows);
-    da.pcmMode = kPcmInt;
-    da.verifyFloat = &block;
-    std::vector<uint8_t> stage(T * fmt.num_channels * cb);
-    if (int32_t rc = decode_host_common(ctx, fmt, da, h_stream, h_packet_bytes, num_packets, stage.size(), nullptr, nullptr,
-                                        stage.data(), 1, 0, h_num_samples_out, nullptr, nullptr, h_status))
-        return rc;
+    int_mode(c, rows);
+    std::vector<uint8_t> stage(T * c.fmt.num_channels * cb);
+    HostDecode h{h_stream, h_packet_bytes, num_packets, stage.size()};
+    h.out = stage.data(), h.numSamplesOut = h_num_samples_out, h.status = h_status;
+    if (int32_t rc = decode_host_common(ctx, c, h)) return rc;
     const uint8_t *from = stage.data();
-    for (uint32_t c = 0; c < fmt.num_channels; c++)
+    for (uint32_t ch = 0; ch < c.fmt.num_channels; ch++)
         for (uint64_t t = 0; t < T; t++, from += cb)
-            memcpy((uint8_t *)h_out + (c * dst->channel_stride + t * dst->frame_stride) * cb, from, cb);
+            memcpy((uint8_t *)h_out + (ch * dst->channel_stride + t * dst->frame_stride) * cb, from, cb);
     return ALAC_HIP_noErr;
 }
 
@@ -2263,17 +2263,16 @@ int32_t alac_hip_verify_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_
                              const uint32_t *h_packet_bytes, uint32_t num_packets, const uint8_t *h_pcm_expected,
                              const uint32_t *h_num_samples_expected, uint32_t *h_first_mismatch, int32_t *h_status)
 {
-    alac_hip_format fmt;
-    DecodeArgs da;
-    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
+    DecodeCall c;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, c)) return rc;
     if (num_packets == 0) return 0;
     if (!h_stream || !h_packet_bytes || !h_pcm_expected) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
     if (num_packets > 0x7fffffffu) return fail(ctx, ALAC_HIP_ParamError, "more packets than the return value counts");
-    const uint64_t pcmBytes = (uint64_t)num_packets * fmt.frame_size * fmt.num_channels * bytes_per_sample(fmt.bit_depth);
-    uint32_t bad = 0;
-    const int32_t rc = decode_host_common(ctx, fmt, da, h_stream, h_packet_bytes, num_packets, pcmBytes, h_pcm_expected,
-                                          h_num_samples_expected, nullptr, 1, 0, nullptr, h_first_mismatch, &bad, h_status);
-    return rc != ALAC_HIP_noErr ? rc : (int32_t)bad;
+    verify_mode(c);
+    HostDecode h{h_stream, h_packet_bytes, num_packets, packed_pcm_bytes(&c.fmt, num_packets)};
+    h.expected = h_pcm_expected, h.numSamplesExpected = h_num_samples_expected;
+    h.firstMismatch = h_first_mismatch, h.status = h_status;
+    return decode_host_common(ctx, c, h);
 }
 
 int32_t alac_hip_verify_float_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size, const uint8_t *h_stream,
@@ -2282,24 +2281,23 @@ int32_t alac_hip_verify_float_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, u
                                    const alac_hip_dither *dither, const uint64_t *h_packet_origin, uint32_t *h_first_mismatch,
                                    int32_t *h_status)
 {
-    alac_hip_format fmt;
-    DecodeArgs da;
-    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, fmt, da)) return rc;
-    if (int32_t rc = verify_float_refusal(ctx, fmt, num_packets, h_in, channel_stride, frame_stride, dither, h_packet_origin))
+    DecodeCall c;
+    if (int32_t rc = parse_cookie(ctx, h_cookie, cookie_size, c)) return rc;
+    if (int32_t rc = verify_float_refusal(ctx, c.fmt, num_packets, h_in, channel_stride, frame_stride, dither, h_packet_origin))
         return rc;
     if (num_packets == 0) return 0;
     if (!h_stream || !h_packet_bytes) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
     if (num_packets > 0x7fffffffu) return fail(ctx, ALAC_HIP_ParamError, "more packets than the return value counts");
     uint64_t span = 0;
-    if (int32_t rc = float_host_span(ctx, &fmt, h_num_samples_expected, num_packets, channel_stride, frame_stride, span)) return rc;
+    if (int32_t rc = float_host_span(ctx, &c.fmt, h_num_samples_expected, num_packets, channel_stride, frame_stride, span)) return rc;
     // nothing expected anywhere: one float the kernels never load keeps the staged source a buffer
     static const float kNone = 0.0f;
-    const VerifyFloatArgs vf = verify_float_args(channel_stride, frame_stride, dither, nullptr);
-    uint32_t bad = 0;
-    const int32_t rc = decode_host_common(ctx, fmt, da, h_stream, h_packet_bytes, num_packets, (span ? span : 1) * sizeof(float),
-                                          span ? h_in : &kNone, h_num_samples_expected, nullptr, 1, 0, nullptr, h_first_mismatch,
-                                          &bad, h_status, &vf, dither_on(dither) ? h_packet_origin : nullptr);
-    return rc != ALAC_HIP_noErr ? rc : (int32_t)bad;
+    verify_float_mode(c, channel_stride, frame_stride, dither, nullptr);  // (the origins: staged by decode_host_common)
+    HostDecode h{h_stream, h_packet_bytes, num_packets, (span ? span : 1) * sizeof(float)};
+    h.expected = span ? h_in : &kNone, h.numSamplesExpected = h_num_samples_expected;
+    h.origin = dither_on(dither) ? h_packet_origin : nullptr;
+    h.firstMismatch = h_first_mismatch, h.status = h_status;
+    return decode_host_common(ctx, c, h);
 }
 
 }  // extern "C"

@@ -296,7 +296,7 @@ __device__ __forceinline__ void store_sample(const DecodeArgs &A, uint8_t *p, in
 }
 
 template <int DEPTH, int CH, PcmMode MODE>
-__global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A, VerifyFloatArgs F)
+__global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A, PcmModeArgs F)
 {
     if (A.gate && *A.gate == 0) return;
     __shared__ int32_t tu[64][65];
@@ -355,8 +355,8 @@ __global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A, VerifyFloatA
         }
         if constexpr (pcm_by_sample(MODE)) {
             const uint32_t lim = pcm_frames<MODE>(A, F, p, rec->numSamples);
-            pcm_float_put<DEPTH, MODE>(A, F, 0, p, j, lim, l);
-            if constexpr (CH == 2) pcm_float_put<DEPTH, MODE>(A, F, 1, p, j, lim, r);
+            pcm_sample_put<DEPTH, MODE>(A, F, 0, p, j, lim, l);
+            if constexpr (CH == 2) pcm_sample_put<DEPTH, MODE>(A, F, 1, p, j, lim, r);
         } else {
             store_sample<DEPTH, MODE>(A, op, l);
             if constexpr (CH == 2) store_sample<DEPTH, MODE>(A, op + BPS, r);
@@ -370,7 +370,7 @@ __global__ __launch_bounds__(256) void k_decode_unmix(DecodeArgs A, VerifyFloatA
 // written at channel c (and c + 1) of the numChannels-interleaved frame (unmixNN / copyPredictorToNN with stride
 // numChannels, codec/ALACDecoder.cu:733-753,:900-935); channels no element carries are zero (:971-998).
 template <int DEPTH, PcmMode MODE>
-__global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A, VerifyFloatArgs F)
+__global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A, PcmModeArgs F)
 {
     if (A.gate && *A.gate == 0) return;
     __shared__ int32_t tu[64][65];
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A, VerifyFlo
             if (!rec) {
                 const uint32_t ns = A.recs[p].elementChannels ? A.recs[p].numSamples : A.frameSize;
                 if (j < ns) {
-                    if constexpr (pcm_by_sample(MODE)) pcm_float_put<DEPTH, MODE>(A, F, c, p, j, pcm_frames<MODE>(A, F, p, ns), 0);
+                    if constexpr (pcm_by_sample(MODE)) pcm_sample_put<DEPTH, MODE>(A, F, c, p, j, pcm_frames<MODE>(A, F, p, ns), 0);
                     else store_sample<DEPTH, MODE>(A, op, 0);
                 }
                 continue;
@@ -429,8 +429,8 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A, VerifyFlo
             }
             if constexpr (pcm_by_sample(MODE)) {
                 const uint32_t lim = pcm_frames<MODE>(A, F, p, rec->numSamples);
-                pcm_float_put<DEPTH, MODE>(A, F, c, p, j, lim, l);
-                if (ech == 2) pcm_float_put<DEPTH, MODE>(A, F, c + 1, p, j, lim, r);
+                pcm_sample_put<DEPTH, MODE>(A, F, c, p, j, lim, l);
+                if (ech == 2) pcm_sample_put<DEPTH, MODE>(A, F, c + 1, p, j, lim, r);
             } else {
                 store_sample<DEPTH, MODE>(A, op, l);
                 if (ech == 2) store_sample<DEPTH, MODE>(A, op + BPS, r);
@@ -442,43 +442,42 @@ __global__ __launch_bounds__(256) void k_decode_unmix_mc(DecodeArgs A, VerifyFlo
 }
 
 template <int DEPTH, PcmMode MODE>
-static hipError_t launch_unmix_depth(const DecodeArgs &da, hipStream_t st)
+static hipError_t launch_unmix_depth(const DecodeArgs &da, const PcmModeArgs &pm, hipStream_t st)
 {
-    const VerifyFloatArgs vf = pcm_has_block(MODE) ? *da.verifyFloat : VerifyFloatArgs{};
     dim3 grid((da.numPackets + 63) / 64, (da.frameSize + 63) / 64);
     if (da.gate) grid = dim3((uint32_t)std::min<uint64_t>((uint64_t)grid.x * grid.y, 2048), 1);  // (see k_decode_unmix)
     // two channels may arrive as one CPE or as two SCE / LFE elements (codec/ALACDecoder.cu:622-756): the per-element
     // kernel follows the records, k_decode_unmix<., 2> would take the packet for one pair
-    if (da.numChannels >= 2) return launch_kernel(k_decode_unmix_mc<DEPTH, MODE>, grid, dim3(256), st, da, vf);
-    return launch_kernel(k_decode_unmix<DEPTH, 1, MODE>, grid, dim3(256), st, da, vf);
+    if (da.numChannels >= 2) return launch_kernel(k_decode_unmix_mc<DEPTH, MODE>, grid, dim3(256), st, da, pm);
+    return launch_kernel(k_decode_unmix<DEPTH, 1, MODE>, grid, dim3(256), st, da, pm);
 }
 
 // MODE: the un-mix instantiations whose store sites store, compare, write planar floats, compare with a float source or
 // write integer containers (alac_verify.hpp)
 template <PcmMode MODE>
-static hipError_t launch_decode_lanes(const DecodeArgs &da, hipStream_t st)
+static hipError_t launch_decode_lanes(const DecodeArgs &da, const PcmModeArgs &pm, hipStream_t st)
 {
     ALAC_TRY(launch_kernel(k_decode_entropy, dim3((da.numPackets + 63) / 64), dim3(64), st, da));
     const uint64_t lanes = (uint64_t)da.numPackets * da.numChannels;
     ALAC_TRY(launch_kernel(k_decode_unpc, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), st, da));
     switch (da.bitDepth) {
-    case 16: return launch_unmix_depth<16, MODE>(da, st);
-    case 20: return launch_unmix_depth<20, MODE>(da, st);
-    case 24: return launch_unmix_depth<24, MODE>(da, st);
-    case 32: return launch_unmix_depth<32, MODE>(da, st);
+    case 16: return launch_unmix_depth<16, MODE>(da, pm, st);
+    case 20: return launch_unmix_depth<20, MODE>(da, pm, st);
+    case 24: return launch_unmix_depth<24, MODE>(da, pm, st);
+    case 32: return launch_unmix_depth<32, MODE>(da, pm, st);
     default: return hipErrorInvalidValue;
     }
 }
 
-hipError_t launch_decode(const DecodeArgs &da, hipStream_t st)
+hipError_t launch_decode(const DecodeArgs &da, const PcmModeArgs &pm, hipStream_t st)
 {
     if (da.numPackets == 0) return hipSuccess;
     switch (da.pcmMode) {
-    case kPcmStore: return launch_decode_lanes<kPcmStore>(da, st);
-    case kPcmVerify: return launch_decode_lanes<kPcmVerify>(da, st);   // alac_hip_verify
-    case kPcmFloat: return launch_decode_lanes<kPcmFloat>(da, st);     // alac_hip_decode_float
-    case kPcmVerifyFloat: return launch_decode_lanes<kPcmVerifyFloat>(da, st);  // alac_hip_verify_float
-    case kPcmInt: return launch_decode_lanes<kPcmInt>(da, st);         // alac_hip_decode_int
+    case kPcmStore: return launch_decode_lanes<kPcmStore>(da, pm, st);
+    case kPcmVerify: return launch_decode_lanes<kPcmVerify>(da, pm, st);   // alac_hip_verify
+    case kPcmFloat: return launch_decode_lanes<kPcmFloat>(da, pm, st);     // alac_hip_decode_float
+    case kPcmVerifyFloat: return launch_decode_lanes<kPcmVerifyFloat>(da, pm, st);  // alac_hip_verify_float
+    case kPcmInt: return launch_decode_lanes<kPcmInt>(da, pm, st);         // alac_hip_decode_int
     default: return hipErrorInvalidValue;
     }
 }

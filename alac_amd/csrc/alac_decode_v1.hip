@@ -502,7 +502,7 @@ __global__ __launch_bounds__(64 * kHdrWaves) void k_dec_header(DecV1Args V)
 // ---- k_dec_raw: uncompressed (escape) elements are fixed-width fields, i.e. not serial at all: one thread per
 // sample-frame reads its fields straight from the staged words (codec/ALACDecoder.cu:697-727 / :856-896)
 template <bool DIRECT, PcmMode MODE>
-__device__ __forceinline__ void raw_body(const DecV1Args &V, const VerifyFloatArgs &F, uint32_t p, uint32_t first, uint32_t step)
+__device__ __forceinline__ void raw_body(const DecV1Args &V, const PcmModeArgs &F, uint32_t p, uint32_t first, uint32_t step)
 {
     const DecodeArgs &A = V.d;
     const DecRec *rec = A.recs + p;
@@ -517,7 +517,7 @@ __device__ __forceinline__ void raw_body(const DecV1Args &V, const VerifyFloatAr
     // written here as one word per frame instead of going through the plane and k_dec_unmix
     const bool direct = rec->pad2 != 0;
     uint32_t *pcm = (uint32_t *)(A.pcmOut + (uint64_t)p * A.frameSize * 4);
-    const uint32_t lim = pcm_frames<MODE>(A, F, p, n);  // float branches: the frames they may touch
+    const uint32_t lim = pcm_frames<MODE>(A, F, p, n);  // sample branches: the frames they may touch
     // four sample-frames per round, every load of the round issued before its first store: the loop is bound by the
     // chain of dependent round trips per wave, not by bytes (an iteration per frame took 1.24 ms for the 15 600 escape
     // packets of the 125 000-packet benchmark)
@@ -557,8 +557,8 @@ __device__ __forceinline__ void raw_body(const DecV1Args &V, const VerifyFloatAr
                     fl[k] = (int32_t)(o[k] & 0xffffu);
                     fr[k] = (int32_t)(o[k] >> 16);
                 }
-                pcm_float_run<16, MODE>(A, F, 0, p, 4 * g, lim, fl);
-                pcm_float_run<16, MODE>(A, F, 1, p, 4 * g, lim, fr);
+                pcm_sample_run<16, MODE>(A, F, 0, p, 4 * g, lim, fl);
+                pcm_sample_run<16, MODE>(A, F, 1, p, 4 * g, lim, fr);
             } else {
                 const U4 t4 = {o[0], o[1], o[2], o[3]};
                 PCM_PUT(MODE, A, (U4 *)(pcm + 4 * (uint64_t)g), t4);
@@ -595,8 +595,8 @@ __device__ __forceinline__ void raw_body(const DecV1Args &V, const VerifyFloatAr
             }
             if constexpr (pcm_by_sample(MODE)) {
                 if (direct && j < n) {  // direct: 16-bit fields (pad2)
-                    pcm_float_put<16, MODE>(A, F, 0, p, j, lim, (int32_t)f[0]);
-                    pcm_float_put<16, MODE>(A, F, 1, p, j, lim, (int32_t)f[1]);
+                    pcm_sample_put<16, MODE>(A, F, 0, p, j, lim, (int32_t)f[0]);
+                    pcm_sample_put<16, MODE>(A, F, 1, p, j, lim, (int32_t)f[1]);
                 }
             } else {
                 if (direct && j < n) PCM_PUT(MODE, A, pcm + j, f[0] | (f[1] << 16));
@@ -613,7 +613,7 @@ __device__ __host__ inline uint32_t blocks_per_packet(uint32_t frameSize) { retu
 // 500 000 workgroups at 125 000 packets, 15 600 of them with work.
 // (round 3: the packets come from k_dec_header's list of uncompressed elements, so nobody reads records to find them)
 template <PcmMode MODE>
-__global__ __launch_bounds__(256) void k_dec_raw(DecV1Args V, VerifyFloatArgs F)
+__global__ __launch_bounds__(256) void k_dec_raw(DecV1Args V, PcmModeArgs F)
 {
     const DecLists L = dec_lists(V);
     const uint32_t count = L.cnt[4];
@@ -1495,7 +1495,7 @@ __device__ __forceinline__ int32_t lms_step_dec_pair(int32_t (&a)[T], int32_t (&
 }
 
 template <int T, int DEPTH = 16, PcmMode MODE = kPcmStore>
-__device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, const VerifyFloatArgs &F, uint32_t block, uint32_t count)
+__device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, const PcmModeArgs &F, uint32_t block, uint32_t count)
 {
     const DecodeArgs &A = V.d;
     if (block * 32u >= count) return;
@@ -1506,7 +1506,7 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, const VerifyF
     const DecRec *rec = A.recs + p;
     const bool active = idx < count && rec->status == 0;  // a packet the entropy lane gave up on keeps its PCM untouched
     const uint32_t n = active ? rec->numSamples : 0;
-    const uint32_t lim = pcm_frames<MODE>(A, F, p, n);  // float branches: the frames they may touch
+    const uint32_t lim = pcm_frames<MODE>(A, F, p, n);  // sample branches: the frames they may touch
     const uint32_t chanbits = A.bitDepth - (active ? rec->bytesShifted : 0) * 8 + 1;
     const bool is4 = T == 4 || !active || rec->c[ch].num == 4;
     const int32_t act = is4 ? 0 : -1;
@@ -1578,8 +1578,8 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, const VerifyF
             if constexpr (pcm_by_sample(MODE)) {
                 // K / 2 frames of each channel: 16-byte stores, the last frames of a short packet one by one
                 if (active) {
-                    pcm_float_run<DEPTH, MODE>(A, F, 0, p, f0, lim, fl);
-                    pcm_float_run<DEPTH, MODE>(A, F, 1, p, f0, lim, fr);
+                    pcm_sample_run<DEPTH, MODE>(A, F, 0, p, f0, lim, fl);
+                    pcm_sample_run<DEPTH, MODE>(A, F, 1, p, f0, lim, fr);
                 }
             } else if (active && f0 + (uint32_t)(K / 2) <= n) {
                 // four 3-byte fields make three words; K fields = 3 K / 4 words = 3 K / 16 sixteen-byte stores
@@ -1634,8 +1634,8 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, const VerifyF
         const uint32_t f0 = jb + (isU ? 0u : (uint32_t)(K / 2));
         if constexpr (pcm_by_sample(MODE)) {
             if (active) {
-                pcm_float_run<16, MODE>(A, F, 0, p, f0, lim, fl);
-                pcm_float_run<16, MODE>(A, F, 1, p, f0, lim, fr);
+                pcm_sample_run<16, MODE>(A, F, 0, p, f0, lim, fl);
+                pcm_sample_run<16, MODE>(A, F, 1, p, f0, lim, fr);
             }
         } else {
 #pragma unroll
@@ -1724,7 +1724,7 @@ __device__ __forceinline__ void unpc_pair_body(const DecV1Args &V, const VerifyF
 // DEPTH: what the pairs write (16: one word per frame; 20 / 24: six bytes per frame) — one instantiation per output format,
 // so that a launch carries four loop bodies, not eight (they share the CU's instruction cache)
 template <int DEPTH, PcmMode MODE>
-__global__ __launch_bounds__(64 * kEntWavesPerWg) void k_dec_unpc_wide(DecV1Args V, VerifyFloatArgs F)
+__global__ __launch_bounds__(64 * kEntWavesPerWg) void k_dec_unpc_wide(DecV1Args V, PcmModeArgs F)
 {
     const uint32_t *cnt = dec_lists(V).cnt;
     const uint32_t c4 = cnt[0], c8 = cnt[1], pA = cnt[2], pB = cnt[3], cAny = cnt[6];
@@ -1750,7 +1750,7 @@ __global__ __launch_bounds__(64 * kEntWavesPerWg) void k_dec_unpc_wide(DecV1Args
 // elements (nobody waits for them; their dispatch hides under the entropy chain instead of costing a launch of its own).
 constexpr int kFusedPpw = 48;
 template <PcmMode MODE>
-__global__ __launch_bounds__(256, 1) void k_dec_fused_wg(DecV1Args V, uint32_t nEnt, VerifyFloatArgs F)
+__global__ __launch_bounds__(256, 1) void k_dec_fused_wg(DecV1Args V, uint32_t nEnt, PcmModeArgs F)
 {
     __shared__ uint32_t ringOne[64 * kWinStride];
     __shared__ uint32_t progLds[kFusedPpw * 2];
@@ -1803,7 +1803,7 @@ __device__ __forceinline__ void put_sample(const DecodeArgs &A, uint8_t *q, int3
 }
 
 template <int DEPTH, int CH, PcmMode MODE>
-__device__ __forceinline__ void unmix_part(const DecV1Args &V, const VerifyFloatArgs &F, uint32_t p, uint32_t part, uint32_t bx)
+__device__ __forceinline__ void unmix_part(const DecV1Args &V, const PcmModeArgs &F, uint32_t p, uint32_t part, uint32_t bx)
 {
     const DecodeArgs &A = V.d;
     const DecRec *rec = A.recs + p;
@@ -1811,7 +1811,7 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, const VerifyFloat
     // element rounds: a packet that ended before this element leaves these channels zero (codec/ALACDecoder.cu:971-998)
     const bool absent = V.elemBit && rec->elementChannels == 0;
     const uint32_t n = absent ? (V.round ? A.numSamplesOut[p] : A.frameSize) : rec->numSamples;
-    const uint32_t lim = pcm_frames<MODE>(A, F, p, n);  // float branches: the frames they may touch
+    const uint32_t lim = pcm_frames<MODE>(A, F, p, n);  // sample branches: the frames they may touch
     const uint32_t shb = absent ? 0 : rec->bytesShifted;
     const int32_t mixRes = rec->mixRes, mixBits = rec->mixBits;
     const int32_t *u = V.plane + (uint64_t)p * CH * A.frameSize;
@@ -1849,8 +1849,8 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, const VerifyFloat
                     }
                 }
                 if constexpr (pcm_by_sample(MODE)) {
-                    pcm_float_run<16, MODE>(A, F, V.outFirst, p, j, pcm_clamp<MODE>(n4, lim), fl);
-                    pcm_float_run<16, MODE>(A, F, V.outFirst + 1, p, j, pcm_clamp<MODE>(n4, lim), fr);
+                    pcm_sample_run<16, MODE>(A, F, V.outFirst, p, j, pcm_clamp<MODE>(n4, lim), fl);
+                    pcm_sample_run<16, MODE>(A, F, V.outFirst + 1, p, j, pcm_clamp<MODE>(n4, lim), fr);
                 } else {
                     PCM_PUT(MODE, A, (U4 *)(out + (uint64_t)j * 4), o);
                 }
@@ -1867,8 +1867,8 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, const VerifyFloat
                     r = vv;
                 }
                 if constexpr (pcm_by_sample(MODE)) {
-                    pcm_float_put<16, MODE>(A, F, V.outFirst, p, j, lim, l);
-                    pcm_float_put<16, MODE>(A, F, V.outFirst + 1, p, j, lim, r);
+                    pcm_sample_put<16, MODE>(A, F, V.outFirst, p, j, lim, l);
+                    pcm_sample_put<16, MODE>(A, F, V.outFirst + 1, p, j, lim, r);
                 } else {
                     PCM_PUT(MODE, A, (uint32_t *)(out + (uint64_t)j * 4), ((uint32_t)(uint16_t)l) | ((uint32_t)r << 16));
                 }
@@ -1932,8 +1932,8 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, const VerifyFloat
                     s[2 * k + 1] = (uint32_t)r & 0xffffffu;
                 }
                 if constexpr (pcm_by_sample(MODE)) {
-                    pcm_float_run<DEPTH, MODE>(A, F, V.outFirst, p, j, pcm_clamp<MODE>(n4, lim), fl);
-                    pcm_float_run<DEPTH, MODE>(A, F, V.outFirst + 1, p, j, pcm_clamp<MODE>(n4, lim), fr);
+                    pcm_sample_run<DEPTH, MODE>(A, F, V.outFirst, p, j, pcm_clamp<MODE>(n4, lim), fl);
+                    pcm_sample_run<DEPTH, MODE>(A, F, V.outFirst + 1, p, j, pcm_clamp<MODE>(n4, lim), fr);
                 } else {
                     // four 3-byte fields make three words
                     U2 *q = (U2 *)(out + (uint64_t)j * 6);
@@ -1978,8 +1978,8 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, const VerifyFloat
             if constexpr (CH == 2) r = (int32_t)(((uint32_t)r << (shb * 8)) | read_bits(base, nbytes, sp, shb * 8));
         }
         if constexpr (pcm_by_sample(MODE)) {
-            pcm_float_put<DEPTH, MODE>(A, F, V.outFirst, p, j, lim, l);
-            if constexpr (CH == 2) pcm_float_put<DEPTH, MODE>(A, F, V.outFirst + 1, p, j, lim, r);
+            pcm_sample_put<DEPTH, MODE>(A, F, V.outFirst, p, j, lim, l);
+            if constexpr (CH == 2) pcm_sample_put<DEPTH, MODE>(A, F, V.outFirst + 1, p, j, lim, r);
         } else {
             uint8_t *q = out + (uint64_t)j * och * BPS;
             if (DEPTH == 16 && CH == 2 && och == 2) {
@@ -1996,7 +1996,7 @@ __device__ __forceinline__ void unmix_part(const DecV1Args &V, const VerifyFloat
 // packets nobody else writes (with pairs and direct uncompressed elements that is none of the benchmark's packets; launching
 // a workgroup per packet just to read a record and leave cost 0.5 ms at 125 000 packets).
 template <int DEPTH, int CH, PcmMode MODE>
-__global__ __launch_bounds__(256) void k_dec_unmix(DecV1Args V, VerifyFloatArgs F)
+__global__ __launch_bounds__(256) void k_dec_unmix(DecV1Args V, PcmModeArgs F)
 {
     const uint32_t bx = blocks_per_packet(V.d.frameSize);
     if (!V.lists) {
@@ -2009,25 +2009,22 @@ __global__ __launch_bounds__(256) void k_dec_unmix(DecV1Args V, VerifyFloatArgs 
 }
 
 template <int DEPTH, PcmMode MODE>
-static hipError_t launch_unmix_v1(const DecV1Args &V, const VerifyFloatArgs &vf, hipStream_t st)
+static hipError_t launch_unmix_v1(const DecV1Args &V, const PcmModeArgs &pm, hipStream_t st)
 {
     const uint64_t all = (uint64_t)blocks_per_packet(V.d.frameSize) * V.d.numPackets;
     dim3 grid((uint32_t)(V.lists && all > 8192 ? 8192 : all));
-    if (V.d.numChannels == 2) return launch_kernel(k_dec_unmix<DEPTH, 2, MODE>, grid, dim3(256), st, V, vf);
-    return launch_kernel(k_dec_unmix<DEPTH, 1, MODE>, grid, dim3(256), st, V, vf);
+    if (V.d.numChannels == 2) return launch_kernel(k_dec_unmix<DEPTH, 2, MODE>, grid, dim3(256), st, V, pm);
+    return launch_kernel(k_dec_unmix<DEPTH, 1, MODE>, grid, dim3(256), st, V, pm);
 }
 
 // one pass of the pipeline over the elements V describes, after the staging of the stream (stageFirst: the pass stages it
 // itself); MODE: the instantiations whose PCM store sites store, compare (alac_hip_verify), write planar floats
 // (alac_hip_decode_float), compare with a float source (alac_hip_verify_float) or write integer containers (alac_hip_decode_int)
 template <PcmMode MODE>
-static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stageFirst)
+static hipError_t decode_v1_pass(const DecV1Args &V0, const PcmModeArgs &pm, hipStream_t st, bool stageFirst)
 {
     DecV1Args V = V0;
     const DecodeArgs &da = V.d;
-    // verify-float and int modes: their words, the last argument of every kernel that writes PCM (the other modes pass an empty
-    // block)
-    const VerifyFloatArgs vf = pcm_has_block(MODE) ? *da.verifyFloat : VerifyFloatArgs{};
     const uint64_t planeBytes = (uint64_t)da.numPackets * da.numChannels * da.frameSize * 4;
     // One launch (entropy lanes followed by the predictor waves, producer/consumer through HBM) where the chains are few
     // enough that a stage is as slow as its longest serial chain; separate launches where every kernel fills the machine by
@@ -2081,9 +2078,9 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stage
     const uint32_t nEnt = (da.numPackets + 63) / 64;
     if (fused) {
         const uint32_t nEntWg = (da.numPackets + kFusedPpw - 1) / kFusedPpw;
-        ALAC_TRY(launch_kernel(k_dec_fused_wg<MODE>, dim3(nEntWg + (da.numPackets + 3) / 4), dim3(256), st, V, nEntWg, vf));
+        ALAC_TRY(launch_kernel(k_dec_fused_wg<MODE>, dim3(nEntWg + (da.numPackets + 3) / 4), dim3(256), st, V, nEntWg, pm));
     } else {
-        ALAC_TRY(launch_kernel(k_dec_raw<MODE>, dim3(da.numPackets < 4096u ? da.numPackets : 4096u), dim3(256), st, V, vf));
+        ALAC_TRY(launch_kernel(k_dec_raw<MODE>, dim3(da.numPackets < 4096u ? da.numPackets : 4096u), dim3(256), st, V, pm));
         // deferred residual stores, four 16-byte stores per round of sixteen consecutive residuals (round 2, 4-byte stores:
         // paid only up to two entropy waves per SIMD; with the wide stores, measured whole decode pass at 125 000 / 250 000 /
         // 500 000 packets: 9.31 -> 8.19, 19.4 -> 14.2, 38.1 -> 26.5 ms — the kernel was bound by the number of store
@@ -2093,28 +2090,28 @@ static hipError_t decode_v1_pass(const DecV1Args &V0, hipStream_t st, bool stage
         // chains sorted by tap count, one lane per chain
         // (five lists, each rounded up to whole waves)
         const dim3 ugrid(((uint32_t)((lanes + 63) / 64) + 6 + kEntWavesPerWg - 1) / kEntWavesPerWg), ublock(64 * kEntWavesPerWg);
-        if (da.bitDepth == 24) ALAC_TRY(launch_kernel(k_dec_unpc_wide<24, MODE>, ugrid, ublock, st, V, vf));
-        else if (da.bitDepth == 20) ALAC_TRY(launch_kernel(k_dec_unpc_wide<20, MODE>, ugrid, ublock, st, V, vf));
-        else ALAC_TRY(launch_kernel(k_dec_unpc_wide<16, MODE>, ugrid, ublock, st, V, vf));
+        if (da.bitDepth == 24) ALAC_TRY(launch_kernel(k_dec_unpc_wide<24, MODE>, ugrid, ublock, st, V, pm));
+        else if (da.bitDepth == 20) ALAC_TRY(launch_kernel(k_dec_unpc_wide<20, MODE>, ugrid, ublock, st, V, pm));
+        else ALAC_TRY(launch_kernel(k_dec_unpc_wide<16, MODE>, ugrid, ublock, st, V, pm));
     }
     ALAC_TRY(launch_kernel(k_dec_unpc, dim3((uint32_t)((lanes + 63) / 64)), dim3(64), st, V));
     switch (da.bitDepth) {
-    case 16: return launch_unmix_v1<16, MODE>(V, vf, st);
-    case 20: return launch_unmix_v1<20, MODE>(V, vf, st);
-    case 24: return launch_unmix_v1<24, MODE>(V, vf, st);
-    case 32: return launch_unmix_v1<32, MODE>(V, vf, st);
+    case 16: return launch_unmix_v1<16, MODE>(V, pm, st);
+    case 20: return launch_unmix_v1<20, MODE>(V, pm, st);
+    case 24: return launch_unmix_v1<24, MODE>(V, pm, st);
+    case 32: return launch_unmix_v1<32, MODE>(V, pm, st);
     default: return hipErrorInvalidValue;
     }
 }
 
-static hipError_t run_decode_v1_pass(const DecV1Args &V, hipStream_t st, bool stageFirst)
+static hipError_t run_decode_v1_pass(const DecV1Args &V, const PcmModeArgs &pm, hipStream_t st, bool stageFirst)
 {
     switch (V.d.pcmMode) {
-    case kPcmStore: return decode_v1_pass<kPcmStore>(V, st, stageFirst);
-    case kPcmVerify: return decode_v1_pass<kPcmVerify>(V, st, stageFirst);  // alac_hip_verify
-    case kPcmFloat: return decode_v1_pass<kPcmFloat>(V, st, stageFirst);    // alac_hip_decode_float
-    case kPcmVerifyFloat: return decode_v1_pass<kPcmVerifyFloat>(V, st, stageFirst);  // alac_hip_verify_float
-    case kPcmInt: return decode_v1_pass<kPcmInt>(V, st, stageFirst);        // alac_hip_decode_int
+    case kPcmStore: return decode_v1_pass<kPcmStore>(V, pm, st, stageFirst);
+    case kPcmVerify: return decode_v1_pass<kPcmVerify>(V, pm, st, stageFirst);  // alac_hip_verify
+    case kPcmFloat: return decode_v1_pass<kPcmFloat>(V, pm, st, stageFirst);    // alac_hip_decode_float
+    case kPcmVerifyFloat: return decode_v1_pass<kPcmVerifyFloat>(V, pm, st, stageFirst);  // alac_hip_verify_float
+    case kPcmInt: return decode_v1_pass<kPcmInt>(V, pm, st, stageFirst);        // alac_hip_decode_int
     default: return hipErrorInvalidValue;
     }
 }
@@ -2142,13 +2139,13 @@ static DecV1Args decode_v1_args(const DecodeArgs &da, uint32_t *words, uint64_t 
     return V;
 }
 
-hipError_t launch_decode_v1(const DecodeArgs &da, uint32_t *words, uint64_t capWords, int32_t *plane, uint32_t *prog,
-                            hipStream_t st, uint32_t *mismatch)
+hipError_t launch_decode_v1(const DecodeArgs &da, const PcmModeArgs &pm, uint32_t *words, uint64_t capWords, int32_t *plane,
+                            uint32_t *prog, hipStream_t st, uint32_t *mismatch)
 {
     if (da.numPackets == 0) return hipSuccess;
     DecV1Args V = decode_v1_args(da, words, capWords, plane, prog);
     V.mismatch = mismatch;
-    return run_decode_v1_pass(V, st, true);
+    return run_decode_v1_pass(V, pm, st, true);
 }
 
 // counts the packets whose status is `code` (the element-sequence mismatch of launch_decode_v1_elements)
@@ -2158,8 +2155,8 @@ __global__ void k_dec_count_status(const int32_t *status, uint32_t n, int32_t co
     if (i < n && status[i] == code) atomicAdd(count, 1u);
 }
 
-hipError_t launch_decode_v1_elements(const DecodeArgs &da, const McElement *el, uint32_t numElements, uint32_t *words,
-                                     uint64_t capWords, int32_t *plane, uint32_t *prog, uint32_t *elemBit,
+hipError_t launch_decode_v1_elements(const DecodeArgs &da, const PcmModeArgs &pm, const McElement *el, uint32_t numElements,
+                                     uint32_t *words, uint64_t capWords, int32_t *plane, uint32_t *prog, uint32_t *elemBit,
                                      uint32_t *mismatch, hipStream_t st)
 {
     if (da.numPackets == 0) return hipSuccess;
@@ -2175,7 +2172,7 @@ hipError_t launch_decode_v1_elements(const DecodeArgs &da, const McElement *el, 
         V.round = r;
         V.outChannels = da.numChannels;
         V.outFirst = el[r].first;
-        ALAC_TRY(run_decode_v1_pass(V, st, false));
+        ALAC_TRY(run_decode_v1_pass(V, pm, st, false));
     }
     return launch_kernel(k_dec_count_status, dim3((da.numPackets + 255) / 256), dim3(256), st, da.statusOut, da.numPackets, -4, mismatch);
 }

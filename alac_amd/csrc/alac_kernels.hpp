@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <type_traits>
 
@@ -242,13 +243,9 @@ struct DecodeArgs {
     uint8_t *pcmOut;  // verify mode: the caller's EXPECTED PCM, only ever read; float mode: the planar float32 output (alac_verify.hpp)
     uint32_t *numSamplesOut;
     int32_t *statusOut;
-    // The two modes' own words share one slot, and the mode sits in the struct's tail padding: the layout of DecodeArgs (and of
-    // DecV1Args behind it) is the one the store and verify instantiations were compiled against, so their code is unchanged.
-    // Verify-float mode (alac_hip_verify_float) has more words than fit here; they travel in a VerifyFloatArgs block of their
-    // own, the LAST argument of every kernel that writes PCM (an argument behind the existing ones moves no offset).  On the
-    // host the block rides behind verifyFloat in this slot; the kernels of that mode never read the slot.
+    // Each mode's own word shares one slot, and the mode sits in what was the struct's tail padding.  A mode with more words
+    // than fit here (verify-float, int) carries them in a PcmModeArgs block beside this struct (below).
     union {
-        const struct VerifyFloatArgs *verifyFloat;  // verify-float and int modes, HOST pointer: what the launchers pass on by value
         // verify mode (alac_hip_verify): [numPackets] lowest sample-frame whose bytes differ, lowered with atomicMin by every
         // store site of the PCM (PCM_PUT, alac_verify.hpp), which loads and compares instead of storing
         uint32_t *firstMismatch = nullptr;
@@ -257,8 +254,14 @@ struct DecodeArgs {
     uint32_t frameBytes = 0;  // verify mode: bytes of one whole output frame (all channels)
     uint32_t pcmMode = 0;     // PcmMode (alac_verify.hpp): what the PCM store sites do
 };
+// by value in the kernel-argument segment (inside DecV1Args too): the compiled kernels read these offsets
+static_assert(sizeof(DecodeArgs) == 144 && offsetof(DecodeArgs, pcmOut) == 104 && offsetof(DecodeArgs, firstMismatch) == 128 &&
+                  offsetof(DecodeArgs, channelStride) == 128 && offsetof(DecodeArgs, frameBytes) == 136 &&
+                  offsetof(DecodeArgs, pcmMode) == 140,
+              "DecodeArgs layout");
 
-hipError_t launch_decode(const DecodeArgs &da, hipStream_t st);
+struct PcmModeArgs;  // `pm` (below): the words of the call's PCM mode that do not fit in DecodeArgs
+hipError_t launch_decode(const DecodeArgs &da, const PcmModeArgs &pm, hipStream_t st);
 // verify mode (alac_verify.hip): firstMismatch[p] = ~0, *bad = 0 in front of the decode; after it, packets of non-zero status
 // get 0, packets whose decoded frame count differs from the expected one min(decoded, expected), and *bad counts the packets
 // left with a mismatch (numSamplesExpected null = every packet frameSize frames)
@@ -270,8 +273,8 @@ hipError_t launch_verify_finish(const int32_t *status, const uint32_t *numSample
 // chain list and its two counters where the stages are separate launches)
 // mismatch (nullable): device counter of the packets whose elements are not the expected sequence (status -4), cleared and
 // counted by the pipeline itself
-hipError_t launch_decode_v1(const DecodeArgs &da, uint32_t *words, uint64_t capWords, int32_t *plane, uint32_t *prog,
-                            hipStream_t st, uint32_t *mismatch);
+hipError_t launch_decode_v1(const DecodeArgs &da, const PcmModeArgs &pm, uint32_t *words, uint64_t capWords, int32_t *plane,
+                            uint32_t *prog, hipStream_t st, uint32_t *mismatch);
 
 // ---- > 2 channels (alac_multichannel.hip): a packet is a sequence of mono / stereo elements ----
 struct McElement {
@@ -308,8 +311,8 @@ hipError_t launch_scan_sizes(const uint32_t *sizes, uint64_t *offsets, uint32_t 
 // sequence, element r of every packet decoded as the mono / stereo packet that starts where element r - 1 ended
 // (elemBit: numPackets uint32 of scratch).  Packets whose elements are not that sequence end with status -4 and are
 // counted in *mismatch (device): the caller then decodes the batch with launch_decode, which follows any sequence.
-hipError_t launch_decode_v1_elements(const DecodeArgs &da, const McElement *el, uint32_t numElements, uint32_t *words,
-                                     uint64_t capWords, int32_t *plane, uint32_t *prog, uint32_t *elemBit,
+hipError_t launch_decode_v1_elements(const DecodeArgs &da, const PcmModeArgs &pm, const McElement *el, uint32_t numElements,
+                                     uint32_t *words, uint64_t capWords, int32_t *plane, uint32_t *prog, uint32_t *elemBit,
                                      uint32_t *mismatch, hipStream_t st);
 
 // ---- float32 input (alac_float_in.hip): alac_hip_encode_float's quantize pass in front of the encoder ----
@@ -433,29 +436,33 @@ hipError_t launch_pcm_crc(const PcmCrcArgs &a, hipStream_t st);
 uint32_t crc_x8_pow(uint64_t bytes);
 uint32_t crc_mul_host(uint32_t a, uint32_t b);
 
-// ---- verify against a float32 source (alac_hip_verify_float): the words of PcmMode kPcmVerifyFloat (alac_verify.hpp) ----
-// DecodeArgs::pcmOut is the source: sample i of channel c of packet p at
-// pcmOut[c * channelStride + (p * frameSize + i) * frameStride] (floats); only frames i < min(numSamplesExpected[p], frameSize)
-// are ever loaded
-// The same block carries the words of PcmMode kPcmInt (alac_hip_decode_int), in the slots verify-float mode leaves it (the
-// block's layout, an argument of every PCM-writing kernel, stays what the other modes were compiled against):
-// DecodeArgs::pcmOut is the destination, the container of that sample at the same index, in containers of containerBytes
-// bytes (2 int16, 3 packed little-endian, 4 int32); the value is the decoded sample, sign-extended at the stream's depth,
-// shifted left by `shift` (left-justified: 8 * containerBytes - depth; right-justified at S bits: S - depth)
-struct VerifyFloatArgs {
-    uint32_t *firstMismatch;             // [numPackets], as DecodeArgs::firstMismatch in verify mode
+// ---- the words of the PCM modes that have more than fit in DecodeArgs (PcmMode, alac_verify.hpp) ----
+// Sample i of channel c of packet p lives at index c * channelStride + (p * frameSize + i) * frameStride of DecodeArgs::pcmOut.
+//  kPcmVerifyFloat (alac_hip_verify_float): pcmOut is the float32 source, only read, and only at frames
+//      i < min(numSamplesExpected[p], frameSize); firstMismatch as DecodeArgs::firstMismatch in verify mode; dither != 0: the
+//      source was quantized with TPDF dither by dz, as alac_hip_encode_float_dither
+//  kPcmInt (alac_hip_decode_int): pcmOut is the destination, in containers of containerBytes bytes (2 int16, 3 packed
+//      little-endian, 4 int32); the value is the decoded sample, sign-extended at the stream's depth, shifted left by `shift`
+//      (left-justified: 8 * containerBytes - depth; right-justified at S bits: S - depth).  The other words are unused.
+//  every other mode: never read (zero, but for the two tables the host files here for verify mode as well: verify_impl)
+struct PcmModeArgs {
+    uint32_t *firstMismatch;             // [numPackets]
     const uint32_t *numSamplesExpected;  // null: every packet frameSize frames
     uint64_t channelStride, frameStride;
     union {
-        uint32_t dither;                 // != 0: TPDF by dz, as alac_hip_encode_float_dither
-        uint32_t containerBytes;         // int mode
+        uint32_t dither;
+        uint32_t containerBytes;
     };
     union {
         uint32_t pad;
-        uint32_t shift;                  // int mode
+        uint32_t shift;
     };
     FloatDitherArgs dz;
 };
+static_assert(sizeof(PcmModeArgs) == 128 && offsetof(PcmModeArgs, channelStride) == 16 && offsetof(PcmModeArgs, frameStride) == 24 &&
+                  offsetof(PcmModeArgs, dither) == 32 && offsetof(PcmModeArgs, containerBytes) == 32 &&
+                  offsetof(PcmModeArgs, pad) == 36 && offsetof(PcmModeArgs, shift) == 36 && offsetof(PcmModeArgs, dz) == 40,
+              "PcmModeArgs layout");
 
 // ---- stage-level ----
 hipError_t launch_pc_block(const int32_t *in, int32_t *pc, uint32_t rows, uint32_t stride, int32_t num,

@@ -13,20 +13,20 @@
 // With kPcmFloat, DecodeArgs::pcmOut is planar float32: sample j of channel c of packet p at
 // pcm_float_row(A, c, p)[j], the value pcm_float<DEPTH>(sample).  Several sites hand PCM_PUT packed words (two 16-bit
 // samples, four 3-byte fields in three words, single bytes), which a float store cannot be made from, so every site has a
-// float branch of its own in front of the packing, on the sample values it holds; PCM_PUT refuses to compile in float mode,
-// so a site without one cannot slip through.  Where a lane holds four or more consecutive frames of a channel, the float
-// branch writes them with 16-byte stores (pcm_float_run).
+// sample branch of its own in front of the packing, on the sample values it holds (the branch of every mode that works by
+// sample, pcm_by_sample); PCM_PUT refuses to compile in those modes, so a site without one cannot slip through.  The branch
+// calls pcm_sample_put (one sample) or pcm_sample_run (four or more consecutive frames of a channel, which float mode writes
+// with 16-byte stores: pcm_float_run).
 // With kPcmVerifyFloat, DecodeArgs::pcmOut is the caller's float32 SOURCE, only ever read, and the mode's own words travel
-// in a VerifyFloatArgs block that the PCM-writing kernels take as their last argument.  The mode lives in the float branches
-// (those hold sample values, channel and frame before any packing): through pcm_float_put / pcm_float_run a site loads the
-// source float of the sample it would have stored, computes the integer the float encode path stages for it
-// (alac_float_rule.hpp: the one spelling of the rule) and compares that with the decoded sample, sign-extended at the
-// stream's depth.  Every site passes the frame limit pcm_frames gave it — min(decoded, expected, frameSize) — and no
-// address is formed for a frame at or behind it, whatever the packet claims to hold.  Nothing is stored.
-// With kPcmInt, DecodeArgs::pcmOut is the caller's integer destination and the layout travels in the same trailing block
-// (alac_kernels.hpp).  It lives in the float branches too, behind the same two helpers: the sample a site holds, sign-extended
-// at the stream's depth and shifted, goes into its container — 2, 3 or 4 bytes, a packed 3-byte container as exactly its
-// three bytes.
+// in the PcmModeArgs block that the PCM-writing kernels take as their last argument (alac_kernels.hpp).  The mode lives in the
+// sample branches: through pcm_sample_put / pcm_sample_run a site loads the source float of the sample it would have stored,
+// computes the integer the float encode path stages for it (alac_float_rule.hpp: the one spelling of the rule) and compares
+// that with the decoded sample, sign-extended at the stream's depth.  Every site passes the frame limit pcm_frames gave it —
+// min(decoded, expected, frameSize) — and no address is formed for a frame at or behind it, whatever the packet claims to
+// hold.  Nothing is stored.
+// With kPcmInt, DecodeArgs::pcmOut is the caller's integer destination and the layout travels in the same trailing block.  It
+// lives in the sample branches too, behind the same two helpers: the sample a site holds, sign-extended at the stream's depth
+// and shifted, goes into its container — 2, 3 or 4 bytes, a packed 3-byte container as exactly its three bytes.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,10 +37,8 @@
 namespace alacdev {
 
 enum PcmMode : int { kPcmStore = 0, kPcmVerify = 1, kPcmFloat = 2, kPcmVerifyFloat = 3, kPcmInt = 4 };
-// the modes whose sites work on sample values per channel (their float branches)
+// the modes whose sites work on sample values per channel (their sample branches)
 constexpr bool pcm_by_sample(PcmMode m) { return m == kPcmFloat || m == kPcmVerifyFloat || m == kPcmInt; }
-// the modes whose words travel in the trailing VerifyFloatArgs block (the others pass an empty one)
-constexpr bool pcm_has_block(PcmMode m) { return m == kPcmVerifyFloat || m == kPcmInt; }
 
 // float mode: a decoded sample as alac_hip_decode stores it (its low DEPTH bits, sign-extended — a 16-bit sample that a damaged
 // packet let grow past 16 bits wraps as the int16 store wraps it) times 2^-(DEPTH - 1).  The conversion rounds to nearest
@@ -88,7 +86,7 @@ __device__ __forceinline__ void pcm_float_run(float *row, uint32_t f0, uint32_t 
 // frame at or behind min(expected[p], frameSize) is never loaded from the source (a damaged or foreign packet may decode
 // more frames than the caller's tensor holds).  k_verify_finish settles the frames behind the shorter count.
 template <PcmMode MODE>
-__device__ __forceinline__ uint32_t pcm_frames(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t p, uint32_t n)
+__device__ __forceinline__ uint32_t pcm_frames(const DecodeArgs &A, const PcmModeArgs &F, uint32_t p, uint32_t n)
 {
     if constexpr (MODE != kPcmVerifyFloat) return n;
     const uint32_t e = F.numSamplesExpected ? F.numSamplesExpected[p] : A.frameSize;
@@ -103,18 +101,18 @@ __device__ __forceinline__ uint32_t pcm_clamp(uint32_t bound, uint32_t lim)
 }
 
 // the same "plain load of the current minimum, then atomicMin" as pcm_mismatch; the site knows packet and frame
-__device__ __forceinline__ void vf_mismatch(const VerifyFloatArgs &F, uint32_t p, uint32_t frame)
+__device__ __forceinline__ void vf_mismatch(const PcmModeArgs &F, uint32_t p, uint32_t frame)
 {
     uint32_t *slot = F.firstMismatch + p;
     if (frame < __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(slot, frame);
 }
 // source float of frame j (of the batch: p * frameSize + i) of channel c
-__device__ __forceinline__ const float *vf_source(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint64_t j)
+__device__ __forceinline__ const float *vf_source(const DecodeArgs &A, const PcmModeArgs &F, uint32_t c, uint64_t j)
 {
     return (const float *)A.pcmOut + c * F.channelStride + j * F.frameStride;
 }
 // stream frame index of frame 0 of packet p
-__device__ __forceinline__ uint64_t vf_origin(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t p)
+__device__ __forceinline__ uint64_t vf_origin(const DecodeArgs &A, const PcmModeArgs &F, uint32_t p)
 {
     return F.dz.origin ? F.dz.origin[p] : (uint64_t)p * A.frameSize;
 }
@@ -129,7 +127,7 @@ __device__ __forceinline__ bool vf_differs(float x, float d, int32_t got)
 }
 // one sample: frame j of channel c of packet p, decoded value x; nothing happens at or behind lim
 template <int DEPTH>
-__device__ __forceinline__ void vf_sample(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p, uint32_t j,
+__device__ __forceinline__ void vf_sample(const DecodeArgs &A, const PcmModeArgs &F, uint32_t c, uint32_t p, uint32_t j,
                                           uint32_t lim, int32_t x)
 {
     if (j >= lim) return;
@@ -149,7 +147,7 @@ __device__ __forceinline__ void vf_sample(const DecodeArgs &A, const VerifyFloat
 // uniform branches on kernel arguments, not template parameters: a template would double (twice) a mode that already
 // adds an instantiation of every PCM-writing kernel, for a branch that costs one scalar compare per group.
 template <int DEPTH, int NF>
-__device__ __forceinline__ void vf_run(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p, uint32_t f0,
+__device__ __forceinline__ void vf_run(const DecodeArgs &A, const PcmModeArgs &F, uint32_t c, uint32_t p, uint32_t f0,
                                        uint32_t lim, const int32_t (&x)[NF])
 {
     typedef float F4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -188,18 +186,18 @@ __device__ __forceinline__ void vf_run(const DecodeArgs &A, const VerifyFloatArg
 // the value of a container: the decoded sample as alac_hip_decode stores it (the wrap of pcm_float), shifted to its place;
 // the container is the low containerBytes bytes of this word (a right-justified sample arrives sign-extended in them)
 template <int DEPTH>
-__device__ __forceinline__ int32_t pcm_int(const VerifyFloatArgs &F, int32_t x)
+__device__ __forceinline__ int32_t pcm_int(const PcmModeArgs &F, int32_t x)
 {
     const int32_t s = DEPTH == 32 ? x : (int32_t)((uint32_t)x << (32 - DEPTH)) >> (32 - DEPTH);
     return (int32_t)((uint32_t)s << F.shift);
 }
 // index (in containers) of frame 0 of packet p of channel c
-__device__ __forceinline__ uint64_t pi_origin(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p)
+__device__ __forceinline__ uint64_t pi_origin(const DecodeArgs &A, const PcmModeArgs &F, uint32_t c, uint32_t p)
 {
     return c * F.channelStride + (uint64_t)p * A.frameSize * F.frameStride;
 }
 // one container; the three bytes of a packed one as three byte stores (other lanes own the bytes on either side)
-__device__ __forceinline__ void pi_store(const DecodeArgs &A, const VerifyFloatArgs &F, uint64_t at, int32_t v)
+__device__ __forceinline__ void pi_store(const DecodeArgs &A, const PcmModeArgs &F, uint64_t at, int32_t v)
 {
     if (F.containerBytes == 4) {
         ((int32_t *)A.pcmOut)[at] = v;
@@ -217,7 +215,7 @@ __device__ __forceinline__ void pi_store(const DecodeArgs &A, const VerifyFloatA
 // every other layout one store per sample.  Container width and strides are uniform branches on kernel arguments, for the
 // reason vf_run gives.
 template <int DEPTH, int NF>
-__device__ __forceinline__ void pi_run(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p, uint32_t f0,
+__device__ __forceinline__ void pi_run(const DecodeArgs &A, const PcmModeArgs &F, uint32_t c, uint32_t p, uint32_t f0,
                                        uint32_t n, const int32_t (&x)[NF])
 {
     typedef int32_t I4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -247,22 +245,22 @@ __device__ __forceinline__ void pi_run(const DecodeArgs &A, const VerifyFloatArg
     }
 }
 
-// ---- what a float branch calls: float mode stores, verify-float mode compares, int mode stores containers; lim =
+// ---- what a sample branch calls: float mode stores, verify-float mode compares, int mode stores containers; lim =
 // pcm_frames(...) of the packet ----
 template <int DEPTH, PcmMode MODE>
-__device__ __forceinline__ void pcm_float_put(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p, uint32_t j,
+__device__ __forceinline__ void pcm_sample_put(const DecodeArgs &A, const PcmModeArgs &F, uint32_t c, uint32_t p, uint32_t j,
                                               uint32_t lim, int32_t x)
 {
-    static_assert(pcm_by_sample(MODE), "a float branch");
+    static_assert(pcm_by_sample(MODE), "a sample branch");
     if constexpr (MODE == kPcmFloat) pcm_float_row(A, c, p)[j] = pcm_float<DEPTH>(x);
     else if constexpr (MODE == kPcmInt) pi_store(A, F, pi_origin(A, F, c, p) + (uint64_t)j * F.frameStride, pcm_int<DEPTH>(F, x));
     else vf_sample<DEPTH>(A, F, c, p, j, lim, x);
 }
 template <int DEPTH, PcmMode MODE, int NF>
-__device__ __forceinline__ void pcm_float_run(const DecodeArgs &A, const VerifyFloatArgs &F, uint32_t c, uint32_t p, uint32_t f0,
+__device__ __forceinline__ void pcm_sample_run(const DecodeArgs &A, const PcmModeArgs &F, uint32_t c, uint32_t p, uint32_t f0,
                                               uint32_t lim, const int32_t (&x)[NF])
 {
-    static_assert(pcm_by_sample(MODE), "a float branch");
+    static_assert(pcm_by_sample(MODE), "a sample branch");
     if constexpr (MODE == kPcmFloat) pcm_float_run<DEPTH>(pcm_float_row(A, c, p), f0, lim, x);
     else if constexpr (MODE == kPcmInt) pi_run<DEPTH>(A, F, c, p, f0, lim, x);
     else vf_run<DEPTH>(A, F, c, p, f0, lim, x);
@@ -304,7 +302,7 @@ __device__ __forceinline__ void pcm_compare(const DecodeArgs &A, const void *q, 
 
 #define PCM_PUT(MODE, A, ptr, value)                                                              \
     do {                                                                                          \
-        static_assert(!alacdev::pcm_by_sample(MODE), "sample modes: the site's float branch does the work"); \
+        static_assert(!alacdev::pcm_by_sample(MODE), "sample modes: the site's sample branch does the work"); \
         if constexpr ((MODE) == alacdev::kPcmVerify) alacdev::pcm_compare((A), (ptr), *(ptr), (value)); \
         else *(ptr) = (value);                                                                    \
     } while (0)

@@ -94,11 +94,12 @@ int main()
     da.bitDepth = DEPTH;
     da.numChannels = CH;
     da.maxElems = CH;
-    expect_failure("launch_decode", launch_decode(da, st));
+    const PcmModeArgs pm{};  // store mode has no words of its own
+    expect_failure("launch_decode", launch_decode(da, pm, st));
     for (int32_t fused : {-1, 0}) {
         da.optFused = fused;
         expect_failure(fused ? "launch_decode_v1 dec_fused -1" : "launch_decode_v1 dec_fused 0",
-                       launch_decode_v1(da, nullptr, 0, nullptr, nullptr, st, nullptr));
+                       launch_decode_v1(da, pm, nullptr, 0, nullptr, nullptr, st, nullptr));
     }
     da.optFused = -1;
     DecodeArgs d6 = da;
@@ -106,7 +107,7 @@ int main()
     McElement el[kMaxChannels];
     const uint32_t nel = channel_elements(6, el);
     expect_failure("launch_decode_v1_elements",
-                   launch_decode_v1_elements(d6, el, nel, nullptr, 0, nullptr, nullptr, nullptr, nullptr, st));
+                   launch_decode_v1_elements(d6, pm, el, nel, nullptr, 0, nullptr, nullptr, nullptr, nullptr, st));
 
     expect_failure("launch_verify_init", launch_verify_init(nullptr, N, nullptr, st));
     expect_failure("launch_verify_finish", launch_verify_finish(nullptr, nullptr, nullptr, FRAME, N, nullptr, nullptr, st));

@@ -1,0 +1,48 @@
+"""GPU: the refusals of the decode family's ten entry points (decode, decode_float, decode_int, verify, verify_float and
+their host forms) are the ones tests/golden/decode_refusals.json pins: same status, same alac_hip_last_error text, in the
+same order of checks (each case breaks one argument of the accepted call, several cases break two).  The list was recorded by
+tests/make_decode_refusals.py on the library of the commit in front of the one that gave the family one call description;
+this file replays it on the library under test.
+
+A refusal writes nothing: every output buffer, device and host, is filled with a sentinel byte in front of each call and must
+still hold it afterwards.  The one exception is pinned too: alac_hip_verify and alac_hip_verify_float have initialised their
+first-mismatch table and their bad-packet word by the time the decode pass refuses the cookie's AG parameters."""
+import json
+
+import pytest
+
+import make_decode_refusals as rec
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def replay(gpu_ctx):
+    with open(rec.GOLDEN) as f:
+        want = json.load(f)
+    return want, rec.record(gpu_ctx)
+
+
+def key(e):
+    return (e["rig"], e["entry"], e["case"])
+
+
+def test_same_calls_in_the_same_order(replay):
+    want, got = replay
+    assert [key(e) for e in got] == [key(e) for e in want]
+    assert {e["entry"] for e in want if e["status"] < 0} == set(rec.PARAMS)
+
+
+def test_status_and_error_text(replay):
+    want, got = replay
+    diff = [(key(w), (w["status"], w["error"]), (g["status"], g["error"])) for w, g in zip(want, got)
+            if (w["status"], w["error"]) != (g["status"], g["error"])]
+    assert diff == []
+
+
+def test_refusals_write_nothing(replay):
+    want, got = replay
+    diff = [(key(w), w["touched"], g["touched"]) for w, g in zip(want, got) if w["touched"] != g["touched"]]
+    assert diff == []
+    wrote = {key(g)[1:]: g["touched"] for g in got if g["status"] < 0 and g["touched"]}
+    assert all(k in rec.LATE and v == rec.LATE[k] for k, v in wrote.items()), wrote

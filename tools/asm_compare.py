@@ -3,8 +3,9 @@
 
     tools/asm_compare.py before.s after.s [mangled-argument ...]
 
-A kernel that gained a trailing argument has another mangled name: give the argument's mangling (NS_15VerifyFloatArgsE for
-alacdev::VerifyFloatArgs) and it is dropped from every name before the two sides are matched.
+A kernel that gained a trailing argument, or whose argument's type was renamed, has another mangled name: give the argument's
+mangling (NS_11PcmModeArgsE for alacdev::PcmModeArgs; both spellings for a rename) and it is dropped from every name before
+the two sides are matched.
 
 Labels are renumbered by order of first appearance and comments dropped, so that a function whose code did not move compares
 equal whatever was added around it.  Prints the functions only one side has, the ones whose bodies differ (with the count of
