@@ -267,12 +267,11 @@ void ALACEncoder::InitializeSampling(void *d_ip, AudioFormatDescription theInput
     // the table back.  alac_hip_synchronize reads the context's hand-off error word: a consumer wave that gave up waiting for
     // its producer has coded garbage, and the batch must fail instead of being handed out.
     mLastStatus = alachost::encode_host_common(
-        (hipStream_t)alac_hip_stream(mCtx), &fmt, ns.data(), np, segFirst, 1, mState, mStateValid ? 1 : 0, out.get(), outMax,
-        mBatchSizes.data(), &total, wsBytes,
-        [&](uint32_t maxSeg, const uint32_t *dNs, const uint32_t *dSeg, int16_t *dState, int32_t stIn, void *dWs, uint8_t *dOut,
-            uint64_t cap, uint32_t *dSizes, uint64_t *dOffs) {
-            return alac_hip_encode_segmented(mCtx, &fmt, d_ip, dNs, np, dSeg, 1, maxSeg, dState, stIn, dWs, wsBytes, dOut, cap,
-                                             dSizes, dOffs);
+        (hipStream_t)alac_hip_stream(mCtx), &fmt,
+        {ns.data(), np, segFirst, 1, mState, mStateValid ? 1 : 0, out.get(), outMax, mBatchSizes.data(), &total}, wsBytes,
+        [&](const alachost::StagedEncode &d) {
+            return alac_hip_encode_segmented(mCtx, &fmt, d_ip, d.numSamples, np, d.segFirst, 1, d.maxSeg, d.state, d.stateIn, d.ws,
+                                             wsBytes, d.out, d.outCapacity, d.packetBytes, d.offsets);
         },
         [](int32_t code, const char *, hipError_t) { return code; }, [&] { return alac_hip_synchronize(mCtx); });
     const bool ok = mLastStatus == ALAC_HIP_noErr;  // (a failed batch hands out nothing)

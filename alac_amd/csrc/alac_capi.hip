@@ -554,7 +554,208 @@ uint64_t alac_hip_encode_max_output_bytes(const alac_hip_format *fmt, uint32_t n
     return max_output_bytes(fmt, num_packets);
 }
 
-// ---- encode: each public call is checked and described once; encode_core / encode_elements run the description ----------
+// ---- the source of an encode call: packed PCM, float32 at strides, or integers in containers at strides --------------------
+// The largest index a strided source of `channels` channels and `frames` (>= 1) frames can form, (channels - 1) *
+// channel_stride + (frames - 1) * frame_stride; false where it does not fit 64 bits.  Each caller compares `last` with its own
+// byte range: float_stride_refusal refuses last > UINT64_MAX / 4 (an index of exactly UINT64_MAX / 4 passes); host_span,
+// int_source_struct_refusal and float_probe_refusal refuse last >= UINT64_MAX / container.
+static bool largest_index(uint32_t channels, uint64_t channel_stride, uint64_t frames, uint64_t frame_stride, uint64_t &last)
+{
+    uint64_t rows, cols;
+    return !__builtin_mul_overflow((uint64_t)(channels - 1), channel_stride, &rows) &&
+           !__builtin_mul_overflow(frames - 1, frame_stride, &cols) && !__builtin_add_overflow(rows, cols, &last);
+}
+
+// host forms: the containers a call reads lie in [0, span) of the host buffer — up to the last frame a packet's count covers
+// (counts null: frame_size); false where that index overflows 64 bits as a byte offset.  The same strides address the device copy.
+static bool host_span(const alac_hip_format *fmt, const uint32_t *h_num_samples, uint32_t np, uint64_t channel_stride,
+                      uint64_t frame_stride, uint32_t container, uint64_t &span)
+{
+    const uint32_t fs = fmt->frame_size;
+    span = 0;
+    for (uint32_t p = 0; p < np; p++) {
+        const uint32_t n = h_num_samples && h_num_samples[p] < fs ? h_num_samples[p] : fs;
+        uint64_t last;
+        if (!n) continue;
+        if (!largest_index(fmt->num_channels, channel_stride, (uint64_t)p * fs + n, frame_stride, last) ||
+            last >= UINT64_MAX / container)
+            return false;
+        span = last + 1 > span ? last + 1 : span;
+    }
+    return true;
+}
+
+// the staged integer PCM of a batch (+ 64: slack behind the last packet, like the gathered copies of a > 2-channel batch)
+static uint64_t float_stage_bytes(const alac_hip_format *fmt, uint32_t num_packets)
+{
+    return align_up(packed_pcm_bytes(fmt, num_packets) + 64, 256);
+}
+
+// the strides of a float call: the largest index the conversion can form must fit 64 bits as a byte offset
+static int32_t float_stride_refusal(alac_hip_ctx *ctx, const alac_hip_format *fmt, uint32_t num_packets, uint64_t channel_stride,
+                                    uint64_t frame_stride)
+{
+    if (frame_stride == 0) return fail(ctx, ALAC_HIP_ParamError, "frame_stride 0");
+    if (channel_stride == 0 && fmt->num_channels > 1)
+        return fail(ctx, ALAC_HIP_ParamError, "channel_stride 0 with more than one channel");
+    uint64_t last;
+    if (!largest_index(fmt->num_channels, channel_stride, (uint64_t)num_packets * fmt->frame_size, frame_stride, last) ||
+        last > UINT64_MAX / sizeof(float))
+        return fail(ctx, ALAC_HIP_ParamError, "the largest index into d_in overflows 64 bits");
+    return ALAC_HIP_noErr;
+}
+
+// the dither of a call: what is wrong with the caller's struct (nullptr: nothing), and whether it asks for dither at all
+static const char *dither_refusal(const alac_hip_format *fmt, const alac_hip_dither *dither, const uint64_t *packet_origin)
+{
+    if (!dither) return nullptr;
+    if (dither->mode > ALAC_HIP_DITHER_TPDF) return "unknown dither mode";
+    if (dither->reserved != 0) return "alac_hip_dither.reserved is not 0";
+    if (dither->mode == ALAC_HIP_DITHER_NONE) return nullptr;
+    if (fmt->bit_depth == 32) return "no dither at 32 bits: a float32 carries nothing below a 32-bit LSB";
+    if ((uintptr_t)packet_origin & 7) return "misaligned packet origin table (8 B)";
+    return nullptr;
+}
+static bool dither_on(const alac_hip_dither *dither) { return dither && dither->mode == ALAC_HIP_DITHER_TPDF; }
+
+// the Philox words of a call's dither (checked; nullptr or mode NONE: none), d_origin the device table or nullptr
+static bool dither_args(const alac_hip_dither *dither, const uint64_t *d_origin, FloatDitherArgs &dz)
+{
+    dz = {};
+    if (!dither_on(dither)) return false;
+    dz.origin = d_origin;
+    philox_round_keys(dither->seed, dz.roundKey);
+    return true;
+}
+
+// what is wrong with an integer source of `channels` channels and `frames` frames; `in` the device or host pointer.  What
+// alac_hip_pcm_requantize and alac_hip_int_probe both refuse, and alac_hip_decode_int in its destination.
+static int32_t int_source_struct_refusal(alac_hip_ctx *ctx, const void *in, const alac_hip_int_source *src, uint32_t channels,
+                                         uint64_t frames)
+{
+    if (!in || !src) return fail(ctx, ALAC_HIP_ParamError, "null buffer or alac_hip_int_source");
+    const uint32_t cb = src->container_bytes, S = src->bits;
+    if (cb < 2 || cb > 4) return fail(ctx, ALAC_HIP_ParamError, "container_bytes is not 2, 3 or 4");
+    if ((S != 16 && S != 20 && S != 24 && S != 32) || S > 8 * cb)
+        return fail(ctx, ALAC_HIP_ParamError, "bits is not 16, 20, 24 or 32, or above 8 * container_bytes");
+    if (src->reserved != 0) return fail(ctx, ALAC_HIP_ParamError, "alac_hip_int_source.reserved is not 0");
+    if (src->left_justified > 1) return fail(ctx, ALAC_HIP_ParamError, "left_justified is not 0 or 1");
+    if (cb != 3 && ((uintptr_t)in & (cb - 1))) return fail(ctx, ALAC_HIP_ParamError, "buffer not aligned to its container");
+    if (src->frame_stride == 0) return fail(ctx, ALAC_HIP_ParamError, "frame_stride 0");
+    if (src->channel_stride == 0 && channels > 1)
+        return fail(ctx, ALAC_HIP_ParamError, "channel_stride 0 with more than one channel");
+    uint64_t last;
+    if (frames && (!largest_index(channels, src->channel_stride, frames, src->frame_stride, last) || last >= UINT64_MAX / cb))
+        return fail(ctx, ALAC_HIP_ParamError, "the largest index into the buffer overflows 64 bits");
+    return ALAC_HIP_noErr;
+}
+
+// What an encode or conversion call reads.  Packed: whole packets of packed PCM at `in`, nothing else is used.  Float: float32
+// at the strides of `lay` (4-byte containers).  Int: containers as the caller's alac_hip_int_source says (`lay` is its copy;
+// noLayout: the caller passed none, which source_refusal reports).  Float and Int may carry a dither with its origin table, and
+// clip counters (source_dither).  A host form checks the source with the host pointer in `in`, then swaps in what it staged.
+enum class SrcKind { Packed, Float, Int };
+struct EncodeSource {
+    SrcKind kind = SrcKind::Packed;
+    const void *in = nullptr;
+    alac_hip_int_source lay = {};  // container bytes, bits, justification; the strides in containers
+    bool noLayout = false;
+    const alac_hip_dither *dither = nullptr;  // nullable; mode NONE: none
+    const uint64_t *origin = nullptr;         // [numPackets] or null: read with dither only
+    uint32_t *clipped = nullptr;              // [numPackets] or null
+};
+
+static EncodeSource packed_source(const void *pcm) { return {SrcKind::Packed, pcm}; }
+static EncodeSource float_source(const float *in, uint64_t channel_stride, uint64_t frame_stride)
+{
+    return {SrcKind::Float, in, {sizeof(float), 32, 0, 0, channel_stride, frame_stride}};
+}
+static EncodeSource int_source(const void *in, const alac_hip_int_source *src)
+{
+    return {SrcKind::Int, in, src ? *src : alac_hip_int_source{}, !src};
+}
+
+// the dither, origin table and clip counters of a float or integer source; refuses a bad dither struct
+static int32_t source_dither(alac_hip_ctx *ctx, const alac_hip_format *fmt, EncodeSource &s, const alac_hip_dither *dither,
+                             const uint64_t *packet_origin, uint32_t *clipped)
+{
+    if (const char *why = dither_refusal(fmt, dither, packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
+    s.dither = dither, s.origin = packet_origin, s.clipped = clipped;
+    return ALAC_HIP_noErr;
+}
+
+// what a call with packets refuses in a source on the device (an integer source: wherever it lies)
+static int32_t source_refusal(alac_hip_ctx *ctx, const EncodeSource &s, const alac_hip_format *fmt, uint32_t num_packets)
+{
+    switch (s.kind) {
+    case SrcKind::Packed:
+        break;
+    case SrcKind::Float:
+        if (!s.in) return fail(ctx, ALAC_HIP_ParamError, "null d_in");
+        if ((uintptr_t)s.in & 3) return fail(ctx, ALAC_HIP_ParamError, "misaligned d_in (4 B)");
+        return float_stride_refusal(ctx, fmt, num_packets, s.lay.channel_stride, s.lay.frame_stride);
+    case SrcKind::Int:
+        if (int32_t rc = int_source_struct_refusal(ctx, s.in, s.noLayout ? nullptr : &s.lay, fmt->num_channels,
+                                                   (uint64_t)num_packets * fmt->frame_size))
+            return rc;
+        if (dither_on(s.dither) && fmt->bit_depth >= s.lay.bits)
+            return fail(ctx, ALAC_HIP_ParamError, "dither where the target depth is not below the source's: nothing is rounded");
+    }
+    return ALAC_HIP_noErr;
+}
+
+// host forms: what a call with packets refuses in a source in host memory (of floats no alignment), and the bytes of it the call
+// may read.  Floats: an index that overflows inside the packets' counts is reported for h_in, one only whole packets reach for d_in.
+static int32_t source_host_span_bytes(alac_hip_ctx *ctx, const EncodeSource &s, const alac_hip_format *fmt,
+                                      const uint32_t *h_num_samples, uint32_t num_packets, uint64_t &bytes)
+{
+    uint64_t span = 0;
+    switch (s.kind) {
+    case SrcKind::Packed:
+        bytes = packed_pcm_bytes(fmt, num_packets);
+        break;
+    case SrcKind::Float:
+        if (!host_span(fmt, h_num_samples, num_packets, s.lay.channel_stride, s.lay.frame_stride, sizeof(float), span))
+            return fail(ctx, ALAC_HIP_ParamError, "the largest index into h_in overflows 64 bits");
+        bytes = span * sizeof(float);
+        return float_stride_refusal(ctx, fmt, num_packets, s.lay.channel_stride, s.lay.frame_stride);
+    case SrcKind::Int:
+        if (int32_t rc = source_refusal(ctx, s, fmt, num_packets)) return rc;
+        // (no packet reaches further than the whole packets source_refusal has measured)
+        if (!host_span(fmt, h_num_samples, num_packets, s.lay.channel_stride, s.lay.frame_stride, s.lay.container_bytes, span))
+            return fail(ctx, ALAC_HIP_ParamError, "the largest index into the buffer overflows 64 bits");
+        bytes = span * s.lay.container_bytes;
+    }
+    return ALAC_HIP_noErr;
+}
+
+// the conversion of a (checked) float or integer source into packed PCM at `pcm`, enqueued on `st`; a packed source: nothing
+static int32_t source_convert(alac_hip_ctx *ctx, const EncodeSource &s, const alac_hip_format &fmt, hipStream_t st,
+                              const uint32_t *d_num_samples, uint32_t np, void *pcm)
+{
+    FloatDitherArgs dz;
+    const FloatDitherArgs *dither = s.kind != SrcKind::Packed && dither_args(s.dither, s.origin, dz) ? &dz : nullptr;
+    switch (s.kind) {
+    case SrcKind::Packed:
+        break;
+    case SrcKind::Float: {
+        const FloatInArgs a{(const float *)s.in, s.lay.channel_stride, s.lay.frame_stride, d_num_samples, np, fmt.frame_size,
+                            fmt.num_channels, (uint8_t *)pcm, s.clipped};
+        if (hipError_t e = launch_float_to_pcm(fmt.bit_depth, a, st, dither))
+            return fail(ctx, ALAC_HIP_ParamError, "float conversion launch", e);
+        break;
+    }
+    case SrcKind::Int: {
+        const PcmInArgs a{s.in, s.lay.channel_stride, s.lay.frame_stride, d_num_samples, np, fmt.frame_size, fmt.num_channels,
+                          s.lay.container_bytes, s.lay.bits, s.lay.left_justified, (uint8_t *)pcm, s.clipped};
+        if (hipError_t e = launch_pcm_requantize(fmt.bit_depth, a, st, dither))
+            return fail(ctx, ALAC_HIP_ParamError, "integer conversion launch", e);
+    }
+    }
+    return ALAC_HIP_noErr;
+}
+
+// ---- encode: each public call is checked and described once; encode_impl runs the description ----------------------------
 // How a call knows its longest segment (the tap-parallel pipeline runs once per packet position of a segment)
 enum class SegKind {
     Host,    // no table (1), or a table the library read back and checked on the host: no device check
@@ -562,10 +763,13 @@ enum class SegKind {
     Unread,  // a table without a bound: the tap-parallel path reads it back (a host wait)
 };
 
-// one encode batch: its format and buffers, the LPC overrides, the resolved segment count, the stream it runs on
+// One encode batch.  An entry point fills it by steps: encode_format (the format, the stream, LPC and fast mode of the context,
+// and the source: packed_source / float_source / int_source), source_dither, encode_tables, encode_state, encode_buffers;
+// encode_pcm then says where the kernels read packed PCM.
 struct EncodeCall {
     alac_hip_format fmt;
-    const void *pcm;
+    EncodeSource src;
+    const void *pcm;  // a packed source itself, else the stage the conversion fills
     const uint32_t *numSamples;
     uint32_t numPackets;
     const uint32_t *segFirst;  // nullptr: every packet is its own segment (in LPC mode whatever table the caller passes)
@@ -583,18 +787,42 @@ struct EncodeCall {
     bool timed;  // may consume a slot of the armed stage timing
 };
 
-// the description of an encode call under the context's options (no checks)
-static EncodeCall describe_encode(const alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *pcm,
-                                  const uint32_t *num_samples, uint32_t num_packets, const uint32_t *seg_first,
-                                  uint32_t num_segments, uint32_t max_segment_packets, int16_t *state, int32_t state_in,
-                                  void *ws, uint8_t *out, uint32_t *packet_bytes, uint64_t *offsets)
+// the format, the options and the source: refuses a null context and a format the library does not encode
+static int32_t encode_format(alac_hip_ctx *ctx, const alac_hip_format *fmt, const EncodeSource &src, EncodeCall &c)
 {
-    const bool lpc = ctx->opt.lpc != 0;
-    const uint32_t *seg = lpc ? nullptr : seg_first;
-    const SegKind kind = !seg ? SegKind::Host : max_segment_packets ? SegKind::Bound : SegKind::Unread;
-    return {*fmt, pcm, num_samples, num_packets, seg, seg ? num_segments : num_packets, kind, seg ? max_segment_packets : 1,
-            lpc ? nullptr : state, lpc ? 0 : state_in, (uint8_t *)ws, out, packet_bytes, offsets, ctx->stream, lpc,
-            ctx->opt.fastMode != 0, true};
+    if (!ctx) return ALAC_HIP_ParamError;
+    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
+    c.fmt = *fmt, c.src = src, c.stream = ctx->stream;
+    c.lpc = ctx->opt.lpc != 0, c.fast = ctx->opt.fastMode != 0, c.timed = true;
+    return ALAC_HIP_noErr;
+}
+
+// the tables (after the options: LPC mode ignores the caller's segment table); max_segment_packets: 0 for none
+static void encode_tables(EncodeCall &c, const uint32_t *num_samples, uint32_t num_packets, const uint32_t *seg_first,
+                          uint32_t num_segments, uint32_t max_segment_packets)
+{
+    c.numSamples = num_samples, c.numPackets = num_packets, c.segFirst = c.lpc ? nullptr : seg_first;
+    c.numSegments = c.segFirst ? num_segments : num_packets;
+    c.segKind = !c.segFirst ? SegKind::Host : max_segment_packets ? SegKind::Bound : SegKind::Unread;
+    c.maxSeg = c.segFirst ? max_segment_packets : 1;
+}
+
+// the coefficient state (after the options: LPC mode ignores it)
+static void encode_state(EncodeCall &c, int16_t *state, int32_t state_in)
+{
+    c.state = c.lpc ? nullptr : state, c.stateIn = c.lpc ? 0 : state_in;
+}
+
+// the workspace and the outputs on the device
+static void encode_buffers(EncodeCall &c, void *ws, uint8_t *out, uint32_t *packet_bytes, uint64_t *offsets)
+{
+    c.ws = (uint8_t *)ws, c.out = out, c.packetBytes = packet_bytes, c.offsets = offsets;
+}
+
+// where the kernels read packed PCM: a packed source itself, else the stage behind encBytes bytes of workspace (null with it)
+static void encode_pcm(EncodeCall &c, uint64_t encBytes)
+{
+    c.pcm = c.src.kind == SrcKind::Packed ? c.src.in : c.ws ? c.ws + encBytes : nullptr;
 }
 
 // The refusals of an encode call in their order; 0 when it may go ahead (num_packets = 0: after the option refusals).
@@ -699,35 +927,14 @@ static int32_t encode_core(alac_hip_ctx *ctx, const EncodeCall &c)
     const uint32_t num_packets = c.numPackets;
     const EncLayout L = enc_layout(fmt, num_packets, c.numSegments);
     uint8_t *ws = c.ws;
-    EncodeArgs ea;
-    ea.pcm = (const uint8_t *)c.pcm;
-    ea.numSamples = c.numSamples;
-    ea.segFirst = c.segFirst;
-    ea.numSegments = c.numSegments;
-    ea.frameSize = fmt->frame_size;
-    ea.state = c.state;
-    ea.stateIn = c.stateIn;
-    ea.pred = (int32_t *)(ws + L.pred);
-    ea.predStride = L.predStride;
-    ea.bitWords = (uint32_t *)(ws + L.bitWords);
-    ea.wcap = L.wcap;
-    ea.recs = (PacketRec *)(ws + L.recs);
-    ea.packetBytes = c.packetBytes;
     // a table with the caller's bound is not read back (no host wait): the kernels test every entry they use, and a table that
     // contradicts the bound fails the next synchronize
     const bool bound = c.segKind == SegKind::Bound;
-    ea.numPackets = num_packets;
-    ea.segMax = bound ? (c.maxSeg < num_packets ? c.maxSeg : num_packets) : 0xffffffffu;
-    ea.segBad = bound ? (uint32_t *)(ws + L.segBad) : nullptr;
-    PackArgs pa;
-    pa.pcm = ea.pcm;
-    pa.recs = ea.recs;
-    pa.bitWords = ea.bitWords;
-    pa.wcap = L.wcap;
-    pa.frameSize = fmt->frame_size;
-    pa.offsets = c.offsets;
-    pa.out = c.out;
-    pa.segBad = ea.segBad;
+    const EncodeArgs ea{(const uint8_t *)c.pcm, c.numSamples, c.segFirst, c.numSegments, fmt->frame_size, c.state, c.stateIn,
+                        (int32_t *)(ws + L.pred), L.predStride, (uint32_t *)(ws + L.bitWords), L.wcap, (PacketRec *)(ws + L.recs),
+                        c.packetBytes, num_packets, bound ? (c.maxSeg < num_packets ? c.maxSeg : num_packets) : 0xffffffffu,
+                        bound ? (uint32_t *)(ws + L.segBad) : nullptr};
+    PackArgs pa{ea.pcm, ea.recs, ea.bitWords, L.wcap, fmt->frame_size, c.offsets, c.out, ea.segBad};
     constexpr uint32_t EV = kEventBlocks * (kNumStages + 1);
     hipEvent_t *ev = nullptr;
     if (c.timed && ctx->profile && (uint64_t)(ctx->profCalls + 1) * EV <= ctx->events.size())
@@ -767,14 +974,7 @@ static int32_t encode_core(alac_hip_ctx *ctx, const EncodeCall &c)
     if (c.lpc) {
         // Apple's independent packets are in the records and bit strings: the LPC candidates replace channels they beat,
         // then the sizes are scanned and the packets packed again, with the LPC headers
-        LpcArgs la;
-        la.pcm = ea.pcm;
-        la.frameSize = fmt->frame_size;
-        la.recs = ea.recs;
-        la.packetBytes = c.packetBytes;
-        la.bitWords = ea.bitWords;
-        la.wcap = L.wcap;
-        la.lpc = (LpcChan *)(ws + L.total);
+        const LpcArgs la{ea.pcm, fmt->frame_size, ea.recs, c.packetBytes, ea.bitWords, L.wcap, (LpcChan *)(ws + L.total)};
         e = launch_lpc(fmt->bit_depth, fmt->num_channels, la, num_packets, c.stream);
         if (e != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "lpc launch", e);
         pa.lpc = la.lpc;
@@ -825,12 +1025,16 @@ static int32_t encode_elements(alac_hip_ctx *ctx, const EncodeCall &c)
             for (uint32_t k = 0; k < G.count && copyErr == hipSuccess; k++)
                 copyErr = hipMemcpyAsync((uint8_t *)gstate + k * rowBytes, (const uint8_t *)c.state + G.elem[k] * rowBytes,
                                          rowBytes, hipMemcpyDeviceToDevice, st);
-        // the group's segment tables are built on the device: with no bound they are read back (SegKind::Unread).  SetFastMode
-        // is consulted for 2-channel STREAMS only (codec/ALACEncoder.cu:998-1001): the stereo elements of a > 2-channel
-        // stream are searched like everything else; no LPC (refused), no stage timing.
-        const EncodeCall g{element_format(fmt, G.channels), ws + G.gather, ns, G.count * num_packets, seg,
-                           G.count * c.numSegments, c.segKind, c.maxSeg, gstate, c.stateIn, ws + G.sub, ws + G.out,
-                           (uint32_t *)(ws + G.sizes), (uint64_t *)(ws + G.offs), st, false, false, false};
+        // the group's segment tables are built on the device and keep the call's bound: with none they are read back
+        // (SegKind::Unread).  SetFastMode is consulted for 2-channel STREAMS only (codec/ALACEncoder.cu:998-1001): the stereo
+        // elements of a > 2-channel stream are searched like everything else; no LPC (refused), no stage timing.
+        EncodeCall g;
+        g.fmt = element_format(fmt, G.channels), g.src = packed_source(ws + G.gather), g.stream = st;
+        g.lpc = g.fast = g.timed = false;
+        encode_tables(g, ns, G.count * num_packets, seg, G.count * c.numSegments, c.maxSeg);
+        encode_state(g, gstate, c.stateIn);
+        encode_buffers(g, ws + G.sub, ws + G.out, (uint32_t *)(ws + G.sizes), (uint64_t *)(ws + G.offs));
+        encode_pcm(g, 0);
         rc = encode_core(ctx, g);
         if (gstate && rc == ALAC_HIP_noErr)
             for (uint32_t k = 0; k < G.count && copyErr == hipSuccess; k++)
@@ -861,22 +1065,38 @@ static int32_t encode_elements(alac_hip_ctx *ctx, const EncodeCall &c)
     return ALAC_HIP_noErr;
 }
 
-// alac_hip_encode and alac_hip_encode_segmented
-static int32_t encode_device(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm, const uint32_t *d_num_samples,
-                             uint32_t num_packets, const uint32_t *d_seg_first, uint32_t num_segments,
-                             uint32_t max_segment_packets, int16_t *d_state, int32_t state_in, void *d_workspace,
-                             uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity, uint32_t *d_packet_bytes,
-                             uint64_t *d_packet_offsets)
+// a (checked) call's work on its stream: the conversion of its source into the stage, if it has one, then the encode
+static int32_t encode_run(alac_hip_ctx *ctx, const EncodeCall &c)
 {
-    if (!ctx) return ALAC_HIP_ParamError;
-    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
-    const EncodeCall c = describe_encode(ctx, fmt, d_pcm, d_num_samples, num_packets, d_seg_first, num_segments,
-                                         max_segment_packets, d_state, state_in, d_workspace, d_out, d_packet_bytes,
-                                         d_packet_offsets);
-    if (int32_t rc = encode_refusal(ctx, fmt, num_packets, c.numSegments, &c, workspace_bytes, out_capacity)) return rc;
-    if (num_packets == 0) return ALAC_HIP_noErr;
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    if (int32_t rc = source_convert(ctx, c.src, c.fmt, c.stream, c.numSamples, c.numPackets, (void *)c.pcm)) return rc;
     return (c.fmt.num_channels > 2 ? encode_elements : encode_core)(ctx, c);
+}
+
+// Every device form behind its description.  With no packets only the option refusals count.  A float or integer source is
+// checked in front of the buffers; its stage is the last whole 256-byte blocks of the workspace, the encoder gets the rest.
+static int32_t encode_impl(alac_hip_ctx *ctx, EncodeCall &c, uint64_t workspace_bytes, uint64_t out_capacity)
+{
+    const alac_hip_format *fmt = &c.fmt;
+    const uint32_t num_packets = c.numPackets;
+    const bool staged = c.src.kind != SrcKind::Packed;
+    if (num_packets == 0) return encode_refusal(ctx, fmt, 0, c.numSegments, &c, workspace_bytes, out_capacity);
+    uint64_t encBytes = workspace_bytes;
+    if (staged) {
+        if (int32_t rc = source_refusal(ctx, c.src, fmt, num_packets)) return rc;
+        const uint64_t stage = float_stage_bytes(fmt, num_packets);
+        if (workspace_bytes < stage) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+        encBytes = (workspace_bytes - stage) & ~255ull;
+    }
+    encode_pcm(c, encBytes);
+    if (int32_t rc = encode_refusal(ctx, fmt, num_packets, c.numSegments, &c, encBytes, out_capacity)) return rc;
+    // tap-parallel path behind a conversion: a table without a bound is read back before anything is enqueued, and handed on
+    if (staged && c.segKind == SegKind::Unread && fmt->num_channels <= 2 &&
+        !use_lane_encoder(ctx, c.fast && fmt->num_channels == 2)) {
+        if (int32_t rc = read_max_segment(ctx, c.stream, c.segFirst, c.numSegments, num_packets, c.maxSeg)) return rc;
+        c.segKind = SegKind::Host;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    return encode_run(ctx, c);
 }
 
 int32_t alac_hip_encode_segmented(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm,
@@ -885,8 +1105,12 @@ int32_t alac_hip_encode_segmented(alac_hip_ctx *ctx, const alac_hip_format *fmt,
                                   void *d_workspace, uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
                                   uint32_t *d_packet_bytes, uint64_t *d_packet_offsets)
 {
-    return encode_device(ctx, fmt, d_pcm, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets, d_state,
-                         state_in, d_workspace, workspace_bytes, d_out, out_capacity, d_packet_bytes, d_packet_offsets);
+    EncodeCall c;
+    if (int32_t rc = encode_format(ctx, fmt, packed_source(d_pcm), c)) return rc;
+    encode_tables(c, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets);
+    encode_state(c, d_state, state_in);
+    encode_buffers(c, d_workspace, d_out, d_packet_bytes, d_packet_offsets);
+    return encode_impl(ctx, c, workspace_bytes, out_capacity);
 }
 
 int32_t alac_hip_encode(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_pcm,
@@ -895,131 +1119,16 @@ int32_t alac_hip_encode(alac_hip_ctx *ctx, const alac_hip_format *fmt, const voi
                         uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity,
                         uint32_t *d_packet_bytes, uint64_t *d_packet_offsets)
 {
-    return encode_device(ctx, fmt, d_pcm, d_num_samples, num_packets, d_seg_first, num_segments, 0, d_state, state_in,
-                         d_workspace, workspace_bytes, d_out, out_capacity, d_packet_bytes, d_packet_offsets);
+    return alac_hip_encode_segmented(ctx, fmt, d_pcm, d_num_samples, num_packets, d_seg_first, num_segments, 0, d_state, state_in,
+                                     d_workspace, workspace_bytes, d_out, out_capacity, d_packet_bytes, d_packet_offsets);
 }
 
 // ---- float32 input: quantize into a stage at the end of the workspace, then encode from it ---------------------------------
-// the staged integer PCM of a batch (+ 64: slack behind the last packet, like the gathered copies of a > 2-channel batch)
-static uint64_t float_stage_bytes(const alac_hip_format *fmt, uint32_t num_packets)
-{
-    return align_up(packed_pcm_bytes(fmt, num_packets) + 64, 256);
-}
-
 uint64_t alac_hip_encode_float_workspace_bytes(const alac_hip_format *fmt, uint32_t num_packets, uint32_t num_segments)
 {
     if (!format_ok(fmt)) return 0;
     return align_up(alac_hip_encode_workspace_bytes(fmt, num_packets, num_segments), 256) + float_stage_bytes(fmt, num_packets);
 }
-
-// the strides of a float call: the largest index the conversion can form, (C - 1) * channel_stride + (frames - 1) *
-// frame_stride, must fit 64 bits as a byte offset
-static int32_t float_stride_refusal(alac_hip_ctx *ctx, const alac_hip_format *fmt, uint32_t num_packets, uint64_t channel_stride,
-                                    uint64_t frame_stride)
-{
-    const uint32_t C = fmt->num_channels;
-    if (frame_stride == 0) return fail(ctx, ALAC_HIP_ParamError, "frame_stride 0");
-    if (channel_stride == 0 && C > 1) return fail(ctx, ALAC_HIP_ParamError, "channel_stride 0 with more than one channel");
-    uint64_t rows, cols, last;
-    if (__builtin_mul_overflow((uint64_t)(C - 1), channel_stride, &rows) ||
-        __builtin_mul_overflow((uint64_t)num_packets * fmt->frame_size - 1, frame_stride, &cols) ||
-        __builtin_add_overflow(rows, cols, &last) || last > UINT64_MAX / sizeof(float))
-        return fail(ctx, ALAC_HIP_ParamError, "the largest index into d_in overflows 64 bits");
-    return ALAC_HIP_noErr;
-}
-
-// the dither of a call: what is wrong with the caller's struct (nullptr: nothing), and whether it asks for dither at all
-static const char *dither_refusal(const alac_hip_format *fmt, const alac_hip_dither *dither, const uint64_t *packet_origin)
-{
-    if (!dither) return nullptr;
-    if (dither->mode > ALAC_HIP_DITHER_TPDF) return "unknown dither mode";
-    if (dither->reserved != 0) return "alac_hip_dither.reserved is not 0";
-    if (dither->mode == ALAC_HIP_DITHER_NONE) return nullptr;
-    if (fmt->bit_depth == 32) return "no dither at 32 bits: a float32 carries nothing below a 32-bit LSB";
-    if ((uintptr_t)packet_origin & 7) return "misaligned packet origin table (8 B)";
-    return nullptr;
-}
-static bool dither_on(const alac_hip_dither *dither) { return dither && dither->mode == ALAC_HIP_DITHER_TPDF; }
-
-// host forms: the floats a call reads lie in [0, span) of h_in — up to the last frame a packet's count covers (counts
-// null: every packet frame_size frames).  The same strides then address the copy on the device.
-static int32_t float_host_span(alac_hip_ctx *ctx, const alac_hip_format *fmt, const uint32_t *h_num_samples, uint32_t np,
-                               uint64_t channel_stride, uint64_t frame_stride, uint64_t &span)
-{
-    const uint32_t fs = fmt->frame_size;
-    span = 0;
-    for (uint32_t p = 0; p < np; p++) {
-        const uint32_t n = h_num_samples && h_num_samples[p] < fs ? h_num_samples[p] : fs;
-        if (!n) continue;
-        uint64_t rows, cols, last;
-        if (__builtin_mul_overflow((uint64_t)(fmt->num_channels - 1), channel_stride, &rows) ||
-            __builtin_mul_overflow((uint64_t)p * fs + n - 1, frame_stride, &cols) || __builtin_add_overflow(rows, cols, &last) ||
-            last >= UINT64_MAX / sizeof(float))
-            return fail(ctx, ALAC_HIP_ParamError, "the largest index into h_in overflows 64 bits");
-        span = last + 1 > span ? last + 1 : span;
-    }
-    return ALAC_HIP_noErr;
-}
-
-// the Philox words of a call's dither (checked; nullptr or mode NONE: none), d_origin the device table or nullptr
-static bool dither_args(const alac_hip_dither *dither, const uint64_t *d_origin, FloatDitherArgs &dz)
-{
-    dz = {};
-    if (!dither_on(dither)) return false;
-    dz.origin = d_origin;
-    philox_round_keys(dither->seed, dz.roundKey);
-    return true;
-}
-
-// the float conversion into `pcm`.  dither (checked, nullptr or mode NONE: plain rounding) is read here
-static int32_t float_to_pcm_run(alac_hip_ctx *ctx, const alac_hip_format &fmt, hipStream_t st, const float *d_in,
-                                uint64_t channel_stride, uint64_t frame_stride, const uint32_t *d_num_samples, uint32_t np,
-                                void *pcm, uint32_t *d_clipped, const alac_hip_dither *dither, const uint64_t *d_origin)
-{
-    const FloatInArgs a{d_in, channel_stride, frame_stride, d_num_samples, np, fmt.frame_size, fmt.num_channels, (uint8_t *)pcm,
-                        d_clipped};
-    FloatDitherArgs dz;
-    const bool on = dither_args(dither, d_origin, dz);
-    const hipError_t e = launch_float_to_pcm(fmt.bit_depth, a, st, on ? &dz : nullptr);
-    return e == hipSuccess ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "float conversion launch", e);
-}
-
-// the encode of a (checked) call from its stage c.pcm, which the conversion in front of it has filled
-static int32_t encode_staged(alac_hip_ctx *ctx, const EncodeCall &c)
-{
-    return (c.fmt.num_channels > 2 ? encode_elements : encode_core)(ctx, c);
-}
-
-// A device encode call whose source is converted into a stage first (alac_hip_encode_float_dither, alac_hip_encode_int).
-// sourceRefusal(): the checks of the source; convert(c): the conversion into c.pcm, enqueued on c.stream.
-extern "C++" {  // (a template: the one piece of this block without C linkage)
-template <class SourceRefusal, class Convert>
-static int32_t encode_through_stage(alac_hip_ctx *ctx, const alac_hip_format *fmt, const uint32_t *d_num_samples,
-                                    uint32_t num_packets, const uint32_t *d_seg_first, uint32_t num_segments,
-                                    uint32_t max_segment_packets, int16_t *d_state, int32_t state_in, void *d_workspace,
-                                    uint64_t workspace_bytes, uint8_t *d_out, uint64_t out_capacity, uint32_t *d_packet_bytes,
-                                    uint64_t *d_packet_offsets, SourceRefusal sourceRefusal, Convert convert)
-{
-    EncodeCall c = describe_encode(ctx, fmt, nullptr, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets,
-                                   d_state, state_in, d_workspace, d_out, d_packet_bytes, d_packet_offsets);
-    if (num_packets == 0) return encode_refusal(ctx, fmt, 0, c.numSegments, &c, workspace_bytes, out_capacity);
-    if (int32_t rc = sourceRefusal()) return rc;
-    // the stage: the last whole 256-byte blocks of the workspace; the encoder gets everything in front of it
-    const uint64_t stage = float_stage_bytes(fmt, num_packets);
-    if (workspace_bytes < stage) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
-    const uint64_t encBytes = (workspace_bytes - stage) & ~255ull;
-    c.pcm = d_workspace ? (uint8_t *)d_workspace + encBytes : nullptr;
-    if (int32_t rc = encode_refusal(ctx, fmt, num_packets, c.numSegments, &c, encBytes, out_capacity)) return rc;
-    // tap-parallel path: a table without a bound is read back and checked before anything is enqueued, and handed on
-    if (c.segKind == SegKind::Unread && fmt->num_channels <= 2 && !use_lane_encoder(ctx, c.fast && fmt->num_channels == 2)) {
-        if (int32_t rc = read_max_segment(ctx, c.stream, c.segFirst, c.numSegments, num_packets, c.maxSeg)) return rc;
-        c.segKind = SegKind::Host;
-    }
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
-    if (int32_t rc = convert(c)) return rc;
-    return encode_staged(ctx, c);
-}
-}  // extern "C++"
 
 int32_t alac_hip_encode_float(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *d_in, uint64_t channel_stride,
                               uint64_t frame_stride, const uint32_t *d_num_samples, uint32_t num_packets,
@@ -1041,86 +1150,31 @@ int32_t alac_hip_encode_float_dither(alac_hip_ctx *ctx, const alac_hip_format *f
                                      uint64_t *d_packet_offsets, uint32_t *d_clipped, const alac_hip_dither *dither,
                                      const uint64_t *d_packet_origin)
 {
-    if (!ctx) return ALAC_HIP_ParamError;
-    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
-    if (const char *why = dither_refusal(fmt, dither, d_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
-    return encode_through_stage(
-        ctx, fmt, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets, d_state, state_in, d_workspace,
-        workspace_bytes, d_out, out_capacity, d_packet_bytes, d_packet_offsets,
-        [&]() -> int32_t {
-            if (!d_in) return fail(ctx, ALAC_HIP_ParamError, "null d_in");
-            if ((uintptr_t)d_in & 3) return fail(ctx, ALAC_HIP_ParamError, "misaligned d_in (4 B)");
-            return float_stride_refusal(ctx, fmt, num_packets, channel_stride, frame_stride);
-        },
-        [&](const EncodeCall &c) {
-            return float_to_pcm_run(ctx, c.fmt, c.stream, d_in, channel_stride, frame_stride, c.numSamples, c.numPackets,
-                                    (void *)c.pcm, d_clipped, dither, d_packet_origin);
-        });
+    EncodeCall c;
+    if (int32_t rc = encode_format(ctx, fmt, float_source(d_in, channel_stride, frame_stride), c)) return rc;
+    if (int32_t rc = source_dither(ctx, fmt, c.src, dither, d_packet_origin, d_clipped)) return rc;
+    encode_tables(c, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets);
+    encode_state(c, d_state, state_in);
+    encode_buffers(c, d_workspace, d_out, d_packet_bytes, d_packet_offsets);
+    return encode_impl(ctx, c, workspace_bytes, out_capacity);
 }
 
 // ---- integer input of any layout, container and depth: requantize by the integer rule, then encode from the result ------
-// what is wrong with an integer source of `channels` channels and `frames` frames; `in` the device or host pointer.  What
-// alac_hip_pcm_requantize and alac_hip_int_probe both refuse, and alac_hip_decode_int in its destination.
-static int32_t int_source_struct_refusal(alac_hip_ctx *ctx, const void *in, const alac_hip_int_source *src, uint32_t channels,
-                                         uint64_t frames)
-{
-    if (!in || !src) return fail(ctx, ALAC_HIP_ParamError, "null buffer or alac_hip_int_source");
-    const uint32_t cb = src->container_bytes, S = src->bits;
-    if (cb < 2 || cb > 4) return fail(ctx, ALAC_HIP_ParamError, "container_bytes is not 2, 3 or 4");
-    if ((S != 16 && S != 20 && S != 24 && S != 32) || S > 8 * cb)
-        return fail(ctx, ALAC_HIP_ParamError, "bits is not 16, 20, 24 or 32, or above 8 * container_bytes");
-    if (src->reserved != 0) return fail(ctx, ALAC_HIP_ParamError, "alac_hip_int_source.reserved is not 0");
-    if (src->left_justified > 1) return fail(ctx, ALAC_HIP_ParamError, "left_justified is not 0 or 1");
-    if (cb != 3 && ((uintptr_t)in & (cb - 1))) return fail(ctx, ALAC_HIP_ParamError, "buffer not aligned to its container");
-    if (src->frame_stride == 0) return fail(ctx, ALAC_HIP_ParamError, "frame_stride 0");
-    if (src->channel_stride == 0 && channels > 1)
-        return fail(ctx, ALAC_HIP_ParamError, "channel_stride 0 with more than one channel");
-    uint64_t rows, cols, last;
-    if (frames && (__builtin_mul_overflow((uint64_t)(channels - 1), src->channel_stride, &rows) ||
-                   __builtin_mul_overflow(frames - 1, src->frame_stride, &cols) || __builtin_add_overflow(rows, cols, &last) ||
-                   last >= UINT64_MAX / cb))
-        return fail(ctx, ALAC_HIP_ParamError, "the largest index into the buffer overflows 64 bits");
-    return ALAC_HIP_noErr;
-}
-
-// what is wrong with a conversion call's integer source.  After dither_refusal.
-static int32_t int_source_refusal(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *in, const alac_hip_int_source *src,
-                                  uint32_t num_packets, const alac_hip_dither *dither)
-{
-    if (int32_t rc = int_source_struct_refusal(ctx, in, src, fmt->num_channels, (uint64_t)num_packets * fmt->frame_size)) return rc;
-    if (dither_on(dither) && fmt->bit_depth >= src->bits)
-        return fail(ctx, ALAC_HIP_ParamError, "dither where the target depth is not below the source's: nothing is rounded");
-    return ALAC_HIP_noErr;
-}
-
-// the integer conversion into `pcm`.  *src and dither (both checked) are read here
-static int32_t pcm_requantize_run(alac_hip_ctx *ctx, const alac_hip_format &fmt, hipStream_t st, const void *d_in,
-                                  const alac_hip_int_source &src, const uint32_t *d_num_samples, uint32_t np, void *pcm,
-                                  uint32_t *d_clipped, const alac_hip_dither *dither, const uint64_t *d_origin)
-{
-    const PcmInArgs a{d_in, src.channel_stride, src.frame_stride, d_num_samples, np, fmt.frame_size, fmt.num_channels,
-                      src.container_bytes, src.bits, src.left_justified, (uint8_t *)pcm, d_clipped};
-    FloatDitherArgs dz;
-    const bool on = dither_args(dither, d_origin, dz);
-    const hipError_t e = launch_pcm_requantize(fmt.bit_depth, a, st, on ? &dz : nullptr);
-    return e == hipSuccess ? ALAC_HIP_noErr : fail(ctx, ALAC_HIP_ParamError, "integer conversion launch", e);
-}
-
 int32_t alac_hip_pcm_requantize(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *d_in, const alac_hip_int_source *src,
                                 const uint32_t *d_num_samples, uint32_t num_packets, uint8_t *d_pcm_out, uint64_t pcm_capacity,
                                 uint32_t *d_clipped, const alac_hip_dither *dither, const uint64_t *d_packet_origin)
 {
     if (!ctx) return ALAC_HIP_ParamError;
     if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
-    if (const char *why = dither_refusal(fmt, dither, d_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
+    EncodeSource s = int_source(d_in, src);
+    if (int32_t rc = source_dither(ctx, fmt, s, dither, d_packet_origin, d_clipped)) return rc;
     if (num_packets == 0) return ALAC_HIP_noErr;
-    if (int32_t rc = int_source_refusal(ctx, fmt, d_in, src, num_packets, dither)) return rc;
+    if (int32_t rc = source_refusal(ctx, s, fmt, num_packets)) return rc;
     if (!d_pcm_out || ((uintptr_t)d_pcm_out & 15)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned d_pcm_out (16 B)");
     if (pcm_capacity < packed_pcm_bytes(fmt, num_packets))
         return fail(ctx, ALAC_HIP_ParamError, "pcm_capacity below num_packets packets");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
-    return pcm_requantize_run(ctx, *fmt, ctx->stream, d_in, *src, d_num_samples, num_packets, d_pcm_out, d_clipped, dither,
-                              d_packet_origin);
+    return source_convert(ctx, s, *fmt, ctx->stream, d_num_samples, num_packets, d_pcm_out);
 }
 
 uint64_t alac_hip_encode_int_workspace_bytes(const alac_hip_format *fmt, uint32_t num_packets, uint32_t num_segments)
@@ -1135,17 +1189,13 @@ int32_t alac_hip_encode_int(alac_hip_ctx *ctx, const alac_hip_format *fmt, const
                             uint32_t *d_packet_bytes, uint64_t *d_packet_offsets, uint32_t *d_clipped,
                             const alac_hip_dither *dither, const uint64_t *d_packet_origin)
 {
-    if (!ctx) return ALAC_HIP_ParamError;
-    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
-    if (const char *why = dither_refusal(fmt, dither, d_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
-    return encode_through_stage(
-        ctx, fmt, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets, d_state, state_in, d_workspace,
-        workspace_bytes, d_out, out_capacity, d_packet_bytes, d_packet_offsets,
-        [&] { return int_source_refusal(ctx, fmt, d_in, src, num_packets, dither); },
-        [&](const EncodeCall &c) {
-            return pcm_requantize_run(ctx, c.fmt, c.stream, d_in, *src, c.numSamples, c.numPackets, (void *)c.pcm, d_clipped,
-                                      dither, d_packet_origin);
-        });
+    EncodeCall c;
+    if (int32_t rc = encode_format(ctx, fmt, int_source(d_in, src), c)) return rc;
+    if (int32_t rc = source_dither(ctx, fmt, c.src, dither, d_packet_origin, d_clipped)) return rc;
+    encode_tables(c, d_num_samples, num_packets, d_seg_first, num_segments, max_segment_packets);
+    encode_state(c, d_state, state_in);
+    encode_buffers(c, d_workspace, d_out, d_packet_bytes, d_packet_offsets);
+    return encode_impl(ctx, c, workspace_bytes, out_capacity);
 }
 
 // ---- float32 probe: the lossless bit depth of float PCM, per segment of frames ---------------------------------------------
@@ -1182,11 +1232,9 @@ static int32_t float_probe_refusal(alac_hip_ctx *ctx, const float *in, uint32_t 
     if (frame_stride == 0) return fail(ctx, ALAC_HIP_ParamError, "frame_stride 0");
     if (channel_stride == 0 && num_channels > 1)
         return fail(ctx, ALAC_HIP_ParamError, "channel_stride 0 with more than one channel");
-    uint64_t rows, cols, last;
+    uint64_t last;
     if (total_frames &&
-        (__builtin_mul_overflow((uint64_t)(num_channels - 1), channel_stride, &rows) ||
-         __builtin_mul_overflow(total_frames - 1, frame_stride, &cols) || __builtin_add_overflow(rows, cols, &last) ||
-         last >= UINT64_MAX / sizeof(float)))
+        (!largest_index(num_channels, channel_stride, total_frames, frame_stride, last) || last >= UINT64_MAX / sizeof(float)))
         return fail(ctx, ALAC_HIP_ParamError, "the largest index into the input overflows 64 bits");
     return probe_table_refusal(ctx, total_frames, h_seg_first_frame, num_segments, lo, hi);
 }
@@ -1879,35 +1927,48 @@ int32_t alac_hip_dyn_decomp(alac_hip_ctx *ctx, uint32_t mb0, uint32_t pb, uint32
 
 // ---- host-buffer convenience ---------------------------------------------------------------------
 
-// alac_hip_encode_host_segments after the format check (alac_hip_encode_host lands here too)
-static int32_t encode_host_segments(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *h_pcm,
-                                    const uint32_t *h_num_samples, uint32_t num_packets, const uint32_t *h_seg_first,
-                                    uint32_t num_segments, int16_t *h_state, int32_t state_in, uint8_t *h_out,
-                                    uint64_t out_capacity, uint32_t *h_packet_bytes, uint64_t *out_total_bytes)
+// Every host encode form behind its format, source (still the caller's host buffer) and dither.  Staged here: the span of the
+// source the call may read, with dither its origin table, for a float or integer source the clip counters; encode_host_common
+// stages the rest and the call runs as encode_run, a float or integer source through the stage behind its workspace.
+static int32_t encode_host(alac_hip_ctx *ctx, EncodeCall &c, const HostEncode &h)
 {
-    if (out_total_bytes) *out_total_bytes = 0;
-    if (num_packets == 0) return ALAC_HIP_noErr;
-    if (!h_pcm || !h_out || !h_packet_bytes || !h_num_samples || !h_seg_first || num_segments == 0)
+    const alac_hip_format *fmt = &c.fmt;
+    const uint32_t np = h.numPackets, nseg = h.numSegments;
+    if (h.outTotalBytes) *h.outTotalBytes = 0;
+    if (np == 0) return ALAC_HIP_noErr;
+    if (!c.src.in || !h.out || !h.packetBytes || !h.numSamples || !h.segFirst || nseg == 0)
         return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (int32_t rc = host_segment_refusal(ctx, h_seg_first, num_segments, num_packets)) return rc;
-    if (int32_t rc = encode_refusal(ctx, fmt, num_packets, ctx->opt.lpc ? num_packets : num_segments, nullptr, 0, 0)) return rc;
-    const uint32_t np = num_packets, nseg = num_segments;
-    const uint64_t pcmBytes = packed_pcm_bytes(fmt, np);
-    const uint64_t wsBytes = alac_hip_encode_workspace_bytes(fmt, np, ctx->opt.lpc ? np : nseg);
-    DevBuf dPcm;
+    if (int32_t rc = host_segment_refusal(ctx, h.segFirst, nseg, np)) return rc;
+    uint64_t spanBytes = 0;
+    if (int32_t rc = source_host_span_bytes(ctx, c.src, fmt, h.numSamples, np, spanBytes)) return rc;
+    if (int32_t rc = encode_refusal(ctx, fmt, np, c.lpc ? np : nseg, nullptr, 0, 0)) return rc;
+    const bool staged = c.src.kind != SrcKind::Packed, origin = dither_on(c.src.dither) && h.packetOrigin;
+    const uint64_t wsBytes =
+        (staged ? alac_hip_encode_float_workspace_bytes : alac_hip_encode_workspace_bytes)(fmt, np, c.lpc ? np : nseg);
+    const uint64_t encBytes = staged ? (wsBytes - float_stage_bytes(fmt, np)) & ~255ull : wsBytes;
+    DevBuf dIn, dClip, dOrigin;
     hipError_t e;
-    if ((e = dPcm.alloc(pcmBytes))) return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
-    if ((e = hipMemcpyAsync(dPcm.p, h_pcm, pcmBytes, hipMemcpyHostToDevice, ctx->stream)))
+    if ((e = dIn.alloc(spanBytes)) || (staged && (e = dClip.alloc(np * 4ull))) || (origin && (e = dOrigin.alloc(np * 8ull))))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if ((e = hipMemcpyAsync(dIn.p, c.src.in, spanBytes, hipMemcpyHostToDevice, ctx->stream)) ||
+        (origin && (e = hipMemcpyAsync(dOrigin.p, h.packetOrigin, np * 8ull, hipMemcpyHostToDevice, ctx->stream))))
         return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    return encode_host_common(
-        ctx->stream, fmt, h_num_samples, np, h_seg_first, nseg, h_state, state_in, h_out, out_capacity, h_packet_bytes,
-        out_total_bytes, wsBytes,
-        [&](uint32_t maxSeg, const uint32_t *ns, const uint32_t *seg, int16_t *state, int32_t stIn, void *ws, uint8_t *out,
-            uint64_t, uint32_t *sizes, uint64_t *offs) {
-            const EncodeCall c = describe_encode(ctx, fmt, dPcm.p, ns, np, seg, nseg, maxSeg, state, stIn, ws, out, sizes, offs);
-            return (c.fmt.num_channels > 2 ? encode_elements : encode_core)(ctx, c);
+    c.src.in = dIn.p, c.src.origin = (const uint64_t *)dOrigin.p, c.src.clipped = h.clipped ? (uint32_t *)dClip.p : nullptr;
+    const int32_t rc = encode_host_common(
+        ctx->stream, fmt, h, wsBytes,
+        [&](const StagedEncode &d) {
+            encode_tables(c, d.numSamples, np, d.segFirst, nseg, d.maxSeg);
+            encode_state(c, d.state, d.stateIn);
+            encode_buffers(c, d.ws, d.out, d.packetBytes, d.offsets);
+            encode_pcm(c, encBytes);
+            return encode_run(ctx, c);
         },
         on_fail(ctx), [ctx] { return alac_hip_synchronize(ctx); });
+    if (rc != ALAC_HIP_noErr || !h.clipped) return rc;
+    if ((e = hipMemcpyAsync(h.clipped, dClip.p, np * 4ull, hipMemcpyDeviceToHost, ctx->stream)) ||
+        (e = hipStreamSynchronize(ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
+    return ALAC_HIP_noErr;
 }
 
 int32_t alac_hip_encode_host_segments(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *h_pcm,
@@ -1915,10 +1976,10 @@ int32_t alac_hip_encode_host_segments(alac_hip_ctx *ctx, const alac_hip_format *
                                       uint32_t num_segments, int16_t *h_state, int32_t state_in, uint8_t *h_out,
                                       uint64_t out_capacity, uint32_t *h_packet_bytes, uint64_t *out_total_bytes)
 {
-    if (!ctx) return ALAC_HIP_ParamError;
-    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
-    return encode_host_segments(ctx, fmt, h_pcm, h_num_samples, num_packets, h_seg_first, num_segments, h_state, state_in,
-                                h_out, out_capacity, h_packet_bytes, out_total_bytes);
+    EncodeCall c;
+    if (int32_t rc = encode_format(ctx, fmt, packed_source(h_pcm), c)) return rc;
+    return encode_host(ctx, c, {h_num_samples, num_packets, h_seg_first, num_segments, h_state, state_in, h_out, out_capacity,
+                                h_packet_bytes, out_total_bytes});
 }
 
 int32_t alac_hip_encode_float_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *h_in, uint64_t channel_stride,
@@ -1932,57 +1993,6 @@ int32_t alac_hip_encode_float_host(alac_hip_ctx *ctx, const alac_hip_format *fmt
                                              out_total_bytes, h_clipped, nullptr, nullptr);
 }
 
-// A host encode call whose source is converted into a stage first (the host forms of encode_through_stage's callers), after
-// the format and dither checks.  source(spanBytes): the checks of the source and the bytes of h_in the call may read;
-// convert(c, d_in, d_clipped, d_origin): the conversion of the staged source into c.pcm.
-extern "C++" {  // (a template: the one piece of this block without C linkage)
-template <class Source, class Convert>
-static int32_t encode_host_through_stage(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *h_in,
-                                         const uint32_t *h_num_samples, uint32_t num_packets, const uint32_t *h_seg_first,
-                                         uint32_t num_segments, int16_t *h_state, int32_t state_in, uint8_t *h_out,
-                                         uint64_t out_capacity, uint32_t *h_packet_bytes, uint64_t *out_total_bytes,
-                                         uint32_t *h_clipped, const alac_hip_dither *dither, const uint64_t *h_packet_origin,
-                                         Source source, Convert convert)
-{
-    if (out_total_bytes) *out_total_bytes = 0;
-    if (num_packets == 0) return ALAC_HIP_noErr;
-    if (!h_in || !h_out || !h_packet_bytes || !h_num_samples || !h_seg_first || num_segments == 0)
-        return fail(ctx, ALAC_HIP_ParamError, "null buffer");
-    if (int32_t rc = host_segment_refusal(ctx, h_seg_first, num_segments, num_packets)) return rc;
-    const uint32_t np = num_packets, nseg = num_segments;
-    uint64_t spanBytes = 0;
-    if (int32_t rc = source(spanBytes)) return rc;
-    if (int32_t rc = encode_refusal(ctx, fmt, np, ctx->opt.lpc ? np : nseg, nullptr, 0, 0)) return rc;
-    const uint64_t wsBytes = alac_hip_encode_float_workspace_bytes(fmt, np, ctx->opt.lpc ? np : nseg);
-    const uint64_t encBytes = (wsBytes - float_stage_bytes(fmt, np)) & ~255ull;  // the stage behind, as alac_hip_encode_float
-    const bool origin = dither_on(dither) && h_packet_origin;
-    DevBuf dIn, dClip, dOrigin;
-    hipError_t e;
-    if ((e = dIn.alloc(spanBytes)) || (e = dClip.alloc(np * 4ull)) || (origin && (e = dOrigin.alloc(np * 8ull))))
-        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
-    if ((e = hipMemcpyAsync(dIn.p, h_in, spanBytes, hipMemcpyHostToDevice, ctx->stream)) ||
-        (origin && (e = hipMemcpyAsync(dOrigin.p, h_packet_origin, np * 8ull, hipMemcpyHostToDevice, ctx->stream))))
-        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    int32_t rc = encode_host_common(
-        ctx->stream, fmt, h_num_samples, np, h_seg_first, nseg, h_state, state_in, h_out, out_capacity, h_packet_bytes,
-        out_total_bytes, wsBytes,
-        [&](uint32_t maxSeg, const uint32_t *ns, const uint32_t *seg, int16_t *state, int32_t stIn, void *ws, uint8_t *out,
-            uint64_t, uint32_t *sizes, uint64_t *offs) {
-            const EncodeCall c = describe_encode(ctx, fmt, (uint8_t *)ws + encBytes, ns, np, seg, nseg, maxSeg, state, stIn, ws,
-                                                 out, sizes, offs);
-            if (int32_t crc = convert(c, (const void *)dIn.p, h_clipped ? (uint32_t *)dClip.p : nullptr, (const uint64_t *)dOrigin.p))
-                return crc;
-            return encode_staged(ctx, c);
-        },
-        on_fail(ctx), [ctx] { return alac_hip_synchronize(ctx); });
-    if (rc != ALAC_HIP_noErr || !h_clipped) return rc;
-    if ((e = hipMemcpyAsync(h_clipped, dClip.p, np * 4ull, hipMemcpyDeviceToHost, ctx->stream)) ||
-        (e = hipStreamSynchronize(ctx->stream)))
-        return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
-    return ALAC_HIP_noErr;
-}
-}  // extern "C++"
-
 int32_t alac_hip_encode_float_dither_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, const float *h_in,
                                           uint64_t channel_stride, uint64_t frame_stride, const uint32_t *h_num_samples,
                                           uint32_t num_packets, const uint32_t *h_seg_first, uint32_t num_segments,
@@ -1990,37 +2000,11 @@ int32_t alac_hip_encode_float_dither_host(alac_hip_ctx *ctx, const alac_hip_form
                                           uint32_t *h_packet_bytes, uint64_t *out_total_bytes, uint32_t *h_clipped,
                                           const alac_hip_dither *dither, const uint64_t *h_packet_origin)
 {
-    if (!ctx) return ALAC_HIP_ParamError;
-    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
-    if (const char *why = dither_refusal(fmt, dither, h_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
-    return encode_host_through_stage(
-        ctx, fmt, h_in, h_num_samples, num_packets, h_seg_first, num_segments, h_state, state_in, h_out, out_capacity,
-        h_packet_bytes, out_total_bytes, h_clipped, dither, h_packet_origin,
-        [&](uint64_t &spanBytes) -> int32_t {
-            uint64_t span = 0;
-            if (int32_t rc = float_host_span(ctx, fmt, h_num_samples, num_packets, channel_stride, frame_stride, span)) return rc;
-            spanBytes = span * sizeof(float);
-            return float_stride_refusal(ctx, fmt, num_packets, channel_stride, frame_stride);
-        },
-        [&](const EncodeCall &c, const void *d_in, uint32_t *d_clipped, const uint64_t *d_origin) {
-            return float_to_pcm_run(ctx, c.fmt, c.stream, (const float *)d_in, channel_stride, frame_stride, c.numSamples,
-                                    c.numPackets, (void *)c.pcm, d_clipped, dither, d_origin);
-        });
-}
-
-// the bytes of h_in an integer host call may read: float_host_span in containers (after int_source_refusal: no overflow)
-static uint64_t int_host_span_bytes(const alac_hip_format *fmt, const alac_hip_int_source *src, const uint32_t *h_num_samples,
-                                    uint32_t np)
-{
-    const uint32_t fs = fmt->frame_size;
-    uint64_t span = 0;
-    for (uint32_t p = 0; p < np; p++) {
-        const uint32_t n = h_num_samples && h_num_samples[p] < fs ? h_num_samples[p] : fs;
-        if (!n) continue;
-        const uint64_t last = (uint64_t)(fmt->num_channels - 1) * src->channel_stride + ((uint64_t)p * fs + n - 1) * src->frame_stride;
-        span = last + 1 > span ? last + 1 : span;
-    }
-    return span * src->container_bytes;
+    EncodeCall c;
+    if (int32_t rc = encode_format(ctx, fmt, float_source(h_in, channel_stride, frame_stride), c)) return rc;
+    if (int32_t rc = source_dither(ctx, fmt, c.src, dither, h_packet_origin, nullptr)) return rc;
+    return encode_host(ctx, c, {h_num_samples, num_packets, h_seg_first, num_segments, h_state, state_in, h_out, out_capacity,
+                                h_packet_bytes, out_total_bytes, h_clipped, h_packet_origin});
 }
 
 int32_t alac_hip_pcm_requantize_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, const void *h_in,
@@ -2030,14 +2014,15 @@ int32_t alac_hip_pcm_requantize_host(alac_hip_ctx *ctx, const alac_hip_format *f
 {
     if (!ctx) return ALAC_HIP_ParamError;
     if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
-    if (const char *why = dither_refusal(fmt, dither, h_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
+    EncodeSource s = int_source(h_in, src);
+    if (int32_t rc = source_dither(ctx, fmt, s, dither, h_packet_origin, nullptr)) return rc;
     if (num_packets == 0) return ALAC_HIP_noErr;
-    if (int32_t rc = int_source_refusal(ctx, fmt, h_in, src, num_packets, dither)) return rc;
+    uint64_t spanBytes = 0;
+    if (int32_t rc = source_host_span_bytes(ctx, s, fmt, h_num_samples, num_packets, spanBytes)) return rc;
     const uint32_t np = num_packets;
     const uint64_t pcmBytes = packed_pcm_bytes(fmt, np);
     if (!h_pcm_out) return fail(ctx, ALAC_HIP_ParamError, "null h_pcm_out");
     if (pcm_capacity < pcmBytes) return fail(ctx, ALAC_HIP_ParamError, "pcm_capacity below num_packets packets");
-    const uint64_t spanBytes = int_host_span_bytes(fmt, src, h_num_samples, np);
     const bool origin = dither_on(dither) && h_packet_origin;
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
     DevBuf dIn, dNs, dPcm, dClip, dOrigin;
@@ -2049,9 +2034,8 @@ int32_t alac_hip_pcm_requantize_host(alac_hip_ctx *ctx, const alac_hip_format *f
         (h_num_samples && (e = hipMemcpyAsync(dNs.p, h_num_samples, np * 4ull, hipMemcpyHostToDevice, ctx->stream))) ||
         (origin && (e = hipMemcpyAsync(dOrigin.p, h_packet_origin, np * 8ull, hipMemcpyHostToDevice, ctx->stream))))
         return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
-    if (int32_t rc = pcm_requantize_run(ctx, *fmt, ctx->stream, dIn.p, *src, (const uint32_t *)dNs.p, np, dPcm.p,
-                                        h_clipped ? (uint32_t *)dClip.p : nullptr, dither, (const uint64_t *)dOrigin.p))
-        return rc;
+    s.in = dIn.p, s.origin = (const uint64_t *)dOrigin.p, s.clipped = h_clipped ? (uint32_t *)dClip.p : nullptr;
+    if (int32_t rc = source_convert(ctx, s, *fmt, ctx->stream, (const uint32_t *)dNs.p, np, dPcm.p)) return rc;
     if ((e = hipMemcpyAsync(h_pcm_out, dPcm.p, pcmBytes, hipMemcpyDeviceToHost, ctx->stream)) ||
         (h_clipped && (e = hipMemcpyAsync(h_clipped, dClip.p, np * 4ull, hipMemcpyDeviceToHost, ctx->stream))) ||
         (e = hipStreamSynchronize(ctx->stream)))
@@ -2065,21 +2049,11 @@ int32_t alac_hip_encode_int_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, 
                                  uint64_t out_capacity, uint32_t *h_packet_bytes, uint64_t *out_total_bytes,
                                  uint32_t *h_clipped, const alac_hip_dither *dither, const uint64_t *h_packet_origin)
 {
-    if (!ctx) return ALAC_HIP_ParamError;
-    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
-    if (const char *why = dither_refusal(fmt, dither, h_packet_origin)) return fail(ctx, ALAC_HIP_ParamError, why);
-    return encode_host_through_stage(
-        ctx, fmt, h_in, h_num_samples, num_packets, h_seg_first, num_segments, h_state, state_in, h_out, out_capacity,
-        h_packet_bytes, out_total_bytes, h_clipped, dither, h_packet_origin,
-        [&](uint64_t &spanBytes) -> int32_t {
-            if (int32_t rc = int_source_refusal(ctx, fmt, h_in, src, num_packets, dither)) return rc;
-            spanBytes = int_host_span_bytes(fmt, src, h_num_samples, num_packets);
-            return ALAC_HIP_noErr;
-        },
-        [&](const EncodeCall &c, const void *d_in, uint32_t *d_clipped, const uint64_t *d_origin) {
-            return pcm_requantize_run(ctx, c.fmt, c.stream, d_in, *src, c.numSamples, c.numPackets, (void *)c.pcm, d_clipped,
-                                      dither, d_origin);
-        });
+    EncodeCall c;
+    if (int32_t rc = encode_format(ctx, fmt, int_source(h_in, src), c)) return rc;
+    if (int32_t rc = source_dither(ctx, fmt, c.src, dither, h_packet_origin, nullptr)) return rc;
+    return encode_host(ctx, c, {h_num_samples, num_packets, h_seg_first, num_segments, h_state, state_in, h_out, out_capacity,
+                                h_packet_bytes, out_total_bytes, h_clipped, h_packet_origin});
 }
 
 int32_t alac_hip_float_probe_host(alac_hip_ctx *ctx, const float *h_in, uint32_t num_channels, uint64_t channel_stride,
@@ -2169,8 +2143,8 @@ int32_t alac_hip_encode_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, cons
                              uint8_t *h_out, uint64_t out_capacity, uint32_t *h_packet_bytes,
                              uint64_t *out_total_bytes)
 {
-    if (!ctx) return ALAC_HIP_ParamError;
-    if (!format_ok(fmt)) return fail(ctx, ALAC_HIP_ParamError, "unsupported format");
+    EncodeCall c;
+    if (int32_t rc = encode_format(ctx, fmt, packed_source(h_pcm), c)) return rc;
     if (out_total_bytes) *out_total_bytes = 0;
     if (total_samples == 0) return ALAC_HIP_noErr;
     if (!h_pcm || !h_out || !h_packet_bytes) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
@@ -2187,15 +2161,14 @@ int32_t alac_hip_encode_host(alac_hip_ctx *ctx, const alac_hip_format *fmt, cons
     }
     // the last packet may be partial: hand over whole packets (zero padded)
     const uint64_t inBytes = total_samples * bpf, pcmBytes = (uint64_t)np * fmt->frame_size * bpf;
-    const void *src = h_pcm;
     std::vector<uint8_t> padded;
     if (inBytes != pcmBytes) {
         padded.assign(pcmBytes, 0);
         memcpy(padded.data(), h_pcm, inBytes);
-        src = padded.data();
+        c.src.in = padded.data();
     }
-    return encode_host_segments(ctx, fmt, src, ns.data(), np, segFirst.data(), nseg, h_state, state_in, h_out, out_capacity,
-                                h_packet_bytes, out_total_bytes);
+    return encode_host(ctx, c, {ns.data(), np, segFirst.data(), nseg, h_state, state_in, h_out, out_capacity, h_packet_bytes,
+                                out_total_bytes});
 }
 
 int32_t alac_hip_decode_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, uint32_t cookie_size,
@@ -2289,7 +2262,8 @@ int32_t alac_hip_verify_float_host(alac_hip_ctx *ctx, const uint8_t *h_cookie, u
     if (!h_stream || !h_packet_bytes) return fail(ctx, ALAC_HIP_ParamError, "null buffer");
     if (num_packets > 0x7fffffffu) return fail(ctx, ALAC_HIP_ParamError, "more packets than the return value counts");
     uint64_t span = 0;
-    if (int32_t rc = float_host_span(ctx, &c.fmt, h_num_samples_expected, num_packets, channel_stride, frame_stride, span)) return rc;
+    if (!host_span(&c.fmt, h_num_samples_expected, num_packets, channel_stride, frame_stride, sizeof(float), span))
+        return fail(ctx, ALAC_HIP_ParamError, "the largest index into h_in overflows 64 bits");
     // nothing expected anywhere: one float the kernels never load keeps the staged source a buffer
     static const float kNone = 0.0f;
     verify_float_mode(c, channel_stride, frame_stride, dither, nullptr);  // (the origins: staged by decode_host_common)

@@ -45,20 +45,46 @@ int32_t upload_stream(const uint8_t *h_stream, const uint32_t *h_packet_bytes, u
     return ALAC_HIP_noErr;
 }
 
+// The caller's side of a host encode call: what is staged in and where the results go.  What a call does not use stays null.
+struct HostEncode {
+    const uint32_t *numSamples;
+    uint32_t numPackets;
+    const uint32_t *segFirst;
+    uint32_t numSegments;
+    int16_t *state;  // nullable: gets the state back; read first where stateIn is set
+    int32_t stateIn;
+    uint8_t *out;
+    uint64_t outCapacity;
+    uint32_t *packetBytes;
+    uint64_t *outTotalBytes = nullptr;  // nullable: the bytes of the stream, on success
+    uint32_t *clipped = nullptr;  // these two of a float or integer source: staged by alac_capi.hip itself
+    const uint64_t *packetOrigin = nullptr;
+};
+
+// the device side encode_host_common has staged for `launch`; maxSeg: the longest segment of the host table
+struct StagedEncode {
+    uint32_t maxSeg;
+    const uint32_t *numSamples, *segFirst;
+    int16_t *state;
+    int32_t stateIn;
+    void *ws;
+    uint8_t *out;
+    uint64_t outCapacity;
+    uint32_t *packetBytes;
+    uint64_t *offsets;
+};
+
 // The encode calls over host tables: the tables and the state staged to the device, `launch` (the device call on the staged
-// buffers: (maxSeg, num samples, segment table, state, state_in, workspace, out, out capacity, sizes, offsets) -> status),
-// the results copied back, then `wait` (the wait and the hand-off check of the context -> status).  wsBytes: the device
-// call's workspace; h_state (nullable) gets the state back; *out_total_bytes (nullable): the bytes of the stream, on success.
+// buffers: const StagedEncode & -> status), the results copied back, then `wait` (the wait and the hand-off check of the
+// context -> status).  wsBytes: the device call's workspace.
 template <class Launch, class Fail, class Wait>
-int32_t encode_host_common(hipStream_t st, const alac_hip_format *fmt, const uint32_t *h_num_samples, uint32_t num_packets,
-                           const uint32_t *h_seg_first, uint32_t num_segments, int16_t *h_state, int32_t state_in,
-                           uint8_t *h_out, uint64_t out_capacity, uint32_t *h_packet_bytes, uint64_t *out_total_bytes,
-                           uint64_t wsBytes, Launch launch, Fail fail, Wait wait)
+int32_t encode_host_common(hipStream_t st, const alac_hip_format *fmt, const HostEncode &h, uint64_t wsBytes, Launch launch,
+                           Fail fail, Wait wait)
 {
-    const uint32_t np = num_packets, nseg = num_segments;
+    const uint32_t np = h.numPackets, nseg = h.numSegments;
     const uint64_t stateBytes = (uint64_t)nseg * alac_hip_state_int16(fmt) * 2;
     const uint64_t outMax = alac_hip_encode_max_output_bytes(fmt, np);
-    const bool stIn = h_state && state_in;
+    const bool stIn = h.state && h.stateIn;
 
     DevBuf dNs, dSeg, dState, dWs, dOut, dSizes, dOffs;
     hipError_t e;
@@ -66,28 +92,28 @@ int32_t encode_host_common(hipStream_t st, const alac_hip_format *fmt, const uin
         (e = dWs.alloc(wsBytes)) || (e = dOut.alloc(outMax)) || (e = dSizes.alloc(np * 4ull)) ||
         (e = dOffs.alloc((np + 1) * 8ull)))
         return fail(ALAC_HIP_MemFullError, "hipMalloc", e);
-    if ((e = hipMemcpyAsync(dNs.p, h_num_samples, np * 4ull, hipMemcpyHostToDevice, st)) ||
-        (e = hipMemcpyAsync(dSeg.p, h_seg_first, (nseg + 1) * 4ull, hipMemcpyHostToDevice, st)))
+    if ((e = hipMemcpyAsync(dNs.p, h.numSamples, np * 4ull, hipMemcpyHostToDevice, st)) ||
+        (e = hipMemcpyAsync(dSeg.p, h.segFirst, (nseg + 1) * 4ull, hipMemcpyHostToDevice, st)))
         return fail(ALAC_HIP_ParamError, "H2D copy", e);
-    if (stIn && (e = hipMemcpyAsync(dState.p, h_state, stateBytes, hipMemcpyHostToDevice, st)))
+    if (stIn && (e = hipMemcpyAsync(dState.p, h.state, stateBytes, hipMemcpyHostToDevice, st)))
         return fail(ALAC_HIP_ParamError, "H2D state", e);
     uint32_t maxSeg = 1;
     for (uint32_t s = 0; s < nseg; s++)
-        maxSeg = h_seg_first[s + 1] - h_seg_first[s] > maxSeg ? h_seg_first[s + 1] - h_seg_first[s] : maxSeg;
-    if (int32_t rc = launch(maxSeg, (const uint32_t *)dNs.p, (const uint32_t *)dSeg.p, (int16_t *)dState.p, stIn ? 1 : 0,
-                            dWs.p, (uint8_t *)dOut.p, outMax, (uint32_t *)dSizes.p, (uint64_t *)dOffs.p))
+        maxSeg = h.segFirst[s + 1] - h.segFirst[s] > maxSeg ? h.segFirst[s + 1] - h.segFirst[s] : maxSeg;
+    if (int32_t rc = launch(StagedEncode{maxSeg, (const uint32_t *)dNs.p, (const uint32_t *)dSeg.p, (int16_t *)dState.p,
+                                         stIn ? 1 : 0, dWs.p, (uint8_t *)dOut.p, outMax, (uint32_t *)dSizes.p, (uint64_t *)dOffs.p}))
         return rc;
     uint64_t total = 0;
     if ((e = hipMemcpyAsync(&total, (uint64_t *)dOffs.p + np, 8, hipMemcpyDeviceToHost, st)) || (e = hipStreamSynchronize(st)))
         return fail(ALAC_HIP_ParamError, "encode execution", e);
-    if (total > out_capacity) return fail(ALAC_HIP_MemFullError, "host output buffer too small", hipSuccess);
-    if ((e = hipMemcpyAsync(h_out, dOut.p, total, hipMemcpyDeviceToHost, st)) ||
-        (e = hipMemcpyAsync(h_packet_bytes, dSizes.p, np * 4ull, hipMemcpyDeviceToHost, st)))
+    if (total > h.outCapacity) return fail(ALAC_HIP_MemFullError, "host output buffer too small", hipSuccess);
+    if ((e = hipMemcpyAsync(h.out, dOut.p, total, hipMemcpyDeviceToHost, st)) ||
+        (e = hipMemcpyAsync(h.packetBytes, dSizes.p, np * 4ull, hipMemcpyDeviceToHost, st)))
         return fail(ALAC_HIP_ParamError, "D2H copy", e);
-    if (h_state && (e = hipMemcpyAsync(h_state, dState.p, stateBytes, hipMemcpyDeviceToHost, st)))
+    if (h.state && (e = hipMemcpyAsync(h.state, dState.p, stateBytes, hipMemcpyDeviceToHost, st)))
         return fail(ALAC_HIP_ParamError, "D2H state", e);
     if (int32_t rc = wait()) return rc;
-    if (out_total_bytes) *out_total_bytes = total;
+    if (h.outTotalBytes) *h.outTotalBytes = total;
     return ALAC_HIP_noErr;
 }
 

@@ -53,6 +53,7 @@ LATE = {("verify", "cookie kb 0"): ["fm", "bad"], ("verify_float", "cookie kb 0"
 
 class Rig:
     """one stream of PACKETS packets, its inputs on both sides, and sentinel-filled outputs on both sides"""
+    params = PARAMS  # entry point -> its parameter names (tests/make_encode_refusals.py: the encode family's)
 
     def __init__(self, ctx, name, depth, channels):
         import torch
@@ -121,7 +122,7 @@ class Rig:
     def call(self, entry, over):
         b = self.base()
         b.update(over)
-        args = [C.byref(b[p]) if isinstance(b[p], C.Structure) else b[p] for p in PARAMS[entry].split()]
+        args = [C.byref(b[p]) if isinstance(b[p], C.Structure) else b[p] for p in self.params[entry].split()]
         h = None if over.get("ctx", 1) is None else self.ctx.h
         rc = getattr(self.ctx.lib, "alac_hip_" + entry)(h, *args)
         self.ctx.lib.alac_hip_synchronize(self.ctx.h)
