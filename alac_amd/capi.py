@@ -61,6 +61,12 @@ class PcmDigest(C.Structure):
     _fields_ = [("bytes", C.c_uint64), ("crc32", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class LoudnessReport(C.Structure):
+    """alac_hip_loudness_report: one per segment of alac_hip_loudness_int / _float, 32 bytes"""
+    _fields_ = [("first_block", C.c_uint32), ("num_blocks", C.c_uint32), ("peak", C.c_double), ("nonfinite", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+
 # what a lane, a wave, a block and one pass of the whole grid of k_pcm_crc take (alac_kernels.hpp, alac_pcm_crc.hip): the sizes
 # at which the kernel changes path, for the tests
 PCM_CRC_LANE_BYTES = 64
@@ -151,6 +157,14 @@ SIGNATURES = {
     "alac_hip_pcm_crc32": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp]),
     "alac_hip_pcm_crc32_host": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp]),
     "alac_hip_crc32_combine": (_u32, [_u32, _u32, _u64]),
+    "alac_hip_loudness_workspace_bytes": (_u64, [_u32, _u32, _u64, _u32]),
+    "alac_hip_loudness_int": (_i32, [_vp, _vp, _vp, _u32, _u32, _u64, _vp, _u32, _vp, _u64, _vp, _u64, _vp]),
+    "alac_hip_loudness_float": (_i32, [_vp, _vp, _u32, _u64, _u64, _u32, _u64, _vp, _u32, _vp, _u64, _vp, _u64, _vp]),
+    "alac_hip_loudness_int_host": (_i32, [_vp, _vp, _vp, _u32, _u32, _u64, _vp, _u32, _vp, _u64, _vp]),
+    "alac_hip_loudness_float_host": (_i32, [_vp, _vp, _u32, _u64, _u64, _u32, _u64, _vp, _u32, _vp, _u64, _vp]),
+    "alac_hip_loudness_filter": (_i32, [_u32, _vp]),
+    "alac_hip_loudness_rows": (_u64, [_u32, _u64, _vp, _u32]),
+    "alac_hip_loudness_integrated": (_i32, [_vp, _u64, _u32, _u32, _vp, C.POINTER(C.c_double)]),
     "alac_synth_frame": (None, [_u64, _u32, _u32, _u32, _vp]),
     "alac_synth_pcm": (None, [_u64, _u32, _u32, _u32, _u32, _vp]),
     "alac_hip_synth_pcm": (_i32, [_vp, _u64, _u32, C.POINTER(Format), _vp]),
@@ -232,6 +246,41 @@ def crc32_combine(crc_a, crc_b, len_b):
     """zlib.crc32(A + B) from crc_a = zlib.crc32(A), crc_b = zlib.crc32(B) and len_b = len(B) (alac_hip_crc32_combine):
     host only, no GPU needed"""
     return int(load_library().alac_hip_crc32_combine(int(crc_a) & 0xFFFFFFFF, int(crc_b) & 0xFFFFFFFF, int(len_b)))
+
+
+def loudness_filter(sample_rate):
+    """alac_hip_loudness_filter: the K-weighting biquads of a sample rate as a float64 array {b0, b1, b2, a1, a2} of the
+    shelf, then of the high-pass.  Host only, no GPU needed."""
+    out = np.zeros(10, dtype=np.float64)
+    if load_library().alac_hip_loudness_filter(int(sample_rate), out.ctypes.data) != 0:
+        raise ValueError("loudness_filter: the sample rate must be a multiple of 10 in [8000, 384000]")
+    return out
+
+
+def loudness_rows(sample_rate, total_frames, seg_first_frame=None):
+    """alac_hip_loudness_rows: the 100 ms rows the segments of a table have in all.  Host only."""
+    table = None if seg_first_frame is None else np.ascontiguousarray(seg_first_frame, dtype=np.uint64)
+    return int(load_library().alac_hip_loudness_rows(int(sample_rate), int(total_frames),
+                                                     None if table is None else table.ctypes.data,
+                                                     1 if table is None else table.size - 1))
+
+
+def integrated_loudness(energy, hop, weights=None):
+    """alac_hip_loudness_integrated: the gated BS.1770 loudness in LUFS of the rows [blocks, channels] of ONE segment
+    (float64; hop = sample_rate // 10); weights None: BS.1770's in the ALAC channel order.  -inf where no block passes the
+    gates.  Host only, no GPU needed."""
+    e = np.ascontiguousarray(energy, dtype=np.float64)
+    if e.ndim != 2 or not 1 <= e.shape[1] <= 8:
+        raise ValueError("integrated_loudness: energy must be [blocks, channels] with 1..8 channels")
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    if w is not None and w.shape != (e.shape[1],):
+        raise ValueError("integrated_loudness: one weight per channel")
+    out = C.c_double(0.0)
+    rc = load_library().alac_hip_loudness_integrated(e.ctypes.data if e.size else None, e.shape[0], e.shape[1], int(hop),
+                                                     None if w is None else w.ctypes.data, C.byref(out))
+    if rc != 0:
+        raise ValueError("integrated_loudness: bad arguments")
+    return out.value
 
 
 def synth_pcm(first_frame, num_frames, fmt):
@@ -627,6 +676,76 @@ class Context:
         self.synchronize()
         rows = np.ascontiguousarray(reports.cpu().numpy())
         return [int(self.lib.alac_hip_int_report_depth(rows[s].ctypes.data)) for s in range(rows.shape[0])]
+
+    def _loudness(self, what, channels, sample_rate, frames, seg_first_frame, call):
+        """the part loudness_int() and loudness_float() share: the table, the outputs and the workspace; call(table pointer,
+        num_segments, workspace, rows tensor, row count, reports tensor) -> status"""
+        t = self.torch
+        table = None if seg_first_frame is None else np.ascontiguousarray(seg_first_frame, dtype=np.uint64)
+        if table is not None and (table.ndim != 1 or table.size < 1):
+            raise ValueError("%s: seg_first_frame must hold num_segments + 1 frame indices" % what)
+        nseg = 1 if table is None else table.size - 1
+        rows = int(self.lib.alac_hip_loudness_rows(int(sample_rate), frames, None if table is None else table.ctypes.data, nseg))
+        energy = t.empty((rows, channels), dtype=t.float64, device=self.device)
+        reports = t.empty((nseg, 8), dtype=t.int32, device=self.device)
+        ws = self._workspace(max(8, int(self.lib.alac_hip_loudness_workspace_bytes(int(sample_rate), channels, frames, nseg))))
+        # a tensor without elements has no address; the call wants one, and writes nothing through it
+        target = energy if rows else t.zeros(1, dtype=t.float64, device=self.device)
+        self._check(call(None if table is None else table.ctypes.data, nseg, ws, target, rows, reports))
+        return energy, reports
+
+    def loudness_int(self, x, sample_rate, bits=None, left_justified=True, seg_first_frame=None, container_bytes=None,
+                     channel_stride=None, frame_stride=None, num_channels=None):
+        """alac_hip_loudness_int: the K-weighted energy of every 100 ms of every channel (ITU-R BS.1770) and the sample peak
+        of integer PCM, per segment of frames.  x, bits, left_justified, the packed 3-byte form and num_channels as in
+        probe_int(); seg_first_frame as in probe_float().  Returns (energy, reports): a float64 cuda tensor [rows, channels],
+        the rows of all segments back to back, and an int32 cuda tensor [num_segments, 8] viewing the alac_hip_loudness_report
+        of every segment (word 0 first_block, 1 num_blocks, 2-3 the peak as a double, 4-5 nonfinite; loudness_reports()
+        reads them).  integrated_loudness() gates the rows of one segment.  Asynchronous."""
+        with self._call() as cur:
+            t = self.torch
+            if x.dim() == 2:
+                channels = int(x.shape[0])
+            elif num_channels is not None:
+                channels = int(num_channels)
+            else:
+                channels = int(frame_stride) if channel_stride == 1 and frame_stride else 1
+            cb, cs, fst, frames = self._int_tensor("loudness_int", x, channels, container_bytes, channel_stride, frame_stride)
+            src = IntSource(cb, 8 * cb if bits is None else int(bits), 1 if left_justified else 0, 0, cs, fst)
+            base = x if x.numel() else t.zeros(4, dtype=t.int32, device=self.device)
+            energy, reports = self._loudness(
+                "loudness_int", channels, sample_rate, frames, seg_first_frame,
+                lambda table, nseg, ws, e, rows, rep: self.lib.alac_hip_loudness_int(
+                    self.h, base.data_ptr(), C.byref(src), channels, int(sample_rate), frames, table, nseg, ws.data_ptr(),
+                    ws.numel(), e.data_ptr(), rows, rep.data_ptr()))
+            energy.record_stream(cur)
+            reports.record_stream(cur)
+            return energy, reports
+
+    def loudness_float(self, x, sample_rate, seg_first_frame=None):
+        """alac_hip_loudness_float: loudness_int() for a float32 cuda tensor [channels, frames] with any strides, passed
+        through like probe_float()'s.  Non-finite samples are read as 0.0 and counted in the reports."""
+        with self._call() as cur:
+            t = self.torch
+            if not (x.is_cuda and x.dtype == t.float32 and x.dim() == 2):
+                raise ValueError("loudness_float: x must be a float32 cuda tensor [channels, frames]")
+            base = x if x.shape[1] else t.zeros(4, dtype=t.float32, device=self.device)
+            channels, frames = int(x.shape[0]), int(x.shape[1])
+            energy, reports = self._loudness(
+                "loudness_float", channels, sample_rate, frames, seg_first_frame,
+                lambda table, nseg, ws, e, rows, rep: self.lib.alac_hip_loudness_float(
+                    self.h, base.data_ptr(), channels, int(x.stride(0)), int(x.stride(1)), int(sample_rate), frames, table, nseg,
+                    ws.data_ptr(), ws.numel(), e.data_ptr(), rows, rep.data_ptr()))
+            energy.record_stream(cur)
+            reports.record_stream(cur)
+            return energy, reports
+
+    @staticmethod
+    def loudness_reports(reports):
+        """the reports of loudness_int() / loudness_float() on the host: a list of LoudnessReport.  The caller has
+        synchronized."""
+        raw = np.ascontiguousarray(reports.cpu().numpy())
+        return [LoudnessReport.from_buffer_copy(raw[s].tobytes()) for s in range(raw.shape[0])]
 
     def pcm_crc32_device(self, pcm, ranges=None):
         """alac_hip_pcm_crc32: zlib.crc32 of ranges of a uint8 cuda tensor, computed where it lies.  ranges: a sequence of

@@ -5,6 +5,7 @@
 
 #include "alac_host.hpp"
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -181,6 +182,116 @@ int32_t ALACDecoder::TestBatch(const uint8_t *stream, const uint32_t *packetByte
             sum.bytes += dig[r].bytes;
         }
         outDigests[j] = sum;
+    }
+    return mLastStatus = ALAC_noErr;
+}
+
+int32_t ALACDecoder::LoudnessBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets,
+                                   const uint32_t *fileFirstPacket, uint32_t numFiles, double *outLufs, double *outPeak,
+                                   uint32_t *outFrames, int32_t *outStatus)
+{
+    if (!mCtx || mCookie.empty() || !fileFirstPacket || !outLufs || !outPeak || (numPackets && (!outFrames || !outStatus)))
+        return kALAC_ParamError;
+    if (numFiles == 0) return mLastStatus = ALAC_noErr;
+    for (uint32_t j = 0; j < numFiles; j++)
+        if (fileFirstPacket[j] > fileFirstPacket[j + 1]) return kALAC_ParamError;
+    if (fileFirstPacket[0] != 0 || fileFirstPacket[numFiles] != numPackets || (numPackets && (!stream || !packetBytes)))
+        return kALAC_ParamError;
+    const uint32_t np = numPackets, frame = mConfig.frameLength, C = mConfig.numChannels, bps = bps_of(mConfig.bitDepth);
+    const uint64_t bpf = (uint64_t)C * bps, packetPcm = frame * bpf;
+    if (np == 0) {  // files without packets: no frames, so neither a loudness nor a peak
+        for (uint32_t j = 0; j < numFiles; j++) outLufs[j] = -HUGE_VAL, outPeak[j] = 0.0;
+        return mLastStatus = ALAC_noErr;
+    }
+    alac_hip_format fmt = {mConfig.frameLength, mConfig.bitDepth, mConfig.numChannels, mConfig.sampleRate};
+    hipStream_t st = (hipStream_t)alac_hip_stream(mCtx);
+    alachost::DevStream d;
+    alachost::DevBuf dWs, dNs, dSt, dPcm, dPacked, dLoudWs, dRows, dRep;
+    uint64_t wsBytes = 0;
+    if (np) {
+        if (alachost::upload_stream(stream, packetBytes, np, st, d,
+                                    [](int32_t, const char *, hipError_t) { return (int32_t)kALAC_MemFullError; }) ||
+            dWs.alloc(wsBytes = alac_hip_decode_workspace_bytes_stream(&fmt, np, d.total)) || dNs.alloc(np * 4ull) ||
+            dSt.alloc(np * 4ull) || dPcm.alloc(np * packetPcm))
+            return mLastStatus = kALAC_MemFullError;
+        mLastStatus = alac_hip_decode(mCtx, mCookie.data(), (uint32_t)mCookie.size(), (const uint8_t *)d.bytes.p,
+                                      (const uint64_t *)d.offs.p, np, dWs.p, wsBytes, (uint8_t *)dPcm.p, (uint32_t *)dNs.p,
+                                      (int32_t *)dSt.p);
+        if (mLastStatus != ALAC_HIP_noErr) return mLastStatus;
+        if (hipMemcpyAsync(outFrames, dNs.p, np * 4ull, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(outStatus, dSt.p, np * 4ull, hipMemcpyDeviceToHost, st) != hipSuccess)
+            return mLastStatus = kALAC_ParamError;
+        if ((mLastStatus = alac_hip_synchronize(mCtx)) != ALAC_HIP_noErr) return mLastStatus;
+    }
+    // one segment per file, in frames of the plane; a file's frames sit back to back only when all its packets but the last
+    // are full.  A file with an undecodable packet is not measured (its segment is empty: -HUGE_VAL and peak 0, and outStatus
+    // names the packet), so that one damaged file does not send the whole batch through the copy below.
+    std::vector<uint64_t> table(numFiles + 1, 0);
+    bool packed = true;
+    for (uint32_t j = 0; j < numFiles; j++) {
+        const uint32_t p0 = fileFirstPacket[j], p1 = fileFirstPacket[j + 1];
+        uint64_t frames = 0;
+        bool whole = true, filePacked = true;
+        for (uint32_t p = p0; p < p1; p++) {
+            if (outFrames[p] > frame) return mLastStatus = kALAC_ParamError;  // (the decoder never reports more)
+            whole = whole && outStatus[p] == 0;
+            filePacked = filePacked && (p + 1 == p1 || outFrames[p] == frame);
+            frames += outFrames[p];
+        }
+        packed = packed && (!whole || filePacked);
+        table[j + 1] = table[j] + (whole ? frames : 0);
+    }
+    const void *plane = dPcm.p;
+    std::vector<uint64_t> seg(2 * (size_t)numFiles + 1, 0);  // packed: [file start, file end) per file, the slack between them
+    uint32_t nseg = numFiles;                               // as segments of its own that nobody reads
+    if (!packed) {
+        // (a file with a short packet in front of its last one: rare; one copy per packet of the batch's measured files)
+        // every packet's frames copied together into a second plane, where segment j is [table[j], table[j + 1])
+        if (dPacked.alloc(table[numFiles] * bpf)) return mLastStatus = kALAC_MemFullError;
+        uint64_t at = 0;
+        for (uint32_t j = 0; j < numFiles; j++) {
+            if (table[j + 1] == table[j]) continue;  // empty, or not measured
+            for (uint32_t p = fileFirstPacket[j]; p < fileFirstPacket[j + 1]; p++) {
+                if (outFrames[p] && hipMemcpyAsync((uint8_t *)dPacked.p + at * bpf, (const uint8_t *)dPcm.p + p * packetPcm,
+                                                   outFrames[p] * bpf, hipMemcpyDeviceToDevice, st) != hipSuccess)
+                    return mLastStatus = kALAC_ParamError;
+                at += outFrames[p];
+            }
+        }
+        plane = dPacked.p;
+        seg.assign(table.begin(), table.end());
+    } else {
+        // file j lies at its first packet's place: segment 2j is the file, segment 2j + 1 what lies behind it up to the next
+        nseg = 2 * numFiles;
+        for (uint32_t j = 0; j < numFiles; j++) {
+            seg[2 * j] = (uint64_t)fileFirstPacket[j] * frame;
+            seg[2 * j + 1] = seg[2 * j] + (table[j + 1] - table[j]);
+        }
+        seg[2 * numFiles] = seg[2 * numFiles - 1];
+    }
+    const uint32_t step = packed ? 2 : 1;
+    const uint64_t totalFrames = packed ? (uint64_t)np * frame : table[numFiles];
+    const alac_hip_int_source src = {bps, mConfig.bitDepth, 1, 0, 1, C};
+    const uint64_t rows = alac_hip_loudness_rows(mConfig.sampleRate, totalFrames, seg.data(), nseg);
+    const uint64_t loudWs = alac_hip_loudness_workspace_bytes(mConfig.sampleRate, C, totalFrames, nseg);
+    if (loudWs == 0) return mLastStatus = kALAC_ParamError;  // a sample rate the measurement does not take
+    std::vector<double> energy((size_t)rows * C);
+    std::vector<alac_hip_loudness_report> rep(nseg);
+    if (dLoudWs.alloc(loudWs) || dRows.alloc(rows * C * 8ull) || dRep.alloc(nseg * 32ull)) return mLastStatus = kALAC_MemFullError;
+    mLastStatus = alac_hip_loudness_int(mCtx, plane, &src, C, mConfig.sampleRate, totalFrames, seg.data(), nseg, dLoudWs.p, loudWs,
+                                        (double *)dRows.p, rows, (alac_hip_loudness_report *)dRep.p);
+    if (mLastStatus != ALAC_HIP_noErr) return mLastStatus;
+    // only the rows and the reports cross the bus: the PCM stays on the device
+    if ((rows && hipMemcpyAsync(energy.data(), dRows.p, rows * C * 8ull, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipMemcpyAsync(rep.data(), dRep.p, nseg * 32ull, hipMemcpyDeviceToHost, st) != hipSuccess)
+        return mLastStatus = kALAC_ParamError;
+    if ((mLastStatus = alac_hip_synchronize(mCtx)) != ALAC_HIP_noErr) return mLastStatus;
+    for (uint32_t j = 0; j < numFiles; j++) {
+        const alac_hip_loudness_report &r = rep[step * j];
+        outPeak[j] = r.peak;
+        mLastStatus = alac_hip_loudness_integrated(energy.data() + (size_t)r.first_block * C, r.num_blocks, C,
+                                                   mConfig.sampleRate / 10, nullptr, &outLufs[j]);
+        if (mLastStatus != ALAC_HIP_noErr) return mLastStatus;
     }
     return mLastStatus = ALAC_noErr;
 }

@@ -1392,6 +1392,125 @@ uint32_t alac_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b)
     return crc_mul_host(crc_a, crc_x8_pow(len_b)) ^ crc_b;
 }
 
+// ---- loudness: BS.1770 energies per 100 ms and the sample peak, per segment of frames ------------------------------------
+// the chunks and groups a call can have at most: every segment ends with at most one short chunk and one short group
+static void loudness_bounds(uint32_t L, uint64_t total_frames, uint32_t num_segments, uint64_t &chunks, uint64_t &groups)
+{
+    chunks = total_frames / L + num_segments;
+    groups = chunks / kLoudGroup + num_segments;
+}
+
+// the workspace: the four tables, the chunks' states, the groups' states, the chunks' sums
+struct LoudnessLayout {
+    uint64_t tables, state, gstate, partial, total;
+};
+static LoudnessLayout loudness_layout(uint32_t L, uint32_t num_channels, uint64_t total_frames, uint32_t num_segments)
+{
+    uint64_t chunks, groups;
+    loudness_bounds(L, total_frames, num_segments, chunks, groups);
+    LoudnessLayout w;
+    w.tables = 0;
+    w.state = align_up(4 * ((uint64_t)num_segments + 1) * 8, 256);
+    w.gstate = w.state + align_up(chunks * num_channels * 32, 256);
+    w.partial = w.gstate + align_up(groups * num_channels * 32, 256);
+    w.total = w.partial + align_up(chunks * num_channels * 8, 256) + 256;  // + 256: the arrays start at the next multiple of 32
+    return w;
+}
+
+uint64_t alac_hip_loudness_workspace_bytes(uint32_t sample_rate, uint32_t num_channels, uint64_t total_frames,
+                                           uint32_t num_segments)
+{
+    if (!loud_rate_ok(sample_rate) || num_channels < 1 || num_channels > kMaxChannels || num_segments == 0) return 0;
+    return loudness_layout(loud_chunk_frames(sample_rate), num_channels, total_frames, num_segments).total;
+}
+
+// What both loudness calls do behind the source's own refusals (the caller's: int_probe_refusal or float_probe_refusal, which
+// leave [lo, hi)): the remaining refusals, then the tables to the device and the passes.  containerBytes 0: float32.
+static int32_t loudness_impl(alac_hip_ctx *ctx, LoudArgs a, uint32_t sample_rate, uint64_t total_frames,
+                             const uint64_t *h_seg_first_frame, uint64_t lo, uint64_t hi, void *d_workspace,
+                             uint64_t workspace_bytes, double *d_energy, uint64_t energy_rows, void *d_reports)
+{
+    if (!loud_rate_ok(sample_rate)) return fail(ctx, ALAC_HIP_ParamError, "sample rate is not a multiple of 10 in [8000, 384000]");
+    if (!d_reports || ((uintptr_t)d_reports & 7)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned d_reports (8 B)");
+    if (!d_energy || ((uintptr_t)d_energy & 7)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned d_energy (8 B)");
+    if (!d_workspace || ((uintptr_t)d_workspace & 7)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned workspace (8 B)");
+    const uint32_t nseg = a.numSegments, L = loud_chunk_frames(sample_rate);
+    const uint64_t hop = sample_rate / 10;
+    const LoudnessLayout w = loudness_layout(L, a.channels, total_frames, nseg);
+    if (workspace_bytes < w.total) return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    // segFirst, rowBase, chunkBase, groupBase, [nseg + 1] each
+    std::vector<uint64_t> table(4 * ((size_t)nseg + 1));
+    uint64_t *first = table.data(), *row = first + nseg + 1, *chunk = row + nseg + 1, *group = chunk + nseg + 1;
+    row[0] = chunk[0] = group[0] = 0;
+    for (uint32_t s = 0; s <= nseg; s++) first[s] = h_seg_first_frame ? h_seg_first_frame[s] : (s ? hi : lo);
+    for (uint32_t s = 0; s < nseg; s++) {
+        const uint64_t n = first[s + 1] - first[s], chunks = (n + L - 1) / L;
+        row[s + 1] = row[s] + n / hop;
+        chunk[s + 1] = chunk[s] + chunks;
+        group[s + 1] = group[s] + (chunks + kLoudGroup - 1) / kLoudGroup;
+    }
+    if (row[nseg] > 0xffffffffull) return fail(ctx, ALAC_HIP_ParamError, "more than 2^32 - 1 rows");
+    if (energy_rows < row[nseg]) return fail(ctx, ALAC_HIP_ParamError, "energy_rows below the table's row count");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    hipError_t e;
+    if ((e = upload_segment_table(ctx, table.data(), table.size(), d_workspace)))
+        return fail(ctx, ALAC_HIP_ParamError, "segment table upload", e);
+    // the tables lie at the workspace's start; the arrays behind them count from the next multiple of 32 bytes
+    uint8_t *ws = (uint8_t *)align_up((uint64_t)(uintptr_t)d_workspace, 32);
+    a.segFirst = (const uint64_t *)d_workspace;
+    a.rowBase = a.segFirst + nseg + 1, a.chunkBase = a.rowBase + nseg + 1, a.groupBase = a.chunkBase + nseg + 1;
+    a.L = L, a.chunksPerHop = (uint32_t)(hop / L);
+    a.totalRows = row[nseg], a.totalChunks = chunk[nseg], a.totalGroups = group[nseg];
+    loud_filter_coefs(sample_rate, a.coef);
+    loud_state_maps(a.coef, L, a.M, a.MG);
+    a.state = (double *)(ws + w.state), a.gstate = (double *)(ws + w.gstate), a.partial = (double *)(ws + w.partial);
+    a.energy = d_energy;
+    a.reports = (uint32_t *)d_reports;
+    if ((e = launch_loudness(a, ctx->stream))) return fail(ctx, ALAC_HIP_ParamError, "loudness launch", e);
+    return ALAC_HIP_noErr;
+}
+
+static LoudArgs loudness_source(const void *in, uint64_t channel_stride, uint64_t frame_stride, uint32_t num_segments,
+                                uint32_t num_channels, uint32_t container_bytes, uint32_t bits, uint32_t left_justified)
+{
+    LoudArgs a = {};
+    a.in = in, a.channelStride = channel_stride, a.frameStride = frame_stride;
+    a.numSegments = num_segments, a.channels = num_channels;
+    a.containerBytes = container_bytes, a.srcBits = bits, a.leftJustified = left_justified;
+    return a;
+}
+
+int32_t alac_hip_loudness_int(alac_hip_ctx *ctx, const void *d_in, const alac_hip_int_source *src, uint32_t num_channels,
+                              uint32_t sample_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                              uint32_t num_segments, void *d_workspace, uint64_t workspace_bytes, double *d_energy,
+                              uint64_t energy_rows, alac_hip_loudness_report *d_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = int_probe_refusal(ctx, d_in, src, num_channels, total_frames, h_seg_first_frame, num_segments, lo, hi))
+        return rc;
+    return loudness_impl(ctx, loudness_source(d_in, src->channel_stride, src->frame_stride, num_segments, num_channels,
+                                              src->container_bytes, src->bits, src->left_justified),
+                         sample_rate, total_frames, h_seg_first_frame, lo, hi, d_workspace, workspace_bytes, d_energy,
+                         energy_rows, d_reports);
+}
+
+int32_t alac_hip_loudness_float(alac_hip_ctx *ctx, const float *d_in, uint32_t num_channels, uint64_t channel_stride,
+                                uint64_t frame_stride, uint32_t sample_rate, uint64_t total_frames,
+                                const uint64_t *h_seg_first_frame, uint32_t num_segments, void *d_workspace,
+                                uint64_t workspace_bytes, double *d_energy, uint64_t energy_rows,
+                                alac_hip_loudness_report *d_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = float_probe_refusal(ctx, d_in, num_channels, channel_stride, frame_stride, total_frames, h_seg_first_frame,
+                                         num_segments, lo, hi))
+        return rc;
+    return loudness_impl(ctx, loudness_source(d_in, channel_stride, frame_stride, num_segments, num_channels, 0, 0, 0),
+                         sample_rate, total_frames, h_seg_first_frame, lo, hi, d_workspace, workspace_bytes, d_energy,
+                         energy_rows, d_reports);
+}
+
 uint32_t alac_hip_num_stages(void) { return kNumStages; }
 
 const char *alac_hip_stage_name(uint32_t stage)
@@ -2112,6 +2231,77 @@ int32_t alac_hip_int_probe_host(alac_hip_ctx *ctx, const void *h_in, const alac_
         (e = hipStreamSynchronize(ctx->stream)))
         return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
     return ALAC_HIP_noErr;
+}
+
+extern "C++" {
+// the host form of a loudness call whose source refusals have passed: stages spanBytes of h_in, runs call(d_in, workspace,
+// its bytes, d_energy, d_reports), brings the table's rows and the reports back
+template <typename Call>
+static int32_t loudness_host(alac_hip_ctx *ctx, const void *h_in, uint64_t spanBytes, uint32_t num_channels, uint32_t sample_rate,
+                             uint64_t total_frames, const uint64_t *h_seg_first_frame, uint32_t num_segments, double *h_energy,
+                             uint64_t energy_rows, alac_hip_loudness_report *h_reports, Call call)
+{
+    if (!h_reports || !h_energy) return fail(ctx, ALAC_HIP_ParamError, "null h_energy or h_reports");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    const uint64_t rows = alac_hip_loudness_rows(sample_rate, total_frames, h_seg_first_frame, num_segments);
+    if (energy_rows < rows) return fail(ctx, ALAC_HIP_ParamError, "energy_rows below the table's row count");
+    const uint64_t wsBytes = alac_hip_loudness_workspace_bytes(sample_rate, num_channels, total_frames, num_segments);
+    const uint64_t rowBytes = rows * num_channels * 8, repBytes = (uint64_t)num_segments * 32;
+    DevBuf dIn, dWs, dRows, dRep;
+    hipError_t e;
+    if ((e = dIn.alloc(spanBytes)) || (e = dWs.alloc(wsBytes)) || (e = dRows.alloc(rowBytes)) || (e = dRep.alloc(repBytes)))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if (spanBytes && (e = hipMemcpyAsync(dIn.p, h_in, spanBytes, hipMemcpyHostToDevice, ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    if (int32_t rc = call(dIn.p, dWs.p, wsBytes, (double *)dRows.p, rows, (alac_hip_loudness_report *)dRep.p)) return rc;
+    if ((rowBytes && (e = hipMemcpyAsync(h_energy, dRows.p, rowBytes, hipMemcpyDeviceToHost, ctx->stream))) ||
+        (e = hipMemcpyAsync(h_reports, dRep.p, repBytes, hipMemcpyDeviceToHost, ctx->stream)) ||
+        (e = hipStreamSynchronize(ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
+    return ALAC_HIP_noErr;
+}
+
+}  // extern "C++"
+
+int32_t alac_hip_loudness_int_host(alac_hip_ctx *ctx, const void *h_in, const alac_hip_int_source *src, uint32_t num_channels,
+                                   uint32_t sample_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                                   uint32_t num_segments, double *h_energy, uint64_t energy_rows,
+                                   alac_hip_loudness_report *h_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = int_probe_refusal(ctx, h_in, src, num_channels, total_frames, h_seg_first_frame, num_segments, lo, hi))
+        return rc;
+    if (!loud_rate_ok(sample_rate)) return fail(ctx, ALAC_HIP_ParamError, "sample rate is not a multiple of 10 in [8000, 384000]");
+    // the containers the call may read lie in [0, span) of h_in: up to the last frame of the last segment
+    const uint64_t span = hi > lo ? (num_channels - 1) * src->channel_stride + (hi - 1) * src->frame_stride + 1 : 0;
+    return loudness_host(ctx, h_in, span * src->container_bytes, num_channels, sample_rate, total_frames, h_seg_first_frame,
+                         num_segments, h_energy, energy_rows, h_reports,
+                         [&](void *dIn, void *dWs, uint64_t wsBytes, double *dRows, uint64_t rows, alac_hip_loudness_report *dRep) {
+                             return alac_hip_loudness_int(ctx, dIn, src, num_channels, sample_rate, total_frames,
+                                                          h_seg_first_frame, num_segments, dWs, wsBytes, dRows, rows, dRep);
+                         });
+}
+
+int32_t alac_hip_loudness_float_host(alac_hip_ctx *ctx, const float *h_in, uint32_t num_channels, uint64_t channel_stride,
+                                     uint64_t frame_stride, uint32_t sample_rate, uint64_t total_frames,
+                                     const uint64_t *h_seg_first_frame, uint32_t num_segments, double *h_energy,
+                                     uint64_t energy_rows, alac_hip_loudness_report *h_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = float_probe_refusal(ctx, h_in, num_channels, channel_stride, frame_stride, total_frames, h_seg_first_frame,
+                                         num_segments, lo, hi))
+        return rc;
+    if (!loud_rate_ok(sample_rate)) return fail(ctx, ALAC_HIP_ParamError, "sample rate is not a multiple of 10 in [8000, 384000]");
+    const uint64_t span = hi > lo ? (num_channels - 1) * channel_stride + (hi - 1) * frame_stride + 1 : 0;
+    return loudness_host(ctx, h_in, span * sizeof(float), num_channels, sample_rate, total_frames, h_seg_first_frame,
+                         num_segments, h_energy, energy_rows, h_reports,
+                         [&](void *dIn, void *dWs, uint64_t wsBytes, double *dRows, uint64_t rows, alac_hip_loudness_report *dRep) {
+                             return alac_hip_loudness_float(ctx, (const float *)dIn, num_channels, channel_stride, frame_stride,
+                                                            sample_rate, total_frames, h_seg_first_frame, num_segments, dWs,
+                                                            wsBytes, dRows, rows, dRep);
+                         });
 }
 
 int32_t alac_hip_pcm_crc32_host(alac_hip_ctx *ctx, const void *h_pcm, uint64_t total_bytes, const uint64_t *h_ranges,

@@ -436,6 +436,40 @@ hipError_t launch_pcm_crc(const PcmCrcArgs &a, hipStream_t st);
 uint32_t crc_x8_pow(uint64_t bytes);
 uint32_t crc_mul_host(uint32_t a, uint32_t b);
 
+// ---- loudness (alac_loudness.hip): alac_hip_loudness_int / _float, BS.1770 energies per 100 ms and the sample peak ----
+// The source as in IntProbeArgs (containerBytes 2, 3, 4) or FloatProbeArgs (containerBytes 0: float32).  Segment s = frames
+// [segFirst[s], segFirst[s + 1]) is cut into chunks of L frames (the last one may be shorter) and its chunks into groups of
+// kLoudGroup; rowBase / chunkBase / groupBase [numSegments + 1]: the first row, chunk and group of every segment in the
+// call's arrays (device tables the host built; rows = floor(frames / hop), hop = L * chunksPerHop).
+constexpr uint32_t kLoudGroup = 256;
+struct LoudArgs {
+    const void *in;
+    uint64_t channelStride, frameStride;
+    const uint64_t *segFirst, *rowBase, *chunkBase, *groupBase;
+    uint32_t numSegments, channels;
+    uint32_t containerBytes, srcBits, leftJustified;
+    uint32_t L, chunksPerHop;
+    uint32_t direct, pad;  // direct != 0: no pass stages its loads through LDS (ALAC_HIP_LOUDNESS_DIRECT=1, for measurements)
+    uint64_t totalChunks, totalGroups, totalRows;
+    double coef[10];  // {b0, b1, b2, a1, a2} of the shelf, then of the high-pass
+    double M[16];     // the zero-input map of the filter's state over L frames, row-major
+    double MG[16];    // ... over kLoudGroup * L frames
+    double *state;    // [totalChunks][channels][4]: a chunk's end state from zero state, then its true start state
+    double *gstate;   // [totalGroups][channels][4]: the same per group
+    double *partial;  // [totalChunks][channels]: the chunk's sum of y^2
+    double *energy;   // [totalRows][channels]
+    uint32_t *reports;  // 8 words per segment: alac_hip_loudness_report
+};
+// the sample rates the loudness calls take: a multiple of 10 in [8 000, 384 000]
+inline bool loud_rate_ok(uint32_t fs) { return fs >= 8000 && fs <= 384000 && fs % 10 == 0; }
+// L of a sample rate: a divisor of hop = fs / 10 — the largest one <= 64, or where that is below 16 the smallest one >= 16
+uint32_t loud_chunk_frames(uint32_t sampleRate);
+// host: the two biquads of fs (fs checked by the caller), and M / MG of LoudArgs for chunks of L frames
+void loud_filter_coefs(uint32_t sampleRate, double (&coef)[10]);
+void loud_state_maps(const double (&coef)[10], uint32_t L, double (&M)[16], double (&MG)[16]);
+// zeroes the reports, then the passes
+hipError_t launch_loudness(const LoudArgs &a, hipStream_t st);
+
 // ---- the words of the PCM modes that have more than fit in DecodeArgs (PcmMode, alac_verify.hpp) ----
 // Sample i of channel c of packet p lives at index c * channelStride + (p * frameSize + i) * frameStride of DecodeArgs::pcmOut.
 //  kPcmVerifyFloat (alac_hip_verify_float): pcmOut is the float32 source, only read, and only at frames

@@ -82,6 +82,16 @@
  *                                             its encode print the same value.  Float PCM is refused.  A file with an
  *                                             undecodable packet is named with the packet's index; exit 1.  With --devices N the
  *                                             files are dealt to N GPUs.  No other option
+ *   --loudness [--devices N] <file> [<file> ...]  print one line per file, "%.2f LUFS  %.2f dBFS  <frames>  <path>": the integrated
+ *                                             loudness (ITU-R BS.1770, the value of ReplayGain 2.0 and EBU R128), the sample
+ *                                             peak and the sample-frames, "-inf" where there is no value (silence, a file
+ *                                             shorter than 400 ms).  ALAC files (CAF, M4A) are decoded on the GPU and measured
+ *                                             where they lie (ALACDecoder::LoudnessBatch); integer PCM files go through
+ *                                             alac_hip_loudness_int_host, float PCM files through alac_hip_loudness_float_host.
+ *                                             Files above two channels are weighted by the layout tag their encode would
+ *                                             carry.  A file that cannot be measured (an undecodable packet, a sample rate
+ *                                             that is not a multiple of 10 in 8 000 .. 384 000) is named on stderr and the exit
+ *                                             status is 1.  No other option is accepted.
  *   --crc-check <list>                        read lines of that format, compute every file's value again and print
  *                                             "<path>: OK", "<path>: FAILED" or "<path>: FAILED open"; exit 1 if any line
  *                                             failed (the flow of sha256sum -c).  With --devices N; no other option
@@ -89,6 +99,7 @@
  * A single chained file is serial by construction: one file runs as one chain of dependent
  * packets; the GPU pays off with --batch or --segment-packets.
  */
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -129,6 +140,8 @@ struct Job {
     bool opened = false, done = false;
     uint32_t crc = 0;
     uint64_t crcFrames = 0;
+    // --loudness (with done and crcFrames): the integrated loudness in LUFS and the sample peak, 1.0 = full scale
+    double lufs = 0.0, peak = 0.0;
 };
 typedef std::map<std::string, std::vector<Job *> > Groups;  // files that go through the GPU in one call
 
@@ -819,6 +832,126 @@ int crc_check(const Options &o)
     return rc;
 }
 
+// ---- --loudness: integrated loudness and sample peak of every file, measured on the GPU; nothing is written ----
+// ALAC files of one cookie: one LoudnessBatch, one segment per file
+void loudness_alac_group(std::vector<Job *> &jobs, int device)
+{
+    ALACDecoder dec;
+    if (!open_decoder(dec, jobs[0]->contents.cookie, device)) {
+        fprintf(stderr, " Cannot initialise the decoder from the magic cookie: \"%s\"\n", jobs[0]->in.c_str());
+        return;
+    }
+    std::vector<Job *> take;
+    for (size_t j = 0; j < jobs.size(); j++)
+        if (cookie_matches_description(dec.mConfig.bitDepth, *jobs[j])) take.push_back(jobs[j]);
+    if (take.empty()) return;
+    std::vector<uint32_t> sizes;
+    Bytes stream;
+    const std::vector<uint32_t> firstPacket = gather_packets(take, stream, sizes);
+    const uint32_t np = (uint32_t)sizes.size();
+    std::vector<double> lufs(take.size()), peak(take.size());
+    std::vector<uint32_t> frames(np, 0);
+    std::vector<int32_t> status(np, 0);
+    const int32_t rc = dec.LoudnessBatch(stream.data(), sizes.data(), np, firstPacket.data(), (uint32_t)take.size(), lufs.data(),
+                                         peak.data(), frames.data(), status.data());
+    if (rc != ALAC_noErr) {
+        fprintf(stderr, " Measuring failed (status %d): \"%s\"\n", rc, take[0]->in.c_str());
+        return;
+    }
+    for (size_t j = 0; j < take.size(); j++) {
+        Job &J = *take[j];
+        uint32_t p = firstPacket[j];
+        while (p < firstPacket[j + 1] && status[p] == 0) p++;
+        if (p < firstPacket[j + 1]) {
+            fprintf(stderr, " Cannot decode packet %u (status %d): \"%s\"\n", p - firstPacket[j], status[p], J.in.c_str());
+            continue;
+        }
+        J.crcFrames = 0;
+        for (p = firstPacket[j]; p < firstPacket[j + 1]; p++) J.crcFrames += frames[p];
+        J.lufs = lufs[j], J.peak = peak[j];
+        J.done = true;
+    }
+}
+
+// PCM files, integer or float: each one staged and measured as one segment
+void loudness_pcm_group(std::vector<Job *> &jobs, int device)
+{
+    alac_hip_ctx *ctx = nullptr;
+    const char *dev = getenv("ALAC_HIP_DEVICE");
+    if (alac_hip_create(&ctx, device >= 0 ? device : (dev ? atoi(dev) : 0), nullptr) != ALAC_HIP_noErr) {
+        fprintf(stderr, " Cannot create a GPU context\n");
+        return;
+    }
+    for (size_t j = 0; j < jobs.size(); j++) {
+        Job &J = *jobs[j];
+        const InputInfo &in = J.info;
+        const uint32_t C = in.channels, rate = (uint32_t)in.sampleRate;
+        // whole frames only: the encoder drops a trailing fraction of a frame (ALACEncoder.cu:984)
+        const uint64_t frames = in.dataSize / frame_bytes(in), bytes = frames * frame_bytes(in);
+        Bytes pcm(J.file.begin() + in.dataPos, J.file.begin() + in.dataPos + bytes);
+        if (in.bigEndianPcm) alacfile::swap_samples_in_place(pcm.data(), bytes, in.bitsPerChannel);
+        const uint64_t rows = (double)rate == in.sampleRate ? alac_hip_loudness_rows(rate, frames, nullptr, 1) : 0;
+        std::vector<double> energy((size_t)rows * C + 1);
+        alac_hip_loudness_report rep = {};
+        int32_t rc = ALAC_HIP_ParamError;
+        if ((double)rate != in.sampleRate) {
+            // (a fractional rate: refused like every other rate that is not a multiple of 10)
+        } else if (in.isFloat) {
+            rc = alac_hip_loudness_float_host(ctx, (const float *)pcm.data(), C, 1, C, rate, frames, nullptr, 1, energy.data(), rows,
+                                              &rep);
+        } else {
+            const alac_hip_int_source src = {bytes_per_sample(in.bitsPerChannel), in.bitsPerChannel, 1, 0, 1, C};
+            rc = alac_hip_loudness_int_host(ctx, pcm.data(), &src, C, rate, frames, nullptr, 1, energy.data(), rows, &rep);
+        }
+        if (rc == ALAC_HIP_noErr) rc = alac_hip_loudness_integrated(energy.data(), rep.num_blocks, C, rate / 10, nullptr, &J.lufs);
+        if (rc != ALAC_HIP_noErr) {
+            fprintf(stderr, " Measuring failed (status %d): %s: \"%s\"\n", rc, alac_hip_last_error(ctx), J.in.c_str());
+            continue;
+        }
+        J.peak = rep.peak;
+        J.crcFrames = frames;
+        J.done = true;
+    }
+    alac_hip_destroy(ctx);
+}
+
+int loudness_files(const Options &o)
+{
+    if (!devices_ok(o.devices)) return 1;
+    std::vector<Job> jobs(o.files.size());
+    Groups groups;  // ALAC files by cookie ("D..."), all PCM files ("P")
+    for (size_t j = 0; j < jobs.size(); j++) {
+        Job &J = jobs[j];
+        J.in = o.files[j];
+        if (!read_job(J)) continue;
+        std::string err = alacfile::sniff_input(J.file, J.info, true);
+        if (err.empty() && J.info.isAlac) err = parse_alac(J);
+        if (refused(err, J)) continue;
+        if (!J.info.isAlac && J.info.isFloat && (J.info.bitsPerChannel != 32 || J.info.channels < 1 || J.info.channels > 8)) {
+            fprintf(stderr, " %u-bit %u-channel float input is not supported (32-bit float, 1 to 8 channels): \"%s\"\n",
+                    J.info.bitsPerChannel, J.info.channels, J.in.c_str());
+            continue;
+        }
+        if (!J.info.isAlac && !J.info.isFloat && !pcm_format_ok(J)) continue;
+        groups[J.info.isAlac ? cookie_key(J) : std::string("P")].push_back(&J);
+    }
+    run_dealt(groups, o.devices, [](std::vector<Job *> &part, int device) {
+        (part[0]->info.isAlac ? loudness_alac_group : loudness_pcm_group)(part, device);
+        return true;
+    });
+    int rc = 0;
+    for (size_t j = 0; j < jobs.size(); j++) {
+        const Job &J = jobs[j];
+        if (!J.done) {
+            rc = 1;
+            continue;
+        }
+        // printf writes -inf for the logarithm of nothing: a silent file has neither a loudness nor a peak in dB
+        printf("%.2f LUFS  %.2f dBFS  %llu  %s\n", J.lufs, 20.0 * log10(J.peak), (unsigned long long)J.crcFrames, J.in.c_str());
+    }
+    return rc;
+}
+
 // ---- the conversions: <in> <out> pairs, PCM in -> ALAC out, ALAC in -> PCM out ----
 int convert(const Options &o)
 {
@@ -907,6 +1040,7 @@ int main(int argc, char *argv[])
 {
     Options o;
     if (!plan::parse_args(argc, argv, o)) return 1;
+    if (o.loudness) return loudness_files(o);
     if (o.crc) return crc_files(o);
     if (!o.crcList.empty()) return crc_check(o);
     return o.compare ? compare_files(o) : convert(o);

@@ -75,6 +75,20 @@ public:
     int32_t TestBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets, const uint32_t *fileFirstPacket,
                       uint32_t numFiles, alac_hip_pcm_digest *outDigests, uint32_t *outFrames, int32_t *outStatus);
 
+    /* batch extension (host buffers): the loudness of whole files, with the PCM never leaving the device.  Files and packets as
+     * in TestBatch.  The packets are decoded into a device buffer, and alac_hip_loudness_int measures one segment per file on
+     * that plane — the descriptor is {the stream's bytes per sample, its depth, left-justified, channel_stride 1, frame_stride
+     * numChannels}, the sample rate the cookie's — where the file's frames lie back to back (a file with a short packet in
+     * front of its last one is first copied together on the device).  outLufs[j] is the integrated loudness of file j
+     * (alac_hip_loudness_integrated with BS.1770's weights in the order of the stream's ALAC layout tag; -HUGE_VAL where no
+     * block passes the gates), outPeak[j] its sample peak (1.0 = full scale).  Only the rows, the reports, outFrames
+     * [numPackets] and outStatus [numPackets] (as TestBatch) are copied back.  Returns ALAC_noErr or a parameter / HIP error (a
+     * cookie whose sample rate alac_hip_loudness_int refuses is one) — an undecodable packet is reported in outStatus, and
+     * its file is not measured: -HUGE_VAL and peak 0, as for a file without frames (a batch without packets gives that for
+     * every file). */
+    int32_t LoudnessBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets, const uint32_t *fileFirstPacket,
+                          uint32_t numFiles, double *outLufs, double *outPeak, uint32_t *outFrames, int32_t *outStatus);
+
     int32_t LastStatus() const { return mLastStatus; }
 
 public:

@@ -737,6 +737,106 @@ int32_t alac_hip_pcm_crc32_host(alac_hip_ctx *ctx, const void *h_pcm, uint64_t t
  * pieces (a long file decoded in chunks) joined without touching the PCM again. */
 uint32_t alac_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 
+/* ---- loudness of PCM: ITU-R BS.1770 energies and the sample peak, computed where the PCM lies --------------------------------
+ * ReplayGain 2.0, EBU R128 and Sound Check are all BS.1770 integrated loudness plus a peak.  This call gives, for PCM in device
+ * memory — the output of alac_hip_decode, alac_hip_decode_int or alac_hip_decode_float, or a source in front of an encode —
+ * the K-weighted energy of every 100 ms of every channel and the peak, per segment of frames, so that only those rows cross
+ * the bus; alac_hip_loudness_integrated gates them on the host.  No reference counterpart.
+ * The rule.
+ *   Sample value.  Integer source (alac_hip_int_source, read exactly as alac_hip_int_probe reads it): x = s * 2^-(S-1) in double,
+ *     s the sample after justification and saturation; exact for every S, 32 included.  Float source, indexed as
+ *     alac_hip_float_probe indexes it: x = (double)f.  A non-finite float (NaN, +inf, -inf) is read as 0.0 and counted.
+ *   Filter.  Two biquads in double, run per channel from zero state at the first frame of each segment, each in the
+ *     transposed direct form II (the recurrence of scipy.signal.lfilter):
+ *         y = b0 x + s1;   s1 = b1 x - a1 y + s2;   s2 = b2 x - a2 y
+ *     with every product-and-sum of it one fused multiply-add (y = fma(b0, x, s1); s1 = fma(b1, x, fma(-a1, y, s2));
+ *     s2 = fma(b2, x, -(a2 y))), on the device and on the host alike,
+ *     the shelf first, the high-pass on its output.  The coefficients for the sample rate fs are the closed forms libebur128
+ *     and ffmpeg use:
+ *       shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196
+ *                  K = tan(pi f0 / fs), Vh = 10^(G/20), Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2
+ *                  b = [(Vh + Vb K/Q + K^2), 2 (K^2 - Vh), (Vh - Vb K/Q + K^2)] / a0
+ *                  a1 = 2 (K^2 - 1) / a0, a2 = (1 - K/Q + K^2) / a0
+ *       high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773
+ *                  b = [1, -2, 1], a1 and a2 as above from its own K
+ *     At 48 kHz these are the table of BS.1770-4 to 9e-16.  fs must be a multiple of 10 in [8 000, 384 000].
+ *   Energies.  hop = fs / 10 frames (100 ms).  Segment s of n frames has floor(n / hop) rows; row k, channel c holds the sum
+ *     of y^2 over frames [k * hop, (k + 1) * hop) of the segment, y the filtered signal.  Frames behind the last whole hop
+ *     feed the peak only.  Rows of all segments lie back to back: d_energy[(first_block[s] + k) * num_channels + c].
+ *   Report.  One alac_hip_loudness_report per segment.  peak is the maximum of |x| over every frame and channel of the
+ *     segment, unfiltered (the sample peak; 0 for an empty segment); nonfinite counts the non-finite floats.
+ *   The device cuts a segment into chunks of L frames, L a divisor of hop and a function of fs alone, filters every chunk from
+ *   zero state, carries the true states over the chunks (s' = M s + z, M the zero-input map over L frames) and filters again;
+ *   the y^2 of a chunk are summed in frame order and the chunks of a hop in ascending order.  Chunking and summation order
+ *   depend on the segment's own frames only: rows and reports are the same bits whatever the other segments of the call and
+ *   wherever the segment lies in the buffer.  They differ from one sequential pass by rounding only (about 1e-10 relative).
+ *   Integrated loudness (alac_hip_loudness_integrated, host only, no context), over num_blocks rows of one segment:
+ *     gating block j covers rows j .. j+3, z_c = sum / (4 * hop);  l_j = -0.691 + 10 log10 sum_c G_c z_cj
+ *     the absolute gate is -70; the relative gate lies 10 LU under the loudness of the mean over the absolutely gated blocks;
+ *     the result is the loudness of the mean over the blocks that pass both gates (l_j above each gate), summed in ascending
+ *     order; -HUGE_VAL when no block passes or there are fewer than 4 rows.
+ *     weights == NULL takes BS.1770's weights in the channel order of the stream's ALAC layout tag (ALACAudioTypes.h:103-110):
+ *       1, 2, 3 (C L R), 4 (C L R Cs)   all 1
+ *       5  C L R Ls Rs                  1 1 1 1.41 1.41
+ *       6  C L R Ls Rs LFE              1 1 1 1.41 1.41 0
+ *       7  C L R Ls Rs Cs LFE           1 1 1 1.41 1.41 1 0
+ *       8  C Lc Rc L R Ls Rs LFE        1 1 1 1 1 1.41 1.41 0
+ *   d_in, src / channel_stride, frame_stride   as in alac_hip_int_probe / alac_hip_float_probe
+ *   sample_rate       fs
+ *   h_seg_first_frame as in alac_hip_float_probe: HOST array [num_segments + 1], ascending, may start behind frame 0 and end
+ *                     before total_frames, empty segments allowed, copied out before the call returns; NULL
+ *                     (num_segments 1): all frames.  Frames outside every segment are never read.
+ *   d_workspace       alac_hip_loudness_workspace_bytes(sample_rate, num_channels, total_frames, num_segments) bytes, 8-byte
+ *                     aligned (the call aligns its own arrays inside it), needed with and without a table: the tables, the chunks'
+ *                     states and their partial sums
+ *   d_energy          [energy_rows * num_channels] doubles, 8-byte aligned; energy_rows >= alac_hip_loudness_rows(...)
+ *   d_reports         [num_segments] alac_hip_loudness_report, 8-byte aligned
+ * Every word of every report and every row (up to the table's row count) is written by every call.  Asynchronous on the
+ * context's stream.  kALAC_ParamError, with nothing enqueued and nothing written: everything alac_hip_int_probe or
+ * alac_hip_float_probe refuses in the source, num_channels, the table and d_reports; a null, misaligned or too small
+ * workspace; a sample rate that is not a multiple of 10 in [8 000, 384 000]; energy_rows below the table's row count (or a row
+ * count above 2^32 - 1); a null or misaligned d_energy.
+ */
+typedef struct alac_hip_loudness_report { /* one per segment, 32 bytes */
+    uint32_t first_block; /* the segment's first row of d_energy */
+    uint32_t num_blocks;  /* its rows: floor(frames / hop) */
+    double peak;          /* max |x| over the segment, 0 if empty */
+    uint64_t nonfinite;   /* non-finite floats, read as 0.0; 0 for an integer source */
+    uint64_t reserved;    /* written as 0 */
+} alac_hip_loudness_report;
+uint64_t alac_hip_loudness_workspace_bytes(uint32_t sample_rate, uint32_t num_channels, uint64_t total_frames,
+                                           uint32_t num_segments);
+int32_t alac_hip_loudness_int(alac_hip_ctx *ctx, const void *d_in, const alac_hip_int_source *src, uint32_t num_channels,
+                              uint32_t sample_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                              uint32_t num_segments, void *d_workspace, uint64_t workspace_bytes, double *d_energy,
+                              uint64_t energy_rows, alac_hip_loudness_report *d_reports);
+int32_t alac_hip_loudness_float(alac_hip_ctx *ctx, const float *d_in, uint32_t num_channels, uint64_t channel_stride,
+                                uint64_t frame_stride, uint32_t sample_rate, uint64_t total_frames,
+                                const uint64_t *h_seg_first_frame, uint32_t num_segments, void *d_workspace,
+                                uint64_t workspace_bytes, double *d_energy, uint64_t energy_rows,
+                                alac_hip_loudness_report *d_reports);
+/* Host-buffer forms (synchronous): h_in in the layout above; only the containers / floats up to the last frame of the last
+ * segment are staged to the device; the rows come back in h_energy [energy_rows * num_channels] (the table's row count of
+ * them is written), the reports in h_reports [num_segments]. */
+int32_t alac_hip_loudness_int_host(alac_hip_ctx *ctx, const void *h_in, const alac_hip_int_source *src, uint32_t num_channels,
+                                   uint32_t sample_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                                   uint32_t num_segments, double *h_energy, uint64_t energy_rows,
+                                   alac_hip_loudness_report *h_reports);
+int32_t alac_hip_loudness_float_host(alac_hip_ctx *ctx, const float *h_in, uint32_t num_channels, uint64_t channel_stride,
+                                     uint64_t frame_stride, uint32_t sample_rate, uint64_t total_frames,
+                                     const uint64_t *h_seg_first_frame, uint32_t num_segments, double *h_energy,
+                                     uint64_t energy_rows, alac_hip_loudness_report *h_reports);
+/* Host only, no context.  alac_hip_loudness_filter: the two biquads of fs as out = {b0, b1, b2, a1, a2} of the shelf, then of
+ * the high-pass; kALAC_ParamError for a bad fs or a null out.  alac_hip_loudness_rows: the rows the table's segments have in
+ * all (h_seg_first_frame NULL: one segment of total_frames); 0 for a bad fs or a table alac_hip_float_probe refuses.
+ * alac_hip_loudness_integrated: the rule above over h_energy [num_blocks * num_channels]; kALAC_ParamError for a null
+ * h_energy (with num_blocks > 0) or out_lufs, num_channels outside 1..8 or hop 0. */
+int32_t alac_hip_loudness_filter(uint32_t sample_rate, double *out);
+uint64_t alac_hip_loudness_rows(uint32_t sample_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                                uint32_t num_segments);
+int32_t alac_hip_loudness_integrated(const double *h_energy, uint64_t num_blocks, uint32_t num_channels, uint32_t hop,
+                                     const double *weights, double *out_lufs);
+
 /* Parse a magic cookie into a format (host only). */
 int32_t alac_hip_format_from_cookie(const uint8_t *h_cookie, uint32_t cookie_size,
                                     alac_hip_format *out_fmt);
