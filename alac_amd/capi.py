@@ -67,6 +67,16 @@ class LoudnessReport(C.Structure):
                 ("reserved", C.c_uint64)]
 
 
+class TruePeakReport(C.Structure):
+    """alac_hip_true_peak_report: one per segment of alac_hip_true_peak_int / _float, 32 bytes"""
+    _fields_ = [("true_peak", C.c_double), ("peak", C.c_double), ("nonfinite", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+# the frames of a lane's run of k_true_peak by oversampling factor (true_peak_run, alac_kernels.hpp); a block covers 256 runs:
+# the sizes at which the kernel changes path, for the tests
+TRUE_PEAK_RUN = {4: 53, 2: 105, 1: 64}
+TRUE_PEAK_BLOCK_RUNS = 256
+
 # what a lane, a wave, a block and one pass of the whole grid of k_pcm_crc take (alac_kernels.hpp, alac_pcm_crc.hip): the sizes
 # at which the kernel changes path, for the tests
 PCM_CRC_LANE_BYTES = 64
@@ -165,6 +175,12 @@ SIGNATURES = {
     "alac_hip_loudness_filter": (_i32, [_u32, _vp]),
     "alac_hip_loudness_rows": (_u64, [_u32, _u64, _vp, _u32]),
     "alac_hip_loudness_integrated": (_i32, [_vp, _u64, _u32, _u32, _vp, C.POINTER(C.c_double)]),
+    "alac_hip_true_peak_workspace_bytes": (_u64, [_u32, _u32]),
+    "alac_hip_true_peak_int": (_i32, [_vp, _vp, _vp, _u32, _u32, _u64, _vp, _u32, _vp, _u64, _vp, _vp]),
+    "alac_hip_true_peak_float": (_i32, [_vp, _vp, _u32, _u64, _u64, _u32, _u64, _vp, _u32, _vp, _u64, _vp, _vp]),
+    "alac_hip_true_peak_int_host": (_i32, [_vp, _vp, _vp, _u32, _u32, _u64, _vp, _u32, _vp, _vp]),
+    "alac_hip_true_peak_float_host": (_i32, [_vp, _vp, _u32, _u64, _u64, _u32, _u64, _vp, _u32, _vp, _vp]),
+    "alac_hip_true_peak_filter": (_i32, [_u32, C.POINTER(_u32), C.POINTER(_u32), _vp]),
     "alac_synth_frame": (None, [_u64, _u32, _u32, _u32, _vp]),
     "alac_synth_pcm": (None, [_u64, _u32, _u32, _u32, _u32, _vp]),
     "alac_hip_synth_pcm": (_i32, [_vp, _u64, _u32, C.POINTER(Format), _vp]),
@@ -281,6 +297,18 @@ def integrated_loudness(energy, hop, weights=None):
     if rc != 0:
         raise ValueError("integrated_loudness: bad arguments")
     return out.value
+
+
+def true_peak_filter(sample_rate):
+    """alac_hip_true_peak_filter: (factor, coefficients) of a sample rate: the oversampling factor F (4, 2 or 1) and the
+    phases 1 .. F-1 of the interpolator as a float64 array [F - 1, taps] (taps 12, 24, or 0 where F is 1).  Host only, no GPU
+    needed."""
+    factor, taps = _u32(0), _u32(0)
+    out = np.zeros(36, dtype=np.float64)
+    if load_library().alac_hip_true_peak_filter(int(sample_rate), C.byref(factor), C.byref(taps), out.ctypes.data) != 0:
+        raise ValueError("true_peak_filter: the sample rate must be a multiple of 10 in [8000, 384000]")
+    n = (factor.value - 1) * taps.value
+    return factor.value, out[:n].reshape(factor.value - 1, taps.value).copy()
 
 
 def synth_pcm(first_frame, num_frames, fmt):
@@ -681,18 +709,37 @@ class Context:
         """the part loudness_int() and loudness_float() share: the table, the outputs and the workspace; call(table pointer,
         num_segments, workspace, rows tensor, row count, reports tensor) -> status"""
         t = self.torch
+        keep, table, nseg, reports = self._measure_table(what, seg_first_frame)
+        rows = int(self.lib.alac_hip_loudness_rows(int(sample_rate), frames, table, nseg))
+        energy = t.empty((rows, channels), dtype=t.float64, device=self.device)
+        ws = self._workspace(max(8, int(self.lib.alac_hip_loudness_workspace_bytes(int(sample_rate), channels, frames, nseg))))
+        # a tensor without elements has no address; the call wants one, and writes nothing through it
+        target = energy if rows else t.zeros(1, dtype=t.float64, device=self.device)
+        self._check(call(table, nseg, ws, target, rows, reports))
+        del keep
+        return energy, reports
+
+    def _measure_table(self, what, seg_first_frame):
+        """what the loudness and the true-peak calls do with seg_first_frame: (the table as a uint64 array or None, its
+        address or None, num_segments, the reports tensor [num_segments, 8]).  The caller holds the array over the C call."""
+        t = self.torch
         table = None if seg_first_frame is None else np.ascontiguousarray(seg_first_frame, dtype=np.uint64)
         if table is not None and (table.ndim != 1 or table.size < 1):
             raise ValueError("%s: seg_first_frame must hold num_segments + 1 frame indices" % what)
         nseg = 1 if table is None else table.size - 1
-        rows = int(self.lib.alac_hip_loudness_rows(int(sample_rate), frames, None if table is None else table.ctypes.data, nseg))
-        energy = t.empty((rows, channels), dtype=t.float64, device=self.device)
-        reports = t.empty((nseg, 8), dtype=t.int32, device=self.device)
-        ws = self._workspace(max(8, int(self.lib.alac_hip_loudness_workspace_bytes(int(sample_rate), channels, frames, nseg))))
-        # a tensor without elements has no address; the call wants one, and writes nothing through it
-        target = energy if rows else t.zeros(1, dtype=t.float64, device=self.device)
-        self._check(call(None if table is None else table.ctypes.data, nseg, ws, target, rows, reports))
-        return energy, reports
+        return (table, None if table is None else table.ctypes.data, nseg,
+                t.empty((nseg, 8), dtype=t.int32, device=self.device))
+
+    def _true_peak(self, what, channels, seg_first_frame, call):
+        """the part true_peak_int() and true_peak_float() share: the table, the outputs and the workspace; call(table pointer,
+        num_segments, workspace, channel peaks tensor, reports tensor) -> status"""
+        t = self.torch
+        keep, table, nseg, reports = self._measure_table(what, seg_first_frame)
+        peaks = t.empty((nseg, channels), dtype=t.float64, device=self.device)
+        ws = self._workspace(max(8, int(self.lib.alac_hip_true_peak_workspace_bytes(channels, nseg))))
+        self._check(call(table, nseg, ws, peaks, reports))
+        del keep
+        return peaks, reports
 
     def loudness_int(self, x, sample_rate, bits=None, left_justified=True, seg_first_frame=None, container_bytes=None,
                      channel_stride=None, frame_stride=None, num_channels=None):
@@ -746,6 +793,57 @@ class Context:
         synchronized."""
         raw = np.ascontiguousarray(reports.cpu().numpy())
         return [LoudnessReport.from_buffer_copy(raw[s].tobytes()) for s in range(raw.shape[0])]
+
+    def true_peak_int(self, x, sample_rate, bits=None, left_justified=True, seg_first_frame=None, container_bytes=None,
+                      channel_stride=None, frame_stride=None, num_channels=None):
+        """alac_hip_true_peak_int: the true peak (ITU-R BS.1770-4 annex 2) of integer PCM, per segment of frames and
+        channel.  The arguments of loudness_int().  Returns (channel_peak, reports): a float64 cuda tensor [num_segments,
+        channels] and an int32 cuda tensor [num_segments, 8] viewing the alac_hip_true_peak_report of every segment (words 0-1
+        the true peak as a double, 2-3 the sample peak, 4-5 nonfinite; true_peak_reports() reads them).  Asynchronous."""
+        with self._call() as cur:
+            t = self.torch
+            if x.dim() == 2:
+                channels = int(x.shape[0])
+            elif num_channels is not None:
+                channels = int(num_channels)
+            else:
+                channels = int(frame_stride) if channel_stride == 1 and frame_stride else 1
+            cb, cs, fst, frames = self._int_tensor("true_peak_int", x, channels, container_bytes, channel_stride, frame_stride)
+            src = IntSource(cb, 8 * cb if bits is None else int(bits), 1 if left_justified else 0, 0, cs, fst)
+            base = x if x.numel() else t.zeros(4, dtype=t.int32, device=self.device)
+            peaks, reports = self._true_peak(
+                "true_peak_int", channels, seg_first_frame,
+                lambda table, nseg, ws, pk, rep: self.lib.alac_hip_true_peak_int(
+                    self.h, base.data_ptr(), C.byref(src), channels, int(sample_rate), frames, table, nseg, ws.data_ptr(),
+                    ws.numel(), pk.data_ptr(), rep.data_ptr()))
+            peaks.record_stream(cur)
+            reports.record_stream(cur)
+            return peaks, reports
+
+    def true_peak_float(self, x, sample_rate, seg_first_frame=None):
+        """alac_hip_true_peak_float: true_peak_int() for a float32 cuda tensor [channels, frames] with any strides, passed
+        through like probe_float()'s.  Non-finite samples are read as 0.0 and counted in the reports."""
+        with self._call() as cur:
+            t = self.torch
+            if not (x.is_cuda and x.dtype == t.float32 and x.dim() == 2):
+                raise ValueError("true_peak_float: x must be a float32 cuda tensor [channels, frames]")
+            base = x if x.shape[1] else t.zeros(4, dtype=t.float32, device=self.device)
+            channels, frames = int(x.shape[0]), int(x.shape[1])
+            peaks, reports = self._true_peak(
+                "true_peak_float", channels, seg_first_frame,
+                lambda table, nseg, ws, pk, rep: self.lib.alac_hip_true_peak_float(
+                    self.h, base.data_ptr(), channels, int(x.stride(0)), int(x.stride(1)), int(sample_rate), frames, table, nseg,
+                    ws.data_ptr(), ws.numel(), pk.data_ptr(), rep.data_ptr()))
+            peaks.record_stream(cur)
+            reports.record_stream(cur)
+            return peaks, reports
+
+    @staticmethod
+    def true_peak_reports(reports):
+        """the reports of true_peak_int() / true_peak_float() on the host: a list of TruePeakReport.  The caller has
+        synchronized."""
+        raw = np.ascontiguousarray(reports.cpu().numpy())
+        return [TruePeakReport.from_buffer_copy(raw[s].tobytes()) for s in range(raw.shape[0])]
 
     def pcm_crc32_device(self, pcm, ranges=None):
         """alac_hip_pcm_crc32: zlib.crc32 of ranges of a uint8 cuda tensor, computed where it lies.  ranges: a sequence of

@@ -190,6 +190,24 @@ int32_t ALACDecoder::LoudnessBatch(const uint8_t *stream, const uint32_t *packet
                                    const uint32_t *fileFirstPacket, uint32_t numFiles, double *outLufs, double *outPeak,
                                    uint32_t *outFrames, int32_t *outStatus)
 {
+    return MeasureBatch(stream, packetBytes, numPackets, fileFirstPacket, numFiles, outLufs, outPeak, nullptr, outFrames, outStatus);
+}
+
+int32_t ALACDecoder::LoudnessTruePeakBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets,
+                                           const uint32_t *fileFirstPacket, uint32_t numFiles, double *outLufs, double *outPeak,
+                                           double *outTruePeak, uint32_t *outFrames, int32_t *outStatus)
+{
+    if (!outTruePeak) return kALAC_ParamError;
+    return MeasureBatch(stream, packetBytes, numPackets, fileFirstPacket, numFiles, outLufs, outPeak, outTruePeak, outFrames,
+                        outStatus);
+}
+
+// what LoudnessBatch and LoudnessTruePeakBatch share: the decode, the per-file segment table, the copy-together of files with a
+// short middle packet, and the measurements on that one plane (outTruePeak NULL: the loudness call alone)
+int32_t ALACDecoder::MeasureBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets,
+                                  const uint32_t *fileFirstPacket, uint32_t numFiles, double *outLufs, double *outPeak,
+                                  double *outTruePeak, uint32_t *outFrames, int32_t *outStatus)
+{
     if (!mCtx || mCookie.empty() || !fileFirstPacket || !outLufs || !outPeak || (numPackets && (!outFrames || !outStatus)))
         return kALAC_ParamError;
     if (numFiles == 0) return mLastStatus = ALAC_noErr;
@@ -200,13 +218,16 @@ int32_t ALACDecoder::LoudnessBatch(const uint8_t *stream, const uint32_t *packet
     const uint32_t np = numPackets, frame = mConfig.frameLength, C = mConfig.numChannels, bps = bps_of(mConfig.bitDepth);
     const uint64_t bpf = (uint64_t)C * bps, packetPcm = frame * bpf;
     if (np == 0) {  // files without packets: no frames, so neither a loudness nor a peak
-        for (uint32_t j = 0; j < numFiles; j++) outLufs[j] = -HUGE_VAL, outPeak[j] = 0.0;
+        for (uint32_t j = 0; j < numFiles; j++) {
+            outLufs[j] = -HUGE_VAL, outPeak[j] = 0.0;
+            if (outTruePeak) outTruePeak[j] = 0.0;
+        }
         return mLastStatus = ALAC_noErr;
     }
     alac_hip_format fmt = {mConfig.frameLength, mConfig.bitDepth, mConfig.numChannels, mConfig.sampleRate};
     hipStream_t st = (hipStream_t)alac_hip_stream(mCtx);
     alachost::DevStream d;
-    alachost::DevBuf dWs, dNs, dSt, dPcm, dPacked, dLoudWs, dRows, dRep;
+    alachost::DevBuf dWs, dNs, dSt, dPcm, dPacked, dLoudWs, dRows, dRep, dPeakWs, dPeaks, dPeakRep;
     uint64_t wsBytes = 0;
     if (np) {
         if (alachost::upload_stream(stream, packetBytes, np, st, d,
@@ -281,6 +302,17 @@ int32_t ALACDecoder::LoudnessBatch(const uint8_t *stream, const uint32_t *packet
     mLastStatus = alac_hip_loudness_int(mCtx, plane, &src, C, mConfig.sampleRate, totalFrames, seg.data(), nseg, dLoudWs.p, loudWs,
                                         (double *)dRows.p, rows, (alac_hip_loudness_report *)dRep.p);
     if (mLastStatus != ALAC_HIP_noErr) return mLastStatus;
+    std::vector<alac_hip_true_peak_report> peakRep(outTruePeak ? nseg : 0);
+    if (outTruePeak) {
+        const uint64_t peakWs = alac_hip_true_peak_workspace_bytes(C, nseg);
+        if (dPeakWs.alloc(peakWs) || dPeaks.alloc((uint64_t)nseg * C * 8) || dPeakRep.alloc(nseg * 32ull))
+            return mLastStatus = kALAC_MemFullError;
+        mLastStatus = alac_hip_true_peak_int(mCtx, plane, &src, C, mConfig.sampleRate, totalFrames, seg.data(), nseg, dPeakWs.p,
+                                             peakWs, (double *)dPeaks.p, (alac_hip_true_peak_report *)dPeakRep.p);
+        if (mLastStatus != ALAC_HIP_noErr) return mLastStatus;
+        if (hipMemcpyAsync(peakRep.data(), dPeakRep.p, nseg * 32ull, hipMemcpyDeviceToHost, st) != hipSuccess)
+            return mLastStatus = kALAC_ParamError;
+    }
     // only the rows and the reports cross the bus: the PCM stays on the device
     if ((rows && hipMemcpyAsync(energy.data(), dRows.p, rows * C * 8ull, hipMemcpyDeviceToHost, st) != hipSuccess) ||
         hipMemcpyAsync(rep.data(), dRep.p, nseg * 32ull, hipMemcpyDeviceToHost, st) != hipSuccess)
@@ -289,6 +321,7 @@ int32_t ALACDecoder::LoudnessBatch(const uint8_t *stream, const uint32_t *packet
     for (uint32_t j = 0; j < numFiles; j++) {
         const alac_hip_loudness_report &r = rep[step * j];
         outPeak[j] = r.peak;
+        if (outTruePeak) outTruePeak[j] = peakRep[step * j].true_peak;
         mLastStatus = alac_hip_loudness_integrated(energy.data() + (size_t)r.first_block * C, r.num_blocks, C,
                                                    mConfig.sampleRate / 10, nullptr, &outLufs[j]);
         if (mLastStatus != ALAC_HIP_noErr) return mLastStatus;

@@ -1511,6 +1511,79 @@ int32_t alac_hip_loudness_float(alac_hip_ctx *ctx, const float *d_in, uint32_t n
                          energy_rows, d_reports);
 }
 
+// ---- true peak: BS.1770-4 annex 2, per segment of frames and channel --------------------------------------------------------
+// the workspace: segFirst and chunkBase, [num_segments + 1] each
+uint64_t alac_hip_true_peak_workspace_bytes(uint32_t num_channels, uint32_t num_segments)
+{
+    if (num_channels < 1 || num_channels > kMaxChannels || num_segments == 0) return 0;
+    return align_up(2 * ((uint64_t)num_segments + 1) * 8, 256);
+}
+
+// What both true-peak calls do behind the source's own refusals (as loudness_impl): the remaining refusals, then the tables to
+// the device and the pass.  src: the source (what loudness_source fills).
+static int32_t true_peak_impl(alac_hip_ctx *ctx, const LoudArgs &src, uint32_t sample_rate, const uint64_t *h_seg_first_frame,
+                              uint64_t lo, uint64_t hi, void *d_workspace, uint64_t workspace_bytes, double *d_channel_peak,
+                              void *d_reports)
+{
+    if (!loud_rate_ok(sample_rate)) return fail(ctx, ALAC_HIP_ParamError, "sample rate is not a multiple of 10 in [8000, 384000]");
+    if (!d_reports || ((uintptr_t)d_reports & 7)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned d_reports (8 B)");
+    if (!d_channel_peak || ((uintptr_t)d_channel_peak & 7))
+        return fail(ctx, ALAC_HIP_ParamError, "null or misaligned d_channel_peak (8 B)");
+    if (!d_workspace || ((uintptr_t)d_workspace & 7)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned workspace (8 B)");
+    const uint32_t nseg = src.numSegments;
+    if (workspace_bytes < alac_hip_true_peak_workspace_bytes(src.channels, nseg))
+        return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    TruePeakArgs a = {};
+    a.in = src.in, a.channelStride = src.channelStride, a.frameStride = src.frameStride;
+    a.numSegments = nseg, a.channels = src.channels;
+    a.containerBytes = src.containerBytes, a.srcBits = src.srcBits, a.leftJustified = src.leftJustified;
+    a.factor = true_peak_factor(sample_rate), a.run = true_peak_run(a.factor);
+    std::vector<uint64_t> table(2 * ((size_t)nseg + 1));
+    uint64_t *first = table.data(), *chunk = first + nseg + 1;
+    chunk[0] = 0;
+    for (uint32_t s = 0; s <= nseg; s++) first[s] = h_seg_first_frame ? h_seg_first_frame[s] : (s ? hi : lo);
+    for (uint32_t s = 0; s < nseg; s++) chunk[s + 1] = chunk[s] + (first[s + 1] - first[s] + a.run - 1) / a.run;
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    hipError_t e;
+    if ((e = upload_segment_table(ctx, table.data(), table.size(), d_workspace)))
+        return fail(ctx, ALAC_HIP_ParamError, "segment table upload", e);
+    a.segFirst = (const uint64_t *)d_workspace, a.chunkBase = a.segFirst + nseg + 1;
+    a.totalChunks = chunk[nseg];
+    true_peak_coefs(a.factor, a.coef);
+    a.channelPeak = (uint64_t *)d_channel_peak;
+    a.reports = (uint32_t *)d_reports;
+    if ((e = launch_true_peak(a, ctx->stream))) return fail(ctx, ALAC_HIP_ParamError, "true peak launch", e);
+    return ALAC_HIP_noErr;
+}
+
+int32_t alac_hip_true_peak_int(alac_hip_ctx *ctx, const void *d_in, const alac_hip_int_source *src, uint32_t num_channels,
+                               uint32_t sample_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                               uint32_t num_segments, void *d_workspace, uint64_t workspace_bytes, double *d_channel_peak,
+                               alac_hip_true_peak_report *d_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = int_probe_refusal(ctx, d_in, src, num_channels, total_frames, h_seg_first_frame, num_segments, lo, hi))
+        return rc;
+    return true_peak_impl(ctx, loudness_source(d_in, src->channel_stride, src->frame_stride, num_segments, num_channels,
+                                               src->container_bytes, src->bits, src->left_justified),
+                          sample_rate, h_seg_first_frame, lo, hi, d_workspace, workspace_bytes, d_channel_peak, d_reports);
+}
+
+int32_t alac_hip_true_peak_float(alac_hip_ctx *ctx, const float *d_in, uint32_t num_channels, uint64_t channel_stride,
+                                 uint64_t frame_stride, uint32_t sample_rate, uint64_t total_frames,
+                                 const uint64_t *h_seg_first_frame, uint32_t num_segments, void *d_workspace,
+                                 uint64_t workspace_bytes, double *d_channel_peak, alac_hip_true_peak_report *d_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = float_probe_refusal(ctx, d_in, num_channels, channel_stride, frame_stride, total_frames, h_seg_first_frame,
+                                         num_segments, lo, hi))
+        return rc;
+    return true_peak_impl(ctx, loudness_source(d_in, channel_stride, frame_stride, num_segments, num_channels, 0, 0, 0),
+                          sample_rate, h_seg_first_frame, lo, hi, d_workspace, workspace_bytes, d_channel_peak, d_reports);
+}
+
 uint32_t alac_hip_num_stages(void) { return kNumStages; }
 
 const char *alac_hip_stage_name(uint32_t stage)
@@ -2302,6 +2375,71 @@ int32_t alac_hip_loudness_float_host(alac_hip_ctx *ctx, const float *h_in, uint3
                                                             sample_rate, total_frames, h_seg_first_frame, num_segments, dWs,
                                                             wsBytes, dRows, rows, dRep);
                          });
+}
+
+extern "C++" {
+// the host form of a true-peak call whose source refusals have passed, as loudness_host: stages spanBytes of h_in, runs
+// call(d_in, workspace, its bytes, d_channel_peak, d_reports), brings the channel peaks and the reports back
+template <typename Call>
+static int32_t true_peak_host(alac_hip_ctx *ctx, const void *h_in, uint64_t spanBytes, uint32_t num_channels,
+                              uint32_t num_segments, double *h_channel_peak, alac_hip_true_peak_report *h_reports, Call call)
+{
+    if (!h_reports || !h_channel_peak) return fail(ctx, ALAC_HIP_ParamError, "null h_channel_peak or h_reports");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    const uint64_t wsBytes = alac_hip_true_peak_workspace_bytes(num_channels, num_segments);
+    const uint64_t peakBytes = (uint64_t)num_segments * num_channels * 8, repBytes = (uint64_t)num_segments * 32;
+    DevBuf dIn, dWs, dPeak, dRep;
+    hipError_t e;
+    if ((e = dIn.alloc(spanBytes)) || (e = dWs.alloc(wsBytes)) || (e = dPeak.alloc(peakBytes)) || (e = dRep.alloc(repBytes)))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if (spanBytes && (e = hipMemcpyAsync(dIn.p, h_in, spanBytes, hipMemcpyHostToDevice, ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    if (int32_t rc = call(dIn.p, dWs.p, wsBytes, (double *)dPeak.p, (alac_hip_true_peak_report *)dRep.p)) return rc;
+    if ((e = hipMemcpyAsync(h_channel_peak, dPeak.p, peakBytes, hipMemcpyDeviceToHost, ctx->stream)) ||
+        (e = hipMemcpyAsync(h_reports, dRep.p, repBytes, hipMemcpyDeviceToHost, ctx->stream)) ||
+        (e = hipStreamSynchronize(ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
+    return ALAC_HIP_noErr;
+}
+
+}  // extern "C++"
+
+int32_t alac_hip_true_peak_int_host(alac_hip_ctx *ctx, const void *h_in, const alac_hip_int_source *src, uint32_t num_channels,
+                                    uint32_t sample_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                                    uint32_t num_segments, double *h_channel_peak, alac_hip_true_peak_report *h_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = int_probe_refusal(ctx, h_in, src, num_channels, total_frames, h_seg_first_frame, num_segments, lo, hi))
+        return rc;
+    if (!loud_rate_ok(sample_rate)) return fail(ctx, ALAC_HIP_ParamError, "sample rate is not a multiple of 10 in [8000, 384000]");
+    // the containers the call may read lie in [0, span) of h_in: up to the last frame of the last segment
+    const uint64_t span = hi > lo ? (num_channels - 1) * src->channel_stride + (hi - 1) * src->frame_stride + 1 : 0;
+    return true_peak_host(ctx, h_in, span * src->container_bytes, num_channels, num_segments, h_channel_peak, h_reports,
+                          [&](void *dIn, void *dWs, uint64_t wsBytes, double *dPeak, alac_hip_true_peak_report *dRep) {
+                              return alac_hip_true_peak_int(ctx, dIn, src, num_channels, sample_rate, total_frames,
+                                                            h_seg_first_frame, num_segments, dWs, wsBytes, dPeak, dRep);
+                          });
+}
+
+int32_t alac_hip_true_peak_float_host(alac_hip_ctx *ctx, const float *h_in, uint32_t num_channels, uint64_t channel_stride,
+                                      uint64_t frame_stride, uint32_t sample_rate, uint64_t total_frames,
+                                      const uint64_t *h_seg_first_frame, uint32_t num_segments, double *h_channel_peak,
+                                      alac_hip_true_peak_report *h_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = float_probe_refusal(ctx, h_in, num_channels, channel_stride, frame_stride, total_frames, h_seg_first_frame,
+                                         num_segments, lo, hi))
+        return rc;
+    if (!loud_rate_ok(sample_rate)) return fail(ctx, ALAC_HIP_ParamError, "sample rate is not a multiple of 10 in [8000, 384000]");
+    const uint64_t span = hi > lo ? (num_channels - 1) * channel_stride + (hi - 1) * frame_stride + 1 : 0;
+    return true_peak_host(ctx, h_in, span * sizeof(float), num_channels, num_segments, h_channel_peak, h_reports,
+                          [&](void *dIn, void *dWs, uint64_t wsBytes, double *dPeak, alac_hip_true_peak_report *dRep) {
+                              return alac_hip_true_peak_float(ctx, (const float *)dIn, num_channels, channel_stride,
+                                                              frame_stride, sample_rate, total_frames, h_seg_first_frame,
+                                                              num_segments, dWs, wsBytes, dPeak, dRep);
+                          });
 }
 
 int32_t alac_hip_pcm_crc32_host(alac_hip_ctx *ctx, const void *h_pcm, uint64_t total_bytes, const uint64_t *h_ranges,

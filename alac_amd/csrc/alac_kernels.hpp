@@ -470,6 +470,34 @@ void loud_state_maps(const double (&coef)[10], uint32_t L, double (&M)[16], doub
 // zeroes the reports, then the passes
 hipError_t launch_loudness(const LoudArgs &a, hipStream_t st);
 
+// ---- true peak (alac_true_peak.hip): alac_hip_true_peak_int / _float, BS.1770 annex 2 ----
+// The source as in LoudArgs.  Segment s = frames [segFirst[s], segFirst[s + 1]) is cut into runs of `run` frames (the last one
+// may be shorter), one lane each; chunkBase[numSegments + 1]: the first run of every segment among the call's runs.
+constexpr uint32_t kTruePeakMaxTaps = 24, kTruePeakMaxCoefs = 36;
+struct TruePeakArgs {
+    const void *in;
+    uint64_t channelStride, frameStride;
+    const uint64_t *segFirst, *chunkBase;
+    uint32_t numSegments, channels;
+    uint32_t containerBytes, srcBits, leftJustified;
+    uint32_t factor, run;  // F of the sample rate; true_peak_run(F)
+    uint32_t direct;       // != 0: no staging through LDS (ALAC_HIP_TRUE_PEAK_DIRECT=1, for measurements)
+    uint64_t totalChunks;
+    double coef[kTruePeakMaxCoefs];  // phases 1 .. F-1, [F - 1][taps]
+    uint64_t *channelPeak;           // [numSegments][channels]: the bits of the non-negative double
+    uint32_t *reports;               // 8 words per segment: alac_hip_true_peak_report
+};
+// F of a sample rate the loudness calls take: 4 below 96 000, 2 below 192 000, 1 from there
+inline uint32_t true_peak_factor(uint32_t fs) { return fs < 96000 ? 4u : fs < 192000 ? 2u : 1u; }
+// taps per phase (K): 12, 24, and 0 where nothing is filtered
+inline uint32_t true_peak_taps(uint32_t F) { return F == 4 ? 12u : F == 2 ? 24u : 0u; }
+// the frames of a lane's run: with the K - 1 frames of history in front of them they fill whole slices of 16 frames
+inline uint32_t true_peak_run(uint32_t F) { return F == 4 ? 53u : F == 2 ? 105u : 64u; }
+// host: phases 1 .. F-1 of the 49-tap Hann-windowed sinc, [F - 1][taps]
+void true_peak_coefs(uint32_t F, double (&coef)[kTruePeakMaxCoefs]);
+// zeroes the reports and the channel peaks, then the pass and the finish
+hipError_t launch_true_peak(const TruePeakArgs &a, hipStream_t st);
+
 // ---- the words of the PCM modes that have more than fit in DecodeArgs (PcmMode, alac_verify.hpp) ----
 // Sample i of channel c of packet p lives at index c * channelStride + (p * frameSize + i) * frameStride of DecodeArgs::pcmOut.
 //  kPcmVerifyFloat (alac_hip_verify_float): pcmOut is the float32 source, only read, and only at frames

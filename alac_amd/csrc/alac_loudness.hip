@@ -11,10 +11,12 @@
 // channel then adds the chunks of a hop in ascending order.  Nothing is summed with atomics, and every index a chunk, group
 // or row is found by counts from its segment's first frame: the rows are the same bits whatever else the call holds.
 // Reads through the loaders of alac_pcm_load.hpp in the layouts of pcm_in_layout, as the probes do; where a chunk's frames are
-// contiguous bytes the loads go through LDS in coalesced 16-byte pieces (LoudStage).
+// contiguous bytes the loads go through LDS in coalesced 16-byte pieces (LoudStage).  The sources' rules and the staging are
+// in alac_loud_source.hpp, shared with alac_true_peak.hip.
 #include "alac_hip.h"
 #include "alac_dev.hpp"
 #include "alac_kernels.hpp"
+#include "alac_loud_source.hpp"
 #include "alac_pcm_load.hpp"
 #include "alac_probe_walk.hpp"
 
@@ -108,46 +110,6 @@ void loud_state_maps(const double (&coef)[10], uint32_t L, double (&M)[16], doub
     zero_input_map(coef, (uint64_t)L * kLoudGroup, MG);
 }
 
-// ---- what a source format adds: a raw container -> x, the peak's word and the non-finite count ----
-// the peak's word orders as |x| does: |s| of an integer sample, the bit pattern of |f| of a finite float
-template <int CB>
-struct LoudInt {
-    static constexpr int kBytes = CB;
-    uint32_t rsh;
-    int32_t lo, hi;
-    double scale;  // 2^-(S-1)
-    __device__ __forceinline__ explicit LoudInt(const LoudArgs &a)
-    {
-        const uint32_t S = a.srcBits;
-        rsh = a.leftJustified ? 8u * CB - S : 0u;
-        hi = (int32_t)(0x7fffffffu >> (32u - S));
-        lo = ~hi;
-        scale = __hiloint2double((int)((1023u - (S - 1u)) << 20), 0);
-    }
-    __device__ __forceinline__ double value(uint32_t raw, uint32_t &peak, uint32_t &nonfinite) const
-    {
-        const int32_t s = min(max((int32_t)raw >> rsh, lo), hi);
-        const uint32_t mag = s < 0 ? 0u - (uint32_t)s : (uint32_t)s;
-        peak = mag > peak ? mag : peak;
-        return (double)s * scale;  // exact: |s| <= 2^31
-    }
-    __device__ __forceinline__ double peak_value(uint32_t word) const { return (double)word * scale; }
-};
-
-struct LoudFloat {
-    static constexpr int kBytes = 4;
-    __device__ __forceinline__ explicit LoudFloat(const LoudArgs &) {}
-    __device__ __forceinline__ double value(uint32_t raw, uint32_t &peak, uint32_t &nonfinite) const
-    {
-        const uint32_t mag = raw & 0x7fffffffu;
-        const bool finite = mag < 0x7f800000u;
-        nonfinite += !finite;
-        peak = finite && mag > peak ? mag : peak;
-        return finite ? (double)__uint_as_float(raw) : 0.0;
-    }
-    __device__ __forceinline__ double peak_value(uint32_t word) const { return (double)__uint_as_float(word); }
-};
-
 // the containers of frames [f0, f0 + 4), f0 a multiple of 4, of the CH channels of a vector layout
 template <int CB, int CH, int LAYOUT>
 __device__ __forceinline__ void loud_load_group(const LoudArgs &a, uint64_t f0, uint32_t (&v)[CH][4])
@@ -165,55 +127,6 @@ __device__ __forceinline__ void loud_load_group(const LoudArgs &a, uint64_t f0, 
         load_run<CB, 4 * CH>((const uint8_t *)a.in + f0 * (CH * CB), e);
 #pragma unroll
         for (int j = 0; j < 4 * CH; j++) v[j % CH][j / CH] = (uint32_t)e[j];
-    }
-}
-
-// adds to one report (8 words: alac_hip_loudness_report; word 2 collects the peak's word, words 4-5 the count)
-__device__ __forceinline__ void loud_add(uint32_t *report, uint32_t peak, uint32_t nonfinite)
-{
-    if (peak) atomicMax(report + 2, peak);
-    if (nonfinite) atomicAdd((unsigned long long *)(report + 4), (unsigned long long)nonfinite);
-}
-
-// The staged loads of a pass (frame-contiguous vector layouts: interleaved stereo and mono, FB bytes per frame).  The lanes of
-// a wave sit L frames apart, so the wave takes its 64 chunks in time slices of kFrames frames: the 64 runs of a slice (kRun
-// bytes each) are loaded kPieces 16-byte pieces per run — consecutive lanes take consecutive pieces, at 16-byte aligned
-// addresses from the run's first byte rounded down — into the wave's 64 rows of LDS, and lane k then walks row k.  A row is
-// kRow bytes: its pieces and one pad word, an odd count of words, so that the 64 lanes' reads fall into different banks.
-template <int FB>
-struct LoudStage {
-    static constexpr uint32_t kFrames = 16, kRun = kFrames * FB, kPieces = kRun / 16 + 1, kRow = 16 * kPieces + 4;
-    uint8_t rows[4][64 * kRow];  // per wave of the block
-    uint64_t first[4][64];       // per lane: the address of its chunk's first byte
-    uint32_t total[4][64];       // ... the chunk's bytes (0: nothing to load)
-    uint32_t slack[4][64];       // ... the bytes of the segment in front of the chunk (low byte) and behind it, each up to 15
-};
-
-// slice t of the wave's runs into its rows.  A piece that lies inside the segment is one aligned 16-byte load; a piece that
-// reaches over an end of the segment is loaded byte by byte, its bytes inside the run only: nothing outside the segment is read
-template <int FB>
-__device__ __forceinline__ void loud_stage_slice(LoudStage<FB> &S, uint32_t w, uint32_t lane, uint32_t t)
-{
-    using St = LoudStage<FB>;
-    for (uint32_t q = lane; q < 64 * St::kPieces; q += 64) {
-        const uint32_t k = q / St::kPieces, i = q % St::kPieces;
-        const uint32_t tot = S.total[w][k], done = t * St::kRun;
-        if (done >= tot) continue;
-        const uint32_t n = tot - done < St::kRun ? tot - done : St::kRun;
-        const uint64_t b = S.first[w][k] + done, e = b + n;
-        const uint64_t p = (b & ~15ull) + 16 * i;
-        if (p >= e) continue;
-        const uint32_t sl = S.slack[w][k], behind = (sl >> 8) + (tot - done - n);
-        const uint64_t lo = b - (t ? 15u : (sl & 255u)), hi = e + (behind < 15 ? behind : 15u);
-        uint8_t *dst = S.rows[w] + k * St::kRow + 16 * i;
-        if (p >= lo && p + 16 <= hi) {
-            const uint4 v = *(const uint4 *)p;
-            uint32_t *d = (uint32_t *)dst;
-            d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
-        } else {
-            for (uint32_t x = 0; x < 16; x++)
-                if (p + x >= b && p + x < e) dst[x] = *(const uint8_t *)(p + x);
-        }
     }
 }
 

@@ -91,7 +91,13 @@
  *                                             Files above two channels are weighted by the layout tag their encode would
  *                                             carry.  A file that cannot be measured (an undecodable packet, a sample rate
  *                                             that is not a multiple of 10 in 8 000 .. 384 000) is named on stderr and the exit
- *                                             status is 1.  No other option is accepted.
+ *                                             status is 1.  No other option is accepted but --true-peak.
+ *   --loudness --true-peak [--devices N] <file> ...  the same lines with the true peak (ITU-R BS.1770-4 annex 2, the peak
+ *                                             ReplayGain 2.0 and EBU R128 mean) in a column of its own,
+ *                                             "%.2f LUFS  %.2f dBFS  %.2f dBTP  <frames>  <path>".  ALAC files go through
+ *                                             ALACDecoder::LoudnessTruePeakBatch (both measurements on the one decoded plane),
+ *                                             PCM files through alac_hip_true_peak_int_host / _float_host as well.
+ *                                             --true-peak without --loudness is refused with the usage text.
  *   --crc-check <list>                        read lines of that format, compute every file's value again and print
  *                                             "<path>: OK", "<path>: FAILED" or "<path>: FAILED open"; exit 1 if any line
  *                                             failed (the flow of sha256sum -c).  With --devices N; no other option
@@ -140,8 +146,9 @@ struct Job {
     bool opened = false, done = false;
     uint32_t crc = 0;
     uint64_t crcFrames = 0;
-    // --loudness (with done and crcFrames): the integrated loudness in LUFS and the sample peak, 1.0 = full scale
-    double lufs = 0.0, peak = 0.0;
+    // --loudness (with done and crcFrames): the integrated loudness in LUFS and the sample peak, 1.0 = full scale; with
+    // --true-peak the true peak as well
+    double lufs = 0.0, peak = 0.0, truePeak = 0.0;
 };
 typedef std::map<std::string, std::vector<Job *> > Groups;  // files that go through the GPU in one call
 
@@ -833,8 +840,8 @@ int crc_check(const Options &o)
 }
 
 // ---- --loudness: integrated loudness and sample peak of every file, measured on the GPU; nothing is written ----
-// ALAC files of one cookie: one LoudnessBatch, one segment per file
-void loudness_alac_group(std::vector<Job *> &jobs, int device)
+// ALAC files of one cookie: one LoudnessBatch (truePeak: one LoudnessTruePeakBatch), one segment per file
+void loudness_alac_group(std::vector<Job *> &jobs, int device, bool truePeak)
 {
     ALACDecoder dec;
     if (!open_decoder(dec, jobs[0]->contents.cookie, device)) {
@@ -849,11 +856,13 @@ void loudness_alac_group(std::vector<Job *> &jobs, int device)
     Bytes stream;
     const std::vector<uint32_t> firstPacket = gather_packets(take, stream, sizes);
     const uint32_t np = (uint32_t)sizes.size();
-    std::vector<double> lufs(take.size()), peak(take.size());
+    std::vector<double> lufs(take.size()), peak(take.size()), tp(take.size(), 0.0);
     std::vector<uint32_t> frames(np, 0);
     std::vector<int32_t> status(np, 0);
-    const int32_t rc = dec.LoudnessBatch(stream.data(), sizes.data(), np, firstPacket.data(), (uint32_t)take.size(), lufs.data(),
-                                         peak.data(), frames.data(), status.data());
+    const int32_t rc = truePeak ? dec.LoudnessTruePeakBatch(stream.data(), sizes.data(), np, firstPacket.data(), (uint32_t)take.size(),
+                                                            lufs.data(), peak.data(), tp.data(), frames.data(), status.data())
+                                : dec.LoudnessBatch(stream.data(), sizes.data(), np, firstPacket.data(), (uint32_t)take.size(),
+                                                    lufs.data(), peak.data(), frames.data(), status.data());
     if (rc != ALAC_noErr) {
         fprintf(stderr, " Measuring failed (status %d): \"%s\"\n", rc, take[0]->in.c_str());
         return;
@@ -868,13 +877,13 @@ void loudness_alac_group(std::vector<Job *> &jobs, int device)
         }
         J.crcFrames = 0;
         for (p = firstPacket[j]; p < firstPacket[j + 1]; p++) J.crcFrames += frames[p];
-        J.lufs = lufs[j], J.peak = peak[j];
+        J.lufs = lufs[j], J.peak = peak[j], J.truePeak = tp[j];
         J.done = true;
     }
 }
 
 // PCM files, integer or float: each one staged and measured as one segment
-void loudness_pcm_group(std::vector<Job *> &jobs, int device)
+void loudness_pcm_group(std::vector<Job *> &jobs, int device, bool truePeak)
 {
     alac_hip_ctx *ctx = nullptr;
     const char *dev = getenv("ALAC_HIP_DEVICE");
@@ -904,6 +913,17 @@ void loudness_pcm_group(std::vector<Job *> &jobs, int device)
             rc = alac_hip_loudness_int_host(ctx, pcm.data(), &src, C, rate, frames, nullptr, 1, energy.data(), rows, &rep);
         }
         if (rc == ALAC_HIP_noErr) rc = alac_hip_loudness_integrated(energy.data(), rep.num_blocks, C, rate / 10, nullptr, &J.lufs);
+        if (rc == ALAC_HIP_noErr && truePeak) {
+            double channelPeak[8];
+            alac_hip_true_peak_report tp = {};
+            if (in.isFloat) {
+                rc = alac_hip_true_peak_float_host(ctx, (const float *)pcm.data(), C, 1, C, rate, frames, nullptr, 1, channelPeak, &tp);
+            } else {
+                const alac_hip_int_source src = {bytes_per_sample(in.bitsPerChannel), in.bitsPerChannel, 1, 0, 1, C};
+                rc = alac_hip_true_peak_int_host(ctx, pcm.data(), &src, C, rate, frames, nullptr, 1, channelPeak, &tp);
+            }
+            J.truePeak = tp.true_peak;
+        }
         if (rc != ALAC_HIP_noErr) {
             fprintf(stderr, " Measuring failed (status %d): %s: \"%s\"\n", rc, alac_hip_last_error(ctx), J.in.c_str());
             continue;
@@ -935,8 +955,8 @@ int loudness_files(const Options &o)
         if (!J.info.isAlac && !J.info.isFloat && !pcm_format_ok(J)) continue;
         groups[J.info.isAlac ? cookie_key(J) : std::string("P")].push_back(&J);
     }
-    run_dealt(groups, o.devices, [](std::vector<Job *> &part, int device) {
-        (part[0]->info.isAlac ? loudness_alac_group : loudness_pcm_group)(part, device);
+    run_dealt(groups, o.devices, [&](std::vector<Job *> &part, int device) {
+        (part[0]->info.isAlac ? loudness_alac_group : loudness_pcm_group)(part, device, o.truePeak);
         return true;
     });
     int rc = 0;
@@ -947,7 +967,11 @@ int loudness_files(const Options &o)
             continue;
         }
         // printf writes -inf for the logarithm of nothing: a silent file has neither a loudness nor a peak in dB
-        printf("%.2f LUFS  %.2f dBFS  %llu  %s\n", J.lufs, 20.0 * log10(J.peak), (unsigned long long)J.crcFrames, J.in.c_str());
+        if (o.truePeak)
+            printf("%.2f LUFS  %.2f dBFS  %.2f dBTP  %llu  %s\n", J.lufs, 20.0 * log10(J.peak), 20.0 * log10(J.truePeak),
+                   (unsigned long long)J.crcFrames, J.in.c_str());
+        else
+            printf("%.2f LUFS  %.2f dBFS  %llu  %s\n", J.lufs, 20.0 * log10(J.peak), (unsigned long long)J.crcFrames, J.in.c_str());
     }
     return rc;
 }

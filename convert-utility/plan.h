@@ -27,7 +27,8 @@ struct DitherOption {
 struct Options {
     std::vector<std::string> files;
     bool batch = false, lpc = false, verify = false, verifySource = false, compare = false, crc = false;
-    bool loudness = false;  // --loudness: no other option but --devices N
+    bool loudness = false;  // --loudness: no other option but --devices N and --true-peak
+    bool truePeak = false;  // --true-peak: only with --loudness
     std::string crcList;  // --crc-check <list>
     uint32_t segmentPackets = 0, devices = 0, floatBits = 0;
     bool floatAuto = false;  // --float-bits auto: floatBits stays 0, every file gets its own depth from the probe
@@ -105,6 +106,8 @@ inline bool parse_args(int argc, char **argv, Options &o)
             o.crc = true;
         } else if (a == "--loudness") {
             o.loudness = true;
+        } else if (a == "--true-peak") {
+            o.truePeak = true;
         } else if (a == "--crc-check" && more) {
             o.crcList = argv[++i];
             malformed = o.crcList.empty();
@@ -146,13 +149,17 @@ inline bool parse_args(int argc, char **argv, Options &o)
     const size_t n = o.files.size();
     const bool crcMode = o.crc || !o.crcList.empty();
     if (o.loudness) {
-        // --loudness stands alone (but --devices N): any number of inputs, no output files
+        // --loudness stands alone (but --devices N and --true-peak): any number of inputs, no output files
         if (malformed || n == 0 || crcMode || o.compare || o.dither.on || o.dither.seed || o.bitsNamed || o.batch || o.lpc ||
             o.verify || o.verifySource || o.segmentPackets || o.floatInput() || o.intConvert()) {
             usage();
             return false;
         }
         return true;
+    }
+    if (o.truePeak) {  // --true-peak adds a column to the lines of --loudness: nothing without it
+        usage();
+        return false;
     }
     if (!malformed && o.bitsNamed && (o.floatInput() || o.compare || crcMode)) {
         fprintf(stderr, " --bits converts integer PCM in front of an encode: not with %s\n",

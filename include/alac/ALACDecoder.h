@@ -89,12 +89,24 @@ public:
     int32_t LoudnessBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets, const uint32_t *fileFirstPacket,
                           uint32_t numFiles, double *outLufs, double *outPeak, uint32_t *outFrames, int32_t *outStatus);
 
+    /* LoudnessBatch with both measurements taken on the one decoded plane: outTruePeak[j] is the true peak of file j (ITU-R
+     * BS.1770-4 annex 2, alac_hip_true_peak_int over the same segments; 1.0 = full scale), the maximum over its channels.  The
+     * other outputs and the return value are LoudnessBatch's.  A file that is not measured gives true peak 0. */
+    int32_t LoudnessTruePeakBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets,
+                                  const uint32_t *fileFirstPacket, uint32_t numFiles, double *outLufs, double *outPeak,
+                                  double *outTruePeak, uint32_t *outFrames, int32_t *outStatus);
+
     int32_t LastStatus() const { return mLastStatus; }
 
 public:
     ALACSpecificConfig mConfig;  /* host-endian copy, as in the reference (codec/ALACDecoder.cu:139-151) */
 
 private:
+    /* LoudnessBatch (outTruePeak NULL) and LoudnessTruePeakBatch */
+    int32_t MeasureBatch(const uint8_t *stream, const uint32_t *packetBytes, uint32_t numPackets, const uint32_t *fileFirstPacket,
+                         uint32_t numFiles, double *outLufs, double *outPeak, double *outTruePeak, uint32_t *outFrames,
+                         int32_t *outStatus);
+
     alac_hip_ctx *mCtx;
     int mDevice; /* -1: ALAC_HIP_DEVICE or 0 */
     std::vector<uint8_t> mCookie;

@@ -837,6 +837,74 @@ uint64_t alac_hip_loudness_rows(uint32_t sample_rate, uint64_t total_frames, con
 int32_t alac_hip_loudness_integrated(const double *h_energy, uint64_t num_blocks, uint32_t num_channels, uint32_t hop,
                                      const double *weights, double *out_lufs);
 
+/* ---- true peak of PCM: ITU-R BS.1770-4 annex 2, computed where the PCM lies -----------------------------------------------------
+ * The peak ReplayGain 2.0 and EBU R128 mean is the true peak: the maximum of the signal oversampled four times, which tells
+ * whether applying a gain will clip (a sine at fs/4 sampled 45 degrees off its crests has a sample peak 3 dB below it).  This
+ * call gives it for PCM in device memory, per segment of frames and per channel, next to the sample peak of the loudness
+ * call; only a few numbers per segment cross the bus.  No reference counterpart.
+ * The rule.
+ *   Sample value.  Exactly that of the loudness rule above: x = s * 2^-(S-1) in double for an integer source read as
+ *     alac_hip_int_probe reads it, x = (double)f for a float source indexed as alac_hip_float_probe indexes it; a non-finite
+ *     float is read as 0.0 and counted.
+ *   Factor.  F = 4 for fs < 96 000, F = 2 for 96 000 <= fs < 192 000, F = 1 from 192 000 up (libebur128's choice).  fs must be
+ *     one the loudness call accepts: a multiple of 10 in [8 000, 384 000].
+ *   Filter.  The closed form libebur128 uses, a 49-tap Hann-windowed sinc: for j = 0..48, m = j - 24,
+ *         h[j] = (m == 0 ? 1 : sin(m pi / F) / (m pi / F)) * 0.5 * (1 - cos(2 pi j / 48))
+ *     Tap j belongs to phase p = j mod F at index k = j div F; taps with |h[j]| < 1e-6 are dropped.  That leaves
+ *       F = 4   phase 0: the single tap 1.0 at k = 6;   phases 1, 2, 3: K = 12 taps each, k = 0..11
+ *       F = 2   phase 0: the single tap 1.0 at k = 12;  phase 1: K = 24 taps, k = 0..23
+ *     Phase 0 is the sample itself: it is not filtered, it is the sample peak.
+ *   Output samples.  For a segment of N frames and a phase p >= 1:
+ *         y_p[n] = sum_k h_p[k] x[n - k]     for n in [0, N + K - 1),   x = 0 outside [0, N) of the segment
+ *     accumulated from 0 with k ascending, every step one fused multiply-add, in double.  Both ends are zero-extended, so the
+ *     filter's tail is flushed.  (libebur128 does not flush it and can report a true peak below the sample peak when the peak
+ *     lies in the last six frames.  This rule cannot do that.)
+ *   Results, per segment.  Per channel: true_peak = max(sample peak, max over p >= 1 and n of |y_p[n]|), in
+ *     d_channel_peak[s * num_channels + c].  The report holds the maximum over the channels, the sample peak over the channels
+ *     (the same value as alac_hip_loudness_report.peak) and the non-finite count.  F = 1: the true peak is the sample peak.  An
+ *     empty segment gives 0.
+ *   A segment is measured from its own frames alone: no frame outside it is read, not even as history, and the history in
+ *   front of its first frame is zero whatever lies there in the buffer.  A maximum does not depend on any order, so the
+ *   results are the same bits whatever the grid, the other segments of the call and the segment's place in the buffer.
+ *   d_in, src / channel_stride, frame_stride, sample_rate, total_frames, h_seg_first_frame, num_segments
+ *                     as in alac_hip_loudness_int / alac_hip_loudness_float
+ *   d_workspace       alac_hip_true_peak_workspace_bytes(num_channels, num_segments) bytes, 8-byte aligned, needed with and
+ *                     without a table: the segment tables.  It does not grow with the frame count.
+ *   d_channel_peak    [num_segments * num_channels] doubles, 8-byte aligned
+ *   d_reports         [num_segments] alac_hip_true_peak_report, 8-byte aligned
+ * Every word of every report and of d_channel_peak is written by every call.  Asynchronous on the context's stream.
+ * kALAC_ParamError, with nothing enqueued and nothing written: everything the loudness call refuses in the source,
+ * num_channels, the table, the sample rate, the workspace and d_reports; a null or misaligned d_channel_peak.
+ */
+typedef struct alac_hip_true_peak_report { /* one per segment, 32 bytes */
+    double true_peak;   /* max over the channels, 1.0 = full scale; 0 if empty */
+    double peak;        /* the sample peak, as alac_hip_loudness_report.peak */
+    uint64_t nonfinite; /* as there */
+    uint64_t reserved;  /* written as 0 */
+} alac_hip_true_peak_report;
+uint64_t alac_hip_true_peak_workspace_bytes(uint32_t num_channels, uint32_t num_segments);
+int32_t alac_hip_true_peak_int(alac_hip_ctx *ctx, const void *d_in, const alac_hip_int_source *src, uint32_t num_channels,
+                               uint32_t sample_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                               uint32_t num_segments, void *d_workspace, uint64_t workspace_bytes, double *d_channel_peak,
+                               alac_hip_true_peak_report *d_reports);
+int32_t alac_hip_true_peak_float(alac_hip_ctx *ctx, const float *d_in, uint32_t num_channels, uint64_t channel_stride,
+                                 uint64_t frame_stride, uint32_t sample_rate, uint64_t total_frames,
+                                 const uint64_t *h_seg_first_frame, uint32_t num_segments, void *d_workspace,
+                                 uint64_t workspace_bytes, double *d_channel_peak, alac_hip_true_peak_report *d_reports);
+/* Host-buffer forms (synchronous): h_in in the layout above, staged as the loudness host forms stage it; the channel peaks come
+ * back in h_channel_peak [num_segments * num_channels], the reports in h_reports [num_segments]. */
+int32_t alac_hip_true_peak_int_host(alac_hip_ctx *ctx, const void *h_in, const alac_hip_int_source *src, uint32_t num_channels,
+                                    uint32_t sample_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                                    uint32_t num_segments, double *h_channel_peak, alac_hip_true_peak_report *h_reports);
+int32_t alac_hip_true_peak_float_host(alac_hip_ctx *ctx, const float *h_in, uint32_t num_channels, uint64_t channel_stride,
+                                      uint64_t frame_stride, uint32_t sample_rate, uint64_t total_frames,
+                                      const uint64_t *h_seg_first_frame, uint32_t num_segments, double *h_channel_peak,
+                                      alac_hip_true_peak_report *h_reports);
+/* Host only, no context: F of fs in *out_factor, the taps per phase K (12, 24, or 0 where F = 1) in *out_taps and the
+ * coefficients of phases 1 .. F-1 in out_coefs [F - 1][K] (room for 36 doubles).  The kernels take their coefficients from
+ * here.  kALAC_ParamError for a bad fs or a null pointer. */
+int32_t alac_hip_true_peak_filter(uint32_t sample_rate, uint32_t *out_factor, uint32_t *out_taps, double *out_coefs);
+
 /* Parse a magic cookie into a format (host only). */
 int32_t alac_hip_format_from_cookie(const uint8_t *h_cookie, uint32_t cookie_size,
                                     alac_hip_format *out_fmt);
