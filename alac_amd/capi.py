@@ -72,6 +72,15 @@ class TruePeakReport(C.Structure):
     _fields_ = [("true_peak", C.c_double), ("peak", C.c_double), ("nonfinite", C.c_uint64), ("reserved", C.c_uint64)]
 
 
+class ResampleReport(C.Structure):
+    """alac_hip_resample_report: one per segment of alac_hip_resample_int / _float, 32 bytes"""
+    _fields_ = [("out_first", C.c_uint64), ("out_frames", C.c_uint64), ("peak", C.c_double), ("nonfinite", C.c_uint64)]
+
+
+# the output frames of a block's tile of k_resample at the usual ratios (kResampleTile, alac_kernels.hpp; long filters take
+# fewer, resample_tile()): the size at which the kernel changes path, for the tests
+RESAMPLE_TILE = 512
+
 # the frames of a lane's run of k_true_peak by oversampling factor (true_peak_run, alac_kernels.hpp); a block covers 256 runs:
 # the sizes at which the kernel changes path, for the tests
 TRUE_PEAK_RUN = {4: 53, 2: 105, 1: 64}
@@ -181,6 +190,14 @@ SIGNATURES = {
     "alac_hip_true_peak_int_host": (_i32, [_vp, _vp, _vp, _u32, _u32, _u64, _vp, _u32, _vp, _vp]),
     "alac_hip_true_peak_float_host": (_i32, [_vp, _vp, _u32, _u64, _u64, _u32, _u64, _vp, _u32, _vp, _vp]),
     "alac_hip_true_peak_filter": (_i32, [_u32, C.POINTER(_u32), C.POINTER(_u32), _vp]),
+    "alac_hip_resample_filter": (_i32, [_u32, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), _vp]),
+    "alac_hip_resample_frames": (_u64, [_u32, _u32, _u64, _vp, _u32, _vp]),
+    "alac_hip_resample_workspace_bytes": (_u64, [_u32, _u32, _u32, _u32]),
+    "alac_hip_resample_int": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _u32, _vp, _u64, _vp, _u64, _u64, _vp]),
+    "alac_hip_resample_float": (_i32, [_vp, _vp, _u32, _u64, _u64, _u32, _u32, _u64, _vp, _u32, _vp, _u64, _vp, _u64, _u64,
+                                       _vp]),
+    "alac_hip_resample_int_host": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _u32, _vp, _u64, _u64, _vp]),
+    "alac_hip_resample_float_host": (_i32, [_vp, _vp, _u32, _u64, _u64, _u32, _u32, _u64, _vp, _u32, _vp, _u64, _u64, _vp]),
     "alac_synth_frame": (None, [_u64, _u32, _u32, _u32, _vp]),
     "alac_synth_pcm": (None, [_u64, _u32, _u32, _u32, _u32, _vp]),
     "alac_hip_synth_pcm": (_i32, [_vp, _u64, _u32, C.POINTER(Format), _vp]),
@@ -309,6 +326,32 @@ def true_peak_filter(sample_rate):
         raise ValueError("true_peak_filter: the sample rate must be a multiple of 10 in [8000, 384000]")
     n = (factor.value - 1) * taps.value
     return factor.value, out[:n].reshape(factor.value - 1, taps.value).copy()
+
+
+def resample_filter(in_rate, out_rate):
+    """alac_hip_resample_filter: (L, M, coefficients) of a rate pair: out_rate / gcd, in_rate / gcd and the polyphase filter
+    h_p[k] as a float64 array [L, K].  Host only, no GPU needed."""
+    lib = load_library()
+    L, M, K = _u32(0), _u32(0), _u32(0)
+    if lib.alac_hip_resample_filter(int(in_rate), int(out_rate), C.byref(L), C.byref(M), C.byref(K), None) != 0:
+        raise ValueError("resample_filter: the rates must be different multiples of 10 in [8000, 384000] with L and M of at "
+                         "most 640")
+    out = np.zeros((L.value, K.value), dtype=np.float64)
+    if lib.alac_hip_resample_filter(int(in_rate), int(out_rate), C.byref(L), C.byref(M), C.byref(K), out.ctypes.data) != 0:
+        raise ValueError("resample_filter: bad arguments")
+    return L.value, M.value, out
+
+
+def resample_frames(in_rate, out_rate, total_frames, seg_first_frame=None):
+    """alac_hip_resample_frames: (total, out_first): the output frames of all segments back to back and every segment's
+    first output frame, a uint64 array [num_segments + 1].  (0, zeros) for arguments the calls refuse.  Host only."""
+    table = None if seg_first_frame is None else np.ascontiguousarray(seg_first_frame, dtype=np.uint64)
+    nseg = 1 if table is None else max(0, table.size - 1)
+    out_first = np.zeros(nseg + 1, dtype=np.uint64)
+    total = int(load_library().alac_hip_resample_frames(int(in_rate), int(out_rate), int(total_frames),
+                                                        None if table is None else table.ctypes.data, nseg,
+                                                        out_first.ctypes.data))
+    return total, out_first
 
 
 def synth_pcm(first_frame, num_frames, fmt):
@@ -844,6 +887,72 @@ class Context:
         synchronized."""
         raw = np.ascontiguousarray(reports.cpu().numpy())
         return [TruePeakReport.from_buffer_copy(raw[s].tobytes()) for s in range(raw.shape[0])]
+
+    def _resample(self, what, channels, in_rate, out_rate, frames, seg_first_frame, call):
+        """the part resample_int() and resample_float() share: the table, the outputs and the workspace; call(table pointer,
+        num_segments, workspace, output tensor, its frames, reports tensor) -> status"""
+        t = self.torch
+        keep, table, nseg, reports = self._measure_table(what, seg_first_frame)
+        total = int(self.lib.alac_hip_resample_frames(int(in_rate), int(out_rate), frames, table, nseg, None))
+        y = t.empty((channels, total), dtype=t.float32, device=self.device)
+        ws = self._workspace(max(16, int(self.lib.alac_hip_resample_workspace_bytes(int(in_rate), int(out_rate), channels, nseg))))
+        # a tensor without elements has no address; the call wants one, and writes nothing through it
+        target = y if total else t.zeros(1, dtype=t.float32, device=self.device)
+        self._check(call(table, nseg, ws, target, total, reports))
+        del keep
+        return y, reports
+
+    def resample_int(self, x, in_rate, out_rate, bits=None, left_justified=True, seg_first_frame=None, container_bytes=None,
+                     channel_stride=None, frame_stride=None, num_channels=None):
+        """alac_hip_resample_int: integer PCM at in_rate -> float32 planar PCM at out_rate, per segment of frames, by the
+        windowed-sinc rule of include/alac_hip.h.  The arguments of true_peak_int().  Returns (y, reports): a float32 cuda
+        tensor [channels, out_total], the segments back to back at the offsets of resample_frames(), which is what
+        encode_float() takes, and an int32 cuda tensor [num_segments, 8] viewing the alac_hip_resample_report of every segment
+        (resample_reports() reads them).  Asynchronous."""
+        with self._call() as cur:
+            t = self.torch
+            if x.dim() == 2:
+                channels = int(x.shape[0])
+            elif num_channels is not None:
+                channels = int(num_channels)
+            else:
+                channels = int(frame_stride) if channel_stride == 1 and frame_stride else 1
+            cb, cs, fst, frames = self._int_tensor("resample_int", x, channels, container_bytes, channel_stride, frame_stride)
+            src = IntSource(cb, 8 * cb if bits is None else int(bits), 1 if left_justified else 0, 0, cs, fst)
+            base = x if x.numel() else t.zeros(4, dtype=t.int32, device=self.device)
+            y, reports = self._resample(
+                "resample_int", channels, in_rate, out_rate, frames, seg_first_frame,
+                lambda table, nseg, ws, out, total, rep: self.lib.alac_hip_resample_int(
+                    self.h, base.data_ptr(), C.byref(src), channels, int(in_rate), int(out_rate), frames, table, nseg,
+                    ws.data_ptr(), ws.numel(), out.data_ptr(), total, total, rep.data_ptr()))
+            y.record_stream(cur)
+            reports.record_stream(cur)
+            return y, reports
+
+    def resample_float(self, x, in_rate, out_rate, seg_first_frame=None):
+        """alac_hip_resample_float: resample_int() for a float32 cuda tensor [channels, frames] with any strides, passed
+        through like probe_float()'s.  Non-finite samples are read as 0.0 and counted in the reports."""
+        with self._call() as cur:
+            t = self.torch
+            if not (x.is_cuda and x.dtype == t.float32 and x.dim() == 2):
+                raise ValueError("resample_float: x must be a float32 cuda tensor [channels, frames]")
+            base = x if x.shape[1] else t.zeros(4, dtype=t.float32, device=self.device)
+            channels, frames = int(x.shape[0]), int(x.shape[1])
+            y, reports = self._resample(
+                "resample_float", channels, in_rate, out_rate, frames, seg_first_frame,
+                lambda table, nseg, ws, out, total, rep: self.lib.alac_hip_resample_float(
+                    self.h, base.data_ptr(), channels, int(x.stride(0)), int(x.stride(1)), int(in_rate), int(out_rate), frames,
+                    table, nseg, ws.data_ptr(), ws.numel(), out.data_ptr(), total, total, rep.data_ptr()))
+            y.record_stream(cur)
+            reports.record_stream(cur)
+            return y, reports
+
+    @staticmethod
+    def resample_reports(reports):
+        """the reports of resample_int() / resample_float() on the host: a list of ResampleReport.  The caller has
+        synchronized."""
+        raw = np.ascontiguousarray(reports.cpu().numpy())
+        return [ResampleReport.from_buffer_copy(raw[s].tobytes()) for s in range(raw.shape[0])]
 
     def pcm_crc32_device(self, pcm, ranges=None):
         """alac_hip_pcm_crc32: zlib.crc32 of ranges of a uint8 cuda tensor, computed where it lies.  ranges: a sequence of

@@ -1584,6 +1584,99 @@ int32_t alac_hip_true_peak_float(alac_hip_ctx *ctx, const float *d_in, uint32_t 
                           sample_rate, h_seg_first_frame, lo, hi, d_workspace, workspace_bytes, d_channel_peak, d_reports);
 }
 
+// ---- sample-rate conversion: a polyphase windowed-sinc FIR, per segment of frames ---------------------------------------------
+// the workspace: segFirst, outFirst and tileBase, [num_segments + 1] each, then the coefficients [L][K]
+static uint64_t resample_table_bytes(uint32_t num_segments) { return align_up(3 * ((uint64_t)num_segments + 1) * 8, 256); }
+
+uint64_t alac_hip_resample_workspace_bytes(uint32_t in_rate, uint32_t out_rate, uint32_t num_channels, uint32_t num_segments)
+{
+    const ResamplePlan p = resample_plan(in_rate, out_rate);
+    if (!p.ok || num_channels < 1 || num_channels > kMaxChannels || num_segments == 0) return 0;
+    return resample_table_bytes(num_segments) + align_up((uint64_t)p.L * p.K * 8, 256);
+}
+
+// What both resampling calls do behind the source's own refusals (as true_peak_impl): the remaining refusals, then the tables
+// and the coefficients to the device in one upload, and the pass.  src: the source (what loudness_source fills).
+static int32_t resample_impl(alac_hip_ctx *ctx, const LoudArgs &src, uint32_t in_rate, uint32_t out_rate, uint64_t total_frames,
+                             const uint64_t *h_seg_first_frame, uint64_t lo, uint64_t hi, void *d_workspace,
+                             uint64_t workspace_bytes, float *d_out, uint64_t out_channel_stride, uint64_t out_frames,
+                             void *d_reports)
+{
+    const ResamplePlan p = resample_plan(in_rate, out_rate);
+    if (!p.ok)
+        return fail(ctx, ALAC_HIP_ParamError,
+                    "rates must be different multiples of 10 in [8000, 384000] with L and M of at most 640");
+    if (total_frames > UINT64_MAX / 1024) return fail(ctx, ALAC_HIP_ParamError, "total_frames too large");
+    if (!d_reports || ((uintptr_t)d_reports & 7)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned d_reports (8 B)");
+    if (!d_out || ((uintptr_t)d_out & 3)) return fail(ctx, ALAC_HIP_ParamError, "null or misaligned d_out (4 B)");
+    if (!d_workspace || ((uintptr_t)d_workspace & 15))
+        return fail(ctx, ALAC_HIP_ParamError, "null or misaligned workspace (16 B)");
+    const uint32_t nseg = src.numSegments;
+    if (workspace_bytes < alac_hip_resample_workspace_bytes(in_rate, out_rate, src.channels, nseg))
+        return fail(ctx, ALAC_HIP_ParamError, "workspace too small");
+    ResampleArgs a = {};
+    a.in = src.in, a.channelStride = src.channelStride, a.frameStride = src.frameStride;
+    a.numSegments = nseg, a.channels = src.channels;
+    a.containerBytes = src.containerBytes, a.srcBits = src.srcBits, a.leftJustified = src.leftJustified;
+    a.L = p.L, a.M = p.M, a.K = p.K;
+    a.tile = resample_tile(p), a.span = (uint32_t)resample_span(p, a.tile);
+    const uint64_t tabWords = resample_table_bytes(nseg) / 8, coefWords = (uint64_t)p.L * p.K;
+    std::vector<uint64_t> table(tabWords + coefWords, 0);
+    uint64_t *first = table.data(), *outFirst = first + nseg + 1, *tileBase = outFirst + nseg + 1;
+    for (uint32_t s = 0; s <= nseg; s++) first[s] = h_seg_first_frame ? h_seg_first_frame[s] : (s ? hi : lo);
+    for (uint32_t s = 0; s < nseg; s++) {
+        const uint64_t n = resample_out_frames(p, first[s + 1] - first[s]);
+        outFirst[s + 1] = outFirst[s] + n;
+        tileBase[s + 1] = tileBase[s] + (n + a.tile - 1) / a.tile;
+    }
+    if (out_frames < outFirst[nseg]) return fail(ctx, ALAC_HIP_ParamError, "out_frames below alac_hip_resample_frames");
+    if (out_channel_stride < out_frames) return fail(ctx, ALAC_HIP_ParamError, "out_channel_stride below out_frames");
+    if (tileBase[nseg] > 0x7fffffffull) return fail(ctx, ALAC_HIP_ParamError, "too many output frames for one call");
+    memcpy(table.data() + tabWords, resample_coefs(p) + coefWords, coefWords * 8);  // the kernels' arrangement
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    hipError_t e;
+    if ((e = upload_segment_table(ctx, table.data(), table.size(), d_workspace)))
+        return fail(ctx, ALAC_HIP_ParamError, "segment table upload", e);
+    a.segFirst = (const uint64_t *)d_workspace, a.outFirst = a.segFirst + nseg + 1, a.tileBase = a.outFirst + nseg + 1;
+    a.coef = (const double *)(a.segFirst + tabWords);
+    a.totalTiles = tileBase[nseg];
+    a.out = d_out, a.outChannelStride = out_channel_stride;
+    a.reports = (uint32_t *)d_reports;
+    if ((e = launch_resample(a, ctx->stream))) return fail(ctx, ALAC_HIP_ParamError, "resample launch", e);
+    return ALAC_HIP_noErr;
+}
+
+int32_t alac_hip_resample_int(alac_hip_ctx *ctx, const void *d_in, const alac_hip_int_source *src, uint32_t num_channels,
+                              uint32_t in_rate, uint32_t out_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                              uint32_t num_segments, void *d_workspace, uint64_t workspace_bytes, float *d_out,
+                              uint64_t out_channel_stride, uint64_t out_frames, alac_hip_resample_report *d_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = int_probe_refusal(ctx, d_in, src, num_channels, total_frames, h_seg_first_frame, num_segments, lo, hi))
+        return rc;
+    return resample_impl(ctx, loudness_source(d_in, src->channel_stride, src->frame_stride, num_segments, num_channels,
+                                              src->container_bytes, src->bits, src->left_justified),
+                         in_rate, out_rate, total_frames, h_seg_first_frame, lo, hi, d_workspace, workspace_bytes, d_out,
+                         out_channel_stride, out_frames, d_reports);
+}
+
+int32_t alac_hip_resample_float(alac_hip_ctx *ctx, const float *d_in, uint32_t num_channels, uint64_t channel_stride,
+                                uint64_t frame_stride, uint32_t in_rate, uint32_t out_rate, uint64_t total_frames,
+                                const uint64_t *h_seg_first_frame, uint32_t num_segments, void *d_workspace,
+                                uint64_t workspace_bytes, float *d_out, uint64_t out_channel_stride, uint64_t out_frames,
+                                alac_hip_resample_report *d_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = float_probe_refusal(ctx, d_in, num_channels, channel_stride, frame_stride, total_frames, h_seg_first_frame,
+                                         num_segments, lo, hi))
+        return rc;
+    return resample_impl(ctx, loudness_source(d_in, channel_stride, frame_stride, num_segments, num_channels, 0, 0, 0), in_rate,
+                         out_rate, total_frames, h_seg_first_frame, lo, hi, d_workspace, workspace_bytes, d_out,
+                         out_channel_stride, out_frames, d_reports);
+}
+
 uint32_t alac_hip_num_stages(void) { return kNumStages; }
 
 const char *alac_hip_stage_name(uint32_t stage)
@@ -2440,6 +2533,85 @@ int32_t alac_hip_true_peak_float_host(alac_hip_ctx *ctx, const float *h_in, uint
                                                               frame_stride, sample_rate, total_frames, h_seg_first_frame,
                                                               num_segments, dWs, wsBytes, dPeak, dRep);
                           });
+}
+
+extern "C++" {
+// the host form of a resampling call whose source refusals have passed, as true_peak_host: stages spanBytes of h_in, runs
+// call(d_in, workspace, its bytes, d_out, d_reports) with the rows out_frames apart, brings the rows (to h_out, out_channel_stride
+// apart) and the reports back
+template <typename Call>
+static int32_t resample_host(alac_hip_ctx *ctx, const void *h_in, uint64_t spanBytes, uint32_t in_rate, uint32_t out_rate,
+                             uint32_t num_channels, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                             uint32_t num_segments, float *h_out, uint64_t out_channel_stride, uint64_t out_frames,
+                             alac_hip_resample_report *h_reports, Call call)
+{
+    if (!h_reports || !h_out) return fail(ctx, ALAC_HIP_ParamError, "null h_out or h_reports");
+    const uint64_t wsBytes = alac_hip_resample_workspace_bytes(in_rate, out_rate, num_channels, num_segments);
+    if (!wsBytes)
+        return fail(ctx, ALAC_HIP_ParamError,
+                    "rates must be different multiples of 10 in [8000, 384000] with L and M of at most 640");
+    const uint64_t total = alac_hip_resample_frames(in_rate, out_rate, total_frames, h_seg_first_frame, num_segments, nullptr);
+    if (out_frames < total) return fail(ctx, ALAC_HIP_ParamError, "out_frames below alac_hip_resample_frames");
+    if (out_channel_stride < out_frames) return fail(ctx, ALAC_HIP_ParamError, "out_channel_stride below out_frames");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, ALAC_HIP_ParamError, "hipSetDevice");
+    const uint64_t repBytes = (uint64_t)num_segments * 32;
+    DevBuf dIn, dWs, dOut, dRep;
+    hipError_t e;
+    if ((e = dIn.alloc(spanBytes)) || (e = dWs.alloc(wsBytes)) || (e = dOut.alloc((uint64_t)num_channels * total * 4)) ||
+        (e = dRep.alloc(repBytes)))
+        return fail(ctx, ALAC_HIP_MemFullError, "hipMalloc", e);
+    if (spanBytes && (e = hipMemcpyAsync(dIn.p, h_in, spanBytes, hipMemcpyHostToDevice, ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "H2D copy", e);
+    if (int32_t rc = call(dIn.p, dWs.p, wsBytes, (float *)dOut.p, total, (alac_hip_resample_report *)dRep.p)) return rc;
+    for (uint32_t c = 0; c < num_channels && total; c++)
+        if ((e = hipMemcpyAsync(h_out + c * out_channel_stride, (const float *)dOut.p + c * total, total * 4,
+                                hipMemcpyDeviceToHost, ctx->stream)))
+            return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
+    if ((e = hipMemcpyAsync(h_reports, dRep.p, repBytes, hipMemcpyDeviceToHost, ctx->stream)) ||
+        (e = hipStreamSynchronize(ctx->stream)))
+        return fail(ctx, ALAC_HIP_ParamError, "D2H copy", e);
+    return ALAC_HIP_noErr;
+}
+
+}  // extern "C++"
+
+int32_t alac_hip_resample_int_host(alac_hip_ctx *ctx, const void *h_in, const alac_hip_int_source *src, uint32_t num_channels,
+                                   uint32_t in_rate, uint32_t out_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                                   uint32_t num_segments, float *h_out, uint64_t out_channel_stride, uint64_t out_frames,
+                                   alac_hip_resample_report *h_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = int_probe_refusal(ctx, h_in, src, num_channels, total_frames, h_seg_first_frame, num_segments, lo, hi))
+        return rc;
+    // the containers the call may read lie in [0, span) of h_in: up to the last frame of the last segment
+    const uint64_t span = hi > lo ? (num_channels - 1) * src->channel_stride + (hi - 1) * src->frame_stride + 1 : 0;
+    return resample_host(ctx, h_in, span * src->container_bytes, in_rate, out_rate, num_channels, total_frames,
+                         h_seg_first_frame, num_segments, h_out, out_channel_stride, out_frames, h_reports,
+                         [&](void *dIn, void *dWs, uint64_t wsBytes, float *dOut, uint64_t total, alac_hip_resample_report *dRep) {
+                             return alac_hip_resample_int(ctx, dIn, src, num_channels, in_rate, out_rate, total_frames,
+                                                          h_seg_first_frame, num_segments, dWs, wsBytes, dOut, total, total, dRep);
+                         });
+}
+
+int32_t alac_hip_resample_float_host(alac_hip_ctx *ctx, const float *h_in, uint32_t num_channels, uint64_t channel_stride,
+                                     uint64_t frame_stride, uint32_t in_rate, uint32_t out_rate, uint64_t total_frames,
+                                     const uint64_t *h_seg_first_frame, uint32_t num_segments, float *h_out,
+                                     uint64_t out_channel_stride, uint64_t out_frames, alac_hip_resample_report *h_reports)
+{
+    if (!ctx) return ALAC_HIP_ParamError;
+    uint64_t lo, hi;
+    if (int32_t rc = float_probe_refusal(ctx, h_in, num_channels, channel_stride, frame_stride, total_frames, h_seg_first_frame,
+                                         num_segments, lo, hi))
+        return rc;
+    const uint64_t span = hi > lo ? (num_channels - 1) * channel_stride + (hi - 1) * frame_stride + 1 : 0;
+    return resample_host(ctx, h_in, span * sizeof(float), in_rate, out_rate, num_channels, total_frames, h_seg_first_frame,
+                         num_segments, h_out, out_channel_stride, out_frames, h_reports,
+                         [&](void *dIn, void *dWs, uint64_t wsBytes, float *dOut, uint64_t total, alac_hip_resample_report *dRep) {
+                             return alac_hip_resample_float(ctx, (const float *)dIn, num_channels, channel_stride, frame_stride,
+                                                            in_rate, out_rate, total_frames, h_seg_first_frame, num_segments, dWs,
+                                                            wsBytes, dOut, total, total, dRep);
+                         });
 }
 
 int32_t alac_hip_pcm_crc32_host(alac_hip_ctx *ctx, const void *h_pcm, uint64_t total_bytes, const uint64_t *h_ranges,

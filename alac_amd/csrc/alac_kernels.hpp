@@ -498,6 +498,49 @@ void true_peak_coefs(uint32_t F, double (&coef)[kTruePeakMaxCoefs]);
 // zeroes the reports and the channel peaks, then the pass and the finish
 hipError_t launch_true_peak(const TruePeakArgs &a, hipStream_t st);
 
+// ---- sample-rate conversion (alac_resample.hip): alac_hip_resample_int / _float ----
+// The source as in LoudArgs.  Segment s = frames [segFirst[s], segFirst[s + 1]) gives the output frames [outFirst[s],
+// outFirst[s + 1]) of every channel's row, cut into tiles of `tile` output frames (the last one may be shorter), one block
+// each; tileBase[numSegments + 1]: the first tile of every segment among the call's tiles.
+struct ResampleArgs {
+    const void *in;
+    uint64_t channelStride, frameStride;
+    const uint64_t *segFirst, *outFirst, *tileBase;
+    uint32_t numSegments, channels;
+    uint32_t containerBytes, srcBits, leftJustified;
+    uint32_t L, M, K;     // the plan of the rate pair (ResamplePlan)
+    uint32_t tile, span;  // output frames of a tile; the input frames a tile needs at most (resample_span), what LDS holds
+    uint64_t totalTiles;
+    const double *coef;   // [K/2][L][2]: taps 2 kk and 2 kk + 1 of phase p at coef[(kk * L + p) * 2], 16-byte aligned
+    float *out;           // channel c's output frame j at out[c * outChannelStride + j]
+    uint64_t outChannelStride;
+    uint32_t *reports;    // 8 words per segment: alac_hip_resample_report
+};
+// the plan of a rate pair by the rule of include/alac_hip.h; ok: the pair is one the calls take
+struct ResamplePlan {
+    uint32_t L, M, K;
+    bool ok;
+};
+ResamplePlan resample_plan(uint32_t inRate, uint32_t outRate);
+// output frames of a segment of n frames: ceil(n L / M)
+inline uint64_t resample_out_frames(const ResamplePlan &p, uint64_t n) { return (n * p.L + p.M - 1) / p.M; }
+// the input frames a tile of t output frames needs at most: its outputs' first and last centre frames and K - 1 around them
+inline uint64_t resample_span(const ResamplePlan &p, uint64_t t) { return (t * p.M + p.L - 1) / p.L + p.K; }
+// the output frames of a tile: 512, or as many as keep the tile's input span, as doubles of two channels (the most a block
+// holds), inside kResampleLdsBytes of LDS (long filters: K grows with M / L, up to 3 840 at 48 : 1)
+constexpr uint32_t kResampleTile = 512, kResampleLdsBytes = 64000;
+inline uint32_t resample_tile(const ResamplePlan &p)
+{
+    uint32_t t = kResampleTile;
+    while (t > 1 && resample_span(p, t) * 16 > kResampleLdsBytes) t /= 2;
+    return t;
+}
+// host: the coefficients of a plan, computed once per pair and kept (the returned table lives as long as the process): [L][K],
+// and behind it the same L * K doubles in the kernels' arrangement (ResampleArgs::coef)
+const double *resample_coefs(const ResamplePlan &p);
+// zeroes the reports, then the pass and the finish
+hipError_t launch_resample(const ResampleArgs &a, hipStream_t st);
+
 // ---- the words of the PCM modes that have more than fit in DecodeArgs (PcmMode, alac_verify.hpp) ----
 // Sample i of channel c of packet p lives at index c * channelStride + (p * frameSize + i) * frameStride of DecodeArgs::pcmOut.
 //  kPcmVerifyFloat (alac_hip_verify_float): pcmOut is the float32 source, only read, and only at frames

@@ -98,6 +98,17 @@
  *                                             ALACDecoder::LoudnessTruePeakBatch (both measurements on the one decoded plane),
  *                                             PCM files through alac_hip_true_peak_int_host / _float_host as well.
  *                                             --true-peak without --loudness is refused with the usage text.
+ *   --rate R [--float-bits N] [--dither [--dither-seed S]] [--batch] [--devices N]
+ *                                             encode only: integer and 32-bit float PCM inputs are converted to R Hz on the GPU
+ *                                             (alac_hip_resample_int / _float, the windowed-sinc rule of include/alac_hip.h: each
+ *                                             file one segment, the files of one rate, channel count and source format in one
+ *                                             call), and the floats are quantized to N bits and encoded as --float-bits N
+ *                                             encodes float input; the output's header carries R.  N defaults to an integer
+ *                                             input's own depth; a float input needs --float-bits N.  A file already at R is
+ *                                             encoded as without --rate and named on stderr; an output peak above full scale is
+ *                                             a warning on stderr.  Refused with the usage text: --bits, --float-bits auto,
+ *                                             --verify, --verify-source, --compare, the modes that only print, ALAC inputs, and
+ *                                             a pair of rates the call does not take
  *   --crc-check <list>                        read lines of that format, compute every file's value again and print
  *                                             "<path>: OK", "<path>: FAILED" or "<path>: FAILED open"; exit 1 if any line
  *                                             failed (the flow of sha256sum -c).  With --devices N; no other option
@@ -138,6 +149,11 @@ struct Job {
     // --float-bits: info describes the integer file of the quantized samples; the floats are at floatPos in `file`
     bool floatIn = false, floatBigEndian = false;
     uint64_t floatPos = 0;
+    // --rate: the file is resampled from srcRate (0: not resampled); afterwards info describes the integer file of the
+    // quantized samples at the new rate, and the floats, interleaved, are in `resampled` instead of `file`
+    uint32_t srcRate = 0;
+    bool srcFloat = false;
+    std::vector<float> resampled;
     // --bits: info describes the integer file of the converted samples; the source's containers, srcBits deep, are at srcPos
     bool intConv = false, srcBigEndian = false;
     uint32_t srcBits = 0;
@@ -205,6 +221,10 @@ bool pcm_format_ok(const Job &J)
 void stage_floats(const Job &J, uint64_t frames, float *dst)
 {
     const uint64_t bytes = frames * J.info.channels * sizeof(float);
+    if (J.srcRate) {
+        memcpy(dst, J.resampled.data(), (size_t)bytes);
+        return;
+    }
     memcpy(dst, J.file.data() + J.floatPos, (size_t)bytes);
     if (J.floatBigEndian) alacfile::swap_samples_in_place((uint8_t *)dst, bytes, 32);
 }
@@ -402,6 +422,85 @@ bool probe_int_jobs(std::vector<Job> &jobs, int device)
             J.info.dataSize = J.srcFrames * frame_bytes(J.info);
         }
     }
+    return ok;
+}
+
+// --rate: the jobs that are to be resampled (srcRate != 0) become float jobs at o.rate: the files of one rate, channel count and
+// source format go through the GPU in one call, each one segment (alac_hip_resample_int_host / _float_host).  An integer job
+// holds its source as a --bits job does (srcBits, srcPos, srcFrames), a float job as a --float-bits job does.
+bool resample_jobs(std::vector<Job> &jobs, const Options &o, int device)
+{
+    std::map<std::string, std::vector<Job *> > groups;
+    for (size_t j = 0; j < jobs.size(); j++) {
+        Job &J = jobs[j];
+        if (!J.srcRate) continue;
+        char key[64];
+        snprintf(key, sizeof(key), "%u/%u/%u", J.srcRate, J.info.channels, J.srcFloat ? 0u : J.srcBits);
+        groups[key].push_back(&J);
+    }
+    if (groups.empty()) return true;
+    alac_hip_ctx *ctx = nullptr;
+    const char *dev = getenv("ALAC_HIP_DEVICE");
+    if (alac_hip_create(&ctx, device >= 0 ? device : (dev ? atoi(dev) : 0), nullptr) != ALAC_HIP_noErr) {
+        fprintf(stderr, " Cannot create a GPU context\n");
+        return false;
+    }
+    bool ok = true;
+    for (std::map<std::string, std::vector<Job *> >::iterator g = groups.begin(); g != groups.end() && ok; ++g) {
+        std::vector<Job *> &v = g->second;
+        const Job &F = *v[0];
+        const uint32_t ch = F.info.channels, sampleBytes = F.srcFloat ? 4u : bytes_per_sample(F.srcBits);
+        std::vector<uint64_t> first(1, 0);  // the files' frames back to back
+        for (size_t j = 0; j < v.size(); j++) first.push_back(first.back() + v[j]->srcFrames);
+        std::vector<uint64_t> outFirst(v.size() + 1, 0);
+        const uint64_t total = alac_hip_resample_frames(F.srcRate, o.rate, first.back(), first.data(), (uint32_t)v.size(), outFirst.data());
+        // interleaved: channel_stride 1, frame_stride ch (room for one frame where every file is empty)
+        Bytes in((size_t)(first.back() * ch * sampleBytes) + 4 * ch, 0);
+        for (size_t j = 0; j < v.size(); j++) {
+            uint8_t *dst = in.data() + (size_t)(first[j] * ch * sampleBytes);
+            if (F.srcFloat) {
+                const uint64_t bytes = v[j]->srcFrames * ch * 4;
+                memcpy(dst, v[j]->file.data() + v[j]->floatPos, (size_t)bytes);
+                if (v[j]->floatBigEndian) alacfile::swap_samples_in_place(dst, bytes, 32);
+            } else {
+                stage_source(*v[j], v[j]->srcFrames, dst);
+            }
+        }
+        std::vector<float> rows((size_t)(total * ch) + 1, 0.0f);
+        std::vector<alac_hip_resample_report> reports(v.size());
+        int32_t rc;
+        if (F.srcFloat) {
+            rc = alac_hip_resample_float_host(ctx, (const float *)in.data(), ch, 1, ch, F.srcRate, o.rate, first.back(), first.data(),
+                                              (uint32_t)v.size(), rows.data(), total, total, reports.data());
+        } else {
+            const alac_hip_int_source src = int_source_of(F);
+            rc = alac_hip_resample_int_host(ctx, in.data(), &src, ch, F.srcRate, o.rate, first.back(), first.data(),
+                                            (uint32_t)v.size(), rows.data(), total, total, reports.data());
+        }
+        if (rc != ALAC_HIP_noErr) {
+            fprintf(stderr, " Resampling to %u Hz failed (status %d: %s)\n", o.rate, rc, alac_hip_last_error(ctx));
+            ok = false;
+            break;
+        }
+        for (size_t j = 0; j < v.size(); j++) {
+            Job &J = *v[j];
+            const uint64_t n = reports[j].out_frames;
+            J.resampled.assign((size_t)(n * ch) + 1, 0.0f);
+            for (uint32_t c = 0; c < ch; c++) {
+                const float *row = rows.data() + (size_t)(c * total + reports[j].out_first);
+                for (uint64_t i = 0; i < n; i++) J.resampled[(size_t)(i * ch + c)] = row[i];
+            }
+            if (reports[j].nonfinite)
+                fprintf(stderr, " Warning: %llu non-finite samples read as 0: \"%s\"\n", (unsigned long long)reports[j].nonfinite,
+                        J.in.c_str());
+            if (reports[j].peak > 1.0)
+                fprintf(stderr, " Warning: the peak after resampling is %.2f dBFS, above full scale: \"%s\"\n",
+                        20.0 * log10(reports[j].peak), J.in.c_str());
+            J.info.sampleRate = o.rate;
+            J.info.dataSize = n * frame_bytes(J.info);
+        }
+    }
+    alac_hip_destroy(ctx);
     return ok;
 }
 
@@ -988,7 +1087,46 @@ int convert(const Options &o)
         if (!read_job(J)) return 1;
         printf("Input file: %s\n", J.in.c_str());
         printf("Output file: %s\n", J.out.c_str());
-        if (refused(alacfile::sniff_input(J.file, J.info, o.floatInput() || o.intConvert()), J)) return 1;
+        if (refused(alacfile::sniff_input(J.file, J.info, o.floatInput() || o.intConvert() || o.rate), J)) return 1;
+        if (o.rate && J.info.isAlac) {  // --rate is encode only
+            plan::usage();
+            return 1;
+        }
+        if (o.rate && J.info.sampleRate == (double)o.rate) {
+            fprintf(stderr, " Already at %u Hz, not resampled: \"%s\"\n", o.rate, J.in.c_str());
+        } else if (o.rate) {
+            uint32_t L = 0, M = 0, K = 0;
+            const uint32_t srcRate = (uint32_t)J.info.sampleRate;
+            if ((double)srcRate != J.info.sampleRate || alac_hip_resample_filter(srcRate, o.rate, &L, &M, &K, nullptr) != ALAC_HIP_noErr) {
+                plan::usage();
+                return 1;
+            }
+            if (J.info.isFloat && !o.floatBits) {
+                fprintf(stderr, " --rate with float PCM input needs --float-bits N: \"%s\"\n", J.in.c_str());
+                return 1;
+            }
+            if (J.info.isFloat ? J.info.bitsPerChannel != 32 : !plan::pcm_depth_ok(J.info.bitsPerChannel)) {
+                fprintf(stderr, " File \"%s\'s\" data format is of an unsupported type\n", J.in.c_str());
+                return 1;
+            }
+            if (J.info.channels < 1 || J.info.channels > 8) {
+                fprintf(stderr, " File \"%s\'s\" data format is of an unsupported type\n", J.in.c_str());
+                return 1;
+            }
+            // from here on the file is the integer file of its resampled, quantized samples (resample_jobs below fills in the
+            // frames); the source stays where it is
+            J.srcRate = srcRate;
+            J.srcFloat = J.info.isFloat;
+            J.srcBits = J.info.bitsPerChannel;
+            J.srcPos = J.floatPos = J.info.dataPos;
+            J.srcBigEndian = J.floatBigEndian = J.info.bigEndianPcm;
+            J.srcFrames = J.info.dataSize / ((uint64_t)J.info.channels * bytes_per_sample(J.info.bitsPerChannel));
+            J.floatIn = true;
+            J.info.isFloat = J.info.bigEndianPcm = false;
+            if (o.floatBits) J.info.bitsPerChannel = o.floatBits;
+            J.info.dataSize = 0;
+            continue;
+        }
         if (o.floatInput()) {
             if (!J.info.isFloat) {
                 fprintf(stderr, " --float-bits takes float PCM input, not integer PCM or ALAC: \"%s\"\n", J.in.c_str());
@@ -1034,6 +1172,7 @@ int convert(const Options &o)
     }
     if (o.floatAuto && !probe_float_jobs(jobs, o.devices ? 0 : -1)) return 1;
     if (o.intAuto && !probe_int_jobs(jobs, o.devices ? 0 : -1)) return 1;
+    if (o.rate && !resample_jobs(jobs, o, o.devices ? 0 : -1)) return 1;
 
     // group: encode jobs by (depth, channels); decode jobs by cookie
     Groups groups;
@@ -1041,7 +1180,8 @@ int convert(const Options &o)
         Job &J = jobs[j];
         if (J.info.isAlac && refused(parse_alac(J), J)) return 1;
         char key[64];
-        snprintf(key, sizeof(key), "E%u/%u", J.info.bitsPerChannel, J.info.channels);
+        // (with --rate a run can hold float jobs, the resampled files, next to integer ones, the files already at that rate)
+        snprintf(key, sizeof(key), "E%u/%u%s", J.info.bitsPerChannel, J.info.channels, J.floatIn ? "f" : "");
         groups[J.info.isAlac ? cookie_key(J) : std::string(key)].push_back(&J);
     }
     if (!devices_ok(o.devices)) return 1;

@@ -39,6 +39,8 @@ struct Options {
     uint32_t intBits = 0;
     bool intAuto = false, bitsNamed = false;
     bool intConvert() const { return intBits != 0 || intAuto; }
+    // --rate R: integer and float PCM inputs are resampled to R Hz on the GPU in front of the encode (0: not given)
+    uint32_t rate = 0;
 };
 
 inline void usage()
@@ -136,6 +138,9 @@ inline bool parse_args(int argc, char **argv, Options &o)
             char *end = nullptr;
             o.dither.seed = strtoull(argv[++i], &end, 0);  // decimal or 0x-hex
             malformed = end == argv[i] || *end;
+        } else if (a == "--rate" && more) {
+            o.rate = (uint32_t)strtoul(argv[++i], nullptr, 10);
+            malformed = o.rate == 0;
         } else if (a == "--devices" && more) {
             o.devices = (uint32_t)strtoul(argv[++i], nullptr, 10);
             malformed = o.devices == 0;
@@ -151,7 +156,7 @@ inline bool parse_args(int argc, char **argv, Options &o)
     if (o.loudness) {
         // --loudness stands alone (but --devices N and --true-peak): any number of inputs, no output files
         if (malformed || n == 0 || crcMode || o.compare || o.dither.on || o.dither.seed || o.bitsNamed || o.batch || o.lpc ||
-            o.verify || o.verifySource || o.segmentPackets || o.floatInput() || o.intConvert()) {
+            o.verify || o.verifySource || o.segmentPackets || o.floatInput() || o.intConvert() || o.rate) {
             usage();
             return false;
         }
@@ -161,13 +166,17 @@ inline bool parse_args(int argc, char **argv, Options &o)
         usage();
         return false;
     }
+    // --rate goes with an encode alone, at a depth the command line or the file fixes: not with --bits, --float-bits auto, a
+    // verification (the PCM or floats to compare with are those of the other rate) or a mode that only prints
+    if (o.rate && (o.bitsNamed || o.floatAuto || o.verify || o.verifySource || o.compare || crcMode)) malformed = true;
     if (!malformed && o.bitsNamed && (o.floatInput() || o.compare || crcMode)) {
         fprintf(stderr, " --bits converts integer PCM in front of an encode: not with %s\n",
                 o.floatInput() ? "--float-bits" : o.compare ? "--compare" : o.crc ? "--crc" : "--crc-check");
         return false;
     }
     // neither --crc / --crc-check nor --compare goes with one of these
-    const bool converting = o.batch || o.lpc || o.verify || o.verifySource || o.segmentPackets || o.floatInput() || o.intConvert();
+    const bool converting =
+        o.batch || o.lpc || o.verify || o.verifySource || o.segmentPackets || o.floatInput() || o.intConvert() || o.rate;
     if (crcMode) {
         // --crc and --crc-check stand alone (but --devices N): any number of inputs resp. one list, no output files
         malformed = malformed || converting || o.compare || o.dither.on || (o.crc && !o.crcList.empty()) || (o.crc ? n == 0 : n != 0);

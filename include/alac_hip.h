@@ -905,6 +905,78 @@ int32_t alac_hip_true_peak_float_host(alac_hip_ctx *ctx, const float *h_in, uint
  * here.  kALAC_ParamError for a bad fs or a null pointer. */
 int32_t alac_hip_true_peak_filter(uint32_t sample_rate, uint32_t *out_factor, uint32_t *out_taps, double *out_coefs);
 
+/* ---- sample-rate conversion of PCM, computed where the PCM lies ------------------------------------------------------------------
+ * A 96 kHz master becomes 48 or 44.1 kHz, 44.1 kHz material becomes 48 kHz: integer or float32 PCM in device memory in, planar
+ * float32 in device memory out, which is what alac_hip_encode_float takes, per segment of frames.  No reference counterpart.
+ * The rule.
+ *   Sample value.  Exactly that of the loudness and true-peak rules above: x = s * 2^-(S-1) in double for an integer source
+ *     described by alac_hip_int_source, x = (double)f for a float32 source; a non-finite float is read as 0.0 and counted.
+ *   Rates.  in_rate and out_rate are multiples of 10 in [8 000, 384 000] and are different.  With g = gcd(in_rate, out_rate),
+ *     L = out_rate / g and M = in_rate / g; both must be at most 640 (every pair out of 8, 16, 22.05, 32, 44.1, 48,
+ *     88.2, 96, 176.4 and 192 kHz whose ratio is at most 640/147 either way).  Anything else is kALAC_ParamError.
+ *   Filter.  One quality: Z = 40 and beta = 10, K = 2 * ceil(Z * max(L, M) / L) taps per phase (80 when the rate goes up, 176
+ *     for 96 -> 44.1 kHz, 350 for 192 -> 44.1 kHz).  With c = min(L, M) / M, for p in [0, L) and k in [0, K), and
+ *     t = p / L + k - K / 2:
+ *         h_p[k] = c * sinc(c t) * I0(beta * sqrt(max(0, 1 - (2 t / K)^2))) / I0(beta)
+ *     sinc(u) = sin(pi u) / (pi u), 1 at u = 0; I0 is the modified Bessel function of the first kind and order 0 (a Kaiser
+ *     window over [-K/2, K/2]).  The window is not zero at t = -K/2 (p = 0, k = 0): that tap is kept.
+ *   Output.  A segment of N frames gives ceil(N * L / M) frames; output 0 sits on input frame 0, so there is no delay, and both
+ *     ends are zero-extended.  For output m: n0 = (m * M) div L and p = (m * M) mod L, in 64-bit, and
+ *         y[m] = (float)( sum_{k = 0}^{K - 1} h_p[k] * x[n0 + K/2 - k] ),   x = 0 outside [0, N) of the segment
+ *     accumulated from 0 in double with k ascending, every step one fused multiply-add, and rounded once to float32.
+ *   A segment is converted from its own frames alone: nothing outside it is read.  Every output has one order of summation, so
+ *   a segment's output is the same bits whatever the grid, the other segments of the call and the segment's place in the buffer.
+ *   d_in, src / channel_stride, frame_stride, total_frames, h_seg_first_frame, num_segments
+ *                     as in alac_hip_loudness_int / alac_hip_loudness_float; empty segments are legal (0 frames, a zero report)
+ *   d_workspace       alac_hip_resample_workspace_bytes(in_rate, out_rate, num_channels, num_segments) bytes, 16-byte aligned:
+ *                     the coefficient table and the segment tables.  It does not grow with the frame count.
+ *   d_out             planar float32: channel c's output frame j at d_out[c * out_channel_stride + j], the segments back to
+ *                     back at the offsets alac_hip_resample_frames gives.  Floats of a row from that total on, and between the
+ *                     rows, are not written.
+ *   out_frames        the frames a row has room for: at least the total of alac_hip_resample_frames
+ *   out_channel_stride  floats from one row to the next, at least out_frames
+ *   d_reports         [num_segments] alac_hip_resample_report, 8-byte aligned; every word is written by every call
+ * Asynchronous on the context's stream.  kALAC_ParamError, with nothing enqueued and nothing written: everything the loudness
+ * call refuses in the source, num_channels and the table; a bad rate pair; a null or misaligned workspace, or one that is too
+ * small; a null or misaligned d_out or d_reports; out_frames below the total; out_channel_stride below out_frames.
+ */
+typedef struct alac_hip_resample_report { /* one per segment, 32 bytes */
+    uint64_t out_first;  /* the segment's first output frame in a row of d_out */
+    uint64_t out_frames; /* its output frames: ceil(N * L / M) */
+    double peak;         /* the largest |float32 written| of the segment, exact; above 1.0: alac_hip_encode_float will clip */
+    uint64_t nonfinite;  /* non-finite input samples of the segment, read as 0.0 */
+} alac_hip_resample_report;
+/* Host only, no context: L, M and K of a rate pair, and with out_coefs not null the coefficients h_p[k] in out_coefs [L * K],
+ * phase-major (out_coefs null: the sizes alone).  The kernels take their coefficients from here.  kALAC_ParamError for a bad
+ * pair or a null out_L, out_M or out_K. */
+int32_t alac_hip_resample_filter(uint32_t in_rate, uint32_t out_rate, uint32_t *out_L, uint32_t *out_M, uint32_t *out_K,
+                                 double *out_coefs);
+/* Host only, no context: the output frames of all segments back to back; h_out_first [num_segments + 1] (may be null) gets
+ * every segment's first output frame and the total.  h_seg_first_frame null: one segment of total_frames.  Returns 0 and
+ * writes nothing for a bad rate pair, num_segments 0 or a table the calls refuse. */
+uint64_t alac_hip_resample_frames(uint32_t in_rate, uint32_t out_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                                  uint32_t num_segments, uint64_t *h_out_first);
+uint64_t alac_hip_resample_workspace_bytes(uint32_t in_rate, uint32_t out_rate, uint32_t num_channels, uint32_t num_segments);
+int32_t alac_hip_resample_int(alac_hip_ctx *ctx, const void *d_in, const alac_hip_int_source *src, uint32_t num_channels,
+                              uint32_t in_rate, uint32_t out_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                              uint32_t num_segments, void *d_workspace, uint64_t workspace_bytes, float *d_out,
+                              uint64_t out_channel_stride, uint64_t out_frames, alac_hip_resample_report *d_reports);
+int32_t alac_hip_resample_float(alac_hip_ctx *ctx, const float *d_in, uint32_t num_channels, uint64_t channel_stride,
+                                uint64_t frame_stride, uint32_t in_rate, uint32_t out_rate, uint64_t total_frames,
+                                const uint64_t *h_seg_first_frame, uint32_t num_segments, void *d_workspace,
+                                uint64_t workspace_bytes, float *d_out, uint64_t out_channel_stride, uint64_t out_frames,
+                                alac_hip_resample_report *d_reports);
+/* Host-buffer forms (synchronous): h_in in the layout above, staged as the loudness host forms stage it; the rows come back in
+ * h_out (channel c's frame j at h_out[c * out_channel_stride + j]), the reports in h_reports [num_segments]. */
+int32_t alac_hip_resample_int_host(alac_hip_ctx *ctx, const void *h_in, const alac_hip_int_source *src, uint32_t num_channels,
+                                   uint32_t in_rate, uint32_t out_rate, uint64_t total_frames, const uint64_t *h_seg_first_frame,
+                                   uint32_t num_segments, float *h_out, uint64_t out_channel_stride, uint64_t out_frames,
+                                   alac_hip_resample_report *h_reports);
+int32_t alac_hip_resample_float_host(alac_hip_ctx *ctx, const float *h_in, uint32_t num_channels, uint64_t channel_stride,
+                                     uint64_t frame_stride, uint32_t in_rate, uint32_t out_rate, uint64_t total_frames,
+                                     const uint64_t *h_seg_first_frame, uint32_t num_segments, float *h_out,
+                                     uint64_t out_channel_stride, uint64_t out_frames, alac_hip_resample_report *h_reports);
+
 /* Parse a magic cookie into a format (host only). */
 int32_t alac_hip_format_from_cookie(const uint8_t *h_cookie, uint32_t cookie_size,
                                     alac_hip_format *out_fmt);
